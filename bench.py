@@ -15,6 +15,8 @@ features / references / random-init weights (no network), already resident in HB
 
     ... bench.py --gpus N --scaling strong     # global batch 64 split over the ranks (64 / N images per GPU) instead of 64 per GPU
 
+    ... bench.py --dump-outputs DIR            # also write the last timed step's loss and updated parameters as DIR/<name>.npy
+
 Rank 0 prints ONE JSON line (see the keys below).  `roofline` is measured live with HIP events around every launch of
 the dominant kernel (gemm_resident_x3_kernel<4,8,1,3,.,4>: 512-deep k ranges on one column tile since round 6; the LSTM-gate and vocabulary-projection GEMMs of every decoder step
 and, on transposed weights, the per-step dgrad GEMMs of BPTT) in an eager re-run of bench steps right after the timed region;
@@ -114,6 +116,26 @@ def end_bias(eng, batches, target_step=11.0):
         steps = steps_at(hi)
     torch.cuda.synchronize()
     return steps
+
+
+DUMP_SAMPLE = 1 << 20      # --dump-outputs: a tensor of more elements is written as a fixed sample of this many
+
+
+def last_step_outputs(eng, losses):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- that step's loss and the model's parameters
+    after its clamp + Adam update (state_dict keys), flattened, float32.  A parameter of more than DUMP_SAMPLE elements is
+    represented by DUMP_SAMPLE of them at sorted indices drawn from RandomState(0): the same indices in every run (~33 MB in all)."""
+    out = {"loss": losses[-1].detach().float().cpu().numpy()}
+    for name, v in eng.model.state_dict().items():
+        if not v.is_floating_point():
+            continue
+        flat = v.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.RandomState(0).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out[name] = flat.float().cpu().numpy()
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    return out
 
 
 def timed_ms(fn, reps=10, rounds=3, warm_ms=60.0):
@@ -651,6 +673,9 @@ def main():
                     help="N > 1: how the timed region exchanges gradients.  4 (default): the backward pass in four captured pieces, each gradient "
                          "group's all-reduce started from the library's callback beside the rest; 1: ONE captured backward and one all-reduce of "
                          "the flat buffer behind it.  Either way the line's `dp_overlap` carries both legs of the same invocation")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (the loss and the updated parameters, see "
+                         "last_step_outputs) as DIR/<name>.npy, on rank 0")
     args = ap.parse_args()
     if args.headline_only:
         args.no_cpu_baseline = args.no_h2d = True
@@ -702,7 +727,7 @@ def main():
     preload_s = time.perf_counter() - t0
 
     def run(loader):
-        eng.SCST_training_epoch(loader, opt, None, tqdm_visible=False)
+        return eng.SCST_training_epoch(loader, opt, None, tqdm_visible=False)
 
     eng.dp_overlap = args.dp_pieces == 4
     run([batches[i] for i in range(args.warmup)] + [batches[0]])      # graph capture, allocator warm-up
@@ -716,12 +741,12 @@ def main():
     torch.cuda.synchronize()
 
     def timed_epoch(loader):
-        """barrier + synchronize on both sides, max over ranks (the driver's contract) -> seconds"""
+        """barrier + synchronize on both sides, max over ranks (the driver's contract) -> (seconds, the losses the epoch returned)"""
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        run(loader)
+        losses = run(loader)
         torch.cuda.synchronize()
         if world > 1:
             torch.distributed.barrier()
@@ -731,8 +756,12 @@ def main():
             tt = torch.tensor([d], dtype=torch.float64, device=device)
             torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
             d = float(tt.item())
-        return d
-    dt = timed_epoch(batches[args.warmup:])
+        return d, losses
+    dt, timed_losses = timed_epoch(batches[args.warmup:])
+    if args.dump_outputs and rank == 0:       # before the passes below, which take further optimizer steps
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in last_step_outputs(eng, timed_losses).items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
     # ---- where a step's time goes, per phase (HIP events on the Engine's stream, max over ranks), in a SECOND pass over the same
     #      batches (the events are not in the timed region), and -- N > 1 -- the same pass with the gradient exchange NOT overlapped
     #      (one all-reduce of the flat buffer behind the backward pass): `dp_overlap` says what the overlap buys
@@ -740,7 +769,7 @@ def main():
     if world > 1 or not args.headline_only:
         def phase_pass():
             eng.phase_events = []
-            d = timed_epoch(batches[args.warmup:])
+            d, _ = timed_epoch(batches[args.warmup:])
             ph = eng.phase_times()
             eng.phase_events = None
             if world > 1:

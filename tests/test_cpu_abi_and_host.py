@@ -374,6 +374,34 @@ def test_bench_reads_its_committed_profiles_for_both_gemm_kernels():
     assert us and 10 < us < 30 and src.startswith("profiles/r0")
 
 
+def test_bench_dump_outputs_are_the_last_step_and_fixed():
+    """bench.py --dump-outputs: the last timed step's loss and every floating parameter after it, float32; a parameter of more than
+    DUMP_SAMPLE elements as the same sample of DUMP_SAMPLE of them in every call (two builds compare output for output)."""
+    import types
+    import bench
+    from simpleimagecaptionzoo_amd.synth import random_butd_params
+    p = {"decoder." + k: v for k, v in random_butd_params(36, 64, 32, 32, 32, 203, "cpu", seed=1).items()}
+    p["decoder.steps"] = torch.zeros(3, dtype=torch.int64)
+    eng = types.SimpleNamespace(model=types.SimpleNamespace(state_dict=lambda: p))
+    old = bench.DUMP_SAMPLE
+    bench.DUMP_SAMPLE = 1000
+    try:
+        a = bench.last_step_outputs(eng, [torch.tensor([9.0]), torch.tensor([1.5])])
+        b = bench.last_step_outputs(eng, [torch.tensor([9.0]), torch.tensor([1.5])])
+    finally:
+        bench.DUMP_SAMPLE = old
+    assert a["loss"].tolist() == [1.5] and "decoder.steps" not in a
+    assert set(a) == {"loss"} | {k for k in p if k != "decoder.steps"}
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.array_equal(v, b[k])
+        if k != "loss":
+            assert v.shape == (min(p[k].numel(), 1000),)
+            if p[k].numel() <= 1000:
+                assert np.array_equal(v, p[k].reshape(-1).numpy())
+            else:
+                assert np.isin(v, p[k].reshape(-1).numpy()).all()
+
+
 def test_routing_of_the_many_row_gemms_at_the_baseline_shapes():
     """gemm_big_cfg (host logic of csrc/gemm_big_x3.hip) at the shapes the BASELINE configs issue, as measured in EXPERIMENTS round 5
     section 6: the LSTM weight-gradient groups, predict's weight gradient, the XE vocabulary projection and the paired AoA Q/K/V
