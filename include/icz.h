@@ -381,6 +381,22 @@ int icz_ciderd_reward_indexed(icz_ciderd_t* h, const int64_t* gen, const int64_t
                               const int32_t* ref_len, float* reward_out, double* scores_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * BLEU and ROUGE-L of the evaluation report (COCO_Eval_Utils.py:15-35 -> coco_caption/pycocoevalcap/eval.py:24-69): the
+ * integer statistics on the device, the float64 scores on the host in the reference's order (coco_eval.py Bleu / Rouge).
+ * All arrays are int32 DEVICE arrays of corpus-local token ids >= 0 in CSR form: hypothesis i = hyp_tok[hyp_ptr[i] ..
+ * hyp_ptr[i+1]) with at most 60 tokens (the caller checks), reference r = ref_tok[ref_ptr[r] .. ref_ptr[r+1]) of any length,
+ * image i owns references img_ref_ptr[i] .. img_ref_ptr[i+1] (at least one).  stream: hipStream_t or NULL.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* Replaces precook / cook_refs / cook_test with option "closest" (bleu/bleu_scorer.py:26-86, :190-191):
+ * stats_out [n_img, 6] = testlen, closest reference length (ties: the shorter), correct[1..4] (clipped n-gram matches). */
+int icz_bleu_stats(const int32_t* hyp_tok, const int32_t* hyp_ptr, const int32_t* ref_tok, const int32_t* ref_ptr,
+                   const int32_t* img_ref_ptr, int32_t n_img, int32_t* stats_out, void* stream);
+/* Replaces my_lcs (rouge/rouge.py:15-36) as called by Rouge.calc_score (:38-71): lcs_out [n_ref] = length of the longest
+ * common subsequence of reference r and its image's hypothesis. */
+int icz_rouge_lcs(const int32_t* hyp_tok, const int32_t* hyp_ptr, const int32_t* ref_tok, const int32_t* ref_ptr,
+                  const int32_t* img_ref_ptr, int32_t n_img, int32_t* lcs_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Building blocks exported for tests and benchmarks
  * ---------------------------------------------------------------------------------------------------------- */
 /* C[M,N] = X[M,K] W[N,K]^T (+ bias[N]) on the fp32 MFMA; layout 0 = NT (y = x W^T), 1 = NN (C = X[M,K] W[K,N]),

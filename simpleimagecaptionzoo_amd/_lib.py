@@ -176,6 +176,8 @@ def lib():
         "icz_ciderd_vocab_oov_id": (C.c_int, [vp, C.c_char_p, i32, C.POINTER(i32)]),
         "icz_ciderd_cook_text": (C.c_int, [vp, vp, vp, i64, C.c_double, C.c_char_p, i64, i32, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]),
         "icz_ciderd_reward_indexed": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_bleu_stats": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp]),
+        "icz_rouge_lcs": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp]),
         "icz_prof_begin": (C.c_int, []),
         "icz_prof_select": (C.c_int, [i32]),
         "icz_prof_pair_overhead": (C.c_int, [vp, i32, C.POINTER(C.c_double)]),
