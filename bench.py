@@ -17,7 +17,14 @@ features / references / random-init weights (no network), already resident in HB
 
     ... bench.py --dump-outputs DIR            # also write the last timed step's loss and updated parameters as DIR/<name>.npy
 
-Rank 0 prints ONE JSON line (see the keys below).  `roofline` is measured live with HIP events around every launch of
+    ... bench.py --full                        # also everything else the line can carry (below); --no-cpu-baseline, --no-h2d and
+                                               # --headline-only leave parts of it out
+
+Rank 0 prints ONE JSON line (see the keys below).  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints
+the headline keys: nothing else runs.  With --full the line also carries the per-phase times of a second pass over the same batches,
+at N > 1 the gradient exchange without overlap (`dp_overlap`), the bare all-reduce and RCCL's choices, the live roofline, and at
+N = 1 the extra legs (cold first epoch, PCIe-inclusive, fp32-MFMA GEMMs, decode, XE, AoA, small batches) and the CPU baseline.  `roofline`
+is measured live with HIP events around every launch of
 the dominant kernel (gemm_resident_x3_kernel<4,8,1,3,.,4>: 512-deep k ranges on one column tile since round 6; the LSTM-gate and vocabulary-projection GEMMs of every decoder step
 and, on transposed weights, the per-step dgrad GEMMs of BPTT) in an eager re-run of bench steps right after the timed region;
 `cpu_baseline` times the CPU oracle (our port of the reference path, oracle/) on a bounded sample on rank 0.
@@ -585,8 +592,8 @@ def fp32_gemm_child(steps, warmup, batch):
     import subprocess
     env = dict(os.environ, ICZ_GEMM_TN_X3="0", ICZ_GEMM_NN_X3="0", ICZ_GEMM_NT_X3BIG="0", ICZ_GEMM_RESIDENT_X3="0")
     try:
-        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--batch", str(batch),
-                              "--headline-only"], env=env, capture_output=True, text=True, timeout=600)
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--batch", str(batch)],
+                             env=env, capture_output=True, text=True, timeout=600)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
         j = json.loads(line)
         return {"value": j["value"], "ms_per_step": j["ms_per_step"], "note": "ICZ_GEMM_TN_X3=0 ICZ_GEMM_NN_X3=0 ICZ_GEMM_NT_X3BIG=0 "
@@ -665,9 +672,12 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="images per step: per GPU (weak scaling, BASELINE config: 64) or in all (strong)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --batch images per GPU (per-GPU work fixed); strong: --batch images split over the ranks (total work fixed)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the PCIe-inclusive / cold-cache / secondary measurements")
-    ap.add_argument("--headline-only", action="store_true", help="timed region + JSON line, nothing else (used by the fp32-GEMM child run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and report everything besides the headline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-h2d", action="store_true", help="with --full: skip the PCIe-inclusive / cold-cache / secondary measurements")
+    ap.add_argument("--headline-only", action="store_true",
+                    help="with --full: no roofline, extra legs or CPU baseline, only the N > 1 phase and exchange fields; alone: a plain run")
     ap.add_argument("--cpu-rows", type=int, default=64)
     ap.add_argument("--dp-pieces", type=int, choices=(1, 4), default=4,
                     help="N > 1: how the timed region exchanges gradients.  4 (default): the backward pass in four captured pieces, each gradient "
@@ -677,8 +687,11 @@ def main():
                     help="after the timed steps, write what the last of them computed (the loss and the updated parameters, see "
                          "last_step_outputs) as DIR/<name>.npy, on rank 0")
     args = ap.parse_args()
-    if args.headline_only:
+    if (args.no_cpu_baseline or args.no_h2d) and not args.full:
+        ap.error("--no-cpu-baseline and --no-h2d leave parts of a --full run out: a plain run has neither")
+    if args.headline_only or not args.full:
         args.no_cpu_baseline = args.no_h2d = True
+    live_roofline = args.full and not args.headline_only
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))      # this process stays off the GPU: the ranks are its children
 
@@ -691,7 +704,7 @@ def main():
     rehearse = os.environ.get("ICZ_REHEARSE_ONE_GPU") == "1"
     # N > 1 over RCCL: have rank 0's RCCL say what it chose (rings / trees, protocol, channels) into a file the line quotes
     nccl_log = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("ICZ_BENCH_NCCL_INFO") == "1") and not rehearse \
+    if args.full and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("ICZ_BENCH_NCCL_INFO") == "1") and not rehearse \
             and os.environ.get("ICZ_BENCH_NCCL_INFO") != "0":
         import tempfile
         nccl_log = os.path.join(tempfile.gettempdir(), "icz_bench_rccl_rank%s_%d.log" % (os.environ.get("RANK", "0"), os.getpid()))
@@ -766,7 +779,7 @@ def main():
     #      batches (the events are not in the timed region), and -- N > 1 -- the same pass with the gradient exchange NOT overlapped
     #      (one all-reduce of the flat buffer behind the backward pass): `dp_overlap` says what the overlap buys
     phases, dp_overlap = None, None
-    if world > 1 or not args.headline_only:
+    if args.full and (world > 1 or not args.headline_only):
         def phase_pass():
             eng.phase_events = []
             d, _ = timed_epoch(batches[args.warmup:])
@@ -798,7 +811,7 @@ def main():
     # data-parallel exchange cost on its own: the all-reduce of the flat gradient buffer (246 MB), as the step issues it when
     # nothing overlaps it -- an upper bound of what the overlapped slices cost a step
     allreduce_ms = None
-    if world > 1:
+    if args.full and world > 1:
         flat = eng._flat
         for _ in range(2):
             torch.distributed.all_reduce(flat)
@@ -815,7 +828,7 @@ def main():
     # also how rocprofv3 sees it (it serialises concurrent branches).
     avg_us, bpl, fpl, nl = C.c_double(), C.c_double(), C.c_double(), C.c_longlong()
     pair_us = C.c_double()
-    if not args.headline_only:
+    if live_roofline:
         # every rank runs the same extra steps (they contain the gradient all-reduce); only rank 0 records events
         eng.use_graphs = False
         eng._hot_handle().set_concurrent(False)
@@ -858,7 +871,7 @@ def main():
         "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
         "vs_baseline": None,
         "vs_baseline_note": "BASELINE.md holds no published number for this metric (the reference publishes no throughput at all): null.  "
-                            "`vs_cpu_baseline_same_run` = value / cpu_baseline.value (the CPU port on this box's host cores, this run; "
+                            "`vs_cpu_baseline_same_run` (--full) = value / cpu_baseline.value (the CPU port on this box's host cores, this run; "
                             "north_star target >= 50x); `vs_reference_in_container` = value / 6.4 captions/s, the reference Engine itself "
                             "on the 8 cores of the survey container (BASELINE.md section 2: another machine)",
         "vs_reference_in_container": value / REFERENCE_IN_CONTAINER["captions_per_s"],
@@ -890,7 +903,7 @@ def main():
     if dp_overlap is not None:
         out["dp_overlap"] = dp_overlap
     roofline_failure = None
-    if not args.headline_only:
+    if live_roofline:
         roof = out["roofline"] = roofline_entry(avg_us.value, pair_us.value, bpl.value, fpl.value, nl.value)
         if world == 1 and not args.no_h2d:
             roof["level"] = weight_stream_level(device)

@@ -360,6 +360,19 @@ def test_bench_launcher_reports_dead_ranks_instead_of_hanging():
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_refuses_to_trim_a_run_that_is_not_full():
+    """--no-cpu-baseline and --no-h2d leave parts of a --full run out; on a plain run (which has neither) they are an error, so that a
+    command written for the old default does not quietly measure less than it asks for."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for flag in ("--no-cpu-baseline", "--no-h2d"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", flag],
+                           capture_output=True, text=True, timeout=300, cwd=root)
+        assert r.returncode == 2 and "a plain run has neither" in r.stderr, r.stderr[-2000:]
+        assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
 def test_bench_reads_its_committed_profiles_for_both_gemm_kernels():
     """bench.py's secondary roofline entries come from the committed rocprofv3 summaries under profiles/: since round 5 the many-row NT
     products sit on two kernels (the 128 x 128 two-barrier one and gemm_big_x3_kernel) -- the entries must find both and stay finite."""

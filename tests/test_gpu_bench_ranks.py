@@ -25,7 +25,7 @@ def test_bench_two_rank_rehearsal_prints_the_contract_line(scaling):
     env = dict(os.environ, ICZ_REHEARSE_ONE_GPU="1", MASTER_ADDR="127.0.0.1")
     port = 29500 + (os.getpid() % 400) + (0 if scaling == "weak" else 1)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--headline-only",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--headline-only",
            "--scaling", scaling] + (["--dp-pieces", "1"] if scaling == "strong" else [])      # round 6: the timed region with ONE all-reduce behind the backward pass
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -48,7 +48,7 @@ def test_bench_starts_its_own_ranks(n, extra):
     decoder path, four gradient slices reduced from the library's callback under graph replay at ranks >= 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["ICZ_REHEARSE_ONE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--headline-only"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--full", "--headline-only"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -82,3 +82,20 @@ def test_bench_refuses_a_rank_count_that_is_not_the_one_asked_for():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--headline-only"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode != 0 and "--gpus 2 but WORLD_SIZE = 1" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+@pytest.mark.gpu_slow
+def test_bench_plain_run_prints_the_headline_and_nothing_else():
+    """A plain `bench.py --gpus 1` sets up, warms up, times its steps and prints the headline: the phase pass, the live roofline, the
+    extra legs and the CPU baseline run only under --full."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"],
+                       env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(line) == 1, r.stdout[-2000:]
+    j = json.loads(line[0])
+    assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["unit"] == "captions/s" and j["dtype"] == "f32"
+    assert j["value"] > 0 and j["higher_is_better"] is True and abs(j["value"] * j["ms_per_step"] * 1e-3 - 64) < 1e-6 * 64
+    assert not set(j) & {"phases_ms", "roofline", "roofline_small_kernels", "cpu_baseline", "secondary", "cold_first_epoch",
+                         "pcie_inclusive", "fp32_mfma_gemms", "grad_allreduce_ms", "rccl"}

@@ -27,8 +27,8 @@ def main():
         write = (w[k][1] / w[k][0] * 1024.0) if k in w and w[k][0] else 0.0
         out[k] = {"launches": n, "fetch_bytes_per_launch": fetch, "write_bytes_per_launch": write,
                   "hbm_bytes_per_launch": fetch + write}
-    json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --steps 3 --warmup 1 "
-                         "--no-cpu-baseline; FETCH_SIZE x2 (gfx950), KiB -> bytes", "kernels": out}, open(sys.argv[3], "w"), indent=1)
+    json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 3 "
+                         "--warmup 1 --no-cpu-baseline; FETCH_SIZE x2 (gfx950), KiB -> bytes", "kernels": out}, open(sys.argv[3], "w"), indent=1)
 
 
 main()
