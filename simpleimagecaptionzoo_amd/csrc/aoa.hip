@@ -65,10 +65,8 @@ int Aoa::init(const icz_aoa_dims& d) {
     ICZ_TRY(alloc((void**)&it, sizeof(int64_t) * rows));
     ICZ_TRY(alloc((void**)&amax_val, sizeof(float) * rows * ARGMAX_PARTS));
     ICZ_TRY(alloc((void**)&amax_idx, sizeof(int) * rows * ARGMAX_PARTS));
-    ICZ_TRY(alloc((void**)&d_seed, 16));
-    ICZ_TRY(alloc((void**)&d_msum, 16));
-    ICZ_CHECK_HIP(hipDeviceSynchronize());      // alloc() zero-fills on the NULL stream; callers use non-blocking streams (see ensure_train)
-    return ICZ_OK;
+    ICZ_TRY(alloc_scalars(mem));
+    return mem.synced();
 }
 
 __global__ __launch_bounds__(256) void aoa_pack_rec_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh, float* __restrict__ w_rec,
@@ -147,7 +145,7 @@ int Aoa::refine(const float* feats, int n_img, bool train, hipStream_t st, const
         if (!bank[0].featp)
         {
             for (int b = 0; b < 2; ++b) ICZ_TRY(alloc((void**)&bank[b].featp, sizeof(float) * (size_t)dims.max_rows * dims.R * dims.D));
-            ICZ_CHECK_HIP(hipDeviceSynchronize());      // alloc() zero-fills on the NULL stream (see ensure_train)
+            ICZ_TRY(mem.synced());
         }
         float* featp = bank[cur_bank].featp;
         hipLaunchKernelGGL(aoa_offsets_kernel, dim3(1), dim3(256), 0, st, lens, n_img, R, off, rowmap);
@@ -355,64 +353,24 @@ int Aoa::greedy(const float* feats, int B, int T, int64_t* ids_out, hipStream_t 
 // AoA_Decoder.beam_search_sample (AoA_Model.py:403-502), batched over images; state (h, m, ctx) re-gathered by source beam
 int Aoa::beam_search(const float* feats, int n_img, int kb, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st) {
     ICZ_REQUIRE(feats && seqs_out && lens_out, "aoa beam: null argument");
-    ICZ_REQUIRE(kb >= 1 && kb <= BEAM_MAX_K, "aoa beam: beam size %d out of range 1..%d", kb, BEAM_MAX_K);
-    ICZ_REQUIRE(n_img > 0 && (long)n_img * kb <= dims.max_rows, "aoa beam: %d images x %d beams exceed row capacity %d", n_img, kb, dims.max_rows);
-    ICZ_REQUIRE(max_steps >= 1 && max_steps <= 256, "aoa beam: max_steps out of range");
+    ICZ_TRY(BeamBuf::check("aoa", n_img, kb, max_steps, dims.max_rows));
     ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
     const int rows = n_img * kb, L = max_steps + 1, Hd = dims.Hd;
-    if (bm.cap_rows < rows || bm.cap_L < L) {
-        const size_t R_ = dims.max_rows, L_ = L > 51 ? L : 51;
-        ICZ_TRY(alloc((void**)&bm.n_act, sizeof(int) * R_));
-        ICZ_TRY(alloc((void**)&bm.run, sizeof(float) * R_));
-        ICZ_TRY(alloc((void**)&bm.seqs[0], sizeof(int32_t) * R_ * L_));
-        ICZ_TRY(alloc((void**)&bm.seqs[1], sizeof(int32_t) * R_ * L_));
-        ICZ_TRY(alloc((void**)&bm.src_row, sizeof(int32_t) * R_));
-        ICZ_TRY(alloc((void**)&bm.img_of_row, sizeof(int32_t) * R_));
-        ICZ_TRY(alloc((void**)&bm.best_score, sizeof(float) * R_));
-        ICZ_TRY(alloc((void**)&bm.best_len, sizeof(int) * R_));
-        ICZ_TRY(alloc((void**)&bm.has_complete, sizeof(int) * R_));
-        ICZ_TRY(alloc((void**)&bm.best_seq, sizeof(int32_t) * R_ * L_));
-        ICZ_TRY(alloc((void**)&bm.n_live, sizeof(int) * 260));
-        ICZ_TRY(alloc((void**)&bm.cand_val, sizeof(float) * R_ * BEAM_MAX_K));
-        ICZ_TRY(alloc((void**)&bm.cand_idx, sizeof(int) * R_ * BEAM_MAX_K));
-        ICZ_CHECK_HIP(hipHostMalloc((void**)&bm.n_live_host, sizeof(int) * 4, 0));
-        ICZ_CHECK_HIP(hipDeviceSynchronize());      // alloc() zero-fills on the NULL stream (see ensure_train)
-        bm.cap_rows = (int)R_;
-        bm.cap_L = (int)L_;
-    }
+    ICZ_TRY(bm.ensure(mem, dims.max_rows, L));
     use_bank(0);
     ICZ_TRY(refine(feats, n_img, false, st));
-    ICZ_CHECK_HIP(hipMemsetAsync(bm.n_live, 0, sizeof(int) * 260, st));
-    ICZ_CHECK_HIP(hipMemsetAsync(bm.run, 0, sizeof(float) * rows, st));
-    hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, n_img, kb, L, bm.n_act, bm.seqs[0], bm.img_of_row, it,
-                       bm.has_complete, bm.best_score);
+    ICZ_TRY(bm.begin(n_img, kb, L, it, st));
     ICZ_TRY(zero_state(*this, rows, st));
-    int sb = 0, steps_done = 0;
-    for (int stp = 1; stp <= max_steps; ++stp) {
-        // step 1: the kb rows of an image are identical and only row 0 is scored -> one decoder row per image (butd_beam.hip)
-        const bool compact = stp == 1 && kb > 1;
+    auto step = [&](int, bool compact) {        // compact: one decoder row per image (butd_beam.hip)
         AoaStepIO s = compact ? scratch_io(*this, n_img, nullptr, 0) : scratch_io(*this, rows, bm.img_of_row, 0);
         s.emb_ready = false;
-        ICZ_TRY(step(s, st));
-        BeamArgs a = {logits, dims.V, Vp, kb, stp, L, bm.n_act, bm.run, bm.seqs[sb], bm.seqs[sb ^ 1], bm.src_row, it,
-                      bm.best_score, bm.best_len, bm.best_seq, bm.has_complete, bm.n_live + stp};
-        launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)bm.n_act, (const float*)bm.run, bm.cand_val, bm.cand_idx,
-                            compact ? 1 : 0);
-        hipLaunchKernelGGL(beam_merge_kernel, dim3(n_img), dim3(64), 0, st, a, (const float*)bm.cand_val, (const int*)bm.cand_idx);
+        return this->step(s, st);
+    };
+    auto gather = [&](bool compact) {
         hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(Hd, 1024), rows), dim3(256), 0, st, bm.src_row, Hd, h[1], m[1], ctx[1], h[1],
                            h[0], m[0], ctx[0], u, compact ? kb : 1);
-        sb ^= 1;
-        steps_done = stp;
-        if (stp >= 6 && (stp % 3) == 0 && stp < max_steps) {
-            ICZ_CHECK_HIP(hipMemcpyAsync(bm.n_live_host, bm.n_live + stp, sizeof(int), hipMemcpyDeviceToHost, st));
-            ICZ_CHECK_HIP(hipStreamSynchronize(st));
-            if (bm.n_live_host[0] == 0) break;
-        }
-    }
-    hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_img), dim3(64), 0, st, kb, L, steps_done, bm.n_act, bm.run, bm.seqs[sb], bm.has_complete,
-                       bm.best_len, bm.best_seq, seqs_out, lens_out);
-    ICZ_CHECK_HIP(hipGetLastError());
-    return ICZ_OK;
+    };
+    return bm.search(n_img, kb, max_steps, true, logits, dims.V, Vp, it, seqs_out, lens_out, st, step, gather);
 }
 
 }  // namespace icz
@@ -421,22 +379,11 @@ int Aoa::beam_search(const float* feats, int n_img, int kb, int max_steps, float
 using namespace icz;
 extern "C" {
 
-int icz_aoa_create(const icz_aoa_dims* dims, icz_aoa_t** out) {
-    ICZ_REQUIRE(dims && out, "icz_aoa_create: null argument");
-    Aoa* n = new Aoa();
-    int s = n->init(*dims);
-    if (s != ICZ_OK) { delete n; return s; }
-    *out = reinterpret_cast<icz_aoa_t*>(n);
-    return ICZ_OK;
-}
+int icz_aoa_create(const icz_aoa_dims* dims, icz_aoa_t** out) { return abi_create<Aoa>("icz_aoa_create", dims, out); }
 int icz_aoa_destroy(icz_aoa_t* h) { delete reinterpret_cast<Aoa*>(h); return ICZ_OK; }
 int icz_aoa_bind_params(icz_aoa_t* h, const icz_aoa_params* p) {
     ICZ_REQUIRE(h && p, "icz_aoa_bind_params: null argument");
-    const float* const* q = reinterpret_cast<const float* const*>(p);
-    for (size_t i = 0; i < sizeof(icz_aoa_params) / sizeof(float*); ++i) {
-        ICZ_REQUIRE(q[i] != nullptr, "icz_aoa_bind_params: parameter pointer %zu is null", i);
-        ICZ_REQUIRE(((uintptr_t)q[i] & 15) == 0, "icz_aoa_bind_params: parameter %zu not 16-byte aligned", i);
-    }
+    ICZ_TRY(check_param_table("icz_aoa_bind_params", p, sizeof(*p)));
     Aoa* n = reinterpret_cast<Aoa*>(h);
     if (n->bound && memcmp(&n->P, p, sizeof(*p)) != 0) {      // captured graphs carry the old parameter addresses
         ICZ_CHECK_HIP(hipDeviceSynchronize());

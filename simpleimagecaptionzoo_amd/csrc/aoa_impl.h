@@ -9,7 +9,6 @@
 #include <vector>
 
 #include "aoa_kernels.h"
-#include "beam_kernels.h"
 #include "butd_impl.h"
 
 namespace icz {
@@ -37,12 +36,12 @@ struct AoaStepIO {
                                      // entry (step_dead, icz_common.h: the reference's break, AoA_Model.py:400)
 };
 
-struct Aoa {
+struct Aoa : CaptionHead {
     static constexpr int STEP_WGS = 256, TARGET_WGS = 512, ARGMAX_PARTS = 8, NL = 6;
     icz_aoa_dims dims;
     icz_aoa_params P;
     bool bound = false, fresh = false;
-    std::vector<void*> allocs;
+    DeviceBuffers mem;
     int Vp = 0;
     float *w_pred = nullptr, *n_pred = nullptr, *zeros = nullptr;
     float* w_qkv[NL] = {}; float* b_qkv[NL] = {};       // per refiner layer [3Hd, Hd] / [3Hd]: linear_Q | linear_K | linear_V (refresh)
@@ -76,15 +75,13 @@ struct Aoa {
     }
     // hipGraph replay of the SCST rollout pair and of the REINFORCE backward pass (option "graphs"; fixed region counts and Philox
     // randomness only: an 'adaptive' batch changes its grid sizes, explicit mask arrays their addresses)
-    GraphCache gc;
+    GraphCache gc{16};
     bool use_graphs = false;
     float* proj_shared = nullptr;        // rollouts: img_feats_porjection(feats) before ReLU / dropout, computed ONCE for the evaluation-
                                          // mode pass of the greedy baseline and the training-mode pass of the sampled rollout
-    hipStream_t side_st = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipStream_t low_st = nullptr;                         // backward: the predict layer's weight gradient beside the reverse-time loop (plain priority)
-    hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;
-    hipEvent_t ev_fork3 = nullptr, ev_join3 = nullptr;      // (round 6) the attention block's small products beside the weight-gradient GEMMs of bptt's tail
+    SideStream side;                     // the greedy chain of the SCST rollout pair
+    SideStream low;                      // backward: the predict layer's weight gradient beside the reverse-time loop (plain priority); its second
+                                         // event pair: (round 6) the attention block's small products beside the weight-gradient GEMMs of bptt's tail
     float *xa = nullptr, *xb = nullptr, *ln = nullptr, *qkv = nullptr, *o = nullptr, *od = nullptr, *nd = nullptr,
           *z = nullptr, *refined = nullptr, *meanf = nullptr, *Kd = nullptr, *Vd = nullptr;
     // decoder state + scratch
@@ -93,25 +90,18 @@ struct Aoa {
     size_t ws_floats = 0;
     int64_t* it = nullptr;
     float* amax_val = nullptr; int* amax_idx = nullptr;
-    uint64_t* d_seed = nullptr; float* d_msum = nullptr;
     icz_grad_ready_cb grad_cb = nullptr; void* grad_cb_user = nullptr;      // DP overlap hook (icz_aoa_set_grad_callback)
-    float ss_prob = 0.f; const float* ss_gate = nullptr; const float* ss_draw = nullptr;      // scheduled sampling in xe_forward
     BeamBuf bm;
     // training buffers (aoa_train.hip), slot stride = max_rows: th/tm/tctx slot 0 = zeros, slot t+1 = after step t
     int tcap_B = 0, tcap_T = 0;          // capacity of the training buffers (grown on demand by ensure_train)
-    std::vector<void*> tallocs; bool alloc_train = false;
     int64_t* tok = nullptr;
     float *th = nullptr, *tm = nullptr, *tctx = nullptr, *temb = nullptr, *tu = nullptr, *tg = nullptr, *tstats = nullptr, *tqn = nullptr,
           *tQp = nullptr, *tP = nullptr, *tPd = nullptr, *tdS = nullptr, *tdX = nullptr, *txatt = nullptr, *tz = nullptr, *tcd = nullptr, *tlogit = nullptr;
     float *dCd = nullptr, *dZ = nullptr, *dQp = nullptr, *dQn = nullptr, *dHln = nullptr, *dG = nullptr, *dEmb = nullptr, *dKd = nullptr,
           *dVd = nullptr, *dcb[2] = {nullptr, nullptr}, *X = nullptr, *X2 = nullptr, *dWp = nullptr, *prod = nullptr;
-    float *coef = nullptr, *lse = nullptr, *loss_rows = nullptr;
-    int32_t* draw = nullptr; uint8_t* unf = nullptr; int* nunf = nullptr; int* pack_idx = nullptr;
-    uint8_t* gunf = nullptr; int* gnunf = nullptr; int* live_rows = nullptr;      // SCST baseline's counters; (steps the sampled rollout ran) x B
     bool early_out = true, bptt_early_out = false;
     size_t xfloats = 0;
     icz_aoa_rng rng = {};
-    int mode = 0, cur_B = 0, cur_T = 0, cur_L = 0, n_tokens = 0;
     // regions per image of the current batch: row stride cur_R <= dims.R and, for the 'adaptive' bottom-up features
     // (10..100 boxes, AoA_Engine.py:37-44), the valid count per image (device, caller-owned; null = all cur_R)
     int cur_R = 0, lens_n = 0, cur_total = 0;      // cur_total = sum of the counts = rows of the packed refiner tensors
@@ -130,30 +120,8 @@ struct Aoa {
         while (qc >= 4 && self_lds(R, qc) > LDS_BUDGET) qc -= 4;
         return qc >= 4 ? qc : 0;
     }
-    bool cur_train = false;
-    const int64_t* cur_seq = nullptr; const float* cur_logp = nullptr;
-    const int64_t* cur_captions = nullptr;
-    std::vector<int> rows_t;
 
-    ~Aoa() {
-        if (side_st) (void)hipStreamDestroy(side_st);
-        if (low_st) (void)hipStreamDestroy(low_st);
-        if (ev_fork2) (void)hipEventDestroy(ev_fork2);
-        if (ev_join2) (void)hipEventDestroy(ev_join2);
-        if (ev_fork3) (void)hipEventDestroy(ev_fork3);
-        if (ev_join3) (void)hipEventDestroy(ev_join3);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-        if (bm.n_live_host) (void)hipHostFree(bm.n_live_host);
-        for (void* p : tallocs) (void)hipFree(p);
-        for (void* p : allocs) (void)hipFree(p);
-    }
-    int alloc(void** p, size_t bytes) {
-        ICZ_CHECK_HIP(hipMalloc(p, bytes ? bytes : 16));
-        ICZ_CHECK_HIP(hipMemset(*p, 0, bytes ? bytes : 16));
-        (alloc_train ? tallocs : allocs).push_back(*p);
-        return ICZ_OK;
-    }
+    int alloc(void** p, size_t bytes) { return mem.alloc(p, bytes); }
     int init(const icz_aoa_dims& d);
     int refresh(hipStream_t st);
     // out[M,N] = A[M,K] W[N,K]^T + bias  (split-K through `ws` when the launch would be too small)

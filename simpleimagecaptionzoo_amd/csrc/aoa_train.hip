@@ -199,19 +199,6 @@ __global__ __launch_bounds__(256) void aoa_ln_prod_kernel(const float* __restric
     prod[i] = dq[i] * (x[i] - stats[2 * row]) * stats[2 * row + 1];
 }
 
-__global__ void aoa_captions_to_tok_kernel(const int64_t* __restrict__ cap, int B, int L, int T, int64_t* __restrict__ tok) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= T * B) return;
-    tok[i] = cap[(size_t)(i % B) * L + i / B];
-}
-__global__ void aoa_gather_packed_kernel(const float* __restrict__ logit, int V, int ldl, int B, const int* __restrict__ row_off,
-                                         const int* __restrict__ rows_t, float* __restrict__ out) {
-    const int tb_ = blockIdx.y, t = tb_ / B, b = tb_ % B;
-    if (b >= rows_t[t]) return;
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v < V) out[(size_t)(row_off[t] + b) * V + v] = logit[(size_t)tb_ * ldl + v];
-}
-
 }  // namespace
 
 // Training buffers sized by what the batches ask for (the reference never truncates captions, Datasets.py:47-51: the step
@@ -223,14 +210,12 @@ int Aoa::ensure_train(int Bq, int Tq) {
     if (tcap_B > Bq) Bq = tcap_B;
     if (tcap_T > Tq) Tq = tcap_T;
     if (dims.max_len > Tq) Tq = dims.max_len;
-    if (!tallocs.empty()) {
-        ICZ_CHECK_HIP(hipDeviceSynchronize());
-        for (void* p : tallocs) (void)hipFree(p);
-        tallocs.clear();
-        tcap_B = tcap_T = 0; mode = 0;
-        gc.clear();     // the captured rollout / backward graphs carry the freed addresses in their kernel arguments
+    if (!mem.training.empty()) {
+        ICZ_TRY(mem.release_training(&gc));
+        tcap_B = tcap_T = 0;
+        drop_loss_buffers();
     }
-    struct Scope { bool& f; Scope(bool& x) : f(x) { f = true; } ~Scope() { f = false; } } scope(alloc_train);
+    DeviceBuffers::TrainingScope scope(mem);
     const size_t B = Bq, T = Tq, Hd = dims.Hd, E = dims.E, R = dims.R, NH = dims.NH;
     {
         const size_t dh = Hd / NH, lds_bwd = sizeof(float) * (2 * R * (dh + 1) + 2 * dh + 128 + 4);
@@ -245,7 +230,6 @@ int Aoa::ensure_train(int Bq, int Tq) {
     ICZ_TRY(alloc((void**)&temb, sizeof(float) * TB * E));
     float** sth[] = {&tu, &tqn, &tQp, &txatt, &tcd, &dCd, &dQp, &dQn, &prod, &tdX};
     for (float** p : sth) ICZ_TRY(alloc((void**)p, sizeof(float) * TB * Hd));
-    ICZ_CHECK_HIP(hipMemset(tcd, 0, sizeof(float) * TB * Hd));      // the batched vocabulary projection of xe_forward reads every (t, b) row
     ICZ_TRY(alloc((void**)&tg, sizeof(float) * TB * 4 * Hd));
     ICZ_TRY(alloc((void**)&dG, sizeof(float) * TB * 4 * Hd));
     ICZ_TRY(alloc((void**)&tz, sizeof(float) * TB * 2 * Hd));
@@ -265,20 +249,8 @@ int Aoa::ensure_train(int Bq, int Tq) {
     ICZ_TRY(alloc((void**)&X, sizeof(float) * xfloats));
     ICZ_TRY(alloc((void**)&X2, sizeof(float) * xfloats));
     ICZ_TRY(alloc((void**)&dWp, sizeof(float) * (size_t)Vp * Hd));
-    ICZ_TRY(alloc((void**)&coef, sizeof(float) * TB));
-    ICZ_TRY(alloc((void**)&lse, sizeof(float) * TB));
-    ICZ_TRY(alloc((void**)&loss_rows, sizeof(float) * TB));
-    ICZ_TRY(alloc((void**)&draw, sizeof(int32_t) * TB));
-    ICZ_TRY(alloc((void**)&unf, B));
-    ICZ_TRY(alloc((void**)&nunf, sizeof(int) * T));
-    ICZ_TRY(alloc((void**)&gunf, B));
-    ICZ_TRY(alloc((void**)&gnunf, sizeof(int) * T));
-    ICZ_TRY(alloc((void**)&live_rows, 16));
-    ICZ_TRY(alloc((void**)&pack_idx, sizeof(int) * 2 * T));
-    // The hipMemset calls above run on the NULL stream; callers enqueue on NON-BLOCKING streams (torch's), which are not ordered behind
-    // it: without this, a kernel of the first call after a (re)allocation could run BEFORE the zero-fill of its buffer and then be
-    // wiped by it (round 5: sample_init_kernel's unfinished flags, seen as an all-zero rollout in 1 of 3 five-rank runs).
-    ICZ_CHECK_HIP(hipDeviceSynchronize());
+    ICZ_TRY(alloc_loss_buffers(mem, TB, B, T));
+    ICZ_TRY(mem.synced());
     tcap_B = Bq; tcap_T = Tq;
     return ICZ_OK;
 }
@@ -371,15 +343,11 @@ static bool aoa_explicit_rng(const icz_aoa_rng& r) {
 // (fixed region counts, Philox randomness), replayed like the BUTD pair.
 int Aoa::rollouts(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* ids_out, int64_t* seq_out, float* logp_out, hipStream_t st) {
     ICZ_REQUIRE(ids_out, "aoa rollouts: null argument");
-    if (!side_st) {
-        ICZ_CHECK_HIP(hipStreamCreateWithFlags(&side_st, hipStreamNonBlocking));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-    }
+    ICZ_TRY(side.ensure());
     ICZ_TRY(sample_prelude(feats, B, T, r, seq_out, logp_out, st));
     if (!lens && !proj_shared) {
         ICZ_TRY(alloc((void**)&proj_shared, sizeof(float) * (size_t)dims.max_rows * dims.R * dims.Hd));
-        ICZ_CHECK_HIP(hipDeviceSynchronize());
+        ICZ_TRY(mem.synced());
     }
     if (!lens && pair_refine && !dual.xa) {      // the pair buffers: twice the rows of a bank's
         const size_t RR2 = (size_t)2 * dims.max_rows * dims.R, Hd = dims.Hd;
@@ -388,7 +356,7 @@ int Aoa::rollouts(const float* feats, int B, int T, const icz_aoa_rng* r, int64_
         ICZ_TRY(alloc((void**)&dual.qkv, sizeof(float) * RR2 * 3 * Hd));
         ICZ_TRY(alloc((void**)&dual.z, sizeof(float) * RR2 * 2 * Hd));
         ICZ_TRY(alloc((void**)&dual.meanf, sizeof(float) * (size_t)2 * dims.max_rows * Hd));
-        ICZ_CHECK_HIP(hipDeviceSynchronize());
+        ICZ_TRY(mem.synced());
     }
     // (host state, outside any captured graph: a replayed rollout pair leaves the banks where this call's batch size puts them)
     if (!lens && pair_refine) point_banks_at_pair(B); else { point_bank_at_own(0); point_bank_at_own(1); }
@@ -406,29 +374,22 @@ int Aoa::rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int64
     }
     const bool pair = proj && pair_refine && dual.xa;
     if (pair) ICZ_TRY(refine_pair(B, st, proj));          // both refiner passes in one, in front of the fork
-    ICZ_CHECK_HIP(hipEventRecord(ev_fork, st));
-    ICZ_CHECK_HIP(hipStreamWaitEvent(side_st, ev_fork, 0));
-    const int sg = greedy(feats, B, T, ids_out, side_st, proj, true, pair);
+    ICZ_CHECK_HIP(hipEventRecord(side.fork[0], st));
+    ICZ_CHECK_HIP(hipStreamWaitEvent(side.st, side.fork[0], 0));
+    const int sg = greedy(feats, B, T, ids_out, side.st, proj, true, pair);
     const int ss = sg == ICZ_OK ? sample_impl(feats, B, T, seq_out, logp_out, st, proj, pair) : sg;
-    ICZ_CHECK_HIP(hipEventRecord(ev_join, side_st));       // always join, also on error (a capture must be closed)
-    ICZ_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0));
+    ICZ_CHECK_HIP(hipEventRecord(side.join[0], side.st));       // always join, also on error (a capture must be closed)
+    ICZ_CHECK_HIP(hipStreamWaitEvent(st, side.join[0], 0));
     return ss;
 }
 
 int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* loss_out, float* msum_out, float msum_global, hipStream_t st) {
-    ICZ_REQUIRE(mode == 1, "aoa: no rollout stored (call icz_aoa_sample first)");
+    ICZ_TRY(require_mode(1, "aoa"));
     ICZ_REQUIRE(reward && G, "aoa sample_backward: null argument");
-    if (msum_global >= 0.f)      // < 0: keep the device value handed over by icz_aoa_set_norm_global
-        hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, (uint64_t*)nullptr, (uint64_t)0, d_msum, msum_global);
+    set_msum_global(msum_global, st);      // < 0: keep the device value handed over by icz_aoa_set_norm_global
     mode = 0;
     bptt_early_out = true;
-    if (!low_st) {          // the side stream of bptt: created here, outside any capture
-        ICZ_CHECK_HIP(hipStreamCreateWithFlags(&low_st, hipStreamNonBlocking));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_fork2, hipEventDisableTiming));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_join2, hipEventDisableTiming));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_fork3, hipEventDisableTiming));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_join3, hipEventDisableTiming));
-    }
+    ICZ_TRY(low.ensure());          // the side stream of bptt: created here, outside any capture
     // with a DP callback the hook must fire on every call: eager launches (a replayed graph would not call it)
     if (!use_graphs || lens || grad_cb || aoa_explicit_rng(rng)) return sample_backward_impl(reward, *G, loss_out, msum_out, st);
     std::vector<uintptr_t> key = {2, (uintptr_t)reward, (uintptr_t)loss_out, (uintptr_t)msum_out, (uintptr_t)cur_B, (uintptr_t)cur_T, (uintptr_t)cur_R,
@@ -441,9 +402,7 @@ int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* lo
 }
 
 int Aoa::sample_backward_impl(const float* reward, const icz_aoa_params& G, float* loss_out, float* msum_out, hipStream_t st) {
-    const int B = cur_B, T = cur_T;
-    hipLaunchKernelGGL(reinforce_loss_kernel, dim3(1), dim3(256), 0, st, cur_logp, cur_seq, reward, B, T, (const float*)d_msum, coef, loss_out, msum_out);
-    hipLaunchKernelGGL(reinforce_dlogits_kernel, dim3(cdiv(Vp, 256), T * B), dim3(256), 0, st, tlogit, dims.V, Vp, draw, lse, coef, B, T);
+    ICZ_TRY(reinforce(reward, tlogit, dims.V, Vp, loss_out, msum_out, st));
     return bptt(G, st);
 }
 
@@ -453,31 +412,18 @@ int Aoa::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
     ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
     ICZ_REQUIRE(!train || r, "aoa xe_forward: training mode needs an icz_aoa_rng");
     int T = 0;
-    for (int b = 0; b < B; ++b) {
-        ICZ_REQUIRE(lengths[b] >= 1 && lengths[b] <= L - 1, "aoa xe_forward: length %d out of range 1..%d", lengths[b], L - 1);
-        ICZ_REQUIRE(b == 0 || lengths[b] <= lengths[b - 1], "aoa xe_forward: lengths must be sorted in decreasing order");
-        if (lengths[b] > T) T = lengths[b];
-    }
+    ICZ_TRY(xe_steps("aoa", lengths, B, L, &T));
     ICZ_TRY(ensure_train(B, T));
     use_bank(1);
     if (r) rng = *r; else rng = {};
-    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
-    mode = 2; cur_B = B; cur_T = T; cur_L = L; cur_train = train != 0; cur_captions = captions;
-    rows_t.assign(T, 0);
-    n_tokens = 0;
-    for (int t = 0; t < T; ++t) {
-        int cnt = 0;
-        for (int b = 0; b < B; ++b) cnt += lengths[b] > t;
-        rows_t[t] = cnt;
-        n_tokens += cnt;
-    }
+    begin_xe(lengths, B, T, L, captions, train != 0, rng.seed, st);
     ICZ_TRY(refine(feats, B, cur_train, st));
     const size_t sH = (size_t)B * dims.Hd;
     ICZ_CHECK_HIP(hipMemsetAsync(th, 0, sizeof(float) * sH, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tm, 0, sizeof(float) * sH, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tctx, 0, sizeof(float) * sH, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tlogit, 0, sizeof(float) * (size_t)T * B * Vp, st));
-    hipLaunchKernelGGL(aoa_captions_to_tok_kernel, dim3(cdiv(T * B, 256)), dim3(256), 0, st, captions, B, L, T, tok);
+    captions_to_tok(tok, st);
     // teacher forcing: one vocabulary projection over all (t, b) rows after the loop unless scheduled sampling needs the previous
     // step's logits (butd_train.hip: xe_forward); rows b >= rows_t[t] are zeroed by xe_loss_dlogits_kernel / the scatter kernel
     const bool batched_predict = ss_prob <= 0.f && T * B >= 128;
@@ -498,35 +444,15 @@ int Aoa::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
         g.M = T * B; g.N = dims.V; g.out = tlogit; g.ldo = Vp; g.bias = P.predict_b; g.nsplit = 1;
         ICZ_TRY(gemm_f32(GEMM_NT, g, st));
     }
-    if (packed_out) {
-        std::vector<int> hostv(2 * T);
-        int acc = 0;
-        for (int t = 0; t < T; ++t) { hostv[t] = acc; hostv[T + t] = rows_t[t]; acc += rows_t[t]; }
-        ICZ_CHECK_HIP(hipMemcpyAsync(pack_idx, hostv.data(), sizeof(int) * 2 * T, hipMemcpyHostToDevice, st));
-        ICZ_CHECK_HIP(hipStreamSynchronize(st));
-        hipLaunchKernelGGL(aoa_gather_packed_kernel, dim3(cdiv(dims.V, 256), T * B), dim3(256), 0, st, tlogit, dims.V, Vp, B, pack_idx,
-                           pack_idx + T, packed_out);
-    }
+    if (packed_out) ICZ_TRY(gather_packed(tlogit, dims.V, Vp, packed_out, st));
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
 
 int Aoa::xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, float n_tokens_global, hipStream_t st) {
-    ICZ_REQUIRE(mode == 2, "aoa: no XE forward stored (call icz_aoa_xe_forward first)");
+    ICZ_TRY(require_mode(2, "aoa"));
     ICZ_REQUIRE(G, "aoa xe_backward: null grads");
-    const int B = cur_B, T = cur_T;
-    const float n = n_tokens_global > 0.f ? n_tokens_global : (float)n_tokens;
-    const float* n_dev = n_tokens_global < 0.f ? d_msum : nullptr;      // < 0: the device scalar handed over by *_set_*_global
-    ICZ_CHECK_HIP(hipMemsetAsync(loss_rows, 0, sizeof(float) * T * B, st));
-    {
-        ICZ_REQUIRE(T <= XE_MAX_T, "xe_backward: %d steps exceed %d", T, XE_MAX_T);
-        XeRows xr = {};
-        for (int t = 0; t < T; ++t) xr.n[t] = rows_t[t];
-        hipLaunchKernelGGL(xe_loss_dlogits_kernel, dim3(B, T), dim3(256), 0, st, tlogit, dims.V, Vp, cur_captions, cur_L, B, xr, smoothing, 1.0f / n, n_dev,
-                           loss_rows);
-    }
-    if (loss_out) hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, st, loss_rows, T * B, 1.0f / n, n_dev, loss_out);
-    mode = 0;
+    ICZ_TRY(xe_loss(smoothing, n_tokens_global, tlogit, dims.V, Vp, loss_out, st));
     bptt_early_out = false;
     return bptt(*G, st);
 }
@@ -583,18 +509,12 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     const bool side = !grad_cb;
     hipStream_t ps = st;
     if (side) {
-        if (!low_st) {
-            // a plain stream: eager launches on a PRIORITISED stream beside other streams' work can serialise on this runtime
-            // (EXPERIMENTS.md, round 4, section 8), and the AoA paths are eager
-            ICZ_CHECK_HIP(hipStreamCreateWithFlags(&low_st, hipStreamNonBlocking));
-            ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_fork2, hipEventDisableTiming));
-            ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_join2, hipEventDisableTiming));
-            ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_fork3, hipEventDisableTiming));
-            ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_join3, hipEventDisableTiming));
-        }
-        ICZ_CHECK_HIP(hipEventRecord(ev_fork2, st));
-        ICZ_CHECK_HIP(hipStreamWaitEvent(low_st, ev_fork2, 0));
-        ps = low_st;
+        // a plain stream: eager launches on a PRIORITISED stream beside other streams' work can serialise on this runtime
+        // (EXPERIMENTS.md, round 4, section 8), and the AoA paths are eager
+        ICZ_TRY(low.ensure());
+        ICZ_CHECK_HIP(hipEventRecord(low.fork[0], st));
+        ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, low.fork[0], 0));
+        ps = low.st;
     }
     const int s_tn = tn(tlogit, Vp, Vp, tcd, Hd, Hd, TB, dWp, Hd, 0, ps, rl);
     if (s_tn == ICZ_OK) {
@@ -602,8 +522,8 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
         hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, ps, dWp, Hd, P.predict_v, P.predict_g, n_pred, G.predict_v,
                            G.predict_g, V, Hd);
     }
-    if (side) ICZ_CHECK_HIP(hipEventRecord(ev_join2, low_st));
-    if (s_tn != ICZ_OK) { if (side) (void)hipStreamWaitEvent(st, ev_join2, 0); return s_tn; }
+    if (side) ICZ_CHECK_HIP(hipEventRecord(low.join[0], low.st));
+    if (s_tn != ICZ_OK) { if (side) (void)hipStreamWaitEvent(st, low.join[0], 0); return s_tn; }
     if (grad_cb) grad_cb(grad_cb_user, 0);      // predict.* complete in stream order: reduced beside the reverse-time loop
     if (rows_t[T - 1] < B || eo) {      // ragged batch / steps that never ran: those rows contribute exact zeros to the batched GEMMs
         ICZ_CHECK_HIP(hipMemsetAsync(dZ, 0, sizeof(float) * (size_t)TB * 2 * Hd, st));
@@ -652,11 +572,11 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     return ICZ_OK;
     };
     const int s_loop = loop();
-    if (side) ICZ_CHECK_HIP(hipStreamWaitEvent(st, ev_join2, 0));      // the predict branch has long finished beside the loop
+    if (side) ICZ_CHECK_HIP(hipStreamWaitEvent(st, low.join[0], 0));      // the predict branch has long finished beside the loop
     if (s_loop != ICZ_OK) return s_loop;
     static const bool tail_side_on = [] { const char* e = getenv("ICZ_AOA_TAIL_SIDE"); return e ? atoi(e) != 0 : true; }();      // A/B switch (read once)
     const bool tail_side = side && tail_side_on;
-    if (tail_side) ICZ_CHECK_HIP(hipEventRecord(ev_fork3, st));
+    if (tail_side) ICZ_CHECK_HIP(hipEventRecord(low.fork[1], st));
     // ---- embedding gradient
     ICZ_TRY(nn(dG, 4 * Hd, TB, 4 * Hd, P.lstm_w_ih, E + Hd, E, X, xfloats, &ns, TARGET_WGS, st, nullptr, rl));
     {
@@ -688,7 +608,7 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     // ---- the attention block's small products (three Hd x Hd weight gradients, d K / d V, seven column sums: 240 us of kernels that fill a
     //      fraction of the chip, eager timeline round 6) depend on the loop only: without a DP callback they run on the side stream beside
     //      the embedding / LSTM / AoA-linear gradients above -- forked at the loop's end, ISSUED last, joined here (as Butd::bptt's tail)
-    hipStream_t ts = tail_side ? low_st : st;
+    hipStream_t ts = tail_side ? low.st : st;
     auto tail = [&]() -> int {
     ICZ_TRY(tn(dQp, Hd, Hd, tqn, Hd, Hd, TB, G.dec.q_w, Hd, 0, ts, rl));
     ICZ_TRY(colsum(dQp, TB, Hd, Hd, G.dec.q_b, ts));
@@ -711,11 +631,11 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     }
     return ICZ_OK;
     };
-    if (tail_side) ICZ_CHECK_HIP(hipStreamWaitEvent(low_st, ev_fork3, 0));
+    if (tail_side) ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, low.fork[1], 0));
     const int s_tail = tail();
     if (tail_side) {       // joined also on an error (inside a capture an unjoined side stream would hide it behind a capture failure)
-        ICZ_CHECK_HIP(hipEventRecord(ev_join3, low_st));
-        ICZ_CHECK_HIP(hipStreamWaitEvent(st, ev_join3, 0));
+        ICZ_CHECK_HIP(hipEventRecord(low.join[1], low.st));
+        ICZ_CHECK_HIP(hipStreamWaitEvent(st, low.join[1], 0));
     }
     if (s_tail != ICZ_OK) return s_tail;
     ICZ_CHECK_HIP(hipGetLastError());
@@ -744,11 +664,7 @@ int icz_aoa_sample_backward(icz_aoa_t* h, const float* reward, const icz_aoa_par
     return reinterpret_cast<Aoa*>(h)->sample_backward(reward, grads, loss_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
 }
 int icz_aoa_set_scheduled_sampling(icz_aoa_t* h, float ss_prob, const float* gate_uniforms, const float* draw_uniforms) {
-    ICZ_REQUIRE(h, "null handle");
-    ICZ_REQUIRE(ss_prob >= 0.f && ss_prob <= 1.f, "icz_aoa_set_scheduled_sampling: ss_prob %g outside [0, 1]", (double)ss_prob);
-    Aoa* a = reinterpret_cast<Aoa*>(h);
-    a->ss_prob = ss_prob; a->ss_gate = gate_uniforms; a->ss_draw = draw_uniforms;
-    return ICZ_OK;
+    return set_scheduled_sampling("icz_aoa_set_scheduled_sampling", reinterpret_cast<Aoa*>(h), ss_prob, gate_uniforms, draw_uniforms);
 }
 int icz_aoa_xe_forward(icz_aoa_t* h, const float* feats, const int64_t* captions, int32_t B, int32_t L, const int32_t* lengths_host,
                        const icz_aoa_rng* rng, int32_t train, float* packed_logits_out, void* stream) {
@@ -771,9 +687,7 @@ int icz_aoa_set_grad_callback(icz_aoa_t* h, icz_grad_ready_cb cb, void* user) {
     return ICZ_OK;
 }
 int icz_aoa_set_norm_global(icz_aoa_t* h, const float* norm_dev, void* stream) {
-    ICZ_REQUIRE(h && norm_dev, "icz_aoa_set_norm_global: null argument");
-    ICZ_CHECK_HIP(hipMemcpyAsync(reinterpret_cast<Aoa*>(h)->d_msum, norm_dev, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return ICZ_OK;
+    return set_norm_global("icz_aoa_set_norm_global", reinterpret_cast<Aoa*>(h), norm_dev, stream);
 }
 int icz_aoa_xe_backward(icz_aoa_t* h, float smoothing, const icz_aoa_params* grads, float* loss_out, float n_tokens_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");

@@ -1,32 +1,11 @@
 // BUTD decoder: handle, launch sequences and C ABI (include/icz.h).  gfx950 only.
-#include <stdarg.h>
-
 #include <vector>
 
 #include "butd_impl.h"
 
 namespace icz {
 
-static thread_local char g_err[1024] = "";
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
 // ------------------------------------------------------------------------------------------------
-int Butd::alloc(void** p, size_t bytes) {
-    ICZ_CHECK_HIP(hipMalloc(p, bytes ? bytes : 16));
-    (alloc_train ? tallocs : allocs).push_back(*p);
-    return ICZ_OK;
-}
-
-void Butd::clear_graphs() {
-    for (auto& e : graphs) (void)hipGraphExecDestroy(e.exec);
-    graphs.clear();
-}
-
 int Butd::init(const icz_butd_dims& d) {
     dims = d;
     ICZ_REQUIRE(d.R > 0 && d.R <= 64, "butd: R=%d must be in 1..64 (36 boxes / 49 grid cells)", d.R);
@@ -38,7 +17,6 @@ int Butd::init(const icz_butd_dims& d) {
     ICZ_TRY(alloc((void**)&w_aff, sizeof(float) * A));
     const size_t Vp = pad_vocab(d.V);           // padded rows stay zero: the dgrad GEMM reads K = Vp rows
     ICZ_TRY(alloc((void**)&w_pred, sizeof(float) * Vp * H));
-    ICZ_CHECK_HIP(hipMemset(w_pred, 0, sizeof(float) * Vp * H));
     ICZ_TRY(alloc((void**)&n_enc, sizeof(float) * A));
     ICZ_TRY(alloc((void**)&n_dec, sizeof(float) * A));
     ICZ_TRY(alloc((void**)&n_aff, sizeof(float) * 4));
@@ -61,10 +39,7 @@ int Butd::init(const icz_butd_dims& d) {
     ICZ_TRY(alloc((void**)&amax_val, sizeof(float) * rows * ARGMAX_PARTS));
     ICZ_TRY(alloc((void**)&amax_idx, sizeof(int) * rows * ARGMAX_PARTS));
     ICZ_TRY(alloc((void**)&it, sizeof(int64_t) * rows));
-    ICZ_TRY(alloc((void**)&d_seed, 16));
-    ICZ_TRY(alloc((void**)&d_msum_global, 16));
-    ICZ_CHECK_HIP(hipMemset(d_seed, 0, 16));
-    ICZ_CHECK_HIP(hipMemset(d_msum_global, 0, 16));
+    ICZ_TRY(alloc_scalars(mem));
     size_t nmax = 4 * H;
     if (A > nmax) nmax = A;
     if (V > nmax) nmax = V;
@@ -75,27 +50,11 @@ int Butd::init(const icz_butd_dims& d) {
         if (need > ws_floats) ws_floats = need;
     }
     ICZ_TRY(alloc((void**)&ws, sizeof(float) * ws_floats));
+    ICZ_TRY(mem.synced());
     // defaults of the options "early_out" / "merge_small" from the environment (A/B runs of whole programs; icz_butd_set_option overrides)
-    ICZ_CHECK_HIP(hipDeviceSynchronize());      // the zero-fills above ran on the NULL stream; callers use non-blocking streams (see ensure_train)
     if (const char* e = getenv("ICZ_EARLY_OUT")) early_out = atoi(e) != 0;
     if (const char* e = getenv("ICZ_MERGE_SMALL")) { const int n = atoi(e); if (n >= 0 && n <= 32) merge_small = n; }
     return ICZ_OK;
-}
-
-Butd::~Butd() {
-    if (side_st) (void)hipStreamDestroy(side_st);
-    if (low_st) (void)hipStreamDestroy(low_st);
-    if (ev_fork2) (void)hipEventDestroy(ev_fork2);
-    if (ev_join2) (void)hipEventDestroy(ev_join2);
-    if (ev_fork3) (void)hipEventDestroy(ev_fork3);
-    if (ev_join3) (void)hipEventDestroy(ev_join3);
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_join) (void)hipEventDestroy(ev_join);
-    clear_graphs();
-    if (cap_st) (void)hipStreamDestroy(cap_st);
-    if (bm.n_live_host) (void)hipHostFree(bm.n_live_host);
-    for (void* p : tallocs) (void)hipFree(p);
-    for (void* p : allocs) (void)hipFree(p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -293,8 +252,9 @@ int Butd::zero_state(int rows, int which, hipStream_t st) {
 int Butd::greedy(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st) {
     ICZ_REQUIRE(feats && ids_out && B > 0 && B <= dims.max_rows && max_len > 0, "butd greedy: bad arguments");
     ICZ_REQUIRE(fresh, "butd: call icz_butd_refresh_weights after binding/updating parameters");
-    const std::vector<uintptr_t> key = {1, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)max_len, (uintptr_t)ids_out, (uintptr_t)alphas_out};
-    return run_cached(key, st, [&](hipStream_t s) { return greedy_impl(feats, B, max_len, ids_out, alphas_out, s); });
+    if (!use_graphs) return greedy_impl(feats, B, max_len, ids_out, alphas_out, st);
+    const std::vector<uintptr_t> key = {1, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)max_len, (uintptr_t)ids_out, (uintptr_t)alphas_out, opt_bits()};
+    return gc.run(key, st, [&](hipStream_t s) { return greedy_impl(feats, B, max_len, ids_out, alphas_out, s); });
 }
 
 int Butd::greedy_impl(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st) {
@@ -309,7 +269,7 @@ int Butd::greedy_impl(const float* feats, int B, int max_len, int64_t* ids_out, 
 // are the same.  icz_butd_greedy (evaluation, `sampler`) never does this: its ids are the reference's in every column.
 int Butd::greedy_chain(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st, bool scst) {
     ICZ_TRY(zero_state(B, 0, st));
-    int* const gn = (scst && early_out && tb.gnunf && tb.T >= max_len && tb.B >= B) ? tb.gnunf : nullptr;
+    int* const gn = (scst && early_out && gnunf && tb.T >= max_len && tb.B >= B) ? gnunf : nullptr;
     hipLaunchKernelGGL(greedy_init_kernel, dim3(cdiv(B > max_len ? B : max_len, 256)), dim3(256), 0, st, it, B, gn, max_len);   // <sta>
     int cur = 0;
     const int Vp = pad_vocab(dims.V);
@@ -330,7 +290,7 @@ int Butd::greedy_chain(const float* feats, int B, int max_len, int64_t* ids_out,
         if (pns > 1)         // 33 - 64 rows: the slabs of the vocabulary projection -> token + next embedding in one launch
             hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(1024), 0, st, (const float*)ws, dims.V, Vp, pns, (size_t)B * Vp,
                                (const float*)P.predict_b, P.embed_weight, dims.E, emb, it, ids_out, max_len, t, 1,
-                               track ? tb.gunf : (uint8_t*)nullptr, track ? gn : (int*)nullptr);
+                               track ? gunf : (uint8_t*)nullptr, track ? gn : (int*)nullptr);
         else {
             hipLaunchKernelGGL(argmax_part_kernel, dim3(B, ARGMAX_PARTS), dim3(256), 0, st, logits, dims.V, Vp, ARGMAX_PARTS, amax_val, amax_idx);
             hipLaunchKernelGGL(embed_argmax_kernel, dim3(cdiv(dims.E, 1024), B), dim3(256), 0, st, amax_val, amax_idx, ARGMAX_PARTS,
@@ -350,17 +310,7 @@ using namespace icz;
 
 extern "C" {
 
-const char* icz_last_error(void) { return icz::g_err; }
-const char* icz_version(void) { return "libicz 0.1 (gfx950)"; }
-
-int icz_butd_create(const icz_butd_dims* dims, icz_butd_t** out) {
-    ICZ_REQUIRE(dims && out, "icz_butd_create: null argument");
-    Butd* b = new Butd();
-    int s = b->init(*dims);
-    if (s != ICZ_OK) { delete b; return s; }
-    *out = reinterpret_cast<icz_butd_t*>(b);
-    return ICZ_OK;
-}
+int icz_butd_create(const icz_butd_dims* dims, icz_butd_t** out) { return abi_create<Butd>("icz_butd_create", dims, out); }
 
 int icz_butd_destroy(icz_butd_t* h) {
     delete reinterpret_cast<Butd*>(h);
@@ -369,17 +319,13 @@ int icz_butd_destroy(icz_butd_t* h) {
 
 int icz_butd_bind_params(icz_butd_t* h, const icz_butd_params* p) {
     ICZ_REQUIRE(h && p, "icz_butd_bind_params: null argument");
-    const float* const* q = reinterpret_cast<const float* const*>(p);
-    for (size_t i = 0; i < sizeof(icz_butd_params) / sizeof(float*); ++i) {
-        ICZ_REQUIRE(q[i] != nullptr, "icz_butd_bind_params: parameter pointer %zu is null", i);
-        ICZ_REQUIRE(((uintptr_t)q[i] & 15) == 0 || i == 16 || i == 17, "icz_butd_bind_params: parameter %zu not 16-byte aligned", i);
-    }
+    ICZ_TRY(check_param_table("icz_butd_bind_params", p, sizeof(*p), (1u << 16) | (1u << 17)));
     Butd* b = reinterpret_cast<Butd*>(h);
     // the captured graphs carry the old parameter pointers in their kernel arguments (embed_weight, the LSTM weights and
     // biases ...): a rebind to other tensors must not replay them
     if (b->bound && memcmp(&b->P, p, sizeof(*p)) != 0) {
         ICZ_CHECK_HIP(hipDeviceSynchronize());
-        b->clear_graphs();
+        b->gc.clear();
     }
     b->P = *p;
     b->bound = true;
@@ -404,10 +350,7 @@ int icz_butd_set_option(icz_butd_t* h, const char* name, int32_t value) {
 }
 
 int icz_butd_set_mask_sum_global(icz_butd_t* h, const float* mask_sum_global_dev, void* stream) {
-    ICZ_REQUIRE(h && mask_sum_global_dev, "icz_butd_set_mask_sum_global: null argument");
-    Butd* b = reinterpret_cast<Butd*>(h);
-    ICZ_CHECK_HIP(hipMemcpyAsync(b->d_msum_global, mask_sum_global_dev, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return ICZ_OK;
+    return set_norm_global("icz_butd_set_mask_sum_global", reinterpret_cast<Butd*>(h), mask_sum_global_dev, stream);
 }
 
 int icz_butd_set_grad_callback(icz_butd_t* h, icz_grad_ready_cb cb, void* user) {
@@ -449,63 +392,6 @@ int icz_butd_step(icz_butd_t* h, const float* feats, int32_t B, const int64_t* i
     ICZ_CHECK_HIP(hipMemcpyAsync(h2, b->h2[0], n, hipMemcpyDeviceToDevice, st));
     ICZ_CHECK_HIP(hipMemcpyAsync(c2, b->c2[0], n, hipMemcpyDeviceToDevice, st));
     return ICZ_OK;
-}
-
-size_t icz_gemm_workspace_floats(int32_t M, int32_t N) {
-    const size_t base = (size_t)Butd::TARGET_WGS * 4096 * 2 + (size_t)M * N;
-    // 65..128 rows: the 128-row resident kernel leaves up to 32 slabs of M x N (one per 256-deep k range of K <= 8192)
-    const size_t m128 = (M > 64 && M <= 128) ? (size_t)32 * M * N : 0;
-    return base > m128 ? base : m128;
-}
-
-int icz_gemm_f32(int32_t layout, const float* X, int32_t ldx, const float* W, int32_t ldw, const float* bias,
-                 float* C, int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t nsplit, float* workspace,
-                 size_t workspace_floats, void* stream) {
-    ICZ_REQUIRE(layout >= 0 && layout <= 2, "icz_gemm_f32: layout %d", layout);
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.seg[0] = {X, W, ldx, ldw, K, nullptr};
-    g.M = M; g.N = N; g.out = C; g.ldo = ldc; g.bias = bias;
-    g.nsplit = nsplit > 0 ? nsplit : gemm_fit_split((GemmLayout)layout, g, gemm_pick_split(g, Butd::TARGET_WGS, (GemmLayout)layout), workspace_floats);
-    g.nsplit = gemm_normalize_split((GemmLayout)layout, g, g.nsplit);   // no empty splits
-    hipStream_t st = (hipStream_t)stream;
-    if (g.nsplit > 1) {
-        ICZ_REQUIRE(workspace, "icz_gemm_f32: split-K needs a workspace");
-        ICZ_REQUIRE(gemm_slab_floats(M, N, g.nsplit) <= workspace_floats, "icz_gemm_f32: workspace of %zu floats too small for %d slabs of %dx%d", workspace_floats, g.nsplit, M, N);
-        ICZ_REQUIRE(ldc == N, "icz_gemm_f32: split-K path needs ldc == N");
-        g.out = workspace; g.bias = nullptr;
-        ICZ_TRY(gemm_f32((GemmLayout)layout, g, st));
-        size_t MN = (size_t)M * N;
-        ICZ_REQUIRE(MN % 4 == 0, "icz_gemm_f32: M*N must be a multiple of 4 for the split-K reduce");
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, workspace, g.nsplit, MN, N, bias, C);
-        ICZ_CHECK_HIP(hipGetLastError());
-        return ICZ_OK;
-    }
-    return gemm_f32((GemmLayout)layout, g, st);
-}
-
-int icz_gemm_set_big_cfg(int32_t cfg) {
-    ICZ_REQUIRE(cfg >= -2 && cfg <= 5, "icz_gemm_set_big_cfg: %d", cfg);
-    gemm_set_big_cfg(cfg);
-    return ICZ_OK;
-}
-
-int icz_gemm_big_cfg_for(int32_t layout, int32_t M, int32_t N, int32_t K, int32_t nsplit) {
-    if (layout < 0 || layout > 2 || M <= 0 || N <= 0 || K <= 0) return -1;
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.seg[0].K = K;
-    g.M = M; g.N = N; g.nsplit = nsplit > 0 ? nsplit : 1;
-    return gemm_big_cfg((GemmLayout)layout, g);
-}
-
-int icz_gemm_tn_grouped(const float* dY, int32_t ldy, int32_t M, int32_t K, int32_t ngroups, const float* const* X, const int32_t* ldx,
-                        const int32_t* cols, float* const* out, const int32_t* ldo, const int32_t* rows_live, void* stream) {
-    ICZ_REQUIRE(ngroups >= 1 && ngroups <= GEMM_MAX_COLGROUPS && X && ldx && cols && out && ldo, "icz_gemm_tn_grouped: bad arguments");
-    GemmColGroup g[GEMM_MAX_COLGROUPS];
-    for (int j = 0; j < ngroups; ++j) g[j] = {X[j], ldx[j], cols[j], out[j], ldo[j]};
-    ICZ_REQUIRE(gemm_tn_grouped_fits(M, K, g, ngroups), "icz_gemm_tn_grouped: shape not taken (M %d, K %d)", M, K);
-    return gemm_tn_grouped(dY, ldy, M, K, g, ngroups, rows_live, (hipStream_t)stream);
 }
 
 }  // extern "C"

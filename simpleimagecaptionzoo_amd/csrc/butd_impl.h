@@ -3,8 +3,7 @@
 #include <vector>
 #include <stdint.h>
 
-#include "butd_kernels.h"
-#include "gemm_f32.h"
+#include "decoder_core.h"
 
 namespace icz {
 
@@ -45,10 +44,6 @@ struct TrainBuf {
     int64_t* tok = nullptr;                                   // [(T+1), B] input token of each step
     float *emb = nullptr, *h1 = nullptr, *c1 = nullptr, *h2 = nullptr, *c2 = nullptr;   // states: [(T+1), B, H], slot 0 = zeros
     float *gtd = nullptr, *glm = nullptr, *dec = nullptr, *alpha = nullptr, *ctx = nullptr, *h2d = nullptr, *logit = nullptr;
-    int32_t* draw = nullptr; float* lse = nullptr;
-    uint8_t* unf = nullptr; int* nunf = nullptr; float *coef = nullptr, *loss_rows = nullptr;
-    uint8_t* gunf = nullptr; int* gnunf = nullptr;            // the same for the greedy baseline of an SCST step (greedy_chain, scst = true)
-    int* live_rows = nullptr;                                 // (steps the sampled rollout ran) x B: row limit of the backward pass's batched GEMMs
     int* nany = nullptr;                                      // merged chain: unfinished sampled rows + greedy rows that have not ended, per step
     int32_t* img2 = nullptr;                                  // merged chain: image of each decoder row (row r of 2 B -> image r mod B)
     float *dGtd = nullptr, *dGlm = nullptr, *dDec = nullptr, *dEmb = nullptr, *dH2d = nullptr, *dEnc = nullptr;
@@ -57,19 +52,9 @@ struct TrainBuf {
     float* X[4] = {nullptr, nullptr, nullptr, nullptr}; size_t xfloats = 0;
     float *dWp = nullptr, *dWenc = nullptr, *dWdec = nullptr, *dWaff = nullptr, *scalars = nullptr;
     float* wslab = nullptr; size_t wslab_floats = 0;      // split-K slabs of the two attention weight gradients (gemm_tn_split, round 6)
-    int* scalars_i = nullptr; int scalars_i_cap = 0;
 };
 
-struct BeamBuf {
-    int cap_rows = 0, cap_L = 0;
-    int* n_act = nullptr; float* run = nullptr; int32_t* seqs[2] = {nullptr, nullptr};
-    int32_t *src_row = nullptr, *img_of_row = nullptr, *best_seq = nullptr;
-    float* best_score = nullptr; int *best_len = nullptr, *has_complete = nullptr, *n_live = nullptr, *n_live_host = nullptr;
-    float* feat_rows = nullptr;       // NIC: image embedding replicated per beam row
-    float* cand_val = nullptr; int* cand_idx = nullptr;     // [rows, BEAM_MAX_K] per-row candidates of one step
-};
-
-struct Butd {
+struct Butd : CaptionHead {
     static constexpr int TARGET_WGS = 512;   // ~2 workgroups per CU on 256 CUs
     static constexpr int ATT_PARTS = 4;
     static constexpr int STEP_WGS = 256;     // skinny decoder-step GEMMs: split-K for ~1 workgroup per CU
@@ -77,9 +62,7 @@ struct Butd {
     icz_butd_dims dims;
     icz_butd_params P;
     bool bound = false, fresh = false;
-    std::vector<void*> allocs;
-    std::vector<void*> tallocs;          // training buffers (TrainBuf): re-allocated when a batch needs more rows / steps
-    bool alloc_train = false;            // alloc() target: tallocs instead of allocs
+    DeviceBuffers mem;                   // training list: TrainBuf and the loss head, re-allocated when a batch needs more rows / steps
 
     // weight-normed weights (w = g v / ||v||) and the row norms ||v||
     float *w_enc = nullptr, *w_dec = nullptr, *w_aff = nullptr, *w_pred = nullptr;
@@ -91,10 +74,6 @@ struct Butd {
     float *emb = nullptr, *ctx = nullptr, *scores = nullptr, *alpha = nullptr, *h2drop = nullptr, *logits = nullptr;
     int64_t* it = nullptr;
     float* amax_val = nullptr; int* amax_idx = nullptr;
-    uint64_t* d_seed = nullptr;          // Philox seed of the current training-mode call (device resident)
-    float ss_prob = 0.f;                 // scheduled sampling in xe_forward (icz_butd_set_scheduled_sampling)
-    const float* ss_gate = nullptr; const float* ss_draw = nullptr;      // explicit [T, B] uniforms (device) or Philox
-    float* d_msum_global = nullptr;      // data-parallel loss normaliser (0 = use the local one)
     float* ws = nullptr;
     size_t ws_floats = 0;
     // Transposed copies of the LSTM weights: the per-step dgrad products of BPTT, dx = dy W, run as NT products on W^T through the
@@ -105,8 +84,7 @@ struct Butd {
     bool wt_possible() const;
     int refresh_transposes(hipStream_t st);
 
-    ~Butd();
-    int alloc(void** p, size_t bytes);
+    int alloc(void** p, size_t bytes) { return mem.alloc(p, bytes); }
     int init(const icz_butd_dims& d);
     int refresh(hipStream_t st);
     int gemm_nt(GemmArgs& g, int* nsplit_out, hipStream_t st);
@@ -115,28 +93,21 @@ struct Butd {
     int zero_state(int rows, int which, hipStream_t st);
     int greedy(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st);
 
-    // hipGraph cache: a whole rollout / backward is ~300-700 launches of 2-30 us kernels; replaying a captured graph
-    // removes the per-launch host cost and shrinks the inter-kernel gaps.  Keyed by every pointer / size baked into
-    // the captured kernel arguments, so it only pays when the caller reuses its buffers (the Engine does).
-    struct GraphEntry { std::vector<uintptr_t> key; hipGraphExec_t exec; uint64_t last_use; };
-    std::vector<GraphEntry> graphs;
+    GraphCache gc{24};                   // keys end with opt_bits(); bypassed unless use_graphs
     bool use_graphs = false;
     bool concurrent = true;      // run independent chains on side streams (off: one stream, for per-kernel timing)
-    hipStream_t cap_st = nullptr;
-    uint64_t tick = 0;
-    template <class F> int run_cached(const std::vector<uintptr_t>& key, hipStream_t st, F&& fn);
-    void clear_graphs();                 // captured kernel arguments hold parameter / buffer addresses: drop them when those change
+    uintptr_t opt_bits() const {         // the options that change the captured launch sequence
+        return (concurrent ? 1 : 0) + (early_out ? 2 : 0) + 4 * merge_small + (small_nt ? 256 : 0);
+    }
     int greedy_impl(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st);
     int sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st);
     int greedy_chain(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st, bool scst = false);
     int sample_chain(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st, int row0 = 0, int64_t* ids_out = nullptr);
     int rollouts(const float* feats, int B, int T, const icz_rng* r, int64_t* ids_out, int64_t* seq_out, float* logp_out, hipStream_t st);
     int rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int64_t* seq_out, float* logp_out, hipStream_t st);
-    hipStream_t side_st = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipStream_t low_st = nullptr;        // lowest-priority stream for work overlapped with the BPTT chain
-    hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;
-    hipEvent_t ev_fork3 = nullptr, ev_join3 = nullptr;   // the attention block's tail beside the LSTM weight gradients (bptt)
+    SideStream side;                     // the greedy chain of the SCST rollout pair
+    SideStream low;                      // lowest priority, for work overlapped with the BPTT chain; its second event pair: the attention
+                                         // block's tail beside the LSTM weight gradients (bptt)
     icz_grad_ready_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // DP overlap hook (icz_butd_set_grad_callback)
     int sample_backward_impl(const float* reward, const icz_butd_params& G, float* loss_out, float* mask_sum_out, hipStream_t st,
                              int phases = 0xF, bool fire_cb = true);
@@ -158,12 +129,7 @@ struct Butd {
     // training paths (butd_train.hip)
     TrainBuf tb;
     icz_rng rng = {};
-    int mode = 0;                 // 0 none, 1 sample rollout stored, 2 XE forward stored
-    int cur_B = 0, cur_T = 0, cur_L = 0, n_tokens = 0;
-    bool cur_train = false;
     const float* cur_feats = nullptr;
-    const int64_t* cur_seq = nullptr; const float* cur_logp = nullptr; const int64_t* cur_captions = nullptr;
-    std::vector<int> rows_t;
     int ensure_train(int B, int T);
     int train_step(const float* feats, int rows, int Bs, int t, bool train, hipStream_t st, bool emb_ready = false, int* pred_nsplit = nullptr,
                    bool skip_predict = false, const int* live = nullptr, int row0 = 0);
@@ -175,7 +141,6 @@ struct Butd {
                    int train, float* packed_out, hipStream_t st);
     int sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hipStream_t st);
     int xe_backward_dlogits(const float* dpacked, const icz_butd_params* G, hipStream_t st);
-    int upload_pack_index(hipStream_t st);
     int xe_backward(float smoothing, const icz_butd_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
     int gemm_auto(GemmLayout layout, GemmArgs& g, float* slab, size_t slab_floats, int* ns_out, hipStream_t st);
     int wgrad(const float* dY, int ldy, int M, const float* X, int ldx, int N, int K, float* out, int ldo, hipStream_t st, const int* rows_live = nullptr);
@@ -183,95 +148,5 @@ struct Butd {
     int colsum(const float* X, int K, int N, int ldx, float* out, hipStream_t st);
     int bptt(const icz_butd_params& G, hipStream_t st, int phases = 0xF, bool fire_cb = true);
 };
-
-void gemm_set_capturing(bool on);
-bool gemm_prof_on();                  // gemm_f32.hip: event timing active (graphs captured now contain event nodes)
-
-// The same hipGraph cache as Butd::run_cached for the other decoders (AoA): capture on first use of a key, replay afterwards.
-struct GraphCache {
-    struct Entry { std::vector<uintptr_t> key; hipGraphExec_t exec; uint64_t last_use; };
-    std::vector<Entry> graphs;
-    hipStream_t cap_st = nullptr;
-    uint64_t tick = 0;
-    void clear() {
-        for (auto& e : graphs) (void)hipGraphExecDestroy(e.exec);
-        graphs.clear();
-    }
-    ~GraphCache() {
-        clear();
-        if (cap_st) (void)hipStreamDestroy(cap_st);
-    }
-    template <class F>
-    int run(const std::vector<uintptr_t>& key_in, hipStream_t st, F&& fn) {
-        ++tick;
-        std::vector<uintptr_t> key = key_in;
-        key.push_back((gemm_prof_on() ? 1 : 0) + 2 * (uintptr_t)(gemm_big_switch() + 2));      // the tile-configuration override changes the captured launches
-        for (auto& e : graphs)
-            if (e.key == key) {
-                e.last_use = tick;
-                ICZ_CHECK_HIP(hipGraphLaunch(e.exec, st));
-                return ICZ_OK;
-            }
-        if (!cap_st) ICZ_CHECK_HIP(hipStreamCreateWithFlags(&cap_st, hipStreamNonBlocking));
-        ICZ_CHECK_HIP(hipStreamBeginCapture(cap_st, hipStreamCaptureModeThreadLocal));
-        gemm_set_capturing(true);
-        const int status = fn(cap_st);
-        gemm_set_capturing(false);
-        hipGraph_t g = nullptr;
-        hipError_t ce = hipStreamEndCapture(cap_st, &g);
-        if (status != ICZ_OK) { if (g) (void)hipGraphDestroy(g); return status; }
-        if (ce != hipSuccess || !g) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ce)); return ICZ_ERR_HIP; }
-        hipGraphExec_t exec = nullptr;
-        hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (ie != hipSuccess) { set_error("hipGraphInstantiate failed: %s", hipGetErrorString(ie)); return ICZ_ERR_HIP; }
-        if (graphs.size() >= 16) {      // evict the least recently used entry
-            size_t lru = 0;
-            for (size_t i = 1; i < graphs.size(); ++i) if (graphs[i].last_use < graphs[lru].last_use) lru = i;
-            (void)hipGraphExecDestroy(graphs[lru].exec);
-            graphs.erase(graphs.begin() + lru);
-        }
-        graphs.push_back({key, exec, tick});
-        ICZ_CHECK_HIP(hipGraphLaunch(exec, st));
-        return ICZ_OK;
-    }
-};
-
-template <class F>
-int Butd::run_cached(const std::vector<uintptr_t>& key_in, hipStream_t st, F&& fn) {
-    if (!use_graphs) return fn(st);
-    ++tick;
-    std::vector<uintptr_t> key = key_in;
-    key.push_back((concurrent ? 1 : 0) + (early_out ? 2 : 0) + 4 * merge_small + (small_nt ? 256 : 0));          // flags that change the captured launch sequence
-    key.push_back((gemm_prof_on() ? 1 : 0) + 2 * (uintptr_t)(gemm_big_switch() + 2));      // the tile-configuration override changes the captured launches
-    for (auto& e : graphs)
-        if (e.key == key) {
-            e.last_use = tick;
-            ICZ_CHECK_HIP(hipGraphLaunch(e.exec, st));
-            return ICZ_OK;
-        }
-    if (!cap_st) ICZ_CHECK_HIP(hipStreamCreateWithFlags(&cap_st, hipStreamNonBlocking));
-    ICZ_CHECK_HIP(hipStreamBeginCapture(cap_st, hipStreamCaptureModeThreadLocal));
-    gemm_set_capturing(true);
-    const int status = fn(cap_st);
-    gemm_set_capturing(false);
-    hipGraph_t g = nullptr;
-    hipError_t ce = hipStreamEndCapture(cap_st, &g);
-    if (status != ICZ_OK) { if (g) (void)hipGraphDestroy(g); return status; }
-    if (ce != hipSuccess || !g) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ce)); return ICZ_ERR_HIP; }
-    hipGraphExec_t exec = nullptr;
-    hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (ie != hipSuccess) { set_error("hipGraphInstantiate failed: %s", hipGetErrorString(ie)); return ICZ_ERR_HIP; }
-    if (graphs.size() >= 24) {      // evict the least recently used entry
-        size_t lru = 0;
-        for (size_t i = 1; i < graphs.size(); ++i) if (graphs[i].last_use < graphs[lru].last_use) lru = i;
-        (void)hipGraphExecDestroy(graphs[lru].exec);
-        graphs.erase(graphs.begin() + lru);
-    }
-    graphs.push_back({key, exec, tick});
-    ICZ_CHECK_HIP(hipGraphLaunch(exec, st));
-    return ICZ_OK;
-}
 
 }  // namespace icz

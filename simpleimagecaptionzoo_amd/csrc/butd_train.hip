@@ -26,13 +26,10 @@ int Butd::ensure_train(int B, int T) {
     if (tb.B > B) B = tb.B;
     if (tb.T > T) T = tb.T;
     if (dims.max_len > T) T = dims.max_len;
-    if (!tallocs.empty()) {
-        ICZ_CHECK_HIP(hipDeviceSynchronize());
-        clear_graphs();
-        for (void* p : tallocs) (void)hipFree(p);
-        tallocs.clear();
+    if (!mem.training.empty()) {
+        ICZ_TRY(mem.release_training(&gc));
         tb = TrainBuf();
-        mode = 0;
+        drop_loss_buffers();
     }
     if (!wt_lm_ih && wt_possible()) {      // permanent (not re-allocated when the training buffers grow)
         const size_t G4 = 4 * (size_t)dims.H;
@@ -42,52 +39,39 @@ int Butd::ensure_train(int B, int T) {
         ICZ_TRY(alloc((void**)&wt_td_hh, sizeof(float) * G4 * dims.H));
         wt_fresh = false;
     }
-    struct Scope { bool& f; Scope(bool& x) : f(x) { f = true; } ~Scope() { f = false; } } scope(alloc_train);
+    DeviceBuffers::TrainingScope scope(mem);
     const size_t H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = dims.R, V = dims.V;
     const size_t Vp = round4(dims.V);
     const size_t TB = (size_t)T * B;
-    auto zalloc = [&](void** p, size_t bytes) -> int {
-        ICZ_TRY(alloc(p, bytes));
-        ICZ_CHECK_HIP(hipMemset(*p, 0, bytes ? bytes : 16));
-        return ICZ_OK;
-    };
-    ICZ_TRY(zalloc((void**)&tb.tok, sizeof(int64_t) * (TB + B)));
-    ICZ_TRY(zalloc((void**)&tb.emb, sizeof(float) * TB * E));
-    ICZ_TRY(zalloc((void**)&tb.h1, sizeof(float) * (TB + B) * H));
-    ICZ_TRY(zalloc((void**)&tb.c1, sizeof(float) * (TB + B) * H));
-    ICZ_TRY(zalloc((void**)&tb.h2, sizeof(float) * (TB + B) * H));
-    ICZ_TRY(zalloc((void**)&tb.c2, sizeof(float) * (TB + B) * H));
-    ICZ_TRY(zalloc((void**)&tb.gtd, sizeof(float) * TB * 4 * H));
-    ICZ_TRY(zalloc((void**)&tb.glm, sizeof(float) * TB * 4 * H));
-    ICZ_TRY(zalloc((void**)&tb.dec, sizeof(float) * TB * A));
-    ICZ_TRY(zalloc((void**)&tb.alpha, sizeof(float) * TB * R));
-    ICZ_TRY(zalloc((void**)&tb.ctx, sizeof(float) * TB * D));
-    ICZ_TRY(zalloc((void**)&tb.h2d, sizeof(float) * TB * H));
-    ICZ_TRY(zalloc((void**)&tb.logit, sizeof(float) * TB * Vp));
-    ICZ_TRY(zalloc((void**)&tb.draw, sizeof(int32_t) * TB));
-    ICZ_TRY(zalloc((void**)&tb.lse, sizeof(float) * TB));
-    ICZ_TRY(zalloc((void**)&tb.unf, B));
-    ICZ_TRY(zalloc((void**)&tb.nunf, sizeof(int) * T));
-    ICZ_TRY(zalloc((void**)&tb.gunf, B));
-    ICZ_TRY(zalloc((void**)&tb.gnunf, sizeof(int) * T));
-    ICZ_TRY(zalloc((void**)&tb.live_rows, 16));
-    ICZ_TRY(zalloc((void**)&tb.nany, sizeof(int) * T));
-    ICZ_TRY(zalloc((void**)&tb.img2, sizeof(int32_t) * B));
-    ICZ_TRY(zalloc((void**)&tb.coef, sizeof(float) * TB));
-    ICZ_TRY(zalloc((void**)&tb.loss_rows, sizeof(float) * TB));
-    ICZ_TRY(zalloc((void**)&tb.dGtd, sizeof(float) * TB * 4 * H));
-    ICZ_TRY(zalloc((void**)&tb.dGlm, sizeof(float) * TB * 4 * H));
-    ICZ_TRY(zalloc((void**)&tb.dDec, sizeof(float) * TB * A));
-    ICZ_TRY(zalloc((void**)&tb.dEmb, sizeof(float) * TB * E));
-    ICZ_TRY(zalloc((void**)&tb.dH2d, sizeof(float) * TB * H));
-    ICZ_TRY(zalloc((void**)&tb.dEnc, sizeof(float) * (size_t)B * R * A));
-    ICZ_TRY(zalloc((void**)&tb.dwaff, sizeof(float) * (size_t)B * ATT_PARTS * A));
-    ICZ_TRY(zalloc((void**)&tb.dalpha, sizeof(float) * (size_t)B * R * cdiv((int)D, DALPHA_COLS)));
-    ICZ_TRY(zalloc((void**)&tb.dS, sizeof(float) * TB * R));
-    ICZ_TRY(zalloc((void**)&tb.dGsum, sizeof(float) * (size_t)B * 4 * H));
+    ICZ_TRY(alloc((void**)&tb.tok, sizeof(int64_t) * (TB + B)));
+    ICZ_TRY(alloc((void**)&tb.emb, sizeof(float) * TB * E));
+    ICZ_TRY(alloc((void**)&tb.h1, sizeof(float) * (TB + B) * H));
+    ICZ_TRY(alloc((void**)&tb.c1, sizeof(float) * (TB + B) * H));
+    ICZ_TRY(alloc((void**)&tb.h2, sizeof(float) * (TB + B) * H));
+    ICZ_TRY(alloc((void**)&tb.c2, sizeof(float) * (TB + B) * H));
+    ICZ_TRY(alloc((void**)&tb.gtd, sizeof(float) * TB * 4 * H));
+    ICZ_TRY(alloc((void**)&tb.glm, sizeof(float) * TB * 4 * H));
+    ICZ_TRY(alloc((void**)&tb.dec, sizeof(float) * TB * A));
+    ICZ_TRY(alloc((void**)&tb.alpha, sizeof(float) * TB * R));
+    ICZ_TRY(alloc((void**)&tb.ctx, sizeof(float) * TB * D));
+    ICZ_TRY(alloc((void**)&tb.h2d, sizeof(float) * TB * H));
+    ICZ_TRY(alloc((void**)&tb.logit, sizeof(float) * TB * Vp));
+    ICZ_TRY(alloc_loss_buffers(mem, TB, B, T));
+    ICZ_TRY(alloc((void**)&tb.nany, sizeof(int) * T));
+    ICZ_TRY(alloc((void**)&tb.img2, sizeof(int32_t) * B));
+    ICZ_TRY(alloc((void**)&tb.dGtd, sizeof(float) * TB * 4 * H));
+    ICZ_TRY(alloc((void**)&tb.dGlm, sizeof(float) * TB * 4 * H));
+    ICZ_TRY(alloc((void**)&tb.dDec, sizeof(float) * TB * A));
+    ICZ_TRY(alloc((void**)&tb.dEmb, sizeof(float) * TB * E));
+    ICZ_TRY(alloc((void**)&tb.dH2d, sizeof(float) * TB * H));
+    ICZ_TRY(alloc((void**)&tb.dEnc, sizeof(float) * (size_t)B * R * A));
+    ICZ_TRY(alloc((void**)&tb.dwaff, sizeof(float) * (size_t)B * ATT_PARTS * A));
+    ICZ_TRY(alloc((void**)&tb.dalpha, sizeof(float) * (size_t)B * R * cdiv((int)D, DALPHA_COLS)));
+    ICZ_TRY(alloc((void**)&tb.dS, sizeof(float) * TB * R));
+    ICZ_TRY(alloc((void**)&tb.dGsum, sizeof(float) * (size_t)B * 4 * H));
     for (int i = 0; i < 2; ++i) {
-        ICZ_TRY(zalloc((void**)&tb.dc1[i], sizeof(float) * (size_t)B * H));
-        ICZ_TRY(zalloc((void**)&tb.dc2[i], sizeof(float) * (size_t)B * H));
+        ICZ_TRY(alloc((void**)&tb.dc1[i], sizeof(float) * (size_t)B * H));
+        ICZ_TRY(alloc((void**)&tb.dc2[i], sizeof(float) * (size_t)B * H));
     }
     tb.xfloats = (size_t)TARGET_WGS * 4096 * 2 + (size_t)B * (D + H);
     {   // X[0] is the sampled chain's slab workspace (train_step): same rule as Butd::init's ws_floats
@@ -95,25 +79,20 @@ int Butd::ensure_train(int B, int T) {
         const size_t need = (kmax / 256 + 1) * r128 * 4 * H;
         if (need > tb.xfloats) tb.xfloats = need;
     }
-    for (int i = 0; i < 4; ++i) ICZ_TRY(zalloc((void**)&tb.X[i], sizeof(float) * tb.xfloats));
-    ICZ_TRY(zalloc((void**)&tb.dWp, sizeof(float) * Vp * H));
-    ICZ_TRY(zalloc((void**)&tb.dWenc, sizeof(float) * A * D));
-    ICZ_TRY(zalloc((void**)&tb.dWdec, sizeof(float) * A * H));
+    for (int i = 0; i < 4; ++i) ICZ_TRY(alloc((void**)&tb.X[i], sizeof(float) * tb.xfloats));
+    ICZ_TRY(alloc((void**)&tb.dWp, sizeof(float) * Vp * H));
+    ICZ_TRY(alloc((void**)&tb.dWenc, sizeof(float) * A * D));
+    ICZ_TRY(alloc((void**)&tb.dWdec, sizeof(float) * A * H));
     {   // slabs of the two attention weight gradients (A x H over T B rows, A x D over B R rows), one buffer: they run one after the other
         const size_t n1 = (size_t)gemm_tn_split_pick((int)A, (int)H, (int)TB) * A * H, n2 = (size_t)gemm_tn_split_pick((int)A, (int)D, (int)(B * R)) * A * D;
         tb.wslab_floats = n1 > n2 ? n1 : n2;
-        if (tb.wslab_floats > A * (H > D ? H : D)) ICZ_TRY(zalloc((void**)&tb.wslab, sizeof(float) * tb.wslab_floats));
+        if (tb.wslab_floats > A * (H > D ? H : D)) ICZ_TRY(alloc((void**)&tb.wslab, sizeof(float) * tb.wslab_floats));
         else tb.wslab_floats = 0;
     }
-    ICZ_TRY(zalloc((void**)&tb.dWaff, sizeof(float) * A));
-    ICZ_TRY(zalloc((void**)&tb.scalars, sizeof(float) * 16));
-    ICZ_TRY(zalloc((void**)&tb.scalars_i, sizeof(int) * 2 * T));
-    tb.scalars_i_cap = 2 * T;
+    ICZ_TRY(alloc((void**)&tb.dWaff, sizeof(float) * A));
+    ICZ_TRY(alloc((void**)&tb.scalars, sizeof(float) * 16));
     (void)V;
-    // The hipMemset calls above run on the NULL stream; callers enqueue on NON-BLOCKING streams (torch's), which are not ordered behind
-    // it: without this, a kernel of the first call after a (re)allocation could run BEFORE the zero-fill of its buffer and then be
-    // wiped by it (round 5: sample_init_kernel's unfinished flags, seen as an all-zero rollout in 1 of 3 five-rank runs).
-    ICZ_CHECK_HIP(hipDeviceSynchronize());
+    ICZ_TRY(mem.synced());
     tb.B = B;
     tb.T = T;
     return ICZ_OK;
@@ -172,8 +151,8 @@ int Butd::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* se
     cur_seq = seq_out; cur_logp = logp_out;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
     if (explicit_rng || !use_graphs) return sample_impl(feats, B, T, seq_out, logp_out, st);
-    const std::vector<uintptr_t> key = {2, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)T, (uintptr_t)seq_out, (uintptr_t)logp_out};
-    return run_cached(key, st, [&](hipStream_t s) { return sample_impl(feats, B, T, seq_out, logp_out, s); });
+    const std::vector<uintptr_t> key = {2, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)T, (uintptr_t)seq_out, (uintptr_t)logp_out, opt_bits()};
+    return gc.run(key, st, [&](hipStream_t s) { return sample_impl(feats, B, T, seq_out, logp_out, s); });
 }
 
 int Butd::sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st) {
@@ -193,11 +172,7 @@ int Butd::rollouts(const float* feats, int B, int T, const icz_rng* r, int64_t* 
     // <= 32 images: ONE chain of 2 B decoder rows (sample_chain with row0 = B) instead of two chains that each stream the weights
     const bool merged = B <= merge_small;
     ICZ_TRY(ensure_train(merged ? 2 * B : B, T));
-    if (!side_st) {
-        ICZ_CHECK_HIP(hipStreamCreateWithFlags(&side_st, hipStreamNonBlocking));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-    }
+    ICZ_TRY(side.ensure());
     rng = *r;
     hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
     mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_feats = feats;
@@ -206,8 +181,8 @@ int Butd::rollouts(const float* feats, int B, int T, const icz_rng* r, int64_t* 
     cur_seq = seq_out; cur_logp = logp_out;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
     if (explicit_rng || !use_graphs) return rollouts_impl(feats, B, T, ids_out, seq_out, logp_out, st);
-    const std::vector<uintptr_t> key = {4, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)T, (uintptr_t)ids_out, (uintptr_t)seq_out, (uintptr_t)logp_out};
-    return run_cached(key, st, [&](hipStream_t s) { return rollouts_impl(feats, B, T, ids_out, seq_out, logp_out, s); });
+    const std::vector<uintptr_t> key = {4, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)T, (uintptr_t)ids_out, (uintptr_t)seq_out, (uintptr_t)logp_out, opt_bits()};
+    return gc.run(key, st, [&](hipStream_t s) { return rollouts_impl(feats, B, T, ids_out, seq_out, logp_out, s); });
 }
 
 int Butd::rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int64_t* seq_out, float* logp_out, hipStream_t st) {
@@ -217,15 +192,15 @@ int Butd::rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int6
         ICZ_TRY(greedy_chain(feats, B, T, ids_out, nullptr, st, true));
         return sample_chain(feats, B, T, seq_out, logp_out, st);
     }
-    ICZ_CHECK_HIP(hipEventRecord(ev_fork, st));
-    ICZ_CHECK_HIP(hipStreamWaitEvent(side_st, ev_fork, 0));
+    ICZ_CHECK_HIP(hipEventRecord(side.fork[0], st));
+    ICZ_CHECK_HIP(hipStreamWaitEvent(side.st, side.fork[0], 0));
     // the sampled chain (the longer one: multinomial draw, dropout) is issued -- and captured -- first: when kernels of both chains are
     // ready the runtime then takes its first.  Measured round 4, three same-box rounds: rollouts 2.758 / 2.774 / 2.769 ms against
     // 2.783 / 2.785 / 2.806 ms with the greedy chain first (profiles/r04_chain_issue_order.log)
     const int ss = sample_chain(feats, B, T, seq_out, logp_out, st);
-    const int sg = greedy_chain(feats, B, T, ids_out, nullptr, side_st, true);
-    ICZ_CHECK_HIP(hipEventRecord(ev_join, side_st));       // always join, also on error (a capture must be closed)
-    ICZ_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0));
+    const int sg = greedy_chain(feats, B, T, ids_out, nullptr, side.st, true);
+    ICZ_CHECK_HIP(hipEventRecord(side.join[0], side.st));       // always join, also on error (a capture must be closed)
+    ICZ_CHECK_HIP(hipStreamWaitEvent(st, side.join[0], 0));
     return sg != ICZ_OK ? sg : ss;
 }
 
@@ -251,9 +226,9 @@ int Butd::sample_chain(const float* feats, int B, int T, int64_t* seq_out, float
         const size_t n = (size_t)Bs * H;
         hipLaunchKernelGGL(zero_bufs_kernel, dim3(cdiv((int)(n / 4), 256)), dim3(256), 0, st, z, n);
     }
-    hipLaunchKernelGGL(sample_init_kernel, dim3(cdiv(B > T ? B : T, 256)), dim3(256), 0, st, tb.unf, tb.nunf, tb.tok + row0, B, T);
+    hipLaunchKernelGGL(sample_init_kernel, dim3(cdiv(B > T ? B : T, 256)), dim3(256), 0, st, unf, nunf, tb.tok + row0, B, T);
     if (row0) hipLaunchKernelGGL(merged_init_kernel, dim3(cdiv(2 * B > T ? 2 * B : T, 256)), dim3(256), 0, st, tb.img2, B, tb.nany, T, tb.tok);
-    const int* const counts = row0 ? tb.nany : tb.nunf;           // what keeps a step alive
+    const int* const counts = row0 ? tb.nany : nunf;           // what keeps a step alive
     for (int t = 0; t < T; ++t) {
         int pns = 1;
         // step t > 0 is dead when no row was left unfinished by step t - 1 (the reference breaks out of its loop there, :233): every
@@ -267,12 +242,12 @@ int Butd::sample_chain(const float* feats, int B, int T, int64_t* seq_out, float
         }
         a.uniforms = rng.uniforms ? rng.uniforms + (size_t)t * B : nullptr;
         a.seed_p = d_seed; a.t = t; a.T = T;
-        a.unfinished = tb.unf; a.n_unfinished = tb.nunf;
-        a.live_rows = tb.live_rows;
+        a.unfinished = unf; a.n_unfinished = nunf;
+        a.live_rows = live_rows;
         a.seq_out = seq_out; a.logp_out = logp_out;
-        a.row0 = row0; a.ids_out = ids_out; a.g_unfinished = tb.gunf; a.n_any = tb.nany;
+        a.row0 = row0; a.ids_out = ids_out; a.g_unfinished = gunf; a.n_any = tb.nany;
         a.it_next = tb.tok + (size_t)(t + 1) * Bs;
-        a.draw_out = tb.draw + (size_t)t * Bs; a.lse_out = tb.lse + (size_t)t * Bs;
+        a.draw_out = draw + (size_t)t * Bs; a.lse_out = lse + (size_t)t * Bs;
         if (t + 1 < T) {             // the next step's input embedding, fused (step t + 1's slot and dropout stream)
             a.emb_table = P.embed_weight; a.emb_next = tb.emb + (size_t)(t + 1) * Bs * dims.E; a.E = dims.E;
             a.emb_drop = make_drop(d_seed, true, rng.emb_mask, (size_t)B * dims.E, RNG_EMB, t + 1);
@@ -286,22 +261,21 @@ int Butd::sample_chain(const float* feats, int B, int T, int64_t* seq_out, float
 }
 
 int Butd::sample_mask_sum(float* out, hipStream_t st) {
-    ICZ_REQUIRE(mode == 1, "butd: no rollout stored (call icz_butd_sample first)");
+    ICZ_TRY(require_mode(1, "butd"));
     ICZ_REQUIRE(out, "null output");
     // reuse the loss kernel with zero reward (coef scratch is overwritten later by backward)
-    ICZ_CHECK_HIP(hipMemsetAsync(tb.loss_rows, 0, sizeof(float) * cur_B * cur_T, st));
-    hipLaunchKernelGGL(reinforce_loss_kernel, dim3(1), dim3(256), 0, st, cur_logp, cur_seq, tb.loss_rows, cur_B, cur_T,
-                       (const float*)nullptr, tb.coef, (float*)nullptr, out);
+    ICZ_CHECK_HIP(hipMemsetAsync(loss_rows, 0, sizeof(float) * cur_B * cur_T, st));
+    hipLaunchKernelGGL(reinforce_loss_kernel, dim3(1), dim3(256), 0, st, cur_logp, cur_seq, loss_rows, cur_B, cur_T,
+                       (const float*)nullptr, coef, (float*)nullptr, out);
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
 
 int Butd::sample_backward(const float* reward, const icz_butd_params* G, float* loss_out, float* mask_sum_out,
                           float mask_sum_global, hipStream_t st) {
-    ICZ_REQUIRE(mode == 1, "butd: no rollout stored (call icz_butd_sample first)");
+    ICZ_TRY(require_mode(1, "butd"));
     ICZ_REQUIRE(reward && G, "butd sample_backward: null argument");
-    if (mask_sum_global >= 0.f)      // < 0: keep the device value set by icz_butd_set_mask_sum_global
-        hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, (uint64_t*)nullptr, (uint64_t)0, d_msum_global, mask_sum_global);
+    set_msum_global(mask_sum_global, st);      // < 0: keep the device value set by icz_butd_set_mask_sum_global
     mode = 0;   // the saved logits are consumed
     bptt_early_out = true;
     ICZ_TRY(bptt_prelude(st));      // outside the captured graph
@@ -313,14 +287,18 @@ int Butd::sample_backward(const float* reward, const icz_butd_params* G, float* 
     const float* const* gp = reinterpret_cast<const float* const*>(G);
     for (size_t i = 0; i < sizeof(icz_butd_params) / sizeof(float*); ++i) key.push_back((uintptr_t)gp[i]);
     const icz_butd_params Gc = *G;
-    if (!grad_cb) return run_cached(key, st, [&](hipStream_t s) { return sample_backward_impl(reward, Gc, loss_out, mask_sum_out, s); });
+    if (!grad_cb) {
+        key.push_back(opt_bits());
+        return gc.run(key, st, [&](hipStream_t s) { return sample_backward_impl(reward, Gc, loss_out, mask_sum_out, s); });
+    }
     // The DP hook must fire on every call (a replayed graph would not call it): the backward is cut at the three points where a
     // gradient group is complete, every piece is its own captured graph, and the hook is called between the replays -- the
     // all-reduce of a group then starts beside the remaining pieces exactly as in the eager form.
     for (int ph = 0; ph < 4; ++ph) {
         std::vector<uintptr_t> k2 = key;
         k2.push_back(0x100 + ph);
-        ICZ_TRY(run_cached(k2, st, [&](hipStream_t s) { return sample_backward_impl(reward, Gc, loss_out, mask_sum_out, s, 1 << ph, false); }));
+        k2.push_back(opt_bits());
+        ICZ_TRY(gc.run(k2, st, [&](hipStream_t s) { return sample_backward_impl(reward, Gc, loss_out, mask_sum_out, s, 1 << ph, false); }));
         if (ph < 3) grad_cb(grad_cb_user, ph);
     }
     return ICZ_OK;
@@ -328,58 +306,22 @@ int Butd::sample_backward(const float* reward, const icz_butd_params* G, float* 
 
 int Butd::sample_backward_impl(const float* reward, const icz_butd_params& G, float* loss_out, float* mask_sum_out, hipStream_t st,
                                int phases, bool fire_cb) {
-    const int B = cur_B, T = cur_T;
-    const int Vp = round4(dims.V);
-    if (phases & 1) {
-        hipLaunchKernelGGL(reinforce_loss_kernel, dim3(1), dim3(256), 0, st, cur_logp, cur_seq, reward, B, T, (const float*)d_msum_global,
-                           tb.coef, loss_out, mask_sum_out);
-        hipLaunchKernelGGL(reinforce_dlogits_kernel, dim3(cdiv(Vp, 256), T * cur_rows), dim3(256), 0, st, tb.logit, dims.V, Vp,
-                           tb.draw, tb.lse, tb.coef, B, T, cur_rows, cur_row0);
-        ICZ_CHECK_HIP(hipGetLastError());
-    }
+    if (phases & 1) ICZ_TRY(reinforce(reward, tb.logit, dims.V, round4(dims.V), loss_out, mask_sum_out, st, cur_rows, cur_row0));
     return bptt(G, st, phases, fire_cb);
 }
 
 // ------------------------------------------------------------------------------------------------
-__global__ void captions_to_tok_kernel(const int64_t* __restrict__ cap, int B, int L, int T, int64_t* __restrict__ tok) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;   // i = t*B + b
-    if (i >= T * B) return;
-    int t = i / B, b = i % B;
-    tok[i] = cap[(size_t)b * L + t];
-}
-__global__ void gather_packed_kernel(const float* __restrict__ logit, int V, int ldl, int B, const int* __restrict__ row_off,
-                                     const int* __restrict__ rows_t, int T, float* __restrict__ out) {
-    // grid (V/256, T*B): copy logits of active (t,b) to packed row row_off[t] + b
-    const int tb_ = blockIdx.y, t = tb_ / B, b = tb_ % B;
-    if (b >= rows_t[t]) return;
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v >= V) return;
-    out[(size_t)(row_off[t] + b) * V + v] = logit[(size_t)tb_ * ldl + v];
-}
-
 int Butd::xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r,
                      int train, float* packed_out, hipStream_t st) {
     ICZ_REQUIRE(feats && captions && lengths && B > 0 && L > 1, "butd xe_forward: bad arguments");
     int T = 0;
-    for (int b = 0; b < B; ++b) {
-        ICZ_REQUIRE(lengths[b] >= 1 && lengths[b] <= L - 1, "butd xe_forward: length %d out of range 1..%d", lengths[b], L - 1);
-        ICZ_REQUIRE(b == 0 || lengths[b] <= lengths[b - 1], "butd xe_forward: lengths must be sorted in decreasing order (Engine.py:179)");
-        if (lengths[b] > T) T = lengths[b];
-    }
+    ICZ_TRY(xe_steps("butd", lengths, B, L, &T));
     ICZ_TRY(ensure_train(B, T));
     if (r) rng = *r; else { rng = {}; }
     ICZ_REQUIRE(!train || r, "butd xe_forward: training mode needs an icz_rng");
-    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
-    mode = 2; cur_B = B; cur_T = T; cur_train = train != 0; cur_feats = feats;
+    begin_xe(lengths, B, T, L, captions, train != 0, rng.seed, st);
+    cur_feats = feats;
     cur_rows = B; cur_row0 = 0;
-    rows_t.assign(T, 0);
-    n_tokens = 0;
-    for (int t = 0; t < T; ++t) {
-        int c = 0;
-        for (int b = 0; b < B; ++b) c += lengths[b] > t;
-        rows_t[t] = c;
-        n_tokens += c;
-    }
     const size_t H = dims.H;
     const size_t Vp = round4(dims.V);
     ICZ_TRY(prologue(feats, B, st));
@@ -388,8 +330,7 @@ int Butd::xe_forward(const float* feats, const int64_t* captions, int B, int L, 
     ICZ_CHECK_HIP(hipMemsetAsync(tb.h2, 0, sizeof(float) * B * H, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tb.c2, 0, sizeof(float) * B * H, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tb.logit, 0, sizeof(float) * (size_t)T * B * Vp, st));
-    hipLaunchKernelGGL(captions_to_tok_kernel, dim3(cdiv(T * B, 256)), dim3(256), 0, st, captions, B, L, T, tb.tok);
-    cur_captions = captions; cur_L = L;
+    captions_to_tok(tb.tok, st);
     // Teacher forcing: no step needs the previous step's logits unless scheduled sampling draws from them -> one vocabulary projection
     // over all time steps after the loop (T B >= 128 rows: a single GEMM on the big-tile kernel instead of T decoder-step GEMMs)
     const bool batched_predict = ss_prob <= 0.f && T * B >= 128;
@@ -416,47 +357,15 @@ int Butd::xe_forward(const float* feats, const int64_t* captions, int B, int L, 
         g.M = T * B; g.N = dims.V; g.out = tb.logit; g.ldo = (int)Vp; g.bias = P.predict_b; g.nsplit = 1;
         ICZ_TRY(gemm_f32(GEMM_NT, g, st));
     }
-    if (packed_out) {
-        ICZ_TRY(upload_pack_index(st));
-        hipLaunchKernelGGL(gather_packed_kernel, dim3(cdiv(dims.V, 256), T * B), dim3(256), 0, st, tb.logit, dims.V, (int)Vp, B,
-                           tb.scalars_i, tb.scalars_i + T, T, packed_out);
-    }
+    if (packed_out) ICZ_TRY(gather_packed(tb.logit, dims.V, (int)Vp, packed_out, st));
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
-}
-
-// device copy of the packed-sequence index: row_off[t] (first packed row of step t) and rows_t[t]
-int Butd::upload_pack_index(hipStream_t st) {
-    const int T = cur_T;
-    std::vector<int> hostv(2 * T);
-    int acc = 0;
-    for (int t = 0; t < T; ++t) { hostv[t] = acc; hostv[T + t] = rows_t[t]; acc += rows_t[t]; }
-    ICZ_REQUIRE(tb.scalars_i && 2 * T <= tb.scalars_i_cap, "butd: pack index capacity");
-    ICZ_CHECK_HIP(hipMemcpyAsync(tb.scalars_i, hostv.data(), sizeof(int) * 2 * T, hipMemcpyHostToDevice, st));
-    ICZ_CHECK_HIP(hipStreamSynchronize(st));   // the host vector goes out of scope
-    return ICZ_OK;
-}
-
-__global__ void scatter_packed_kernel(const float* __restrict__ dpacked, int V, int ldl, int B, const int* __restrict__ row_off,
-                                      const int* __restrict__ rows_t, int T, float* __restrict__ logit) {
-    // inverse of gather_packed_kernel; inactive rows and pad columns become zero
-    const int tb_ = blockIdx.y, t = tb_ / B, b = tb_ % B;
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v >= ldl) return;
-    float g = 0.f;
-    if (b < rows_t[t] && v < V) g = dpacked[(size_t)(row_off[t] + b) * V + v];
-    logit[(size_t)tb_ * ldl + v] = g;
 }
 
 int Butd::xe_backward_dlogits(const float* dpacked, const icz_butd_params* G, hipStream_t st) {
-    ICZ_REQUIRE(mode == 2, "butd: no XE forward stored (call icz_butd_xe_forward first)");
+    ICZ_TRY(require_mode(2, "butd"));
     ICZ_REQUIRE(dpacked && G, "butd xe_backward_dlogits: null argument");
-    const int B = cur_B, T = cur_T;
-    const int Vp = round4(dims.V);
-    ICZ_TRY(upload_pack_index(st));
-    hipLaunchKernelGGL(scatter_packed_kernel, dim3(cdiv(Vp, 256), T * B), dim3(256), 0, st, dpacked, dims.V, Vp, B, tb.scalars_i,
-                       tb.scalars_i + T, T, tb.logit);
-    ICZ_CHECK_HIP(hipGetLastError());
+    ICZ_TRY(scatter_packed(dpacked, dims.V, round4(dims.V), tb.logit, st));
     mode = 0;
     bptt_early_out = false;
     ICZ_TRY(bptt_prelude(st));
@@ -469,13 +378,13 @@ __global__ void transpose_coef_kernel(const float* __restrict__ dlogp, int n, fl
 }
 
 int Butd::sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hipStream_t st) {
-    ICZ_REQUIRE(mode == 1, "butd: no rollout stored (call icz_butd_sample first)");
+    ICZ_TRY(require_mode(1, "butd"));
     ICZ_REQUIRE(dlogp && G, "butd sample_backward_dlogp: null argument");
     const int B = cur_B, T = cur_T;
     const int Vp = round4(dims.V);
-    ICZ_CHECK_HIP(hipMemcpyAsync(tb.coef, dlogp, sizeof(float) * B * T, hipMemcpyDeviceToDevice, st));
+    ICZ_CHECK_HIP(hipMemcpyAsync(coef, dlogp, sizeof(float) * B * T, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(reinforce_dlogits_kernel, dim3(cdiv(Vp, 256), T * cur_rows), dim3(256), 0, st, tb.logit, dims.V, Vp,
-                       tb.draw, tb.lse, tb.coef, B, T, cur_rows, cur_row0);
+                       draw, lse, coef, B, T, cur_rows, cur_row0);
     ICZ_CHECK_HIP(hipGetLastError());
     mode = 0;
     bptt_early_out = true;
@@ -484,23 +393,9 @@ int Butd::sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hi
 }
 
 int Butd::xe_backward(float smoothing, const icz_butd_params* G, float* loss_out, float n_tokens_global, hipStream_t st) {
-    ICZ_REQUIRE(mode == 2, "butd: no XE forward stored (call icz_butd_xe_forward first)");
+    ICZ_TRY(require_mode(2, "butd"));
     ICZ_REQUIRE(G, "butd xe_backward: null grads");
-    const int B = cur_B, T = cur_T;
-    const int Vp = round4(dims.V);
-    const float n = n_tokens_global > 0.f ? n_tokens_global : (float)n_tokens;
-    const float* n_dev = n_tokens_global < 0.f ? d_msum_global : nullptr;      // < 0: the device scalar handed over by *_set_*_global
-    ICZ_CHECK_HIP(hipMemsetAsync(tb.loss_rows, 0, sizeof(float) * T * B, st));
-    {
-        ICZ_REQUIRE(T <= XE_MAX_T, "xe_backward: %d steps exceed %d", T, XE_MAX_T);
-        XeRows xr = {};
-        for (int t = 0; t < T; ++t) xr.n[t] = rows_t[t];
-        hipLaunchKernelGGL(xe_loss_dlogits_kernel, dim3(B, T), dim3(256), 0, st, tb.logit, dims.V, Vp, cur_captions, cur_L, B, xr, smoothing, 1.0f / n, n_dev,
-                           tb.loss_rows);
-    }
-    if (loss_out) hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, st, tb.loss_rows, T * B, 1.0f / n, n_dev, loss_out);
-    ICZ_CHECK_HIP(hipGetLastError());
-    mode = 0;
+    ICZ_TRY(xe_loss(smoothing, n_tokens_global, tb.logit, dims.V, round4(dims.V), loss_out, st));
     bptt_early_out = false;
     ICZ_TRY(bptt_prelude(st));
     return bptt(*G, st);
@@ -569,21 +464,13 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     const float* feats = cur_feats;
     const size_t sH = (size_t)Bs * H;
     // backward of a sampled rollout: the GEMMs over all (t, b) rows stop behind the last step the rollout ran (GemmArgs::rows_live)
-    const int* const rl = (bptt_early_out && early_out) ? tb.live_rows : nullptr;
+    const int* const rl = (bptt_early_out && early_out) ? live_rows : nullptr;
 
     // ---- predict layer, all time steps at once.  d h2drop feeds the BPTT chain; the weight / bias gradients of
     //      `predict` depend only on dlogits, so they run on the side stream concurrently with the (skinny,
     //      latency-bound) BPTT chain and are joined at the end.
-    if (!low_st) {
-        int lo = 0, hi = 0;
-        ICZ_CHECK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));      // lo = least urgent
-        ICZ_CHECK_HIP(hipStreamCreateWithPriority(&low_st, hipStreamNonBlocking, lo));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_fork2, hipEventDisableTiming));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_join2, hipEventDisableTiming));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_fork3, hipEventDisableTiming));
-        ICZ_CHECK_HIP(hipEventCreateWithFlags(&ev_join3, hipEventDisableTiming));
-    }
-    hipEvent_t ev_fork = ev_fork2, ev_join = ev_join2;
+    ICZ_TRY(low.ensure(true));
+    hipEvent_t ev_fork = low.fork[0], ev_join = low.join[0];
     if (phases & 1) {
     bptt_joined = false;
     // The side branch is forked here (it depends on dlogits only) but ISSUED behind the d h2drop GEMM below, the head of the critical
@@ -591,8 +478,8 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     // 2.738 / 2.718 / 2.729 ms against 2.777 / 2.828 / 2.803 ms (profiles/r04_backward_issue_order.log); forking it behind the
     // product as well (no overlap with it at all): 2.762 / 2.779 / 2.750 ms.
     auto side_branch = [&]() -> int {
-        ICZ_CHECK_HIP(hipStreamWaitEvent(low_st, ev_fork, 0));
-        hipStream_t sb = concurrent ? low_st : st;   // low priority: the big GEMM only fills CUs the BPTT chain leaves idle
+        ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, ev_fork, 0));
+        hipStream_t sb = concurrent ? low.st : st;   // low priority: the big GEMM only fills CUs the BPTT chain leaves idle
         int s1 = wgrad(tb.logit, Vp, Vp, tb.h2d, H, H, TB, tb.dWp, H, sb, rl);
         hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(V, 32)), dim3(256), 0, sb, tb.logit, TB, V, (int)Vp, G.predict_b);
         hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, sb, tb.dWp, H, P.predict_v, P.predict_g, n_pred,
@@ -637,8 +524,8 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
         // REINFORCE backward of a sampled rollout: the steps behind the reference's break never ran (sample_chain) -- their kernels
         // return at entry, the producers of d gates / d dec / ds rows write zeros (the GEMMs over all steps read them), and the
         // first live step takes no carry from the dead one behind it
-        const int* const live = (bptt_early_out && early_out && t > 0) ? tb.nunf + (t - 1) : nullptr;
-        const int* const carry_live = (bptt_early_out && early_out && t + 1 < T) ? tb.nunf + t : nullptr;
+        const int* const live = (bptt_early_out && early_out && t > 0) ? nunf + (t - 1) : nullptr;
+        const int* const carry_live = (bptt_early_out && early_out && t + 1 < T) ? nunf + t : nullptr;
         DropCfg d_out = make_drop(d_seed, cur_train, rng.out_mask, (size_t)B * H, RNG_OUT, t);
         DropCfg d_att = make_drop(d_seed, cur_train, rng.att_mask, (size_t)B * R * A, RNG_ATT, t);
         DropCfg d_off = {0, nullptr, nullptr, 0, 0};
@@ -772,7 +659,7 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     // instead: slower, 2.73 - 2.75 ms; round 2 had issued such a branch FIRST and lost 0.25 ms).  With a callback the phases are
     // separate graphs and stay in line.
     const bool tail_side = phases == 0xF && !grad_cb && concurrent;
-    if (tail_side) ICZ_CHECK_HIP(hipEventRecord(ev_fork3, st));
+    if (tail_side) ICZ_CHECK_HIP(hipEventRecord(low.fork[1], st));
     bool tail_forked = false;
     hipStream_t const main_st = st;
     auto behind_loop = [&]() -> int {
@@ -824,9 +711,9 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     if ((phases & 4) && grad_cb && fire_cb) grad_cb(grad_cb_user, 2);
     if (phases & 8) {
     if (tail_side) {
-        ICZ_CHECK_HIP(hipStreamWaitEvent(low_st, ev_fork3, 0));
+        ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, low.fork[1], 0));
         tail_forked = true;
-        st = low_st;
+        st = low.st;
     }
     ICZ_TRY(wgrad(tb.dDec, A, A, tb.h1 + sH, H, H, TB, tb.dWdec, H, st));
     {   // d enc_ctx (sum over time) and the affine-weight partials, from the ds_t recorded by the loop
@@ -869,8 +756,8 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     st = main_st;
     // joins, also on an error (inside a capture an unjoined side stream would hide the original error behind a capture failure)
     if (tail_forked) {
-        ICZ_CHECK_HIP(hipEventRecord(ev_join3, low_st));
-        ICZ_CHECK_HIP(hipStreamWaitEvent(st, ev_join3, 0));
+        ICZ_CHECK_HIP(hipEventRecord(low.join[1], low.st));
+        ICZ_CHECK_HIP(hipStreamWaitEvent(st, low.join[1], 0));
     }
     if (((phases & 8) || s_tail != ICZ_OK) && !bptt_joined) {      // join the predict-gradient branch
         ICZ_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0));
@@ -925,11 +812,7 @@ int icz_butd_saved_alphas(icz_butd_t* h, float* alphas_out, void* stream) {
     return ICZ_OK;
 }
 int icz_butd_set_scheduled_sampling(icz_butd_t* h, float ss_prob, const float* gate_uniforms, const float* draw_uniforms) {
-    ICZ_REQUIRE(h, "icz_butd_set_scheduled_sampling: null handle");
-    ICZ_REQUIRE(ss_prob >= 0.f && ss_prob <= 1.f, "icz_butd_set_scheduled_sampling: ss_prob %g outside [0, 1]", (double)ss_prob);
-    Butd* b = reinterpret_cast<Butd*>(h);
-    b->ss_prob = ss_prob; b->ss_gate = gate_uniforms; b->ss_draw = draw_uniforms;
-    return ICZ_OK;
+    return set_scheduled_sampling("icz_butd_set_scheduled_sampling", reinterpret_cast<Butd*>(h), ss_prob, gate_uniforms, draw_uniforms);
 }
 int icz_butd_xe_forward(icz_butd_t* h, const float* feats, const int64_t* captions, int32_t B, int32_t L,
                         const int32_t* lengths_host, const icz_rng* rng, int32_t train, float* packed_logits_out,

@@ -1,0 +1,249 @@
+// Host-side machinery shared by the BUTD, AoA and NIC decoder handles: device allocations, the hipGraph cache, side
+// streams, the caption loss head (teacher-forced XE input, packed logits, XE / REINFORCE losses) and the beam-search driver.
+// Each rule below ("free => clear graphs", "zero-fill then sync") has this one owner.
+#pragma once
+#include <vector>
+#include <stdint.h>
+
+#include "beam_kernels.h"
+#include "butd_kernels.h"
+#include "gemm_f32.h"
+
+namespace icz {
+
+void gemm_set_capturing(bool on);
+bool gemm_prof_on();                  // gemm_f32.hip: event timing active (graphs captured now contain event nodes)
+
+// hipGraph cache: a whole rollout / backward is ~300-700 launches of 2-30 us kernels; replaying a captured graph removes the
+// per-launch host cost and shrinks the inter-kernel gaps.  Capture on first use of a key, replay afterwards.  The key holds every
+// pointer / size / option baked into the captured kernel arguments, so it only pays when the caller reuses its buffers (the Engine does).
+struct GraphCache {
+    struct Entry { std::vector<uintptr_t> key; hipGraphExec_t exec; uint64_t last_use; };
+    explicit GraphCache(size_t capacity) : capacity(capacity) {}
+    GraphCache(const GraphCache&) = delete;
+    GraphCache& operator=(const GraphCache&) = delete;
+    ~GraphCache() {
+        clear();
+        if (cap_st) (void)hipStreamDestroy(cap_st);
+    }
+    void clear() {                    // captured kernel arguments hold parameter / buffer addresses: drop them when those change
+        for (auto& e : graphs) (void)hipGraphExecDestroy(e.exec);
+        graphs.clear();
+    }
+    template <class F>
+    int run(std::vector<uintptr_t> key, hipStream_t st, F&& fn) {
+        ++tick;
+        key.push_back((gemm_prof_on() ? 1 : 0) + 2 * (uintptr_t)(gemm_big_switch() + 2));      // the tile-configuration override changes the captured launches
+        for (auto& e : graphs)
+            if (e.key == key) {
+                e.last_use = tick;
+                ICZ_CHECK_HIP(hipGraphLaunch(e.exec, st));
+                return ICZ_OK;
+            }
+        if (!cap_st) ICZ_CHECK_HIP(hipStreamCreateWithFlags(&cap_st, hipStreamNonBlocking));
+        ICZ_CHECK_HIP(hipStreamBeginCapture(cap_st, hipStreamCaptureModeThreadLocal));
+        gemm_set_capturing(true);
+        const int status = fn(cap_st);
+        gemm_set_capturing(false);
+        hipGraph_t g = nullptr;
+        hipError_t ce = hipStreamEndCapture(cap_st, &g);
+        if (status != ICZ_OK) { if (g) (void)hipGraphDestroy(g); return status; }
+        if (ce != hipSuccess || !g) { set_error("hipStreamEndCapture failed: %s", hipGetErrorString(ce)); return ICZ_ERR_HIP; }
+        hipGraphExec_t exec = nullptr;
+        hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        if (ie != hipSuccess) { set_error("hipGraphInstantiate failed: %s", hipGetErrorString(ie)); return ICZ_ERR_HIP; }
+        if (graphs.size() >= capacity) {      // evict the least recently used entry
+            size_t lru = 0;
+            for (size_t i = 1; i < graphs.size(); ++i) if (graphs[i].last_use < graphs[lru].last_use) lru = i;
+            (void)hipGraphExecDestroy(graphs[lru].exec);
+            graphs.erase(graphs.begin() + lru);
+        }
+        graphs.push_back({key, exec, tick});
+        ICZ_CHECK_HIP(hipGraphLaunch(exec, st));
+        return ICZ_OK;
+    }
+    std::vector<Entry> graphs;
+    size_t capacity;
+    hipStream_t cap_st = nullptr;
+    uint64_t tick = 0;
+};
+
+// Owner of a handle's device allocations: a persistent list and a training list (grown on demand).  Every allocation is
+// zero-filled on the NULL stream; callers enqueue on NON-BLOCKING streams (torch's), which are not ordered behind it, so each
+// growth ends with synced(): without it a kernel of the first call after a (re)allocation could run BEFORE the zero-fill of its
+// buffer and then be wiped by it (round 5: sample_init_kernel's unfinished flags, seen as an all-zero rollout in 1 of 3 five-rank runs).
+struct DeviceBuffers {
+    std::vector<void*> persistent, training;
+    bool to_training = false;        // alloc() target while a TrainingScope is alive
+    struct TrainingScope {
+        DeviceBuffers& m;
+        explicit TrainingScope(DeviceBuffers& x) : m(x) { m.to_training = true; }
+        ~TrainingScope() { m.to_training = false; }
+    };
+    DeviceBuffers() = default;
+    DeviceBuffers(const DeviceBuffers&) = delete;
+    DeviceBuffers& operator=(const DeviceBuffers&) = delete;
+    ~DeviceBuffers() {
+        for (void* p : training) (void)hipFree(p);
+        for (void* p : persistent) (void)hipFree(p);
+    }
+    int alloc(void** p, size_t bytes) {
+        if (!bytes) bytes = 16;
+        ICZ_CHECK_HIP(hipMalloc(p, bytes));
+        ICZ_CHECK_HIP(hipMemset(*p, 0, bytes));
+        (to_training ? training : persistent).push_back(*p);
+        return ICZ_OK;
+    }
+    int synced() {
+        ICZ_CHECK_HIP(hipDeviceSynchronize());
+        return ICZ_OK;
+    }
+    // sync -> clear the graph cache -> free: the captured graphs carry the freed addresses in their kernel arguments
+    int release_training(GraphCache* gc) {
+        if (training.empty()) return ICZ_OK;
+        ICZ_CHECK_HIP(hipDeviceSynchronize());
+        if (gc) gc->clear();
+        for (void* p : training) (void)hipFree(p);
+        training.clear();
+        return ICZ_OK;
+    }
+};
+
+// A stream for work beside the caller's stream and its fork / join events (two pairs: the backward passes fork twice),
+// created lazily -- outside any capture -- by ensure().
+struct SideStream {
+    hipStream_t st = nullptr;
+    hipEvent_t fork[2] = {}, join[2] = {};
+    SideStream() = default;
+    SideStream(const SideStream&) = delete;
+    SideStream& operator=(const SideStream&) = delete;
+    ~SideStream() {
+        if (st) (void)hipStreamDestroy(st);
+        for (int i = 0; i < 2; ++i) {
+            if (fork[i]) (void)hipEventDestroy(fork[i]);
+            if (join[i]) (void)hipEventDestroy(join[i]);
+        }
+    }
+    int ensure(bool lowest_priority = false) {
+        if (st) return ICZ_OK;
+        if (lowest_priority) {
+            int lo = 0, hi = 0;
+            ICZ_CHECK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));      // lo = least urgent
+            ICZ_CHECK_HIP(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, lo));
+        } else {
+            ICZ_CHECK_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        }
+        for (int i = 0; i < 2; ++i) {
+            ICZ_CHECK_HIP(hipEventCreateWithFlags(&fork[i], hipEventDisableTiming));
+            ICZ_CHECK_HIP(hipEventCreateWithFlags(&join[i], hipEventDisableTiming));
+        }
+        return ICZ_OK;
+    }
+};
+
+// The caption loss head: host-side state of a stored training-mode forward pass and the loss buffers of all three decoders.
+struct CaptionHead {
+    int mode = 0;                 // 0 none, 1 sample rollout stored, 2 XE forward stored
+    int cur_B = 0, cur_T = 0, cur_L = 0, n_tokens = 0;
+    bool cur_train = false;
+    const int64_t* cur_seq = nullptr; const float* cur_logp = nullptr; const int64_t* cur_captions = nullptr;
+    std::vector<int> rows_t;      // active rows per step of the XE batch (lengths sorted in decreasing order)
+    float ss_prob = 0.f;          // scheduled sampling in xe_forward (icz_*_set_scheduled_sampling)
+    const float* ss_gate = nullptr; const float* ss_draw = nullptr;      // explicit [T, B] uniforms (device) or Philox
+    uint64_t* d_seed = nullptr;   // Philox seed of the current training-mode call (device resident)
+    float* d_msum = nullptr;      // data-parallel loss normaliser (0 = use the local one)
+    // training buffers (alloc_loss_buffers): TB = steps x rows
+    float *coef = nullptr, *lse = nullptr, *loss_rows = nullptr;
+    int32_t* draw = nullptr;
+    uint8_t* unf = nullptr; int* nunf = nullptr;
+    uint8_t* gunf = nullptr; int* gnunf = nullptr;     // the same for the greedy baseline of an SCST step
+    int* live_rows = nullptr;     // (steps the sampled rollout ran) x B: row limit of the backward pass's batched GEMMs
+    int* pack_idx = nullptr; int pack_cap = 0;         // packed-sequence index: row_off[T] | rows_t[T]
+
+    int alloc_scalars(DeviceBuffers& m);
+    int alloc_loss_buffers(DeviceBuffers& m, size_t TB, size_t B, size_t T);
+    void drop_loss_buffers();     // the training list was released: forget its pointers
+    int require_mode(int want, const char* who) const;
+    // teacher-forced XE input: lengths checked (per-model prefix `who`), T = the longest
+    static int xe_steps(const char* who, const int32_t* lengths, int B, int L, int* T_out);
+    // the state of an XE forward pass (rows_t, n_tokens) and the Philox seed upload
+    void begin_xe(const int32_t* lengths, int B, int T, int L, const int64_t* captions, bool train, uint64_t seed, hipStream_t st);
+    void captions_to_tok(int64_t* tok, hipStream_t st) const;
+    // logits [T B, ldl] <-> packed rows [n_tokens, V] through the packed-sequence index
+    int gather_packed(const float* logit, int V, int ldl, float* packed_out, hipStream_t st);
+    int scatter_packed(const float* dpacked, int V, int ldl, float* logit, hipStream_t st);
+    // LabelSmoothingLoss: loss and dlogits (in place) of the stored XE forward pass
+    int xe_loss(float smoothing, float n_tokens_global, float* logits, int V, int ldl, float* loss_out, hipStream_t st);
+    // REINFORCE: loss, mask sum and dlogits (in place) of the stored rollout; rows / row0: rows per step slot and the first of the
+    // sampled rollout's (a merged SCST chain stores 2 B rows per slot)
+    int reinforce(const float* reward, float* logits, int V, int ldl, float* loss_out, float* msum_out, hipStream_t st, int rows = 0, int row0 = 0);
+    void set_msum_global(float msum_global, hipStream_t st) const;       // < 0: keep the device value handed over by icz_*_set_norm_global
+    int upload_pack_index(hipStream_t st);
+};
+
+// Beam-search buffers and the step loop shared by the decoders.
+struct BeamBuf {
+    int cap_rows = 0, cap_L = 0;
+    int* n_act = nullptr; float* run = nullptr; int32_t* seqs[2] = {nullptr, nullptr};
+    int32_t *src_row = nullptr, *img_of_row = nullptr, *best_seq = nullptr;
+    float* best_score = nullptr; int *best_len = nullptr, *has_complete = nullptr, *n_live = nullptr, *n_live_host = nullptr;
+    float* feat_rows = nullptr;       // NIC: image embedding replicated per beam row
+    float* cand_val = nullptr; int* cand_idx = nullptr;     // [rows, BEAM_MAX_K] per-row candidates of one step
+    BeamBuf() = default;
+    BeamBuf(const BeamBuf&) = delete;
+    BeamBuf& operator=(const BeamBuf&) = delete;
+    ~BeamBuf() { if (n_live_host) (void)hipHostFree(n_live_host); }
+
+    static int check(const char* who, int n_img, int k, int max_steps, int max_rows);
+    int ensure(DeviceBuffers& m, int max_rows, int L, int extra_feat_cols = 0);
+    int begin(int n_img, int k, int L, int64_t* it, hipStream_t st);       // scores, live counts and the <sta> rows of every image
+    // The step loop (DecoderRNN.beam_search_sample, BUTD_Model.py:236-318, batched over images): step(step_no, compact) runs the
+    // decoder on `it` into `logits`; then a row-top-k, the per-image merge and gather(compact) re-gathering the model state by
+    // source row; every few steps one 4-byte read-back asks whether any image still has live beams.  compact_first: step 1 runs
+    // one decoder row per image (the k rows of an image are identical and only row 0 is scored, :273-274).
+    template <class Step, class Gather>
+    int search(int n_img, int k, int max_steps, bool compact_first, const float* logits, int V, int ldl, int64_t* it, float* seqs_out,
+               int32_t* lens_out, hipStream_t st, Step&& step, Gather&& gather) {
+        const int rows = n_img * k, L = max_steps + 1;
+        int sb = 0, steps_done = 0;
+        for (int s = 1; s <= max_steps; ++s) {
+            const bool compact = compact_first && s == 1 && k > 1;
+            ICZ_TRY(step(s, compact));
+            BeamArgs a = {logits, V, ldl, k, s, L, n_act, run, seqs[sb], seqs[sb ^ 1], src_row, it, best_score, best_len, best_seq,
+                          has_complete, n_live + s};
+            launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)n_act, (const float*)run, cand_val, cand_idx,
+                                compact ? 1 : 0);
+            hipLaunchKernelGGL(beam_merge_kernel, dim3(n_img), dim3(64), 0, st, a, (const float*)cand_val, (const int*)cand_idx);
+            gather(compact);
+            sb ^= 1;
+            steps_done = s;
+            if (s >= 6 && (s % 3) == 0 && s < max_steps) {
+                ICZ_CHECK_HIP(hipMemcpyAsync(n_live_host, n_live + s, sizeof(int), hipMemcpyDeviceToHost, st));
+                ICZ_CHECK_HIP(hipStreamSynchronize(st));
+                if (n_live_host[0] == 0) break;
+            }
+        }
+        hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_act, run, seqs[sb], has_complete,
+                           best_len, best_seq, seqs_out, lens_out);
+        ICZ_CHECK_HIP(hipGetLastError());
+        return ICZ_OK;
+    }
+};
+
+// C ABI helpers (butd.hip, aoa.hip, nic.hip)
+template <class Handle, class Dims, class Opaque>
+int abi_create(const char* who, const Dims* dims, Opaque** out) {
+    ICZ_REQUIRE(dims && out, "%s: null argument", who);
+    Handle* h = new Handle();
+    const int s = h->init(*dims);
+    if (s != ICZ_OK) { delete h; return s; }
+    *out = reinterpret_cast<Opaque*>(h);
+    return ICZ_OK;
+}
+// every parameter pointer non-null and 16-byte aligned (bit i of `unaligned_ok`: parameter i may be unaligned)
+int check_param_table(const char* who, const void* params, size_t bytes, uint32_t unaligned_ok = 0);
+int set_scheduled_sampling(const char* who, CaptionHead* h, float ss_prob, const float* gate, const float* draw);
+int set_norm_global(const char* who, CaptionHead* h, const float* norm_dev, void* stream);
+
+}  // namespace icz

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gemm_f32.h"
+#include "butd_kernels.h"      // slab_reduce_kernel (icz_gemm_f32)
 
 namespace icz {
 
@@ -1337,5 +1338,66 @@ int icz_prof_select(int32_t which) {
 }
 int icz_prof_end(double* avg_us, double* bytes_per_launch, double* flops_per_launch, long long* launches) {
     return icz::gemm_prof_end(avg_us, bytes_per_launch, flops_per_launch, launches);
+}
+
+// ---- the GEMM entries of the C ABI
+using namespace icz;
+static constexpr int ABI_TARGET_WGS = 512;     // ~2 workgroups per CU on 256 CUs (the decoders' TARGET_WGS)
+
+size_t icz_gemm_workspace_floats(int32_t M, int32_t N) {
+    const size_t base = (size_t)ABI_TARGET_WGS * 4096 * 2 + (size_t)M * N;
+    // 65..128 rows: the 128-row resident kernel leaves up to 32 slabs of M x N (one per 256-deep k range of K <= 8192)
+    const size_t m128 = (M > 64 && M <= 128) ? (size_t)32 * M * N : 0;
+    return base > m128 ? base : m128;
+}
+
+int icz_gemm_f32(int32_t layout, const float* X, int32_t ldx, const float* W, int32_t ldw, const float* bias,
+                 float* C, int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t nsplit, float* workspace,
+                 size_t workspace_floats, void* stream) {
+    ICZ_REQUIRE(layout >= 0 && layout <= 2, "icz_gemm_f32: layout %d", layout);
+    GemmArgs g = {};
+    g.nseg = 1;
+    g.seg[0] = {X, W, ldx, ldw, K, nullptr};
+    g.M = M; g.N = N; g.out = C; g.ldo = ldc; g.bias = bias;
+    g.nsplit = nsplit > 0 ? nsplit : gemm_fit_split((GemmLayout)layout, g, gemm_pick_split(g, ABI_TARGET_WGS, (GemmLayout)layout), workspace_floats);
+    g.nsplit = gemm_normalize_split((GemmLayout)layout, g, g.nsplit);   // no empty splits
+    hipStream_t st = (hipStream_t)stream;
+    if (g.nsplit > 1) {
+        ICZ_REQUIRE(workspace, "icz_gemm_f32: split-K needs a workspace");
+        ICZ_REQUIRE(gemm_slab_floats(M, N, g.nsplit) <= workspace_floats, "icz_gemm_f32: workspace of %zu floats too small for %d slabs of %dx%d", workspace_floats, g.nsplit, M, N);
+        ICZ_REQUIRE(ldc == N, "icz_gemm_f32: split-K path needs ldc == N");
+        g.out = workspace; g.bias = nullptr;
+        ICZ_TRY(gemm_f32((GemmLayout)layout, g, st));
+        size_t MN = (size_t)M * N;
+        ICZ_REQUIRE(MN % 4 == 0, "icz_gemm_f32: M*N must be a multiple of 4 for the split-K reduce");
+        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, workspace, g.nsplit, MN, N, bias, C);
+        ICZ_CHECK_HIP(hipGetLastError());
+        return ICZ_OK;
+    }
+    return gemm_f32((GemmLayout)layout, g, st);
+}
+
+int icz_gemm_set_big_cfg(int32_t cfg) {
+    ICZ_REQUIRE(cfg >= -2 && cfg <= 5, "icz_gemm_set_big_cfg: %d", cfg);
+    gemm_set_big_cfg(cfg);
+    return ICZ_OK;
+}
+
+int icz_gemm_big_cfg_for(int32_t layout, int32_t M, int32_t N, int32_t K, int32_t nsplit) {
+    if (layout < 0 || layout > 2 || M <= 0 || N <= 0 || K <= 0) return -1;
+    GemmArgs g = {};
+    g.nseg = 1;
+    g.seg[0].K = K;
+    g.M = M; g.N = N; g.nsplit = nsplit > 0 ? nsplit : 1;
+    return gemm_big_cfg((GemmLayout)layout, g);
+}
+
+int icz_gemm_tn_grouped(const float* dY, int32_t ldy, int32_t M, int32_t K, int32_t ngroups, const float* const* X, const int32_t* ldx,
+                        const int32_t* cols, float* const* out, const int32_t* ldo, const int32_t* rows_live, void* stream) {
+    ICZ_REQUIRE(ngroups >= 1 && ngroups <= GEMM_MAX_COLGROUPS && X && ldx && cols && out && ldo, "icz_gemm_tn_grouped: bad arguments");
+    GemmColGroup g[GEMM_MAX_COLGROUPS];
+    for (int j = 0; j < ngroups; ++j) g[j] = {X[j], ldx[j], cols[j], out[j], ldo[j]};
+    ICZ_REQUIRE(gemm_tn_grouped_fits(M, K, g, ngroups), "icz_gemm_tn_grouped: shape not taken (M %d, K %d)", M, K);
+    return gemm_tn_grouped(dY, ldy, M, K, g, ngroups, rows_live, (hipStream_t)stream);
 }
 }

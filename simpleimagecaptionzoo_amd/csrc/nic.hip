@@ -5,17 +5,16 @@
 
 #include <vector>
 
-#include "beam_kernels.h"
 #include "butd_impl.h"
 
 namespace icz {
 
-struct Nic {
+struct Nic : CaptionHead {
     static constexpr int STEP_WGS = 256, TARGET_WGS = 512, ARGMAX_PARTS = 8;
     icz_nic_dims dims;
     icz_nic_params P;
     bool bound = false, fresh = false;
-    std::vector<void*> allocs;
+    DeviceBuffers mem;
     int Vp = 0;
     float *w_pred = nullptr, *n_pred = nullptr, *zeros = nullptr;
     float *h[2], *c[2];
@@ -23,37 +22,18 @@ struct Nic {
     size_t ws_floats = 0;
     int64_t* it = nullptr;
     float* amax_val = nullptr; int* amax_idx = nullptr;
-    uint64_t* d_seed = nullptr; float* d_msum = nullptr;
-    float ss_prob = 0.f; const float* ss_gate = nullptr; const float* ss_draw = nullptr;      // scheduled sampling in xe_forward
     // training buffers (slot stride = capacity rows): th/tc slot 0 = zeros, slot 1 = after the image step, slot t+2 =
     // after token step t; tg / dG slot 0 = image step, slot t+1 = token step t
     int tcap_B = 0, tcap_T = 0;          // capacity of the training buffers (grown on demand by ensure_train)
-    std::vector<void*> tallocs; bool alloc_train = false;
     int64_t* tok = nullptr;
     float *th = nullptr, *tc = nullptr, *temb = nullptr, *tg = nullptr, *thd = nullptr, *tlogit = nullptr;
     float *dG = nullptr, *dHd = nullptr, *dEmb = nullptr, *dcb[2] = {nullptr, nullptr}, *X = nullptr, *dWp = nullptr;
-    float *coef = nullptr, *lse = nullptr, *loss_rows = nullptr;
-    int32_t* draw = nullptr; uint8_t* unf = nullptr; int* nunf = nullptr; int* pack_idx = nullptr;
     size_t xfloats = 0;
     BeamBuf bm;
     icz_rng rng = {};
-    int mode = 0, cur_B = 0, cur_T = 0, cur_L = 0, n_tokens = 0;
-    bool cur_train = false;
-    const float* cur_feats = nullptr; const int64_t* cur_seq = nullptr; const float* cur_logp = nullptr;
-    const int64_t* cur_captions = nullptr;
-    std::vector<int> rows_t;
+    const float* cur_feats = nullptr;
 
-    ~Nic() {
-        if (bm.n_live_host) (void)hipHostFree(bm.n_live_host);
-        for (void* p : tallocs) (void)hipFree(p);
-        for (void* p : allocs) (void)hipFree(p);
-    }
-    int alloc(void** p, size_t bytes) {
-        ICZ_CHECK_HIP(hipMalloc(p, bytes ? bytes : 16));
-        ICZ_CHECK_HIP(hipMemset(*p, 0, bytes ? bytes : 16));
-        (alloc_train ? tallocs : allocs).push_back(*p);
-        return ICZ_OK;
-    }
+    int alloc(void** p, size_t bytes) { return mem.alloc(p, bytes); }
     int init(const icz_nic_dims& d);
     int refresh(hipStream_t st);
     int image_step(const float* feats, int rows, float* h_out, float* c_out, float* gates_out, hipStream_t st);
@@ -91,8 +71,7 @@ int Nic::init(const icz_nic_dims& d) {
     ICZ_TRY(alloc((void**)&it, sizeof(int64_t) * rows));
     ICZ_TRY(alloc((void**)&amax_val, sizeof(float) * rows * ARGMAX_PARTS));
     ICZ_TRY(alloc((void**)&amax_idx, sizeof(int) * rows * ARGMAX_PARTS));
-    ICZ_TRY(alloc((void**)&d_seed, 16));
-    ICZ_TRY(alloc((void**)&d_msum, 16));
+    ICZ_TRY(alloc_scalars(mem));
     const size_t nmax = 4 * H > (size_t)Vp ? 4 * H : (size_t)Vp;
     ws_floats = (size_t)TARGET_WGS * 4096 * 2 + rows * nmax;
     {   // the resident decoder-step GEMM (33..128 rows) leaves one slab per 256-deep k range of K = E + H (Butd::init's rule)
@@ -101,8 +80,7 @@ int Nic::init(const icz_nic_dims& d) {
         if (need > ws_floats) ws_floats = need;
     }
     ICZ_TRY(alloc((void**)&ws, sizeof(float) * ws_floats));
-    ICZ_CHECK_HIP(hipDeviceSynchronize());      // alloc() zero-fills on the NULL stream; callers use non-blocking streams (see ensure_train)
-    return ICZ_OK;
+    return mem.synced();
 }
 
 int Nic::refresh(hipStream_t st) {
@@ -185,13 +163,12 @@ int Nic::ensure_train(int Bq, int Tq) {
     if (tcap_B > Bq) Bq = tcap_B;
     if (tcap_T > Tq) Tq = tcap_T;
     if (dims.max_len > Tq) Tq = dims.max_len;
-    if (!tallocs.empty()) {
-        ICZ_CHECK_HIP(hipDeviceSynchronize());
-        for (void* p : tallocs) (void)hipFree(p);
-        tallocs.clear();
-        tcap_B = tcap_T = 0; mode = 0;
+    if (!mem.training.empty()) {
+        ICZ_TRY(mem.release_training(nullptr));
+        tcap_B = tcap_T = 0;
+        drop_loss_buffers();
     }
-    struct Scope { bool& f; Scope(bool& x) : f(x) { f = true; } ~Scope() { f = false; } } scope(alloc_train);
+    DeviceBuffers::TrainingScope scope(mem);
     const size_t B = Bq, T = Tq, H = dims.H, E = dims.E;
     const size_t TB = T * B;
     ICZ_TRY(alloc((void**)&tok, sizeof(int64_t) * (TB + B)));
@@ -209,17 +186,8 @@ int Nic::ensure_train(int Bq, int Tq) {
     xfloats = (size_t)TARGET_WGS * 4096 * 2 + B * H;
     ICZ_TRY(alloc((void**)&X, sizeof(float) * xfloats));
     ICZ_TRY(alloc((void**)&dWp, sizeof(float) * (size_t)Vp * H));
-    ICZ_TRY(alloc((void**)&coef, sizeof(float) * TB));
-    ICZ_TRY(alloc((void**)&lse, sizeof(float) * TB));
-    ICZ_TRY(alloc((void**)&loss_rows, sizeof(float) * TB));
-    ICZ_TRY(alloc((void**)&draw, sizeof(int32_t) * TB));
-    ICZ_TRY(alloc((void**)&unf, B));
-    ICZ_TRY(alloc((void**)&nunf, sizeof(int) * T));
-    ICZ_TRY(alloc((void**)&pack_idx, sizeof(int) * 2 * T));
-    // The hipMemset calls above run on the NULL stream; callers enqueue on NON-BLOCKING streams (torch's), which are not ordered behind
-    // it: without this, a kernel of the first call after a (re)allocation could run BEFORE the zero-fill of its buffer and then be
-    // wiped by it (round 5: sample_init_kernel's unfinished flags, seen as an all-zero rollout in 1 of 3 five-rank runs).
-    ICZ_CHECK_HIP(hipDeviceSynchronize());
+    ICZ_TRY(alloc_loss_buffers(mem, TB, B, T));
+    ICZ_TRY(mem.synced());
     tcap_B = Bq; tcap_T = Tq;
     return ICZ_OK;
 }
@@ -268,29 +236,13 @@ int Nic::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq
 
 int Nic::sample_backward(const float* reward, const icz_nic_params* G, float* dfeats, float* loss_out, float* msum_out, float msum_global,
                          hipStream_t st) {
-    ICZ_REQUIRE(mode == 1, "nic: no rollout stored (call icz_nic_sample first)");
+    ICZ_TRY(require_mode(1, "nic"));
     ICZ_REQUIRE(reward && G, "nic sample_backward: null argument");
-    const int B = cur_B, T = cur_T;
-    if (msum_global >= 0.f)      // < 0: keep the device value handed over by icz_nic_set_norm_global
-        hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, (uint64_t*)nullptr, (uint64_t)0, d_msum, msum_global);
-    hipLaunchKernelGGL(reinforce_loss_kernel, dim3(1), dim3(256), 0, st, cur_logp, cur_seq, reward, B, T, (const float*)d_msum, coef, loss_out, msum_out);
-    hipLaunchKernelGGL(reinforce_dlogits_kernel, dim3(cdiv(Vp, 256), T * B), dim3(256), 0, st, tlogit, dims.V, Vp, draw, lse, coef, B, T);
+    set_msum_global(msum_global, st);      // < 0: keep the device value handed over by icz_nic_set_norm_global
+    ICZ_TRY(reinforce(reward, tlogit, dims.V, Vp, loss_out, msum_out, st));
     mode = 0;
     bptt_early_out = true;
     return bptt(*G, dfeats, st);
-}
-
-__global__ void nic_captions_to_tok_kernel(const int64_t* __restrict__ cap, int B, int L, int T, int64_t* __restrict__ tok) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= T * B) return;
-    tok[i] = cap[(size_t)(i % B) * L + i / B];
-}
-__global__ void nic_gather_packed_kernel(const float* __restrict__ logit, int V, int ldl, int B, const int* __restrict__ row_off,
-                                         const int* __restrict__ rows_t, float* __restrict__ out) {
-    const int tb_ = blockIdx.y, t = tb_ / B, b = tb_ % B;
-    if (b >= rows_t[t]) return;
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    if (v < V) out[(size_t)(row_off[t] + b) * V + v] = logit[(size_t)tb_ * ldl + v];
 }
 
 int Nic::xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r, int train,
@@ -299,28 +251,16 @@ int Nic::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
     ICZ_REQUIRE(fresh, "nic: call icz_nic_refresh_weights after binding/updating parameters");
     ICZ_REQUIRE(!train || r, "nic xe_forward: training mode needs an icz_rng");
     int T = 0;
-    for (int b = 0; b < B; ++b) {
-        ICZ_REQUIRE(lengths[b] >= 1 && lengths[b] <= L - 1, "nic xe_forward: length %d out of range 1..%d", lengths[b], L - 1);
-        ICZ_REQUIRE(b == 0 || lengths[b] <= lengths[b - 1], "nic xe_forward: lengths must be sorted in decreasing order");
-        if (lengths[b] > T) T = lengths[b];
-    }
+    ICZ_TRY(xe_steps("nic", lengths, B, L, &T));
     ICZ_TRY(ensure_train(B, T));
     if (r) rng = *r; else rng = {};
-    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
-    mode = 2; cur_B = B; cur_T = T; cur_L = L; cur_train = train != 0; cur_feats = feats; cur_captions = captions;
-    rows_t.assign(T, 0);
-    n_tokens = 0;
-    for (int t = 0; t < T; ++t) {
-        int cnt = 0;
-        for (int b = 0; b < B; ++b) cnt += lengths[b] > t;
-        rows_t[t] = cnt;
-        n_tokens += cnt;
-    }
+    begin_xe(lengths, B, T, L, captions, train != 0, rng.seed, st);
+    cur_feats = feats;
     const size_t H = dims.H, E = dims.E, sH = (size_t)B * H;
     ICZ_CHECK_HIP(hipMemsetAsync(th, 0, sizeof(float) * sH, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tc, 0, sizeof(float) * sH, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tlogit, 0, sizeof(float) * (size_t)T * B * Vp, st));
-    hipLaunchKernelGGL(nic_captions_to_tok_kernel, dim3(cdiv(T * B, 256)), dim3(256), 0, st, captions, B, L, T, tok);
+    captions_to_tok(tok, st);
     ICZ_TRY(image_step(feats, B, th + sH, tc + sH, tg, st));
     for (int t = 0; t < T; ++t) {
         const size_t slot = (size_t)t * B;
@@ -330,35 +270,15 @@ int Nic::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
                            tc + (slot + 2 * B) * H, temb + slot * E, tg + (slot + B) * 4 * H, thd + slot * H, tlogit + slot * Vp,
                            nic_drop(d_seed, train != 0, rng.out_mask, sH, t), st));
     }
-    if (packed_out) {
-        std::vector<int> hostv(2 * T);
-        int acc = 0;
-        for (int t = 0; t < T; ++t) { hostv[t] = acc; hostv[T + t] = rows_t[t]; acc += rows_t[t]; }
-        ICZ_CHECK_HIP(hipMemcpyAsync(pack_idx, hostv.data(), sizeof(int) * 2 * T, hipMemcpyHostToDevice, st));
-        ICZ_CHECK_HIP(hipStreamSynchronize(st));
-        hipLaunchKernelGGL(nic_gather_packed_kernel, dim3(cdiv(dims.V, 256), T * B), dim3(256), 0, st, tlogit, dims.V, Vp, B, pack_idx,
-                           pack_idx + T, packed_out);
-    }
+    if (packed_out) ICZ_TRY(gather_packed(tlogit, dims.V, Vp, packed_out, st));
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
 
 int Nic::xe_backward(float smoothing, const icz_nic_params* G, float* dfeats, float* loss_out, float n_tokens_global, hipStream_t st) {
-    ICZ_REQUIRE(mode == 2, "nic: no XE forward stored (call icz_nic_xe_forward first)");
+    ICZ_TRY(require_mode(2, "nic"));
     ICZ_REQUIRE(G, "nic xe_backward: null grads");
-    const int B = cur_B, T = cur_T;
-    const float n = n_tokens_global > 0.f ? n_tokens_global : (float)n_tokens;
-    const float* n_dev = n_tokens_global < 0.f ? d_msum : nullptr;      // < 0: the device scalar handed over by *_set_*_global
-    ICZ_CHECK_HIP(hipMemsetAsync(loss_rows, 0, sizeof(float) * T * B, st));
-    {
-        ICZ_REQUIRE(T <= XE_MAX_T, "xe_backward: %d steps exceed %d", T, XE_MAX_T);
-        XeRows xr = {};
-        for (int t = 0; t < T; ++t) xr.n[t] = rows_t[t];
-        hipLaunchKernelGGL(xe_loss_dlogits_kernel, dim3(B, T), dim3(256), 0, st, tlogit, dims.V, Vp, cur_captions, cur_L, B, xr, smoothing, 1.0f / n, n_dev,
-                           loss_rows);
-    }
-    if (loss_out) hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, st, loss_rows, T * B, 1.0f / n, n_dev, loss_out);
-    mode = 0;
+    ICZ_TRY(xe_loss(smoothing, n_tokens_global, tlogit, dims.V, Vp, loss_out, st));
     bptt_early_out = false;
     return bptt(*G, dfeats, st);
 }
@@ -450,60 +370,20 @@ int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st) {
 
 int Nic::beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st) {
     ICZ_REQUIRE(feats && seqs_out && lens_out, "nic beam: null argument");
-    ICZ_REQUIRE(k >= 1 && k <= BEAM_MAX_K, "nic beam: beam size %d out of range 1..%d", k, BEAM_MAX_K);
-    ICZ_REQUIRE(n_img > 0 && (long)n_img * k <= dims.max_rows, "nic beam: %d images x %d beams exceed row capacity %d", n_img, k, dims.max_rows);
-    ICZ_REQUIRE(max_steps >= 1 && max_steps <= 256, "nic beam: max_steps out of range");
+    ICZ_TRY(BeamBuf::check("nic", n_img, k, max_steps, dims.max_rows));
     ICZ_REQUIRE(fresh, "nic: call icz_nic_refresh_weights after binding/updating parameters");
     const int rows = n_img * k, L = max_steps + 1, H = dims.H;
-    if (bm.cap_rows < rows || bm.cap_L < L) {
-        const size_t R_ = dims.max_rows, L_ = L > 51 ? L : 51;
-        ICZ_TRY(alloc((void**)&bm.n_act, sizeof(int) * R_));
-        ICZ_TRY(alloc((void**)&bm.run, sizeof(float) * R_));
-        ICZ_TRY(alloc((void**)&bm.seqs[0], sizeof(int32_t) * R_ * L_));
-        ICZ_TRY(alloc((void**)&bm.seqs[1], sizeof(int32_t) * R_ * L_));
-        ICZ_TRY(alloc((void**)&bm.src_row, sizeof(int32_t) * R_));
-        ICZ_TRY(alloc((void**)&bm.img_of_row, sizeof(int32_t) * R_));
-        ICZ_TRY(alloc((void**)&bm.best_score, sizeof(float) * R_));
-        ICZ_TRY(alloc((void**)&bm.best_len, sizeof(int) * R_));
-        ICZ_TRY(alloc((void**)&bm.has_complete, sizeof(int) * R_));
-        ICZ_TRY(alloc((void**)&bm.best_seq, sizeof(int32_t) * R_ * L_));
-        ICZ_TRY(alloc((void**)&bm.n_live, sizeof(int) * 260));
-        ICZ_TRY(alloc((void**)&bm.cand_val, sizeof(float) * R_ * BEAM_MAX_K));
-        ICZ_TRY(alloc((void**)&bm.cand_idx, sizeof(int) * R_ * BEAM_MAX_K));
-        ICZ_TRY(alloc((void**)&bm.feat_rows, sizeof(float) * R_ * dims.E));
-        ICZ_CHECK_HIP(hipHostMalloc((void**)&bm.n_live_host, sizeof(int) * 4, 0));
-        ICZ_CHECK_HIP(hipDeviceSynchronize());      // alloc() zero-fills on the NULL stream (see ensure_train)
-        bm.cap_rows = (int)R_;
-        bm.cap_L = (int)L_;
-    }
-    ICZ_CHECK_HIP(hipMemsetAsync(bm.n_live, 0, sizeof(int) * 260, st));
-    ICZ_CHECK_HIP(hipMemsetAsync(bm.run, 0, sizeof(float) * rows, st));
-    hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, n_img, k, L, bm.n_act, bm.seqs[0], bm.img_of_row, it,
-                       bm.has_complete, bm.best_score);
+    ICZ_TRY(bm.ensure(mem, dims.max_rows, L, dims.E));
+    ICZ_TRY(bm.begin(n_img, k, L, it, st));
     // every beam row starts from the image step of its image (features.expand(k, ...), NIC_Model.py:164)
     hipLaunchKernelGGL(beam_expand_rows_kernel, dim3(cdiv(dims.E, 1024), rows), dim3(256), 0, st, feats, bm.img_of_row, dims.E, bm.feat_rows);
     ICZ_TRY(image_step(bm.feat_rows, rows, h[0], c[0], nullptr, st));
     DropCfg off = {0, nullptr, nullptr, 0, 0};
-    int sb = 0, steps_done = 0;
-    for (int step = 1; step <= max_steps; ++step) {
-        ICZ_TRY(token_step(rows, it, false, h[0], c[0], h[1], c[1], emb, nullptr, hdrop, logits, off, st));
-        BeamArgs a = {logits, dims.V, Vp, k, step, L, bm.n_act, bm.run, bm.seqs[sb], bm.seqs[sb ^ 1], bm.src_row, it,
-                      bm.best_score, bm.best_len, bm.best_seq, bm.has_complete, bm.n_live + step};
-        launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)bm.n_act, (const float*)bm.run, bm.cand_val, bm.cand_idx);
-        hipLaunchKernelGGL(beam_merge_kernel, dim3(n_img), dim3(64), 0, st, a, (const float*)bm.cand_val, (const int*)bm.cand_idx);
+    auto step = [&](int, bool) { return token_step(rows, it, false, h[0], c[0], h[1], c[1], emb, nullptr, hdrop, logits, off, st); };
+    auto gather = [&](bool) {
         hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(H, 1024), rows), dim3(256), 0, st, bm.src_row, H, h[1], c[1], h[1], c[1], h[0], c[0], h[0], c[0], 1);
-        sb ^= 1;
-        steps_done = step;
-        if (step >= 6 && (step % 3) == 0 && step < max_steps) {
-            ICZ_CHECK_HIP(hipMemcpyAsync(bm.n_live_host, bm.n_live + step, sizeof(int), hipMemcpyDeviceToHost, st));
-            ICZ_CHECK_HIP(hipStreamSynchronize(st));
-            if (bm.n_live_host[0] == 0) break;
-        }
-    }
-    hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, bm.n_act, bm.run, bm.seqs[sb], bm.has_complete,
-                       bm.best_len, bm.best_seq, seqs_out, lens_out);
-    ICZ_CHECK_HIP(hipGetLastError());
-    return ICZ_OK;
+    };
+    return bm.search(n_img, k, max_steps, false, logits, dims.V, Vp, it, seqs_out, lens_out, st, step, gather);
 }
 
 }  // namespace icz
@@ -512,22 +392,11 @@ int Nic::beam_search(const float* feats, int n_img, int k, int max_steps, float*
 using namespace icz;
 extern "C" {
 
-int icz_nic_create(const icz_nic_dims* dims, icz_nic_t** out) {
-    ICZ_REQUIRE(dims && out, "icz_nic_create: null argument");
-    Nic* n = new Nic();
-    int s = n->init(*dims);
-    if (s != ICZ_OK) { delete n; return s; }
-    *out = reinterpret_cast<icz_nic_t*>(n);
-    return ICZ_OK;
-}
+int icz_nic_create(const icz_nic_dims* dims, icz_nic_t** out) { return abi_create<Nic>("icz_nic_create", dims, out); }
 int icz_nic_destroy(icz_nic_t* h) { delete reinterpret_cast<Nic*>(h); return ICZ_OK; }
 int icz_nic_bind_params(icz_nic_t* h, const icz_nic_params* p) {
     ICZ_REQUIRE(h && p, "icz_nic_bind_params: null argument");
-    const float* const* q = reinterpret_cast<const float* const*>(p);
-    for (size_t i = 0; i < sizeof(icz_nic_params) / sizeof(float*); ++i) {
-        ICZ_REQUIRE(q[i] != nullptr, "icz_nic_bind_params: parameter pointer %zu is null", i);
-        ICZ_REQUIRE(((uintptr_t)q[i] & 15) == 0, "icz_nic_bind_params: parameter %zu not 16-byte aligned", i);
-    }
+    ICZ_TRY(check_param_table("icz_nic_bind_params", p, sizeof(*p)));
     Nic* n = reinterpret_cast<Nic*>(h);
     n->P = *p; n->bound = true; n->fresh = false;
     return ICZ_OK;
@@ -551,11 +420,7 @@ int icz_nic_sample_backward(icz_nic_t* h, const float* reward, const icz_nic_par
     return reinterpret_cast<Nic*>(h)->sample_backward(reward, grads, dfeatures_out, loss_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
 }
 int icz_nic_set_scheduled_sampling(icz_nic_t* h, float ss_prob, const float* gate_uniforms, const float* draw_uniforms) {
-    ICZ_REQUIRE(h, "null handle");
-    ICZ_REQUIRE(ss_prob >= 0.f && ss_prob <= 1.f, "icz_nic_set_scheduled_sampling: ss_prob %g outside [0, 1]", (double)ss_prob);
-    Nic* n = reinterpret_cast<Nic*>(h);
-    n->ss_prob = ss_prob; n->ss_gate = gate_uniforms; n->ss_draw = draw_uniforms;
-    return ICZ_OK;
+    return set_scheduled_sampling("icz_nic_set_scheduled_sampling", reinterpret_cast<Nic*>(h), ss_prob, gate_uniforms, draw_uniforms);
 }
 int icz_nic_xe_forward(icz_nic_t* h, const float* features, const int64_t* captions, int32_t B, int32_t L, const int32_t* lengths_host,
                        const icz_rng* rng, int32_t train, float* packed_logits_out, void* stream) {
@@ -569,9 +434,7 @@ int icz_nic_set_option(icz_nic_t* h, const char* name, int32_t value) {
     return ICZ_ERR_INVALID;
 }
 int icz_nic_set_norm_global(icz_nic_t* h, const float* norm_dev, void* stream) {
-    ICZ_REQUIRE(h && norm_dev, "icz_nic_set_norm_global: null argument");
-    ICZ_CHECK_HIP(hipMemcpyAsync(reinterpret_cast<Nic*>(h)->d_msum, norm_dev, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return ICZ_OK;
+    return set_norm_global("icz_nic_set_norm_global", reinterpret_cast<Nic*>(h), norm_dev, stream);
 }
 int icz_nic_xe_backward(icz_nic_t* h, float smoothing, const icz_nic_params* grads, float* dfeatures_out, float* loss_out,
                         float n_tokens_global, void* stream) {
