@@ -79,7 +79,11 @@ int icz_butd_bind_params(icz_butd_t* h, const icz_butd_params* params);
  * kernels), so that the weights are streamed once per step pair; same tokens, log-probs, loss as the two chains.
  * "small_nt" (default 1): BPTT steps of <= 32 rows (small batches, the short tail of an XE batch) take their per-step dgrad products on
  * the transposed LSTM weight copies through the fp32 NT kernel instead of NN products on the weights (which stream at half the rate
- * at so few rows); 0 = the NN products of rounds 1 - 4.  Gradients agree to fp32 rounding. */
+ * at so few rows); 0 = the NN products of rounds 1 - 4.  Gradients agree to fp32 rounding.
+ * "group_att" (default 0): 1 = icz_butd_sample_n's attention runs on the grouped kernels (the K rows of an image in one workgroup:
+ * scores, context and, in its backward, d enc_ctx read each image's features / projected features once); 0 = the per-row kernels,
+ * which find the image of each row through an index (measured faster).  Ids and log-probs are bitwise the same;
+ * gradients too except enc_att.*, affine.* and TD_atten.weight_ih, which may differ by fp32 rounding. */
 int icz_butd_set_option(icz_butd_t* h, const char* name, int32_t value);
 /* Data-parallel overlap hook (no reference counterpart: the reference is single-process).  While a backward call is
  * being enqueued, `cb(user, stage)` is invoked each time a group of gradient tensors is complete in stream order:
@@ -129,6 +133,15 @@ int icz_butd_sample(icz_butd_t* h, const float* feats, int32_t B, int32_t max_le
  * columns behind the step at which the LAST row emitted it are 0, see option "early_out".) */
 int icz_butd_scst_rollouts(icz_butd_t* h, const float* feats, int32_t B, int32_t max_len, const icz_rng* rng,
                            int64_t* greedy_ids_out, int64_t* seq_out, float* logprobs_out, void* stream);
+/* Beyond the reference (which draws ONE sampled caption per image, Engine.py:258-262): the multi-sample rollout of the "new
+ * self-critical" SCST variant -- K = 2..8 sampled captions per image for B images, decoder row = img * K + k, B K <= max_rows.  The
+ * per-image work (mean features, enc_att(feats), the mean part of the TD gates) runs once per image, the sampled chain over the B K
+ * rows.  Dropout keep-bits and draws are indexed by the row in the B K space (explicit icz_rng arrays are laid out for B K rows):
+ * row img * K + k gets the draws row img * K + k of icz_butd_sample on the features repeated K times gets (the ids agree with that
+ * call up to draws at a CDF edge; the per-image GEMMs run at another M, so their rounding may differ).  feats [B,R,D]; seq_out
+ * [B K, max_len] int64, logprobs_out [B K, max_len].  icz_butd_sample_backward / _dlogp then take rewards [B K, max_len]. */
+int icz_butd_sample_n(icz_butd_t* h, const float* feats, int32_t B, int32_t K, int32_t max_len, const icz_rng* rng,
+                      int64_t* seq_out, float* logprobs_out, void* stream);
 
 /* RewardCriterion.forward + loss.backward() for the rollout kept by the last icz_butd_sample
  * (Utils.py:295-317, Engine.py:266-270).  reward [B,max_len]; grads receives d loss / d parameter (overwritten,
@@ -379,6 +392,15 @@ int icz_ciderd_reward_indexed(icz_ciderd_t* h, const int64_t* gen, const int64_t
                               const int32_t* img_slot, const int32_t* img_ref_ptr, const int32_t* ref_ent_ptr,
                               const int32_t* ent_key, const int32_t* ent_order, const double* ent_w, const double* ref_norm,
                               const int32_t* ref_len, float* reward_out, double* scores_out, void* stream);
+/* Beyond the reference (Utils.py:319-367 baselines a sampled caption with the greedy one): the reward of the multi-sample SCST
+ * variant with a leave-one-out mean baseline.  gen [B K, T] holds K sampled captions per image (row = img * K + k, K = 2..8),
+ * img_slot [B] the store row of each IMAGE, the store arrays as in icz_ciderd_reward_indexed.  scores_out [B K] float64 receives
+ * the CIDEr-D scores s_i; reward_out [B K, T] every column of row i = (float)(s_i - (sum_{j != i, ascending j} s_j) / (K - 1)),
+ * computed in float64, the sum over the other K - 1 captions of the same image. */
+int icz_ciderd_reward_loo(icz_ciderd_t* h, const int64_t* gen, int32_t B, int32_t K, int32_t T, const int32_t* img_slot,
+                          const int32_t* img_ref_ptr, const int32_t* ref_ent_ptr, const int32_t* ent_key, const int32_t* ent_order,
+                          const double* ent_w, const double* ref_norm, const int32_t* ref_len, float* reward_out, double* scores_out,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * BLEU and ROUGE-L of the evaluation report (COCO_Eval_Utils.py:15-35 -> coco_caption/pycocoevalcap/eval.py:24-69): the

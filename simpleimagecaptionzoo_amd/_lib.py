@@ -127,6 +127,7 @@ def lib():
         "icz_butd_step": (C.c_int, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "icz_butd_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(Rng), vp, vp, vp]),
         "icz_butd_scst_rollouts": (C.c_int, [vp, vp, i32, i32, C.POINTER(Rng), vp, vp, vp, vp]),
+        "icz_butd_sample_n": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(Rng), vp, vp, vp]),
         "icz_butd_sample_backward": (C.c_int, [vp, vp, C.POINTER(ButdParams), vp, vp, f32, vp]),
         "icz_butd_sample_backward_dlogp": (C.c_int, [vp, vp, C.POINTER(ButdParams), vp]),
         "icz_butd_xe_backward_dlogits": (C.c_int, [vp, vp, C.POINTER(ButdParams), vp]),
@@ -176,6 +177,7 @@ def lib():
         "icz_ciderd_vocab_oov_id": (C.c_int, [vp, C.c_char_p, i32, C.POINTER(i32)]),
         "icz_ciderd_cook_text": (C.c_int, [vp, vp, vp, i64, C.c_double, C.c_char_p, i64, i32, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]),
         "icz_ciderd_reward_indexed": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_ciderd_reward_loo": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "icz_bleu_stats": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp]),
         "icz_rouge_lcs": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp]),
         "icz_prof_begin": (C.c_int, []),

@@ -49,7 +49,7 @@ class ButdHandle:
         check(lib().icz_butd_set_option(self._h, b"concurrent", 1 if on else 0))
 
     def set_option(self, name, value):
-        """icz_butd_set_option (include/icz.h): "graphs", "concurrent"."""
+        """icz_butd_set_option (include/icz.h): "graphs", "concurrent", "early_out", "merge_small", "small_nt", "group_att"."""
         check(lib().icz_butd_set_option(self._h, name.encode(), int(value)))
 
     def _buf(self, name, shape, dtype):
@@ -119,6 +119,24 @@ class ButdHandle:
         seq = self._buf("sample_seq", (B, max_len), torch.int64)
         lp = self._buf("sample_lp", (B, max_len), torch.float32)
         check(lib().icz_butd_sample(self._h, ptr(feats), B, max_len, C.byref(rng), ptr(seq), ptr(lp), stream_ptr()))
+        self._live = (feats, rng, seq, lp)
+        return seq, lp
+
+    def sample_n(self, feats, n, max_len=20, rng=None):
+        """Beyond the reference: n = 2..8 sampled captions per image (multi-sample SCST, include/icz.h icz_butd_sample_n) ->
+        (seq int64 (B n, T), logprobs (B n, T)), row img * n + k.  Row img * n + k draws what row img * n + k of
+        sample(feats.repeat_interleave(n, 0), rng) draws; explicit rng arrays are laid out for B n rows.  sample_backward then
+        takes a (B n, T) reward."""
+        feats = self._check_feats(feats)
+        B, n = feats.shape[0], int(n)
+        if not 2 <= n <= 8:          # checked before any buffer is made: nothing is queued on a bad call
+            raise _lib.IczError("sample_n: n=%d samples per image outside 2..8" % n)
+        if B * n > self.max_rows:
+            raise _lib.IczError("sample_n: %d images x %d samples exceed the handle's row capacity %d" % (B, n, self.max_rows))
+        rng = rng or make_rng(0)
+        seq = self._buf("sample_n_seq", (B * n, max_len), torch.int64)
+        lp = self._buf("sample_n_lp", (B * n, max_len), torch.float32)
+        check(lib().icz_butd_sample_n(self._h, ptr(feats), B, n, max_len, C.byref(rng), ptr(seq), ptr(lp), stream_ptr()))
         self._live = (feats, rng, seq, lp)
         return seq, lp
 

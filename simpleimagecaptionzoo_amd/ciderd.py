@@ -17,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, stream_ptr
+from ._lib import IczError, check, lib, ptr, stream_ptr
 from .features import wait_event as _wait
 
 _FNV_OFF, _FNV_PRIME = np.uint32(2166136261), np.uint32(16777619)
@@ -416,6 +416,50 @@ class CiderDReward:
                                               ptr(st["key"]), ptr(st["ord"]), ptr(st["w"]), ptr(st["norm"]), ptr(st["len"]),
                                               ptr(reward), ptr(scores), stream_ptr()))
         return (reward, scores) if return_scores else reward
+
+    def reward_loo(self, gen, n, ground_truth, img_ids, return_scores=False):
+        """Beyond the reference: the multi-sample SCST reward with a leave-one-out baseline (include/icz.h icz_ciderd_reward_loo).
+        gen (B n, T) holds n sampled captions per image (row img * n + k), img_ids / ground_truth the B images.  Every column of row i
+        = float32(s_i - mean of the other n - 1 scores of its image), in float64 on the device; scores (B n,) float64 on request."""
+        n = int(n)
+        BK, T = gen.shape
+        img_ids = list(img_ids)
+        B = len(img_ids)
+        if n < 2 or n > 8:
+            raise IczError("reward_loo: n=%d samples per image outside 2..8" % n)
+        if B * n != BK:
+            raise IczError("reward_loo: %d caption rows for %d images x %d samples" % (BK, B, n))
+        gen = gen.to(device=self.device, dtype=torch.int64).contiguous()
+        idx = self._slots(img_ids, ground_truth)
+        st = self._st
+        if self.persistent:
+            key = ("loo", B, n, T)
+            if key not in self._out:
+                self._out[key] = (torch.empty(BK, T, dtype=torch.float32, device=self.device),
+                                  torch.empty(BK, dtype=torch.float64, device=self.device))
+            reward, scores = self._out[key]
+        else:
+            reward = torch.empty(BK, T, dtype=torch.float32, device=self.device)
+            scores = torch.empty(BK, dtype=torch.float64, device=self.device)
+        check(lib().icz_ciderd_reward_loo(self._h, ptr(gen), B, n, T, ptr(idx), ptr(st["irp"]), ptr(st["rep"]), ptr(st["key"]),
+                                          ptr(st["ord"]), ptr(st["w"]), ptr(st["norm"]), ptr(st["len"]), ptr(reward), ptr(scores),
+                                          stream_ptr()))
+        return (reward, scores) if return_scores else reward
+
+
+def loo_baseline_reward(scores, n):
+    """Host restatement of icz_ciderd_reward_loo's arithmetic (tests): scores (B n,) float64 -> float32 (B n,) rewards
+    s_i - (sum_{j != i, ascending j} s_j) / (n - 1), the sum over the other captions of the same image in ascending order."""
+    s = np.asarray(scores, dtype=np.float64)
+    out = np.empty(s.shape[0], dtype=np.float32)
+    for i in range(s.shape[0]):
+        j0 = i - i % n
+        acc = 0.0
+        for j in range(j0, j0 + n):
+            if j != i:
+                acc += float(s[j])
+        out[i] = np.float32(float(s[i]) - acc / float(n - 1))
+    return out
 
 
 # ---- the reference's own entry point -----------------------------------------------------------------------------------

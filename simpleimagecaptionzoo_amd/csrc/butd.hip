@@ -203,13 +203,16 @@ int Butd::step(const StepIO& s, hipStream_t st) {
         const int G = s.rows_per_img;
         // compare the accumulation order: the per-row kernel sums a region row in the lane order of three regions at a time, the
         // grouped one region by region -- identical per (row, region): a wave's lanes cover the same columns in the same order
-        if (G > 1 && G <= ATT_CTX_MAX_G && rows % G == 0 && s.drop_att.mode == 0 && sizeof(float) * A * G <= 60 * 1024)
+        const bool grouped = G > 1 && G <= ATT_CTX_MAX_G && rows % G == 0 && sizeof(float) * A * G <= 60 * 1024;
+        if (grouped && s.drop_att.mode == 0 && !s.live)          // beam search
             hipLaunchKernelGGL(att_scores_group_kernel, dim3(rows / G, ATT_PARTS), dim3(256), sizeof(float) * A * G, st, a, G);
+        else if (grouped)                                        // the multi-sample rollout (sample_n): dropout per row, early-out
+            hipLaunchKernelGGL(att_scores_group_train_kernel, dim3(rows / G, ATT_PARTS), dim3(256), sizeof(float) * A * G, st, a, s.drop_att, G);
         else
             hipLaunchKernelGGL(att_scores_kernel, dim3(rows, ATT_PARTS), dim3(256), sizeof(float) * A, st, a, s.drop_att);
         if (G > 1 && G <= ATT_CTX_MAX_G && rows % G == 0 && !s.alpha_out2)
             hipLaunchKernelGGL(att_ctx_group_kernel, dim3(rows / G, cdiv(D, 512)), dim3(256), 0, st, s.feats, (const float*)scores,
-                               s.alpha_out ? s.alpha_out : alpha, s.ctx_out ? s.ctx_out : ctx, R, D, G);
+                               s.alpha_out ? s.alpha_out : alpha, s.ctx_out ? s.ctx_out : ctx, R, D, G, s.live);
         else
             hipLaunchKernelGGL(att_ctx_kernel, dim3(rows, cdiv(D, 512)), dim3(256), 0, st, s.feats, s.img_of_row, (const float*)scores,
                                s.alpha_out ? s.alpha_out : alpha, s.alpha_out2, s.alpha2_stride, s.ctx_out ? s.ctx_out : ctx, R, D, s.live);
@@ -340,6 +343,7 @@ int icz_butd_set_option(icz_butd_t* h, const char* name, int32_t value) {
     if (strcmp(name, "concurrent") == 0) { b->concurrent = value != 0; return ICZ_OK; }
     if (strcmp(name, "early_out") == 0) { b->early_out = value != 0; return ICZ_OK; }
     if (strcmp(name, "small_nt") == 0) { b->small_nt = value != 0; return ICZ_OK; }
+    if (strcmp(name, "group_att") == 0) { b->group_att = value != 0; return ICZ_OK; }
     if (strcmp(name, "merge_small") == 0) {
         ICZ_REQUIRE(value >= 0 && value <= 32, "icz_butd_set_option: merge_small %d outside 0..32", value);
         b->merge_small = value;

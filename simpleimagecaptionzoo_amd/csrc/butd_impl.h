@@ -46,6 +46,8 @@ struct TrainBuf {
     float *gtd = nullptr, *glm = nullptr, *dec = nullptr, *alpha = nullptr, *ctx = nullptr, *h2d = nullptr, *logit = nullptr;
     int* nany = nullptr;                                      // merged chain: unfinished sampled rows + greedy rows that have not ended, per step
     int32_t* img2 = nullptr;                                  // merged chain: image of each decoder row (row r of 2 B -> image r mod B)
+    int32_t* imgk = nullptr;                                  // multi-sample rollout: image of each decoder row (row r of B K -> image r / K)
+    float* dEncImg = nullptr;                                 // multi-sample backward: d enc_ctx folded onto the images [n_img, R, A]
     float *dGtd = nullptr, *dGlm = nullptr, *dDec = nullptr, *dEmb = nullptr, *dH2d = nullptr, *dEnc = nullptr;
     float *dwaff = nullptr, *dalpha = nullptr, *dS = nullptr, *dGsum = nullptr;
     float *dc1[2] = {nullptr, nullptr}, *dc2[2] = {nullptr, nullptr};
@@ -97,7 +99,7 @@ struct Butd : CaptionHead {
     bool use_graphs = false;
     bool concurrent = true;      // run independent chains on side streams (off: one stream, for per-kernel timing)
     uintptr_t opt_bits() const {         // the options that change the captured launch sequence
-        return (concurrent ? 1 : 0) + (early_out ? 2 : 0) + 4 * merge_small + (small_nt ? 256 : 0);
+        return (concurrent ? 1 : 0) + (early_out ? 2 : 0) + 4 * merge_small + (small_nt ? 256 : 0) + (group_att ? 512 : 0);
     }
     int greedy_impl(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st);
     int sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st);
@@ -121,6 +123,14 @@ struct Butd : CaptionHead {
     bool early_out = true;               // option "early_out": 0 = run the steps behind the reference's break as rounds 1 - 4 did (A/B)
     bool bptt_early_out = false;         // backward of a sampled rollout: steps behind the reference's break return at entry (bptt)
     bool small_nt = true;                // option "small_nt": BPTT steps of <= 32 rows take their dgrad products on the transposed weight copies (fp32 NT kernel)
+    // multi-sample SCST rollout (sample_n, beyond the reference): K sampled rows per image, row = img * K + k, sharing the image's
+    // hoisted tensors.  cur_K = rows per image of the stored rollout (1 = every other entry point), cur_nimg = its image count.
+    int cur_K = 1, cur_nimg = 0;
+    bool group_att = false;              // option "group_att": 1 = sample_n's attention (forward scores / context, backward d enc_ctx) runs on
+                                         // the grouped kernels (each image's features / enc_ctx read once for its K rows); 0 (default) = the
+                                         // per-row kernels through img_of_row.  Measured (tools/perf_scst_n.py): the
+                                         // grouped route is slower, 16.3 against 15.9 ms at 64 images x 5 and 5.65 against 4.94 ms at 16 x 4
+                                         // (fewer, longer workgroups; the features fit the Infinity Cache either way)
 
     // beam search (butd_beam.hip)
     BeamBuf bm;
@@ -134,6 +144,8 @@ struct Butd : CaptionHead {
     int train_step(const float* feats, int rows, int Bs, int t, bool train, hipStream_t st, bool emb_ready = false, int* pred_nsplit = nullptr,
                    bool skip_predict = false, const int* live = nullptr, int row0 = 0);
     int sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
+    int sample_n(const float* feats, int B, int K, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
+    int sample_n_impl(const float* feats, int B, int K, int T, int64_t* seq_out, float* logp_out, hipStream_t st);
     int sample_mask_sum(float* out, hipStream_t st);
     int sample_backward(const float* reward, const icz_butd_params* G, float* loss_out, float* mask_sum_out,
                         float mask_sum_global, hipStream_t st);

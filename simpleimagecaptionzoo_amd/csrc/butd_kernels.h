@@ -466,6 +466,70 @@ __global__ __launch_bounds__(256) void att_scores_group_kernel(AttScoreArgs a, i
     }
 }
 
+// Training-mode form of the grouped kernel, for the multi-sample SCST rollout (Butd::sample_n: the G = K sampled rows of an image,
+// row = img * G + k): attention dropout per row (the row's own keep-bits, indexed as att_scores_kernel indexes them) and the
+// early-out flag.  Same arithmetic and summation order per row as att_scores_kernel with the same DropCfg.  Grid (n_img, parts).
+__global__ __launch_bounds__(256) void att_scores_group_train_kernel(AttScoreArgs a, DropCfg dc, int G) {
+    extern __shared__ __attribute__((aligned(16))) float sdec[];   // [G][A]
+    const int lflag = live_flag(a.live);
+    const int img = blockIdx.x, part = blockIdx.y, nparts = gridDim.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t MN = (size_t)a.rows * a.A;
+    if (flag_dead(lflag)) return;
+    for (int g = 0; g < G; ++g) {
+        const int row = img * G + g;
+        for (int c = tid * 4; c < a.A; c += 1024) {
+            const size_t off = (size_t)row * a.A + c;
+            f32x4 s = *reinterpret_cast<const f32x4*>(a.dec_slab + off);
+            for (int z = 1; z < a.nsplit; ++z) s += *reinterpret_cast<const f32x4*>(a.dec_slab + (size_t)z * MN + off);
+            s += *reinterpret_cast<const f32x4*>(a.b_dec + c);
+            *reinterpret_cast<f32x4*>(sdec + (size_t)g * a.A + c) = s;
+            if (a.dec_ctx_out && part == 0) *reinterpret_cast<f32x4*>(a.dec_ctx_out + off) = s;
+        }
+    }
+    __syncthreads();
+    const float baff = a.b_aff[0];
+    const float sc = dc.mode ? 2.0f : 1.0f;
+    for (int i0 = wave; part + nparts * i0 < a.R; i0 += 4) {
+        const int r = part + nparts * i0;
+        const float* e = a.enc_ctx + ((size_t)img * a.R + r) * a.A;
+        float acc[ATT_CTX_MAX_G];
+#pragma unroll
+        for (int g = 0; g < ATT_CTX_MAX_G; ++g) acc[g] = 0.f;
+        for (int c0 = lane * 4; c0 < a.A; c0 += 1024) {
+            f32x4 x[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) x[u] = *reinterpret_cast<const f32x4*>(e + min(c0 + 256 * u, a.A - 4));
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int c = c0 + 256 * u;
+                if (c < a.A) {
+                    const f32x4 w = *reinterpret_cast<const f32x4*>(a.w_aff + c);
+#pragma unroll
+                    for (int g = 0; g < ATT_CTX_MAX_G; ++g)
+                        if (g < G) {
+                            const f32x4 d = *reinterpret_cast<const f32x4*>(sdec + (size_t)g * a.A + c);
+                            const uint64_t drow = (uint64_t)(img * G + g - dc.row0);
+                            const uint32_t k = dc.mode ? dc.keep4((drow * a.R + r) * a.A + c) : 0xFu;
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                float zv = fmaxf(x[u][j] + d[j], 0.f);
+                                zv = ((k >> j) & 1u) ? zv * sc : 0.f;
+                                acc[g] += zv * w[j];
+                            }
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < ATT_CTX_MAX_G; ++g)
+            if (g < G) {
+                const float v = wave_sum(acc[g]);
+                if (lane == 0) a.scores[(size_t)(img * G + g) * a.R + r] = v + baff;
+            }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // softmax over regions + attention-weighted feature sum (:60-61):
 //   alpha = softmax_r(score[row,:]);  ctx[row, d] = sum_r alpha[r] * feats[img, r, d]
@@ -533,11 +597,13 @@ __global__ __launch_bounds__(256) void att_ctx_kernel(const float* __restrict__ 
 // The same for beam search, where the G = beam rows of an image sit next to each other (row = img * G + b) and share its
 // features: one workgroup does the G rows of one image for its 512 columns, so every feature vector is fetched once
 // instead of G times (at 640 rows the per-row kernel moves 189 MB through the caches per step).  Same arithmetic and
-// summation order per row as att_ctx_kernel.  Grid (n_img, D/512).
+// summation order per row as att_ctx_kernel.  Grid (n_img, D/512).  `live`: the multi-sample rollout's early-out (null for beam search).
 __global__ __launch_bounds__(256) void att_ctx_group_kernel(const float* __restrict__ feats, const float* __restrict__ scores,
-                                                            float* __restrict__ alpha_out, float* __restrict__ ctx, int R, int D, int G) {
+                                                            float* __restrict__ alpha_out, float* __restrict__ ctx, int R, int D, int G,
+                                                            const int* __restrict__ live) {
     __shared__ float sal[ATT_CTX_MAX_G][64];
     __shared__ __attribute__((aligned(16))) float spart[ATT_CTX_MAX_G][128 * 4];
+    if (step_dead(live)) return;
     const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int g = wave; g < G; g += 4) {                 // wave w: softmax of rows w, w + 4
         const int row = img * G + g;
@@ -1355,7 +1421,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_point_kernel(LstmBwdArgs a, Drop
 constexpr int DALPHA_COLS = 512;
 __global__ __launch_bounds__(256) void att_bwd_dalpha_kernel(const float* __restrict__ dctx, int ns, int ldc, int rows,
                                                              const float* __restrict__ feats, int R, int D,
-                                                             float* __restrict__ dalpha_part, const int* __restrict__ live) {
+                                                             float* __restrict__ dalpha_part, const int* __restrict__ live,
+                                                             const int32_t* __restrict__ img_of_row) {     // null = identity
     __shared__ __attribute__((aligned(16))) float sd[DALPHA_COLS];
     const int lflag = live_flag(live);
     const int row = blockIdx.x, part = blockIdx.y, nparts = gridDim.y;
@@ -1365,7 +1432,7 @@ __global__ __launch_bounds__(256) void att_bwd_dalpha_kernel(const float* __rest
     constexpr int NR = 5;                         // regions per wave and pass (R <= 64: at most 16 per wave)
     const int ca = c0 + 4 * lane, cb = ca + 256;
     const bool va = ca < D, vb = cb < D;
-    const float* frow = feats + (size_t)row * R * D;
+    const float* frow = feats + (size_t)(img_of_row ? img_of_row[row] : row) * R * D;
     f32x4 xa[NR], xb[NR];
     auto load_pass = [&](int r0) {                // clamped: a pass past the last region re-reads it and is not stored
 #pragma unroll
@@ -1406,12 +1473,14 @@ struct AttBwdDdecArgs {
     float* ddec; float* ds_out;
     int R, A, nparts;
     const int* live;              // step_dead(live): ddec and ds rows of this step are ZERO (read by the GEMMs / kernels over all steps)
+    const int32_t* img_of_row;    // image of each row (enc_ctx row); null = identity
 };
 __global__ __launch_bounds__(256) void att_bwd_ddec_kernel(AttBwdDdecArgs a, DropCfg dc) {
     __shared__ float sds[64];
     __shared__ __attribute__((aligned(16))) float spart[3 * 64 * 4];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wq = tid >> 6;
     const int lflag = live_flag(a.live);
+    const int img = a.img_of_row ? a.img_of_row[row] : row;
     const float al = lane < a.R ? a.alpha[(size_t)row * a.R + lane] : 0.f;
     const float da0 = lane < a.R ? a.dalpha[(size_t)row * a.nparts * a.R + lane] : 0.f;
     if (flag_dead(lflag)) {                       // behind the first loads (icz_common.h); a dead step's d dec / ds rows are zeros
@@ -1444,7 +1513,7 @@ __global__ __launch_bounds__(256) void att_bwd_ddec_kernel(AttBwdDdecArgs a, Dro
 #pragma unroll
             for (int u = 0; u < RB; ++u) {
                 const int r = min(r0 + 4 * u, a.R - 1);
-                x[u] = *reinterpret_cast<const f32x4*>(a.enc_ctx + ((size_t)row * a.R + r) * a.A + c);
+                x[u] = *reinterpret_cast<const f32x4*>(a.enc_ctx + ((size_t)img * a.R + r) * a.A + c);
             }
             // Philox keep-bits, shared as in att_scores_kernel: lane 2 u + half computes the block of region u's half-strip
             uint32_t kq[RB];
@@ -1498,6 +1567,7 @@ struct AttBwdDencArgs {
     int B, R, A, T;
     int mode; const uint8_t* mask; size_t mask_step; const uint64_t* seed_p; uint32_t stream;
     int Bs;          // rows per time step in dec_all / ds_all (0 = B; a merged chain stores 2 B, the pointers then start at its second half)
+    const int32_t* img_of_row;   // image of each row (enc_ctx row); null = identity.  denc, the masks and the Philox index stay per row
 };
 template <int TT>
 __global__ __launch_bounds__(256) void att_bwd_denc_kernel(AttBwdDencArgs a) {
@@ -1510,6 +1580,7 @@ __global__ __launch_bounds__(256) void att_bwd_denc_kernel(AttBwdDencArgs a) {
     const int row = blockIdx.x, part = blockIdx.y, nparts = gridDim.y, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, hl = lane & 31;
     const int Bst = a.Bs > 0 ? a.Bs : a.B;
+    const int img = a.img_of_row ? a.img_of_row[row] : row;
     for (int i = tid; i < a.T * a.R; i += 256) {
         const int t = i / a.R, r = i % a.R;
         sds_t[i] = a.ds_all[((size_t)t * Bst + row) * a.R + r];
@@ -1544,7 +1615,7 @@ __global__ __launch_bounds__(256) void att_bwd_denc_kernel(AttBwdDencArgs a) {
                     __syncthreads();
                 }
                 if (!cv) continue;
-                const f32x4 x = *reinterpret_cast<const f32x4*>(a.enc_ctx + eoff);
+                const f32x4 x = *reinterpret_cast<const f32x4*>(a.enc_ctx + ((size_t)img * a.R + r) * a.A + c);
                 f32x4 de = {0.f, 0.f, 0.f, 0.f};
                 if (t0 > 0) de = *reinterpret_cast<const f32x4*>(a.denc + eoff);
 #pragma unroll
@@ -1575,6 +1646,122 @@ __global__ __launch_bounds__(256) void att_bwd_denc_kernel(AttBwdDencArgs a) {
         }
         if (cv) *reinterpret_cast<f32x4*>(a.dwaff_part + ((size_t)row * nparts + part) * a.A + c) = dw;
     }
+}
+
+// Multi-sample SCST (Butd::sample_n): the G rows img * G + k of an image share its enc_ctx.  One workgroup per (image, part) does
+// what att_bwd_denc_kernel does for each of the G rows, in k order: a thread reads its enc_ctx elements of the part's regions ONCE
+// (registers, for all G rows), forms each row's d enc_ctx exactly as the per-row kernel forms it, and adds the G of them in k order
+// into denc[img] (the per-row route, att_bwd_denc_kernel + rowgroup_sum_kernel, gets the same sums).  dwaff_part[img, part] = the
+// rows' partials added in k order.  Grid (n_img, parts) with parts * DENC_GROUP_REGS >= R; a.B = rows, a.img_of_row unused.
+constexpr int DENC_GROUP_REGS = 16;
+template <int TT>
+__global__ __launch_bounds__(256) void att_bwd_denc_group_kernel(AttBwdDencArgs a, int G) {
+    static_assert(TT <= 32, "one half-wave computes the TT Philox words of its 128-column group");
+    extern __shared__ __attribute__((aligned(16))) float sds_t[];     // [T][R] ds of the current row
+    __shared__ uint32_t sbits[4][2][TT][4];
+    const int img = blockIdx.x, part = blockIdx.y, nparts = gridDim.y, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, hl = lane & 31;
+    const int Bst = a.Bs > 0 ? a.Bs : a.B;
+    const float sc = a.mode ? 2.0f : 1.0f;
+    const bool shared_bits = a.mode == 2 && (a.A & 127) == 0;
+    for (int c0 = 0; c0 < a.A; c0 += 1024) {          // uniform over the workgroup (barriers inside)
+        const int c = c0 + tid * 4;
+        const bool cv = c < a.A;
+        const f32x4 w = cv ? *reinterpret_cast<const f32x4*>(a.w_aff + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        f32x4 x[DENC_GROUP_REGS];
+#pragma unroll
+        for (int i = 0; i < DENC_GROUP_REGS; ++i) {
+            const int r = part + i * nparts;
+            x[i] = (cv && r < a.R) ? *reinterpret_cast<const f32x4*>(a.enc_ctx + ((size_t)img * a.R + r) * a.A + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+        f32x4 dwsum = {0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < G; ++k) {
+            const int row = img * G + k;
+            __syncthreads();                            // the previous row's ds have been read
+            for (int i = tid; i < a.T * a.R; i += 256) {
+                const int t = i / a.R, r = i % a.R;
+                sds_t[i] = a.ds_all[((size_t)t * Bst + row) * a.R + r];
+            }
+            __syncthreads();
+            f32x4 de[DENC_GROUP_REGS];
+#pragma unroll
+            for (int i = 0; i < DENC_GROUP_REGS; ++i) de[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            f32x4 dw = {0.f, 0.f, 0.f, 0.f};
+            for (int t0 = 0; t0 < a.T; t0 += TT) {
+                f32x4 d[TT];
+#pragma unroll
+                for (int j = 0; j < TT; ++j) {
+                    const int t = min(t0 + j, a.T - 1);
+                    d[j] = cv ? *reinterpret_cast<const f32x4*>(a.dec_all + ((size_t)t * Bst + row) * a.A + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+#pragma unroll
+                for (int i = 0; i < DENC_GROUP_REGS; ++i) {
+                    const int r = part + i * nparts;
+                    if (r >= a.R) break;                // uniform
+                    const size_t eoff = ((size_t)row * a.R + r) * a.A + c;      // the row's element: mask / Philox index
+                    if (shared_bits) {
+                        __syncthreads();
+                        if (cv && hl < TT && t0 + hl < a.T) {
+                            const uint64_t g = (eoff - (size_t)(4 * hl)) >> 7;
+                            const uint64_t seed = *a.seed_p;
+                            uint4_ ctr = {(uint32_t)g, (uint32_t)(g >> 32), (uint32_t)(t0 + hl), a.stream};
+                            const uint4_ rr = philox4x32_10(ctr, (uint32_t)seed, (uint32_t)(seed >> 32));
+                            uint32_t* o = sbits[wave][half][hl];
+                            o[0] = rr.x; o[1] = rr.y; o[2] = rr.z; o[3] = rr.w;
+                        }
+                        __syncthreads();
+                    }
+                    if (!cv) continue;
+#pragma unroll
+                    for (int j = 0; j < TT; ++j) {
+                        const int t = t0 + j;
+                        if (t < a.T) {
+                            const float ds = sds_t[t * a.R + r];
+                            uint32_t kb = 0xFu;
+                            if (a.mode == 1) {
+                                const uint32_t m = *reinterpret_cast<const uint32_t*>(a.mask + (size_t)t * a.mask_step + eoff);
+                                kb = ((m & 0xFFu) ? 1u : 0u) | ((m & 0xFF00u) ? 2u : 0u) | ((m & 0xFF0000u) ? 4u : 0u) | ((m & 0xFF000000u) ? 8u : 0u);
+                            } else if (shared_bits) {
+                                kb = (sbits[wave][half][j][(eoff >> 5) & 3] >> (eoff & 31)) & 0xFu;
+                            } else if (a.mode == 2) {
+                                kb = (rng_group_bits(*a.seed_p, a.stream, (uint32_t)t, eoff) >> (eoff & 31)) & 0xFu;
+                            }
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) {
+                                const float zp = x[i][q] + d[j][q];
+                                const bool on = (zp > 0.f) && ((kb >> q) & 1u);
+                                de[i][q] += on ? ds * w[q] * sc : 0.f;
+                                dw[q] += on ? zp * sc * ds : 0.f;
+                            }
+                        }
+                    }
+                }
+            }
+            if (cv) {
+#pragma unroll
+                for (int i = 0; i < DENC_GROUP_REGS; ++i) {
+                    const int r = part + i * nparts;
+                    if (r >= a.R) break;
+                    f32x4* o = reinterpret_cast<f32x4*>(a.denc + ((size_t)img * a.R + r) * a.A + c);
+                    *o = k == 0 ? de[i] : *o + de[i];
+                }
+                dwsum = k == 0 ? dw : dwsum + dw;
+            }
+        }
+        if (cv) *reinterpret_cast<f32x4*>(a.dwaff_part + ((size_t)img * nparts + part) * a.A + c) = dwsum;
+    }
+}
+
+// out[i, n] = sum_{k < G} X[i G + k, n], added in k order (multi-sample SCST: the G sampled rows of an image folded onto it).
+// N % 4 == 0; one thread per 4 consecutive columns.
+__global__ __launch_bounds__(256) void rowgroup_sum_kernel(const float* __restrict__ X, int n_img, int G, size_t N, float* __restrict__ out) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= (size_t)n_img * N) return;
+    const size_t img = i / N, n = i % N;
+    const float* x = X + img * G * N + n;
+    f32x4 s = *reinterpret_cast<const f32x4*>(x);
+    for (int k = 1; k < G; ++k) s += *reinterpret_cast<const f32x4*>(x + (size_t)k * N);
+    *reinterpret_cast<f32x4*>(out + i) = s;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1714,11 +1901,81 @@ __global__ __launch_bounds__(256) void embed_grad_kernel(const int64_t* __restri
         }
     }
 }
-// host side: grid, LDS size (above the 64 KB default the kernel needs the explicit opt-in)
+// The same for token lists longer than embed_grad_kernel's LDS holds (more than ~4500 (t, b) pairs: the multi-sample rollout's B K rows
+// x T steps).  The list is walked in windows of EG_WIN tokens: per window each wave finds the occurrences of two of the rows (ballot,
+// list order), then every wave adds them for its columns; the partial sums are carried across windows in registers -- the same
+// additions in the same order as embed_grad_kernel.  E <= 1024 (one group of four columns per lane).
+constexpr int EG_WIN = 1024;
+__global__ __launch_bounds__(256) void embed_grad_win_kernel(const int64_t* __restrict__ tok, int n_tok,
+                                                             const float* __restrict__ demb, int ns, size_t slab_stride,
+                                                             const float* __restrict__ emb, float scale, int E,
+                                                             float* __restrict__ dE, int V, int relu, const int* __restrict__ rows_live) {
+    __shared__ int stok[EG_WIN];
+    __shared__ int shits[EG_ROWS][EG_WIN];
+    __shared__ int snh[EG_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (rows_live) n_tok = min(n_tok, *rows_live);
+    const int e = 256 * wave + lane * 4;
+    const bool ev = e < E;
+    f32x4 s[EG_ROWS];
+#pragma unroll
+    for (int r = 0; r < EG_ROWS; ++r) s[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int w0 = 0; w0 < n_tok; w0 += EG_WIN) {
+        const int nw = min(EG_WIN, n_tok - w0);
+        __syncthreads();                                  // the previous window's lists have been read
+        for (int i = tid; i < nw; i += 256) stok[i] = (int)tok[w0 + i];
+        __syncthreads();
+        for (int rr = 0; rr < EG_ROWS / 4; ++rr) {
+            const int row8 = wave + 4 * rr, v = blockIdx.x * EG_ROWS + row8;
+            int nh = 0;
+            for (int i0 = 0; i0 < nw; i0 += 64) {
+                const int i = i0 + lane;
+                const bool m = i < nw && stok[i] == v;
+                const unsigned long long bal = __ballot(m);
+                if (m) shits[row8][nh + __popcll(bal & ((1ull << lane) - 1ull))] = w0 + i;
+                nh += __popcll(bal);
+            }
+            if (lane == 0) snh[row8] = nh;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int row8 = 0; row8 < EG_ROWS; ++row8) {
+            const int nh = snh[row8];
+            if (!ev) continue;
+            for (int h0 = 0; h0 < nh; h0 += 8) {
+                f32x4 g[8], x[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const size_t off = (size_t)shits[row8][min(h0 + u, nh - 1)] * E + e;
+                    g[u] = sum_slabs4(demb, ns, slab_stride, off);
+                    if (relu) x[u] = *reinterpret_cast<const f32x4*>(emb + off);
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (h0 + u < nh) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) s[row8][j] += (!relu || x[u][j] > 0.f) ? g[u][j] * scale : 0.f;
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int row8 = 0; row8 < EG_ROWS; ++row8) {
+        const int v = blockIdx.x * EG_ROWS + row8;
+        if (v < V && ev) *reinterpret_cast<f32x4*>(dE + (size_t)v * E + e) = s[row8];
+    }
+}
+
+// host side: grid, LDS size (above the 64 KB default the kernel needs the explicit opt-in); longer token lists: the windowed form
 inline hipError_t embed_grad_launch(hipStream_t st, const int64_t* tok, int n_tok, const float* demb, int ns, size_t slab_stride,
                                     const float* emb, float scale, int E, float* dE, int V, int relu, const int* rows_live = nullptr) {
     const size_t lds = sizeof(int) * (1 + EG_ROWS) * (size_t)n_tok;
-    if (lds > 160 * 1024 - 1024) return hipErrorInvalidValue;
+    if (lds > 160 * 1024 - 1024) {
+        if (E > 1024 || E % 4 != 0) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(embed_grad_win_kernel, dim3((V + EG_ROWS - 1) / EG_ROWS), dim3(256), 0, st, tok, n_tok, demb, ns, slab_stride, emb, scale,
+                           E, dE, V, relu, rows_live);
+        return hipSuccess;
+    }
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(embed_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

@@ -59,16 +59,18 @@ int Butd::ensure_train(int B, int T) {
     ICZ_TRY(alloc_loss_buffers(mem, TB, B, T));
     ICZ_TRY(alloc((void**)&tb.nany, sizeof(int) * T));
     ICZ_TRY(alloc((void**)&tb.img2, sizeof(int32_t) * B));
+    ICZ_TRY(alloc((void**)&tb.imgk, sizeof(int32_t) * B));
     ICZ_TRY(alloc((void**)&tb.dGtd, sizeof(float) * TB * 4 * H));
     ICZ_TRY(alloc((void**)&tb.dGlm, sizeof(float) * TB * 4 * H));
     ICZ_TRY(alloc((void**)&tb.dDec, sizeof(float) * TB * A));
     ICZ_TRY(alloc((void**)&tb.dEmb, sizeof(float) * TB * E));
     ICZ_TRY(alloc((void**)&tb.dH2d, sizeof(float) * TB * H));
     ICZ_TRY(alloc((void**)&tb.dEnc, sizeof(float) * (size_t)B * R * A));
+    ICZ_TRY(alloc((void**)&tb.dEncImg, sizeof(float) * (size_t)(B / 2) * R * A));      // sample_n: at most B / 2 images (K >= 2)
     ICZ_TRY(alloc((void**)&tb.dwaff, sizeof(float) * (size_t)B * ATT_PARTS * A));
     ICZ_TRY(alloc((void**)&tb.dalpha, sizeof(float) * (size_t)B * R * cdiv((int)D, DALPHA_COLS)));
     ICZ_TRY(alloc((void**)&tb.dS, sizeof(float) * TB * R));
-    ICZ_TRY(alloc((void**)&tb.dGsum, sizeof(float) * (size_t)B * 4 * H));
+    ICZ_TRY(alloc((void**)&tb.dGsum, sizeof(float) * (size_t)(B + B / 2) * 4 * H));     // + sample_n's per-image sums behind the B rows
     for (int i = 0; i < 2; ++i) {
         ICZ_TRY(alloc((void**)&tb.dc1[i], sizeof(float) * (size_t)B * H));
         ICZ_TRY(alloc((void**)&tb.dc2[i], sizeof(float) * (size_t)B * H));
@@ -132,6 +134,10 @@ int Butd::train_step(const float* feats, int rows, int Bs, int t, bool train, hi
     s.drop_att = make_drop(d_seed, train, rng.att_mask, Bd * R * A, RNG_ATT, t, row0);
     s.drop_out = make_drop(d_seed, train, rng.out_mask, Bd * H, RNG_OUT, t, row0);
     if (row0 > 0) s.img_of_row = tb.img2;
+    else if (cur_K > 1) {             // sample_n: K rows per image
+        s.img_of_row = tb.imgk;
+        s.rows_per_img = group_att ? cur_K : 1;
+    }
     s.pred_nsplit = pred_nsplit;
     s.skip_predict = skip_predict;
     s.live = live;
@@ -146,7 +152,7 @@ int Butd::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* se
     rng = *r;
     hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
     mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_feats = feats;
-    cur_rows = B; cur_row0 = 0;
+    cur_rows = B; cur_row0 = 0; cur_K = 1; cur_nimg = B;
     rows_t.assign(T, B);
     cur_seq = seq_out; cur_logp = logp_out;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
@@ -158,6 +164,42 @@ int Butd::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* se
 int Butd::sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st) {
     ICZ_TRY(prologue(feats, B, st));
     return sample_chain(feats, B, T, seq_out, logp_out, st);
+}
+
+__global__ void imgk_init_kernel(int32_t* imgk, int rows, int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rows) imgk[i] = i / K;
+}
+
+// Multi-sample SCST rollout (beyond the reference: the "new self-critical" variant, K sampled captions per image): the per-image
+// prologue runs once over the B images, the sampled chain over B K decoder rows, row = img * K + k, whose kernels find their image's
+// hoisted tensors / features through tb.imgk (the grouped attention kernels take the K rows of an image in one workgroup).  Dropout
+// keep-bits and draws are indexed by the row in the B K space: row img * K + k gets what row img * K + k of
+// sample(feats.repeat_interleave(K, 0)) gets.
+int Butd::sample_n(const float* feats, int B, int K, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st) {
+    ICZ_REQUIRE(feats && seq_out && logp_out && r, "butd sample_n: null argument");
+    ICZ_REQUIRE(K >= 2 && K <= ATT_CTX_MAX_G, "butd sample_n: K=%d samples per image outside 2..%d", K, ATT_CTX_MAX_G);
+    ICZ_REQUIRE(B > 0 && T > 0, "butd sample_n: bad B/T");
+    ICZ_REQUIRE((int64_t)B * K <= dims.max_rows, "butd sample_n: %d images x %d samples exceed the row capacity %d", B, K, dims.max_rows);
+    ICZ_REQUIRE(fresh, "butd: call icz_butd_refresh_weights after binding/updating parameters");
+    const int rows = B * K;
+    ICZ_TRY(ensure_train(rows, T));
+    rng = *r;
+    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
+    mode = 1; cur_B = rows; cur_T = T; cur_train = true; cur_feats = feats;
+    cur_rows = rows; cur_row0 = 0; cur_K = K; cur_nimg = B;
+    rows_t.assign(T, rows);
+    cur_seq = seq_out; cur_logp = logp_out;
+    const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
+    if (explicit_rng || !use_graphs) return sample_n_impl(feats, B, K, T, seq_out, logp_out, st);
+    const std::vector<uintptr_t> key = {5, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)K, (uintptr_t)T, (uintptr_t)seq_out, (uintptr_t)logp_out, opt_bits()};
+    return gc.run(key, st, [&](hipStream_t s) { return sample_n_impl(feats, B, K, T, seq_out, logp_out, s); });
+}
+
+int Butd::sample_n_impl(const float* feats, int B, int K, int T, int64_t* seq_out, float* logp_out, hipStream_t st) {
+    ICZ_TRY(prologue(feats, B, st));
+    hipLaunchKernelGGL(imgk_init_kernel, dim3(cdiv(B * K, 256)), dim3(256), 0, st, tb.imgk, B * K, K);
+    return sample_chain(feats, B * K, T, seq_out, logp_out, st);
 }
 
 // Greedy baseline and sampled rollout of one SCST step (Engine.py:258-262) as two concurrent chains: they share the
@@ -176,7 +218,7 @@ int Butd::rollouts(const float* feats, int B, int T, const icz_rng* r, int64_t* 
     rng = *r;
     hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
     mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_feats = feats;
-    cur_rows = merged ? 2 * B : B; cur_row0 = merged ? B : 0;
+    cur_rows = merged ? 2 * B : B; cur_row0 = merged ? B : 0; cur_K = 1; cur_nimg = B;
     rows_t.assign(T, B);
     cur_seq = seq_out; cur_logp = logp_out;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
@@ -283,7 +325,8 @@ int Butd::sample_backward(const float* reward, const icz_butd_params* G, float* 
     if (explicit_rng || !use_graphs) return sample_backward_impl(reward, *G, loss_out, mask_sum_out, st);
     std::vector<uintptr_t> key = {3, (uintptr_t)reward, (uintptr_t)loss_out, (uintptr_t)mask_sum_out, (uintptr_t)cur_B, (uintptr_t)cur_T,
                                   (uintptr_t)cur_feats, (uintptr_t)cur_seq, (uintptr_t)cur_logp,
-                                  (uintptr_t)cur_rows, (uintptr_t)cur_row0};      // merged / unmerged rollouts share the caller's buffers: slot strides differ
+                                  (uintptr_t)cur_rows, (uintptr_t)cur_row0,       // merged / unmerged rollouts share the caller's buffers: slot strides differ
+                                  (uintptr_t)cur_K};                              // sample_n of B K rows against sample of B K rows: other kernels
     const float* const* gp = reinterpret_cast<const float* const*>(G);
     for (size_t i = 0; i < sizeof(icz_butd_params) / sizeof(float*); ++i) key.push_back((uintptr_t)gp[i]);
     const icz_butd_params Gc = *G;
@@ -321,7 +364,7 @@ int Butd::xe_forward(const float* feats, const int64_t* captions, int B, int L, 
     ICZ_REQUIRE(!train || r, "butd xe_forward: training mode needs an icz_rng");
     begin_xe(lengths, B, T, L, captions, train != 0, rng.seed, st);
     cur_feats = feats;
-    cur_rows = B; cur_row0 = 0;
+    cur_rows = B; cur_row0 = 0; cur_K = 1; cur_nimg = B;
     const size_t H = dims.H;
     const size_t Vp = round4(dims.V);
     ICZ_TRY(prologue(feats, B, st));
@@ -465,6 +508,10 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     const size_t sH = (size_t)Bs * H;
     // backward of a sampled rollout: the GEMMs over all (t, b) rows stop behind the last step the rollout ran (GemmArgs::rows_live)
     const int* const rl = (bptt_early_out && early_out) ? live_rows : nullptr;
+    // behind sample_n: K rows per image (row = img * K + k) -- the kernels that read the image's features / enc_ctx per row find it
+    // through tb.imgk, and the image-side products (d enc_ctx, the mean-feature weights) are folded onto the n_img images first
+    const int K = cur_K, n_img = K > 1 ? cur_nimg : B;
+    const int32_t* const imgk = K > 1 ? tb.imgk : nullptr;
 
     // ---- predict layer, all time steps at once.  d h2drop feeds the BPTT chain; the weight / bias gradients of
     //      `predict` depend only on dlogits, so they run on the side stream concurrently with the (skinny,
@@ -571,8 +618,8 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
         }
         {   // attention backward
             const int dparts = cdiv(D, DALPHA_COLS);
-            hipLaunchKernelGGL(att_bwd_dalpha_kernel, dim3(bt, dparts), dim3(256), 0, st, tb.X[0], ns1, D + H, bt, feats, R, D, tb.dalpha, live);
-            AttBwdDdecArgs da = {enc_ctx, tb.dec + slot * A, w_aff, tb.alpha + slot * R, tb.dalpha, tb.dDec + slot * A, tb.dS + slot * R, R, A, dparts, live};
+            hipLaunchKernelGGL(att_bwd_dalpha_kernel, dim3(bt, dparts), dim3(256), 0, st, tb.X[0], ns1, D + H, bt, feats, R, D, tb.dalpha, live, imgk);
+            AttBwdDdecArgs da = {enc_ctx, tb.dec + slot * A, w_aff, tb.alpha + slot * R, tb.dalpha, tb.dDec + slot * A, tb.dS + slot * R, R, A, dparts, live, imgk};
             hipLaunchKernelGGL(att_bwd_ddec_kernel, dim3(bt, cdiv(A, 256)), dim3(256), 0, st, da, d_att);
             // X2 = dDec . w_dec   [bt, H]
             GemmArgs g = {};
@@ -689,7 +736,13 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     if (td_grouped) ICZ_TRY(gemm_tn_grouped(tb.dGtd, 4 * H, 4 * H, TB, td_groups, 3, rl, st));
     else ICZ_TRY(wgrad(tb.dGtd, 4 * H, 4 * H, tb.h2, H, H, TB, G.td_w_ih, ldtd, st, rl));
     hipLaunchKernelGGL(timesum_kernel, dim3(cdiv((int)((size_t)Bs * 4 * H / 4), 256)), dim3(256), 0, st, tb.dGtd, T, (size_t)Bs * 4 * H, tb.dGsum);
-    ICZ_TRY(wgrad(tb.dGsum + (size_t)roff * 4 * H, 4 * H, 4 * H, mean, D, D, B, G.td_w_ih + H, ldtd, st));      // mean features
+    if (K > 1) {      // sample_n: the K rows of an image share its mean features -- their time sums are added in k order first
+        float* const gimg = tb.dGsum + (size_t)Bs * 4 * H;
+        const size_t N4 = (size_t)4 * H;
+        hipLaunchKernelGGL(rowgroup_sum_kernel, dim3(cdiv((int)((size_t)n_img * N4 / 4), 256)), dim3(256), 0, st, (const float*)tb.dGsum, n_img, K, N4, gimg);
+        ICZ_TRY(wgrad(gimg, 4 * H, 4 * H, mean, D, D, n_img, G.td_w_ih + H, ldtd, st));
+    } else
+        ICZ_TRY(wgrad(tb.dGsum + (size_t)roff * 4 * H, 4 * H, 4 * H, mean, D, D, B, G.td_w_ih + H, ldtd, st));      // mean features
     if (!td_grouped) {
         ICZ_TRY(wgrad(tb.dGtd, 4 * H, 4 * H, tb.emb, E, E, TB, G.td_w_ih + H + D, ldtd, st, rl));
         ICZ_TRY(wgrad(tb.dGtd, 4 * H, 4 * H, tb.h1, H, H, TB, G.td_w_hh, H, st, rl));
@@ -718,10 +771,23 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     ICZ_TRY(wgrad(tb.dDec, A, A, tb.h1 + sH, H, H, TB, tb.dWdec, H, st));
     {   // d enc_ctx (sum over time) and the affine-weight partials, from the ds_t recorded by the loop
         AttBwdDencArgs ea = {enc_ctx, tb.dec + (size_t)roff * A, tb.dS + (size_t)roff * R, w_aff, tb.dEnc, tb.dwaff, B, R, A, T,
-                             cur_train ? (rng.att_mask ? 1 : 2) : 0, rng.att_mask, (size_t)B * R * A, d_seed, (uint32_t)RNG_ATT, Bs};
-        hipLaunchKernelGGL(att_bwd_denc_kernel<20>, dim3(B, ATT_PARTS), dim3(256), sizeof(float) * T * R, st, ea);
+                             cur_train ? (rng.att_mask ? 1 : 2) : 0, rng.att_mask, (size_t)B * R * A, d_seed, (uint32_t)RNG_ATT, Bs, imgk};
+        if (K > 1 && group_att) {       // sample_n, grouped: the K rows of an image in one workgroup, summed into d enc_ctx[img]
+            ea.denc = tb.dEncImg;
+            hipLaunchKernelGGL(att_bwd_denc_group_kernel<20>, dim3(n_img, ATT_PARTS), dim3(256), sizeof(float) * T * R, st, ea, K);
+        } else {
+            hipLaunchKernelGGL(att_bwd_denc_kernel<20>, dim3(B, ATT_PARTS), dim3(256), sizeof(float) * T * R, st, ea);
+            if (K > 1) {                // sample_n, per row: d enc_ctx of the B K rows, then the K rows of an image added in k order
+                const size_t N = (size_t)R * A;
+                hipLaunchKernelGGL(rowgroup_sum_kernel, dim3(cdiv((int)((size_t)n_img * N / 4), 256)), dim3(256), 0, st, (const float*)tb.dEnc,
+                                   n_img, K, N, tb.dEncImg);
+            }
+        }
     }
-    ICZ_TRY(wgrad(tb.dEnc, A, A, feats, D, D, B * R, tb.dWenc, D, st));
+    const float* const denc = K > 1 ? tb.dEncImg : tb.dEnc;
+    // d affine partials: one [parts, A] block per decoder row, or per image behind the grouped kernel
+    const int waff_rows = (K > 1 && group_att ? n_img : B) * ATT_PARTS;
+    ICZ_TRY(wgrad(denc, A, A, feats, D, D, n_img * R, tb.dWenc, D, st));
     {   // bias gradients: five column sums (+ the b_hh copies, + the identically zero affine bias: softmax shift invariance) in one launch
         ColsumTable ct = {};
         int nb = 0;
@@ -732,8 +798,8 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
         add(tb.dGtd, TB, 4 * H, 4 * H, G.td_b_ih, G.td_b_hh);
         add(tb.dGlm, TB, 4 * H, 4 * H, G.lm_b_ih, G.lm_b_hh);
         add(tb.dDec, TB, A, A, G.dec_att_b, nullptr);
-        add(tb.dEnc, B * R, A, A, G.enc_att_b, nullptr);
-        add(tb.dwaff, B * ATT_PARTS, A, A, tb.dWaff, nullptr);
+        add(denc, n_img * R, A, A, G.enc_att_b, nullptr);
+        add(tb.dwaff, waff_rows, A, A, tb.dWaff, nullptr);
         add(tb.dwaff, 0, 1, 1, G.affine_b, nullptr);
         hipLaunchKernelGGL(colsum_multi_kernel, dim3(nb), dim3(256), 0, st, ct);
     }
@@ -778,6 +844,12 @@ int icz_butd_sample(icz_butd_t* h, const float* feats, int32_t B, int32_t max_le
                     int64_t* seq_out, float* logprobs_out, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Butd*>(h)->sample(feats, B, max_len, rng, seq_out, logprobs_out, (hipStream_t)stream);
+}
+int icz_butd_sample_n(icz_butd_t* h, const float* feats, int32_t B, int32_t K, int32_t max_len, const icz_rng* rng,
+                      int64_t* seq_out, float* logprobs_out, void* stream) {
+    ICZ_REQUIRE(K >= 2 && K <= ATT_CTX_MAX_G, "icz_butd_sample_n: K=%d samples per image outside 2..%d", K, ATT_CTX_MAX_G);
+    ICZ_REQUIRE(h, "icz_butd_sample_n: null handle");
+    return reinterpret_cast<Butd*>(h)->sample_n(feats, B, K, max_len, rng, seq_out, logprobs_out, (hipStream_t)stream);
 }
 int icz_butd_scst_rollouts(icz_butd_t* h, const float* feats, int32_t B, int32_t max_len, const icz_rng* rng,
                            int64_t* greedy_ids_out, int64_t* seq_out, float* logprobs_out, void* stream) {

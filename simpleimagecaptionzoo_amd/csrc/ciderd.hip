@@ -45,7 +45,8 @@ struct CiderArgs {
     const int32_t* img_slot;     // [B] slot of image b in the reference store, or null = b (the arrays below are the batch's own)
     const int32_t* img_ref_ptr; const int32_t* ref_ent_ptr; const int32_t* ent_key; const int32_t* ent_order;
     const double* ent_w; const double* ref_norm; const int32_t* ref_len;
-    double* scores;      // [2B]
+    double* scores;      // [2B] ([B] without greedy)
+    int rows_per_img;    // hypothesis b belongs to image b / rows_per_img (img_slot index; 0 = 1): the multi-sample reward
 };
 
 __global__ __launch_bounds__(64 * CD_NW) void ciderd_kernel(CiderArgs a) {
@@ -59,7 +60,8 @@ __global__ __launch_bounds__(64 * CD_NW) void ciderd_kernel(CiderArgs a) {
     constexpr int NT = 64 * CD_NW;
     const int hyp = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = hyp % a.B;
-    const bool is_greedy = hyp >= a.B;
+    const bool is_greedy = hyp >= a.B;            // (no greedy hypotheses without a.greedy: B blocks)
+    const int bi = a.rows_per_img > 1 ? b / a.rows_per_img : b;
     const int64_t* ids = (is_greedy ? a.greedy : a.gen) + (size_t)b * a.T;
     // ---- sentence length (Utils.py:337-356)
     int len;
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(64 * CD_NW) void ciderd_kernel(CiderArgs a) {
     }
     __syncthreads();
     // ---- references of this image, CD_NW at a time: wave w takes reference rc + w
-    const int slot = a.img_slot ? a.img_slot[b] : b;
+    const int slot = a.img_slot ? a.img_slot[bi] : bi;
     const int r0 = a.img_ref_ptr[slot], r1 = a.img_ref_ptr[slot + 1];
     double score[4] = {0.0, 0.0, 0.0, 0.0};
     for (int rc = r0; rc < r1; rc += CD_NW) {
@@ -193,6 +195,20 @@ __global__ void ciderd_reward_kernel(const double* __restrict__ scores, int B, i
     if (i >= B * T) return;
     int b = i / T;
     reward[i] = (float)(scores[b] - scores[B + b]);
+}
+
+// Leave-one-out baseline of the multi-sample reward (the "new self-critical" variant): hypothesis i = img * K + k,
+//   base_i = (sum_{j != i, ascending j} s_j) / (K - 1)   over the K hypotheses of its image,   reward[i, :] = (float)(s_i - base_i)
+// in float64, the sum in a fixed order (one thread per element recomputes its row's K - 1 terms: K <= 8).
+__global__ void ciderd_loo_kernel(const double* __restrict__ scores, int BK, int K, int T, float* __restrict__ reward) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= BK * T) return;
+    const int h = i / T, j0 = h - h % K;
+    double s = 0.0;
+    for (int j = j0; j < j0 + K; ++j)
+        if (j != h) s += scores[j];
+    const double base = s / (double)(K - 1);
+    reward[i] = (float)(scores[h] - base);
 }
 
 }  // namespace icz
@@ -382,6 +398,28 @@ int icz_ciderd_reward(icz_ciderd_t* h, const int64_t* gen, const int64_t* greedy
                       float* reward_out, double* scores_out, void* stream) {
     return ciderd_reward_impl(h, gen, greedy, B, T, nullptr, img_ref_ptr, ref_ent_ptr, ent_key, ent_order, ent_w, ref_norm, ref_len,
                               reward_out, scores_out, stream);
+}
+
+int icz_ciderd_reward_loo(icz_ciderd_t* h, const int64_t* gen, int32_t B, int32_t K, int32_t T, const int32_t* img_slot,
+                          const int32_t* img_ref_ptr, const int32_t* ref_ent_ptr, const int32_t* ent_key, const int32_t* ent_order,
+                          const double* ent_w, const double* ref_norm, const int32_t* ref_len, float* reward_out, double* scores_out,
+                          void* stream) {
+    ICZ_REQUIRE(K >= 2 && K <= 8, "icz_ciderd_reward_loo: K=%d samples per image outside 2..8", K);
+    ICZ_REQUIRE(h, "icz_ciderd_reward_loo: null handle");
+    ICZ_REQUIRE(gen && img_slot && img_ref_ptr && ref_ent_ptr && ent_key && ent_order && ent_w && ref_norm && ref_len && reward_out,
+                "icz_ciderd_reward_loo: null argument");
+    ICZ_REQUIRE(scores_out, "icz_ciderd_reward_loo: scores_out (B K float64 scratch) is required");
+    ICZ_REQUIRE(B > 0 && T > 0 && T <= CD_MAXT, "icz_ciderd_reward_loo: B=%d, T=%d out of range (T 1..%d)", B, T, CD_MAXT);
+    ICZ_REQUIRE((int64_t)B * K * T < (1ll << 31), "icz_ciderd_reward_loo: B K T too large");
+    CiderD* c = reinterpret_cast<CiderD*>(h);
+    const int BK = B * K;
+    CiderArgs a = {c->keys, c->idf, c->penalty, c->cap, c->default_idf, gen, nullptr, BK, T, img_slot,
+                   img_ref_ptr, ref_ent_ptr, ent_key, ent_order, ent_w, ref_norm, ref_len, scores_out, K};
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ciderd_kernel, dim3(BK), dim3(64 * CD_NW), 0, st, a);
+    hipLaunchKernelGGL(ciderd_loo_kernel, dim3(cdiv(BK * T, 256)), dim3(256), 0, st, (const double*)scores_out, BK, K, T, reward_out);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
 }
 
 int icz_ciderd_reward_indexed(icz_ciderd_t* h, const int64_t* gen, const int64_t* greedy, int32_t B, int32_t T,

@@ -406,11 +406,25 @@ class BUTDDetection_Eng(Engine):
         return losses
 
     # ---- E2 -------------------------------------------------------------------------------------------------
-    def SCST_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None):
-        with _on_stream(self):
-            return self._scst_training_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs)
+    # decoders whose handle has the multi-sample rollout (icz_butd_sample_n); AoA and NIC do not
+    _multi_sample = True
 
-    def _scst_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None):
+    def SCST_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=None):
+        """samples_per_image (beyond the reference): None = the reference's step (one sampled caption per image, greedy baseline);
+        K = 2..8 = the multi-sample variant: K sampled captions per image, each baselined by the mean CIDEr-D of the other K - 1,
+        no greedy rollout (BUTD decoders only)."""
+        if samples_per_image is not None:
+            k = samples_per_image
+            if not self._multi_sample:
+                raise ValueError("samples_per_image: the %s decoder has no multi-sample SCST rollout (BUTD only); pass "
+                                 "samples_per_image=None" % type(self).__name__)
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= int(k) <= 8:
+                raise ValueError("samples_per_image must be None or an integer in 2..8, got %r" % (k,))
+            samples_per_image = int(k)
+        with _on_stream(self):
+            return self._scst_training_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs, samples_per_image)
+
+    def _scst_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=None):
         """Engine.py:251-272: greedy baseline (eval mode) + multinomial rollout (train mode) + CIDEr-D reward +
         REINFORCE + clamp 0.25 + Adam, all on the device; `criterion` (RewardCriterion) is implied."""
         self.model.train()
@@ -423,7 +437,7 @@ class BUTDDetection_Eng(Engine):
         monitor = _monitor(dataloader, "Training Process", tqdm_visible)
         losses = []
         try:
-            self._scst_steps(monitor, scorer, optimizer, rngs, tqdm_visible, losses)
+            self._scst_steps(monitor, scorer, optimizer, rngs, tqdm_visible, losses, samples_per_image)
         finally:
             restore()
         return losses
@@ -444,7 +458,7 @@ class BUTDDetection_Eng(Engine):
             return {}
         return {n: sum(m[i].elapsed_time(m[i + 1]) for m in steps) / len(steps) for i, n in enumerate(names)}
 
-    def _scst_steps(self, monitor, scorer, optimizer, rngs, tqdm_visible, losses):
+    def _scst_steps(self, monitor, scorer, optimizer, rngs, tqdm_visible, losses, samples_per_image=None):
         for batch_i, (img_ids, img_tensors, img_gts, supp_info_datas) in enumerate(monitor):
             visual_inputs = self.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
             feats = self._features(visual_inputs)
@@ -452,9 +466,14 @@ class BUTDDetection_Eng(Engine):
             rng = rngs[batch_i] if rngs is not None else self.model._next_rng()
             marks = [] if self.phase_events is not None else None
             self._mark(marks)
-            greedy_res, seq_gen, seq_logprobs = h.rollouts(feats, 20, rng)
-            self._mark(marks)
-            rewards = scorer.reward(seq_gen, greedy_res, img_gts, img_ids)
+            if samples_per_image is None:
+                greedy_res, seq_gen, seq_logprobs = h.rollouts(feats, 20, rng)
+                self._mark(marks)
+                rewards = scorer.reward(seq_gen, greedy_res, img_gts, img_ids)
+            else:       # K sampled captions per image (rows img * K + k), each baselined by the mean reward of the other K - 1
+                seq_gen, seq_logprobs = h.sample_n(feats, samples_per_image, 20, rng)
+                self._mark(marks)
+                rewards = scorer.reward_loo(seq_gen, samples_per_image, img_gts, img_ids)
             self._mark(marks)
             grads = self._grads()
             msum_glob = 0.0
@@ -536,6 +555,7 @@ class AoADetection_Eng(BUTDDetection_Eng):
 
     # the AoA library's callback stages (include/icz.h: icz_aoa_set_grad_callback): 41 MB + 92 MB of the 163 MB of decoder gradients are
     # on the wire before the backward call returns; the attention block and h_norm (30 MB) follow after it
+    _multi_sample = False
     _GRAD_STAGES = (("decoder.predict.weight_v", "decoder.predict.weight_g", "decoder.predict.bias"),
                     ("decoder.embed.0.weight", "decoder.lstm.weight_ih", "decoder.lstm.weight_hh", "decoder.lstm.bias_ih", "decoder.lstm.bias_hh"))
 
@@ -556,6 +576,8 @@ class NIC_Eng(BUTDDetection_Eng):
     """ModelEngines/NIC_Engine.py (= the base Engine) with the three hot methods on the NIC decoder handle.  The CNN encoder +
     img_embedding of NIC_Model.py:8-37 is outside the path: batches carry the image embedding -- `supp_info_datas =
     {'img_feats': (B, embed_dim) tensor}` -- or the Captioner was given an `encoder` module for `img_tensors`."""
+
+    _multi_sample = False
 
     def model_construction(self, max_batch):
         from .nic import NICDecoder_Captioner
