@@ -192,6 +192,31 @@ int icz_butd_xe_backward_dlogits(icz_butd_t* h, const float* dpacked, const icz_
 int icz_butd_beam_search(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
                          float* seqs_out, int32_t* lens_out, void* stream);
 
+/* Options of the icz_*_beam_search_opts entries (the same search, every step as above):
+ *   n_best       1..beam: hypotheses returned per image.  Each image ends with exactly `beam` of them (the retired ones and those
+ *                live at the step limit), ranked finished before live, then by normalised score (descending), then by order of
+ *                retirement (step, then merge rank; live ones in beam order).
+ *   block_ngram  0 (off), 2, 3 or 4: a beam with prefix y_0..y_s may not take v if (y_{s-n+2}, ..., y_s, v) already occurs in the
+ *                prefix.  A banned token scores -inf after the log-softmax (whose normaliser still runs over the whole vocabulary),
+ *                so every score stays the model's log-probability of its tokens.  The first step has no bans.
+ *   lp_kind      0 none, 1 avg (score / len^alpha), 2 wu (score / ((5 + len) / 6)^alpha), len = generated tokens with <end>
+ *                (lens - 1), fp32.  It changes only the final ranking, never which beams expand, retire or survive.
+ *   lp_alpha     >= 0, finite.
+ * {1, 0, 0, 0} is icz_*_beam_search bit for bit. */
+typedef struct {
+    int32_t n_best;
+    int32_t block_ngram;
+    int32_t lp_kind;   /* 0 none, 1 avg, 2 wu */
+    float lp_alpha;
+} icz_beam_opts;
+
+/* Beam search with options: seqs_out [n_img, n_best, max_steps+1] float32 (zero-padded), lens_out [n_img, n_best] int32,
+ * scores_out [n_img, n_best] float32 raw summed log-probabilities.  Argument errors (null handle / argument / options, n_best
+ * outside 1..beam, block_ngram not in {0, 2, 3, 4}, lp_kind unknown, lp_alpha negative or not finite) return ICZ_ERR_INVALID
+ * before any device work. */
+int icz_butd_beam_search_opts(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                              const icz_beam_opts* opts, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream);
+
 /* One decoder step from an explicit state (BUTD_Model.py:172-182) -- exposed for the per-kernel parity tests.
  * it [B] int64; state tensors [B,H] are updated in place; ctx_out [B,D], alpha_out [B,R], logits_out [B,V]. */
 int icz_butd_step(icz_butd_t* h, const float* feats, int32_t B, const int64_t* it, float* h1, float* c1,
@@ -236,6 +261,9 @@ int icz_nic_set_scheduled_sampling(icz_nic_t* h, float ss_prob, const float* gat
 /* DecoderRNN.beam_search_sample, NIC_Model.py:153-212 (batched over images) */
 int icz_nic_beam_search(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps, float* seqs_out,
                         int32_t* lens_out, void* stream);
+/* ... with options (icz_beam_opts, see icz_butd_beam_search_opts) */
+int icz_nic_beam_search_opts(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps,
+                             const icz_beam_opts* opts, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * AoADetection captioner (Models/AoA_Model.py:657-753): img_feats_porjection (Linear 2048->Hd + ReLU + Dropout) ->
@@ -300,6 +328,8 @@ int icz_aoa_refine(icz_aoa_t* h, const float* feats, int32_t B, float* refined_o
 int icz_aoa_greedy(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, int64_t* ids_out, void* stream);
 int icz_aoa_beam_search(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, float* seqs_out,
                         int32_t* lens_out, void* stream);
+int icz_aoa_beam_search_opts(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                             const icz_beam_opts* opts, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream);
 int icz_aoa_sample(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, const icz_aoa_rng* rng, int64_t* seq_out,
                    float* logprobs_out, void* stream);
 /* The two decodes of one SCST step (Engine.py:256-261: greedy in eval mode, sampler_rl in train mode) as concurrent chains. */

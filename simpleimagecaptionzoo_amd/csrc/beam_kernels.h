@@ -16,7 +16,32 @@ struct BeamArgs {
     int64_t* it_next;       // [n_img*k]
     float* best_score; int* best_len; int32_t* best_seq; int* has_complete;   // best finished hypothesis per image
     int* n_live;            // [1] number of images that still have active beams after this step
+    // n-best list (null = off): every retirement of image img in order, slot img * k + h, h < hyp_cnt[img] <= k
+    int32_t* hyp_seq; float* hyp_score; int* hyp_len; int* hyp_cnt;      // [n_img,k,L] [n_img,k] [n_img,k] [n_img]
 };
+
+// n-gram blocking (ngram = n > 0): the row with prefix y_0 .. y_s (s = step - 1) may not take token v when the n-gram
+// (y_{s-n+2} .. y_s, v) already occurs in the prefix.  The first s - n + 2 threads test one start position i each and append
+// y_{i+n-1} to the LDS list on a match (duplicates are harmless); at most step - n + 1 <= 255 entries, usually none.  Returns the
+// count.  Called by every thread of the workgroup (it synchronises), with step >= ngram.
+__device__ inline int beam_ban_list(const int32_t* __restrict__ prefix, int step, int ngram, int* s_ban, int* s_nban) {
+    if (threadIdx.x == 0) *s_nban = 0;
+    __syncthreads();
+    const int s = step - 1, i = threadIdx.x;
+    if (i < s - ngram + 2) {
+        bool hit = true;
+        for (int t = 0; t < ngram - 1; ++t) hit &= prefix[i + t] == prefix[s - ngram + 2 + t];
+        if (hit) s_ban[atomicAdd(s_nban, 1)] = prefix[i + ngram - 1];
+    }
+    __syncthreads();
+    return *s_nban;
+}
+
+__device__ inline bool beam_banned(int v, const int* s_ban, int nban) {
+    bool b = false;
+    for (int q = 0; q < nban; ++q) b |= s_ban[q] == v;
+    return b;
+}
 
 // Beam expand / prune of one step (:271-300) in two launches:
 //   beam_rowtopk_kernel  grid (n_img * k): one workgroup per decoder row -> its log-softmax normaliser and its own best
@@ -24,16 +49,23 @@ struct BeamArgs {
 //   beam_merge_kernel    grid (n_img), one wave: top-n_act of the <= k*k row candidates (ties -> lower flat index r*V+v,
 //                        the order of a top-k over the flattened [k, V] scores), retire finished beams, compact the rest
 // The global top-n_act are contained in the union of the per-row top-n_act, so the result equals a search over all k*V.
+// Blocking (ngram > 0, from step ngram on; seqs_in / L: the rows' prefixes): a banned token scores -inf after the log-softmax,
+// whose normaliser still runs over the whole row.  Here a banned token is skipped where it would enter a thread's list; BAN = false
+// (no list this step) compiles the kernel without the test (the list check costs it 20 VGPRs and its occupancy).
+template <bool BAN>
 __global__ __launch_bounds__(256) void beam_rowtopk_kernel(const float* __restrict__ logits, int V, int ldl, int k, int step,
                                                            const int* __restrict__ n_act, const float* __restrict__ run,
-                                                           float* __restrict__ cand_val, int* __restrict__ cand_idx, int compact) {
+                                                           float* __restrict__ cand_val, int* __restrict__ cand_idx, int compact,
+                                                           const int32_t* __restrict__ seqs_in, int L, int ngram) {
     __shared__ float smf[4];
     __shared__ float s_val[4];
     __shared__ int s_idx[4], s_who[4];
+    __shared__ int s_ban[256], s_nban;
     const int row = blockIdx.x, img = row / k, r = row % k, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int na = n_act[img];
     const int nr = (step == 1) ? 1 : na;          // step 1 scores row 0 only (:273-274)
     if (r >= nr) return;
+    const int nban = BAN ? beam_ban_list(seqs_in + (size_t)row * L, step, ngram, s_ban, &s_nban) : 0;
     const float* l = logits + (size_t)(compact ? img : row) * ldl;      // compact (step 1 only): one decoder row per image
     // Every sweep fetches the thread's strided slice (40 logits at V = 10102) in batches of U independent loads: one memory
     // latency per batch instead of one per element.  (All 40 in registers across the three sweeps: the unrolled kernel
@@ -79,6 +111,7 @@ __global__ __launch_bounds__(256) void beam_rowtopk_kernel(const float* __restri
             float val = rs + ((x[u] - mx) - ls);
             int idx = v0 + 256 * u;
             if (!(val > worst || (val == worst && idx < worst_i))) continue;
+            if (BAN && nban && beam_banned(idx, s_ban, nban)) continue;
 #pragma unroll
             for (int j = 0; j < BEAM_MAX_K; ++j) {          // branch-free insertion: swap down the list
                 const bool take = (j < na) & ((val > tv[j]) | ((val == tv[j]) & (idx < ti[j])));
@@ -130,15 +163,19 @@ __global__ __launch_bounds__(256) void beam_rowtopk_kernel(const float* __restri
 // e.g. constant logits) sends the workgroup through the insertion algorithm on the LDS-staged scores instead.
 // Needs V <= 1024 NV4, 16-byte aligned rows (ldl % 4 == 0).  The log-sum-exp is summed in a different element order than in
 // the kernel above (thread t holds elements 4 (t + 256 u) + j): scores may differ in the last bit.
+// Blocking: the thread that owns a banned token sets its score to -inf before its maximum is taken (a fully unrolled select:
+// no dynamic register index), so tau, the candidate list and the overflow path never see it.  The ban list lives at the
+// start of the overflow path's LDS row, which is written only after the list has been read.
 constexpr int BEAM_CAND_CAP = 128;
 template <int NV4>
 __global__ __launch_bounds__(256) void beam_rowtopk_reg_kernel(const float* __restrict__ logits, int V, int ldl, int k, int step,
                                                                const int* __restrict__ n_act, const float* __restrict__ run,
-                                                               float* __restrict__ cand_val, int* __restrict__ cand_idx, int compact) {
+                                                               float* __restrict__ cand_val, int* __restrict__ cand_idx, int compact,
+                                                               const int32_t* __restrict__ seqs_in, int L, int ngram) {
     __shared__ float smf[4];
     __shared__ float s_val[4];
     __shared__ int s_idx[4], s_who[4];
-    __shared__ int s_cnt, s_taken;
+    __shared__ int s_cnt, s_taken, s_nban;
     __shared__ float s_cv[BEAM_CAND_CAP];
     __shared__ int s_ci[BEAM_CAND_CAP];
     extern __shared__ __attribute__((aligned(16))) float s_row[];          // overflow path only: 1024 NV4 floats
@@ -168,14 +205,27 @@ __global__ __launch_bounds__(256) void beam_rowtopk_reg_kernel(const float* __re
     se = block_sum_256(se, smf);
     const float ls = logf(se);
     const float rs = (step == 1) ? 0.f : run[row];
+#pragma unroll
+    for (int u = 0; u < NV4; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[u][j] = rs + ((x[u][j] - mx) - ls);      // the candidate score (beyond V: -inf)
+    if (ngram && step >= ngram) {
+        int* s_ban = reinterpret_cast<int*>(s_row);
+        const int nban = beam_ban_list(seqs_in + (size_t)row * L, step, ngram, s_ban, &s_nban);
+        for (int b = 0; b < nban; ++b) {
+            const int q = s_ban[b] >> 2, bu = q >> 8, bj = s_ban[b] & 3;
+            if ((q & 255) != tid) continue;
+#pragma unroll
+            for (int u = 0; u < NV4; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) x[u][j] = (u == bu && j == bj) ? -INFINITY : x[u][j];
+        }
+    }
     float tmax = -INFINITY;
 #pragma unroll
     for (int u = 0; u < NV4; ++u)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            x[u][j] = rs + ((x[u][j] - mx) - ls);                      // the candidate score (beyond V: -inf)
-            tmax = fmaxf(tmax, x[u][j]);
-        }
+        for (int j = 0; j < 4; ++j) tmax = fmaxf(tmax, x[u][j]);
     // tau: rounds of block maximum over the thread maxima not yet counted, until na of them are
     float tau = -INFINITY;
     {
@@ -277,12 +327,15 @@ __global__ __launch_bounds__(256) void beam_rowtopk_reg_kernel(const float* __re
 }
 
 // per-row candidates of one beam step: the register kernel where the vocabulary fits it, else the sweep kernel
+// (ngram > 0: n-gram blocking on the prefixes seqs_in [rows, L])
 inline void launch_beam_rowtopk(hipStream_t st, int rows, const float* logits, int V, int ldl, int k, int step, const int* n_act,
-                                const float* run, float* cand_val, int* cand_idx, int compact = 0) {
+                                const float* run, float* cand_val, int* cand_idx, int compact = 0, const int32_t* seqs_in = nullptr,
+                                int L = 0, int ngram = 0) {
     const bool ok = ldl % 4 == 0 && ((uintptr_t)logits & 15) == 0;
-    if (ok && V <= 1024 * 3) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<3>), dim3(rows), dim3(256), sizeof(float) * 1024 * 3, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact);
-    else if (ok && V <= 1024 * 10) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<10>), dim3(rows), dim3(256), sizeof(float) * 1024 * 10, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact);
-    else hipLaunchKernelGGL(beam_rowtopk_kernel, dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact);
+    if (ok && V <= 1024 * 3) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<3>), dim3(rows), dim3(256), sizeof(float) * 1024 * 3, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram);
+    else if (ok && V <= 1024 * 10) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<10>), dim3(rows), dim3(256), sizeof(float) * 1024 * 10, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram);
+    else if (ngram && step >= ngram) hipLaunchKernelGGL(beam_rowtopk_kernel<true>, dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram);
+    else hipLaunchKernelGGL(beam_rowtopk_kernel<false>, dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram);
 }
 
 __global__ __launch_bounds__(64) void beam_merge_kernel(BeamArgs a, const float* __restrict__ cand_val, const int* __restrict__ cand_idx) {
@@ -304,8 +357,11 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(BeamArgs a, const float*
     float val = -INFINITY;
     int idx = 0x7fffffff;
     if (cr < nr && cj < na) {
-        val = cand_val[(row0 + cr) * BEAM_MAX_K + cj];
-        idx = cr * V + cand_idx[(row0 + cr) * BEAM_MAX_K + cj];
+        const int ci = cand_idx[(row0 + cr) * BEAM_MAX_K + cj];
+        if (ci < V) {          // a row with fewer than na admissible tokens (every other one banned) leaves empty slots
+            val = cand_val[(row0 + cr) * BEAM_MAX_K + cj];
+            idx = cr * V + ci;
+        }
     }
     for (int j = 0; j < na; ++j) {
         float best = val;
@@ -324,16 +380,25 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(BeamArgs a, const float*
     if (lane == 0) {
         int nn = 0;
         for (int j = 0; j < na; ++j) {
+            if (pick_idx[j] == 0x7fffffff) continue;       // no admissible candidate left for this beam: it ends unfinished and unlisted
             const int src = pick_idx[j] / V, tok = pick_idx[j] % V;
             if (tok == 2) {
+                const int32_t* ss = a.seqs_in + (size_t)(row0 + src) * a.L;
                 if (!a.has_complete[img] || pick_val[j] > a.best_score[img]) {
                     a.has_complete[img] = 1;
                     a.best_score[img] = pick_val[j];
                     a.best_len[img] = a.step + 1;
                     int32_t* bs = a.best_seq + (size_t)img * a.L;
-                    const int32_t* ss = a.seqs_in + (size_t)(row0 + src) * a.L;
                     for (int i = 0; i < a.step; ++i) bs[i] = ss[i];
                     bs[a.step] = 2;
+                }
+                if (a.hyp_cnt && a.hyp_cnt[img] < k) {      // the n-best list: every retirement, in order
+                    const int slot = row0 + a.hyp_cnt[img]++;
+                    a.hyp_score[slot] = pick_val[j];
+                    a.hyp_len[slot] = a.step + 1;
+                    int32_t* hs = a.hyp_seq + (size_t)slot * a.L;
+                    for (int i = 0; i < a.step; ++i) hs[i] = ss[i];
+                    hs[a.step] = 2;
                 }
             } else {
                 new_src[nn] = src; new_tok[nn] = tok; new_run[nn] = pick_val[j];
@@ -390,17 +455,20 @@ __global__ __launch_bounds__(256) void beam_expand_rows_kernel(const float* __re
     *reinterpret_cast<f32x4*>(out + (size_t)row * E + e) = *reinterpret_cast<const f32x4*>(in + (size_t)img_of_row[row] * E + e);
 }
 
-// final selection (:302-313): best finished hypothesis if any, else the best-scoring live beam
+// final selection (:302-313): best finished hypothesis if any, else the best-scoring live beam (scores: its raw score, if non-null)
 __global__ void beam_finalize_kernel(int k, int L, int steps_done, const int* __restrict__ n_act, const float* __restrict__ run,
                                      const int32_t* __restrict__ seqs, const int* __restrict__ has_complete,
                                      const int* __restrict__ best_len, const int32_t* __restrict__ best_seq,
-                                     float* __restrict__ out, int32_t* __restrict__ lens) {
+                                     float* __restrict__ out, int32_t* __restrict__ lens, const float* __restrict__ best_score = nullptr,
+                                     float* __restrict__ scores = nullptr) {
     const int img = blockIdx.x;
     const int32_t* src;
     int len;
+    float sc;
     if (has_complete[img]) {
         src = best_seq + (size_t)img * L;
         len = best_len[img];
+        sc = scores ? best_score[img] : 0.f;
     } else {
         int bi = 0;
         float bv = -INFINITY;
@@ -408,13 +476,68 @@ __global__ void beam_finalize_kernel(int k, int L, int steps_done, const int* __
             if (run[img * k + j] > bv) { bv = run[img * k + j]; bi = j; }
         src = seqs + (size_t)(img * k + bi) * L;
         len = steps_done + 1;
+        sc = bv;
     }
     for (int i = threadIdx.x; i < L; i += blockDim.x) out[(size_t)img * L + i] = i < len ? (float)src[i] : 0.f;
-    if (threadIdx.x == 0) lens[img] = len;
+    if (threadIdx.x == 0) {
+        lens[img] = len;
+        if (scores) scores[img] = sc;
+    }
+}
+
+// length penalty of the final ranking (tokens = generated tokens, <end> counted): 1 avg: s / tokens^a, 2 wu: s / ((5 + tokens) / 6)^a
+__device__ inline float beam_lp_norm(float s, int tokens, int kind, float alpha) {
+    if (kind == 1) return s / powf((float)tokens, alpha);
+    if (kind == 2) return s / powf((5.f + (float)tokens) / 6.f, alpha);
+    return s;
+}
+
+// n-best selection, one wave per image: the image's k hypotheses are its retirements (hyp_*, in retirement order) and the beams
+// still live when the step limit ran out (rows 0 .. n_act - 1 of `seqs`, in merge order).  Ranked: finished before live, then by
+// the length-normalised score (descending), then by that order.  Writes the first n_best: ids out [n_img, n_best, L] (float32,
+// zero-padded), lens [n_img, n_best], raw scores [n_img, n_best]; a rank past the image's hypotheses (only when every token of
+// some beam was banned) is written as length 0, score -inf.
+__global__ __launch_bounds__(64) void beam_finalize_nbest_kernel(int k, int L, int steps_done, int n_best, int lp_kind, float lp_alpha,
+                                                                 const int* __restrict__ n_act, const float* __restrict__ run,
+                                                                 const int32_t* __restrict__ seqs, const int* __restrict__ hyp_cnt,
+                                                                 const float* __restrict__ hyp_score, const int* __restrict__ hyp_len,
+                                                                 const int32_t* __restrict__ hyp_seq, float* __restrict__ out,
+                                                                 int32_t* __restrict__ lens, float* __restrict__ scores) {
+    __shared__ int s_pick[BEAM_MAX_K];
+    const int img = blockIdx.x, lane = threadIdx.x, row0 = img * k;
+    const int nf = hyp_cnt[img], tot = min(nf + n_act[img], k);
+    const bool fin = lane < nf;
+    float raw = -INFINITY;
+    int len = 1;
+    if (lane < tot) {
+        raw = fin ? hyp_score[row0 + lane] : run[row0 + lane - nf];
+        len = fin ? hyp_len[row0 + lane] : steps_done + 1;
+    }
+    const float ns = beam_lp_norm(raw, len - 1, lp_kind, lp_alpha);
+    int rank = 0;
+    for (int f = 0; f < tot; ++f) {
+        const float nf_s = __shfl(ns, f, 64);
+        const bool f_fin = f < nf;
+        rank += (f_fin && !fin) || (f_fin == fin && (nf_s > ns || (nf_s == ns && f < lane)));
+    }
+    if (lane < BEAM_MAX_K) s_pick[lane] = -1;
+    __syncthreads();
+    if (lane < tot) s_pick[rank] = lane;
+    __syncthreads();
+    for (int m = 0; m < n_best; ++m) {
+        const int e = s_pick[m], o = img * n_best + m;
+        const int32_t* src = e < 0 ? nullptr : e < nf ? hyp_seq + (size_t)(row0 + e) * L : seqs + (size_t)(row0 + e - nf) * L;
+        const int ln = e < 0 ? 0 : e < nf ? hyp_len[row0 + e] : steps_done + 1;
+        for (int i = lane; i < L; i += 64) out[(size_t)o * L + i] = i < ln ? (float)src[i] : 0.f;
+        if (lane == 0) {
+            lens[o] = ln;
+            scores[o] = e < 0 ? -INFINITY : e < nf ? hyp_score[row0 + e] : run[row0 + e - nf];
+        }
+    }
 }
 
 __global__ void beam_init_kernel(int n_img, int k, int L, int* n_act, int32_t* seqs, int32_t* img_of_row, int64_t* it,
-                                 int* has_complete, float* best_score) {
+                                 int* has_complete, float* best_score, int* hyp_cnt) {
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n_img * k) return;
     seqs[(size_t)row * L] = 1;      // <sta>
@@ -425,6 +548,7 @@ __global__ void beam_init_kernel(int n_img, int k, int L, int* n_act, int32_t* s
         n_act[img] = k;
         has_complete[img] = 0;
         best_score[img] = -INFINITY;
+        hyp_cnt[img] = 0;
     }
 }
 

@@ -190,30 +190,37 @@ struct BeamBuf {
     float* best_score = nullptr; int *best_len = nullptr, *has_complete = nullptr, *n_live = nullptr, *n_live_host = nullptr;
     float* feat_rows = nullptr;       // NIC: image embedding replicated per beam row
     float* cand_val = nullptr; int* cand_idx = nullptr;     // [rows, BEAM_MAX_K] per-row candidates of one step
+    int32_t* hyp_seq = nullptr; float* hyp_score = nullptr; int *hyp_len = nullptr, *hyp_cnt = nullptr;    // n-best list (BeamArgs)
     BeamBuf() = default;
     BeamBuf(const BeamBuf&) = delete;
     BeamBuf& operator=(const BeamBuf&) = delete;
     ~BeamBuf() { if (n_live_host) (void)hipHostFree(n_live_host); }
 
     static int check(const char* who, int n_img, int k, int max_steps, int max_rows);
+    static int check_opts(const char* who, int k, const icz_beam_opts* o);      // the icz_*_beam_search_opts argument rules
+    static const icz_beam_opts defaults;                                       // n_best 1, no blocking, no length penalty
     int ensure(DeviceBuffers& m, int max_rows, int L, int extra_feat_cols = 0);
     int begin(int n_img, int k, int L, int64_t* it, hipStream_t st);       // scores, live counts and the <sta> rows of every image
     // The step loop (DecoderRNN.beam_search_sample, BUTD_Model.py:236-318, batched over images): step(step_no, compact) runs the
     // decoder on `it` into `logits`; then a row-top-k, the per-image merge and gather(compact) re-gathering the model state by
     // source row; every few steps one 4-byte read-back asks whether any image still has live beams.  compact_first: step 1 runs
     // one decoder row per image (the k rows of an image are identical and only row 0 is scored, :273-274).
+    // Options (icz_beam_opts, checked by check_opts): block_ngram goes to the row-top-k; n_best > 1 or a length penalty keeps the
+    // n-best list in the merge and ranks it in beam_finalize_nbest_kernel (seqs_out [n_img, n_best, L], lens_out / scores_out
+    // [n_img, n_best]).  At the defaults the launches are today's; scores_out (may be null) receives the raw score of the caption.
     template <class Step, class Gather>
     int search(int n_img, int k, int max_steps, bool compact_first, const float* logits, int V, int ldl, int64_t* it, float* seqs_out,
-               int32_t* lens_out, hipStream_t st, Step&& step, Gather&& gather) {
+               int32_t* lens_out, const icz_beam_opts& o, float* scores_out, hipStream_t st, Step&& step, Gather&& gather) {
         const int rows = n_img * k, L = max_steps + 1;
+        const bool listed = o.n_best > 1 || o.lp_kind != 0;
         int sb = 0, steps_done = 0;
         for (int s = 1; s <= max_steps; ++s) {
             const bool compact = compact_first && s == 1 && k > 1;
             ICZ_TRY(step(s, compact));
             BeamArgs a = {logits, V, ldl, k, s, L, n_act, run, seqs[sb], seqs[sb ^ 1], src_row, it, best_score, best_len, best_seq,
-                          has_complete, n_live + s};
+                          has_complete, n_live + s, listed ? hyp_seq : nullptr, hyp_score, hyp_len, listed ? hyp_cnt : nullptr};
             launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)n_act, (const float*)run, cand_val, cand_idx,
-                                compact ? 1 : 0);
+                                compact ? 1 : 0, seqs[sb], L, o.block_ngram);
             hipLaunchKernelGGL(beam_merge_kernel, dim3(n_img), dim3(64), 0, st, a, (const float*)cand_val, (const int*)cand_idx);
             gather(compact);
             sb ^= 1;
@@ -224,8 +231,13 @@ struct BeamBuf {
                 if (n_live_host[0] == 0) break;
             }
         }
-        hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_act, run, seqs[sb], has_complete,
-                           best_len, best_seq, seqs_out, lens_out);
+        if (listed)
+            hipLaunchKernelGGL(beam_finalize_nbest_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, o.n_best, o.lp_kind, o.lp_alpha,
+                               (const int*)n_act, (const float*)run, (const int32_t*)seqs[sb], (const int*)hyp_cnt, (const float*)hyp_score,
+                               (const int*)hyp_len, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out);
+        else
+            hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_act, run, seqs[sb], has_complete,
+                               best_len, best_seq, seqs_out, lens_out, (const float*)best_score, scores_out);
         ICZ_CHECK_HIP(hipGetLastError());
         return ICZ_OK;
     }

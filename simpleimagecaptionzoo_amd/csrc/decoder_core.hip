@@ -1,5 +1,6 @@
 // The out-of-line half of decoder_core.h (caption loss head, beam buffers, C ABI helpers) and the library's error slot.
 #include <stdarg.h>
+#include <cmath>
 
 #include "decoder_core.h"
 
@@ -167,6 +168,18 @@ int BeamBuf::check(const char* who, int n_img, int k, int max_steps, int max_row
     return ICZ_OK;
 }
 
+const icz_beam_opts BeamBuf::defaults = {1, 0, 0, 0.f};
+
+int BeamBuf::check_opts(const char* who, int k, const icz_beam_opts* o) {
+    ICZ_REQUIRE(o, "%s: null options", who);
+    ICZ_REQUIRE(o->n_best >= 1 && o->n_best <= k, "%s: n_best %d outside 1..beam (%d)", who, o->n_best, k);
+    ICZ_REQUIRE(o->block_ngram == 0 || (o->block_ngram >= 2 && o->block_ngram <= 4), "%s: block_ngram %d not 0, 2, 3 or 4", who,
+                o->block_ngram);
+    ICZ_REQUIRE(o->lp_kind >= 0 && o->lp_kind <= 2, "%s: lp_kind %d unknown (0 none, 1 avg, 2 wu)", who, o->lp_kind);
+    ICZ_REQUIRE(std::isfinite(o->lp_alpha) && o->lp_alpha >= 0.f, "%s: lp_alpha %g negative or not finite", who, (double)o->lp_alpha);
+    return ICZ_OK;
+}
+
 // sized for the handle's row capacity and at least 51 columns; a longer search re-allocates (the old buffers stay in the
 // handle's persistent list), the pinned read-back word is allocated once
 int BeamBuf::ensure(DeviceBuffers& m, int max_rows, int L, int extra_feat_cols) {
@@ -185,6 +198,10 @@ int BeamBuf::ensure(DeviceBuffers& m, int max_rows, int L, int extra_feat_cols) 
     ICZ_TRY(m.alloc((void**)&n_live, sizeof(int) * 260));
     ICZ_TRY(m.alloc((void**)&cand_val, sizeof(float) * R_ * BEAM_MAX_K));
     ICZ_TRY(m.alloc((void**)&cand_idx, sizeof(int) * R_ * BEAM_MAX_K));
+    ICZ_TRY(m.alloc((void**)&hyp_seq, sizeof(int32_t) * R_ * L_));
+    ICZ_TRY(m.alloc((void**)&hyp_score, sizeof(float) * R_));
+    ICZ_TRY(m.alloc((void**)&hyp_len, sizeof(int) * R_));
+    ICZ_TRY(m.alloc((void**)&hyp_cnt, sizeof(int) * R_));
     if (extra_feat_cols) ICZ_TRY(m.alloc((void**)&feat_rows, sizeof(float) * R_ * extra_feat_cols));
     if (!n_live_host) ICZ_CHECK_HIP(hipHostMalloc((void**)&n_live_host, sizeof(int) * 4, 0));
     ICZ_TRY(m.synced());
@@ -197,7 +214,8 @@ int BeamBuf::begin(int n_img, int k, int L, int64_t* it, hipStream_t st) {
     const int rows = n_img * k;
     ICZ_CHECK_HIP(hipMemsetAsync(n_live, 0, sizeof(int) * 260, st));
     ICZ_CHECK_HIP(hipMemsetAsync(run, 0, sizeof(float) * rows, st));
-    hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, n_img, k, L, n_act, seqs[0], img_of_row, it, has_complete, best_score);
+    hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, n_img, k, L, n_act, seqs[0], img_of_row, it, has_complete, best_score,
+                       hyp_cnt);
     return ICZ_OK;
 }
 

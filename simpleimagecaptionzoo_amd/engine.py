@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from ._lib import BUTD_PARAM_KEYS, check, lib, ptr, stream_ptr
+from .beam import parse_length_penalty
 from .captioner import BUTDDetection_Captioner
 from .ciderd import CiderDReward
 from . import dist as icz_dist
@@ -500,11 +501,21 @@ class BUTDDetection_Eng(Engine):
                 monitor.set_postfix(Loss=np.round(loss.item(), decimals=4))
 
     # ---- E3 -------------------------------------------------------------------------------------------------
-    def eval_captions_json_generation(self, dataloader, eval_beam_size=-1, tqdm_visible=True):
+    def eval_captions_json_generation(self, dataloader, eval_beam_size=-1, tqdm_visible=True, *, length_penalty=None, block_ngram=0):
+        """length_penalty / block_ngram (an extension, beam search only; include/icz.h: icz_beam_opts): rank the finished beams by
+        a length-penalised score (None, ('avg' | 'wu', alpha), 'avg_<alpha>', 'wu_<alpha>') and forbid repeated n-grams."""
+        opts = None
+        if length_penalty is not None or block_ngram:
+            if eval_beam_size == -1:
+                raise ValueError("length_penalty / block_ngram need beam search (eval_beam_size != -1)")
+            parse_length_penalty(length_penalty)          # a bad penalty raises here, before any device work
+            if int(block_ngram) not in (0, 2, 3, 4):
+                raise ValueError("block_ngram %d not 0, 2, 3 or 4" % int(block_ngram))
+            opts = (length_penalty, int(block_ngram))
         with _on_stream(self):
-            return self._eval_captions_json_generation(dataloader, eval_beam_size, tqdm_visible)
+            return self._eval_captions_json_generation(dataloader, eval_beam_size, tqdm_visible, opts)
 
-    def _eval_captions_json_generation(self, dataloader, eval_beam_size=-1, tqdm_visible=True):
+    def _eval_captions_json_generation(self, dataloader, eval_beam_size=-1, tqdm_visible=True, opts=None):
         """Engine.py:274-300.  Beam search accepts any batch size here (the reference's loader uses 1).
         Data-parallel (torch.distributed initialised): rank r decodes the batches i with i % world == r (and
         loads only those where the loader allows, _rank_batches); the (image id, token ids) rows are all-gathered and every rank returns the
@@ -523,7 +534,11 @@ class BUTDDetection_Eng(Engine):
             nb = len(image_ids)
             visual_inputs = self.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
             h = self._hot_handle()
-            if eval_beam_size != -1:
+            if eval_beam_size != -1 and opts is not None:
+                seqs, lens, _ = h.beam_search_opts(self._features(visual_inputs), eval_beam_size, 50, 1, opts[0], opts[1])
+                seqs, lens = seqs[:, 0].cpu().numpy(), lens[:, 0].cpu().numpy()
+                rows = [seqs[i, :lens[i]] for i in range(len(lens))]
+            elif eval_beam_size != -1:
                 seqs, lens = h.beam_search(self._features(visual_inputs), eval_beam_size, 50)
                 seqs, lens = seqs.cpu().numpy(), lens.cpu().numpy()
                 rows = [seqs[i, :lens[i]] for i in range(len(lens))]
