@@ -217,6 +217,28 @@ typedef struct {
 int icz_butd_beam_search_opts(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
                               const icz_beam_opts* opts, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream);
 
+/* Diverse beam search (Vijayakumar et al., "Diverse Beam Search", AAAI 2018) for the icz_*_beam_search_diverse entries:
+ *   groups     1..beam, dividing beam: the beam splits into `groups` groups of kg = beam / groups beams, each run as the search
+ *              above (shrinking kg, its own <end> retirements) over the same decoder step.
+ *   diversity  lambda >= 0, finite.  At every step the groups select in order; group g ranks its candidates by
+ *              score - fp32(lambda * c), c = how often groups 0 .. g-1 picked that token at this step (<end> included).
+ *              The penalty acts on this step's selection only: it never enters the running score, and every group starts at
+ *              step 1 (self-critical.pytorch's variant accumulates it and staggers the groups; neither is done here).
+ * The image's list holds the beam hypotheses of all groups (retirements in order of step, group, merge rank, then the beams
+ * live at the limit in group, slot order), ranked as icz_beam_opts says, with raw log-probability scores.
+ * {1, 0} is icz_*_beam_search_opts bit for bit; lambda = 0 runs `groups` independent copies of the kg-beam search. */
+typedef struct {
+    int32_t groups;
+    float diversity;
+} icz_beam_diversity;
+
+/* icz_butd_beam_search_opts with grouped beams and a diversity penalty; the outputs are those of _opts.  Argument errors return
+ * ICZ_ERR_INVALID before any device work, checked in this order: the options (as _opts), a null `div`, groups outside 1..beam
+ * or not dividing it, diversity negative or not finite, null arguments, null handle. */
+int icz_butd_beam_search_diverse(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                                 const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out,
+                                 float* scores_out, void* stream);
+
 /* One decoder step from an explicit state (BUTD_Model.py:172-182) -- exposed for the per-kernel parity tests.
  * it [B] int64; state tensors [B,H] are updated in place; ctx_out [B,D], alpha_out [B,R], logits_out [B,V]. */
 int icz_butd_step(icz_butd_t* h, const float* feats, int32_t B, const int64_t* it, float* h1, float* c1,
@@ -264,6 +286,10 @@ int icz_nic_beam_search(icz_nic_t* h, const float* features, int32_t n_img, int3
 /* ... with options (icz_beam_opts, see icz_butd_beam_search_opts) */
 int icz_nic_beam_search_opts(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps,
                              const icz_beam_opts* opts, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream);
+/* ... with grouped beams and a diversity penalty (icz_beam_diversity, see icz_butd_beam_search_diverse) */
+int icz_nic_beam_search_diverse(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps,
+                                const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out,
+                                float* scores_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * AoADetection captioner (Models/AoA_Model.py:657-753): img_feats_porjection (Linear 2048->Hd + ReLU + Dropout) ->
@@ -330,6 +356,10 @@ int icz_aoa_beam_search(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t
                         int32_t* lens_out, void* stream);
 int icz_aoa_beam_search_opts(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
                              const icz_beam_opts* opts, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream);
+/* ... with grouped beams and a diversity penalty (icz_beam_diversity, see icz_butd_beam_search_diverse) */
+int icz_aoa_beam_search_diverse(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                                const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out,
+                                float* scores_out, void* stream);
 int icz_aoa_sample(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, const icz_aoa_rng* rng, int64_t* seq_out,
                    float* logprobs_out, void* stream);
 /* The two decodes of one SCST step (Engine.py:256-261: greedy in eval mode, sampler_rl in train mode) as concurrent chains. */

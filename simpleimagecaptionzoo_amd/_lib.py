@@ -99,6 +99,10 @@ class BeamOpts(C.Structure):       # icz_beam_opts
     _fields_ = [("n_best", C.c_int32), ("block_ngram", C.c_int32), ("lp_kind", C.c_int32), ("lp_alpha", C.c_float)]
 
 
+class BeamDiversity(C.Structure):  # icz_beam_diversity
+    _fields_ = [("groups", C.c_int32), ("diversity", C.c_float)]
+
+
 _lib = None
 
 
@@ -137,6 +141,7 @@ def lib():
         "icz_butd_xe_backward_dlogits": (C.c_int, [vp, vp, C.POINTER(ButdParams), vp]),
         "icz_butd_beam_search": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "icz_butd_beam_search_opts": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), vp, vp, vp, vp]),
+        "icz_butd_beam_search_diverse": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamDiversity), vp, vp, vp, vp]),
         "icz_butd_sample_mask_sum": (C.c_int, [vp, vp, vp]),
         "icz_butd_xe_forward": (C.c_int, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Rng), i32, vp, vp]),
         "icz_butd_xe_backward": (C.c_int, [vp, f32, C.POINTER(ButdParams), vp, f32, vp]),
@@ -159,6 +164,7 @@ def lib():
         "icz_aoa_set_norm_global": (C.c_int, [vp, vp, vp]),
         "icz_nic_beam_search": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "icz_nic_beam_search_opts": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), vp, vp, vp, vp]),
+        "icz_nic_beam_search_diverse": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamDiversity), vp, vp, vp, vp]),
         "icz_aoa_create": (C.c_int, [C.POINTER(AoaDims), C.POINTER(vp)]),
         "icz_aoa_destroy": (C.c_int, [vp]),
         "icz_aoa_bind_params": (C.c_int, [vp, C.POINTER(AoaParams)]),
@@ -170,6 +176,7 @@ def lib():
         "icz_aoa_greedy": (C.c_int, [vp, vp, i32, i32, vp, vp]),
         "icz_aoa_beam_search": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "icz_aoa_beam_search_opts": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), vp, vp, vp, vp]),
+        "icz_aoa_beam_search_diverse": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamDiversity), vp, vp, vp, vp]),
         "icz_aoa_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),
         "icz_aoa_scst_rollouts": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp, vp]),
         "icz_aoa_sample_backward": (C.c_int, [vp, vp, C.POINTER(AoaParams), vp, vp, f32, vp]),

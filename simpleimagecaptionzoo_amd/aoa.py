@@ -181,13 +181,16 @@ class AoaHandle:
         check(lib().icz_aoa_beam_search(self._h, ptr(feats), n, beam_size, max_steps, ptr(seqs), ptr(lens), stream_ptr()))
         return seqs, lens
 
-    def beam_search_opts(self, feats, beam_size=5, max_steps=50, n_best=1, length_penalty=None, block_ngram=0):
+    def beam_search_opts(self, feats, beam_size=5, max_steps=50, n_best=1, length_penalty=None, block_ngram=0, groups=1, diversity=0.0):
         """beam_search with options (include/icz.h: icz_beam_opts): the n_best best of each image's beam_size hypotheses,
         ranked finished first, then by the length-penalised score (None | ('avg' | 'wu', alpha) | 'avg_<alpha>' | 'wu_<alpha>');
         block_ngram = n (2, 3, 4; 0 = off) forbids repeating an n-gram of the prefix.  Returns (seqs float32 (n_img, n_best,
-        max_steps+1) zero-padded, lens int32 (n_img, n_best), raw log-prob scores (n_img, n_best)); the defaults give beam_search."""
-        opts = _beam.make_opts(n_best, length_penalty, block_ngram)
-        return _beam.search_opts(lib().icz_aoa_beam_search_opts, self._h, self._feats(feats), beam_size, max_steps, opts)
+        max_steps+1) zero-padded, lens int32 (n_img, n_best), raw log-prob scores (n_img, n_best)); the defaults give beam_search.
+        groups > 1 (dividing beam_size) runs diverse beam search (icz_beam_diversity): the beam splits into `groups` groups, and
+        each step a group's choice of a token is penalised by `diversity` for every earlier group that chose it at that step."""
+        opts = _beam.make_opts(n_best, length_penalty, block_ngram)        # ValueError before the features are looked at
+        div = _beam.make_diversity(groups, diversity, beam_size)
+        return _beam.search(lib(), "aoa", self._h, self._feats(feats), beam_size, max_steps, opts, div)
 
     def sample(self, feats, max_len=20, rng=None):
         feats = self._feats(feats)
@@ -397,13 +400,13 @@ class AoADetection_Captioner(nn.Module, ScheduledSamplingState):
         out = [seqs[i:i + 1, :lens[i]] for i in range(len(lens))]
         return out[0] if len(out) == 1 else out
 
-    def beam_search_nbest(self, visual_inputs, beam_size=5, n_best=None, length_penalty=None, block_ngram=0):
+    def beam_search_nbest(self, visual_inputs, beam_size=5, n_best=None, length_penalty=None, block_ngram=0, groups=1, diversity=0.0):
         """Beam search returning each image's n-best list (an extension; include/icz.h: icz_beam_opts): per image a list of
         (ids float32 (1, L_i) with <sta> and, if finished, <end>; raw summed log-prob), best first; n_best=None = all beam_size
         hypotheses.  length_penalty (None, ('avg' | 'wu', alpha), 'avg_<alpha>', 'wu_<alpha>') ranks them; block_ngram = n
-        forbids repeating an n-gram."""
+        forbids repeating an n-gram; groups > 1 with a diversity penalty runs diverse beam search (icz_beam_diversity)."""
         seqs, lens, scores = self._handle().beam_search_opts(self._feats(visual_inputs), beam_size, 50, beam_size if n_best is None else n_best,
-                                                             length_penalty, block_ngram)
+                                                             length_penalty, block_ngram, groups, diversity)
         return nbest_lists(seqs, lens, scores)
 
     def eval_test_image(self, visual_inputs, caption_vocab, max_len=20, eval_beam_size=-1):

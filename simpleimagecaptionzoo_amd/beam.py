@@ -1,11 +1,13 @@
-"""Beam-search options of the three decoders (include/icz.h: icz_beam_opts): n-best lists, length penalty and n-gram blocking.
-The search itself runs on the device (csrc/beam_kernels.h); this module parses the options and shapes the results."""
+"""Beam-search options of the three decoders (include/icz.h: icz_beam_opts, icz_beam_diversity): n-best lists, length penalty,
+n-gram blocking and diverse beam search (grouped beams with a diversity penalty).  The search itself runs on the device
+(csrc/beam_kernels.h); this module parses the options and shapes the results."""
 import ctypes as C
 import math
+import numbers
 
 import torch
 
-from ._lib import BeamOpts, check, ptr, stream_ptr
+from ._lib import BeamDiversity, BeamOpts, check, ptr, stream_ptr
 
 LP_KINDS = {"avg": 1, "wu": 2}
 
@@ -43,14 +45,48 @@ def make_opts(n_best=1, length_penalty=None, block_ngram=0):
     return BeamOpts(int(n_best), int(block_ngram), kind, alpha)
 
 
+def make_diversity(groups=1, diversity=0.0, beam=None):
+    """-> icz_beam_diversity: `groups` (an int in 1..beam dividing beam) groups of beam / groups beams; `diversity` lambda (a finite
+    real >= 0) penalises, at every step, a token once per earlier group that picked it at that step.  ValueError otherwise (bools
+    included), before any device work."""
+    if isinstance(groups, bool) or not isinstance(groups, numbers.Integral):
+        raise ValueError("groups %r: expected an int" % (groups,))
+    if isinstance(diversity, bool) or not isinstance(diversity, numbers.Real):
+        raise ValueError("diversity %r: expected a real number" % (diversity,))
+    groups, diversity = int(groups), float(diversity)
+    if groups < 1 or (beam is not None and (groups > int(beam) or int(beam) % groups != 0)):
+        raise ValueError("groups %d: must lie in 1..beam (%s) and divide it" % (groups, beam))
+    if not math.isfinite(diversity) or diversity < 0:
+        raise ValueError("diversity %r: must be finite and >= 0" % (diversity,))
+    return BeamDiversity(groups, diversity)
+
+
+def _outputs(feats, max_steps, opts):
+    n, m, dev = feats.shape[0], max(1, int(opts.n_best)), feats.device
+    return (torch.zeros(n, m, max_steps + 1, dtype=torch.float32, device=dev), torch.zeros(n, m, dtype=torch.int32, device=dev),
+            torch.zeros(n, m, dtype=torch.float32, device=dev))
+
+
 def search_opts(entry, handle, feats, beam_size, max_steps, opts):
     """Calls icz_*_beam_search_opts `entry` on checked features -> (seqs float32 (n, m, L), lens int32 (n, m), scores (n, m))."""
-    n, m, dev = feats.shape[0], max(1, int(opts.n_best)), feats.device
-    seqs = torch.zeros(n, m, max_steps + 1, dtype=torch.float32, device=dev)
-    lens = torch.zeros(n, m, dtype=torch.int32, device=dev)
-    scores = torch.zeros(n, m, dtype=torch.float32, device=dev)
-    check(entry(handle, ptr(feats), n, beam_size, max_steps, C.byref(opts), ptr(seqs), ptr(lens), ptr(scores), stream_ptr()))
+    seqs, lens, scores = _outputs(feats, max_steps, opts)
+    check(entry(handle, ptr(feats), feats.shape[0], beam_size, max_steps, C.byref(opts), ptr(seqs), ptr(lens), ptr(scores), stream_ptr()))
     return seqs, lens, scores
+
+
+def search_diverse(entry, handle, feats, beam_size, max_steps, opts, div):
+    """Calls icz_*_beam_search_diverse `entry`; the outputs of search_opts."""
+    seqs, lens, scores = _outputs(feats, max_steps, opts)
+    check(entry(handle, ptr(feats), feats.shape[0], beam_size, max_steps, C.byref(opts), C.byref(div), ptr(seqs), ptr(lens), ptr(scores),
+                stream_ptr()))
+    return seqs, lens, scores
+
+
+def search(lib, model, handle, feats, beam_size, max_steps, opts, div):
+    """icz_<model>_beam_search_opts for one group (today's search), icz_<model>_beam_search_diverse otherwise"""
+    if div.groups == 1:
+        return search_opts(getattr(lib, "icz_%s_beam_search_opts" % model), handle, feats, beam_size, max_steps, opts)
+    return search_diverse(getattr(lib, "icz_%s_beam_search_diverse" % model), handle, feats, beam_size, max_steps, opts, div)
 
 
 def nbest_lists(seqs, lens, scores):

@@ -235,13 +235,16 @@ class ButdHandle:
         check(lib().icz_butd_beam_search(self._h, ptr(feats), n, beam_size, max_steps, ptr(seqs), ptr(lens), stream_ptr()))
         return seqs, lens
 
-    def beam_search_opts(self, feats, beam_size=5, max_steps=50, n_best=1, length_penalty=None, block_ngram=0):
+    def beam_search_opts(self, feats, beam_size=5, max_steps=50, n_best=1, length_penalty=None, block_ngram=0, groups=1, diversity=0.0):
         """beam_search with options (include/icz.h: icz_beam_opts): the n_best best of each image's beam_size hypotheses,
         ranked finished first, then by the length-penalised score (None | ('avg' | 'wu', alpha) | 'avg_<alpha>' | 'wu_<alpha>');
         block_ngram = n (2, 3, 4; 0 = off) forbids repeating an n-gram of the prefix.  Returns (seqs float32 (n_img, n_best,
-        max_steps+1) zero-padded, lens int32 (n_img, n_best), raw log-prob scores (n_img, n_best)); the defaults give beam_search."""
+        max_steps+1) zero-padded, lens int32 (n_img, n_best), raw log-prob scores (n_img, n_best)); the defaults give beam_search.
+        groups > 1 (dividing beam_size) runs diverse beam search (icz_beam_diversity): the beam splits into `groups` groups, and
+        each step a group's choice of a token is penalised by `diversity` for every earlier group that chose it at that step."""
         opts = _beam.make_opts(n_best, length_penalty, block_ngram)        # ValueError before the features are looked at
-        return _beam.search_opts(lib().icz_butd_beam_search_opts, self._h, self._check_feats(feats), beam_size, max_steps, opts)
+        div = _beam.make_diversity(groups, diversity, beam_size)
+        return _beam.search(lib(), "butd", self._h, self._check_feats(feats), beam_size, max_steps, opts, div)
 
     def step(self, feats, it, h1, c1, h2, c2):
         """One decoder step from an explicit state (BUTD_Model.py:172-182); state tensors are updated in place.

@@ -194,13 +194,13 @@ class BUTDDetection_Captioner(nn.Module, ScheduledSamplingState):
         out = [seqs[i:i + 1, :lens[i]] for i in range(len(lens))]
         return out[0] if len(out) == 1 else out
 
-    def beam_search_nbest(self, visual_inputs, beam_size=5, n_best=None, length_penalty=None, block_ngram=0):
+    def beam_search_nbest(self, visual_inputs, beam_size=5, n_best=None, length_penalty=None, block_ngram=0, groups=1, diversity=0.0):
         """Beam search returning each image's n-best list (an extension; include/icz.h: icz_beam_opts): per image a list of
         (ids float32 (1, L_i) with <sta> and, if finished, <end>; raw summed log-prob), best first; n_best=None = all beam_size
         hypotheses.  length_penalty (None, ('avg' | 'wu', alpha), 'avg_<alpha>', 'wu_<alpha>') ranks them; block_ngram = n
-        forbids repeating an n-gram."""
+        forbids repeating an n-gram; groups > 1 with a diversity penalty runs diverse beam search (icz_beam_diversity)."""
         seqs, lens, scores = self._handle().beam_search_opts(visual_inputs["bu_feats"], beam_size, 50, beam_size if n_best is None else n_best,
-                                                             length_penalty, block_ngram)
+                                                             length_penalty, block_ngram, groups, diversity)
         return nbest_lists(seqs, lens, scores)
 
     def _replay_handle(self):

@@ -352,7 +352,7 @@ int Aoa::greedy(const float* feats, int B, int T, int64_t* ids_out, hipStream_t 
 
 // AoA_Decoder.beam_search_sample (AoA_Model.py:403-502), batched over images; state (h, m, ctx) re-gathered by source beam
 int Aoa::beam_search(const float* feats, int n_img, int kb, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                      const icz_beam_opts& o, float* scores_out) {
+                      const icz_beam_opts& o, float* scores_out, const icz_beam_diversity& d) {
     ICZ_REQUIRE(feats && seqs_out && lens_out, "aoa beam: null argument");
     ICZ_TRY(BeamBuf::check("aoa", n_img, kb, max_steps, dims.max_rows));
     ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
@@ -371,7 +371,7 @@ int Aoa::beam_search(const float* feats, int n_img, int kb, int max_steps, float
         hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(Hd, 1024), rows), dim3(256), 0, st, bm.src_row, Hd, h[1], m[1], ctx[1], h[1],
                            h[0], m[0], ctx[0], u, compact ? kb : 1);
     };
-    return bm.search(n_img, kb, max_steps, true, logits, dims.V, Vp, it, seqs_out, lens_out, o, scores_out, st, step, gather);
+    return bm.search(n_img, kb, max_steps, true, logits, dims.V, Vp, it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
 }
 
 }  // namespace icz
@@ -465,4 +465,12 @@ int icz_aoa_beam_search_opts(icz_aoa_t* h, const float* feats, int32_t n_img, in
     return reinterpret_cast<Aoa*>(h)->beam_search(feats, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out);
 }
 
+int icz_aoa_beam_search_diverse(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                                const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
+    ICZ_TRY(BeamBuf::check_opts("icz_aoa_beam_search_diverse", beam, opts));      // the arguments first: no handle needed to report them
+    ICZ_TRY(BeamBuf::check_diversity("icz_aoa_beam_search_diverse", beam, div));
+    ICZ_REQUIRE(feats && seqs_out && lens_out && scores_out, "icz_aoa_beam_search_diverse: null argument");
+    ICZ_REQUIRE(h, "icz_aoa_beam_search_diverse: null handle");
+    return reinterpret_cast<Aoa*>(h)->beam_search(feats, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out, *div);
+}
 }  // extern "C"

@@ -136,7 +136,8 @@ struct Aoa : CaptionHead {
     int rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int64_t* seq_out, float* logp_out, hipStream_t st);
     int rollouts(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* ids_out, int64_t* seq_out, float* logp_out, hipStream_t st);
     int beam_search(const float* feats, int n_img, int kb, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                    const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr);
+                    const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr,
+                    const icz_beam_diversity& d = BeamBuf::no_diversity);
     DropP dropp(bool train, const uint8_t* mask, size_t off, uint32_t stream, int step, float p) const {
         DropP d = {0, nullptr, d_seed, stream, (uint32_t)step, (uint32_t)((double)p * 4294967296.0), 1.0f / (1.0f - p)};
         if (!train) return d;

@@ -9,7 +9,7 @@ constexpr int BEAM_MAX_K = 8;
 
 struct BeamArgs {
     const float* logits; int V; int ldl; int k; int step; int L;   // L = max_steps + 1 (sequence capacity)
-    int* n_act;             // [n_img]   active beams (the reference's shrinking k)
+    int* n_act;             // [n_img]   active beams (the reference's shrinking k); grouped search: [n_img, groups]
     float* run;             // [n_img,k] running scores of the active beams
     const int32_t* seqs_in; int32_t* seqs_out;     // [n_img,k,L]
     int32_t* src_row;       // [n_img*k] decoder row whose state feeds this row next step
@@ -43,6 +43,25 @@ __device__ inline bool beam_banned(int v, const int* s_ban, int nban) {
     return b;
 }
 
+// Candidates the row-top-k emits for row `row` (r = its slot within its image) this step; 0: the row is not scored.
+// Plain search: every live row emits n_act[img]; step 1 scores row 0 only (:273-274).
+// Grouped (diverse) search, rows group-major (row img * k + g * kg + j, kg = k / groups), n_act [n_img, groups]: a live row of
+// group g emits min(k, n_act[0] + ... + n_act[g]) -- at most that many tokens are penalised before group g selects and a penalty
+// only lowers a key, so the group's top n_act[g] lie within each row's unpenalised top (n_act[g] + #penalised).  Step 1 scores
+// the image's row 0 with k candidates, which every group reads.
+template <bool GROUPED>
+__device__ inline int beam_row_cands(const int* __restrict__ n_act, int img, int r, int k, int groups, int step) {
+    if (!GROUPED) {
+        const int na = n_act[img];
+        return r < ((step == 1) ? 1 : na) ? na : 0;
+    }
+    if (step == 1) return r == 0 ? k : 0;
+    const int kg = k / groups, g = r / kg;
+    int c = 0;
+    for (int q = 0; q <= g; ++q) c += n_act[img * groups + q];
+    return (r % kg) < n_act[img * groups + g] ? min(k, c) : 0;
+}
+
 // Beam expand / prune of one step (:271-300) in two launches:
 //   beam_rowtopk_kernel  grid (n_img * k): one workgroup per decoder row -> its log-softmax normaliser and its own best
 //                        n_act candidates (value = run + log_softmax, index v); every row of every image in parallel
@@ -52,19 +71,18 @@ __device__ inline bool beam_banned(int v, const int* s_ban, int nban) {
 // Blocking (ngram > 0, from step ngram on; seqs_in / L: the rows' prefixes): a banned token scores -inf after the log-softmax,
 // whose normaliser still runs over the whole row.  Here a banned token is skipped where it would enter a thread's list; BAN = false
 // (no list this step) compiles the kernel without the test (the list check costs it 20 VGPRs and its occupancy).
-template <bool BAN>
+template <bool BAN, bool GROUPED>
 __global__ __launch_bounds__(256) void beam_rowtopk_kernel(const float* __restrict__ logits, int V, int ldl, int k, int step,
                                                            const int* __restrict__ n_act, const float* __restrict__ run,
                                                            float* __restrict__ cand_val, int* __restrict__ cand_idx, int compact,
-                                                           const int32_t* __restrict__ seqs_in, int L, int ngram) {
+                                                           const int32_t* __restrict__ seqs_in, int L, int ngram, int groups) {
     __shared__ float smf[4];
     __shared__ float s_val[4];
     __shared__ int s_idx[4], s_who[4];
     __shared__ int s_ban[256], s_nban;
     const int row = blockIdx.x, img = row / k, r = row % k, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int na = n_act[img];
-    const int nr = (step == 1) ? 1 : na;          // step 1 scores row 0 only (:273-274)
-    if (r >= nr) return;
+    const int na = beam_row_cands<GROUPED>(n_act, img, r, k, groups, step);     // candidates of this row (0: not scored)
+    if (na == 0) return;
     const int nban = BAN ? beam_ban_list(seqs_in + (size_t)row * L, step, ngram, s_ban, &s_nban) : 0;
     const float* l = logits + (size_t)(compact ? img : row) * ldl;      // compact (step 1 only): one decoder row per image
     // Every sweep fetches the thread's strided slice (40 logits at V = 10102) in batches of U independent loads: one memory
@@ -167,11 +185,11 @@ __global__ __launch_bounds__(256) void beam_rowtopk_kernel(const float* __restri
 // no dynamic register index), so tau, the candidate list and the overflow path never see it.  The ban list lives at the
 // start of the overflow path's LDS row, which is written only after the list has been read.
 constexpr int BEAM_CAND_CAP = 128;
-template <int NV4>
+template <int NV4, bool GROUPED>
 __global__ __launch_bounds__(256) void beam_rowtopk_reg_kernel(const float* __restrict__ logits, int V, int ldl, int k, int step,
                                                                const int* __restrict__ n_act, const float* __restrict__ run,
                                                                float* __restrict__ cand_val, int* __restrict__ cand_idx, int compact,
-                                                               const int32_t* __restrict__ seqs_in, int L, int ngram) {
+                                                               const int32_t* __restrict__ seqs_in, int L, int ngram, int groups) {
     __shared__ float smf[4];
     __shared__ float s_val[4];
     __shared__ int s_idx[4], s_who[4];
@@ -180,9 +198,8 @@ __global__ __launch_bounds__(256) void beam_rowtopk_reg_kernel(const float* __re
     __shared__ int s_ci[BEAM_CAND_CAP];
     extern __shared__ __attribute__((aligned(16))) float s_row[];          // overflow path only: 1024 NV4 floats
     const int row = blockIdx.x, img = row / k, r = row % k, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int na = n_act[img];
-    const int nr = (step == 1) ? 1 : na;          // step 1 scores row 0 only (:273-274)
-    if (r >= nr) return;
+    const int na = beam_row_cands<GROUPED>(n_act, img, r, k, groups, step);     // candidates of this row (0: not scored)
+    if (na == 0) return;
     const float* l = logits + (size_t)(compact ? img : row) * ldl;      // compact (step 1 only): one decoder row per image
     f32x4 x[NV4];
 #pragma unroll
@@ -327,15 +344,22 @@ __global__ __launch_bounds__(256) void beam_rowtopk_reg_kernel(const float* __re
 }
 
 // per-row candidates of one beam step: the register kernel where the vocabulary fits it, else the sweep kernel
-// (ngram > 0: n-gram blocking on the prefixes seqs_in [rows, L])
+// (ngram > 0: n-gram blocking on the prefixes seqs_in [rows, L]; groups > 1: the grouped instances, n_act [n_img, groups])
+template <bool GROUPED>
+inline void launch_beam_rowtopk_t(hipStream_t st, int rows, const float* logits, int V, int ldl, int k, int step, const int* n_act,
+                                  const float* run, float* cand_val, int* cand_idx, int compact, const int32_t* seqs_in, int L,
+                                  int ngram, int groups) {
+    const bool ok = ldl % 4 == 0 && ((uintptr_t)logits & 15) == 0;
+    if (ok && V <= 1024 * 3) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<3, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 3, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
+    else if (ok && V <= 1024 * 10) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<10, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 10, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
+    else if (ngram && step >= ngram) hipLaunchKernelGGL((beam_rowtopk_kernel<true, GROUPED>), dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
+    else hipLaunchKernelGGL((beam_rowtopk_kernel<false, GROUPED>), dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
+}
 inline void launch_beam_rowtopk(hipStream_t st, int rows, const float* logits, int V, int ldl, int k, int step, const int* n_act,
                                 const float* run, float* cand_val, int* cand_idx, int compact = 0, const int32_t* seqs_in = nullptr,
-                                int L = 0, int ngram = 0) {
-    const bool ok = ldl % 4 == 0 && ((uintptr_t)logits & 15) == 0;
-    if (ok && V <= 1024 * 3) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<3>), dim3(rows), dim3(256), sizeof(float) * 1024 * 3, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram);
-    else if (ok && V <= 1024 * 10) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<10>), dim3(rows), dim3(256), sizeof(float) * 1024 * 10, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram);
-    else if (ngram && step >= ngram) hipLaunchKernelGGL(beam_rowtopk_kernel<true>, dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram);
-    else hipLaunchKernelGGL(beam_rowtopk_kernel<false>, dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram);
+                                int L = 0, int ngram = 0, int groups = 1) {
+    if (groups > 1) launch_beam_rowtopk_t<true>(st, rows, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
+    else launch_beam_rowtopk_t<false>(st, rows, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, 1);
 }
 
 __global__ __launch_bounds__(64) void beam_merge_kernel(BeamArgs a, const float* __restrict__ cand_val, const int* __restrict__ cand_idx) {
@@ -429,6 +453,122 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(BeamArgs a, const float*
     }
 }
 
+// key of a diverse-search candidate: score - fp32(lambda * c), the product rounded on its own.  The build contracts by default,
+// which would fuse the two into one fma (one rounding) and move the key off the spec by an ulp whenever lambda * c is inexact.
+__device__ inline float beam_diverse_key(float score, float lambda, int c) {
+#pragma clang fp contract(off)
+    const float pen = lambda * (float)c;
+    return score - pen;
+}
+
+// Diverse beam search (Vijayakumar et al., "Diverse Beam Search", AAAI 2018), one wave per image: the k rows of the image form
+// `groups` groups of kg = k / groups beams (group-major rows, n_act [n_img, groups]).  The groups select in order; group g ranks
+// its candidates by key = score - fp32(lambda * c), c = how often groups 0 .. g-1 picked the token at this step (an LDS table of
+// at most k entries), with the tie rule of beam_merge_kernel over its own rows (flat index r * V + v), and keeps the raw score.
+// Every pick counts, <end> included.  Retirements go to the n-best list in order (step, group, merge rank); each group's
+// survivors are compacted into the group's own slots.  Step 1: every group reads the k candidates of the image's row 0.
+__global__ __launch_bounds__(64) void beam_merge_groups_kernel(BeamArgs a, int groups, float lambda, const float* __restrict__ cand_val,
+                                                               const int* __restrict__ cand_idx) {
+    __shared__ float pick_val[BEAM_MAX_K];
+    __shared__ int pick_idx[BEAM_MAX_K];
+    __shared__ int new_src[BEAM_MAX_K], new_tok[BEAM_MAX_K], s_newn;
+    __shared__ float new_run[BEAM_MAX_K];
+    __shared__ int s_na[BEAM_MAX_K];                             // live beams per group when the step began
+    __shared__ int cnt_tok[BEAM_MAX_K], cnt_n[BEAM_MAX_K], s_ncnt;
+    const int img = blockIdx.x, lane = threadIdx.x;
+    const int k = a.k, V = a.V, kg = k / groups, row0 = img * k;
+    if (lane < groups) s_na[lane] = a.n_act[img * groups + lane];
+    if (lane == 0) s_ncnt = 0;
+    __syncthreads();
+    // lane c <-> candidate (row r = c / BEAM_MAX_K of the group, rank j = c % BEAM_MAX_K): kg x k <= 64
+    const int cr = lane / BEAM_MAX_K, cj = lane % BEAM_MAX_K;
+    int csum = 0, live = 0;
+    for (int g = 0; g < groups; ++g) {                           // uniform: s_na, s_ncnt and s_newn are read after a barrier
+        const int na = s_na[g], gr0 = row0 + g * kg;
+        csum += na;
+        if (na == 0) {
+            for (int j = lane; j < kg; j += 64) { a.src_row[gr0 + j] = gr0 + j; a.it_next[gr0 + j] = 0; }
+            continue;
+        }
+        const int nr = (a.step == 1) ? 1 : na, nc = (a.step == 1) ? k : min(k, csum);     // beam_row_cands<true>
+        float key = -INFINITY, val = -INFINITY;
+        int idx = 0x7fffffff;
+        if (cr < nr && cj < nc) {
+            const int crow = (a.step == 1) ? row0 : gr0 + cr;
+            const int ci = cand_idx[crow * BEAM_MAX_K + cj];
+            if (ci < V) {
+                val = cand_val[crow * BEAM_MAX_K + cj];
+                int c = 0;
+                for (int q = 0; q < s_ncnt; ++q) c += cnt_tok[q] == ci ? cnt_n[q] : 0;
+                key = beam_diverse_key(val, lambda, c);
+                idx = cr * V + ci;
+            }
+        }
+        for (int j = 0; j < na; ++j) {
+            float best = key, bv = val;
+            int bi = idx;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ob = __shfl_xor(best, o, 64), ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; bv = ov; }
+            }
+            if (idx == bi) { key = -INFINITY; idx = 0x7fffffff; }      // taken (flat indices are unique)
+            if (lane == 0) { pick_val[j] = bv; pick_idx[j] = bi; }
+        }
+        __syncthreads();
+        if (lane == 0) {
+            int nn = 0, nt = s_ncnt;
+            for (int j = 0; j < na; ++j) {
+                if (pick_idx[j] == 0x7fffffff) continue;       // no admissible candidate left for this beam: it ends unfinished and unlisted
+                const int src = pick_idx[j] / V, tok = pick_idx[j] % V;
+                int q = 0;
+                while (q < nt && cnt_tok[q] != tok) ++q;
+                if (q == nt) { cnt_tok[q] = tok; cnt_n[q] = 0; ++nt; }
+                ++cnt_n[q];
+                if (tok == 2) {
+                    if (a.hyp_cnt[img] < k) {
+                        const int32_t* ss = a.seqs_in + (size_t)(gr0 + src) * a.L;
+                        const int slot = row0 + a.hyp_cnt[img]++;
+                        a.hyp_score[slot] = pick_val[j];
+                        a.hyp_len[slot] = a.step + 1;
+                        int32_t* hs = a.hyp_seq + (size_t)slot * a.L;
+                        for (int i = 0; i < a.step; ++i) hs[i] = ss[i];
+                        hs[a.step] = 2;
+                    }
+                } else {
+                    new_src[nn] = src; new_tok[nn] = tok; new_run[nn] = pick_val[j];
+                    ++nn;
+                }
+            }
+            s_ncnt = nt;
+            s_newn = nn;
+            a.n_act[img * groups + g] = nn;
+            live += nn;
+        }
+        __syncthreads();
+        const int nn = s_newn;
+        for (int j = 0; j < kg; ++j) {
+            if (j < nn) {
+                const int32_t* ss = a.seqs_in + (size_t)(gr0 + new_src[j]) * a.L;
+                int32_t* so = a.seqs_out + (size_t)(gr0 + j) * a.L;
+                for (int i = lane; i < a.step; i += 64) so[i] = ss[i];
+                if (lane == 0) {
+                    so[a.step] = new_tok[j];
+                    a.run[gr0 + j] = new_run[j];
+                    a.src_row[gr0 + j] = gr0 + new_src[j];
+                    a.it_next[gr0 + j] = new_tok[j];
+                }
+            } else if (lane == 0) {
+                a.src_row[gr0 + j] = gr0 + j;
+                a.it_next[gr0 + j] = 0;
+            }
+        }
+        __syncthreads();                                         // the next group overwrites pick_* / new_*
+    }
+    if (lane == 0 && live > 0) atomicAdd(a.n_live, 1);
+}
+
 // state re-gather: out[row,:] = in[src_row[row],:] for the four state tensors
 __global__ __launch_bounds__(256) void beam_gather_kernel(const int32_t* __restrict__ src_row, int H,
                                                           const float* __restrict__ a0, const float* __restrict__ a1,
@@ -493,24 +633,44 @@ __device__ inline float beam_lp_norm(float s, int tokens, int kind, float alpha)
 }
 
 // n-best selection, one wave per image: the image's k hypotheses are its retirements (hyp_*, in retirement order) and the beams
-// still live when the step limit ran out (rows 0 .. n_act - 1 of `seqs`, in merge order).  Ranked: finished before live, then by
+// still live when the step limit ran out (rows 0 .. n_act - 1 of `seqs`, in merge order; grouped: group by group).  Ranked: finished before live, then by
 // the length-normalised score (descending), then by that order.  Writes the first n_best: ids out [n_img, n_best, L] (float32,
 // zero-padded), lens [n_img, n_best], raw scores [n_img, n_best]; a rank past the image's hypotheses (only when every token of
 // some beam was banned) is written as length 0, score -inf.
+// GROUPED (diverse search, n_act [n_img, groups]): the live beams are enumerated in (group, slot) order.
+template <bool GROUPED>
+__device__ inline int beam_live_total(const int* __restrict__ n_act, int img, int groups) {
+    if (!GROUPED) return n_act[img];
+    int t = 0;
+    for (int g = 0; g < groups; ++g) t += n_act[img * groups + g];
+    return t;
+}
+template <bool GROUPED>
+__device__ inline int beam_live_row(const int* __restrict__ n_act, int img, int k, int groups, int q) {     // row of live beam q
+    if (!GROUPED) return img * k + q;
+    const int kg = k / groups;
+    for (int g = 0; g < groups; ++g) {
+        const int na = n_act[img * groups + g];
+        if (q < na) return img * k + g * kg + q;
+        q -= na;
+    }
+    return img * k;      // q < beam_live_total: not reached
+}
+template <bool GROUPED>
 __global__ __launch_bounds__(64) void beam_finalize_nbest_kernel(int k, int L, int steps_done, int n_best, int lp_kind, float lp_alpha,
                                                                  const int* __restrict__ n_act, const float* __restrict__ run,
                                                                  const int32_t* __restrict__ seqs, const int* __restrict__ hyp_cnt,
                                                                  const float* __restrict__ hyp_score, const int* __restrict__ hyp_len,
                                                                  const int32_t* __restrict__ hyp_seq, float* __restrict__ out,
-                                                                 int32_t* __restrict__ lens, float* __restrict__ scores) {
+                                                                 int32_t* __restrict__ lens, float* __restrict__ scores, int groups) {
     __shared__ int s_pick[BEAM_MAX_K];
     const int img = blockIdx.x, lane = threadIdx.x, row0 = img * k;
-    const int nf = hyp_cnt[img], tot = min(nf + n_act[img], k);
+    const int nf = hyp_cnt[img], tot = min(nf + beam_live_total<GROUPED>(n_act, img, groups), k);
     const bool fin = lane < nf;
     float raw = -INFINITY;
     int len = 1;
     if (lane < tot) {
-        raw = fin ? hyp_score[row0 + lane] : run[row0 + lane - nf];
+        raw = fin ? hyp_score[row0 + lane] : run[beam_live_row<GROUPED>(n_act, img, k, groups, lane - nf)];
         len = fin ? hyp_len[row0 + lane] : steps_done + 1;
     }
     const float ns = beam_lp_norm(raw, len - 1, lp_kind, lp_alpha);
@@ -526,12 +686,13 @@ __global__ __launch_bounds__(64) void beam_finalize_nbest_kernel(int k, int L, i
     __syncthreads();
     for (int m = 0; m < n_best; ++m) {
         const int e = s_pick[m], o = img * n_best + m;
-        const int32_t* src = e < 0 ? nullptr : e < nf ? hyp_seq + (size_t)(row0 + e) * L : seqs + (size_t)(row0 + e - nf) * L;
+        const int lr = e < nf ? 0 : beam_live_row<GROUPED>(n_act, img, k, groups, e - nf);
+        const int32_t* src = e < 0 ? nullptr : e < nf ? hyp_seq + (size_t)(row0 + e) * L : seqs + (size_t)lr * L;
         const int ln = e < 0 ? 0 : e < nf ? hyp_len[row0 + e] : steps_done + 1;
         for (int i = lane; i < L; i += 64) out[(size_t)o * L + i] = i < ln ? (float)src[i] : 0.f;
         if (lane == 0) {
             lens[o] = ln;
-            scores[o] = e < 0 ? -INFINITY : e < nf ? hyp_score[row0 + e] : run[row0 + e - nf];
+            scores[o] = e < 0 ? -INFINITY : e < nf ? hyp_score[row0 + e] : run[lr];
         }
     }
 }
@@ -550,6 +711,12 @@ __global__ void beam_init_kernel(int n_img, int k, int L, int* n_act, int32_t* s
         best_score[img] = -INFINITY;
         hyp_cnt[img] = 0;
     }
+}
+
+// grouped search: n_act [n_img, groups] = kg, after beam_init_kernel (which wrote n_act [n_img] = k)
+__global__ void beam_init_groups_kernel(int n, int kg, int* n_act) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) n_act[i] = kg;
 }
 
 }  // namespace

@@ -9,7 +9,7 @@
 namespace icz {
 
 int Butd::beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                      const icz_beam_opts& o, float* scores_out) {
+                      const icz_beam_opts& o, float* scores_out, const icz_beam_diversity& d) {
     ICZ_REQUIRE(feats && seqs_out && lens_out, "butd beam: null argument");
     ICZ_TRY(BeamBuf::check("butd", n_img, k, max_steps, dims.max_rows));
     const int rows = n_img * k, L = max_steps + 1, H = dims.H;
@@ -31,7 +31,7 @@ int Butd::beam_search(const float* feats, int n_img, int k, int max_steps, float
         hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(H, 1024), rows), dim3(256), 0, st, bm.src_row, H, h1[1], c1[1], h2[1], c2[1],
                            h1[0], c1[0], h2[0], c2[0], compact ? k : 1);
     };
-    return bm.search(n_img, k, max_steps, true, logits, dims.V, pad_vocab(dims.V), it, seqs_out, lens_out, o, scores_out, st, step, gather);
+    return bm.search(n_img, k, max_steps, true, logits, dims.V, pad_vocab(dims.V), it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
 }
 
 }  // namespace icz
@@ -48,4 +48,12 @@ extern "C" int icz_butd_beam_search_opts(icz_butd_t* h, const float* feats, int3
     ICZ_REQUIRE(feats && seqs_out && lens_out && scores_out, "icz_butd_beam_search_opts: null argument");
     ICZ_REQUIRE(h, "icz_butd_beam_search_opts: null handle");
     return reinterpret_cast<Butd*>(h)->beam_search(feats, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out);
+}
+extern "C" int icz_butd_beam_search_diverse(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                                            const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
+    ICZ_TRY(BeamBuf::check_opts("icz_butd_beam_search_diverse", beam, opts));      // the arguments first: no handle needed to report them
+    ICZ_TRY(BeamBuf::check_diversity("icz_butd_beam_search_diverse", beam, div));
+    ICZ_REQUIRE(feats && seqs_out && lens_out && scores_out, "icz_butd_beam_search_diverse: null argument");
+    ICZ_REQUIRE(h, "icz_butd_beam_search_diverse: null handle");
+    return reinterpret_cast<Butd*>(h)->beam_search(feats, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out, *div);
 }

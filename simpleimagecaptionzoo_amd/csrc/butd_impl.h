@@ -135,7 +135,8 @@ struct Butd : CaptionHead {
     // beam search (butd_beam.hip)
     BeamBuf bm;
     int beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                    const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr);
+                    const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr,
+                    const icz_beam_diversity& d = BeamBuf::no_diversity);
 
     // training paths (butd_train.hip)
     TrainBuf tb;

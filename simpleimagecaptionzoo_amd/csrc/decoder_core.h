@@ -199,6 +199,8 @@ struct BeamBuf {
     static int check(const char* who, int n_img, int k, int max_steps, int max_rows);
     static int check_opts(const char* who, int k, const icz_beam_opts* o);      // the icz_*_beam_search_opts argument rules
     static const icz_beam_opts defaults;                                       // n_best 1, no blocking, no length penalty
+    static int check_diversity(const char* who, int k, const icz_beam_diversity* d);   // the icz_*_beam_search_diverse rules
+    static const icz_beam_diversity no_diversity;                             // one group: the plain search
     int ensure(DeviceBuffers& m, int max_rows, int L, int extra_feat_cols = 0);
     int begin(int n_img, int k, int L, int64_t* it, hipStream_t st);       // scores, live counts and the <sta> rows of every image
     // The step loop (DecoderRNN.beam_search_sample, BUTD_Model.py:236-318, batched over images): step(step_no, compact) runs the
@@ -208,11 +210,15 @@ struct BeamBuf {
     // Options (icz_beam_opts, checked by check_opts): block_ngram goes to the row-top-k; n_best > 1 or a length penalty keeps the
     // n-best list in the merge and ranks it in beam_finalize_nbest_kernel (seqs_out [n_img, n_best, L], lens_out / scores_out
     // [n_img, n_best]).  At the defaults the launches are today's; scores_out (may be null) receives the raw score of the caption.
+    // Diversity (icz_beam_diversity, checked by check_diversity): groups > 1 keeps n_act per (image, group), runs the grouped
+    // row-top-k instances and beam_merge_groups_kernel, and always keeps the n-best list; one group launches the plain kernels.
     template <class Step, class Gather>
     int search(int n_img, int k, int max_steps, bool compact_first, const float* logits, int V, int ldl, int64_t* it, float* seqs_out,
-               int32_t* lens_out, const icz_beam_opts& o, float* scores_out, hipStream_t st, Step&& step, Gather&& gather) {
-        const int rows = n_img * k, L = max_steps + 1;
-        const bool listed = o.n_best > 1 || o.lp_kind != 0;
+               int32_t* lens_out, const icz_beam_opts& o, const icz_beam_diversity& d, float* scores_out, hipStream_t st, Step&& step,
+               Gather&& gather) {
+        const int rows = n_img * k, L = max_steps + 1, G = d.groups;
+        const bool listed = o.n_best > 1 || o.lp_kind != 0 || G > 1;
+        if (G > 1) hipLaunchKernelGGL(beam_init_groups_kernel, dim3(cdiv(n_img * G, 256)), dim3(256), 0, st, n_img * G, k / G, n_act);
         int sb = 0, steps_done = 0;
         for (int s = 1; s <= max_steps; ++s) {
             const bool compact = compact_first && s == 1 && k > 1;
@@ -220,8 +226,12 @@ struct BeamBuf {
             BeamArgs a = {logits, V, ldl, k, s, L, n_act, run, seqs[sb], seqs[sb ^ 1], src_row, it, best_score, best_len, best_seq,
                           has_complete, n_live + s, listed ? hyp_seq : nullptr, hyp_score, hyp_len, listed ? hyp_cnt : nullptr};
             launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)n_act, (const float*)run, cand_val, cand_idx,
-                                compact ? 1 : 0, seqs[sb], L, o.block_ngram);
-            hipLaunchKernelGGL(beam_merge_kernel, dim3(n_img), dim3(64), 0, st, a, (const float*)cand_val, (const int*)cand_idx);
+                                compact ? 1 : 0, seqs[sb], L, o.block_ngram, G);
+            if (G > 1)
+                hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(n_img), dim3(64), 0, st, a, G, d.diversity, (const float*)cand_val,
+                                   (const int*)cand_idx);
+            else
+                hipLaunchKernelGGL(beam_merge_kernel, dim3(n_img), dim3(64), 0, st, a, (const float*)cand_val, (const int*)cand_idx);
             gather(compact);
             sb ^= 1;
             steps_done = s;
@@ -231,10 +241,14 @@ struct BeamBuf {
                 if (n_live_host[0] == 0) break;
             }
         }
-        if (listed)
-            hipLaunchKernelGGL(beam_finalize_nbest_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, o.n_best, o.lp_kind, o.lp_alpha,
+        if (G > 1)
+            hipLaunchKernelGGL(beam_finalize_nbest_kernel<true>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, o.n_best, o.lp_kind, o.lp_alpha,
                                (const int*)n_act, (const float*)run, (const int32_t*)seqs[sb], (const int*)hyp_cnt, (const float*)hyp_score,
-                               (const int*)hyp_len, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out);
+                               (const int*)hyp_len, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out, G);
+        else if (listed)
+            hipLaunchKernelGGL(beam_finalize_nbest_kernel<false>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, o.n_best, o.lp_kind, o.lp_alpha,
+                               (const int*)n_act, (const float*)run, (const int32_t*)seqs[sb], (const int*)hyp_cnt, (const float*)hyp_score,
+                               (const int*)hyp_len, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out, 1);
         else
             hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_act, run, seqs[sb], has_complete,
                                best_len, best_seq, seqs_out, lens_out, (const float*)best_score, scores_out);

@@ -180,6 +180,16 @@ int BeamBuf::check_opts(const char* who, int k, const icz_beam_opts* o) {
     return ICZ_OK;
 }
 
+const icz_beam_diversity BeamBuf::no_diversity = {1, 0.f};
+
+int BeamBuf::check_diversity(const char* who, int k, const icz_beam_diversity* d) {
+    ICZ_REQUIRE(d, "%s: null diversity", who);
+    ICZ_REQUIRE(d->groups >= 1 && d->groups <= k && k % d->groups == 0, "%s: groups %d outside 1..beam (%d) or not dividing it", who,
+                d->groups, k);
+    ICZ_REQUIRE(std::isfinite(d->diversity) && d->diversity >= 0.f, "%s: diversity %g negative or not finite", who, (double)d->diversity);
+    return ICZ_OK;
+}
+
 // sized for the handle's row capacity and at least 51 columns; a longer search re-allocates (the old buffers stay in the
 // handle's persistent list), the pinned read-back word is allocated once
 int BeamBuf::ensure(DeviceBuffers& m, int max_rows, int L, int extra_feat_cols) {

@@ -54,7 +54,8 @@ struct Nic : CaptionHead {
            const int* live = nullptr);
     int tn(const float* dY, int ldy, int M, const float* Xm, int ldx, int N, int K, float* out, int ldo, int accumulate, hipStream_t st);
     int beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                    const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr);
+                    const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr,
+                    const icz_beam_diversity& d = BeamBuf::no_diversity);
 };
 
 int Nic::init(const icz_nic_dims& d) {
@@ -370,7 +371,7 @@ int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st) {
 }
 
 int Nic::beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                      const icz_beam_opts& o, float* scores_out) {
+                      const icz_beam_opts& o, float* scores_out, const icz_beam_diversity& d) {
     ICZ_REQUIRE(feats && seqs_out && lens_out, "nic beam: null argument");
     ICZ_TRY(BeamBuf::check("nic", n_img, k, max_steps, dims.max_rows));
     ICZ_REQUIRE(fresh, "nic: call icz_nic_refresh_weights after binding/updating parameters");
@@ -385,7 +386,7 @@ int Nic::beam_search(const float* feats, int n_img, int k, int max_steps, float*
     auto gather = [&](bool) {
         hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(H, 1024), rows), dim3(256), 0, st, bm.src_row, H, h[1], c[1], h[1], c[1], h[0], c[0], h[0], c[0], 1);
     };
-    return bm.search(n_img, k, max_steps, false, logits, dims.V, Vp, it, seqs_out, lens_out, o, scores_out, st, step, gather);
+    return bm.search(n_img, k, max_steps, false, logits, dims.V, Vp, it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
 }
 
 }  // namespace icz
@@ -456,4 +457,12 @@ int icz_nic_beam_search_opts(icz_nic_t* h, const float* features, int32_t n_img,
     return reinterpret_cast<Nic*>(h)->beam_search(features, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out);
 }
 
+int icz_nic_beam_search_diverse(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                                const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
+    ICZ_TRY(BeamBuf::check_opts("icz_nic_beam_search_diverse", beam, opts));      // the arguments first: no handle needed to report them
+    ICZ_TRY(BeamBuf::check_diversity("icz_nic_beam_search_diverse", beam, div));
+    ICZ_REQUIRE(features && seqs_out && lens_out && scores_out, "icz_nic_beam_search_diverse: null argument");
+    ICZ_REQUIRE(h, "icz_nic_beam_search_diverse: null handle");
+    return reinterpret_cast<Nic*>(h)->beam_search(features, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out, *div);
+}
 }  // extern "C"

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ._lib import BUTD_PARAM_KEYS, check, lib, ptr, stream_ptr
-from .beam import parse_length_penalty
+from .beam import make_diversity, parse_length_penalty
 from .captioner import BUTDDetection_Captioner
 from .ciderd import CiderDReward
 from . import dist as icz_dist
@@ -501,17 +501,22 @@ class BUTDDetection_Eng(Engine):
                 monitor.set_postfix(Loss=np.round(loss.item(), decimals=4))
 
     # ---- E3 -------------------------------------------------------------------------------------------------
-    def eval_captions_json_generation(self, dataloader, eval_beam_size=-1, tqdm_visible=True, *, length_penalty=None, block_ngram=0):
+    def eval_captions_json_generation(self, dataloader, eval_beam_size=-1, tqdm_visible=True, *, length_penalty=None, block_ngram=0,
+                                      beam_groups=1, diversity=0.0):
         """length_penalty / block_ngram (an extension, beam search only; include/icz.h: icz_beam_opts): rank the finished beams by
-        a length-penalised score (None, ('avg' | 'wu', alpha), 'avg_<alpha>', 'wu_<alpha>') and forbid repeated n-grams."""
+        a length-penalised score (None, ('avg' | 'wu', alpha), 'avg_<alpha>', 'wu_<alpha>') and forbid repeated n-grams.
+        beam_groups / diversity (beam search only; icz_beam_diversity): diverse beam search with eval_beam_size / beam_groups
+        beams per group; the JSON holds each image's rank-0 hypothesis."""
         opts = None
-        if length_penalty is not None or block_ngram:
+        diverse = isinstance(beam_groups, bool) or isinstance(diversity, bool) or beam_groups != 1 or diversity != 0.0
+        if length_penalty is not None or block_ngram or diverse:
             if eval_beam_size == -1:
-                raise ValueError("length_penalty / block_ngram need beam search (eval_beam_size != -1)")
+                raise ValueError("length_penalty / block_ngram / beam_groups / diversity need beam search (eval_beam_size != -1)")
             parse_length_penalty(length_penalty)          # a bad penalty raises here, before any device work
             if int(block_ngram) not in (0, 2, 3, 4):
                 raise ValueError("block_ngram %d not 0, 2, 3 or 4" % int(block_ngram))
-            opts = (length_penalty, int(block_ngram))
+            make_diversity(beam_groups, diversity, eval_beam_size)      # groups not dividing the beam, bad diversity
+            opts = (length_penalty, int(block_ngram), int(beam_groups), float(diversity))
         with _on_stream(self):
             return self._eval_captions_json_generation(dataloader, eval_beam_size, tqdm_visible, opts)
 
@@ -535,7 +540,7 @@ class BUTDDetection_Eng(Engine):
             visual_inputs = self.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
             h = self._hot_handle()
             if eval_beam_size != -1 and opts is not None:
-                seqs, lens, _ = h.beam_search_opts(self._features(visual_inputs), eval_beam_size, 50, 1, opts[0], opts[1])
+                seqs, lens, _ = h.beam_search_opts(self._features(visual_inputs), eval_beam_size, 50, 1, *opts)
                 seqs, lens = seqs[:, 0].cpu().numpy(), lens[:, 0].cpu().numpy()
                 rows = [seqs[i, :lens[i]] for i in range(len(lens))]
             elif eval_beam_size != -1:
