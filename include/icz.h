@@ -386,6 +386,37 @@ int icz_aoa_saved_alphas(icz_aoa_t* h, float* alphas_out, void* stream);
 int icz_aoa_set_scheduled_sampling(icz_aoa_t* h, float ss_prob, const float* gate_uniforms, const float* draw_uniforms);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Model ensembles (beyond the reference; self-critical.pytorch's AttEnsemble): M = 1..4 member decoders -- any mix of BUTD, AoA
+ * and NIC handles (kinds 0, 1, 2) of one vocabulary size V -- decode together.  Each member gets its own features (BUTD / AoA
+ * [B, R_m, D], NIC [B, E]); image b of every member's features is image b of the batch.  Optional weights w_m (finite, >= 0,
+ * sum > 0; normalised to sum 1; NULL = uniform).  Every step, every row's combined log-probability is
+ *     lp[v] = log( sum_m w_m softmax(logits_m)[v] )
+ * (probabilities are averaged, not log-probabilities), computed as lse_m per member, then shifted by the largest term over m.
+ *   greedy: argmax_v lp (ties to the lowest index, as torch.max) for max_len steps, no early stop; ids [B, max_len] int64.
+ *   beam search: the shared search of icz_*_beam_search_diverse runs on lp (its row-top-k takes log_softmax of the row again,
+ *   which leaves a normalised row's selections unchanged); every option holds, the outputs are those of _diverse.
+ * The ensemble does not own its members: they stay alive, bound and refreshed while it decodes; an AoA member's region counts are
+ * those of its last icz_aoa_set_regions.  A decode runs each member's step on one stream, then the combine kernel; beam search
+ * re-gathers every member's state.  Training and sampling from an ensemble are out of scope.
+ * Argument errors return ICZ_ERR_INVALID before any device work: create -- M outside 1..4, a null array, an unknown kind, a null
+ * or repeated member, a bad weight, members of different V; decode -- the options (as _diverse, checked first), a null handle, null
+ * features, an unrefreshed member, B (greedy) or n_img x beam (beam) above any member's row capacity.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct icz_ensemble icz_ensemble_t;
+int icz_ensemble_create(const int32_t* kinds, void* const* members, const float* weights, int32_t M, icz_ensemble_t** out);
+int icz_ensemble_destroy(icz_ensemble_t* h);
+/* feats: HOST array of M device pointers */
+int icz_ensemble_greedy(icz_ensemble_t* h, const float* const* feats, int32_t B, int32_t max_len, int64_t* ids_out, void* stream);
+int icz_ensemble_beam_search_diverse(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                                     const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out,
+                                     float* scores_out, void* stream);
+/* The combine kernel on its own (tests): member m's logits are finished rows [rows][ld_m] (nsplit 1) or nsplit split-K slabs
+ * [nsplit][rows][ld_m] summed in slab order + bias_m.  lp_out [rows][ldo] receives lp; or, argmax_out != NULL, the greedy variant
+ * writes each row's argmax there instead.  Host arrays of device pointers; bias may be NULL when every nsplit is 1. */
+int icz_ensemble_logprob(int32_t M, const float* const* logits, const float* const* bias, const int32_t* nsplit, const int32_t* ld,
+                         const float* weights, int32_t rows, int32_t V, float* lp_out, int32_t ldo, int64_t* argmax_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser step: clip_gradient (Utils.py:241-250, value clamp) + torch.optim.Adam(betas=(0.9,0.999),
  * eps=1e-8, weight_decay=0) (Utils.py:219-220) fused, one call per parameter tensor.
  * ---------------------------------------------------------------------------------------------------------- */

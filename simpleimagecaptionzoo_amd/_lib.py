@@ -177,6 +177,13 @@ def lib():
         "icz_aoa_beam_search": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "icz_aoa_beam_search_opts": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), vp, vp, vp, vp]),
         "icz_aoa_beam_search_diverse": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamDiversity), vp, vp, vp, vp]),
+        "icz_ensemble_create": (C.c_int, [C.POINTER(i32), C.POINTER(vp), C.POINTER(f32), i32, C.POINTER(vp)]),
+        "icz_ensemble_destroy": (C.c_int, [vp]),
+        "icz_ensemble_greedy": (C.c_int, [vp, C.POINTER(vp), i32, i32, vp, vp]),
+        "icz_ensemble_beam_search_diverse": (C.c_int, [vp, C.POINTER(vp), i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamDiversity), vp, vp,
+                                                       vp, vp]),
+        "icz_ensemble_logprob": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32, vp, i32,
+                                           vp, vp]),
         "icz_aoa_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),
         "icz_aoa_scst_rollouts": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp, vp]),
         "icz_aoa_sample_backward": (C.c_int, [vp, vp, C.POINTER(AoaParams), vp, vp, f32, vp]),

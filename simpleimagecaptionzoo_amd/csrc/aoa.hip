@@ -356,23 +356,42 @@ int Aoa::beam_search(const float* feats, int n_img, int kb, int max_steps, float
     ICZ_REQUIRE(feats && seqs_out && lens_out, "aoa beam: null argument");
     ICZ_TRY(BeamBuf::check("aoa", n_img, kb, max_steps, dims.max_rows));
     ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
-    const int rows = n_img * kb, L = max_steps + 1, Hd = dims.Hd;
+    const int rows = n_img * kb, L = max_steps + 1;
     ICZ_TRY(bm.ensure(mem, dims.max_rows, L));
-    use_bank(0);
-    ICZ_TRY(refine(feats, n_img, false, st));
+    ICZ_TRY(prologue(feats, n_img, kb, nullptr, st));
     ICZ_TRY(bm.begin(n_img, kb, L, it, st));
-    ICZ_TRY(zero_state(*this, rows, st));
     auto step = [&](int, bool compact) {        // compact: one decoder row per image (butd_beam.hip)
-        AoaStepIO s = compact ? scratch_io(*this, n_img, nullptr, 0) : scratch_io(*this, rows, bm.img_of_row, 0);
-        s.emb_ready = false;
-        return this->step(s, st);
+        return compact ? this->step(n_img, it, nullptr, 1, 0, false, nullptr, st) : this->step(rows, it, bm.img_of_row, kb, 0, false, nullptr, st);
     };
-    auto gather = [&](bool compact) {
-        hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(Hd, 1024), rows), dim3(256), 0, st, bm.src_row, Hd, h[1], m[1], ctx[1], h[1],
-                           h[0], m[0], ctx[0], u, compact ? kb : 1);
-    };
+    auto gather = [&](bool compact) { this->gather(bm.src_row, rows, compact ? kb : 1, st); };
     return bm.search(n_img, kb, max_steps, true, logits, dims.V, Vp, it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
 }
+
+// ---- decoder seams (DecodeMember) ------------------------------------------------------------------------------------------------
+// the refiner pass (evaluation mode, bank 0; the region counts of icz_aoa_set_regions) and k zeroed state rows per image
+int Aoa::prologue(const float* feats, int n_img, int k, const int32_t*, hipStream_t st) {
+    ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
+    use_bank(0);
+    ICZ_TRY(refine(feats, n_img, false, st));
+    return zero_state(*this, n_img * k, st);
+}
+
+int Aoa::step(int rows, const int64_t* it_, const int32_t* img_of_row, int, int cur, bool slabs, LogitsView* out, hipStream_t st) {
+    AoaStepIO s = scratch_io(*this, rows, img_of_row, cur);
+    s.it = it_;
+    int pns = 1;
+    if (slabs) s.pred_nsplit = &pns;
+    ICZ_TRY(step(s, st));
+    if (out) *out = pns > 1 ? LogitsView{ws, P.predict_b, (size_t)rows * Vp, Vp, pns} : LogitsView{logits, nullptr, 0, Vp, 1};
+    return ICZ_OK;
+}
+
+void Aoa::gather(const int32_t* src_row, int rows, int fan, hipStream_t st) {
+    hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(dims.Hd, 1024), rows), dim3(256), 0, st, src_row, dims.Hd, h[1], m[1], ctx[1], h[1],
+                       h[0], m[0], ctx[0], u, fan);
+}
+
+DecodeMember* aoa_member(void* handle) { return static_cast<DecodeMember*>(reinterpret_cast<Aoa*>(handle)); }
 
 }  // namespace icz
 

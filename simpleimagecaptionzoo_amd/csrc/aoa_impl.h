@@ -36,7 +36,7 @@ struct AoaStepIO {
                                      // entry (step_dead, icz_common.h: the reference's break, AoA_Model.py:400)
 };
 
-struct Aoa : CaptionHead {
+struct Aoa : CaptionHead, DecodeMember {
     static constexpr int STEP_WGS = 256, TARGET_WGS = 512, ARGMAX_PARTS = 8, NL = 6;
     icz_aoa_dims dims;
     icz_aoa_params P;
@@ -138,6 +138,15 @@ struct Aoa : CaptionHead {
     int beam_search(const float* feats, int n_img, int kb, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
                     const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr,
                     const icz_beam_diversity& d = BeamBuf::no_diversity);
+    // decoder seams (DecodeMember, decoder_core.h): the refiner pass, one decoder step, the beam-state gather
+    int vocab() const override { return dims.V; }
+    int row_capacity() const override { return dims.max_rows; }
+    bool refreshed() const override { return fresh; }
+    bool compact_step() const override { return true; }
+    int prologue(const float* feats, int n_img, int k, const int32_t* img_of_row, hipStream_t st) override;
+    int step(int rows, const int64_t* it, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
+             hipStream_t st) override;
+    void gather(const int32_t* src_row, int rows, int fan, hipStream_t st) override;
     DropP dropp(bool train, const uint8_t* mask, size_t off, uint32_t stream, int step, float p) const {
         DropP d = {0, nullptr, d_seed, stream, (uint32_t)step, (uint32_t)((double)p * 4294967296.0), 1.0f / (1.0f - p)};
         if (!train) return d;

@@ -12,27 +12,48 @@ int Butd::beam_search(const float* feats, int n_img, int k, int max_steps, float
                       const icz_beam_opts& o, float* scores_out, const icz_beam_diversity& d) {
     ICZ_REQUIRE(feats && seqs_out && lens_out, "butd beam: null argument");
     ICZ_TRY(BeamBuf::check("butd", n_img, k, max_steps, dims.max_rows));
-    const int rows = n_img * k, L = max_steps + 1, H = dims.H;
+    const int rows = n_img * k, L = max_steps + 1;
     ICZ_TRY(bm.ensure(mem, dims.max_rows, L));
-    ICZ_TRY(prologue(feats, n_img, st));
-    ICZ_TRY(zero_state(rows, 0, st));
+    ICZ_TRY(prologue(feats, n_img, k, nullptr, st));
     ICZ_TRY(bm.begin(n_img, k, L, it, st));
     // Step 1 (compact): the decoder runs ONE row per image (row img of the buffers); the top-k kernel reads image img's logits from
     // row img and the state gather fans row img out to the image's k rows.
     auto step = [&](int, bool compact) {
-        StepIO s = {};
-        s.rows = compact ? n_img : rows; s.feats = feats; s.img_of_row = compact ? nullptr : bm.img_of_row; s.it = it;
-        s.rows_per_img = compact ? 1 : k;
-        s.h1_in = h1[0]; s.c1_in = c1[0]; s.h2_in = h2[0]; s.c2_in = c2[0];
-        s.h1_out = h1[1]; s.c1_out = c1[1]; s.h2_out = h2[1]; s.c2_out = c2[1];
-        return this->step(s, st);
+        return compact ? this->step(n_img, it, nullptr, 1, 0, false, nullptr, st) : this->step(rows, it, bm.img_of_row, k, 0, false, nullptr, st);
     };
-    auto gather = [&](bool compact) {
-        hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(H, 1024), rows), dim3(256), 0, st, bm.src_row, H, h1[1], c1[1], h2[1], c2[1],
-                           h1[0], c1[0], h2[0], c2[0], compact ? k : 1);
-    };
+    auto gather = [&](bool compact) { this->gather(bm.src_row, rows, compact ? k : 1, st); };
     return bm.search(n_img, k, max_steps, true, logits, dims.V, pad_vocab(dims.V), it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
 }
+
+// ---- decoder seams (DecodeMember) ------------------------------------------------------------------------------------------------
+// the per-image prologue, then k zeroed state rows per image
+int Butd::prologue(const float* feats, int n_img, int k, const int32_t*, hipStream_t st) {
+    ICZ_TRY(prologue(feats, n_img, st));
+    seam_feats = feats;
+    return zero_state(n_img * k, 0, st);
+}
+
+int Butd::step(int rows, const int64_t* it_, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
+               hipStream_t st) {
+    StepIO s = {};
+    s.rows = rows; s.feats = seam_feats; s.img_of_row = img_of_row; s.it = it_;
+    s.rows_per_img = rows_per_img;
+    s.h1_in = h1[cur]; s.c1_in = c1[cur]; s.h2_in = h2[cur]; s.c2_in = c2[cur];
+    s.h1_out = h1[cur ^ 1]; s.c1_out = c1[cur ^ 1]; s.h2_out = h2[cur ^ 1]; s.c2_out = c2[cur ^ 1];
+    int pns = 1;
+    if (slabs) s.pred_nsplit = &pns;
+    ICZ_TRY(step(s, st));
+    const int Vp = pad_vocab(dims.V);
+    if (out) *out = pns > 1 ? LogitsView{ws, P.predict_b, (size_t)rows * Vp, Vp, pns} : LogitsView{logits, nullptr, 0, Vp, 1};
+    return ICZ_OK;
+}
+
+void Butd::gather(const int32_t* src_row, int rows, int fan, hipStream_t st) {
+    hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(dims.H, 1024), rows), dim3(256), 0, st, src_row, dims.H, h1[1], c1[1], h2[1], c2[1],
+                       h1[0], c1[0], h2[0], c2[0], fan);
+}
+
+DecodeMember* butd_member(void* handle) { return static_cast<DecodeMember*>(reinterpret_cast<Butd*>(handle)); }
 
 }  // namespace icz
 

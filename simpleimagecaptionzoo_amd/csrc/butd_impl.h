@@ -56,7 +56,7 @@ struct TrainBuf {
     float* wslab = nullptr; size_t wslab_floats = 0;      // split-K slabs of the two attention weight gradients (gemm_tn_split, round 6)
 };
 
-struct Butd : CaptionHead {
+struct Butd : CaptionHead, DecodeMember {
     static constexpr int TARGET_WGS = 512;   // ~2 workgroups per CU on 256 CUs
     static constexpr int ATT_PARTS = 4;
     static constexpr int STEP_WGS = 256;     // skinny decoder-step GEMMs: split-K for ~1 workgroup per CU
@@ -132,8 +132,17 @@ struct Butd : CaptionHead {
                                          // grouped route is slower, 16.3 against 15.9 ms at 64 images x 5 and 5.65 against 4.94 ms at 16 x 4
                                          // (fewer, longer workgroups; the features fit the Infinity Cache either way)
 
-    // beam search (butd_beam.hip)
+    // beam search (butd_beam.hip) on the decoder seams (DecodeMember, decoder_core.h)
     BeamBuf bm;
+    const float* seam_feats = nullptr;   // the features of the last prologue(feats, n_img, k, ...): the steps that follow attend over them
+    int vocab() const override { return dims.V; }
+    int row_capacity() const override { return dims.max_rows; }
+    bool refreshed() const override { return fresh; }
+    bool compact_step() const override { return true; }
+    int prologue(const float* feats, int n_img, int k, const int32_t* img_of_row, hipStream_t st) override;
+    int step(int rows, const int64_t* it, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
+             hipStream_t st) override;
+    void gather(const int32_t* src_row, int rows, int fan, hipStream_t st) override;
     int beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
                     const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr,
                     const icz_beam_diversity& d = BeamBuf::no_diversity);

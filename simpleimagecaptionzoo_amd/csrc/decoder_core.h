@@ -257,6 +257,32 @@ struct BeamBuf {
     }
 };
 
+// Where one decoder step left its logits: ns == 1 finished rows [rows][ld]; ns > 1 the predict GEMM's split-K slabs [ns][rows][ld]
+// (slab z at p + z * slab_stride, no bias yet) + bias[v], summed in slab order as argmax_part_kernel / greedy_select_kernel do.
+struct LogitsView { const float* p; const float* bias; size_t slab_stride; int ld; int ns; };
+
+// The per-image work, one decoder step and the beam-state gather of a decoder, callable from outside its own beam_search: the
+// BUTD, AoA and NIC handles implement it (their beam searches run on it), the model ensemble (ensemble.hip) drives several at once.
+// State: a step reads slot `cur` of the recurrent state and writes slot cur ^ 1; gather() moves slot 1 into slot 0 by source row.
+struct DecodeMember {
+    virtual ~DecodeMember() = default;
+    virtual int vocab() const = 0;
+    virtual int row_capacity() const = 0;
+    virtual bool refreshed() const = 0;
+    virtual bool compact_step() const = 0;      // beam step 1 may run one row per image (gather then fans it out to the k rows)
+    // per-image work for n_img images, k state rows each (zeroed, or NIC's image step; img_of_row: image of each of the n_img k rows)
+    virtual int prologue(const float* feats, int n_img, int k, const int32_t* img_of_row, hipStream_t st) = 0;
+    // one step over `rows` rows on the caller's tokens `it`; img_of_row null = row i is image i.  slabs: the caller's consumer sums
+    // split-K slabs (the view reports which form the logits are in)
+    virtual int step(int rows, const int64_t* it, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
+                     hipStream_t st) = 0;
+    virtual void gather(const int32_t* src_row, int rows, int fan, hipStream_t st) = 0;
+};
+enum { ICZ_MEMBER_BUTD = 0, ICZ_MEMBER_AOA = 1, ICZ_MEMBER_NIC = 2 };
+DecodeMember* butd_member(void* handle);        // the seams of an icz_butd_t / icz_aoa_t / icz_nic_t
+DecodeMember* aoa_member(void* handle);
+DecodeMember* nic_member(void* handle);
+
 // C ABI helpers (butd.hip, aoa.hip, nic.hip)
 template <class Handle, class Dims, class Opaque>
 int abi_create(const char* who, const Dims* dims, Opaque** out) {

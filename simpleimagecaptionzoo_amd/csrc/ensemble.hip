@@ -1,0 +1,327 @@
+// Model ensembles (beyond the reference; self-critical.pytorch's AttEnsemble): M = 1..4 BUTD / AoA / NIC decoder handles of one
+// vocabulary decode together.  Every step each member runs its own step (DecodeMember, decoder_core.h) on the shared tokens, then
+// ensemble_logprob_kernel combines the members' logits into lp[v] = log(sum_m w_m softmax(logits_m)[v]): greedy takes its argmax in
+// the same launch, beam search hands the rows to the shared driver (BeamBuf::search) with every option it has.
+#include <cmath>
+
+#include "decoder_core.h"
+
+namespace icz {
+
+constexpr int ENS_MAX_M = 4;
+
+struct EnsArgs {
+    LogitsView m[ENS_MAX_M];
+    float logw[ENS_MAX_M];            // log of the normalised weights (-inf for a zero weight)
+    int M, V;
+};
+
+__device__ __forceinline__ bool ens_vec_ok(const LogitsView& l) {
+    return ((l.ld | (int)(l.slab_stride & 3)) & 3) == 0 && (((uintptr_t)l.p | (uintptr_t)l.bias) & 15) == 0;
+}
+
+// logits v .. v + 3 of `row` (v % 4 == 0), the slabs summed in slab order then the bias; columns >= V read as -inf
+__device__ __forceinline__ f32x4 ens_load4(const LogitsView& l, int row, int v, int V, bool vec) {
+    const float* r = l.p + (size_t)row * l.ld;
+    f32x4 x;
+    if (vec && v + 4 <= V) {
+        x = *reinterpret_cast<const f32x4*>(r + v);
+        for (int z = 1; z < l.ns; ++z) x += *reinterpret_cast<const f32x4*>(r + (size_t)z * l.slab_stride + v);
+        if (l.ns > 1) x += *reinterpret_cast<const f32x4*>(l.bias + v);
+        return x;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float y = -INFINITY;
+        if (v + j < V) {
+            y = r[v + j];
+            for (int z = 1; z < l.ns; ++z) y += r[(size_t)z * l.slab_stride + v + j];
+            if (l.ns > 1) y += l.bias[v + j];
+        }
+        x[j] = y;
+    }
+    return x;
+}
+
+// running (max, sum of exp(x - max)) pairs
+__device__ __forceinline__ void lse_combine(float& m, float& s, float om, float os) {
+    const float n = fmaxf(m, om);
+    if (n == -INFINITY) return;
+    s = s * expf(m - n) + os * expf(om - n);
+    m = n;
+}
+
+// One workgroup (four waves) per row.  Pass 1: lse_m of every member in one online max / sum-exp pass over its logits (read
+// straight from the member's finished row or its split-K slabs + bias).  Pass 2: lp[v] = log(sum_m w_m exp(x_m[v] - lse_m)), shifted
+// by the largest term over m.  GREEDY: lp is not stored; its argmax (ties to the lowest index, as torch.max) becomes the row's next
+// token it_next[row] and ids_out[row, t].
+template <bool GREEDY>
+__global__ __launch_bounds__(256) void ensemble_logprob_kernel(EnsArgs a, float* __restrict__ out, int ldo, int64_t* __restrict__ it_next,
+                                                               int64_t* __restrict__ ids_out, int ids_stride, int t) {
+    __shared__ float sm[4], ss[4];
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = a.V;
+    float shift[ENS_MAX_M];           // log w_m - lse_m
+    bool vec[ENS_MAX_M];
+#pragma unroll
+    for (int m = 0; m < ENS_MAX_M; ++m) {
+        shift[m] = -INFINITY;
+        vec[m] = false;
+        if (m >= a.M) continue;
+        const LogitsView l = a.m[m];
+        vec[m] = ens_vec_ok(l);
+        float mx = -INFINITY, s = 0.f;
+        for (int v = tid * 4; v < V; v += 1024) {
+            const f32x4 x = ens_load4(l, row, v, V, vec[m]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float y = x[j];
+                if (y > mx) { s = s * expf(mx - y) + 1.f; mx = y; }
+                else if (y != -INFINITY) s += expf(y - mx);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) lse_combine(mx, s, __shfl_xor(mx, o, 64), __shfl_xor(s, o, 64));
+        if (lane == 0) { sm[wave] = mx; ss[wave] = s; }
+        __syncthreads();
+        mx = sm[0]; s = ss[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) lse_combine(mx, s, sm[w], ss[w]);
+        __syncthreads();              // sm / ss are rewritten by the next member
+        shift[m] = a.logw[m] - (mx + logf(s));
+    }
+    float* o_row = out ? out + (size_t)row * ldo : nullptr;
+    const bool ovec = !GREEDY && ((ldo & 3) == 0) && (((uintptr_t)out & 15) == 0);
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int v = tid * 4; v < V; v += 1024) {
+        f32x4 term[ENS_MAX_M];
+        f32x4 top = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+        for (int m = 0; m < ENS_MAX_M; ++m) {
+            if (m >= a.M) continue;
+            term[m] = ens_load4(a.m[m], row, v, V, vec[m]) + shift[m];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) top[j] = fmaxf(top[j], term[m][j]);
+        }
+        f32x4 lp;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float s = 0.f;
+#pragma unroll
+            for (int m = 0; m < ENS_MAX_M; ++m)
+                if (m < a.M && term[m][j] != -INFINITY) s += expf(term[m][j] - top[j]);
+            lp[j] = top[j] == -INFINITY ? -INFINITY : top[j] + logf(s);
+        }
+        if (GREEDY) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (v + j < V && lp[j] > best) { best = lp[j]; bi = v + j; }
+        } else if (ovec && v + 4 <= V) {
+            *reinterpret_cast<f32x4*>(o_row + v) = lp;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (v + j < V) o_row[v + j] = lp[j];
+        }
+    }
+    if (GREEDY) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) argmax_combine(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
+        if (lane == 0) { sv[wave] = best; si[wave] = bi; }
+        __syncthreads();
+        if (tid == 0) {
+            best = sv[0]; bi = si[0];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) argmax_combine(best, bi, sv[w], si[w]);
+            if ((unsigned)bi >= (unsigned)V) bi = 0;       // a row of NaN / -inf log-probs never updates bi: <pad>, not a wild id
+            it_next[row] = bi;
+            if (ids_out) ids_out[(size_t)row * ids_stride + t] = bi;
+        }
+    }
+}
+
+// weights: null = uniform; else finite, >= 0, sum > 0 -> log of the normalised weights
+static int ens_log_weights(const char* who, const float* weights, int M, float* logw) {
+    double sum = 0.0;
+    for (int i = 0; i < M; ++i) {
+        const double w = weights ? (double)weights[i] : 1.0;
+        ICZ_REQUIRE(std::isfinite(w) && w >= 0.0, "%s: weight %d (%g) negative or not finite", who, i, w);
+        sum += w;
+    }
+    ICZ_REQUIRE(sum > 0.0, "%s: the weights sum to 0", who);
+    for (int i = 0; i < M; ++i) {
+        const double w = weights ? (double)weights[i] : 1.0;
+        logw[i] = w > 0.0 ? (float)std::log(w / sum) : -INFINITY;
+    }
+    return ICZ_OK;
+}
+
+static void launch_combine(const EnsArgs& a, int rows, float* out, int ldo, int64_t* it_next, int64_t* ids_out, int ids_stride, int t,
+                           hipStream_t st) {
+    if (it_next)
+        hipLaunchKernelGGL(ensemble_logprob_kernel<true>, dim3(rows), dim3(256), 0, st, a, (float*)nullptr, 0, it_next, ids_out, ids_stride, t);
+    else
+        hipLaunchKernelGGL(ensemble_logprob_kernel<false>, dim3(rows), dim3(256), 0, st, a, out, ldo, (int64_t*)nullptr, (int64_t*)nullptr, 0, 0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The driver: owns the shared tokens `it`, the beam buffers and the combined rows lp [rows, Vp]; the members stay the caller's.
+struct Ensemble {
+    int M = 0, V = 0, Vp = 0, cap = 0;
+    DecodeMember* m[ENS_MAX_M] = {};
+    float logw[ENS_MAX_M] = {};
+    DeviceBuffers mem;
+    BeamBuf bm;
+    int64_t* it = nullptr;
+    float* lp = nullptr;
+
+    int init(const int32_t* kinds, void* const* members, const float* weights, int n);
+    int check_call(const char* who, const float* const* feats, int rows) const;
+    EnsArgs args(const LogitsView* lv) const {
+        EnsArgs a = {};
+        for (int i = 0; i < M; ++i) { a.m[i] = lv[i]; a.logw[i] = logw[i]; }
+        a.M = M; a.V = V;
+        return a;
+    }
+    int greedy(const float* const* feats, int B, int max_len, int64_t* ids_out, hipStream_t st);
+    int beam_search(const float* const* feats, int n_img, int k, int max_steps, const icz_beam_opts& o, const icz_beam_diversity& d,
+                    float* seqs_out, int32_t* lens_out, float* scores_out, hipStream_t st);
+};
+
+int Ensemble::init(const int32_t* kinds, void* const* members, const float* weights, int n) {
+    const char* who = "icz_ensemble_create";
+    ICZ_REQUIRE(n >= 1 && n <= ENS_MAX_M, "%s: %d members outside 1..%d", who, n, ENS_MAX_M);
+    ICZ_REQUIRE(kinds && members, "%s: null argument", who);
+    for (int i = 0; i < n; ++i) {
+        ICZ_REQUIRE(kinds[i] >= ICZ_MEMBER_BUTD && kinds[i] <= ICZ_MEMBER_NIC, "%s: member %d has unknown kind %d (0 BUTD, 1 AoA, 2 NIC)", who, i,
+                    kinds[i]);
+        ICZ_REQUIRE(members[i], "%s: member %d is null", who, i);
+        for (int j = 0; j < i; ++j)
+            ICZ_REQUIRE(members[j] != members[i], "%s: members %d and %d are one handle (its decoder state cannot serve two members)", who, j, i);
+    }
+    ICZ_TRY(ens_log_weights(who, weights, n, logw));
+    for (int i = 0; i < n; ++i)
+        m[i] = kinds[i] == ICZ_MEMBER_BUTD ? butd_member(members[i]) : kinds[i] == ICZ_MEMBER_AOA ? aoa_member(members[i]) : nic_member(members[i]);
+    V = m[0]->vocab();
+    cap = m[0]->row_capacity();
+    for (int i = 1; i < n; ++i) {
+        ICZ_REQUIRE(m[i]->vocab() == V, "%s: member %d has vocabulary %d, member 0 has %d", who, i, m[i]->vocab(), V);
+        if (m[i]->row_capacity() < cap) cap = m[i]->row_capacity();
+    }
+    M = n;
+    Vp = pad_vocab(V);
+    ICZ_TRY(mem.alloc((void**)&it, sizeof(int64_t) * cap));
+    ICZ_TRY(mem.alloc((void**)&lp, sizeof(float) * (size_t)cap * Vp));
+    return mem.synced();
+}
+
+int Ensemble::check_call(const char* who, const float* const* feats, int rows) const {
+    ICZ_REQUIRE(feats, "%s: null features", who);
+    for (int i = 0; i < M; ++i) {
+        ICZ_REQUIRE(feats[i], "%s: null features of member %d", who, i);
+        ICZ_REQUIRE(m[i]->refreshed(), "%s: member %d is not refreshed (call its icz_*_refresh_weights after binding/updating parameters)", who, i);
+        ICZ_REQUIRE(rows <= m[i]->row_capacity(), "%s: %d rows exceed member %d's row capacity %d", who, rows, i, m[i]->row_capacity());
+    }
+    return ICZ_OK;
+}
+
+// one row per image for max_len steps, no early stop (the reference's sample)
+int Ensemble::greedy(const float* const* feats, int B, int max_len, int64_t* ids_out, hipStream_t st) {
+    const char* who = "icz_ensemble_greedy";
+    ICZ_REQUIRE(ids_out && B > 0 && max_len > 0, "%s: bad arguments", who);
+    ICZ_TRY(check_call(who, feats, B));
+    for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->prologue(feats[i], B, 1, nullptr, st));
+    hipLaunchKernelGGL(fill_i64_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, it, (int64_t)1, B);       // <sta>
+    LogitsView lv[ENS_MAX_M];
+    int cur = 0;
+    for (int t = 0; t < max_len; ++t) {
+        for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->step(B, it, nullptr, 1, cur, true, &lv[i], st));
+        launch_combine(args(lv), B, nullptr, 0, it, ids_out, max_len, t, st);
+        cur ^= 1;
+    }
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int Ensemble::beam_search(const float* const* feats, int n_img, int k, int max_steps, const icz_beam_opts& o, const icz_beam_diversity& d,
+                          float* seqs_out, int32_t* lens_out, float* scores_out, hipStream_t st) {
+    const char* who = "icz_ensemble_beam_search_diverse";
+    ICZ_TRY(BeamBuf::check("ensemble", n_img, k, max_steps, 1 << 30));
+    ICZ_TRY(check_call(who, feats, n_img * k));
+    const int rows = n_img * k, L = max_steps + 1;
+    bool compact = true;
+    for (int i = 0; i < M; ++i) compact = compact && m[i]->compact_step();
+    ICZ_TRY(bm.ensure(mem, cap, L));
+    ICZ_TRY(bm.begin(n_img, k, L, it, st));
+    for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->prologue(feats[i], n_img, k, bm.img_of_row, st));
+    LogitsView lv[ENS_MAX_M];
+    auto step = [&](int, bool c) -> int {
+        const int r = c ? n_img : rows;
+        for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->step(r, it, c ? nullptr : bm.img_of_row, c ? 1 : k, 0, true, &lv[i], st));
+        launch_combine(args(lv), r, lp, Vp, nullptr, nullptr, 0, 0, st);
+        return ICZ_OK;
+    };
+    auto gather = [&](bool c) {
+        for (int i = 0; i < M; ++i) m[i]->gather(bm.src_row, rows, c ? k : 1, st);
+    };
+    return bm.search(n_img, k, max_steps, compact, lp, V, Vp, it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
+}
+
+}  // namespace icz
+
+// ================================================================================================
+using namespace icz;
+extern "C" {
+
+int icz_ensemble_create(const int32_t* kinds, void* const* members, const float* weights, int32_t M, icz_ensemble_t** out) {
+    ICZ_REQUIRE(out, "icz_ensemble_create: null argument");
+    Ensemble* e = new Ensemble();
+    const int s = e->init(kinds, members, weights, M);
+    if (s != ICZ_OK) { delete e; return s; }
+    *out = reinterpret_cast<icz_ensemble_t*>(e);
+    return ICZ_OK;
+}
+
+int icz_ensemble_destroy(icz_ensemble_t* h) {
+    delete reinterpret_cast<Ensemble*>(h);
+    return ICZ_OK;
+}
+
+int icz_ensemble_greedy(icz_ensemble_t* h, const float* const* feats, int32_t B, int32_t max_len, int64_t* ids_out, void* stream) {
+    ICZ_REQUIRE(h, "icz_ensemble_greedy: null handle");
+    return reinterpret_cast<Ensemble*>(h)->greedy(feats, B, max_len, ids_out, (hipStream_t)stream);
+}
+
+int icz_ensemble_beam_search_diverse(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                                     const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out,
+                                     float* scores_out, void* stream) {
+    ICZ_TRY(BeamBuf::check_opts("icz_ensemble_beam_search_diverse", beam, opts));      // the arguments first: no handle needed to report them
+    ICZ_TRY(BeamBuf::check_diversity("icz_ensemble_beam_search_diverse", beam, div));
+    ICZ_REQUIRE(seqs_out && lens_out && scores_out, "icz_ensemble_beam_search_diverse: null argument");
+    ICZ_REQUIRE(h, "icz_ensemble_beam_search_diverse: null handle");
+    return reinterpret_cast<Ensemble*>(h)->beam_search(feats, n_img, beam, max_steps, *opts, *div, seqs_out, lens_out, scores_out,
+                                                       (hipStream_t)stream);
+}
+
+int icz_ensemble_logprob(int32_t M, const float* const* logits, const float* const* bias, const int32_t* nsplit, const int32_t* ld,
+                         const float* weights, int32_t rows, int32_t V, float* lp_out, int32_t ldo, int64_t* argmax_out, void* stream) {
+    const char* who = "icz_ensemble_logprob";
+    ICZ_REQUIRE(M >= 1 && M <= ENS_MAX_M, "%s: %d members outside 1..%d", who, M, ENS_MAX_M);
+    ICZ_REQUIRE(logits && nsplit && ld && rows > 0 && V > 0, "%s: bad arguments", who);
+    ICZ_REQUIRE(argmax_out || (lp_out && ldo >= V), "%s: no output (lp_out with ldo >= V, or argmax_out)", who);
+    EnsArgs a = {};
+    ICZ_TRY(ens_log_weights(who, weights, M, a.logw));
+    for (int i = 0; i < M; ++i) {
+        ICZ_REQUIRE(logits[i] && ld[i] >= V && nsplit[i] >= 1, "%s: member %d: null logits, ld < V or nsplit < 1", who, i);
+        ICZ_REQUIRE(nsplit[i] == 1 || (bias && bias[i]), "%s: member %d: split-K slabs need a bias", who, i);
+        a.m[i] = LogitsView{logits[i], nsplit[i] > 1 ? bias[i] : nullptr, (size_t)rows * ld[i], ld[i], nsplit[i]};
+    }
+    a.M = M; a.V = V;
+    launch_combine(a, rows, lp_out, ldo, argmax_out, nullptr, 0, 0, (hipStream_t)stream);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+}  // extern "C"

@@ -9,7 +9,7 @@
 
 namespace icz {
 
-struct Nic : CaptionHead {
+struct Nic : CaptionHead, DecodeMember {
     static constexpr int STEP_WGS = 256, TARGET_WGS = 512, ARGMAX_PARTS = 8;
     icz_nic_dims dims;
     icz_nic_params P;
@@ -56,6 +56,15 @@ struct Nic : CaptionHead {
     int beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
                     const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr,
                     const icz_beam_diversity& d = BeamBuf::no_diversity);
+    // decoder seams (DecodeMember, decoder_core.h): the image step, one token step, the beam-state gather
+    int vocab() const override { return dims.V; }
+    int row_capacity() const override { return dims.max_rows; }
+    bool refreshed() const override { return fresh; }
+    bool compact_step() const override { return false; }
+    int prologue(const float* feats, int n_img, int k, const int32_t* img_of_row, hipStream_t st) override;
+    int step(int rows, const int64_t* it, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
+             hipStream_t st) override;
+    void gather(const int32_t* src_row, int rows, int fan, hipStream_t st) override;
 };
 
 int Nic::init(const icz_nic_dims& d) {
@@ -375,19 +384,41 @@ int Nic::beam_search(const float* feats, int n_img, int k, int max_steps, float*
     ICZ_REQUIRE(feats && seqs_out && lens_out, "nic beam: null argument");
     ICZ_TRY(BeamBuf::check("nic", n_img, k, max_steps, dims.max_rows));
     ICZ_REQUIRE(fresh, "nic: call icz_nic_refresh_weights after binding/updating parameters");
-    const int rows = n_img * k, L = max_steps + 1, H = dims.H;
+    const int rows = n_img * k, L = max_steps + 1;
     ICZ_TRY(bm.ensure(mem, dims.max_rows, L, dims.E));
     ICZ_TRY(bm.begin(n_img, k, L, it, st));
-    // every beam row starts from the image step of its image (features.expand(k, ...), NIC_Model.py:164)
-    hipLaunchKernelGGL(beam_expand_rows_kernel, dim3(cdiv(dims.E, 1024), rows), dim3(256), 0, st, feats, bm.img_of_row, dims.E, bm.feat_rows);
-    ICZ_TRY(image_step(bm.feat_rows, rows, h[0], c[0], nullptr, st));
-    DropCfg off = {0, nullptr, nullptr, 0, 0};
-    auto step = [&](int, bool) { return token_step(rows, it, false, h[0], c[0], h[1], c[1], emb, nullptr, hdrop, logits, off, st); };
-    auto gather = [&](bool) {
-        hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(H, 1024), rows), dim3(256), 0, st, bm.src_row, H, h[1], c[1], h[1], c[1], h[0], c[0], h[0], c[0], 1);
-    };
+    ICZ_TRY(prologue(feats, n_img, k, bm.img_of_row, st));
+    auto step = [&](int, bool) { return this->step(rows, it, bm.img_of_row, k, 0, false, nullptr, st); };
+    auto gather = [&](bool) { this->gather(bm.src_row, rows, 1, st); };
     return bm.search(n_img, k, max_steps, false, logits, dims.V, Vp, it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
 }
+
+// ---- decoder seams (DecodeMember) ------------------------------------------------------------------------------------------------
+// img_of_row null: the image step of the n_img images (k = 1, greedy); else every beam row starts from the image step of its image
+// (features.expand(k, ...), NIC_Model.py:164), through the handle's expanded-feature rows
+int Nic::prologue(const float* feats, int n_img, int k, const int32_t* img_of_row, hipStream_t st) {
+    ICZ_REQUIRE(fresh, "nic: call icz_nic_refresh_weights after binding/updating parameters");
+    if (!img_of_row) return image_step(feats, n_img * k, h[0], c[0], nullptr, st);
+    const int rows = n_img * k;
+    ICZ_TRY(bm.ensure(mem, dims.max_rows, 1, dims.E));       // the beam buffers hold feat_rows (a no-op once a search has run)
+    hipLaunchKernelGGL(beam_expand_rows_kernel, dim3(cdiv(dims.E, 1024), rows), dim3(256), 0, st, feats, img_of_row, dims.E, bm.feat_rows);
+    return image_step(bm.feat_rows, rows, h[0], c[0], nullptr, st);
+}
+
+int Nic::step(int rows, const int64_t* it_, const int32_t*, int, int cur, bool slabs, LogitsView* out, hipStream_t st) {
+    DropCfg off = {0, nullptr, nullptr, 0, 0};
+    int pns = 1;
+    ICZ_TRY(token_step(rows, it_, false, h[cur], c[cur], h[cur ^ 1], c[cur ^ 1], emb, nullptr, hdrop, logits, off, st, slabs ? &pns : nullptr));
+    if (out) *out = pns > 1 ? LogitsView{ws, P.predict_b, (size_t)rows * Vp, Vp, pns} : LogitsView{logits, nullptr, 0, Vp, 1};
+    return ICZ_OK;
+}
+
+void Nic::gather(const int32_t* src_row, int rows, int fan, hipStream_t st) {
+    hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(dims.H, 1024), rows), dim3(256), 0, st, src_row, dims.H, h[1], c[1], h[1], c[1], h[0], c[0],
+                       h[0], c[0], fan);
+}
+
+DecodeMember* nic_member(void* handle) { return static_cast<DecodeMember*>(reinterpret_cast<Nic*>(handle)); }
 
 }  // namespace icz
 

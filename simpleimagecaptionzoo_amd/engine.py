@@ -688,3 +688,73 @@ def _monitor(dataloader, desc, visible):
         return dataloader
     import tqdm
     return tqdm.tqdm(dataloader, desc=desc)
+
+
+def eval_ensemble_captions_json_generation(engines, dataloader, eval_beam_size=-1, tqdm_visible=True, *, weights=None, length_penalty=None,
+                                           block_ngram=0, beam_groups=1, diversity=0.0):
+    """Engine.eval_captions_json_generation for an ensemble of 1..4 engines (BUTD / AoA / NIC) of one vocabulary (an extension;
+    include/icz.h: icz_ensemble_*): every engine turns the shared batch into its own features (its modify_visual_inputs and
+    _features), the members decode together on the averaged word probabilities (`weights`: None = uniform), greedy or with beam
+    search and its options.  Returns the JSON list of the single-model method (the first engine's vocabulary), sharded over the
+    ranks and all-gathered in loader order the same way.  Arguments are checked before any device work (ValueError)."""
+    from .ensemble import EnsembleHandle, check_members, check_weights
+    engines = list(engines)
+    check_members(len(engines))
+    if len({len(e.caption_vocab) for e in engines}) != 1:
+        raise ValueError("the engines' vocabularies differ in size %s" % [len(e.caption_vocab) for e in engines])
+    if len({str(e.device) for e in engines}) != 1:
+        raise ValueError("the engines sit on different devices %s" % [str(e.device) for e in engines])
+    check_weights(weights, len(engines))
+    diverse = isinstance(beam_groups, bool) or isinstance(diversity, bool) or beam_groups != 1 or diversity != 0.0
+    if (length_penalty is not None or block_ngram or diverse) and eval_beam_size == -1:
+        raise ValueError("length_penalty / block_ngram / beam_groups / diversity need beam search (eval_beam_size != -1)")
+    parse_length_penalty(length_penalty)
+    if int(block_ngram) not in (0, 2, 3, 4):
+        raise ValueError("block_ngram %d not 0, 2, 3 or 4" % int(block_ngram))
+    if eval_beam_size != -1:
+        if isinstance(eval_beam_size, bool) or not isinstance(eval_beam_size, int) or eval_beam_size < 1:
+            raise ValueError("eval_beam_size %r: -1 (greedy) or a beam size >= 1" % (eval_beam_size,))
+        make_diversity(beam_groups, diversity, eval_beam_size)
+    opts = (1, length_penalty, int(block_ngram), int(beam_groups), float(diversity))
+    lead = engines[0]
+    with _on_stream(lead):
+        for e in engines:
+            e.model.eval()
+        print("Generating captions json for evaluation (ensemble of %d). Beam Search: %s" % (len(engines), eval_beam_size != -1))
+        dp = icz_dist.is_distributed()
+        rank, world = icz_dist.rank(), icz_dist.world_size()
+        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Generating Process", tqdm_visible)
+        ens = None
+        ids_out, rows_out, keys_out = [], [], []
+        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
+            nb = len(image_ids)
+            feats = []
+            for e in engines:
+                vi = e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
+                feats.append(e._features(vi))
+            handles = [e._hot_handle() for e in engines]
+            if ens is None or any(a is not b for a, b in zip(ens.handles, handles)):
+                ens = EnsembleHandle(handles, weights)
+            if eval_beam_size != -1:
+                seqs, lens, _ = ens.beam_search_opts(feats, eval_beam_size, 50, *opts)
+                seqs, lens = seqs[:, 0].cpu().numpy(), lens[:, 0].cpu().numpy()
+                rows = [seqs[i, :lens[i]] for i in range(len(lens))]
+            else:
+                rows = list(ens.greedy(feats, 20).cpu().numpy())
+            ids_out += [int(i) for i in image_ids]
+            rows_out += rows
+            keys_out += [(batch_i << 20) + j for j in range(nb)]      # loader order: batch index, then row
+        if dp:
+            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, lead.device)
+    result = []
+    ix2word = lead.caption_vocab.ix2word
+    for image_id, sampled_ids in zip(ids_out, rows_out):
+        sampled_caption = []
+        for word_id in sampled_ids:
+            word = ix2word[int(word_id)]
+            if word == "<end>":
+                break
+            elif word != "<sta>":
+                sampled_caption.append(word)
+        result.append({"image_id": image_id, "caption": " ".join(sampled_caption)})
+    return result

@@ -1,0 +1,177 @@
+"""Model ensembles (beyond the reference; self-critical.pytorch's AttEnsemble): several BUTD / AoA / NIC checkpoints of one
+vocabulary decode together, greedy or with every beam-search option, averaging the members' word probabilities each step
+(include/icz.h: icz_ensemble_*).  The members' steps and the combine kernel run on the device (csrc/ensemble.hip)."""
+import ctypes as C
+import math
+import numbers
+
+import torch
+
+from . import beam as _beam
+from ._lib import check, lib, ptr, stream_ptr
+from .aoa import AoADetection_Captioner, AoaHandle
+from .beam import nbest_lists
+from .butd import ButdHandle
+from .captioner import BUTDDetection_Captioner
+from .nic import NICDecoder_Captioner, NicHandle
+
+MAX_MEMBERS = 4
+KINDS = ((ButdHandle, 0), (AoaHandle, 1), (NicHandle, 2))        # icz_ensemble_create's member kinds
+
+
+def _kind(h):
+    for cls, k in KINDS:
+        if isinstance(h, cls):
+            return k
+    raise ValueError("ensemble member %r: expected a ButdHandle, AoaHandle or NicHandle" % (h,))
+
+
+def check_weights(weights, m):
+    """None (uniform) or m finite reals >= 0 with a positive sum -> list of floats (normalised on the device); ValueError otherwise."""
+    if weights is None:
+        return None
+    weights = list(weights)
+    if len(weights) != m:
+        raise ValueError("%d weights for %d members" % (len(weights), m))
+    for w in weights:
+        if isinstance(w, bool) or not isinstance(w, numbers.Real) or not math.isfinite(float(w)) or float(w) < 0:
+            raise ValueError("weight %r: expected a finite real >= 0" % (w,))
+    if sum(float(w) for w in weights) <= 0:
+        raise ValueError("the weights sum to 0")
+    return [float(w) for w in weights]
+
+
+def check_members(n):
+    if not 1 <= n <= MAX_MEMBERS:
+        raise ValueError("an ensemble has 1..%d members, got %d" % (MAX_MEMBERS, n))
+
+
+class EnsembleHandle:
+    """Wraps icz_ensemble_* over decoder handles (ButdHandle / AoaHandle / NicHandle) of one vocabulary.  The handles stay the
+    caller's (this object keeps them referenced): bound and refreshed, they decode image b of each member's features as image b."""
+
+    def __init__(self, handles, weights=None):
+        handles = list(handles)
+        check_members(len(handles))
+        kinds = [_kind(h) for h in handles]
+        if len({id(h) for h in handles}) != len(handles):
+            raise ValueError("an ensemble member appears twice: each member needs a handle of its own")
+        if len({h.V for h in handles}) != 1:
+            raise ValueError("ensemble members have different vocabulary sizes %s" % [h.V for h in handles])
+        w = check_weights(weights, len(handles))
+        self.handles, self.V, self.device = handles, handles[0].V, handles[0].device
+        self._h = C.c_void_p()
+        arr_k = (C.c_int32 * len(handles))(*kinds)
+        arr_m = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
+        arr_w = (C.c_float * len(handles))(*w) if w is not None else None
+        with torch.cuda.device(self.device):
+            check(lib().icz_ensemble_create(arr_k, arr_m, arr_w, len(handles), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().icz_ensemble_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _feats(self, feats_list):
+        """each member's features through its handle's own checks (an AoA member's RegionBatch sets its region counts) ->
+        (the host pointer array, the batch size)"""
+        feats_list = list(feats_list)
+        if len(feats_list) != len(self.handles):
+            raise ValueError("%d feature tensors for %d members" % (len(feats_list), len(self.handles)))
+        out = []
+        for h, f in zip(self.handles, feats_list):
+            out.append(h._check_feats(f) if isinstance(h, ButdHandle) else h._feats(f))
+        sizes = {int(f.shape[0]) for f in out}
+        if len(sizes) != 1:
+            raise ValueError("the members' features hold different image counts %s" % sorted(sizes))
+        self._keep = out           # the kernels of this call read them
+        return (C.c_void_p * len(out))(*[f.data_ptr() for f in out]), sizes.pop()
+
+    def greedy(self, feats_list, max_len=20):
+        """argmax of the combined log-probabilities for max_len steps -> ids (B, max_len) int64, as the members' greedy."""
+        arr, B = self._feats(feats_list)
+        ids = torch.empty(B, max_len, dtype=torch.int64, device=self.device)
+        check(lib().icz_ensemble_greedy(self._h, arr, B, max_len, ptr(ids), stream_ptr()))
+        return ids
+
+    def beam_search_opts(self, feats_list, beam_size=5, max_steps=50, n_best=1, length_penalty=None, block_ngram=0, groups=1, diversity=0.0):
+        """The members' beam_search_opts on the combined log-probabilities: (seqs float32 (n_img, n_best, max_steps+1), lens int32
+        (n_img, n_best), raw scores (n_img, n_best)); the options as ButdHandle.beam_search_opts."""
+        opts = _beam.make_opts(n_best, length_penalty, block_ngram)        # ValueError before the features are looked at
+        div = _beam.make_diversity(groups, diversity, beam_size)
+        arr, n = self._feats(feats_list)
+        m, dev = int(opts.n_best), self.device
+        seqs = torch.zeros(n, m, max_steps + 1, dtype=torch.float32, device=dev)
+        lens = torch.zeros(n, m, dtype=torch.int32, device=dev)
+        scores = torch.zeros(n, m, dtype=torch.float32, device=dev)
+        check(lib().icz_ensemble_beam_search_diverse(self._h, arr, n, beam_size, max_steps, C.byref(opts), C.byref(div), ptr(seqs), ptr(lens),
+                                                      ptr(scores), stream_ptr()))
+        return seqs, lens, scores
+
+
+def member_features(captioner, visual_inputs):
+    """The features `captioner`'s own sampler hands its handle."""
+    if isinstance(captioner, AoADetection_Captioner):
+        return captioner._feats(visual_inputs)
+    if isinstance(captioner, NICDecoder_Captioner):
+        return captioner._features(visual_inputs).detach()
+    if isinstance(captioner, BUTDDetection_Captioner):
+        return visual_inputs["bu_feats"]
+    raise ValueError("ensemble member %r: expected a BUTD, AoA or NIC captioner" % (captioner,))
+
+
+class CaptionEnsemble:
+    """The Captioner decode methods over several captioners (BUTDDetection / AoADetection / NICDecoder) of one vocabulary.  Each
+    method takes one `visual_inputs` per member, in member order."""
+
+    def __init__(self, captioners, weights=None):
+        self.captioners = list(captioners)
+        check_members(len(self.captioners))
+        for c in self.captioners:
+            if not isinstance(c, (BUTDDetection_Captioner, AoADetection_Captioner, NICDecoder_Captioner)):
+                raise ValueError("ensemble member %r: expected a BUTD, AoA or NIC captioner" % (c,))
+        self.weights = check_weights(weights, len(self.captioners))
+        self._ens = None
+
+    def _handle(self):
+        """the members' handles, (re)bound and refreshed as their own samplers do, under one ensemble handle"""
+        handles = [c._handle() for c in self.captioners]
+        if self._ens is None or any(a is not b for a, b in zip(self._ens.handles, handles)):
+            self._ens = EnsembleHandle(handles, self.weights)
+        return self._ens
+
+    def _feats(self, visual_inputs_list):
+        visual_inputs_list = list(visual_inputs_list)
+        if len(visual_inputs_list) != len(self.captioners):
+            raise ValueError("%d visual_inputs for %d members" % (len(visual_inputs_list), len(self.captioners)))
+        return [member_features(c, vi) for c, vi in zip(self.captioners, visual_inputs_list)]
+
+    def sampler(self, visual_inputs_list, max_len=20):
+        """Greedy decode -> LongTensor (B, max_len)."""
+        feats = self._feats(visual_inputs_list)
+        return self._handle().greedy(feats, max_len)
+
+    def beam_search_sampler(self, visual_inputs_list, beam_size=5):
+        """Beam search: a batch of one image returns a (1, L) float tensor, larger batches a list of (1, L_i) tensors."""
+        feats = self._feats(visual_inputs_list)
+        seqs, lens, _ = self._handle().beam_search_opts(feats, beam_size, 50)
+        lens = lens[:, 0].tolist()
+        out = [seqs[i:i + 1, 0, :lens[i]] for i in range(len(lens))]
+        return out[0] if len(out) == 1 else out
+
+    def beam_search_nbest(self, visual_inputs_list, beam_size=5, n_best=None, length_penalty=None, block_ngram=0, groups=1, diversity=0.0):
+        """Each image's n-best list as the captioners' beam_search_nbest: [(ids float32 (1, L_i), raw score)], best first."""
+        opts = (beam_size if n_best is None else n_best, length_penalty, block_ngram, groups, diversity)
+        _beam.make_opts(*opts[:3])
+        _beam.make_diversity(groups, diversity, beam_size)
+        feats = self._feats(visual_inputs_list)
+        return nbest_lists(*self._handle().beam_search_opts(feats, beam_size, 50, *opts))
+
+
+__all__ = ["EnsembleHandle", "CaptionEnsemble", "check_weights", "member_features"]
