@@ -534,6 +534,24 @@ int icz_gemm_big_cfg_for(int32_t layout, int32_t M, int32_t N, int32_t K, int32_
  * LSTM weight gradients (BUTD_Model.py:137-145 under loss.backward(), Engine.py:186,270). */
 int icz_gemm_tn_grouped(const float* dY, int32_t ldy, int32_t M, int32_t K, int32_t ngroups, const float* const* X, const int32_t* ldx,
                         const int32_t* cols, float* const* out, const int32_t* ldo, const int32_t* rows_live, void* stream);
+/* The split-K factor Butd::wgrad gives a weight gradient dY[K, M]^T X[K, N] with fewer than 256 tiles of 128 x 128 (host logic only, no
+ * GPU needed): > 1 = that many slabs on the large-tile split-precision kernel (gemm_tn_split), 1 = shape not taken (it goes through
+ * icz_gemm_f32's TN route), -1 = bad arguments.  Taken: M, N >= 128 and multiples of 4, K >= 512 and a multiple of 16. */
+int icz_gemm_tn_split_pick(int32_t M, int32_t N, int32_t K);
+/* out[M, N] (dense: ldo == N) = dY[K, M]^T X[K, N] the way Butd::wgrad computes such a product: icz_gemm_tn_split_pick(M, N, K) slabs of
+ * M x N floats into `workspace` (splits on 128-deep chunk boundaries of K), then their sum in slab order into `out`.  ICZ_ERR when the
+ * shape is not taken or the workspace is too small.  rows_live: optional device count of the leading rows of K that matter (rounded
+ * up to 32); the rows behind it are not read. */
+int icz_gemm_tn_split(const float* dY, int32_t ldy, int32_t M, const float* X, int32_t ldx, int32_t N, int32_t K, float* out, int32_t ldo,
+                      float* workspace, size_t workspace_floats, const int32_t* rows_live, void* stream);
+/* The kernel icz_gemm_f32 / the decoders' GEMM calls launch for a product of K[0] + ... + K[nseg - 1] (host logic only, no GPU needed):
+ * 0 / 1 / 2 = fp32-MFMA NT kernel with 16 / 32 / 64-row tiles, 3 = resident-activation kernel, four 64-deep stages per workgroup,
+ * 4 = its 512-deep form, 5 = its 128-row form, 6 = split-precision 128 x 128 two-barrier kernel, 7 = a large-tile configuration
+ * (icz_gemm_big_cfg_for says which), 8 = fp32-MFMA NN kernel, 9 = fp32-MFMA TN kernel on 64 x 64 tiles, 10 = fp32 TN kernel on
+ * 128 x 128 tiles (ICZ_GEMM_TN_X3=0); -1 = bad arguments or a split the library refuses.  nsplit 0: the split of a decoder step. */
+int icz_gemm_route_for(int32_t layout, int32_t M, int32_t N, int32_t nseg, const int32_t* K, int32_t nsplit);
+/* Whether icz_gemm_tn_grouped takes column groups of these widths over K rows (host logic only, no GPU needed): 1 / 0, -1 = bad arguments. */
+int icz_gemm_tn_grouped_fits(int32_t M, int32_t K, int32_t ngroups, const int32_t* cols);
 /* Live timing of the dominant kernel (the forward GEMMs of a decoder step at 33..64 rows: gemm_resident_x3_kernel, or
  * gemm_nt_kernel<4, ...> with ICZ_GEMM_RESIDENT_X3=0; see icz_prof_select) with HIP events on its launch stream, for bench.py's
  * roofline line.  Between begin and end every launch is bracketed by an event

@@ -214,6 +214,10 @@ def lib():
         "icz_gemm_set_big_cfg": (C.c_int, [i32]),
         "icz_gemm_big_cfg_for": (C.c_int, [i32, i32, i32, i32, i32]),
         "icz_gemm_tn_grouped": (C.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_gemm_tn_split_pick": (C.c_int, [i32, i32, i32]),
+        "icz_gemm_tn_split": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, C.c_size_t, vp, vp]),
+        "icz_gemm_route_for": (C.c_int, [i32, i32, i32, i32, vp, i32]),
+        "icz_gemm_tn_grouped_fits": (C.c_int, [i32, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         try:

@@ -314,3 +314,41 @@ def gemm_tn_grouped(dY, Xs, outs=None, rows_live=None):
     ldo = (C.c_int32 * n)(*[o.stride(0) for o in outs])
     check(lib().icz_gemm_tn_grouped(ptr(dY), dY.stride(0), M, K, n, xp, ldx, cols, op, ldo, ptr(rows_live), stream_ptr()))
     return outs
+
+
+def gemm_tn_split_pick(M, N, K):
+    """icz_gemm_tn_split_pick (host logic, no GPU): the slabs Butd::wgrad splits dY[K,M]^T X[K,N] into; 1 = shape not taken."""
+    return int(lib().icz_gemm_tn_split_pick(int(M), int(N), int(K)))
+
+
+def gemm_tn_split(dY, X, out=None, workspace=None, rows_live=None):
+    """Test/bench entry for icz_gemm_tn_split: out[M,N] = dY[K,M]^T X[K,N] through split-K slabs in `workspace` and their ordered sum
+    (what Butd::wgrad does for a weight gradient with few tiles), on the current stream.  Raises where the shape is not taken."""
+    K, M = dY.shape
+    N = X.shape[1]
+    if out is None:
+        out = torch.empty(M, N, device=dY.device, dtype=torch.float32)
+    if workspace is None:
+        workspace = torch.empty(max(gemm_tn_split_pick(M, N, K), 1) * M * N, device=dY.device, dtype=torch.float32)
+    check(lib().icz_gemm_tn_split(ptr(dY), dY.stride(0), M, ptr(X), X.stride(0), N, K, ptr(out), out.stride(0), ptr(workspace),
+                                  workspace.numel(), ptr(rows_live), stream_ptr()))
+    return out
+
+
+GEMM_ROUTES = ("nt_fp32_mt1", "nt_fp32_mt2", "nt_fp32_mt4", "resident_4stage", "resident_512deep", "resident_128row", "x3_128tile",
+               "large_tile", "nn_fp32", "tn_fp32_64", "tn_fp32_128")
+
+
+def gemm_route_for(layout, M, N, Ks, nsplit=0):
+    """icz_gemm_route_for (host logic, no GPU): the name of the kernel a product over the K segments `Ks` is launched on (GEMM_ROUTES),
+    None where the library refuses the call."""
+    Ks = [int(k) for k in (Ks if isinstance(Ks, (list, tuple)) else [Ks])]
+    arr = (C.c_int32 * len(Ks))(*Ks)
+    r = int(lib().icz_gemm_route_for({"nt": 0, "nn": 1, "tn": 2}[layout], int(M), int(N), len(Ks), arr, int(nsplit)))
+    return GEMM_ROUTES[r] if r >= 0 else None
+
+
+def gemm_tn_grouped_fits(M, K, cols):
+    """icz_gemm_tn_grouped_fits (host logic, no GPU): whether the grouped weight-gradient launch takes these column groups."""
+    arr = (C.c_int32 * len(cols))(*[int(c) for c in cols])
+    return int(lib().icz_gemm_tn_grouped_fits(int(M), int(K), len(cols), arr)) == 1

@@ -53,7 +53,9 @@ struct TrainBuf {
     float *dc1[2] = {nullptr, nullptr}, *dc2[2] = {nullptr, nullptr};
     float* X[4] = {nullptr, nullptr, nullptr, nullptr}; size_t xfloats = 0;
     float *dWp = nullptr, *dWenc = nullptr, *dWdec = nullptr, *dWaff = nullptr, *scalars = nullptr;
-    float* wslab = nullptr; size_t wslab_floats = 0;      // split-K slabs of the two attention weight gradients (gemm_tn_split, round 6)
+    // split-K slabs of the weight gradients that take gemm_tn_split (Butd::wgrad), one region per stream that can be inside bptt() at the
+    // same time: [0] the stream bptt() was called on, [1] the low-priority side stream (predict branch, then the attention tail)
+    float* wslab[2] = {nullptr, nullptr}; size_t wslab_floats[2] = {0, 0};
 };
 
 struct Butd : CaptionHead, DecodeMember {

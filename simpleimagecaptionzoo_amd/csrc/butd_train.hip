@@ -85,11 +85,21 @@ int Butd::ensure_train(int B, int T) {
     ICZ_TRY(alloc((void**)&tb.dWp, sizeof(float) * Vp * H));
     ICZ_TRY(alloc((void**)&tb.dWenc, sizeof(float) * A * D));
     ICZ_TRY(alloc((void**)&tb.dWdec, sizeof(float) * A * H));
-    {   // slabs of the two attention weight gradients (A x H over T B rows, A x D over B R rows), one buffer: they run one after the other
-        const size_t n1 = (size_t)gemm_tn_split_pick((int)A, (int)H, (int)TB) * A * H, n2 = (size_t)gemm_tn_split_pick((int)A, (int)D, (int)(B * R)) * A * D;
-        tb.wslab_floats = n1 > n2 ? n1 : n2;
-        if (tb.wslab_floats > A * (H > D ? H : D)) ICZ_TRY(alloc((void**)&tb.wslab, sizeof(float) * tb.wslab_floats));
-        else tb.wslab_floats = 0;
+    {   // Split-K slabs of the weight gradients Butd::wgrad sends through gemm_tn_split (fewer than 256 tiles of 128 x 128, written with
+        // ldo == N): W_hh of the two LSTMs when their column group is not taken (4H x H over T B rows), the two attention projections
+        // (A x H over T B rows, A x D over B R rows), predict (Vp x H over T B rows).  One region per stream that can be inside bptt() at
+        // the same time -- products of one stream run one after the other and share theirs: [1] belongs to the low-priority side stream
+        // (predict branch, then the attention tail), [0] to the stream bptt() was called on (the LSTM products; all five when nothing is
+        // forked: `concurrent` off, a gradient callback, phases as separate calls).  A product whose slabs do not fit takes the plain route.
+        auto slabs = [](size_t M, size_t N, size_t K) { return (size_t)gemm_tn_split_pick((int)M, (int)N, (int)K) * M * N; };   // M N = no split
+        const size_t side[3] = {slabs(A, H, TB), slabs(A, D, B * R), slabs(Vp, H, TB)}, own = slabs(4 * H, H, TB);
+        const size_t direct[3] = {A * H, A * D, Vp * H};
+        for (int i = 0; i < 3; ++i)
+            if (side[i] > direct[i] && side[i] > tb.wslab_floats[1]) tb.wslab_floats[1] = side[i];
+        tb.wslab_floats[0] = tb.wslab_floats[1];
+        if (own > 4 * H * H && own > tb.wslab_floats[0]) tb.wslab_floats[0] = own;
+        for (int i = 0; i < 2; ++i)
+            if (tb.wslab_floats[i]) ICZ_TRY(alloc((void**)&tb.wslab[i], sizeof(float) * tb.wslab_floats[i]));
     }
     ICZ_TRY(alloc((void**)&tb.dWaff, sizeof(float) * A));
     ICZ_TRY(alloc((void**)&tb.scalars, sizeof(float) * 16));
@@ -459,13 +469,16 @@ int Butd::gemm_auto(GemmLayout layout, GemmArgs& g, float* slab, size_t slab_flo
 
 // C (ldc) = A^T B over K rows, written directly (no split): weight gradients
 int Butd::wgrad(const float* dY, int ldy, int M, const float* X, int ldx, int N, int K, float* out, int ldo, hipStream_t st, const int* rows_live) {
-    // too few 128 x 128 tiles to fill the chip (the attention projections): split K on the large-tile split-precision kernel, sum the slabs
-    if (tb.wslab && ldo == N) {
+    // too few 128 x 128 tiles to fill the chip (at full width the attention projections): split K on the large-tile split-precision kernel, sum the slabs
+    // (no two streams share slab memory: the side stream's products have a region of their own, see ensure_train)
+    float* const slab = tb.wslab[st == low.st ? 1 : 0];
+    const size_t slab_floats = tb.wslab_floats[st == low.st ? 1 : 0];
+    if (slab && ldo == N) {
         const int ns = gemm_tn_split_pick(M, N, K);
-        if (ns > 1 && (size_t)ns * M * N <= tb.wslab_floats && ((size_t)M * N) % 4 == 0) {
-            ICZ_TRY(gemm_tn_split(dY, ldy, M, X, ldx, N, K, ns, tb.wslab, rows_live, st));
+        if (ns > 1 && (size_t)ns * M * N <= slab_floats && ((size_t)M * N) % 4 == 0) {
+            ICZ_TRY(gemm_tn_split(dY, ldy, M, X, ldx, N, K, ns, slab, rows_live, st));
             const size_t MN = (size_t)M * N;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, (const float*)tb.wslab, ns, MN, N, (const float*)nullptr, out);
+            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, (const float*)slab, ns, MN, N, (const float*)nullptr, out);
             ICZ_CHECK_HIP(hipGetLastError());
             return ICZ_OK;
         }

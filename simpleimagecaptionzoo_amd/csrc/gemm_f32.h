@@ -62,6 +62,8 @@ struct GemmArgs {
 };
 
 int gemm_f32(GemmLayout layout, const GemmArgs& a, hipStream_t stream);
+// the kernel gemm_f32 picks for a product (host logic, shapes only; values: icz_gemm_route_for in include/icz.h), -1 = refused
+int gemm_route(GemmLayout layout, const GemmArgs& a);
 // picks a split-K factor so that the launch has about `target_wgs` workgroups
 int gemm_pick_split(const GemmArgs& a, int target_wgs, GemmLayout layout = GEMM_NT);
 // the same for launches with many tiles: balances whole rounds of workgroups over the 256 CUs (see gemm_f32.hip)
@@ -112,8 +114,8 @@ int gemm_tn_grouped(const float* dY, int ldy, int M, int K, const GemmColGroup* 
 // ICZ_GEMM_RESIDENT_M128 (0: 65..128 rows go to the 128 x 128-tile kernel instead of the 128-row resident kernel),
 // ICZ_PREDICT_SLABS (0: un-split vocabulary projection -- the slab A/B test), ICZ_PROF_EVERY (event pairs on every n-th launch),
 // ICZ_GEMM_BIG (unset / -1: gemm_big_cfg's choice per shape; 0: the 128 x 128 two-barrier kernel everywhere; 1..5: that large-tile configuration everywhere).
-// (round 6) TN products too small to fill the chip on 128 x 128 tiles (fewer than 256 of them: the weight gradients of the two attention
-// projections, 1024 x 1024 over 1280 rows and 1024 x 2048 over 2304) on the large-tile split-precision kernel with split-K slabs
+// (round 6) TN products too small to fill the chip on 128 x 128 tiles (fewer than 256 of them: at full width the weight gradients of the two
+// attention projections, 1024 x 1024 over 1280 rows and 1024 x 2048 over 2304; at other widths W_hh of the LSTMs and predict as well) on the large-tile split-precision kernel with split-K slabs
 // [nsplit][M][N] (the caller sums them: slab_reduce_kernel) instead of the fp32-MFMA 64 x 64 kernel.  gemm_tn_split_pick: the split (1 =
 // shape not taken); gemm_tn_split: the launch (K a multiple of 16, splits on 128-deep chunk boundaries, rows_live as in gemm_tn_grouped).
 int gemm_tn_split_pick(int M, int N, int K);

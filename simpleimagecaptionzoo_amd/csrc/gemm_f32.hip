@@ -1219,6 +1219,31 @@ int gemm_f32(GemmLayout layout, const GemmArgs& a_in, hipStream_t stream) {
     return ICZ_OK;
 }
 
+// The kernel gemm_f32 launches for a product, by the tests of gemm_f32 above in the same order (host logic only; include/icz.h:
+// icz_gemm_route_for names the values).  `a` needs shapes only: M, N, nseg, seg[].K, nsplit.
+int gemm_route(GemmLayout layout, const GemmArgs& a_in) {
+    GemmArgs a = a_in;
+    const int tot = total_chunks(a, stage_k(layout, a));
+    if (a.nsplit < 1 || a.nsplit > tot) return -1;
+    a.chunks_per_split = cdiv(tot, a.nsplit);
+    if (cdiv(tot, a.chunks_per_split) != a.nsplit) return -1;          // empty splits: gemm_f32 refuses
+    if (layout == GEMM_NT) {
+        if (nt_x3big(a)) return gemm_big_cfg(layout, a) ? 7 : 6;
+        if (gemm_resident_x3_fits(a) && a.nsplit == gemm_resident_x3_nsplit(a) && a.chunks_per_split == gemm_resident_x3_stages(a))
+            return a.M > 64 ? 5 : (a.chunks_per_split == 8 ? 4 : 3);
+        return a.M <= 16 ? 0 : (a.M <= 32 ? 1 : 2);
+    }
+    if (layout == GEMM_NN) {
+        if (nn_x3(a)) return gemm_big_cfg(layout, a) ? 7 : 6;
+        return 8;
+    }
+    if (a.nsplit == 1 && a.nseg == 1 && cdiv(a.M, 128) * cdiv(a.N, 128) >= 256 && a.seg[0].K % 32 == 0 && a.seg[0].K >= 64) {
+        if (!gemm_switches().tn_x3) return 10;
+        return gemm_big_cfg(layout, a) ? 7 : 6;
+    }
+    return 9;
+}
+
 bool gemm_prof_on() { return g_prof.on; }
 void gemm_prof_select(int which) { g_prof.select = which; }
 void gemm_prof_begin() {
@@ -1390,6 +1415,47 @@ int icz_gemm_big_cfg_for(int32_t layout, int32_t M, int32_t N, int32_t K, int32_
     g.seg[0].K = K;
     g.M = M; g.N = N; g.nsplit = nsplit > 0 ? nsplit : 1;
     return gemm_big_cfg((GemmLayout)layout, g);
+}
+
+int icz_gemm_tn_grouped_fits(int32_t M, int32_t K, int32_t ngroups, const int32_t* cols) {
+    if (M <= 0 || K <= 0 || ngroups < 1 || ngroups > GEMM_MAX_COLGROUPS || !cols) return -1;
+    GemmColGroup g[GEMM_MAX_COLGROUPS] = {};
+    for (int j = 0; j < ngroups; ++j) g[j].cols = cols[j];
+    return gemm_tn_grouped_fits(M, K, g, ngroups) ? 1 : 0;
+}
+
+int icz_gemm_route_for(int32_t layout, int32_t M, int32_t N, int32_t nseg, const int32_t* K, int32_t nsplit) {
+    if (layout < 0 || layout > 2 || M <= 0 || N <= 0 || nseg < 1 || nseg > GEMM_MAX_SEG || !K || nsplit < 0) return -1;
+    GemmArgs g = {};
+    g.nseg = nseg;
+    for (int s = 0; s < nseg; ++s) {
+        if (K[s] <= 0) return -1;
+        g.seg[s].K = K[s];
+    }
+    g.M = M; g.N = N;
+    g.nsplit = nsplit > 0 ? nsplit : gemm_pick_split(g, 256, (GemmLayout)layout);      // 256: the decoder steps' target (STEP_WGS)
+    return gemm_route((GemmLayout)layout, g);
+}
+
+int icz_gemm_tn_split_pick(int32_t M, int32_t N, int32_t K) {
+    if (M <= 0 || N <= 0 || K <= 0) return -1;
+    return gemm_tn_split_pick(M, N, K);
+}
+
+int icz_gemm_tn_split(const float* dY, int32_t ldy, int32_t M, const float* X, int32_t ldx, int32_t N, int32_t K, float* out, int32_t ldo,
+                      float* workspace, size_t workspace_floats, const int32_t* rows_live, void* stream) {
+    ICZ_REQUIRE(dY && X && out && M > 0 && N > 0 && K > 0 && ldy >= M && ldx >= N, "icz_gemm_tn_split: bad arguments");
+    ICZ_REQUIRE(ldo == N, "icz_gemm_tn_split: the slab sum writes a dense output (ldo %d, N %d)", ldo, N);
+    const int ns = gemm_tn_split_pick(M, N, K);
+    ICZ_REQUIRE(ns > 1, "icz_gemm_tn_split: shape not taken (M %d N %d K %d): issue it through icz_gemm_f32", M, N, K);
+    const size_t MN = (size_t)M * N;
+    ICZ_REQUIRE(workspace && (size_t)ns * MN <= workspace_floats, "icz_gemm_tn_split: workspace of %zu floats too small for %d slabs of %d x %d", workspace_floats, ns, M, N);
+    ICZ_REQUIRE(((uintptr_t)out & 15) == 0, "icz_gemm_tn_split: output must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    ICZ_TRY(gemm_tn_split(dY, ldy, M, X, ldx, N, K, ns, workspace, rows_live, st));
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, (const float*)workspace, ns, MN, N, (const float*)nullptr, out);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
 }
 
 int icz_gemm_tn_grouped(const float* dY, int32_t ldy, int32_t M, int32_t K, int32_t ngroups, const float* const* X, const int32_t* ldx,

@@ -13,15 +13,16 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 from synth import feats_from_seed, probe_indices  # noqa: E402,F401
 
 R, D, H, E, A, V = 36, 2048, 1024, 1024, 1024, 10102
+FULL_DIMS = (R, D, H, E, A, V)
 
 
 def _cpu(params, grad=False):
     return {k: v.detach().cpu().clone().requires_grad_(grad) for k, v in params.items()}
 
 
-def _full_params(seed=77, sharpen=6.0):
+def _full_params(seed=77, sharpen=6.0, dims=FULL_DIMS):
     from simpleimagecaptionzoo_amd.synth import random_butd_params
-    params = random_butd_params(R, D, H, E, A, V, "cuda", seed=seed)
+    params = random_butd_params(*dims, "cuda", seed=seed)
     params["predict.weight_g"].mul_(sharpen)      # trained decoders are far from uniform: well separated argmax / draws
     return params
 
@@ -109,14 +110,18 @@ def attention_kink_units(feats64, p64, h1_steps, att_masks, tol=3e-6, active_row
     return hit.numpy()
 
 
-def _butd_scst_case(B, T, seed, sharpen=6.0, options=None, with_reward=False):
-    """device rollouts + REINFORCE gradients of B rows x T steps at full width, and the fp32 / float64 oracle passes on the same inputs
-    (options: {handle option: value} set before the run).  with_reward: the step's CIDEr-D reward as well -- computed on the device from
-    the ids the device produced, bit-exact against the oracle's (Utils.py:319-367) -- and used as the REINFORCE reward (plus a per-row
+def _butd_scst_case(B, T, seed, sharpen=6.0, options=None, with_reward=False, dims=FULL_DIMS, samples_per_image=1):
+    """device rollouts + REINFORCE gradients of B rows x T steps at full width (or at the widths `dims` = (R, D, H, E, A, V)), and the
+    fp32 / float64 oracle passes on the same inputs (options: {handle option: value} set before the run).  samples_per_image = K > 1:
+    the B rows are K sampled captions of each of B / K images (sample_n; the greedy decode of the images runs beside it).
+    with_reward: the step's CIDEr-D reward as well -- computed on the device from the ids the device produced, bit-exact against the oracle's (Utils.py:319-367) -- and used as the REINFORCE reward (plus a per-row
     signal: a random-init model scores ~0 against random references)"""
     from oracle import butd as ob
     from simpleimagecaptionzoo_amd.butd import ButdHandle, make_rng
     from simpleimagecaptionzoo_amd.synth import random_butd_params
+    R, D, H, E, A, V = dims
+    K = samples_per_image
+    assert B % K == 0
     params = random_butd_params(R, D, H, E, A, V, "cuda", seed=seed)
     params["predict.weight_g"].mul_(sharpen)
     h = ButdHandle(R, D, H, E, A, V, max(B, 8), T)
@@ -125,14 +130,19 @@ def _butd_scst_case(B, T, seed, sharpen=6.0, options=None, with_reward=False):
         h.set_option(name, value)
     g = torch.Generator(device="cpu")
     g.manual_seed(1000 + seed)
-    feats_c = torch.relu(torch.randn(B, R, D, generator=g))
+    img_feats = torch.relu(torch.randn(B // K, R, D, generator=g))
+    feats_c = img_feats.repeat_interleave(K, 0) if K > 1 else img_feats         # what each decoder row attends over
     rs = np.random.RandomState(seed)
     em, am, om = rs.rand(T, B, E) < 0.5, rs.rand(T, B, R, A) < 0.5, rs.rand(T, B, H) < 0.5
     u = rs.rand(T, B).astype(np.float32)
     dev = "cuda"
     rng = make_rng(0, torch.tensor(u, device=dev), torch.tensor(em.astype(np.uint8), device=dev),
                    torch.tensor(am.astype(np.uint8), device=dev), torch.tensor(om.astype(np.uint8), device=dev))
-    greedy, seq, lp = h.rollouts(feats_c.cuda(), T, rng)
+    if K > 1:
+        greedy = h.greedy(img_feats.cuda(), T).clone()
+        seq, lp = h.sample_n(img_feats.cuda(), K, T, rng)
+    else:
+        greedy, seq, lp = h.rollouts(feats_c.cuda(), T, rng)
     greedy, seq, lp = greedy.cpu().numpy(), seq.cpu().numpy(), lp.cpu().numpy()
     out = {}
     for name, dt in (("f32", torch.float32), ("f64", torch.float64)):
@@ -146,7 +156,7 @@ def _butd_scst_case(B, T, seed, sharpen=6.0, options=None, with_reward=False):
             torch.set_default_dtype(torch.float32)
     p32 = out["f32"][0]
     with torch.no_grad():
-        w_greedy, _, w_glog = ob.greedy(feats_c, {k: v.detach() for k, v in p32.items()}, T, hoisted=True)
+        w_greedy, _, w_glog = ob.greedy(img_feats, {k: v.detach() for k, v in p32.items()}, T, hoisted=True)
     limit = max(1, B // 32)
     _excuse_greedy(greedy, w_greedy, w_glog, limit)
     ok = _excuse_sampled(seq, out["f32"][1], out["f32"][3], u, limit)
@@ -192,7 +202,8 @@ def _butd_scst_case(B, T, seed, sharpen=6.0, options=None, with_reward=False):
     return rep, kink
 
 
-def _butd_inputs(seed, B):      # as tests/golden/make_fullwidth_goldens.py: butd_inputs
+def _butd_inputs(seed, B, dims=FULL_DIMS):      # as tests/golden/make_fullwidth_goldens.py: butd_inputs
+    R, D, H, E, A, V = dims
     rs = np.random.RandomState(seed)
     feats = feats_from_seed(seed + 1, B, R, D)
     st = [(rs.randn(B, H) * 0.5).astype(np.float32) for _ in range(4)]
@@ -303,3 +314,172 @@ def _check_dp_fields(j):
     ov = j["dp_overlap"]
     assert ov["on_ms"] > 0 and ov["off_ms"] > 0 and ov["allreduce_exposed_off_ms"] > 0 and ov["allreduce_exposed_on_ms"] >= 0
     assert j["vs_baseline"] is None and j["vs_reference_in_container"] > 0
+
+
+# ---- BUTD between the golden widths and the benchmark width -------------------------------------------------------------------------
+# One table for the GPU parity tests (tests/test_gpu_butd_midwidth.py) and the CPU route test (tests/test_cpu_abi_and_host.py):
+# name -> (dims = (R, D, H, E, A, V), [(rows, steps, kind)], what the width is there for).  kind: "scst" = rollouts + sample_backward,
+# "merged" = the same on the merged chain of a small batch (merge_small), "sample_n4" = 4 samples per image.  `midwidth_routes` states
+# each purpose as host predicates; the CPU test asserts them, so a retuned threshold names the width that lost its purpose.
+MIDWIDTH = {
+    "w512": ((36, 2048, 512, 512, 512, 3000), [(64, 20, "scst")],
+             "gates N = 2048, the first width on the resident kernel; TD group not taken, LM group taken; td_w_hh, dWdec, dWenc and "
+             "predict's weight gradient all on split-K slabs (gemm_tn_split) from two streams"),
+    "w640": ((36, 2048, 640, 512, 384, 5000), [(64, 20, "scst")],
+             "60 / 52 stages: the resident kernel's four-stage form; A != H != E; no weight-gradient group taken (640 % 256), td_w_hh and "
+             "lm_w_hh both on split-K slabs beside the attention tail's and predict's"),
+    "w768": ((36, 2048, 768, 512, 768, 10102), [(64, 20, "scst"), (100, 8, "scst")],
+             "stage counts % 8 == 0 (512-deep resident form) away from 1024; 100 rows: the 128-row resident kernel; both weight-gradient "
+             "groups taken with column groups of 768 and 512"),
+    "w256": ((36, 1024, 256, 192, 320, 2051), [(48, 20, "scst"), (16, 20, "merged"), (48, 20, "sample_n4")],
+             "gates N = 1024 < 2048: every decoder-step product on the fp32-MFMA kernels, no transposed weight copies; odd V; the merged "
+             "chain of a 16-row batch; 4 samples per image"),
+    "w336": ((49, 512, 336, 160, 224, 1237), [(20, 12, "scst")],
+             "H and E no multiples of 64 (tail kernels), 4 H no multiple of 128 (the split-precision NN / NT kernels refuse the dgrad "
+             "products); <= 32 rows (32-row NT tiles); 49 regions; no weight gradient on slabs"),
+}
+
+
+def midwidth_routes(name):
+    """{claim: bool} -- what MIDWIDTH[name] is there for, from the library's host-only routing entries (no GPU needed)"""
+    from simpleimagecaptionzoo_amd.butd import gemm_route_for as route, gemm_tn_grouped_fits as grouped, gemm_tn_split_pick as split
+    (R_, D_, H_, E_, A_, V_), cases, _ = MIDWIDTH[name]
+    B, T, _ = cases[0]
+    TB, Vp = B * T, (V_ + 63) // 64 * 64
+    td, lm = route("nt", B, 4 * H_, [H_, E_, H_]), route("nt", B, 4 * H_, [D_, H_, H_])
+    td_grp, lm_grp = grouped(4 * H_, TB, [H_, E_, H_]), grouped(4 * H_, TB, [D_, H_, H_])
+    s_hh, s_dec, s_enc, s_p = split(4 * H_, H_, TB), split(A_, H_, TB), split(A_, D_, B * R_), split(Vp, H_, TB)
+    fp32_nt = ("nt_fp32_mt1", "nt_fp32_mt2", "nt_fp32_mt4")
+    if name == "w512":
+        return {"gates on the resident kernel": td.startswith("resident") and lm.startswith("resident"),
+                "one width below (N = 1984) not": route("nt", B, 4 * 496, [496, E_, 496]) in fp32_nt,
+                "TD group not taken, LM group taken": not td_grp and lm_grp,
+                "td_w_hh, dWdec, dWenc, dWp on slabs": min(s_hh, s_dec, s_enc, s_p) > 1}
+    if name == "w640":
+        return {"four-stage resident form": td == lm == "resident_4stage",
+                "no group taken": not td_grp and not lm_grp,
+                "td_w_hh / lm_w_hh, dWdec, dWenc, dWp on slabs": min(s_hh, s_dec, s_enc, s_p) > 1}
+    if name == "w768":
+        B2, T2, _ = cases[1]
+        return {"512-deep resident form at 64 rows": td == lm == "resident_512deep",
+                "128-row resident kernel at 100 rows": route("nt", B2, 4 * H_, [H_, E_, H_]) == route("nt", B2, 4 * H_, [D_, H_, H_]) == "resident_128row",
+                "both groups taken": td_grp and lm_grp and grouped(4 * H_, B2 * T2, [H_, E_, H_]) and grouped(4 * H_, B2 * T2, [D_, H_, H_]),
+                "attention tail on slabs": s_dec > 1 and s_enc > 1}
+    if name == "w256":
+        small = [route("nt", 32, 4 * H_, [H_, E_, H_]), route("nt", 32, 4 * H_, [D_, H_, H_]), route("nt", 32, A_, [H_])]
+        return {"decoder step on the fp32-MFMA NT kernel": td == lm == route("nt", B, A_, [H_]) == route("nt", B, Vp, [H_]) == "nt_fp32_mt4",
+                "merged chain (32 rows) on 32-row tiles": all(r == "nt_fp32_mt2" for r in small),
+                "per-step dgrad on the fp32 NN kernel": route("nn", B, D_ + H_, [4 * H_], 1) == "nn_fp32",
+                "no group taken, weight gradients of the LSTMs on the 64 x 64 TN kernel": not td_grp and not lm_grp and route("tn", 4 * H_, D_, [TB], 1) == "tn_fp32_64",
+                "odd V": V_ % 2 == 1 and V_ % 64 != 0}
+    if name == "w336":
+        return {"32-row NT tiles": td == lm == "nt_fp32_mt2",
+                "K % 64 != 0 in the gate segments": H_ % 64 != 0 and E_ % 64 != 0,
+                "dgrad over all steps refused by the split-precision NN kernel": route("nn", TB, E_, [4 * H_], 1) == "nn_fp32" and (4 * H_) % 128 != 0,
+                "XE vocabulary projection on the fp32 NT kernel": route("nt", TB, Vp, [H_], 1) == "nt_fp32_mt4",
+                "no weight gradient on slabs": max(s_hh, s_dec, s_enc, s_p) == 1 and not td_grp and not lm_grp}
+    raise KeyError(name)
+
+
+def _ragged_captions(B, V_, seed):
+    """B captions of 5 .. 14 tokens, sorted by length (descending): (captions [B, L] int64, lengths)"""
+    rs = np.random.RandomState(seed)
+    lengths = sorted(rs.randint(5, 15, size=B).tolist(), reverse=True)
+    caps = torch.zeros(B, max(lengths) + 1, dtype=torch.int64)
+    for b, n in enumerate(lengths):
+        caps[b, 0] = 1
+        caps[b, 1:n] = torch.from_numpy(rs.randint(4, V_, size=n - 1))
+        caps[b, n] = 2
+    return caps, lengths
+
+
+def _butd_xe_case(dims, B, seed, via="loss", options=None):
+    """Teacher-forced XE forward (evaluation mode, ragged caption lengths: the batch shrinks with t) + backward at the widths `dims`
+    against the fp32 / float64 oracle: packed logits 2e-4 / 1e-4 (as the 49-region full-width test), loss 1e-4, every gradient under
+    check_grads_against_float64.  via: "loss" = xe_backward with label smoothing 0.1; "callback" = the same with a gradient callback set
+    (phases as separate calls, stages 0, 1, 2 in order); "dlogits" = xe_backward_dlogits for a random upstream gradient G, the oracle's
+    loss being sum(logits * G)."""
+    from oracle import butd as ob
+    from simpleimagecaptionzoo_amd.butd import ButdHandle
+    from simpleimagecaptionzoo_amd.synth import random_butd_params
+    R_, D_, H_, E_, A_, V_ = dims
+    params = random_butd_params(R_, D_, H_, E_, A_, V_, "cuda", seed=seed)
+    params["predict.weight_g"].mul_(6.0)
+    h = ButdHandle(R_, D_, H_, E_, A_, V_, B, 20)
+    h.bind(params)
+    for name, value in (options or {}).items():
+        h.set_option(name, value)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(2000 + seed)
+    feats = torch.relu(torch.randn(B, R_, D_, generator=g))
+    caps, lengths = _ragged_captions(B, V_, seed)
+    order = ob.packed_order(lengths)
+    tgt = torch.tensor([int(caps[b, t + 1]) for b, t in order])
+    G = torch.randn(len(order), V_, generator=g) / len(order)
+    stages = []
+    if via == "callback":
+        h.set_grad_callback(stages.append)
+    logits = h.xe_forward(feats.cuda(), caps.cuda(), lengths, None, train=False, want_logits=True)
+    grads = h.new_grads()
+    if via == "dlogits":
+        h.xe_backward_dlogits(G.cuda(), grads)
+        loss = None
+    else:
+        loss = h.xe_backward(grads, smoothing=0.1).item()
+    torch.cuda.synchronize()
+    if via == "callback":
+        assert stages == [0, 1, 2], stages
+        h.set_grad_callback(None)
+    gsets, trace64, p64 = {}, None, None
+    for name, dt in (("f32", torch.float32), ("f64", torch.float64)):
+        torch.set_default_dtype(dt)
+        try:
+            p = {k: v.detach().cpu().to(dt).requires_grad_(True) for k, v in params.items()}
+            trace = {}
+            w_logits = ob.forward_xe(feats.to(dt), caps, lengths, p, trace=trace)
+            w_loss = (w_logits * G.to(dt)).sum() if via == "dlogits" else ob.label_smoothing_loss(w_logits, tgt, 0.1)
+            w_loss.backward()
+            gsets[name] = {k: v.grad.numpy() for k, v in p.items()}
+            if name == "f32":
+                np.testing.assert_allclose(logits.cpu().numpy(), w_logits.detach().numpy(), atol=2e-4, rtol=1e-4)
+                if loss is not None:
+                    assert abs(loss - float(w_loss.item())) < 1e-4, (loss, float(w_loss.item()))
+            else:
+                trace64, p64 = trace, {k: v.detach() for k, v in p.items()}
+        finally:
+            torch.set_default_dtype(torch.float32)
+    kink = attention_kink_units(feats.double(), p64, trace64["h1"], None, active_rows=[sum(l > t for l in lengths) for t in range(max(lengths))])
+    rep = check_grads_against_float64(grads, gsets["f32"], gsets["f64"], {"atten.enc_att": kink, "atten.dec_att": kink})
+    h.close()
+    return rep, kink
+
+
+def _device_scst_runs(dims, B, T, seed, schedule):
+    """Device only: one handle, one SCST step (rollouts with Philox dropout / draws from `seed`, REINFORCE backward with a fixed random
+    reward) once per entry of `schedule` = [{handle option: value}, ...], options applied in front of the run and kept for the next.
+    Returns per run (greedy ids, sampled ids, log-probs, {name: gradient}) as CPU tensors."""
+    from simpleimagecaptionzoo_amd.butd import ButdHandle, make_rng
+    R_, D_, H_, E_, A_, V_ = dims
+    params = _full_params(seed=seed, dims=dims)
+    h = ButdHandle(R_, D_, H_, E_, A_, V_, max(B, 8), T)
+    h.bind(params)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(3000 + seed)
+    feats = torch.relu(torch.randn(B, R_, D_, generator=g)).cuda()
+    rw = torch.randn(B, 1, generator=g).repeat(1, T).cuda()
+    runs = []
+    for opts in schedule:
+        for name, value in opts.items():
+            if name == "graphs":
+                h.enable_graphs(bool(value))
+            else:
+                h.set_option(name, value)
+        greedy, seq, lp = h.rollouts(feats, T, make_rng(seed))
+        grads = h.new_grads()
+        for v in grads.values():
+            v.fill_(float("nan"))                   # every element is written by the backward, none accumulated
+        h.sample_backward(rw, grads)
+        torch.cuda.synchronize()
+        runs.append((greedy.cpu().clone(), seq.cpu().clone(), lp.cpu().clone(), {k: v.cpu().clone() for k, v in grads.items()}))
+    h.close()
+    return runs

@@ -432,6 +432,47 @@ def test_routing_of_the_many_row_gemms_at_the_baseline_shapes():
     assert f(5, 1, 1, 1, 1) == -1
 
 
+def _midwidth_names():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _fullwidth import MIDWIDTH
+    return sorted(MIDWIDTH)
+
+
+@pytest.mark.parametrize("name", _midwidth_names())
+def test_midwidth_configurations_reach_the_routes_they_are_there_for(name):
+    """tests/_fullwidth.py: MIDWIDTH (the widths of tests/test_gpu_butd_midwidth.py) -- every purpose a width is listed for, stated through
+    the library's host-only routing entries (icz_gemm_route_for, icz_gemm_tn_split_pick, icz_gemm_tn_grouped_fits).  A retuned threshold
+    that takes a width off its route turns this red and names the width."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _fullwidth import midwidth_routes
+    claims = midwidth_routes(name)
+    assert len(claims) >= 3
+    lost = [c for c, ok in claims.items() if not ok]
+    assert not lost, (name, lost)
+
+
+def test_routing_entries_at_the_baseline_shapes_and_the_split_pick():
+    """icz_gemm_route_for / icz_gemm_tn_split_pick at the benchmark width (36 x 2048, H = E = A = 1024, V = 10102 -> 10112, 64 x 20): the
+    decoder-step gates on the 512-deep resident form (128 rows: its 128-row form, 16 rows: the fp32 NT kernel), dec_att on the fp32 NT
+    kernel (N < 2048), the LSTM weight-gradient groups on large tiles, the two attention weight gradients on 5 and 3 slabs and nothing
+    else on slabs (4H x H is exactly 256 tiles; Vp x H is 632), K below 512 / ragged operands never."""
+    from simpleimagecaptionzoo_amd.butd import gemm_route_for as route, gemm_tn_grouped_fits as grouped, gemm_tn_split_pick as split
+    assert route("nt", 64, 4096, [1024, 1024, 1024]) == route("nt", 64, 4096, [2048, 1024, 1024]) == "resident_512deep"
+    assert route("nt", 128, 4096, [1024, 1024, 1024]) == "resident_128row" and route("nt", 16, 4096, [1024, 1024, 1024]) == "nt_fp32_mt1"
+    assert route("nt", 64, 1024, [1024]) == "nt_fp32_mt4" and route("nt", 24, 1024, [1024]) == "nt_fp32_mt2"
+    assert route("tn", 4096, 4096, [1280], 1) == "large_tile" and route("tn", 4096, 1024, [1280], 1) == "x3_128tile"
+    assert route("tn", 1024, 1024, [1280], 1) == "tn_fp32_64" and route("nn", 1280, 1024, [4096], 4) == "large_tile"
+    assert route("nn", 64, 3072, [4096], 1) == "nn_fp32" and route("nt", 64, 4096, [1024], 5) is None      # 16 stages in 5 splits: an empty split
+    assert grouped(4096, 1280, [1024, 1024, 1024]) and grouped(4096, 1280, [2048, 1024, 1024]) and not grouped(4096, 1280, [1024, 640])
+    assert split(1024, 1024, 1280) == 5 and split(1024, 2048, 2304) == 3
+    assert split(4096, 1024, 1280) == 1 and split(10112, 1024, 1280) == 1                   # >= 256 tiles: the plain route
+    assert split(1024, 1024, 512) == 2 and split(1024, 1024, 496) == 1 and split(1024, 1024, 520) == 1      # K >= 512, K % 16
+    assert split(1024, 126, 1280) == 1 and split(124, 1024, 1280) == 1 and split(1022, 1024, 1280) == 1
+    assert split(1792, 2048, 1280) == 2 and split(1920, 1920, 1280) == 1                    # 224 tiles: two splits still fit 448 workgroups; 225: not
+
+
 def test_bench_parses_what_rccl_says_about_its_rings(tmp_path):
     """bench.py --gpus N quotes rank 0's RCCL choices (NCCL_DEBUG=INFO into NCCL_DEBUG_FILE): channel count, algorithm / protocol per
     all-reduce size, environment overrides.  The wording below is NCCL 2.2x's; unknown lines are ignored, a missing file is an error

@@ -124,3 +124,96 @@ def test_predict_slab_path_matches_the_unsplit_gemm(tmp_path):
         if same.all():
             np.testing.assert_allclose(a[fam + "_dbias"], b[fam + "_dbias"], atol=1e-6, err_msg=fam)
         assert (sa > 0).any() and np.isfinite(a[fam + "_lp"]).all()
+
+
+# ---- gemm_tn_split (csrc/gemm_big_x3.hip) on its own: split-K slabs + their ordered sum, what Butd::wgrad does for a weight gradient with
+# fewer than 256 tiles of 128 x 128.  Bound: 3e-6 of max|C| against the float64 product (K <= 4096), as for every GEMM of this file.
+SPLIT_SHAPES = [(1024, 1024, 1280), (1024, 2048, 2304),      # the two users at full width: d dec_att (5 slabs), d enc_att (3 slabs)
+                (512, 2048, 1296),                           # K % 128 == 16: 11 chunks in 4 splits, the last one 128 + 16 deep
+                (1020, 1012, 1280),                          # M, N ragged against the 128 x 128 tile (multiples of 4)
+                (1024, 1024, 512),                           # the smallest K taken: 2 splits of two chunks
+                (1792, 2048, 1280),                          # 224 tiles, the most that are split (225 and more: 448 / tiles < 2)
+                (2560, 640, 1280), (3008, 512, 1280)]        # W_hh of an LSTM at H = 640, predict at V = 3000, H = 512 (tests/_fullwidth.py: MIDWIDTH)
+
+
+def _split_operands(M, N, K, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    return torch.randn(K, M, device="cuda", generator=g), torch.randn(K, N, device="cuda", generator=g)
+
+
+@pytest.mark.parametrize("M,N,K", SPLIT_SHAPES)
+def test_tn_split_against_float64_with_guards(M, N, K):
+    from simpleimagecaptionzoo_amd.butd import gemm_tn_split, gemm_tn_split_pick
+    ns = gemm_tn_split_pick(M, N, K)
+    assert ns > 1, (M, N, K, ns)
+    dY, X = _split_operands(M, N, K, 3 * M + N + K)
+    buf = torch.full((M + 8, N), 7.0, device="cuda")                 # four guard rows in front of the output, four behind it
+    ws = torch.full((ns * M * N + 4096,), 7.0, device="cuda")        # ... and 4096 guard floats behind the slabs
+    out = gemm_tn_split(dY, X, buf[4:4 + M], ws[:ns * M * N])
+    ref = dY.double().t() @ X.double()
+    err = ((out.double() - ref).abs().max() / ref.abs().max()).item()
+    print("tn_split %d x %d x %d: %d slabs, err %.3g" % (M, N, K, ns, err))
+    assert err < 3e-6, (M, N, K, ns, err)
+    assert torch.all(buf[:4] == 7.0) and torch.all(buf[4 + M:] == 7.0) and torch.all(ws[ns * M * N:] == 7.0)
+
+
+def test_tn_split_refuses_what_the_pick_does_not_take():
+    """K = 496 (just below 512), a workspace one float short, a strided output: an error, nothing launched."""
+    from simpleimagecaptionzoo_amd._lib import IczError
+    from simpleimagecaptionzoo_amd.butd import gemm_tn_split, gemm_tn_split_pick
+    assert gemm_tn_split_pick(1024, 1024, 496) == 1 and gemm_tn_split_pick(1024, 1024, 512) == 2
+    dY, X = _split_operands(1024, 1024, 512, 1)
+    out = torch.full((1024, 1024), 7.0, device="cuda")
+    with pytest.raises(IczError):
+        gemm_tn_split(dY[:496], X[:496], out)
+    with pytest.raises(IczError):
+        gemm_tn_split(dY, X, out, torch.empty(2 * 1024 * 1024 - 1, device="cuda"))
+    wide = torch.full((1024, 1032), 7.0, device="cuda")
+    with pytest.raises(IczError):
+        gemm_tn_split(dY, X, wide[:, :1024])
+    torch.cuda.synchronize()
+    assert torch.all(out == 7.0) and torch.all(wide == 7.0)
+
+
+def test_tn_split_row_limit_and_nan_containment():
+    """rows_live = 700 of K = 1280 (rounded up to 704: the middle of the sixth 128-deep chunk, inside the third of five splits): rows
+    behind it hold 1e18 and are not read -- the result is the product over 704 rows, and a NaN behind the limit changes no bit.  A NaN
+    in dY[k0, m] in front of it makes row m of the result non-finite and no other."""
+    from simpleimagecaptionzoo_amd.butd import gemm_tn_split, gemm_tn_split_pick
+    M, N, K = 1024, 1024, 1280
+    assert gemm_tn_split_pick(M, N, K) == 5
+    dY, X = _split_operands(M, N, K, 11)
+    dY[704:] = 1e18
+    X[704:] = 1e18
+    live = torch.tensor([700], device="cuda", dtype=torch.int32)
+    out = gemm_tn_split(dY, X, rows_live=live)
+    ref = dY[:704].double().t() @ X[:704].double()
+    err = ((out.double() - ref).abs().max() / ref.abs().max()).item()
+    print("tn_split rows_live 700: err %.3g" % err)
+    assert err < 3e-6, err
+    X[900, 17] = float("nan")
+    dY[1279, 5] = float("nan")
+    assert torch.equal(gemm_tn_split(dY, X, rows_live=live), out)
+    dY[300, 77] = float("nan")
+    bad = ~torch.isfinite(gemm_tn_split(dY, X, rows_live=live))
+    assert bad[77].all() and not bad[:77].any() and not bad[78:].any()
+
+
+def test_tn_split_on_two_streams_with_two_workspaces_equals_one_after_the_other():
+    """The two attention weight gradients of a full-width backward at the same time, each on its own stream with its own slabs: the bits
+    of the two products computed one after the other (fixed split, slabs summed in slab order, no atomics)."""
+    from simpleimagecaptionzoo_amd.butd import gemm_tn_split, gemm_tn_split_pick
+    shapes = [(1024, 1024, 1280), (1024, 2048, 2304)]
+    ops = [_split_operands(M, N, K, 23 + i) for i, (M, N, K) in enumerate(shapes)]
+    wss = [torch.empty(gemm_tn_split_pick(M, N, K) * M * N, device="cuda") for (M, N, K) in shapes]
+    serial = [gemm_tn_split(dY, X, None, ws).clone() for (dY, X), ws in zip(ops, wss)]
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    outs = [torch.empty_like(o) for o in serial]
+    for _ in range(3):
+        for (dY, X), ws, o, s in zip(ops, wss, outs, streams):
+            with torch.cuda.stream(s):
+                gemm_tn_split(dY, X, o, ws)
+    torch.cuda.synchronize()
+    for o, want in zip(outs, serial):
+        assert torch.equal(o, want)
