@@ -417,6 +417,50 @@ int icz_ensemble_logprob(int32_t M, const float* const* logits, const float* con
                          const float* weights, int32_t rows, int32_t V, float* lp_out, int32_t ldo, int64_t* argmax_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Sampling decode (beyond the reference; self-critical.pytorch's sample_method / temperature / top-k / top-p): n = 1..8 captions
+ * per image drawn in EVALUATION mode (dropout off, nothing kept for a backward pass), decoder row = img * n + j.  The per-image
+ * work runs once per image.  At every step, for every unfinished row with finished logits x [V]:
+ *   1. y = x / temperature (temperature > 0, finite), evaluated in float64.
+ *   2. top-k (top_k = 0: off; else 1..V): the top_k largest y survive; ties at the cut go to the LOWEST token index, so exactly
+ *      top_k tokens survive.
+ *   3. nucleus (top_p = 1: off; else 0 < top_p < 1): q = softmax(y over the survivors); tokens ordered by q descending, ties to
+ *      the lowest index; a token survives while the mass of the tokens before it is < top_p (the largest always survives).
+ *   4. the draw is the sampler contract of icz_butd_sample over the survivors' masses exp(y - max y) (a filtered token carries
+ *      mass 0): the smallest token index v, in vocabulary order, with cumsum(mass)[v] > u * sum(mass), sums in float64.
+ *   5. logp_out[row, t] = log_softmax(x)[token] -- the model's own log-probability (temperature 1, unfiltered), the quantity
+ *      the beam scores are; score_out[row] = their fp32 sum in step order.
+ *   6. a drawn <end> (2) is recorded with its log-probability and finishes the row: behind it ids are 0 and log-probs 0.  Once
+ *      every row has finished, the kernels of the remaining steps return at entry (the early-out of the rollouts).
+ * The order of steps 2 and 3 is the order of x: x -> x / temperature is monotone.  The nucleus cut is found on masses held as
+ * 2^-40 fixed-point integers (integer sums are the same in any order); the draw's float64 sums run in one fixed order: one seed
+ * gives the same bits run to run.
+ * Uniforms: `uniforms` [max_len, n_img n] in [0, 1) (tests), or NULL = Philox keyed by (seed, step, row) under a stream tag of
+ * its own (no other stream changes).  ids_out [n_img n, max_len] int64, logp_out [n_img n, max_len], score_out [n_img n].
+ * An AoA handle decodes on the region counts of its last icz_aoa_set_regions.
+ * Argument errors return ICZ_ERR_INVALID before any device work, in this order: null options, n outside 1..8, temperature <= 0 or
+ * not finite, top_k < 0 or > V, top_p outside (0, 1], n_img n above the row capacity, null arguments, null handle.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    float temperature;   /* > 0, finite; 1 = the model's distribution */
+    int32_t top_k;       /* 0 = off, else 1..V */
+    float top_p;         /* (0, 1]; 1 = off */
+} icz_sample_opts;
+/* the argument rules above on the host alone (no handle, no device): V and max_rows are the handle's */
+int icz_sample_decode_check(const icz_sample_opts* opts, int32_t n_img, int32_t n, int32_t V, int32_t max_rows);
+int icz_butd_sample_decode(icz_butd_t* h, const float* feats, int32_t n_img, int32_t n, int32_t max_len, const icz_sample_opts* opts,
+                           uint64_t seed, const float* uniforms, int64_t* ids_out, float* logp_out, float* score_out, void* stream);
+int icz_aoa_sample_decode(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t n, int32_t max_len, const icz_sample_opts* opts,
+                          uint64_t seed, const float* uniforms, int64_t* ids_out, float* logp_out, float* score_out, void* stream);
+int icz_nic_sample_decode(icz_nic_t* h, const float* features, int32_t n_img, int32_t n, int32_t max_len, const icz_sample_opts* opts,
+                          uint64_t seed, const float* uniforms, int64_t* ids_out, float* logp_out, float* score_out, void* stream);
+/* The filter-and-draw kernel on its own (tests): logits are finished rows [rows][ld] (nsplit 1) or nsplit split-K slabs
+ * [nsplit][rows][ld] summed in slab order + bias.  uniforms [rows]; tok_out [rows] int64, logp_out [rows]; keep_out [rows][V]
+ * (may be NULL) receives 1 for every token that survived the filters. */
+int icz_sample_filter_draw(const float* logits, const float* bias, int32_t nsplit, int32_t ld, int32_t rows, int32_t V,
+                           const icz_sample_opts* opts, const float* uniforms, int64_t* tok_out, float* logp_out, uint8_t* keep_out,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser step: clip_gradient (Utils.py:241-250, value clamp) + torch.optim.Adam(betas=(0.9,0.999),
  * eps=1e-8, weight_decay=0) (Utils.py:219-220) fused, one call per parameter tensor.
  * ---------------------------------------------------------------------------------------------------------- */

@@ -103,6 +103,10 @@ class BeamDiversity(C.Structure):  # icz_beam_diversity
     _fields_ = [("groups", C.c_int32), ("diversity", C.c_float)]
 
 
+class SampleOpts(C.Structure):     # icz_sample_opts
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
+
+
 _lib = None
 
 
@@ -184,6 +188,11 @@ def lib():
                                                        vp, vp]),
         "icz_ensemble_logprob": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32, vp, i32,
                                            vp, vp]),
+        "icz_sample_decode_check": (C.c_int, [C.POINTER(SampleOpts), i32, i32, i32, i32]),
+        "icz_butd_sample_decode": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
+        "icz_aoa_sample_decode": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
+        "icz_nic_sample_decode": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
+        "icz_sample_filter_draw": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(SampleOpts), vp, vp, vp, vp, vp]),
         "icz_aoa_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),
         "icz_aoa_scst_rollouts": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp, vp]),
         "icz_aoa_sample_backward": (C.c_int, [vp, vp, C.POINTER(AoaParams), vp, vp, f32, vp]),

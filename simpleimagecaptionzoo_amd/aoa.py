@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import beam as _beam
+from . import sampling as _sampling
 from .beam import nbest_lists
 from .scheduled import ScheduledSamplingState, handle_set_scheduled_sampling
 from ._lib import AOA_DECODER_KEYS, AOA_PARAM_KEYS, AoaDims, AoaParams, AoaRng, check, lib, ptr, stream_ptr
@@ -62,6 +63,7 @@ def counts_from_masks(bu_masks):
 class AoaHandle:
     def __init__(self, R, D, Hd, E, V, NH, max_rows, max_len=20, device="cuda:0"):
         self.R, self.D, self.Hd, self.E, self.V, self.NH = R, D, Hd, E, V, NH
+        self.max_rows = max_rows
         self.device = torch.device(device)
         self._h = C.c_void_p()
         self._params = None
@@ -191,6 +193,17 @@ class AoaHandle:
         opts = _beam.make_opts(n_best, length_penalty, block_ngram)        # ValueError before the features are looked at
         div = _beam.make_diversity(groups, diversity, beam_size)
         return _beam.search(lib(), "aoa", self._h, self._feats(feats), beam_size, max_steps, opts, div)
+
+    def sample_decode(self, feats, n=1, max_len=20, temperature=1.0, top_k=0, top_p=1.0, rng=None):
+        """Beyond the reference (include/icz.h: icz_aoa_sample_decode): n = 1..8 captions per image drawn in evaluation mode from
+        softmax(logits / temperature) restricted to the top_k largest tokens (0 = off) and then to the nucleus of mass top_p
+        (1 = off).  rng: None / an integer Philox seed, or explicit uniforms (max_len, B n) fp32 on the device.  Returns (ids int64
+        (B n, max_len) with the drawn <end> and 0 behind it, the model's own log-prob of every token (B n, max_len), their sum
+        (B n,)), row img * n + j.  Bad options raise ValueError before the features are looked at."""
+        opts = _sampling.make_sample_opts(temperature, top_k, top_p, n)
+        if top_k > self.V:
+            raise ValueError("top_k %d above the vocabulary size %d" % (top_k, self.V))
+        return _sampling.decode("aoa", self._h, self._feats(feats), int(n), int(max_len), opts, rng, self.max_rows)
 
     def sample(self, feats, max_len=20, rng=None):
         feats = self._feats(feats)
@@ -392,6 +405,11 @@ class AoADetection_Captioner(nn.Module, ScheduledSamplingState):
     def sampler_rl(self, visual_inputs, max_len=20, rng=None):
         """AoA_Model.py:716-734."""
         return self._handle().sample(self._feats(visual_inputs), max_len, rng or self._next_rng())
+
+    def sample_decode(self, visual_inputs, n=1, max_len=20, temperature=1.0, top_k=0, top_p=1.0, rng=None):
+        """n sampled captions per image in evaluation mode with temperature / top-k / nucleus filtering (an extension; the handle's
+        sample_decode) -> (ids (B n, max_len), log-probs (B n, max_len), scores (B n,)), row img * n + j."""
+        return self._handle().sample_decode(self._feats(visual_inputs), n, max_len, temperature, top_k, top_p, rng)
 
     def beam_search_sampler(self, visual_inputs, beam_size=5):
         """AoA_Model.py:736-753."""

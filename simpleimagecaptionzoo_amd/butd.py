@@ -5,6 +5,7 @@ import torch
 
 from . import _lib
 from . import beam as _beam
+from . import sampling as _sampling
 from ._lib import BUTD_PARAM_FIELDS, BUTD_PARAM_KEYS, ButdDims, ButdParams, Rng, check, lib, ptr, stream_ptr
 
 
@@ -245,6 +246,17 @@ class ButdHandle:
         opts = _beam.make_opts(n_best, length_penalty, block_ngram)        # ValueError before the features are looked at
         div = _beam.make_diversity(groups, diversity, beam_size)
         return _beam.search(lib(), "butd", self._h, self._check_feats(feats), beam_size, max_steps, opts, div)
+
+    def sample_decode(self, feats, n=1, max_len=20, temperature=1.0, top_k=0, top_p=1.0, rng=None):
+        """Beyond the reference (include/icz.h: icz_butd_sample_decode): n = 1..8 captions per image drawn in evaluation mode from
+        softmax(logits / temperature) restricted to the top_k largest tokens (0 = off) and then to the nucleus of mass top_p
+        (1 = off).  rng: None / an integer Philox seed, or explicit uniforms (max_len, B n) fp32 on the device.  Returns (ids int64
+        (B n, max_len) with the drawn <end> and 0 behind it, the model's own log-prob of every token (B n, max_len), their sum
+        (B n,)), row img * n + j.  Bad options raise ValueError before the features are looked at."""
+        opts = _sampling.make_sample_opts(temperature, top_k, top_p, n)
+        if top_k > self.V:
+            raise ValueError("top_k %d above the vocabulary size %d" % (top_k, self.V))
+        return _sampling.decode("butd", self._h, self._check_feats(feats), int(n), int(max_len), opts, rng, self.max_rows)
 
     def step(self, feats, it, h1, c1, h2, c2):
         """One decoder step from an explicit state (BUTD_Model.py:172-182); state tensors are updated in place.

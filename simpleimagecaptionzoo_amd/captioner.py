@@ -186,6 +186,11 @@ class BUTDDetection_Captioner(nn.Module, ScheduledSamplingState):
             return _SampleFunction.apply(self, feats, max_len, rng, *params)
         return self._handle().sample(feats, max_len, rng)
 
+    def sample_decode(self, visual_inputs, n=1, max_len=20, temperature=1.0, top_k=0, top_p=1.0, rng=None):
+        """n sampled captions per image in evaluation mode with temperature / top-k / nucleus filtering (an extension; the handle's
+        sample_decode) -> (ids (B n, max_len), log-probs (B n, max_len), scores (B n,)), row img * n + j."""
+        return self._handle().sample_decode(visual_inputs["bu_feats"], n, max_len, temperature, top_k, top_p, rng)
+
     def beam_search_sampler(self, visual_inputs, beam_size=5):
         """Beam search (BUTD_Model.py:505-517).  A batch of one image returns the reference's (1, L) float tensor;
         larger batches (an extension) return a list of (1, L_i) tensors."""

@@ -379,6 +379,7 @@ int Aoa::prologue(const float* feats, int n_img, int k, const int32_t*, hipStrea
 int Aoa::step(int rows, const int64_t* it_, const int32_t* img_of_row, int, int cur, bool slabs, LogitsView* out, hipStream_t st) {
     AoaStepIO s = scratch_io(*this, rows, img_of_row, cur);
     s.it = it_;
+    s.emb_ready = seam_emb_ready; s.live = seam_live;
     int pns = 1;
     if (slabs) s.pred_nsplit = &pns;
     ICZ_TRY(step(s, st));

@@ -143,6 +143,8 @@ struct Aoa : CaptionHead, DecodeMember {
     int row_capacity() const override { return dims.max_rows; }
     bool refreshed() const override { return fresh; }
     bool compact_step() const override { return true; }
+    EmbSlot emb_slot() const override { return {P.embed_weight, emb, dims.E, 1}; }
+    DeviceBuffers& buffers() override { return mem; }
     int prologue(const float* feats, int n_img, int k, const int32_t* img_of_row, hipStream_t st) override;
     int step(int rows, const int64_t* it, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
              hipStream_t st) override;

@@ -38,6 +38,7 @@ int Butd::step(int rows, const int64_t* it_, const int32_t* img_of_row, int rows
     StepIO s = {};
     s.rows = rows; s.feats = seam_feats; s.img_of_row = img_of_row; s.it = it_;
     s.rows_per_img = rows_per_img;
+    s.emb_ready = seam_emb_ready; s.live = seam_live;
     s.h1_in = h1[cur]; s.c1_in = c1[cur]; s.h2_in = h2[cur]; s.c2_in = c2[cur];
     s.h1_out = h1[cur ^ 1]; s.c1_out = c1[cur ^ 1]; s.h2_out = h2[cur ^ 1]; s.c2_out = c2[cur ^ 1];
     int pns = 1;

@@ -277,7 +277,21 @@ struct DecodeMember {
     virtual int step(int rows, const int64_t* it, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
                      hipStream_t st) = 0;
     virtual void gather(const int32_t* src_row, int rows, int fan, hipStream_t st) = 0;
+    // ---- the sampling decode (sample_decode.hip) ----
+    // where step() reads its input embedding: emb[row, :E] = table[it[row]] (relu: behind a ReLU), no dropout in evaluation mode
+    struct EmbSlot { const float* table; float* emb; int E; int relu; };
+    virtual EmbSlot emb_slot() const = 0;
+    virtual DeviceBuffers& buffers() = 0;       // the handle's allocations: the driver's buffers live and die with them
+    // Set around a step() by a driver whose select kernel has written emb_slot() for the rows' tokens itself (the step skips its
+    // embedding kernel) and keeps the count of unfinished rows (step_dead, icz_common.h); every other caller leaves them alone.
+    bool seam_emb_ready = false;
+    const int* seam_live = nullptr;
+    struct SampleBuf { int cap_rows = 0, cap_T = 0; int64_t* it = nullptr; uint8_t* fin = nullptr; int* n_unf = nullptr; int32_t* img_of_row = nullptr; } sb;
 };
+// The sampling decode on a member: prologue once per image, the rows expanded through img_of_row, then max_len steps of the
+// member's step + sample_decode_kernel (include/icz.h: icz_*_sample_decode; `who` names the entry in its errors).
+int sample_decode(DecodeMember* m, const char* who, const float* feats, int n_img, int n, int max_len, const icz_sample_opts* opts,
+                  uint64_t seed, const float* uniforms, int64_t* ids_out, float* logp_out, float* score_out, hipStream_t st);
 enum { ICZ_MEMBER_BUTD = 0, ICZ_MEMBER_AOA = 1, ICZ_MEMBER_NIC = 2 };
 DecodeMember* butd_member(void* handle);        // the seams of an icz_butd_t / icz_aoa_t / icz_nic_t
 DecodeMember* aoa_member(void* handle);

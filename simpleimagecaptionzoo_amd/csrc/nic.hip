@@ -61,6 +61,8 @@ struct Nic : CaptionHead, DecodeMember {
     int row_capacity() const override { return dims.max_rows; }
     bool refreshed() const override { return fresh; }
     bool compact_step() const override { return false; }
+    EmbSlot emb_slot() const override { return {P.embed_weight, emb, dims.E, 0}; }
+    DeviceBuffers& buffers() override { return mem; }
     int prologue(const float* feats, int n_img, int k, const int32_t* img_of_row, hipStream_t st) override;
     int step(int rows, const int64_t* it, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
              hipStream_t st) override;
@@ -408,7 +410,8 @@ int Nic::prologue(const float* feats, int n_img, int k, const int32_t* img_of_ro
 int Nic::step(int rows, const int64_t* it_, const int32_t*, int, int cur, bool slabs, LogitsView* out, hipStream_t st) {
     DropCfg off = {0, nullptr, nullptr, 0, 0};
     int pns = 1;
-    ICZ_TRY(token_step(rows, it_, false, h[cur], c[cur], h[cur ^ 1], c[cur ^ 1], emb, nullptr, hdrop, logits, off, st, slabs ? &pns : nullptr));
+    ICZ_TRY(token_step(rows, it_, seam_emb_ready, h[cur], c[cur], h[cur ^ 1], c[cur ^ 1], emb, nullptr, hdrop, logits, off, st, slabs ? &pns : nullptr,
+                       seam_live));
     if (out) *out = pns > 1 ? LogitsView{ws, P.predict_b, (size_t)rows * Vp, Vp, pns} : LogitsView{logits, nullptr, 0, Vp, 1};
     return ICZ_OK;
 }

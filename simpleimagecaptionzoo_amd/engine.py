@@ -18,6 +18,7 @@ import torch
 
 from ._lib import BUTD_PARAM_KEYS, check, lib, ptr, stream_ptr
 from .beam import make_diversity, parse_length_penalty
+from .sampling import make_sample_opts
 from .captioner import BUTDDetection_Captioner
 from .ciderd import CiderDReward
 from . import dist as icz_dist
@@ -565,6 +566,53 @@ class BUTDDetection_Eng(Engine):
                 elif word != "<sta>":
                     sampled_caption.append(word)
             result.append({"image_id": image_id, "caption": " ".join(sampled_caption)})
+        return result
+
+    def sample_captions_json_generation(self, dataloader, samples_per_image=1, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                                        tqdm_visible=True):
+        """Sampled captions for evaluation (an extension; include/icz.h: icz_*_sample_decode): `samples_per_image` (1..8) captions
+        per image drawn in evaluation mode from softmax(logits / temperature) restricted to the top_k largest tokens (0 = off) and
+        the nucleus of mass top_p (1 = off), 20 steps as the greedy evaluation.  Returns {"image_id", "caption", "score"} entries,
+        samples_per_image per image in loader order; score = the model's summed log-probability of the caption's tokens.  Batch i
+        of the loader draws from Philox seed `seed * 2**20 + i`: one seed gives the same captions run to run.  Sharded over the
+        ranks and gathered as eval_captions_json_generation does.  Bad arguments raise ValueError before any device work."""
+        make_sample_opts(temperature, top_k, top_p, samples_per_image)
+        if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+            raise ValueError("seed %r is not a non-negative integer" % (seed,))
+        if top_k > len(self.caption_vocab):
+            raise ValueError("top_k %d above the vocabulary size %d" % (top_k, len(self.caption_vocab)))
+        with _on_stream(self):
+            return self._sample_captions_json_generation(dataloader, int(samples_per_image), temperature, top_k, top_p, seed, tqdm_visible)
+
+    def _sample_captions_json_generation(self, dataloader, n, temperature, top_k, top_p, seed, tqdm_visible):
+        self.model.eval()
+        dp = icz_dist.is_distributed()
+        rank, world = icz_dist.rank(), icz_dist.world_size()
+        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Sampling Process", tqdm_visible)
+        ids_out, rows_out, keys_out = [], [], []
+        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
+            visual_inputs = self.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
+            h = self._hot_handle()
+            ids, _, score = h.sample_decode(self._features(visual_inputs), n, 20, temperature, top_k, top_p, (seed << 20) + batch_i)
+            ids, bits = ids.cpu().numpy(), score.cpu().numpy().view(np.uint32)
+            for r in range(ids.shape[0]):
+                ids_out.append(int(image_ids[r // n]))
+                rows_out.append(np.concatenate([ids[r], [int(bits[r])]]))      # the score travels as its bit pattern (non-negative)
+                keys_out.append((batch_i << 20) + r)                           # loader order: batch index, then image, then sample
+        if dp:
+            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, self.device)
+        result = []
+        ix2word = self.caption_vocab.ix2word
+        for image_id, row in zip(ids_out, rows_out):
+            words = []
+            for word_id in row[:-1]:
+                word = ix2word[int(word_id)]
+                if word == "<end>" or int(word_id) == 0:
+                    break
+                elif word != "<sta>":
+                    words.append(word)
+            score = float(np.array([int(row[-1])], dtype=np.uint32).view(np.float32)[0])
+            result.append({"image_id": image_id, "caption": " ".join(words), "score": score})
         return result
 
 

@@ -6,6 +6,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import beam as _beam
+from . import sampling as _sampling
 from .beam import nbest_lists
 from ._lib import NIC_PARAM_FIELDS, NIC_PARAM_KEYS, NicDims, NicParams, check, lib, ptr, stream_ptr
 from .butd import make_rng
@@ -15,6 +16,7 @@ from .scheduled import ScheduledSamplingState, handle_set_scheduled_sampling
 class NicHandle:
     def __init__(self, E, H, V, max_rows, max_len=20, device="cuda:0"):
         self.E, self.H, self.V = E, H, V
+        self.max_rows = max_rows
         self.device = torch.device(device)
         self._h = C.c_void_p()
         self._params = None
@@ -86,6 +88,17 @@ class NicHandle:
         ids = torch.empty(feats.shape[0], max_len, dtype=torch.int64, device=feats.device)
         check(lib().icz_nic_greedy(self._h, ptr(feats), feats.shape[0], max_len, ptr(ids), stream_ptr()))
         return ids
+
+    def sample_decode(self, feats, n=1, max_len=20, temperature=1.0, top_k=0, top_p=1.0, rng=None):
+        """Beyond the reference (include/icz.h: icz_nic_sample_decode): n = 1..8 captions per image drawn in evaluation mode from
+        softmax(logits / temperature) restricted to the top_k largest tokens (0 = off) and then to the nucleus of mass top_p
+        (1 = off).  rng: None / an integer Philox seed, or explicit uniforms (max_len, B n) fp32 on the device.  Returns (ids int64
+        (B n, max_len) with the drawn <end> and 0 behind it, the model's own log-prob of every token (B n, max_len), their sum
+        (B n,)), row img * n + j.  Bad options raise ValueError before the features are looked at."""
+        opts = _sampling.make_sample_opts(temperature, top_k, top_p, n)
+        if top_k > self.V:
+            raise ValueError("top_k %d above the vocabulary size %d" % (top_k, self.V))
+        return _sampling.decode("nic", self._h, self._feats(feats), int(n), int(max_len), opts, rng, self.max_rows)
 
     def sample(self, feats, max_len=20, rng=None):
         feats = self._feats(feats)
@@ -232,6 +245,11 @@ class NICDecoder_Captioner(nn.Module, ScheduledSamplingState):
     def sampler_rl(self, visual_inputs, max_len=20, rng=None):
         """NIC_Model.py:275-287 (fused path: no autograd graph; use the handle's sample_backward)."""
         return self._handle().sample(self._features(visual_inputs).detach(), max_len, rng or self._next_rng())
+
+    def sample_decode(self, visual_inputs, n=1, max_len=20, temperature=1.0, top_k=0, top_p=1.0, rng=None):
+        """n sampled captions per image in evaluation mode with temperature / top-k / nucleus filtering (an extension; the handle's
+        sample_decode) -> (ids (B n, max_len), log-probs (B n, max_len), scores (B n,)), row img * n + j."""
+        return self._handle().sample_decode(self._features(visual_inputs).detach(), n, max_len, temperature, top_k, top_p, rng)
 
     def beam_search_sampler(self, visual_inputs, beam_size=5):
         """NIC_Model.py:289-301."""
