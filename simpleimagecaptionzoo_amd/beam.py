@@ -82,11 +82,11 @@ def search_diverse(entry, handle, feats, beam_size, max_steps, opts, div):
     return seqs, lens, scores
 
 
-def search(lib, model, handle, feats, beam_size, max_steps, opts, div):
-    """icz_<model>_beam_search_opts for one group (today's search), icz_<model>_beam_search_diverse otherwise"""
+def search(entries, handle, feats, beam_size, max_steps, opts, div):
+    """a family's beam_search_opts entry for one group (today's search), its beam_search_diverse entry otherwise"""
     if div.groups == 1:
-        return search_opts(getattr(lib, "icz_%s_beam_search_opts" % model), handle, feats, beam_size, max_steps, opts)
-    return search_diverse(getattr(lib, "icz_%s_beam_search_diverse" % model), handle, feats, beam_size, max_steps, opts, div)
+        return search_opts(entries.beam_search_opts, handle, feats, beam_size, max_steps, opts)
+    return search_diverse(entries.beam_search_diverse, handle, feats, beam_size, max_steps, opts, div)
 
 
 def nbest_lists(seqs, lens, scores):

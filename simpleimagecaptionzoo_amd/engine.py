@@ -332,8 +332,9 @@ class BUTDDetection_Eng(Engine):
         self._pending = []
 
     def _features(self, visual_inputs):
-        """The device tensor the decoder handle consumes (bottom-up features here; NIC: the image embedding)."""
-        return visual_inputs["bu_feats"]
+        """What the decoder handle consumes: the captioner's own hook (bottom-up features, AoA: with the region counts, NIC: the
+        image embedding)."""
+        return self.model._features(visual_inputs)
 
     def _trainable(self):
         """name -> parameter for everything the optimizer updates (AoA: the decoder only, AoA_Model.py:669-674)."""
@@ -636,9 +637,6 @@ class AoADetection_Eng(BUTDDetection_Eng):
                                       embed_dim=s["embed_dim"], device=str(self.device), num_regions=regions,
                                       enc_dim=s.get("enc_dim", 2048), max_batch=max_batch)
 
-    def _features(self, visual_inputs):
-        return self.model._feats(visual_inputs)
-
 
 class NIC_Eng(BUTDDetection_Eng):
     """ModelEngines/NIC_Engine.py (= the base Engine) with the three hot methods on the NIC decoder handle.  The CNN encoder +
@@ -658,9 +656,6 @@ class NIC_Eng(BUTDDetection_Eng):
         if isinstance(supp_info_datas, dict) and torch.is_tensor(supp_info_datas.get("img_feats")):
             return {"img_feats": supp_info_datas["img_feats"].to(self.device, torch.float32)}
         return {"img_tensors": img_tensors.to(self.device)}            # Engine.py:32-41
-
-    def _features(self, visual_inputs):
-        return self.model._features(visual_inputs).detach().contiguous()
 
 
 class BUTDSpatial_Eng(BUTDDetection_Eng):

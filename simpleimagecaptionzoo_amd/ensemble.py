@@ -9,21 +9,10 @@ import torch
 
 from . import beam as _beam
 from ._lib import check, lib, ptr, stream_ptr
-from .aoa import AoADetection_Captioner, AoaHandle
 from .beam import nbest_lists
-from .butd import ButdHandle
-from .captioner import BUTDDetection_Captioner
-from .nic import NICDecoder_Captioner, NicHandle
+from .handle import CaptionerBase, DecoderHandle
 
 MAX_MEMBERS = 4
-KINDS = ((ButdHandle, 0), (AoaHandle, 1), (NicHandle, 2))        # icz_ensemble_create's member kinds
-
-
-def _kind(h):
-    for cls, k in KINDS:
-        if isinstance(h, cls):
-            return k
-    raise ValueError("ensemble member %r: expected a ButdHandle, AoaHandle or NicHandle" % (h,))
 
 
 def check_weights(weights, m):
@@ -53,7 +42,9 @@ class EnsembleHandle:
     def __init__(self, handles, weights=None):
         handles = list(handles)
         check_members(len(handles))
-        kinds = [_kind(h) for h in handles]
+        for h in handles:
+            if not isinstance(h, DecoderHandle):
+                raise ValueError("ensemble member %r: expected a ButdHandle, AoaHandle or NicHandle" % (h,))
         if len({id(h) for h in handles}) != len(handles):
             raise ValueError("an ensemble member appears twice: each member needs a handle of its own")
         if len({h.V for h in handles}) != 1:
@@ -61,7 +52,7 @@ class EnsembleHandle:
         w = check_weights(weights, len(handles))
         self.handles, self.V, self.device = handles, handles[0].V, handles[0].device
         self._h = C.c_void_p()
-        arr_k = (C.c_int32 * len(handles))(*kinds)
+        arr_k = (C.c_int32 * len(handles))(*[h.kind for h in handles])       # icz_ensemble_create's member kinds
         arr_m = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
         arr_w = (C.c_float * len(handles))(*w) if w is not None else None
         with torch.cuda.device(self.device):
@@ -84,9 +75,7 @@ class EnsembleHandle:
         feats_list = list(feats_list)
         if len(feats_list) != len(self.handles):
             raise ValueError("%d feature tensors for %d members" % (len(feats_list), len(self.handles)))
-        out = []
-        for h, f in zip(self.handles, feats_list):
-            out.append(h._check_feats(f) if isinstance(h, ButdHandle) else h._feats(f))
+        out = [h._feats(f) for h, f in zip(self.handles, feats_list)]
         sizes = {int(f.shape[0]) for f in out}
         if len(sizes) != 1:
             raise ValueError("the members' features hold different image counts %s" % sorted(sizes))
@@ -117,13 +106,9 @@ class EnsembleHandle:
 
 def member_features(captioner, visual_inputs):
     """The features `captioner`'s own sampler hands its handle."""
-    if isinstance(captioner, AoADetection_Captioner):
-        return captioner._feats(visual_inputs)
-    if isinstance(captioner, NICDecoder_Captioner):
-        return captioner._features(visual_inputs).detach()
-    if isinstance(captioner, BUTDDetection_Captioner):
-        return visual_inputs["bu_feats"]
-    raise ValueError("ensemble member %r: expected a BUTD, AoA or NIC captioner" % (captioner,))
+    if not isinstance(captioner, CaptionerBase):
+        raise ValueError("ensemble member %r: expected a BUTD, AoA or NIC captioner" % (captioner,))
+    return captioner._features(visual_inputs)
 
 
 class CaptionEnsemble:
@@ -134,7 +119,7 @@ class CaptionEnsemble:
         self.captioners = list(captioners)
         check_members(len(self.captioners))
         for c in self.captioners:
-            if not isinstance(c, (BUTDDetection_Captioner, AoADetection_Captioner, NICDecoder_Captioner)):
+            if not isinstance(c, CaptionerBase):
                 raise ValueError("ensemble member %r: expected a BUTD, AoA or NIC captioner" % (c,))
         self.weights = check_weights(weights, len(self.captioners))
         self._ens = None

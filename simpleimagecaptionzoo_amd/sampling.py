@@ -43,8 +43,9 @@ def rng_args(rng):
     raise ValueError("rng must be None, an integer seed or a tensor of uniforms")
 
 
-def decode(model, handle, feats, n, max_len, opts, rng, max_rows):
-    """-> (ids int64 (rows, max_len), logp (rows, max_len), score (rows,)), rows = images x n, row img * n + j"""
+def decode(entry, handle, feats, n, max_len, opts, rng, max_rows):
+    """Calls icz_*_sample_decode `entry` -> (ids int64 (rows, max_len), logp (rows, max_len), score (rows,)), rows = images x n,
+    row img * n + j"""
     seed, uniforms = rng_args(rng)
     n_img, rows = feats.shape[0], feats.shape[0] * n
     if rows > max_rows:
@@ -54,7 +55,6 @@ def decode(model, handle, feats, n, max_len, opts, rng, max_rows):
     ids = torch.zeros(rows, max_len, dtype=torch.int64, device=feats.device)
     logp = torch.zeros(rows, max_len, dtype=torch.float32, device=feats.device)
     score = torch.zeros(rows, dtype=torch.float32, device=feats.device)
-    entry = getattr(lib(), "icz_%s_sample_decode" % model)
     check(entry(handle, ptr(feats), n_img, n, max_len, C.byref(opts), seed, ptr(uniforms), ptr(ids), ptr(logp), ptr(score), stream_ptr()))
     return ids, logp, score
 

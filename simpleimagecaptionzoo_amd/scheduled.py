@@ -5,16 +5,6 @@ it on the Captioner while each DecoderRNN reads its own attribute, so the refere
 The drop-in default is therefore the same: the Captioner accepts the attribute and ignores it.  `scheduled_sampling =
 True` on the Captioner makes the attribute live: the device path then does what DecoderRNN.forward does when its own
 `ss_prob` is set (pinned by goldens generated from the reference decoders with exactly that attribute set)."""
-import torch
-
-from ._lib import check, lib, ptr
-
-
-def handle_set_scheduled_sampling(handle, fn_name, ss_prob, gate=None, draw=None):
-    """icz_<family>_set_scheduled_sampling on a handle wrapper; gate / draw: optional explicit uniforms [T, B]."""
-    keep = [None if u is None else torch.as_tensor(u, dtype=torch.float32).to(handle.device).contiguous() for u in (gate, draw)]
-    check(getattr(lib(), fn_name)(handle._h, float(ss_prob), ptr(keep[0]), ptr(keep[1])))
-    handle._ss_live = keep           # the library reads them during the next xe_forward
 
 
 def scheduled_sampling_prob(epoch, ss_opts):
