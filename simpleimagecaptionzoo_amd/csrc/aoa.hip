@@ -335,40 +335,18 @@ int Aoa::greedy(const float* feats, int B, int T, int64_t* ids_out, hipStream_t 
         if (track && t > 0) s.live = gn + (t - 1);
         ICZ_TRY(step(s, st));
         if (t == 0) track = gn && pns > 1;       // the one-launch select keeps the count (the two-kernel argmax of <= 32 rows does not)
-        if (pns > 1)         // 33 - 64 rows: slabs of the vocabulary projection -> token + next embedding in one launch
-            hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(1024), 0, st, (const float*)ws, dims.V, Vp, pns, (size_t)B * Vp,
-                               (const float*)P.predict_b, P.embed_weight, dims.E, emb, it, ids_out, T, t, 1,
-                               track ? gunf : (uint8_t*)nullptr, track ? gn : (int*)nullptr);
-        else {
-            hipLaunchKernelGGL(argmax_part_kernel, dim3(B, ARGMAX_PARTS), dim3(256), 0, st, logits, dims.V, Vp, ARGMAX_PARTS, amax_val, amax_idx);
-            hipLaunchKernelGGL(embed_argmax_kernel, dim3(cdiv(dims.E, 1024), B), dim3(256), 0, st, amax_val, amax_idx, ARGMAX_PARTS,
-                               P.embed_weight, dims.E, emb, it, ids_out, T, t, 1);
-        }
+        launch_greedy_select(logits_view(ws, P.predict_b, logits, B, Vp, pns), emb_slot(), B, dims.V, amax_val, amax_idx, it, ids_out, T, t,
+                             track ? gunf : nullptr, track ? gn : nullptr, st);
         cur ^= 1;
     }
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
 
-// AoA_Decoder.beam_search_sample (AoA_Model.py:403-502), batched over images; state (h, m, ctx) re-gathered by source beam
-int Aoa::beam_search(const float* feats, int n_img, int kb, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                      const icz_beam_opts& o, float* scores_out, const icz_beam_diversity& d) {
-    ICZ_REQUIRE(feats && seqs_out && lens_out, "aoa beam: null argument");
-    ICZ_TRY(BeamBuf::check("aoa", n_img, kb, max_steps, dims.max_rows));
-    ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
-    const int rows = n_img * kb, L = max_steps + 1;
-    ICZ_TRY(bm.ensure(mem, dims.max_rows, L));
-    ICZ_TRY(prologue(feats, n_img, kb, nullptr, st));
-    ICZ_TRY(bm.begin(n_img, kb, L, it, st));
-    auto step = [&](int, bool compact) {        // compact: one decoder row per image (butd_beam.hip)
-        return compact ? this->step(n_img, it, nullptr, 1, 0, false, nullptr, st) : this->step(rows, it, bm.img_of_row, kb, 0, false, nullptr, st);
-    };
-    auto gather = [&](bool compact) { this->gather(bm.src_row, rows, compact ? kb : 1, st); };
-    return bm.search(n_img, kb, max_steps, true, logits, dims.V, Vp, it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
-}
-
 // ---- decoder seams (DecodeMember) ------------------------------------------------------------------------------------------------
-// the refiner pass (evaluation mode, bank 0; the region counts of icz_aoa_set_regions) and k zeroed state rows per image
+// AoA_Decoder.beam_search_sample (AoA_Model.py:403-502), batched over images, is the shared driver (beam.hip) on these seams; the
+// state (h, m, ctx) is re-gathered by source beam.
+// prologue: the refiner pass (evaluation mode, bank 0; the region counts of icz_aoa_set_regions) and k zeroed state rows per image
 int Aoa::prologue(const float* feats, int n_img, int k, const int32_t*, hipStream_t st) {
     ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
     use_bank(0);
@@ -383,7 +361,7 @@ int Aoa::step(int rows, const int64_t* it_, const int32_t* img_of_row, int, int 
     int pns = 1;
     if (slabs) s.pred_nsplit = &pns;
     ICZ_TRY(step(s, st));
-    if (out) *out = pns > 1 ? LogitsView{ws, P.predict_b, (size_t)rows * Vp, Vp, pns} : LogitsView{logits, nullptr, 0, Vp, 1};
+    if (out) *out = logits_view(ws, P.predict_b, logits, rows, Vp, pns);
     return ICZ_OK;
 }
 
@@ -471,26 +449,5 @@ int icz_aoa_set_regions(icz_aoa_t* h, int32_t regions, const int32_t* counts_dev
 int icz_aoa_greedy(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, int64_t* ids_out, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Aoa*>(h)->greedy(feats, B, max_len, ids_out, (hipStream_t)stream);
-}
-int icz_aoa_beam_search(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, float* seqs_out,
-                        int32_t* lens_out, void* stream) {
-    ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Aoa*>(h)->beam_search(feats, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream);
-}
-int icz_aoa_beam_search_opts(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
-                             float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
-    ICZ_TRY(BeamBuf::check_opts("icz_aoa_beam_search_opts", beam, opts));      // the arguments first: no handle needed to report them
-    ICZ_REQUIRE(feats && seqs_out && lens_out && scores_out, "icz_aoa_beam_search_opts: null argument");
-    ICZ_REQUIRE(h, "icz_aoa_beam_search_opts: null handle");
-    return reinterpret_cast<Aoa*>(h)->beam_search(feats, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out);
-}
-
-int icz_aoa_beam_search_diverse(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
-                                const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
-    ICZ_TRY(BeamBuf::check_opts("icz_aoa_beam_search_diverse", beam, opts));      // the arguments first: no handle needed to report them
-    ICZ_TRY(BeamBuf::check_diversity("icz_aoa_beam_search_diverse", beam, div));
-    ICZ_REQUIRE(feats && seqs_out && lens_out && scores_out, "icz_aoa_beam_search_diverse: null argument");
-    ICZ_REQUIRE(h, "icz_aoa_beam_search_diverse: null handle");
-    return reinterpret_cast<Aoa*>(h)->beam_search(feats, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out, *div);
 }
 }  // extern "C"

@@ -37,7 +37,7 @@ struct AoaStepIO {
 };
 
 struct Aoa : CaptionHead, DecodeMember {
-    static constexpr int STEP_WGS = 256, TARGET_WGS = 512, ARGMAX_PARTS = 8, NL = 6;
+    static constexpr int STEP_WGS = 256, TARGET_WGS = 512, NL = 6;
     icz_aoa_dims dims;
     icz_aoa_params P;
     bool bound = false, fresh = false;
@@ -91,7 +91,6 @@ struct Aoa : CaptionHead, DecodeMember {
     int64_t* it = nullptr;
     float* amax_val = nullptr; int* amax_idx = nullptr;
     icz_grad_ready_cb grad_cb = nullptr; void* grad_cb_user = nullptr;      // DP overlap hook (icz_aoa_set_grad_callback)
-    BeamBuf bm;
     // training buffers (aoa_train.hip), slot stride = max_rows: th/tm/tctx slot 0 = zeros, slot t+1 = after step t
     int tcap_B = 0, tcap_T = 0;          // capacity of the training buffers (grown on demand by ensure_train)
     int64_t* tok = nullptr;
@@ -135,9 +134,6 @@ struct Aoa : CaptionHead, DecodeMember {
     int greedy(const float* feats, int B, int T, int64_t* ids_out, hipStream_t st, const float* proj = nullptr, bool scst = false, bool refined_ready = false);
     int rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int64_t* seq_out, float* logp_out, hipStream_t st);
     int rollouts(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* ids_out, int64_t* seq_out, float* logp_out, hipStream_t st);
-    int beam_search(const float* feats, int n_img, int kb, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                    const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr,
-                    const icz_beam_diversity& d = BeamBuf::no_diversity);
     // decoder seams (DecodeMember, decoder_core.h): the refiner pass, one decoder step, the beam-state gather
     int vocab() const override { return dims.V; }
     int row_capacity() const override { return dims.max_rows; }

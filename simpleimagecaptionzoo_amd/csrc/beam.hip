@@ -1,0 +1,230 @@
+// Batched beam search (DecoderRNN.beam_search_sample, Models/BUTD_Model.py:236-318) for many images at once, one driver for the
+// BUTD, AoA and NIC decoders and their ensembles (DecodeMember, decoder_core.h).
+// The reference decodes one image per call with a Python list comprehension over tensor elements every step
+// (k host syncs per step, :282-283).  Here every image owns k consecutive decoder rows; after the shared decoder
+// step a per-image workgroup does log-softmax + running score + top-k over (active beams x V), retires beams that
+// emitted <end> (k shrinks exactly as in the reference; no length normalisation unless icz_beam_opts asks for it), and emits the row permutation
+// that re-gathers the LSTM state.  No host synchronisation inside a step.
+#include <cmath>
+
+#include "beam_kernels.h"
+#include "decoder_core.h"
+
+namespace icz {
+
+int BeamBuf::check(const char* who, int n_img, int k, int max_steps, int max_rows) {
+    ICZ_REQUIRE(k >= 1 && k <= BEAM_MAX_K, "%s beam: beam size %d out of range 1..%d", who, k, BEAM_MAX_K);
+    ICZ_REQUIRE(n_img > 0 && (long)n_img * k <= max_rows, "%s beam: %d images x %d beams exceed row capacity %d", who, n_img, k, max_rows);
+    ICZ_REQUIRE(max_steps >= 1 && max_steps <= 256, "%s beam: max_steps out of range", who);
+    return ICZ_OK;
+}
+
+const icz_beam_opts BeamBuf::defaults = {1, 0, 0, 0.f};
+
+int BeamBuf::check_opts(const char* who, int k, const icz_beam_opts* o) {
+    ICZ_REQUIRE(o, "%s: null options", who);
+    ICZ_REQUIRE(o->n_best >= 1 && o->n_best <= k, "%s: n_best %d outside 1..beam (%d)", who, o->n_best, k);
+    ICZ_REQUIRE(o->block_ngram == 0 || (o->block_ngram >= 2 && o->block_ngram <= 4), "%s: block_ngram %d not 0, 2, 3 or 4", who,
+                o->block_ngram);
+    ICZ_REQUIRE(o->lp_kind >= 0 && o->lp_kind <= 2, "%s: lp_kind %d unknown (0 none, 1 avg, 2 wu)", who, o->lp_kind);
+    ICZ_REQUIRE(std::isfinite(o->lp_alpha) && o->lp_alpha >= 0.f, "%s: lp_alpha %g negative or not finite", who, (double)o->lp_alpha);
+    return ICZ_OK;
+}
+
+const icz_beam_diversity BeamBuf::no_diversity = {1, 0.f};
+
+int BeamBuf::check_diversity(const char* who, int k, const icz_beam_diversity* d) {
+    ICZ_REQUIRE(d, "%s: null diversity", who);
+    ICZ_REQUIRE(d->groups >= 1 && d->groups <= k && k % d->groups == 0, "%s: groups %d outside 1..beam (%d) or not dividing it", who,
+                d->groups, k);
+    ICZ_REQUIRE(std::isfinite(d->diversity) && d->diversity >= 0.f, "%s: diversity %g negative or not finite", who, (double)d->diversity);
+    return ICZ_OK;
+}
+
+// sized for the handle's row capacity and at least 51 columns; a longer search re-allocates (the old buffers stay in the
+// handle's persistent list), the pinned read-back word is allocated once
+int BeamBuf::ensure(DeviceBuffers& m, int max_rows, int L) {
+    if (cap_rows >= max_rows && cap_L >= L) return ICZ_OK;
+    const size_t R_ = max_rows, L_ = L > 51 ? L : 51;
+    ICZ_TRY(m.alloc((void**)&n_act, sizeof(int) * R_));
+    ICZ_TRY(m.alloc((void**)&run, sizeof(float) * R_));
+    ICZ_TRY(m.alloc((void**)&seqs[0], sizeof(int32_t) * R_ * L_));
+    ICZ_TRY(m.alloc((void**)&seqs[1], sizeof(int32_t) * R_ * L_));
+    ICZ_TRY(m.alloc((void**)&src_row, sizeof(int32_t) * R_));
+    ICZ_TRY(m.alloc((void**)&img_of_row, sizeof(int32_t) * R_));
+    ICZ_TRY(m.alloc((void**)&best_score, sizeof(float) * R_));
+    ICZ_TRY(m.alloc((void**)&best_len, sizeof(int) * R_));
+    ICZ_TRY(m.alloc((void**)&has_complete, sizeof(int) * R_));
+    ICZ_TRY(m.alloc((void**)&best_seq, sizeof(int32_t) * R_ * L_));
+    ICZ_TRY(m.alloc((void**)&n_live, sizeof(int) * 260));
+    ICZ_TRY(m.alloc((void**)&cand_val, sizeof(float) * R_ * BEAM_MAX_K));
+    ICZ_TRY(m.alloc((void**)&cand_idx, sizeof(int) * R_ * BEAM_MAX_K));
+    ICZ_TRY(m.alloc((void**)&hyp_seq, sizeof(int32_t) * R_ * L_));
+    ICZ_TRY(m.alloc((void**)&hyp_score, sizeof(float) * R_));
+    ICZ_TRY(m.alloc((void**)&hyp_len, sizeof(int) * R_));
+    ICZ_TRY(m.alloc((void**)&hyp_cnt, sizeof(int) * R_));
+    ICZ_TRY(m.alloc((void**)&it, sizeof(int64_t) * R_));
+    if (!n_live_host) ICZ_CHECK_HIP(hipHostMalloc((void**)&n_live_host, sizeof(int) * 4, 0));
+    ICZ_TRY(m.synced());
+    cap_rows = (int)R_;
+    cap_L = (int)L_;
+    return ICZ_OK;
+}
+
+int BeamBuf::begin(int n_img, int k, int L, hipStream_t st) {
+    const int rows = n_img * k;
+    ICZ_CHECK_HIP(hipMemsetAsync(n_live, 0, sizeof(int) * 260, st));
+    ICZ_CHECK_HIP(hipMemsetAsync(run, 0, sizeof(float) * rows, st));
+    hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, n_img, k, L, n_act, seqs[0], img_of_row, it, has_complete, best_score,
+                       hyp_cnt);
+    return ICZ_OK;
+}
+
+int BeamBuf::search(DecodeMember* const* m, int M, const BeamCombine* ens, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out,
+                    const icz_beam_opts& o, const icz_beam_diversity& d, float* scores_out, hipStream_t st) {
+    const int rows = n_img * k, L = max_steps + 1, G = d.groups, V = m[0]->vocab();
+    const bool listed = o.n_best > 1 || o.lp_kind != 0 || G > 1;
+    bool compact_first = true;
+    for (int i = 0; i < M; ++i) compact_first = compact_first && m[i]->compact_step();
+    if (G > 1) hipLaunchKernelGGL(beam_init_groups_kernel, dim3(cdiv(n_img * G, 256)), dim3(256), 0, st, n_img * G, k / G, n_act);
+    LogitsView lv[ENS_MAX_M];
+    int sb = 0, steps_done = 0;
+    for (int s = 1; s <= max_steps; ++s) {
+        // Step 1 (compact): the decoder runs ONE row per image (row img of the buffers); the top-k kernel reads image img's logits from
+        // row img and the state gather fans row img out to the image's k rows.
+        const bool compact = compact_first && s == 1 && k > 1;
+        const int r = compact ? n_img : rows;
+        // a single handle's consumer reads finished rows; the ensemble's combine kernel sums split-K slabs itself
+        for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->step(r, it, compact ? nullptr : img_of_row, compact ? 1 : k, 0, ens != nullptr, &lv[i], st));
+        if (ens) ens->run(lv, r);
+        BeamArgs a = {ens ? ens->lp : lv[0].p, V, ens ? ens->ld : lv[0].ld, k, s, L, n_act, run, seqs[sb], seqs[sb ^ 1], src_row, it, best_score,
+                      best_len, best_seq, has_complete, n_live + s, listed ? hyp_seq : nullptr, hyp_score, hyp_len, listed ? hyp_cnt : nullptr};
+        launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)n_act, (const float*)run, cand_val, cand_idx,
+                            compact ? 1 : 0, seqs[sb], L, o.block_ngram, G);
+        if (G > 1)
+            hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(n_img), dim3(64), 0, st, a, G, d.diversity, (const float*)cand_val,
+                               (const int*)cand_idx);
+        else
+            hipLaunchKernelGGL(beam_merge_kernel, dim3(n_img), dim3(64), 0, st, a, (const float*)cand_val, (const int*)cand_idx);
+        for (int i = 0; i < M; ++i) m[i]->gather(src_row, rows, compact ? k : 1, st);
+        sb ^= 1;
+        steps_done = s;
+        if (s >= 6 && (s % 3) == 0 && s < max_steps) {
+            ICZ_CHECK_HIP(hipMemcpyAsync(n_live_host, n_live + s, sizeof(int), hipMemcpyDeviceToHost, st));
+            ICZ_CHECK_HIP(hipStreamSynchronize(st));
+            if (n_live_host[0] == 0) break;
+        }
+    }
+    if (G > 1)
+        hipLaunchKernelGGL(beam_finalize_nbest_kernel<true>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, o.n_best, o.lp_kind, o.lp_alpha,
+                           (const int*)n_act, (const float*)run, (const int32_t*)seqs[sb], (const int*)hyp_cnt, (const float*)hyp_score,
+                           (const int*)hyp_len, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out, G);
+    else if (listed)
+        hipLaunchKernelGGL(beam_finalize_nbest_kernel<false>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, o.n_best, o.lp_kind, o.lp_alpha,
+                           (const int*)n_act, (const float*)run, (const int32_t*)seqs[sb], (const int*)hyp_cnt, (const float*)hyp_score,
+                           (const int*)hyp_len, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out, 1);
+    else
+        hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_act, run, seqs[sb], has_complete,
+                           best_len, best_seq, seqs_out, lens_out, (const float*)best_score, scores_out);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int check_members(const char* who, DecodeMember* const* m, int M, const float* const* feats, int rows) {
+    ICZ_REQUIRE(feats, "%s: null features", who);
+    for (int i = 0; i < M; ++i) {
+        ICZ_REQUIRE(feats[i], "%s: null features of member %d", who, i);
+        ICZ_REQUIRE(m[i]->refreshed(), "%s: member %d is not refreshed (call its icz_*_refresh_weights after binding/updating parameters)", who, i);
+        ICZ_REQUIRE(rows <= m[i]->row_capacity(), "%s: %d rows exceed member %d's row capacity %d", who, rows, i, m[i]->row_capacity());
+    }
+    return ICZ_OK;
+}
+
+// Every check runs before the first allocation or launch: a refused call queues nothing.  begin() precedes the prologues: NIC's (and so
+// an ensemble's) reads img_of_row, which begin() writes; begin() writes only the beam buffers and a prologue only its handle's
+// per-image tensors and state, so for BUTD and AoA the order of the two is free.
+int beam_search(const char* who, DecodeMember* const* m, int M, const BeamCombine* ens, const float* const* feats, int n_img, int k,
+                int max_steps, const icz_beam_opts& o, const icz_beam_diversity& d, float* seqs_out, int32_t* lens_out, float* scores_out,
+                hipStream_t st) {
+    if (!ens) ICZ_REQUIRE(feats[0] && seqs_out && lens_out, "%s beam: null argument", who);
+    ICZ_TRY(BeamBuf::check(who, n_img, k, max_steps, ens ? 1 << 30 : m[0]->row_capacity()));
+    if (ens) ICZ_TRY(check_members(ens->who, m, M, feats, n_img * k));
+    else ICZ_REQUIRE(m[0]->refreshed(), "%s: call icz_%s_refresh_weights after binding/updating parameters", who, who);
+    BeamBuf& bm = ens ? *ens->bm : m[0]->bm;
+    const int L = max_steps + 1;
+    ICZ_TRY(bm.ensure(ens ? *ens->mem : m[0]->buffers(), ens ? ens->cap : m[0]->row_capacity(), L));
+    ICZ_TRY(bm.begin(n_img, k, L, st));
+    for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->prologue(feats[i], n_img, k, bm.img_of_row, st));
+    return bm.search(m, M, ens, n_img, k, max_steps, seqs_out, lens_out, o, d, scores_out, st);
+}
+
+// The three beam entries of a family on its member m (null for a null handle): plain (the default options, scores_out may be
+// null), _opts and _diverse.  `entry` names the C entry in the argument errors, `who` the family in the search's own.
+enum BeamEntry { BEAM_PLAIN, BEAM_OPTS, BEAM_DIVERSE };
+static int beam_entry(BeamEntry kind, const char* entry, const char* who, DecodeMember* m, const float* feats, int n_img, int beam, int max_steps,
+                      const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out,
+                      void* stream) {
+    if (kind == BEAM_PLAIN) {
+        ICZ_REQUIRE(m, "null handle");
+    } else {
+        ICZ_TRY(BeamBuf::check_opts(entry, beam, opts));      // the arguments first: no handle needed to report them
+        if (kind == BEAM_DIVERSE) ICZ_TRY(BeamBuf::check_diversity(entry, beam, div));
+        ICZ_REQUIRE(feats && seqs_out && lens_out && scores_out, "%s: null argument", entry);
+        ICZ_REQUIRE(m, "%s: null handle", entry);
+    }
+    return beam_search(who, &m, 1, nullptr, &feats, n_img, beam, max_steps, *opts, *div, seqs_out, lens_out, scores_out, (hipStream_t)stream);
+}
+
+}  // namespace icz
+
+// ================================================================================================
+using namespace icz;
+extern "C" {
+
+int icz_butd_beam_search(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, float* seqs_out, int32_t* lens_out,
+                         void* stream) {
+    return beam_entry(BEAM_PLAIN, "icz_butd_beam_search", "butd", butd_member(h), feats, n_img, beam, max_steps, &BeamBuf::defaults, &BeamBuf::no_diversity,
+                      seqs_out, lens_out, nullptr, stream);
+}
+int icz_butd_beam_search_opts(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                              float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
+    return beam_entry(BEAM_OPTS, "icz_butd_beam_search_opts", "butd", butd_member(h), feats, n_img, beam, max_steps, opts, &BeamBuf::no_diversity, seqs_out,
+                      lens_out, scores_out, stream);
+}
+int icz_butd_beam_search_diverse(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                                 const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
+    return beam_entry(BEAM_DIVERSE, "icz_butd_beam_search_diverse", "butd", butd_member(h), feats, n_img, beam, max_steps, opts, div, seqs_out, lens_out,
+                      scores_out, stream);
+}
+int icz_aoa_beam_search(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, float* seqs_out, int32_t* lens_out,
+                        void* stream) {
+    return beam_entry(BEAM_PLAIN, "icz_aoa_beam_search", "aoa", aoa_member(h), feats, n_img, beam, max_steps, &BeamBuf::defaults, &BeamBuf::no_diversity,
+                      seqs_out, lens_out, nullptr, stream);
+}
+int icz_aoa_beam_search_opts(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                             float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
+    return beam_entry(BEAM_OPTS, "icz_aoa_beam_search_opts", "aoa", aoa_member(h), feats, n_img, beam, max_steps, opts, &BeamBuf::no_diversity, seqs_out,
+                      lens_out, scores_out, stream);
+}
+int icz_aoa_beam_search_diverse(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                                const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
+    return beam_entry(BEAM_DIVERSE, "icz_aoa_beam_search_diverse", "aoa", aoa_member(h), feats, n_img, beam, max_steps, opts, div, seqs_out, lens_out,
+                      scores_out, stream);
+}
+int icz_nic_beam_search(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps, float* seqs_out, int32_t* lens_out,
+                        void* stream) {
+    return beam_entry(BEAM_PLAIN, "icz_nic_beam_search", "nic", nic_member(h), features, n_img, beam, max_steps, &BeamBuf::defaults, &BeamBuf::no_diversity,
+                      seqs_out, lens_out, nullptr, stream);
+}
+int icz_nic_beam_search_opts(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                             float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
+    return beam_entry(BEAM_OPTS, "icz_nic_beam_search_opts", "nic", nic_member(h), features, n_img, beam, max_steps, opts, &BeamBuf::no_diversity, seqs_out,
+                      lens_out, scores_out, stream);
+}
+int icz_nic_beam_search_diverse(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                                const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
+    return beam_entry(BEAM_DIVERSE, "icz_nic_beam_search_diverse", "nic", nic_member(h), features, n_img, beam, max_steps, opts, div, seqs_out, lens_out,
+                      scores_out, stream);
+}
+
+}  // extern "C"

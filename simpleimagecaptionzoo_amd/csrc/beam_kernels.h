@@ -1,4 +1,5 @@
-// Per-image beam expand / prune kernels shared by the decoders (BUTD: butd_beam.hip, NIC: nic.hip).
+// Per-image beam expand / prune kernels of the shared beam-search driver (beam.hip); the state re-gather and the row expansion the
+// decoders launch from their seams live in butd_kernels.h.
 #pragma once
 #include "butd_kernels.h"
 
@@ -567,32 +568,6 @@ __global__ __launch_bounds__(64) void beam_merge_groups_kernel(BeamArgs a, int g
         __syncthreads();                                         // the next group overwrites pick_* / new_*
     }
     if (lane == 0 && live > 0) atomicAdd(a.n_live, 1);
-}
-
-// state re-gather: out[row,:] = in[src_row[row],:] for the four state tensors
-__global__ __launch_bounds__(256) void beam_gather_kernel(const int32_t* __restrict__ src_row, int H,
-                                                          const float* __restrict__ a0, const float* __restrict__ a1,
-                                                          const float* __restrict__ a2, const float* __restrict__ a3,
-                                                          float* __restrict__ o0, float* __restrict__ o1,
-                                                          float* __restrict__ o2, float* __restrict__ o3, int src_div) {
-    const int row = blockIdx.y;
-    const int j = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (j >= H) return;
-    // src_div = k after a compact first step (the state of image img sits in row img, src_row says img k + 0), else 1
-    const size_t s = (size_t)(src_row[row] / src_div) * H + j, d = (size_t)row * H + j;
-    *reinterpret_cast<f32x4*>(o0 + d) = *reinterpret_cast<const f32x4*>(a0 + s);
-    *reinterpret_cast<f32x4*>(o1 + d) = *reinterpret_cast<const f32x4*>(a1 + s);
-    *reinterpret_cast<f32x4*>(o2 + d) = *reinterpret_cast<const f32x4*>(a2 + s);
-    *reinterpret_cast<f32x4*>(o3 + d) = *reinterpret_cast<const f32x4*>(a3 + s);
-}
-
-// out[row,:] = in[img_of_row[row],:]   (features.expand(k, ...) of the reference's beam search)
-__global__ __launch_bounds__(256) void beam_expand_rows_kernel(const float* __restrict__ in, const int32_t* __restrict__ img_of_row, int E,
-                                                               float* __restrict__ out) {
-    const int row = blockIdx.y;
-    const int e = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (e >= E) return;
-    *reinterpret_cast<f32x4*>(out + (size_t)row * E + e) = *reinterpret_cast<const f32x4*>(in + (size_t)img_of_row[row] * E + e);
 }
 
 // final selection (:302-313): best finished hypothesis if any, else the best-scoring live beam (scores: its raw score, if non-null)

@@ -290,21 +290,44 @@ int Butd::greedy_chain(const float* feats, int B, int max_len, int64_t* ids_out,
         ICZ_TRY(step(s, st));
         if (t == 0) track = gn && pns > 1;     // the one-launch select below keeps the count (the two-kernel argmax of <= 32 rows does not)
         kprof_mark(KP_GREEDY_SELECT, true, st);
-        if (pns > 1)         // 33 - 64 rows: the slabs of the vocabulary projection -> token + next embedding in one launch
-            hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(1024), 0, st, (const float*)ws, dims.V, Vp, pns, (size_t)B * Vp,
-                               (const float*)P.predict_b, P.embed_weight, dims.E, emb, it, ids_out, max_len, t, 1,
-                               track ? gunf : (uint8_t*)nullptr, track ? gn : (int*)nullptr);
-        else {
-            hipLaunchKernelGGL(argmax_part_kernel, dim3(B, ARGMAX_PARTS), dim3(256), 0, st, logits, dims.V, Vp, ARGMAX_PARTS, amax_val, amax_idx);
-            hipLaunchKernelGGL(embed_argmax_kernel, dim3(cdiv(dims.E, 1024), B), dim3(256), 0, st, amax_val, amax_idx, ARGMAX_PARTS,
-                               P.embed_weight, dims.E, emb, it, ids_out, max_len, t);
-        }
+        launch_greedy_select(logits_view(ws, P.predict_b, logits, B, Vp, pns), emb_slot(), B, dims.V, amax_val, amax_idx, it, ids_out, max_len, t,
+                             track ? gunf : nullptr, track ? gn : nullptr, st);
         kprof_mark(KP_GREEDY_SELECT, false, st);
         cur ^= 1;
     }
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
+
+// ---- decoder seams (DecodeMember) ------------------------------------------------------------------------------------------------
+// the per-image prologue, then k zeroed state rows per image
+int Butd::prologue(const float* feats, int n_img, int k, const int32_t*, hipStream_t st) {
+    ICZ_TRY(prologue(feats, n_img, st));
+    seam_feats = feats;
+    return zero_state(n_img * k, 0, st);
+}
+
+int Butd::step(int rows, const int64_t* it_, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
+               hipStream_t st) {
+    StepIO s = {};
+    s.rows = rows; s.feats = seam_feats; s.img_of_row = img_of_row; s.it = it_;
+    s.rows_per_img = rows_per_img;
+    s.emb_ready = seam_emb_ready; s.live = seam_live;
+    s.h1_in = h1[cur]; s.c1_in = c1[cur]; s.h2_in = h2[cur]; s.c2_in = c2[cur];
+    s.h1_out = h1[cur ^ 1]; s.c1_out = c1[cur ^ 1]; s.h2_out = h2[cur ^ 1]; s.c2_out = c2[cur ^ 1];
+    int pns = 1;
+    if (slabs) s.pred_nsplit = &pns;
+    ICZ_TRY(step(s, st));
+    if (out) *out = logits_view(ws, P.predict_b, logits, rows, pad_vocab(dims.V), pns);
+    return ICZ_OK;
+}
+
+void Butd::gather(const int32_t* src_row, int rows, int fan, hipStream_t st) {
+    hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(dims.H, 1024), rows), dim3(256), 0, st, src_row, dims.H, h1[1], c1[1], h2[1], c2[1],
+                       h1[0], c1[0], h2[0], c2[0], fan);
+}
+
+DecodeMember* butd_member(void* handle) { return static_cast<DecodeMember*>(reinterpret_cast<Butd*>(handle)); }
 
 }  // namespace icz
 

@@ -62,7 +62,6 @@ struct Butd : CaptionHead, DecodeMember {
     static constexpr int TARGET_WGS = 512;   // ~2 workgroups per CU on 256 CUs
     static constexpr int ATT_PARTS = 4;
     static constexpr int STEP_WGS = 256;     // skinny decoder-step GEMMs: split-K for ~1 workgroup per CU
-    static constexpr int ARGMAX_PARTS = 8;
     icz_butd_dims dims;
     icz_butd_params P;
     bool bound = false, fresh = false;
@@ -134,8 +133,7 @@ struct Butd : CaptionHead, DecodeMember {
                                          // grouped route is slower, 16.3 against 15.9 ms at 64 images x 5 and 5.65 against 4.94 ms at 16 x 4
                                          // (fewer, longer workgroups; the features fit the Infinity Cache either way)
 
-    // beam search (butd_beam.hip) on the decoder seams (DecodeMember, decoder_core.h)
-    BeamBuf bm;
+    // the decoder seams (DecodeMember, decoder_core.h): beam search (beam.hip), the sampling decode and the ensemble run on them
     const float* seam_feats = nullptr;   // the features of the last prologue(feats, n_img, k, ...): the steps that follow attend over them
     int vocab() const override { return dims.V; }
     int row_capacity() const override { return dims.max_rows; }
@@ -147,9 +145,6 @@ struct Butd : CaptionHead, DecodeMember {
     int step(int rows, const int64_t* it, const int32_t* img_of_row, int rows_per_img, int cur, bool slabs, LogitsView* out,
              hipStream_t st) override;
     void gather(const int32_t* src_row, int rows, int fan, hipStream_t st) override;
-    int beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                    const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr,
-                    const icz_beam_diversity& d = BeamBuf::no_diversity);
 
     // training paths (butd_train.hip)
     TrainBuf tb;

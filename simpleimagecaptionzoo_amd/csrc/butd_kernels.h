@@ -866,6 +866,33 @@ __global__ void fill_i64_kernel(int64_t* p, int64_t v, int n) {
     if (i < n) p[i] = v;
 }
 
+// ---- beam search: launched by the decoders' seams (DecodeMember::gather / prologue); the search's own kernels: beam_kernels.h ----
+// state re-gather: out[row,:] = in[src_row[row],:] for the four state tensors
+__global__ __launch_bounds__(256) void beam_gather_kernel(const int32_t* __restrict__ src_row, int H,
+                                                          const float* __restrict__ a0, const float* __restrict__ a1,
+                                                          const float* __restrict__ a2, const float* __restrict__ a3,
+                                                          float* __restrict__ o0, float* __restrict__ o1,
+                                                          float* __restrict__ o2, float* __restrict__ o3, int src_div) {
+    const int row = blockIdx.y;
+    const int j = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (j >= H) return;
+    // src_div = k after a compact first step (the state of image img sits in row img, src_row says img k + 0), else 1
+    const size_t s = (size_t)(src_row[row] / src_div) * H + j, d = (size_t)row * H + j;
+    *reinterpret_cast<f32x4*>(o0 + d) = *reinterpret_cast<const f32x4*>(a0 + s);
+    *reinterpret_cast<f32x4*>(o1 + d) = *reinterpret_cast<const f32x4*>(a1 + s);
+    *reinterpret_cast<f32x4*>(o2 + d) = *reinterpret_cast<const f32x4*>(a2 + s);
+    *reinterpret_cast<f32x4*>(o3 + d) = *reinterpret_cast<const f32x4*>(a3 + s);
+}
+
+// out[row,:] = in[img_of_row[row],:]   (features.expand(k, ...) of the reference's beam search)
+__global__ __launch_bounds__(256) void beam_expand_rows_kernel(const float* __restrict__ in, const int32_t* __restrict__ img_of_row, int E,
+                                                               float* __restrict__ out) {
+    const int row = blockIdx.y;
+    const int e = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (e >= E) return;
+    *reinterpret_cast<f32x4*>(out + (size_t)row * E + e) = *reinterpret_cast<const f32x4*>(in + (size_t)img_of_row[row] * E + e);
+}
+
 }  // namespace
 }  // namespace icz
 

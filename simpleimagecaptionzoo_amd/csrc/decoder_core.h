@@ -1,11 +1,12 @@
 // Host-side machinery shared by the BUTD, AoA and NIC decoder handles: device allocations, the hipGraph cache, side
-// streams, the caption loss head (teacher-forced XE input, packed logits, XE / REINFORCE losses) and the beam-search driver.
+// streams, the caption loss head (teacher-forced XE input, packed logits, XE / REINFORCE losses), the decoder seams (DecodeMember)
+// with the drivers that run on them (beam search: beam.hip, sampling: sample_decode.hip) and the greedy select tail.
 // Each rule below ("free => clear graphs", "zero-fill then sync") has this one owner.
 #pragma once
+#include <functional>
 #include <vector>
 #include <stdint.h>
 
-#include "beam_kernels.h"
 #include "butd_kernels.h"
 #include "gemm_f32.h"
 
@@ -182,13 +183,35 @@ struct CaptionHead {
     int upload_pack_index(hipStream_t st);
 };
 
-// Beam-search buffers and the step loop shared by the decoders.
+// Where one decoder step left its logits: ns == 1 finished rows [rows][ld]; ns > 1 the predict GEMM's split-K slabs [ns][rows][ld]
+// (slab z at p + z * slab_stride, no bias yet) + bias[v], summed in slab order as argmax_part_kernel / greedy_select_kernel do.
+struct LogitsView { const float* p; const float* bias; size_t slab_stride; int ld; int ns; };
+// the view of a step whose predict GEMM (gemm_predict) reported `pns` slabs in `ws`, or finished rows in `logits`
+inline LogitsView logits_view(const float* ws, const float* bias, const float* logits, int rows, int Vp, int pns) {
+    return pns > 1 ? LogitsView{ws, bias, (size_t)rows * Vp, Vp, pns} : LogitsView{logits, nullptr, 0, Vp, 1};
+}
+
+struct DecodeMember;
+constexpr int ENS_MAX_M = 4;          // members of one beam search / ensemble
+
+struct BeamBuf;
+// An ensemble's side of a beam search (ensemble.hip): its own beam buffers, allocated from `mem` for `cap` rows, and its route to the
+// rows the search scores: run(lv, rows) combines the members' views of one step into lp [rows, ld].  A single handle has none: the
+// search runs on the member's own bm / buffers() / row_capacity() and reads its finished rows.
+struct BeamCombine {
+    const char* who;                  // the entry, named by the member checks
+    BeamBuf* bm; DeviceBuffers* mem; int cap;
+    const float* lp; int ld;
+    std::function<void(const LogitsView* lv, int rows)> run;
+};
+
+// Beam-search buffers and the step loop shared by the decoders (beam.hip).
 struct BeamBuf {
     int cap_rows = 0, cap_L = 0;
     int* n_act = nullptr; float* run = nullptr; int32_t* seqs[2] = {nullptr, nullptr};
     int32_t *src_row = nullptr, *img_of_row = nullptr, *best_seq = nullptr;
     float* best_score = nullptr; int *best_len = nullptr, *has_complete = nullptr, *n_live = nullptr, *n_live_host = nullptr;
-    float* feat_rows = nullptr;       // NIC: image embedding replicated per beam row
+    int64_t* it = nullptr;            // the token rows of the search: every member steps on them
     float* cand_val = nullptr; int* cand_idx = nullptr;     // [rows, BEAM_MAX_K] per-row candidates of one step
     int32_t* hyp_seq = nullptr; float* hyp_score = nullptr; int *hyp_len = nullptr, *hyp_cnt = nullptr;    // n-best list (BeamArgs)
     BeamBuf() = default;
@@ -201,68 +224,24 @@ struct BeamBuf {
     static const icz_beam_opts defaults;                                       // n_best 1, no blocking, no length penalty
     static int check_diversity(const char* who, int k, const icz_beam_diversity* d);   // the icz_*_beam_search_diverse rules
     static const icz_beam_diversity no_diversity;                             // one group: the plain search
-    int ensure(DeviceBuffers& m, int max_rows, int L, int extra_feat_cols = 0);
-    int begin(int n_img, int k, int L, int64_t* it, hipStream_t st);       // scores, live counts and the <sta> rows of every image
-    // The step loop (DecoderRNN.beam_search_sample, BUTD_Model.py:236-318, batched over images): step(step_no, compact) runs the
-    // decoder on `it` into `logits`; then a row-top-k, the per-image merge and gather(compact) re-gathering the model state by
-    // source row; every few steps one 4-byte read-back asks whether any image still has live beams.  compact_first: step 1 runs
+    int ensure(DeviceBuffers& m, int max_rows, int L);
+    int begin(int n_img, int k, int L, hipStream_t st);       // scores, live counts and the <sta> rows of every image
+    // The step loop (DecoderRNN.beam_search_sample, BUTD_Model.py:236-318, batched over images): every member's step runs the
+    // decoder on `it`; the rows scored are the one member's finished logits or the ensemble's combined rows (BeamCombine); then a
+    // row-top-k, the per-image merge and every member's gather re-gathering the model state by source row; every few steps one
+    // 4-byte read-back asks whether any image still has live beams.  Step 1 is compact when every member's compact_step() holds:
     // one decoder row per image (the k rows of an image are identical and only row 0 is scored, :273-274).
     // Options (icz_beam_opts, checked by check_opts): block_ngram goes to the row-top-k; n_best > 1 or a length penalty keeps the
     // n-best list in the merge and ranks it in beam_finalize_nbest_kernel (seqs_out [n_img, n_best, L], lens_out / scores_out
     // [n_img, n_best]).  At the defaults the launches are today's; scores_out (may be null) receives the raw score of the caption.
     // Diversity (icz_beam_diversity, checked by check_diversity): groups > 1 keeps n_act per (image, group), runs the grouped
     // row-top-k instances and beam_merge_groups_kernel, and always keeps the n-best list; one group launches the plain kernels.
-    template <class Step, class Gather>
-    int search(int n_img, int k, int max_steps, bool compact_first, const float* logits, int V, int ldl, int64_t* it, float* seqs_out,
-               int32_t* lens_out, const icz_beam_opts& o, const icz_beam_diversity& d, float* scores_out, hipStream_t st, Step&& step,
-               Gather&& gather) {
-        const int rows = n_img * k, L = max_steps + 1, G = d.groups;
-        const bool listed = o.n_best > 1 || o.lp_kind != 0 || G > 1;
-        if (G > 1) hipLaunchKernelGGL(beam_init_groups_kernel, dim3(cdiv(n_img * G, 256)), dim3(256), 0, st, n_img * G, k / G, n_act);
-        int sb = 0, steps_done = 0;
-        for (int s = 1; s <= max_steps; ++s) {
-            const bool compact = compact_first && s == 1 && k > 1;
-            ICZ_TRY(step(s, compact));
-            BeamArgs a = {logits, V, ldl, k, s, L, n_act, run, seqs[sb], seqs[sb ^ 1], src_row, it, best_score, best_len, best_seq,
-                          has_complete, n_live + s, listed ? hyp_seq : nullptr, hyp_score, hyp_len, listed ? hyp_cnt : nullptr};
-            launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)n_act, (const float*)run, cand_val, cand_idx,
-                                compact ? 1 : 0, seqs[sb], L, o.block_ngram, G);
-            if (G > 1)
-                hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(n_img), dim3(64), 0, st, a, G, d.diversity, (const float*)cand_val,
-                                   (const int*)cand_idx);
-            else
-                hipLaunchKernelGGL(beam_merge_kernel, dim3(n_img), dim3(64), 0, st, a, (const float*)cand_val, (const int*)cand_idx);
-            gather(compact);
-            sb ^= 1;
-            steps_done = s;
-            if (s >= 6 && (s % 3) == 0 && s < max_steps) {
-                ICZ_CHECK_HIP(hipMemcpyAsync(n_live_host, n_live + s, sizeof(int), hipMemcpyDeviceToHost, st));
-                ICZ_CHECK_HIP(hipStreamSynchronize(st));
-                if (n_live_host[0] == 0) break;
-            }
-        }
-        if (G > 1)
-            hipLaunchKernelGGL(beam_finalize_nbest_kernel<true>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, o.n_best, o.lp_kind, o.lp_alpha,
-                               (const int*)n_act, (const float*)run, (const int32_t*)seqs[sb], (const int*)hyp_cnt, (const float*)hyp_score,
-                               (const int*)hyp_len, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out, G);
-        else if (listed)
-            hipLaunchKernelGGL(beam_finalize_nbest_kernel<false>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, o.n_best, o.lp_kind, o.lp_alpha,
-                               (const int*)n_act, (const float*)run, (const int32_t*)seqs[sb], (const int*)hyp_cnt, (const float*)hyp_score,
-                               (const int*)hyp_len, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out, 1);
-        else
-            hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_act, run, seqs[sb], has_complete,
-                               best_len, best_seq, seqs_out, lens_out, (const float*)best_score, scores_out);
-        ICZ_CHECK_HIP(hipGetLastError());
-        return ICZ_OK;
-    }
+    int search(DecodeMember* const* m, int M, const BeamCombine* ens, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out,
+               const icz_beam_opts& o, const icz_beam_diversity& d, float* scores_out, hipStream_t st);
 };
 
-// Where one decoder step left its logits: ns == 1 finished rows [rows][ld]; ns > 1 the predict GEMM's split-K slabs [ns][rows][ld]
-// (slab z at p + z * slab_stride, no bias yet) + bias[v], summed in slab order as argmax_part_kernel / greedy_select_kernel do.
-struct LogitsView { const float* p; const float* bias; size_t slab_stride; int ld; int ns; };
-
-// The per-image work, one decoder step and the beam-state gather of a decoder, callable from outside its own beam_search: the
-// BUTD, AoA and NIC handles implement it (their beam searches run on it), the model ensemble (ensemble.hip) drives several at once.
+// The per-image work, one decoder step and the beam-state gather of a decoder: the BUTD, AoA and NIC handles implement it, the
+// drivers below run on it -- beam_search on one member (a handle's own search) or on several at once (the model ensemble, ensemble.hip).
 // State: a step reads slot `cur` of the recurrent state and writes slot cur ^ 1; gather() moves slot 1 into slot 0 by source row.
 struct DecodeMember {
     virtual ~DecodeMember() = default;
@@ -287,7 +266,23 @@ struct DecodeMember {
     bool seam_emb_ready = false;
     const int* seam_live = nullptr;
     struct SampleBuf { int cap_rows = 0, cap_T = 0; int64_t* it = nullptr; uint8_t* fin = nullptr; int* n_unf = nullptr; int32_t* img_of_row = nullptr; } sb;
+    BeamBuf bm;                                 // a handle's own beam search (beam_search with no BeamCombine); an ensemble keeps its own
 };
+// an ensemble call of `rows` decoder rows: features, refreshed weights and row capacity of every member (`who` names the entry)
+int check_members(const char* who, DecodeMember* const* m, int M, const float* const* feats, int rows);
+// Beam search over M >= 1 members on the caller's stream (include/icz.h: icz_*_beam_search*): every check, then BeamBuf::ensure,
+// begin, every member's prologue, the step loop and the final selection (BeamBuf::search).  `who` names the family in the errors.
+// ens null: M = 1, a handle's own search, scoring the member's finished logits.
+int beam_search(const char* who, DecodeMember* const* m, int M, const BeamCombine* ens, const float* const* feats, int n_img, int k,
+                int max_steps, const icz_beam_opts& o, const icz_beam_diversity& d, float* seqs_out, int32_t* lens_out, float* scores_out,
+                hipStream_t st);
+// The greedy select tail of a decoder step: the argmax of the step's logits becomes it[row] and ids_out[row, t] (row stride T) and its
+// embedding row goes to the member's EmbSlot for the next step.  Split-K slabs (lv.ns > 1; 33 - 64 rows): one launch of
+// greedy_select_kernel, which also keeps the SCST baseline's count of unfinished rows (gunf / gn, may be null); finished rows: the
+// two-kernel argmax over ARGMAX_PARTS slices of the vocabulary (amax_val / amax_idx [rows, ARGMAX_PARTS]), which does not.
+constexpr int ARGMAX_PARTS = 8;
+void launch_greedy_select(const LogitsView& lv, const DecodeMember::EmbSlot& e, int rows, int V, float* amax_val, int* amax_idx, int64_t* it,
+                          int64_t* ids_out, int T, int t, uint8_t* gunf, int* gn, hipStream_t st);
 // The sampling decode on a member: prologue once per image, the rows expanded through img_of_row, then max_len steps of the
 // member's step + sample_decode_kernel (include/icz.h: icz_*_sample_decode; `who` names the entry in its errors).
 int sample_decode(DecodeMember* m, const char* who, const float* feats, int n_img, int n, int max_len, const icz_sample_opts* opts,

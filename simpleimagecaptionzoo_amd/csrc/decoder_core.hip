@@ -1,6 +1,5 @@
-// The out-of-line half of decoder_core.h (caption loss head, beam buffers, C ABI helpers) and the library's error slot.
+// The out-of-line half of decoder_core.h (caption loss head, greedy select tail, C ABI helpers) and the library's error slot.
 #include <stdarg.h>
-#include <cmath>
 
 #include "decoder_core.h"
 
@@ -161,72 +160,16 @@ int CaptionHead::reinforce(const float* reward, float* logits, int V, int ldl, f
 }
 
 // ------------------------------------------------------------------------------------------------
-int BeamBuf::check(const char* who, int n_img, int k, int max_steps, int max_rows) {
-    ICZ_REQUIRE(k >= 1 && k <= BEAM_MAX_K, "%s beam: beam size %d out of range 1..%d", who, k, BEAM_MAX_K);
-    ICZ_REQUIRE(n_img > 0 && (long)n_img * k <= max_rows, "%s beam: %d images x %d beams exceed row capacity %d", who, n_img, k, max_rows);
-    ICZ_REQUIRE(max_steps >= 1 && max_steps <= 256, "%s beam: max_steps out of range", who);
-    return ICZ_OK;
-}
-
-const icz_beam_opts BeamBuf::defaults = {1, 0, 0, 0.f};
-
-int BeamBuf::check_opts(const char* who, int k, const icz_beam_opts* o) {
-    ICZ_REQUIRE(o, "%s: null options", who);
-    ICZ_REQUIRE(o->n_best >= 1 && o->n_best <= k, "%s: n_best %d outside 1..beam (%d)", who, o->n_best, k);
-    ICZ_REQUIRE(o->block_ngram == 0 || (o->block_ngram >= 2 && o->block_ngram <= 4), "%s: block_ngram %d not 0, 2, 3 or 4", who,
-                o->block_ngram);
-    ICZ_REQUIRE(o->lp_kind >= 0 && o->lp_kind <= 2, "%s: lp_kind %d unknown (0 none, 1 avg, 2 wu)", who, o->lp_kind);
-    ICZ_REQUIRE(std::isfinite(o->lp_alpha) && o->lp_alpha >= 0.f, "%s: lp_alpha %g negative or not finite", who, (double)o->lp_alpha);
-    return ICZ_OK;
-}
-
-const icz_beam_diversity BeamBuf::no_diversity = {1, 0.f};
-
-int BeamBuf::check_diversity(const char* who, int k, const icz_beam_diversity* d) {
-    ICZ_REQUIRE(d, "%s: null diversity", who);
-    ICZ_REQUIRE(d->groups >= 1 && d->groups <= k && k % d->groups == 0, "%s: groups %d outside 1..beam (%d) or not dividing it", who,
-                d->groups, k);
-    ICZ_REQUIRE(std::isfinite(d->diversity) && d->diversity >= 0.f, "%s: diversity %g negative or not finite", who, (double)d->diversity);
-    return ICZ_OK;
-}
-
-// sized for the handle's row capacity and at least 51 columns; a longer search re-allocates (the old buffers stay in the
-// handle's persistent list), the pinned read-back word is allocated once
-int BeamBuf::ensure(DeviceBuffers& m, int max_rows, int L, int extra_feat_cols) {
-    if (cap_rows >= max_rows && cap_L >= L) return ICZ_OK;
-    const size_t R_ = max_rows, L_ = L > 51 ? L : 51;
-    ICZ_TRY(m.alloc((void**)&n_act, sizeof(int) * R_));
-    ICZ_TRY(m.alloc((void**)&run, sizeof(float) * R_));
-    ICZ_TRY(m.alloc((void**)&seqs[0], sizeof(int32_t) * R_ * L_));
-    ICZ_TRY(m.alloc((void**)&seqs[1], sizeof(int32_t) * R_ * L_));
-    ICZ_TRY(m.alloc((void**)&src_row, sizeof(int32_t) * R_));
-    ICZ_TRY(m.alloc((void**)&img_of_row, sizeof(int32_t) * R_));
-    ICZ_TRY(m.alloc((void**)&best_score, sizeof(float) * R_));
-    ICZ_TRY(m.alloc((void**)&best_len, sizeof(int) * R_));
-    ICZ_TRY(m.alloc((void**)&has_complete, sizeof(int) * R_));
-    ICZ_TRY(m.alloc((void**)&best_seq, sizeof(int32_t) * R_ * L_));
-    ICZ_TRY(m.alloc((void**)&n_live, sizeof(int) * 260));
-    ICZ_TRY(m.alloc((void**)&cand_val, sizeof(float) * R_ * BEAM_MAX_K));
-    ICZ_TRY(m.alloc((void**)&cand_idx, sizeof(int) * R_ * BEAM_MAX_K));
-    ICZ_TRY(m.alloc((void**)&hyp_seq, sizeof(int32_t) * R_ * L_));
-    ICZ_TRY(m.alloc((void**)&hyp_score, sizeof(float) * R_));
-    ICZ_TRY(m.alloc((void**)&hyp_len, sizeof(int) * R_));
-    ICZ_TRY(m.alloc((void**)&hyp_cnt, sizeof(int) * R_));
-    if (extra_feat_cols) ICZ_TRY(m.alloc((void**)&feat_rows, sizeof(float) * R_ * extra_feat_cols));
-    if (!n_live_host) ICZ_CHECK_HIP(hipHostMalloc((void**)&n_live_host, sizeof(int) * 4, 0));
-    ICZ_TRY(m.synced());
-    cap_rows = (int)R_;
-    cap_L = (int)L_;
-    return ICZ_OK;
-}
-
-int BeamBuf::begin(int n_img, int k, int L, int64_t* it, hipStream_t st) {
-    const int rows = n_img * k;
-    ICZ_CHECK_HIP(hipMemsetAsync(n_live, 0, sizeof(int) * 260, st));
-    ICZ_CHECK_HIP(hipMemsetAsync(run, 0, sizeof(float) * rows, st));
-    hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, n_img, k, L, n_act, seqs[0], img_of_row, it, has_complete, best_score,
-                       hyp_cnt);
-    return ICZ_OK;
+void launch_greedy_select(const LogitsView& lv, const DecodeMember::EmbSlot& e, int rows, int V, float* amax_val, int* amax_idx, int64_t* it,
+                          int64_t* ids_out, int T, int t, uint8_t* gunf, int* gn, hipStream_t st) {
+    if (lv.ns > 1)         // 33 - 64 rows: the slabs of the vocabulary projection -> token + next embedding in one launch
+        hipLaunchKernelGGL(greedy_select_kernel, dim3(rows), dim3(1024), 0, st, lv.p, V, lv.ld, lv.ns, lv.slab_stride, lv.bias, e.table, e.E, e.emb,
+                           it, ids_out, T, t, e.relu, gunf, gn);
+    else {
+        hipLaunchKernelGGL(argmax_part_kernel, dim3(rows, ARGMAX_PARTS), dim3(256), 0, st, lv.p, V, lv.ld, ARGMAX_PARTS, amax_val, amax_idx);
+        hipLaunchKernelGGL(embed_argmax_kernel, dim3(cdiv(e.E, 1024), rows), dim3(256), 0, st, (const float*)amax_val, (const int*)amax_idx,
+                           ARGMAX_PARTS, e.table, e.E, e.emb, it, ids_out, T, t, e.relu);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,14 +1,12 @@
 // Model ensembles (beyond the reference; self-critical.pytorch's AttEnsemble): M = 1..4 BUTD / AoA / NIC decoder handles of one
 // vocabulary decode together.  Every step each member runs its own step (DecodeMember, decoder_core.h) on the shared tokens, then
 // ensemble_logprob_kernel combines the members' logits into lp[v] = log(sum_m w_m softmax(logits_m)[v]): greedy takes its argmax in
-// the same launch, beam search hands the rows to the shared driver (BeamBuf::search) with every option it has.
+// the same launch, beam search hands the rows to the shared driver (beam_search, beam.hip) with every option it has.
 #include <cmath>
 
 #include "decoder_core.h"
 
 namespace icz {
-
-constexpr int ENS_MAX_M = 4;
 
 struct EnsArgs {
     LogitsView m[ENS_MAX_M];
@@ -167,7 +165,7 @@ static void launch_combine(const EnsArgs& a, int rows, float* out, int ldo, int6
 }
 
 // ------------------------------------------------------------------------------------------------
-// The driver: owns the shared tokens `it`, the beam buffers and the combined rows lp [rows, Vp]; the members stay the caller's.
+// The ensemble: owns the greedy loop's tokens `it`, its beam buffers and the combined rows lp [rows, Vp]; the members stay the caller's.
 struct Ensemble {
     int M = 0, V = 0, Vp = 0, cap = 0;
     DecodeMember* m[ENS_MAX_M] = {};
@@ -178,7 +176,6 @@ struct Ensemble {
     float* lp = nullptr;
 
     int init(const int32_t* kinds, void* const* members, const float* weights, int n);
-    int check_call(const char* who, const float* const* feats, int rows) const;
     EnsArgs args(const LogitsView* lv) const {
         EnsArgs a = {};
         for (int i = 0; i < M; ++i) { a.m[i] = lv[i]; a.logw[i] = logw[i]; }
@@ -186,8 +183,6 @@ struct Ensemble {
         return a;
     }
     int greedy(const float* const* feats, int B, int max_len, int64_t* ids_out, hipStream_t st);
-    int beam_search(const float* const* feats, int n_img, int k, int max_steps, const icz_beam_opts& o, const icz_beam_diversity& d,
-                    float* seqs_out, int32_t* lens_out, float* scores_out, hipStream_t st);
 };
 
 int Ensemble::init(const int32_t* kinds, void* const* members, const float* weights, int n) {
@@ -217,21 +212,11 @@ int Ensemble::init(const int32_t* kinds, void* const* members, const float* weig
     return mem.synced();
 }
 
-int Ensemble::check_call(const char* who, const float* const* feats, int rows) const {
-    ICZ_REQUIRE(feats, "%s: null features", who);
-    for (int i = 0; i < M; ++i) {
-        ICZ_REQUIRE(feats[i], "%s: null features of member %d", who, i);
-        ICZ_REQUIRE(m[i]->refreshed(), "%s: member %d is not refreshed (call its icz_*_refresh_weights after binding/updating parameters)", who, i);
-        ICZ_REQUIRE(rows <= m[i]->row_capacity(), "%s: %d rows exceed member %d's row capacity %d", who, rows, i, m[i]->row_capacity());
-    }
-    return ICZ_OK;
-}
-
 // one row per image for max_len steps, no early stop (the reference's sample)
 int Ensemble::greedy(const float* const* feats, int B, int max_len, int64_t* ids_out, hipStream_t st) {
     const char* who = "icz_ensemble_greedy";
     ICZ_REQUIRE(ids_out && B > 0 && max_len > 0, "%s: bad arguments", who);
-    ICZ_TRY(check_call(who, feats, B));
+    ICZ_TRY(check_members(who, m, M, feats, B));
     for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->prologue(feats[i], B, 1, nullptr, st));
     hipLaunchKernelGGL(fill_i64_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, it, (int64_t)1, B);       // <sta>
     LogitsView lv[ENS_MAX_M];
@@ -243,30 +228,6 @@ int Ensemble::greedy(const float* const* feats, int B, int max_len, int64_t* ids
     }
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
-}
-
-int Ensemble::beam_search(const float* const* feats, int n_img, int k, int max_steps, const icz_beam_opts& o, const icz_beam_diversity& d,
-                          float* seqs_out, int32_t* lens_out, float* scores_out, hipStream_t st) {
-    const char* who = "icz_ensemble_beam_search_diverse";
-    ICZ_TRY(BeamBuf::check("ensemble", n_img, k, max_steps, 1 << 30));
-    ICZ_TRY(check_call(who, feats, n_img * k));
-    const int rows = n_img * k, L = max_steps + 1;
-    bool compact = true;
-    for (int i = 0; i < M; ++i) compact = compact && m[i]->compact_step();
-    ICZ_TRY(bm.ensure(mem, cap, L));
-    ICZ_TRY(bm.begin(n_img, k, L, it, st));
-    for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->prologue(feats[i], n_img, k, bm.img_of_row, st));
-    LogitsView lv[ENS_MAX_M];
-    auto step = [&](int, bool c) -> int {
-        const int r = c ? n_img : rows;
-        for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->step(r, it, c ? nullptr : bm.img_of_row, c ? 1 : k, 0, true, &lv[i], st));
-        launch_combine(args(lv), r, lp, Vp, nullptr, nullptr, 0, 0, st);
-        return ICZ_OK;
-    };
-    auto gather = [&](bool c) {
-        for (int i = 0; i < M; ++i) m[i]->gather(bm.src_row, rows, c ? k : 1, st);
-    };
-    return bm.search(n_img, k, max_steps, compact, lp, V, Vp, it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
 }
 
 }  // namespace icz
@@ -301,8 +262,13 @@ int icz_ensemble_beam_search_diverse(icz_ensemble_t* h, const float* const* feat
     ICZ_TRY(BeamBuf::check_diversity("icz_ensemble_beam_search_diverse", beam, div));
     ICZ_REQUIRE(seqs_out && lens_out && scores_out, "icz_ensemble_beam_search_diverse: null argument");
     ICZ_REQUIRE(h, "icz_ensemble_beam_search_diverse: null handle");
-    return reinterpret_cast<Ensemble*>(h)->beam_search(feats, n_img, beam, max_steps, *opts, *div, seqs_out, lens_out, scores_out,
-                                                       (hipStream_t)stream);
+    // the combined rows also for M = 1: the member's logits go through ensemble_logprob_kernel, not straight to the search
+    Ensemble* e = reinterpret_cast<Ensemble*>(h);
+    hipStream_t st = (hipStream_t)stream;
+    const BeamCombine ens = {"icz_ensemble_beam_search_diverse", &e->bm, &e->mem, e->cap, e->lp, e->Vp, [=](const LogitsView* lv, int rows) {
+                                 launch_combine(e->args(lv), rows, e->lp, e->Vp, nullptr, nullptr, 0, 0, st);
+                             }};
+    return beam_search("ensemble", e->m, e->M, &ens, feats, n_img, beam, max_steps, *opts, *div, seqs_out, lens_out, scores_out, st);
 }
 
 int icz_ensemble_logprob(int32_t M, const float* const* logits, const float* const* bias, const int32_t* nsplit, const int32_t* ld,

@@ -10,7 +10,7 @@
 namespace icz {
 
 struct Nic : CaptionHead, DecodeMember {
-    static constexpr int STEP_WGS = 256, TARGET_WGS = 512, ARGMAX_PARTS = 8;
+    static constexpr int STEP_WGS = 256, TARGET_WGS = 512;
     icz_nic_dims dims;
     icz_nic_params P;
     bool bound = false, fresh = false;
@@ -29,7 +29,7 @@ struct Nic : CaptionHead, DecodeMember {
     float *th = nullptr, *tc = nullptr, *temb = nullptr, *tg = nullptr, *thd = nullptr, *tlogit = nullptr;
     float *dG = nullptr, *dHd = nullptr, *dEmb = nullptr, *dcb[2] = {nullptr, nullptr}, *X = nullptr, *dWp = nullptr;
     size_t xfloats = 0;
-    BeamBuf bm;
+    float* feat_rows = nullptr;          // beam search: the image embedding replicated per beam row (prologue)
     icz_rng rng = {};
     const float* cur_feats = nullptr;
 
@@ -53,9 +53,6 @@ struct Nic : CaptionHead, DecodeMember {
     int nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* out, int* ns, int target, hipStream_t st,
            const int* live = nullptr);
     int tn(const float* dY, int ldy, int M, const float* Xm, int ldx, int N, int K, float* out, int ldo, int accumulate, hipStream_t st);
-    int beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                    const icz_beam_opts& o = BeamBuf::defaults, float* scores_out = nullptr,
-                    const icz_beam_diversity& d = BeamBuf::no_diversity);
     // decoder seams (DecodeMember, decoder_core.h): the image step, one token step, the beam-state gather
     int vocab() const override { return dims.V; }
     int row_capacity() const override { return dims.max_rows; }
@@ -154,14 +151,8 @@ int Nic::greedy(const float* feats, int B, int T, int64_t* ids_out, hipStream_t 
     for (int t = 0; t < T; ++t) {
         int pns = 1;
         ICZ_TRY(token_step(B, it, t > 0, h[cur], c[cur], h[cur ^ 1], c[cur ^ 1], emb, nullptr, hdrop, logits, off, st, &pns));
-        if (pns > 1)
-            hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(1024), 0, st, (const float*)ws, dims.V, Vp, pns, (size_t)B * Vp,
-                               (const float*)P.predict_b, P.embed_weight, dims.E, emb, it, ids_out, T, t, 0);
-        else {
-            hipLaunchKernelGGL(argmax_part_kernel, dim3(B, ARGMAX_PARTS), dim3(256), 0, st, logits, dims.V, Vp, ARGMAX_PARTS, amax_val, amax_idx);
-            hipLaunchKernelGGL(embed_argmax_kernel, dim3(cdiv(dims.E, 1024), B), dim3(256), 0, st, amax_val, amax_idx, ARGMAX_PARTS,
-                               P.embed_weight, dims.E, emb, it, ids_out, T, t, 0);
-        }
+        launch_greedy_select(logits_view(ws, P.predict_b, logits, B, Vp, pns), emb_slot(), B, dims.V, amax_val, amax_idx, it, ids_out, T, t, nullptr,
+                             nullptr, st);
         cur ^= 1;
     }
     ICZ_CHECK_HIP(hipGetLastError());
@@ -381,20 +372,6 @@ int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st) {
     return ICZ_OK;
 }
 
-int Nic::beam_search(const float* feats, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out, hipStream_t st,
-                      const icz_beam_opts& o, float* scores_out, const icz_beam_diversity& d) {
-    ICZ_REQUIRE(feats && seqs_out && lens_out, "nic beam: null argument");
-    ICZ_TRY(BeamBuf::check("nic", n_img, k, max_steps, dims.max_rows));
-    ICZ_REQUIRE(fresh, "nic: call icz_nic_refresh_weights after binding/updating parameters");
-    const int rows = n_img * k, L = max_steps + 1;
-    ICZ_TRY(bm.ensure(mem, dims.max_rows, L, dims.E));
-    ICZ_TRY(bm.begin(n_img, k, L, it, st));
-    ICZ_TRY(prologue(feats, n_img, k, bm.img_of_row, st));
-    auto step = [&](int, bool) { return this->step(rows, it, bm.img_of_row, k, 0, false, nullptr, st); };
-    auto gather = [&](bool) { this->gather(bm.src_row, rows, 1, st); };
-    return bm.search(n_img, k, max_steps, false, logits, dims.V, Vp, it, seqs_out, lens_out, o, d, scores_out, st, step, gather);
-}
-
 // ---- decoder seams (DecodeMember) ------------------------------------------------------------------------------------------------
 // img_of_row null: the image step of the n_img images (k = 1, greedy); else every beam row starts from the image step of its image
 // (features.expand(k, ...), NIC_Model.py:164), through the handle's expanded-feature rows
@@ -402,9 +379,12 @@ int Nic::prologue(const float* feats, int n_img, int k, const int32_t* img_of_ro
     ICZ_REQUIRE(fresh, "nic: call icz_nic_refresh_weights after binding/updating parameters");
     if (!img_of_row) return image_step(feats, n_img * k, h[0], c[0], nullptr, st);
     const int rows = n_img * k;
-    ICZ_TRY(bm.ensure(mem, dims.max_rows, 1, dims.E));       // the beam buffers hold feat_rows (a no-op once a search has run)
-    hipLaunchKernelGGL(beam_expand_rows_kernel, dim3(cdiv(dims.E, 1024), rows), dim3(256), 0, st, feats, img_of_row, dims.E, bm.feat_rows);
-    return image_step(bm.feat_rows, rows, h[0], c[0], nullptr, st);
+    if (!feat_rows) {
+        ICZ_TRY(alloc((void**)&feat_rows, sizeof(float) * (size_t)dims.max_rows * dims.E));
+        ICZ_TRY(mem.synced());
+    }
+    hipLaunchKernelGGL(beam_expand_rows_kernel, dim3(cdiv(dims.E, 1024), rows), dim3(256), 0, st, feats, img_of_row, dims.E, feat_rows);
+    return image_step(feat_rows, rows, h[0], c[0], nullptr, st);
 }
 
 int Nic::step(int rows, const int64_t* it_, const int32_t*, int, int cur, bool slabs, LogitsView* out, hipStream_t st) {
@@ -412,7 +392,7 @@ int Nic::step(int rows, const int64_t* it_, const int32_t*, int, int cur, bool s
     int pns = 1;
     ICZ_TRY(token_step(rows, it_, seam_emb_ready, h[cur], c[cur], h[cur ^ 1], c[cur ^ 1], emb, nullptr, hdrop, logits, off, st, slabs ? &pns : nullptr,
                        seam_live));
-    if (out) *out = pns > 1 ? LogitsView{ws, P.predict_b, (size_t)rows * Vp, Vp, pns} : LogitsView{logits, nullptr, 0, Vp, 1};
+    if (out) *out = logits_view(ws, P.predict_b, logits, rows, Vp, pns);
     return ICZ_OK;
 }
 
@@ -477,26 +457,5 @@ int icz_nic_xe_backward(icz_nic_t* h, float smoothing, const icz_nic_params* gra
                         float n_tokens_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Nic*>(h)->xe_backward(smoothing, grads, dfeatures_out, loss_out, n_tokens_global, (hipStream_t)stream);
-}
-int icz_nic_beam_search(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps, float* seqs_out,
-                        int32_t* lens_out, void* stream) {
-    ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Nic*>(h)->beam_search(features, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream);
-}
-int icz_nic_beam_search_opts(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
-                             float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
-    ICZ_TRY(BeamBuf::check_opts("icz_nic_beam_search_opts", beam, opts));      // the arguments first: no handle needed to report them
-    ICZ_REQUIRE(features && seqs_out && lens_out && scores_out, "icz_nic_beam_search_opts: null argument");
-    ICZ_REQUIRE(h, "icz_nic_beam_search_opts: null handle");
-    return reinterpret_cast<Nic*>(h)->beam_search(features, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out);
-}
-
-int icz_nic_beam_search_diverse(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
-                                const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
-    ICZ_TRY(BeamBuf::check_opts("icz_nic_beam_search_diverse", beam, opts));      // the arguments first: no handle needed to report them
-    ICZ_TRY(BeamBuf::check_diversity("icz_nic_beam_search_diverse", beam, div));
-    ICZ_REQUIRE(features && seqs_out && lens_out && scores_out, "icz_nic_beam_search_diverse: null argument");
-    ICZ_REQUIRE(h, "icz_nic_beam_search_diverse: null handle");
-    return reinterpret_cast<Nic*>(h)->beam_search(features, n_img, beam, max_steps, seqs_out, lens_out, (hipStream_t)stream, *opts, scores_out, *div);
 }
 }  // extern "C"

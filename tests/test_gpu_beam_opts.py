@@ -27,8 +27,9 @@ def _regime(sd, g, regime, pre):
     return sd
 
 
-def _setup(golden_dir, name, regime="nat", max_rows=16, max_len=20):
-    """-> (model, device handle, CPU parameters for the oracle, device features of up to 3 images)"""
+def _setup(golden_dir, name, regime="nat", max_rows=16, max_len=20, bind=True):
+    """-> (model, device handle, CPU parameters for the oracle, device features of up to 3 images); bind=False: the handle is left
+    unbound"""
     g = dict(np.load(os.path.join(golden_dir, name + ".npz")))
     sd = {k[3:]: v for k, v in g.items() if k.startswith("sd.")}
     if name.startswith("butd"):
@@ -50,7 +51,8 @@ def _setup(golden_dir, name, regime="nat", max_rows=16, max_len=20):
         h = NicHandle(E, H, V, max_rows, max_len)
         feats = torch.tensor(g["feats"])
     params = {k: torch.tensor(np.asarray(v), dtype=torch.float32, device="cuda") for k, v in sd.items()}
-    h.bind(params)
+    if bind:
+        h.bind(params)
     p = {k: v.cpu() for k, v in params.items()}
     return model, h, p, feats[:min(3, feats.shape[0])].contiguous().cuda()
 
@@ -71,6 +73,31 @@ def test_defaults_are_todays_beam_search(golden_dir, name, regime):
         assert s2.shape == (feats.shape[0], 1, 51) and l2.shape == sc.shape == (feats.shape[0], 1)
         assert torch.equal(s2[:, 0], seqs) and torch.equal(l2[:, 0], lens), (name, regime, k)
         assert torch.isfinite(sc).all()
+
+
+@pytest.mark.parametrize("name", ["butd_dec_tiny", "aoa_tiny", "nic_dec_tiny"])
+def test_unrefreshed_handle_is_refused_by_every_beam_entry(golden_dir, name):
+    """The refresh check of the shared beam driver: a handle that was never bound is refused by icz_*_beam_search, _opts and
+    _diverse with the family's own hint; once bound, the same handle searches as test_defaults_are_todays_beam_search expects."""
+    from simpleimagecaptionzoo_amd._lib import IczError
+    model, h, p, feats = _setup(golden_dir, name, bind=False)
+    assert feats.shape[0] == 3
+    hint = "icz_%s_refresh_weights" % model
+    with pytest.raises(IczError, match=hint):
+        h.beam_search(feats, 3, 20)
+    with pytest.raises(IczError, match=hint):
+        h.beam_search_opts(feats, 3, 20)
+    with pytest.raises(IczError, match=hint):
+        h.beam_search_opts(feats, 3, 20, groups=3, diversity=0.5)
+    h.bind({k: v.cuda() for k, v in p.items()})
+    seqs, lens = h.beam_search(feats, 3, 20)
+    s2, l2, sc = h.beam_search_opts(feats, 3, 20)
+    assert s2.shape == (3, 1, 21) and l2.shape == sc.shape == (3, 1)
+    assert torch.equal(s2[:, 0], seqs) and torch.equal(l2[:, 0], lens)
+    assert torch.isfinite(sc).all()
+    _, ref, _, _ = _setup(golden_dir, name)                # a handle bound from the start
+    want_seqs, want_lens = ref.beam_search(feats, 3, 20)
+    assert torch.equal(seqs, want_seqs) and torch.equal(lens, want_lens) and (lens > 1).all()
 
 
 @pytest.mark.parametrize("name", GOLDENS)
