@@ -345,7 +345,16 @@ int icz_aoa_set_regions(icz_aoa_t* h, int32_t regions, const int32_t* counts_dev
  * bits in both halves as the two passes when the GEMMs take the same split-K decomposition (they do at the BASELINE batch of 64;
  * otherwise within fp32 rounding); 0 = two passes.  Fixed region counts only (a batch under icz_aoa_set_regions runs two passes).
  * Option "mha_mfma" (default 1, round 5): the refiner's self-attention (AoA_Model.py:41-69) on the fp32 matrix pipe for up to 64
- * regions; 0 = the register-blocked kernel of rounds 1 - 4 (which larger region sets use anyway). */
+ * regions; 0 = the register-blocked kernel of rounds 1 - 4 (which larger region sets use anyway). 
+ * Option "train_refiner" (default 0; beyond the reference, which optimises the decoder only, AoA_Model.py:669-674): 1 = the backward passes
+ * (icz_aoa_xe_backward, icz_aoa_sample_backward) also fill the gradient slots of img_feats_porjection.* and aoa_refine.* of `grads`: d refined
+ * from the decoder block's linear_K / linear_V and the region mean, back through the final norm, the six refiner layers (each recomputed from
+ * its stored input: a training-mode refiner pass keeps 7 tensors of region rows x Hd) and the projection; there is no gradient to the features.
+ * With 1 every one of those 64 slots must be non-null (ICZ_ERR_INVALID before any launch otherwise) and the forward pass must have been a
+ * training-mode one made while the option was on (an evaluation-mode pass stores nothing).  With 0 those slots are ignored, as before, and
+ * nothing else changes.  The self-attention backward keeps three head tiles and two R x R tiles of an (image, head) in LDS: batches whose region
+ * count needs more than 156 KB (more than 64 regions at heads of 128 columns) are REFUSED with an error, there is no slower path.  Changing the
+ * option releases the training buffers and the captured graphs.  Deterministic: no atomics, fixed summation order. */
 int icz_aoa_set_option(icz_aoa_t* h, const char* name, int32_t value);
 /* eval-mode refined features [B,regions,Hd] (AoADetection_Captioner.sampler's first two lines, :712-713) -- for tests.  With
  * region counts the refiner runs on the packed valid rows; rows past an image's count come back as zeros. */

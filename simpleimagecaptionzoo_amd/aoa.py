@@ -69,6 +69,10 @@ class AoaHandle(GraphDecoderHandle):
         self._regions = (R, None)
         self._counts_dev = None
 
+    def _option_set(self, name, value):
+        if name == "train_refiner":       # on: new_grads / _grad_struct cover every key, the refiner's buffers are required
+            self._frozen_keys = frozenset() if value else type(self)._frozen_keys
+
     def set_regions(self, regions, counts=None):
         """icz_aoa_set_regions: the batches that follow are [B, regions, D]; counts = valid regions per image or None."""
         if counts is None:
@@ -136,6 +140,10 @@ class AoADetection_Captioner(CaptionerBase, nn.Module):
     (forward :676-696, sampler :698-714, sampler_rl :716-734, beam_search_sampler :736-753)."""
 
     _Handle = AoaHandle
+    # Beyond the reference (which optimises the decoder only, AoA_Model.py:669-674): True also trains aoa_refine.* and
+    # img_feats_porjection.* -- get_param_groups / _trainable return every parameter and the handle's backward passes fill the
+    # refiner's gradient buffers (icz_aoa_set_option "train_refiner").  A plain attribute, like ss_prob.
+    train_refiner = False
 
     def __init__(self, vocab_size, num_heads=8, hidden_dim=1024, embed_dim=1024, dropout_aoa=0.3, dropout_prob=0.5, device="cuda:0",
                  num_regions=36, enc_dim=2048, max_batch=128, max_beam=5, max_len=20):
@@ -168,8 +176,23 @@ class AoADetection_Captioner(CaptionerBase, nn.Module):
         return {k: sd[k] for k in AOA_PARAM_KEYS}
 
     def _trainable(self):
+        """The decoder's parameters; with train_refiner the projection's and the refiner's behind them (the order of the flat
+        gradient buffer: the decoder's layout does not move)."""
         sd = dict(self.named_parameters())
-        return {k: sd[k] for k in AOA_DECODER_KEYS}
+        keys = AOA_DECODER_KEYS + (tuple(k for k in AOA_PARAM_KEYS if k not in AOA_DECODER_KEYS) if self.train_refiner else ())
+        return {k: sd[k] for k in keys}
+
+    def get_param_groups(self, lr_dict):
+        """The decoder only (AoA_Model.py:669-674); with train_refiner every parameter, the decoder's first."""
+        if not self.train_refiner:
+            return super().get_param_groups(lr_dict)
+        return [{"params": list(self._trainable().values()), "lr": lr_dict["lr"]}]
+
+    def _push_options(self, h):
+        want = bool(self.train_refiner)
+        if getattr(h, "_train_refiner", False) != want:
+            h.set_option("train_refiner", 1 if want else 0)
+            h._train_refiner = want
 
     def _features(self, visual_inputs):
         """bu_feats (+ the region counts behind bu_masks: `bu_counts` when the Engine supplies them, else read back from the

@@ -96,7 +96,6 @@ int Aoa::refresh(hipStream_t st) {
     return ICZ_OK;
 }
 
-// C = sum_s A_s W_s^T + bias, dense [M,N]; split-K slabs through `ws` when one pass would leave most CUs idle
 static int aoa_linear(Aoa& a, GemmArgs& g, const float* bias, float* out, hipStream_t st) {
     g.out = out; g.ldo = g.N;
     g.nsplit = gemm_fit_split(GEMM_NT, g, gemm_pick_split(g, Aoa::STEP_WGS), a.ws_floats);
@@ -120,6 +119,14 @@ void Aoa::launch_mha_self(int n_img, int R, int qc, size_t lds, const RegionRows
     else
         hipLaunchKernelGGL(mha_self_kernel, dim3(n_img, NH), dim3(256), lds, st, qkv_, qkv_ + Hd, qkv_ + 2 * Hd, o_, R, Hd, NH, qc, rr, dp, 3 * Hd);
 }
+
+void Aoa::mha_self_layer(int n_img, int l, bool train, hipStream_t st) {
+    const int R = cur_R, qc = self_qc(R);
+    launch_mha_self(n_img, R, qc, self_lds(R, qc), region_rows(), qkv, o,
+                    dropp(train, rng.ref_att_mask, (size_t)l * n_img * dims.NH * R * R, AOA_RNG_REF_ATT, l, 0.1f), st);
+}
+
+int Aoa::linear(GemmArgs& g, const float* bias, float* out, hipStream_t st) { return aoa_linear(*this, g, bias, out, st); }
 
 int Aoa::lin(const float* A, int M, int K, const float* W, const float* bias, int N, float* out, hipStream_t st) {
     GemmArgs g = {};
@@ -155,11 +162,18 @@ int Aoa::refine(const float* feats, int n_img, bool train, hipStream_t st, const
         xin = featp;
     }
     if (!proj) ICZ_TRY(lin(xin, rows, dims.D, P.proj_w, P.proj_b, Hd, xa, st));
-    hipLaunchKernelGGL(relu_drop_kernel, dim3(eb), dim3(256), 0, st, proj ? proj : (const float*)xa, xa, nel,
+    // option "train_refiner": a training-mode pass runs its residual chain through xs[0..NL] instead of the ping-pong pair and so leaves
+    // the input of every layer behind for the backward pass (same kernels, same values)
+    const bool store = train && train_refiner;
+    if (store) {
+        ICZ_REQUIRE(xs[0] && n_img <= tcap_B, "aoa: the refiner's training buffers are not allocated for %d images", n_img);
+        ref_feats = xin; xs_valid = true;
+    }
+    hipLaunchKernelGGL(relu_drop_kernel, dim3(eb), dim3(256), 0, st, proj ? proj : (const float*)xa, store ? xs[0] : xa, nel,
                        dropp(train, rng.proj_mask, 0, AOA_RNG_PROJ, 0, 0.5f), rr, Hd);
     const int qc = self_qc(R);
     const size_t lds = self_lds(R, qc);
-    float *cur = xa, *nxt = xb;
+    float *cur = store ? xs[0] : xa, *nxt = store ? xs[1] : xb;
     for (int l = 0; l < NL; ++l) {
         const icz_aoa_block& b = P.layer[l];
         hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, cur, b.ln_g, b.ln_b, ln, rows, Hd, (float*)nullptr);
@@ -179,7 +193,8 @@ int Aoa::refine(const float* feats, int n_img, bool train, hipStream_t st, const
         ICZ_TRY(aoa_linear(*this, g, b.aoa_b, z, st));
         hipLaunchKernelGGL(glu_residual_kernel, dim3(eb), dim3(256), 0, st, z, cur, nxt, (size_t)rows, Hd, rr,
                            dropp(train, rng.ref_sc_mask, (size_t)l * n_img * R * Hd, AOA_RNG_REF_SC, l, 0.1f));
-        float* t_ = cur; cur = nxt; nxt = t_;
+        if (store) { cur = nxt; nxt = l + 2 <= NL ? xs[l + 2] : nullptr; }
+        else { float* t_ = cur; cur = nxt; nxt = t_; }
     }
     hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, cur, P.ref_ln_g, P.ref_ln_b, refined, rows, Hd, (float*)nullptr);
     hipLaunchKernelGGL(mean_rows_kernel, dim3(cdiv(Hd, 256), n_img), dim3(256), 0, st, refined, meanf, Hd, rr);
@@ -205,6 +220,12 @@ int Aoa::refine_pair(int n_img, hipStream_t st, const float* proj) {
     auto second = [&](DropP d, size_t elems_first) { d.idx0 = elems_first; return d; };
     hipLaunchKernelGGL(relu_drop_kernel, dim3(eb), dim3(256), 0, st, proj, w.xa, nel, dropp(false, nullptr, 0, AOA_RNG_PROJ, 0, 0.5f), rr, Hd);
     hipLaunchKernelGGL(relu_drop_kernel, dim3(eb), dim3(256), 0, st, proj, w.xa + nel, nel, dropp(true, rng.proj_mask, 0, AOA_RNG_PROJ, 0, 0.5f), rr, Hd);
+    // option "train_refiner": the training half's layer inputs are copied out for the backward pass (7 x nel floats)
+    const bool store = train_refiner;
+    if (store) {
+        ICZ_REQUIRE(xs[0] && n_img <= tcap_B, "aoa: the refiner's training buffers are not allocated for %d images", n_img);
+        ICZ_CHECK_HIP(hipMemcpyAsync(xs[0], w.xa + nel, sizeof(float) * nel, hipMemcpyDeviceToDevice, st));
+    }
     const int qc = self_qc(R);
     const size_t lds = self_lds(R, qc);
     float *cur = w.xa, *nxt = w.xb;
@@ -225,6 +246,7 @@ int Aoa::refine_pair(int n_img, hipStream_t st, const float* proj) {
         ICZ_TRY(aoa_linear(*this, g, b.aoa_b, w.z, st));
         hipLaunchKernelGGL(glu_residual_kernel, dim3(eb2), dim3(256), 0, st, w.z, cur, nxt, (size_t)rows2, Hd, rr,
                            second(dropp(true, rng.ref_sc_mask, (size_t)l * n_img * R * Hd, AOA_RNG_REF_SC, l, 0.1f), nel));
+        if (store) ICZ_CHECK_HIP(hipMemcpyAsync(xs[l + 1], nxt + nel, sizeof(float) * nel, hipMemcpyDeviceToDevice, st));
         float* t_ = cur; cur = nxt; nxt = t_;
     }
     hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows2, 4)), dim3(256), 0, st, cur, P.ref_ln_g, P.ref_ln_b, w.refined, rows2, Hd, (float*)nullptr);
@@ -395,6 +417,10 @@ int icz_aoa_set_option(icz_aoa_t* h, const char* name, int32_t value) {
     ICZ_REQUIRE(h && name, "icz_aoa_set_option: null argument");
     Aoa* n = reinterpret_cast<Aoa*>(h);
     if (strcmp(name, "graphs") == 0) { n->use_graphs = value != 0; return ICZ_OK; }
+    if (strcmp(name, "train_refiner") == 0) {
+        ICZ_REQUIRE(value == 0 || value == 1, "icz_aoa_set_option: train_refiner takes 0 or 1, got %d", (int)value);
+        return n->set_train_refiner(value != 0);
+    }
     const bool eo = strcmp(name, "early_out") == 0, rp = strcmp(name, "refine_pair") == 0, mm = strcmp(name, "mha_mfma") == 0;
     if (eo || rp || mm) {
         ICZ_CHECK_HIP(hipDeviceSynchronize());      // a replay of a graph about to be destroyed may still be in flight

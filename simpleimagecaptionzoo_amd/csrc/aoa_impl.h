@@ -100,6 +100,25 @@ struct Aoa : CaptionHead, DecodeMember {
           *dVd = nullptr, *dcb[2] = {nullptr, nullptr}, *X = nullptr, *X2 = nullptr, *dWp = nullptr, *prod = nullptr;
     bool early_out = true, bptt_early_out = false;
     size_t xfloats = 0;
+    // option "train_refiner" (aoa_refine_train.hip): a training-mode refiner pass keeps the input of every layer and of the final norm
+    // (xs[l], xs[NL]: region rows x Hd each); the backward pass recomputes one layer at a time from them.  Training buffers, allocated
+    // only while the option is on.
+    bool train_refiner = false;
+    float* xs[NL + 1] = {};
+    bool xs_valid = false;               // xs hold the pass the stored forward state belongs to
+    const float* ref_feats = nullptr;    // what that pass projected: the caller's features, or the bank's packed rows
+    float *rdx[2] = {nullptr, nullptr}, *rdz = nullptr, *rdo = nullptr, *rdln = nullptr, *rdqkv = nullptr, *rdq = nullptr, *rprod = nullptr,
+          *rslab = nullptr, *rdmean = nullptr;
+    size_t rslab_floats = 0;
+    void drop_refiner_buffers() {
+        for (float*& p : xs) p = nullptr;
+        rdx[0] = rdx[1] = rdz = rdo = rdln = rdqkv = rdq = rprod = rslab = rdmean = nullptr;
+        rslab_floats = 0; xs_valid = false; ref_feats = nullptr;
+    }
+    int set_train_refiner(bool on);
+    int alloc_refiner_train(size_t B);
+    int refiner_backward_check(const icz_aoa_params& G) const;      // argument / capacity errors, raised before any launch
+    int refiner_backward(const icz_aoa_params& G, hipStream_t st);
     icz_aoa_rng rng = {};
     // regions per image of the current batch: row stride cur_R <= dims.R and, for the 'adaptive' bottom-up features
     // (10..100 boxes, AoA_Engine.py:37-44), the valid count per image (device, caller-owned; null = all cur_R)
@@ -129,6 +148,8 @@ struct Aoa : CaptionHead, DecodeMember {
     int refine_pair(int n_img, hipStream_t st, const float* proj);
     bool mha_mfma = true;                // icz_aoa_set_option("mha_mfma"): refiner self-attention on the fp32 matrix pipe (<= 64 regions)
     void launch_mha_self(int n_img, int R, int qc, size_t lds, const RegionRows& rr, const float* qkv_, float* o_, const DropP& dp, hipStream_t st);
+    // layer l's self-attention of a pass of its own over n_img images, qkv -> o of the current bank (the backward pass's recompute)
+    void mha_self_layer(int n_img, int l, bool train, hipStream_t st);
     int project(const float* feats, int n_img, float* out, hipStream_t st);
     int step(const AoaStepIO& s, hipStream_t st);
     int greedy(const float* feats, int B, int T, int64_t* ids_out, hipStream_t st, const float* proj = nullptr, bool scst = false, bool refined_ready = false);
@@ -170,6 +191,8 @@ struct Aoa : CaptionHead, DecodeMember {
     int xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
     int bptt(const icz_aoa_params& G, hipStream_t st);
     int colsum(const float* Xm, int K, int N, int ldx, float* out, hipStream_t st);
+    // C = sum_s A_s W_s^T + bias, dense [M,N]; split-K slabs through `ws` when one pass would leave most CUs idle
+    int linear(GemmArgs& g, const float* bias, float* out, hipStream_t st);
     int nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* slab_out, size_t cap, int* ns, int target, hipStream_t st,
            const int* live = nullptr, const int* rows_live = nullptr);
     int tn(const float* dY, int ldy, int M, const float* Xm, int ldx, int N, int K, float* out, int ldo, int accumulate, hipStream_t st,

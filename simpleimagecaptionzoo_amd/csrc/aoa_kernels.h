@@ -536,5 +536,223 @@ __global__ __launch_bounds__(256) void mean_rows_kernel(const float* __restrict_
     m[(size_t)img * Hd + c] = s / (float)len;
 }
 
+
+// ---- refiner backward (option "train_refiner", aoa_refine_train.hip) ------------------------------------------------------------
+// Each refiner layer is recomputed from its stored input in front of its backward step, so these kernels read the forward buffers of
+// that one layer (ln, qkv, z) and regenerate the dropout draws from the indices the forward pass used.
+
+// d meanf[b, c] = sum over steps (then slabs) of du[t, b, c]: u_t = meanf + drop(ctx) (AoA_Model.py:321-323).  du = slabs [ns][T B][Hd]
+// of d gates . W_ih[:, E:]; rows of steps that never ran / rows b >= rows_t[t] hold exact zeros (their d gates are zero).
+__global__ __launch_bounds__(256) void aoa_dmean_kernel(const float* __restrict__ du, int ns, int T, int B, int Hd, float* __restrict__ dmean) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)B * Hd) return;
+    const size_t MN = (size_t)T * B * Hd;
+    float s = 0.f;
+    for (int t = 0; t < T; ++t) s += sum_slabs1(du, ns, MN, (size_t)t * B * Hd + i);
+    dmean[i] = s;
+}
+
+// d refined[row, c] = (dKd k_w)[row, c] + (dVd v_w)[row, c] + d meanf[img, c] / count(img)     (grid (Hd / 256, n_img))
+__global__ __launch_bounds__(256) void aoa_dref_kernel(const float* __restrict__ dk, int nsk, const float* __restrict__ dv, int nsv, size_t MN,
+                                                       const float* __restrict__ dmean, float* __restrict__ dref, int Hd, RegionRows rr) {
+    const int img = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= Hd) return;
+    const int len = rr.count(img);
+    const size_t r0 = rr.first(img);
+    const float m = dmean[(size_t)img * Hd + c] / (float)len;
+    for (int r = 0; r < len; ++r) {
+        const size_t o = (r0 + r) * Hd + c;
+        dref[o] = sum_slabs1(dk, nsk, MN, o) + sum_slabs1(dv, nsv, MN, o) + m;
+    }
+}
+
+// Custom LayerNorm backward over dense rows (aoa_ln_bwd_kernel's maths, aoa_train.hip; the row statistics are recomputed from x).
+//   dq = dq_a (slabs [ns_a][rows][n], may be null) + dq_b (dense [rows][n], may be null);  dq_tot = dq, prod = dq xhat inv (their column sums
+//   are d bias and d gain);  dx = res (the residual branch's gradient, may be null) + LayerNorm'(dq g).  One workgroup per row, n <= 4096.
+__global__ __launch_bounds__(256) void aoa_ln_bwd_dense_kernel(const float* __restrict__ dq_a, int ns_a, const float* __restrict__ dq_b, int rows,
+                                                               const float* __restrict__ x, const float* __restrict__ gain,
+                                                               const float* __restrict__ res, float* __restrict__ dq_tot, float* __restrict__ prod,
+                                                               float* __restrict__ dx, int n) {
+    __shared__ float sm_red[4];
+    constexpr int NV = 4;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const size_t ro = (size_t)row * n;
+    f32x4 dy[NV], xc[NV];
+    float s0 = 0.f;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        const int c = 4 * tid + 1024 * u;
+        xc[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        dy[u] = xc[u];
+        if (c < n) {
+            xc[u] = *reinterpret_cast<const f32x4*>(x + ro + c);
+            s0 += (xc[u][0] + xc[u][1]) + (xc[u][2] + xc[u][3]);
+        }
+    }
+    const float mean = block_sum_256(s0, sm_red) / (float)n;
+    float q = 0.f;
+#pragma unroll
+    for (int u = 0; u < NV; ++u)
+        if (4 * tid + 1024 * u < n) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { xc[u][j] -= mean; q += xc[u][j] * xc[u][j]; }
+        }
+    const float stdv = sqrtf(block_sum_256(q, sm_red) / (float)(n - 1));
+    const float inv = 1.0f / (stdv + 1e-6f);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        const int c = 4 * tid + 1024 * u;
+        if (c < n) {
+            f32x4 dq = {0.f, 0.f, 0.f, 0.f};
+            if (dq_a) dq = sum_slabs4(dq_a, ns_a, (size_t)rows * n, ro + c);
+            if (dq_b) dq += *reinterpret_cast<const f32x4*>(dq_b + ro + c);
+            const f32x4 g = *reinterpret_cast<const f32x4*>(gain + c);
+            f32x4 pr;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                pr[j] = dq[j] * xc[u][j] * inv;
+                dy[u][j] = dq[j] * g[j];
+                s1 += dy[u][j];
+                s2 += dy[u][j] * xc[u][j];
+            }
+            if (dq_tot) *reinterpret_cast<f32x4*>(dq_tot + ro + c) = dq;
+            *reinterpret_cast<f32x4*>(prod + ro + c) = pr;
+        }
+    }
+    s1 = block_sum_256(s1, sm_red);
+    s2 = block_sum_256(s2, sm_red);
+    // stdv = 0 (a constant row) has no defined gradient in the reference either (0 / 0): kx stays finite here
+    const float kx = stdv > 0.f ? -inv * inv * s2 / (stdv * (float)(n - 1)) : 0.f;
+    const float mdx = inv * s1 / (float)n;
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        const int c = 4 * tid + 1024 * u;
+        if (c < n) {
+            f32x4 o = {0.f, 0.f, 0.f, 0.f};
+            if (res) o = *reinterpret_cast<const f32x4*>(res + ro + c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] += dy[u][j] * inv + kx * xc[u][j] - mdx;
+            *reinterpret_cast<f32x4*>(dx + ro + c) = o;
+        }
+    }
+}
+
+// glu_residual_kernel backward: x_out = x + drop(a sigmoid(b)), z = [a | b].  The residual passes d through unchanged (the caller keeps d);
+//   g = drop'(d) (the ref_sc draw of the forward pass);  dz = [g s | g a s (1 - s)]
+__global__ __launch_bounds__(256) void glu_residual_bwd_kernel(const float* __restrict__ d, const float* __restrict__ z, float* __restrict__ dz,
+                                                               size_t rows, int Hd, RegionRows rr, DropP dp) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * Hd) return;
+    const size_t row = i / Hd;
+    const int c = (int)(i % Hd);
+    const float g = dp.apply(d[i], rr.padded(row) * Hd + c);
+    const float a = z[row * 2 * Hd + c], s = sigmoidf_(z[row * 2 * Hd + Hd + c]);
+    dz[row * 2 * Hd + c] = g * s;
+    dz[row * 2 * Hd + Hd + c] = g * a * s * (1.f - s);
+}
+
+// drop_concat_kernel backward: dcat = slabs [ns][rows][2Hd] (the AoA linear's dgrad) -> d o = drop'(dcat[:, :Hd]), d ln = drop'(dcat[:, Hd:])
+__global__ __launch_bounds__(256) void drop_concat_bwd_kernel(const float* __restrict__ dcat, int ns, float* __restrict__ d_o, float* __restrict__ d_ln,
+                                                              size_t rows, int Hd, RegionRows rr, DropP dp) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * Hd) return;
+    const size_t row = i / Hd, prow = rr.padded(row), MN = rows * 2 * Hd;
+    const int c = (int)(i % Hd);
+    d_o[i] = dp.apply(sum_slabs1(dcat, ns, MN, row * 2 * Hd + c), prow * 2 * Hd + c);
+    d_ln[i] = dp.apply(sum_slabs1(dcat, ns, MN, row * 2 * Hd + Hd + c), prow * 2 * Hd + Hd + c);
+}
+
+// relu_drop_kernel backward from its OUTPUT y = drop(relu(x)): y != 0 exactly where the draw kept a positive x
+__global__ __launch_bounds__(256) void relu_drop_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy, float* __restrict__ dx, size_t n,
+                                                            float keep_scale) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    dx[i] = y[i] != 0.f ? dy[i] * keep_scale : 0.f;
+}
+
+// LDS floats of mha_self_bwd_kernel for images of up to R regions and heads of d columns: three head tiles [R][d + 1] and two [R][R + 1]
+__host__ __device__ __forceinline__ size_t mha_self_bwd_lds_floats(int R, int d) { return (size_t)3 * R * (d + 1) + (size_t)2 * R * (R + 1); }
+
+// Refiner self-attention backward, one workgroup per (image, head); n = the image's rows (queries = keys: R, or its count when packed).
+//   P = softmax(Q K^T / sqrt(d)) is recomputed, Pd = drop(P) with the ref_att draw of the forward pass (same index);
+//   dV = Pd^T dO;  dPd = dO V^T;  dP = drop'(dPd);  dS = P (dP - sum_k P dP) / sqrt(d);  dQ = dS K;  dK = dS^T Q
+// Q, K, V are the column blocks of the fused projection `qkv` (rows 3 Hd apart), dO rows are Hd apart, dqkv is written in the fused
+// [dQ | dK | dV] layout.  LDS (mha_self_bwd_lds_floats, checked by the host): phase 1 holds dO and V and leaves dPd; phase 2 loads Q and K over V.
+__global__ __launch_bounds__(256) void mha_self_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dO, float* __restrict__ dqkv, int R,
+                                                           int Hd, int NH, RegionRows rr, DropP dp) {
+    extern __shared__ __attribute__((aligned(16))) float sm_mb[];
+    const int img = blockIdx.x, hd = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int d = Hd / NH, d4 = d >> 2, ld = d + 1, lp = R + 1, ldi = 3 * Hd;
+    const int n = rr.count(img);
+    float* tq = sm_mb;                  // Q
+    float* tk = tq + R * ld;            // V, then K
+    float* tg = tk + R * ld;            // dO
+    float* p1 = tg + R * ld;            // S -> P -> Pd
+    float* p2 = p1 + R * lp;            // dPd -> dS
+    const size_t obase = rr.first(img) * Hd + (size_t)hd * d;
+    const size_t ibase = rr.first(img) * ldi + (size_t)hd * d;
+    for (int i = tid; i < n * d4; i += 256) {
+        const int r = i / d4, j = (i % d4) * 4;
+        const f32x4 g = *reinterpret_cast<const f32x4*>(dO + obase + (size_t)r * Hd + j);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(qkv + ibase + 2 * Hd + (size_t)r * ldi + j);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { tg[r * ld + j + c] = g[c]; tk[r * ld + j + c] = v[c]; }
+    }
+    __syncthreads();
+    for (int i = tid; i < n * n; i += 256) {          // dPd[q][k] = dO[q] . V[k]
+        const int q = i / n, k = i % n;
+        float acc = 0.f;
+        for (int j = 0; j < d; ++j) acc += tg[q * ld + j] * tk[k * ld + j];
+        p2[q * lp + k] = acc;
+    }
+    __syncthreads();
+    for (int i = tid; i < n * d4; i += 256) {
+        const int r = i / d4, j = (i % d4) * 4;
+        const f32x4 qv = *reinterpret_cast<const f32x4*>(qkv + ibase + (size_t)r * ldi + j);
+        const f32x4 kv = *reinterpret_cast<const f32x4*>(qkv + ibase + Hd + (size_t)r * ldi + j);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { tq[r * ld + j + c] = qv[c]; tk[r * ld + j + c] = kv[c]; }
+    }
+    __syncthreads();
+    const float scale = 1.0f / sqrtf((float)d);
+    for (int i = tid; i < n * n; i += 256) {          // S = Q K^T / sqrt(d)
+        const int q = i / n, k = i % n;
+        float acc = 0.f;
+        for (int j = 0; j < d; ++j) acc += tq[q * ld + j] * tk[k * ld + j];
+        p1[q * lp + k] = acc * scale;
+    }
+    __syncthreads();
+    for (int q = wave; q < n; q += 4) {               // one wave per query row, keys lane, lane + 64
+        const int k1 = lane + 64;
+        const float v0 = lane < n ? p1[q * lp + lane] : -INFINITY;
+        const float v1 = k1 < n ? p1[q * lp + k1] : -INFINITY;
+        const float mx = wave_max(fmaxf(v0, v1));
+        const float e0 = lane < n ? expf(v0 - mx) : 0.f;
+        const float e1 = k1 < n ? expf(v1 - mx) : 0.f;
+        const float sum = wave_sum(e0 + e1);
+        const uint64_t idx = (((uint64_t)img * NH + hd) * R + q) * R;
+        const float P0 = e0 / sum, P1 = e1 / sum;
+        // dp.apply(1, i) = the keep factor of draw i: 1 / (1 - p) or 0 (1 without dropout)
+        const float f0 = lane < n ? dp.apply(1.f, idx + lane) : 0.f, f1 = k1 < n ? dp.apply(1.f, idx + k1) : 0.f;
+        const float dP0 = lane < n ? f0 * p2[q * lp + lane] : 0.f, dP1 = k1 < n ? f1 * p2[q * lp + k1] : 0.f;
+        const float dot = wave_sum(P0 * dP0 + P1 * dP1);
+        if (lane < n) { p1[q * lp + lane] = P0 * f0; p2[q * lp + lane] = P0 * (dP0 - dot) * scale; }
+        if (k1 < n) { p1[q * lp + k1] = P1 * f1; p2[q * lp + k1] = P1 * (dP1 - dot) * scale; }
+    }
+    __syncthreads();
+    for (int i = tid; i < n * d; i += 256) {
+        const int r = i / d, j = i % d;
+        float dq = 0.f, dk = 0.f, dv = 0.f;
+        for (int k = 0; k < n; ++k) {
+            dq += p2[r * lp + k] * tk[k * ld + j];           // dQ[r] = sum_k dS[r][k] K[k]
+            dk += p2[k * lp + r] * tq[k * ld + j];           // dK[r] = sum_q dS[q][r] Q[q]
+            dv += p1[k * lp + r] * tg[k * ld + j];           // dV[r] = sum_q Pd[q][r] dO[q]
+        }
+        float* o = dqkv + ibase + (size_t)r * ldi + j;
+        o[0] = dq; o[Hd] = dk; o[2 * Hd] = dv;
+    }
+}
+
 }  // namespace
 }  // namespace icz

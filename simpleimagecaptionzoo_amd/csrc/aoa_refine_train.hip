@@ -1,0 +1,170 @@
+// AoADetection captioner, option "train_refiner": the backward pass through aoa_refine.* and img_feats_porjection.* behind Aoa::bptt
+// (beyond the reference, which optimises the decoder only, AoA_Model.py:669-674).
+//
+// Memory route: a training-mode refiner pass keeps the input of each of the six layers and of the final norm (xs[0..6], region rows x Hd
+// each); the backward pass walks the layers 5 -> 0 and RECOMPUTES a layer's forward (LayerNorm, fused Q/K/V projection, self-attention,
+// dropout of [o | ln], AoA linear) into the bank's scratch buffers in front of its backward step.  The dropout draws come back from Philox
+// or the explicit mask pointers with the indices the forward pass used, as the decoder's backward regenerates its own.
+// Everything runs on the caller's stream behind the joins of bptt: every workspace here has one writer at a time.
+#include "aoa_impl.h"
+
+namespace icz {
+
+int Aoa::set_train_refiner(bool on) {
+    if (on == train_refiner) return ICZ_OK;
+    // the training buffers change their set and the captured graphs their launches: both are dropped and come back on the next call
+    ICZ_TRY(mem.release_training(&gc));
+    ICZ_CHECK_HIP(hipDeviceSynchronize());
+    gc.clear();
+    tcap_B = tcap_T = 0;
+    drop_loss_buffers();
+    drop_refiner_buffers();
+    train_refiner = on;
+    mode = 0;
+    return ICZ_OK;
+}
+
+// called inside ensure_train's TrainingScope: released with the other training buffers
+int Aoa::alloc_refiner_train(size_t B) {
+    const size_t RR = B * dims.R, Hd = dims.Hd;
+    for (float*& p : xs) ICZ_TRY(alloc((void**)&p, sizeof(float) * RR * Hd));
+    float** one[] = {&rdx[0], &rdx[1], &rdo, &rdln, &rdq, &rprod};
+    for (float** p : one) ICZ_TRY(alloc((void**)p, sizeof(float) * RR * Hd));
+    ICZ_TRY(alloc((void**)&rdz, sizeof(float) * RR * 2 * Hd));
+    ICZ_TRY(alloc((void**)&rdqkv, sizeof(float) * RR * 3 * Hd));
+    ICZ_TRY(alloc((void**)&rdmean, sizeof(float) * B * Hd));
+    // split-K slabs of the dgrad products: two slabs of the widest one (rows x 2Hd) and the small-launch reserve of the decoder's slabs
+    rslab_floats = (size_t)TARGET_WGS * 4096 * 2 + 2 * RR * 2 * Hd;
+    ICZ_TRY(alloc((void**)&rslab, sizeof(float) * rslab_floats));
+    const size_t lds = sizeof(float) * mha_self_bwd_lds_floats(dims.R, dims.Hd / dims.NH);
+    if (lds > 48 * 1024)      // (a narrower batch may fit where the handle's capacity does not: refiner_backward_check decides per call)
+        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mha_self_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)(lds < LDS_BUDGET ? lds : LDS_BUDGET)));
+    return ICZ_OK;
+}
+
+int Aoa::refiner_backward_check(const icz_aoa_params& G) const {
+    static const char* const block_names[10] = {"linear_Q.weight", "linear_Q.bias", "linear_K.weight", "linear_K.bias", "linear_V.weight",
+                                                "linear_V.bias", "aoa_module.0.weight", "aoa_module.0.bias", "norm.gain", "norm.bias"};
+    ICZ_REQUIRE(G.proj_w && G.proj_b, "aoa: option train_refiner is on and the gradient buffer of img_feats_porjection.0.%s is null",
+                G.proj_w ? "bias" : "weight");
+    for (int l = 0; l < NL; ++l) {
+        const float* const* slot = reinterpret_cast<const float* const*>(&G.layer[l]);
+        for (int i = 0; i < 10; ++i)
+            ICZ_REQUIRE(slot[i], "aoa: option train_refiner is on and the gradient buffer of aoa_refine.aoa_layers.%d %s is null", l, block_names[i]);
+    }
+    ICZ_REQUIRE(G.ref_ln_g && G.ref_ln_b, "aoa: option train_refiner is on and the gradient buffer of aoa_refine.norm.%s is null",
+                G.ref_ln_g ? "bias" : "gain");
+    ICZ_REQUIRE(xs_valid && xs[0] && ref_feats, "aoa: option train_refiner needs a training-mode forward pass made while it was on "
+                "(an evaluation-mode pass stores nothing)");
+    const size_t lds = sizeof(float) * mha_self_bwd_lds_floats(cur_R, dims.Hd / dims.NH);
+    ICZ_REQUIRE(lds <= LDS_BUDGET, "aoa: train_refiner: the self-attention backward needs %zu bytes of LDS for %d regions and heads of %d "
+                "columns (limit %zu)", lds, cur_R, dims.Hd / dims.NH, LDS_BUDGET);
+    return ICZ_OK;
+}
+
+namespace {
+
+// slabs [ns][M][N] = A[M,K] . B[K,N] into `slab` (capacity `cap` floats); the split shrinks to fit
+int rnn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* slab, size_t cap, int* ns_out, hipStream_t st) {
+    GemmArgs g = {};
+    g.nseg = 1;
+    g.seg[0] = {A, Bm, lda, ldb, K, nullptr};
+    g.M = M; g.N = N; g.out = slab; g.ldo = N;
+    g.nsplit = M <= 64 ? gemm_fit_split(GEMM_NN, g, gemm_pick_split(g, Aoa::TARGET_WGS, GEMM_NN), cap) : gemm_pick_split_balanced(g, GEMM_NN, cap);
+    ICZ_REQUIRE(gemm_slab_floats(M, N, g.nsplit) <= cap, "aoa: refiner slab buffer too small");
+    ICZ_TRY(gemm_f32(GEMM_NN, g, st));
+    *ns_out = g.nsplit;
+    return ICZ_OK;
+}
+
+}  // namespace
+
+int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
+    use_bank(1);
+    const int B = cur_B, T = cur_T, Hd = dims.Hd, E = dims.E, NH = dims.NH, R = cur_R, D = dims.D, TB = T * B;
+    const int rows = (int)region_row_count(B);
+    const RegionRows rr = region_rows();
+    const size_t nel = (size_t)rows * Hd;
+    const unsigned eb = (unsigned)((nel + 255) / 256);
+    const bool train = cur_train;
+    // ---- 1. d refined = dKd k_w + dVd v_w + d meanf / count;  d meanf[b] = sum_t du_t[b], du = d gates . W_ih[:, E:] over all (t, b) rows
+    //         (the rows of steps that never ran and rows b >= rows_t[t] hold zero d gates: bptt zeroed them in front of its loop)
+    int nsu = 1, nsk = 1, nsv = 1;
+    ICZ_TRY(rnn(dG, 4 * Hd, TB, 4 * Hd, P.lstm_w_ih + E, E + Hd, Hd, rslab, rslab_floats, &nsu, st));
+    hipLaunchKernelGGL(aoa_dmean_kernel, dim3((unsigned)(((size_t)B * Hd + 255) / 256)), dim3(256), 0, st, rslab, nsu, T, B, Hd, rdmean);
+    const size_t half = rslab_floats / 2;
+    ICZ_TRY(rnn(dKd, Hd, rows, Hd, P.dec.k_w, Hd, Hd, rslab, half, &nsk, st));
+    ICZ_TRY(rnn(dVd, Hd, rows, Hd, P.dec.v_w, Hd, Hd, rslab + half, half, &nsv, st));
+    hipLaunchKernelGGL(aoa_dref_kernel, dim3(cdiv(Hd, 256), B), dim3(256), 0, st, rslab, nsk, rslab + half, nsv, nel, rdmean, rdq, Hd, rr);
+    // ---- 2. aoa_refine.norm
+    int c = 0;
+    hipLaunchKernelGGL(aoa_ln_bwd_dense_kernel, dim3(rows), dim3(256), 0, st, (const float*)nullptr, 0, (const float*)rdq, rows, (const float*)xs[NL],
+                       P.ref_ln_g, (const float*)nullptr, (float*)nullptr, rprod, rdx[c], Hd);
+    ICZ_TRY(colsum(rprod, rows, Hd, Hd, G.ref_ln_g, st));
+    ICZ_TRY(colsum(rdq, rows, Hd, Hd, G.ref_ln_b, st));
+    // ---- 3. the layers, last to first
+    const size_t lds_b = sizeof(float) * mha_self_bwd_lds_floats(R, Hd / NH);
+    for (int l = NL - 1; l >= 0; --l) {
+        const icz_aoa_block& b = P.layer[l];
+        const icz_aoa_block& gb = G.layer[l];
+        const DropP d_att = dropp(train, rng.ref_att_mask, (size_t)l * B * NH * R * R, AOA_RNG_REF_ATT, l, 0.1f);
+        const DropP d_aoa = dropp(train, rng.ref_aoa_mask, (size_t)l * B * R * 2 * Hd, AOA_RNG_REF_AOA, l, 0.3f);
+        const DropP d_sc = dropp(train, rng.ref_sc_mask, (size_t)l * B * R * Hd, AOA_RNG_REF_SC, l, 0.1f);
+        // forward of layer l from its stored input (Aoa::refine's launches)
+        hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, (const float*)xs[l], b.ln_g, b.ln_b, ln, rows, Hd, (float*)nullptr);
+        ICZ_TRY(lin(ln, rows, Hd, w_qkv[l], b_qkv[l], 3 * Hd, qkv, st));
+        mha_self_layer(B, l, train, st);
+        const float *xo = o, *xn = ln;
+        if (train) {
+            hipLaunchKernelGGL(drop_concat_kernel, dim3(eb), dim3(256), 0, st, (const float*)o, (const float*)ln, od, nd, (size_t)rows, Hd, rr, d_aoa);
+            xo = od; xn = nd;
+        }
+        {
+            GemmArgs g = {};
+            g.nseg = 2;
+            g.seg[0] = {xo, b.aoa_w, Hd, 2 * Hd, Hd, nullptr};
+            g.seg[1] = {xn, b.aoa_w + Hd, Hd, 2 * Hd, Hd, nullptr};
+            g.M = rows; g.N = 2 * Hd;
+            ICZ_TRY(linear(g, b.aoa_b, z, st));
+        }
+        // GLU + residual: rdx[c] = d x_{l+1} stays the residual branch's gradient
+        hipLaunchKernelGGL(glu_residual_bwd_kernel, dim3(eb), dim3(256), 0, st, (const float*)rdx[c], (const float*)z, rdz, (size_t)rows, Hd, rr, d_sc);
+        // AoA linear: weight gradient against the dropped inputs (two column groups of aoa_w), bias, input gradient
+        const GemmColGroup groups[2] = {{xo, Hd, Hd, gb.aoa_w, 2 * Hd}, {xn, Hd, Hd, gb.aoa_w + Hd, 2 * Hd}};
+        if (gemm_tn_grouped_fits(2 * Hd, rows, groups, 2)) {
+            ICZ_TRY(gemm_tn_grouped(rdz, 2 * Hd, 2 * Hd, rows, groups, 2, nullptr, st));
+        } else {
+            ICZ_TRY(tn(rdz, 2 * Hd, 2 * Hd, xo, Hd, Hd, rows, gb.aoa_w, 2 * Hd, 0, st));
+            ICZ_TRY(tn(rdz, 2 * Hd, 2 * Hd, xn, Hd, Hd, rows, gb.aoa_w + Hd, 2 * Hd, 0, st));
+        }
+        ICZ_TRY(colsum(rdz, rows, 2 * Hd, 2 * Hd, gb.aoa_b, st));
+        int ns = 1;
+        ICZ_TRY(rnn(rdz, 2 * Hd, rows, 2 * Hd, b.aoa_w, 2 * Hd, 2 * Hd, rslab, rslab_floats, &ns, st));
+        hipLaunchKernelGGL(drop_concat_bwd_kernel, dim3(eb), dim3(256), 0, st, (const float*)rslab, ns, rdo, rdln, (size_t)rows, Hd, rr, d_aoa);
+        // self-attention
+        hipLaunchKernelGGL(mha_self_bwd_kernel, dim3(B, NH), dim3(256), lds_b, st, (const float*)qkv, (const float*)rdo, rdqkv, R, Hd, NH, rr, d_att);
+        // fused Q/K/V projection: the three weight gradients go to the separate reference tensors
+        float* const gw[3] = {gb.q_w, gb.k_w, gb.v_w};
+        float* const gbias[3] = {gb.q_b, gb.k_b, gb.v_b};
+        for (int w = 0; w < 3; ++w) {
+            ICZ_TRY(tn(rdqkv + (size_t)w * Hd, 3 * Hd, Hd, ln, Hd, Hd, rows, gw[w], Hd, 0, st));
+            ICZ_TRY(colsum(rdqkv + (size_t)w * Hd, rows, Hd, 3 * Hd, gbias[w], st));
+        }
+        ICZ_TRY(rnn(rdqkv, 3 * Hd, rows, 3 * Hd, w_qkv[l], Hd, Hd, rslab, rslab_floats, &ns, st));
+        // LayerNorm (its output fed the projection and the [o | ln] concatenation) + the residual
+        hipLaunchKernelGGL(aoa_ln_bwd_dense_kernel, dim3(rows), dim3(256), 0, st, (const float*)rslab, ns, (const float*)rdln, rows, (const float*)xs[l],
+                           b.ln_g, (const float*)rdx[c], rdq, rprod, rdx[c ^ 1], Hd);
+        ICZ_TRY(colsum(rprod, rows, Hd, Hd, gb.ln_g, st));
+        ICZ_TRY(colsum(rdq, rows, Hd, Hd, gb.ln_b, st));
+        c ^= 1;
+    }
+    // ---- 4. img_feats_porjection: ReLU + dropout backward from the stored output, weight gradient over the region rows
+    hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3(eb), dim3(256), 0, st, (const float*)xs[0], (const float*)rdx[c], rdo, nel, train ? 2.0f : 1.0f);
+    ICZ_TRY(tn(rdo, Hd, Hd, ref_feats, D, D, rows, G.proj_w, D, 0, st));
+    ICZ_TRY(colsum(rdo, rows, Hd, Hd, G.proj_b, st));
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+}  // namespace icz

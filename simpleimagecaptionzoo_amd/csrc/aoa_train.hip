@@ -214,6 +214,7 @@ int Aoa::ensure_train(int Bq, int Tq) {
         ICZ_TRY(mem.release_training(&gc));
         tcap_B = tcap_T = 0;
         drop_loss_buffers();
+        drop_refiner_buffers();
     }
     DeviceBuffers::TrainingScope scope(mem);
     const size_t B = Bq, T = Tq, Hd = dims.Hd, E = dims.E, R = dims.R, NH = dims.NH;
@@ -250,6 +251,7 @@ int Aoa::ensure_train(int Bq, int Tq) {
     ICZ_TRY(alloc((void**)&X2, sizeof(float) * xfloats));
     ICZ_TRY(alloc((void**)&dWp, sizeof(float) * (size_t)Vp * Hd));
     ICZ_TRY(alloc_loss_buffers(mem, TB, B, T));
+    if (train_refiner) ICZ_TRY(alloc_refiner_train(B));
     ICZ_TRY(mem.synced());
     tcap_B = Bq; tcap_T = Tq;
     return ICZ_OK;
@@ -282,6 +284,7 @@ int Aoa::sample_prelude(const float* feats, int B, int T, const icz_aoa_rng* r, 
     rng = *r;
     hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
     mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_seq = seq_out; cur_logp = logp_out;
+    xs_valid = false;                  // set by the training-mode refiner pass of this rollout (option "train_refiner")
     rows_t.assign(T, B);
     return ICZ_OK;
 }
@@ -360,6 +363,8 @@ int Aoa::rollouts(const float* feats, int B, int T, const icz_aoa_rng* r, int64_
     }
     // (host state, outside any captured graph: a replayed rollout pair leaves the banks where this call's batch size puts them)
     if (!lens && pair_refine) point_banks_at_pair(B); else { point_bank_at_own(0); point_bank_at_own(1); }
+    // (host state too: a replayed graph does not run the refiner's host code) fixed region counts project the caller's features
+    if (train_refiner && !lens) { ref_feats = feats; xs_valid = true; }
     if (!use_graphs || lens || aoa_explicit_rng(rng)) return rollouts_impl(feats, B, T, ids_out, seq_out, logp_out, st);
     const std::vector<uintptr_t> key = {1, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)T, (uintptr_t)cur_R, (uintptr_t)ids_out, (uintptr_t)seq_out,
                                         (uintptr_t)logp_out};
@@ -386,6 +391,7 @@ int Aoa::rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int64
 int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* loss_out, float* msum_out, float msum_global, hipStream_t st) {
     ICZ_TRY(require_mode(1, "aoa"));
     ICZ_REQUIRE(reward && G, "aoa sample_backward: null argument");
+    if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
     set_msum_global(msum_global, st);      // < 0: keep the device value handed over by icz_aoa_set_norm_global
     mode = 0;
     bptt_early_out = true;
@@ -394,7 +400,8 @@ int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* lo
     if (!use_graphs || lens || grad_cb || aoa_explicit_rng(rng)) return sample_backward_impl(reward, *G, loss_out, msum_out, st);
     std::vector<uintptr_t> key = {2, (uintptr_t)reward, (uintptr_t)loss_out, (uintptr_t)msum_out, (uintptr_t)cur_B, (uintptr_t)cur_T, (uintptr_t)cur_R,
                                   (uintptr_t)cur_seq, (uintptr_t)cur_logp,
-                                  (uintptr_t)bank[0].refined, (uintptr_t)bank[0].Kd, (uintptr_t)bank[1].refined, (uintptr_t)bank[1].Kd, (uintptr_t)bank[1].Vd, (uintptr_t)cur_bank};      // paired-refine banks (rollouts) or the handle's own (sample)
+                                  (uintptr_t)bank[0].refined, (uintptr_t)bank[0].Kd, (uintptr_t)bank[1].refined, (uintptr_t)bank[1].Kd, (uintptr_t)bank[1].Vd, (uintptr_t)cur_bank,      // paired-refine banks (rollouts) or the handle's own (sample)
+                                  (uintptr_t)train_refiner, (uintptr_t)xs[0], (uintptr_t)ref_feats};      // the refiner's backward pass behind bptt
     const float* const* gp = reinterpret_cast<const float* const*>(G);
     for (size_t i = 0; i < sizeof(icz_aoa_params) / sizeof(float*); ++i) key.push_back((uintptr_t)gp[i]);
     const icz_aoa_params Gc = *G;
@@ -417,6 +424,7 @@ int Aoa::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
     use_bank(1);
     if (r) rng = *r; else rng = {};
     begin_xe(lengths, B, T, L, captions, train != 0, rng.seed, st);
+    xs_valid = false;
     ICZ_TRY(refine(feats, B, cur_train, st));
     const size_t sH = (size_t)B * dims.Hd;
     ICZ_CHECK_HIP(hipMemsetAsync(th, 0, sizeof(float) * sH, st));
@@ -452,6 +460,7 @@ int Aoa::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
 int Aoa::xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, float n_tokens_global, hipStream_t st) {
     ICZ_TRY(require_mode(2, "aoa"));
     ICZ_REQUIRE(G, "aoa xe_backward: null grads");
+    if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
     ICZ_TRY(xe_loss(smoothing, n_tokens_global, tlogit, dims.V, Vp, loss_out, st));
     bptt_early_out = false;
     return bptt(*G, st);
@@ -639,6 +648,9 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     }
     if (s_tail != ICZ_OK) return s_tail;
     ICZ_CHECK_HIP(hipGetLastError());
+    // option "train_refiner": d refined -> the refiner and the feature projection, on the caller's stream behind every join above
+    // (dKd / dVd from the tail, d gates from the loop)
+    if (train_refiner) return refiner_backward(G, st);
     return ICZ_OK;
 }
 

@@ -60,8 +60,11 @@ class FusedAdam:
 
     def load_state_dict(self, sd):
         params = [p for g in self.param_groups for p in g["params"]]
-        if [len(g["params"]) for g in sd["param_groups"]] != [len(g["params"]) for g in self.param_groups]:
-            raise ValueError("optimizer state has a different parameter grouping")
+        have, want = [len(g["params"]) for g in sd["param_groups"]], [len(g["params"]) for g in self.param_groups]
+        if have != want:
+            raise ValueError("optimizer state has a different parameter grouping: the checkpoint holds %s parameters per group, this optimizer "
+                             "%s (an AoA checkpoint written without train_refiner does not load into an optimizer made with it, or the "
+                             "reverse: create the optimizer from the same get_param_groups)" % (have, want))
         for g, saved in zip(self.param_groups, sd["param_groups"]):
             g["lr"] = saved["lr"]
         self.state = {}
@@ -627,6 +630,23 @@ class AoADetection_Eng(BUTDDetection_Eng):
     _multi_sample = False
     _GRAD_STAGES = (("decoder.predict.weight_v", "decoder.predict.weight_g", "decoder.predict.bias"),
                     ("decoder.embed.0.weight", "decoder.lstm.weight_ih", "decoder.lstm.weight_hh", "decoder.lstm.bias_ih", "decoder.lstm.bias_hh"))
+
+    def __init__(self, *args, train_refiner=False, **kwargs):
+        """train_refiner (beyond the reference, which optimises the decoder only): also fit aoa_refine.* and img_feats_porjection.*."""
+        super().__init__(*args, **kwargs)
+        self.train_refiner = train_refiner
+
+    @property
+    def train_refiner(self):
+        return self.model.train_refiner
+
+    @train_refiner.setter
+    def train_refiner(self, on):
+        on = bool(on)
+        if on != self.model.train_refiner:
+            self.model.train_refiner = on         # pushed to the handle as its option by the next _handle()
+            self._flat = None                      # the flat gradient buffer gains / loses the refiner's slice
+            self._hooked = None
 
     def model_construction(self, max_batch):
         from .aoa import AoADetection_Captioner

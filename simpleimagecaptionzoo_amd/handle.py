@@ -241,6 +241,10 @@ class GraphDecoderHandle(DecoderHandle):
     def set_option(self, name, value):
         """icz_<family>_set_option (include/icz.h): "graphs", "early_out", ...; the family's header comment lists its own."""
         check(self._e.set_option(self._h, name.encode(), int(value)))
+        self._option_set(name, int(value))
+
+    def _option_set(self, name, value):
+        """What an accepted option changes on the host side (AoA: "train_refiner" unfreezes the refiner's gradient buffers)."""
 
     def set_grad_callback(self, fn):
         """fn(stage) is called while a backward call is being enqueued, each time a group of gradients is complete in
@@ -291,7 +295,11 @@ class CaptionerBase(ScheduledSamplingState):
         else:
             self._h.refresh()
         self._ss_push(self._h, fresh)
+        self._push_options(self._h)
         return self._h
+
+    def _push_options(self, h):
+        """Captioner attributes that are handle options (AoA: train_refiner); called by _handle()."""
 
     def _replay_handle(self):
         """One-row handle for the teacher-forced replay behind eval_test_image's attention maps: the training handle keeps its
