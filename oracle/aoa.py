@@ -117,7 +117,7 @@ def greedy(feats, p, max_len=20, lens=None, hoisted=False):
     return torch.stack(ids, 1), torch.stack(lgs, 1)
 
 
-def sample_rl(feats, p, uniforms, masks, max_len=20, early_exit=True, lens=None, hoisted=False):
+def sample_rl(feats, p, uniforms, masks, max_len=20, early_exit=True, lens=None, hoisted=False, logits_out=None):
     enc = refine(feats, p, masks, lens)
     B, R, Hd = enc.shape
     bu = key_mask(lens, R)
@@ -129,6 +129,8 @@ def sample_rl(feats, p, uniforms, masks, max_len=20, early_exit=True, lens=None,
     pre = hoist_dec(enc, p) if hoisted else None
     for t in range(max_len):
         logits, _, st = dec_step(it, st, enc, meanf, p, _step_masks(masks, t), bu, pre)
+        if logits_out is not None:          # the logits each draw was made from (for the tests' CDF-edge rule)
+            logits_out.append(logits.detach())
         logp = torch.log_softmax(logits, dim=1)
         draw = inverse_cdf_draw(torch.exp(logp.detach()), uniforms[t])
         lps[t] = logp.gather(1, draw.unsqueeze(1)).squeeze(1)

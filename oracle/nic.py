@@ -32,7 +32,7 @@ def greedy(feats, p, max_len=20):
     return torch.stack(ids, 1), torch.stack(lgs, 1)
 
 
-def sample_rl(feats, p, uniforms, out_masks, max_len=20, early_exit=True):
+def sample_rl(feats, p, uniforms, out_masks, max_len=20, early_exit=True, logits_out=None):
     """DecoderRNN.sample_rl, NIC_Model.py:121-151 with explicit uniforms / masks."""
     B = feats.shape[0]
     h, c = init_state(feats, p)
@@ -42,6 +42,8 @@ def sample_rl(feats, p, uniforms, out_masks, max_len=20, early_exit=True):
     unfinished = torch.ones(B, dtype=torch.bool)
     for t in range(max_len):
         logits, h, c = step(it, h, c, p, None if out_masks is None else torch.as_tensor(out_masks[t]))
+        if logits_out is not None:          # the logits each draw was made from (for the tests' CDF-edge rule)
+            logits_out.append(logits.detach())
         logp = torch.log_softmax(logits, dim=1)
         draw = inverse_cdf_draw(torch.exp(logp.detach()), uniforms[t])
         lps[t] = logp.gather(1, draw.unsqueeze(1)).squeeze(1)

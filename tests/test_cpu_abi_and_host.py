@@ -453,6 +453,35 @@ def test_midwidth_configurations_reach_the_routes_they_are_there_for(name):
     assert not lost, (name, lost)
 
 
+def _table_names(table):
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _fullwidth
+    return sorted(getattr(_fullwidth, table))
+
+
+@pytest.mark.parametrize("name", _table_names("AOA_MIDWIDTH"))
+def test_aoa_midwidth_configurations_reach_the_routes_they_are_there_for(name):
+    """tests/_fullwidth.py: AOA_MIDWIDTH (the widths of tests/test_gpu_aoa_midwidth.py) -- every purpose a width is listed for, stated
+    through the library's host-only routing entries and the attention predicates of csrc/aoa.hip (matrix-pipe kernel up to 64 regions
+    at head widths that are multiples of 64; the two LDS sizes against the 48 KB opt-in)."""
+    from _fullwidth import aoa_midwidth_routes
+    claims = aoa_midwidth_routes(name)
+    assert len(claims) >= 3
+    lost = [c for c, ok in claims.items() if not ok]
+    assert not lost, (name, lost)
+
+
+@pytest.mark.parametrize("name", _table_names("NIC_MIDWIDTH"))
+def test_nic_midwidth_configurations_reach_the_routes_they_are_there_for(name):
+    """tests/_fullwidth.py: NIC_MIDWIDTH (the widths of tests/test_gpu_nic_midwidth.py), as above"""
+    from _fullwidth import nic_midwidth_routes
+    claims = nic_midwidth_routes(name)
+    assert len(claims) >= 3
+    lost = [c for c, ok in claims.items() if not ok]
+    assert not lost, (name, lost)
+
+
 def test_routing_entries_at_the_baseline_shapes_and_the_split_pick():
     """icz_gemm_route_for / icz_gemm_tn_split_pick at the benchmark width (36 x 2048, H = E = A = 1024, V = 10102 -> 10112, 64 x 20): the
     decoder-step gates on the 512-deep resident form (128 rows: its 128-row form, 16 rows: the fp32 NT kernel), dec_att on the fp32 NT

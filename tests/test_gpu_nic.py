@@ -186,47 +186,9 @@ from _fullwidth import (_excuse_greedy, _first_divergence)  # noqa: E402
 def test_nic_config1_size_matches_oracle():
     """BASELINE config 1 at its own size: NIC decoder, Flickr8K-size vocabulary 2543, E = H = 512, batch 16, 20 steps, random-init
     (un-sharpened) weights: greedy ids exact, sampled ids exact up to CDF-boundary draws, log-probs 1e-4, REINFORCE gradients
-    2e-4 (NIC_Model.py:100-151)."""
-    from oracle import butd as ob
-    from oracle import nic as onic
-    from simpleimagecaptionzoo_amd.butd import make_rng
-    from simpleimagecaptionzoo_amd.nic import NicHandle
-    from simpleimagecaptionzoo_amd.synth import random_nic_params
-    En, Hn, Vn, B, T = 512, 512, 2543, 16, 20
-    params = random_nic_params(En, Hn, Vn, "cuda", seed=7)
-    h = NicHandle(En, Hn, Vn, B, T)
-    h.bind(params)
-    g = torch.Generator(device="cpu")
-    g.manual_seed(11)
-    feats_c = torch.randn(B, En, generator=g)
-    feats = feats_c.cuda()
-    p = {k: v.detach().cpu().clone().requires_grad_(True) for k, v in params.items()}
-    ids = h.greedy(feats, T).cpu().numpy()
-    with torch.no_grad():
-        w_ids, w_glog = onic.greedy(feats_c, p, T)
-    _excuse_greedy(ids, w_ids, w_glog, 1)
-    rs = np.random.RandomState(12)
-    om = rs.rand(T, B, Hn) < 0.5
-    u = rs.rand(T, B).astype(np.float32)
-    rng = make_rng(0, torch.tensor(u, device="cuda"), None, None, torch.tensor(om.astype(np.uint8), device="cuda"))
-    seq, lp = h.sample(feats, T, rng)
-    seq, lp = seq.cpu().numpy(), lp.cpu().numpy()
-    w_seq, w_lp = onic.sample_rl(feats_c, p, u.astype(np.float64), om, T, early_exit=False)
-    sdiv = _first_divergence(seq, w_seq.numpy())
-    assert (sdiv >= 0).sum() <= 1
-    ok = sdiv < 0
-    np.testing.assert_allclose(lp[ok], w_lp.detach().numpy()[ok], atol=1e-4)
-    rw = (rs.randn(B, 1).astype(np.float32) * ok[:, None]).repeat(T, 1)
-    grads = h.new_grads()
-    loss, _ = h.sample_backward(torch.tensor(rw, device="cuda"), grads)
-    w_loss = ob.reward_criterion(w_lp, torch.from_numpy(np.where(ok[:, None], w_seq.numpy(), seq)), torch.from_numpy(rw))
-    w_loss.backward()
-    assert abs(loss.item() - w_loss.item()) < 1e-4
-    for k, gt in grads.items():
-        want = p[k].grad.numpy()
-        scale = max(1e-6, float(np.abs(want).max()))
-        assert np.abs(gt.cpu().numpy() - want).max() <= 2e-4 * scale + 1e-7, (k, float(np.abs(gt.cpu().numpy() - want).max()), scale)
-    h.close()
+    2e-4 (NIC_Model.py:100-151).  The body is tests/_fullwidth.py: _nic_scst_case (shared with tests/test_gpu_nic_midwidth.py)."""
+    from _fullwidth import _nic_scst_case
+    _nic_scst_case((512, 512, 2543), 16, 20, seed=7, seeds=(7, 11, 12), limit=1, sampled_rule="count")
 
 
 @pytest.mark.parametrize("B", [5, 40])
