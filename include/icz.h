@@ -547,6 +547,44 @@ int icz_ciderd_reward_loo(icz_ciderd_t* h, const int64_t* gen, int32_t B, int32_
                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Caption sets (beyond the reference): K candidate captions per image, as n-best lists, diverse beams, ensembles and the sampling
+ * decode produce them, scored against EACH OTHER -- consensus (minimum-Bayes-risk) reranking -- and counted for the diversity
+ * metrics of a set report (Div-n, mBLEU, mean pairwise CIDEr-D).  Candidates arrive as int32 DEVICE arrays in CSR form, as for
+ * icz_bleu_stats: candidate c = img * K + k is tok[ptr[c] .. ptr[c+1]), token ids >= 0, every token a word (no <sta>, <end> or
+ * <pad> unless the caller wants them counted), at most 60 tokens (the caller checks), empty candidates are legal.  Argument
+ * errors return ICZ_ERR_INVALID before any device work, in the order K, n_img, null arrays, null handle.  No atomics and fixed
+ * summation orders: two runs give the same bits.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* icz_ciderd_cook_host on the device, against the handle's df table: one workgroup per candidate; entries in the scorer's
+ * dict-insertion order (order k = 1..4, first occurrence ascending), weight = (double)tf * idf, norms = sqrt of the squares summed
+ * in that order, length = number of bigrams -- bit for bit what icz_ciderd_cook_host writes for the same tokens.  The entries are
+ * PACKED: candidate c owns ent_ptr_out[c] .. ent_ptr_out[c+1] with ent_ptr_out[0] = 0 (a counting pass and a prefix sum over the
+ * candidates run in front of the writing pass); the three entry arrays must hold the worst case of 240 entries per candidate
+ * (ent_key_out [n_cand*240, 4], ent_order_out / ent_w_out [n_cand*240]), ent_ptr_out [n_cand+1], norm_out [n_cand, 4], len_out [n_cand]. */
+int icz_ciderd_cook_device(icz_ciderd_t* h, const int32_t* tok, const int32_t* ptr, int32_t n_cand, int32_t* ent_key_out,
+                           int32_t* ent_order_out, double* ent_w_out, int32_t* ent_ptr_out, double* norm_out, int32_t* len_out, void* stream);
+/* CIDEr-D of every candidate with its siblings as references, K = 2..8: the n_img K candidates are cooked once on the device, then
+ * the matching loop of the reward kernel runs hypothesis a against the cooked candidates of its image.
+ *   pair_out [n_img, K, K] float64: [i][a][b] = CIDEr-D of a with b as its only reference (sim() of ciderD_scorer.py:155-183, mean over
+ *     n, * 10), diagonal included; not symmetric (the clipping min(vh, vr) * vr is not).
+ *   consensus_out [n_img, K] float64 or NULL: CIDEr-D of a with the OTHER K - 1 candidates as its reference set in the scorer's order
+ *     (per-order sums over b ascending, b != a; mean over n; / (K - 1); * 10).
+ *   best_out [n_img] int32 or NULL: the a with the largest consensus, ties to the lowest a.
+ * workspace: icz_ciderd_pairwise_workspace_bytes(n_img, K) bytes of device memory, 8-byte aligned (0 = bad arguments). */
+size_t icz_ciderd_pairwise_workspace_bytes(int32_t n_img, int32_t K);
+int icz_ciderd_pairwise(icz_ciderd_t* h, const int32_t* tok, const int32_t* ptr, int32_t n_img, int32_t K, double* pair_out,
+                        double* consensus_out, int32_t* best_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The CSR candidates against the reference STORE (arrays and img_slot [n_img] as icz_ciderd_reward_loo), K = 1..8:
+ * scores_out [n_img K] float64 = CIDEr-D of candidate img * K + k against the references of image img -- the reward kernel with
+ * a CSR hypothesis source instead of the int64 rows and their length rules. */
+int icz_ciderd_scores_csr(icz_ciderd_t* h, const int32_t* tok, const int32_t* ptr, int32_t n_img, int32_t K, const int32_t* img_slot,
+                          const int32_t* img_ref_ptr, const int32_t* ref_ent_ptr, const int32_t* ent_key, const int32_t* ent_order,
+                          const double* ent_w, const double* ref_norm, const int32_t* ref_len, double* scores_out, void* stream);
+/* counts_out [n_img, 4, 2] int32: for n = 1..4 {distinct n-grams over the image's K candidates, n-gram positions over them}
+ * (n-grams do not cross candidates), K = 1..8.  One workgroup per image, the set in LDS. */
+int icz_ngram_diversity(const int32_t* tok, const int32_t* ptr, int32_t n_img, int32_t K, int32_t* counts_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * BLEU and ROUGE-L of the evaluation report (COCO_Eval_Utils.py:15-35 -> coco_caption/pycocoevalcap/eval.py:24-69): the
  * integer statistics on the device, the float64 scores on the host in the reference's order (coco_eval.py Bleu / Rouge).
  * All arrays are int32 DEVICE arrays of corpus-local token ids >= 0 in CSR form: hypothesis i = hyp_tok[hyp_ptr[i] ..

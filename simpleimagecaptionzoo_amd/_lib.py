@@ -208,6 +208,11 @@ def lib():
         "icz_ciderd_cook_text": (C.c_int, [vp, vp, vp, i64, C.c_double, C.c_char_p, i64, i32, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]),
         "icz_ciderd_reward_indexed": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "icz_ciderd_reward_loo": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_ciderd_cook_device": (C.c_int, [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_ciderd_pairwise_workspace_bytes": (C.c_size_t, [i32, i32]),
+        "icz_ciderd_pairwise": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]),
+        "icz_ciderd_scores_csr": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_ngram_diversity": (C.c_int, [vp, vp, i32, i32, vp, vp]),
         "icz_bleu_stats": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp]),
         "icz_rouge_lcs": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp]),
         "icz_prof_begin": (C.c_int, []),

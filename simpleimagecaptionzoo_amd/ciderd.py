@@ -446,6 +446,63 @@ class CiderDReward:
                                           stream_ptr()))
         return (reward, scores) if return_scores else reward
 
+    # ---- caption sets (include/icz.h "Caption sets"; packing and the host-side metrics: caption_sets.py) ----------------------
+    def _set_dims(self, cands, K, lo, what):
+        K = int(K)
+        if K < lo or K > 8:
+            raise IczError("%s: K=%d candidates per image outside %d..8" % (what, K, lo))
+        n_cand = int(cands.ptr.numel()) - 1
+        if n_cand <= 0 or n_cand % K:
+            raise IczError("%s: %d candidates are not a positive multiple of K=%d" % (what, n_cand, K))
+        if cands.tok.device != self.device or cands.tok.dtype != torch.int32 or cands.ptr.dtype != torch.int32:
+            raise IczError("%s: the candidates must be int32 CSR tensors on %s" % (what, self.device))
+        return K, n_cand // K
+
+    def _set_out(self, key, make):
+        if not self.persistent:
+            return make()
+        if key not in self._out:
+            self._out[key] = make()
+        return self._out[key]
+
+    def pairwise(self, cands, K):
+        """Beyond the reference: CIDEr-D of every candidate of a caption set against its siblings (icz_ciderd_pairwise).  cands:
+        caption_sets.CandidateSet (int32 CSR tensors .tok / .ptr on this device, candidate img * K + k), K = 2..8 ->
+        (pair [n_img, K, K] float64, consensus [n_img, K] float64, best [n_img] int32) on the device: pair[i][a][b] = CIDEr-D of a
+        with b as its only reference, consensus[i][a] = CIDEr-D of a with the other K - 1 candidates as its references, best[i] =
+        the candidate with the largest consensus (ties: the lowest).  The candidates are cooked on the device against this
+        scorer's df table.  With `persistent` the outputs keep their addresses (overwritten by the next call of the same shape)."""
+        K, n_img = self._set_dims(cands, K, 2, "pairwise")
+        dev = self.device
+        need = int(lib().icz_ciderd_pairwise_workspace_bytes(n_img, K))
+        ws = getattr(self, "_pair_ws", None)
+        if ws is None or ws.numel() < need:
+            # grown outside any launch; the caching allocator orders the old block's reuse behind the work queued on its stream
+            ws = self._pair_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws.record_stream(torch.cuda.current_stream(dev))
+        pair, cons, best = self._set_out(("pair", n_img, K), lambda: (torch.empty(n_img, K, K, dtype=torch.float64, device=dev),
+                                                                       torch.empty(n_img, K, dtype=torch.float64, device=dev),
+                                                                       torch.empty(n_img, dtype=torch.int32, device=dev)))
+        check(lib().icz_ciderd_pairwise(self._h, ptr(cands.tok), ptr(cands.ptr), n_img, K, ptr(pair), ptr(cons), ptr(best), ptr(ws),
+                                        ws.numel(), stream_ptr()))
+        return pair, cons, best
+
+    def scores_csr(self, cands, K, ground_truth, img_ids):
+        """CIDEr-D of the candidates of a caption set against the references of their images (icz_ciderd_scores_csr): cands as for
+        `pairwise`, K = 1..8, img_ids / ground_truth the n_img images as for `reward_loo` -> scores [n_img, K] float64 on the
+        device.  Every token of a candidate counts as a word: there are no length rules as for the int64 rows of `reward`."""
+        K, n_img = self._set_dims(cands, K, 1, "scores_csr")
+        img_ids = list(img_ids)
+        if len(img_ids) != n_img:
+            raise IczError("scores_csr: %d image ids for %d images" % (len(img_ids), n_img))
+        idx = self._slots(img_ids, ground_truth)
+        st = self._st
+        scores = self._set_out(("csr", n_img, K), lambda: torch.empty(n_img, K, dtype=torch.float64, device=self.device))
+        check(lib().icz_ciderd_scores_csr(self._h, ptr(cands.tok), ptr(cands.ptr), n_img, K, ptr(idx), ptr(st["irp"]), ptr(st["rep"]),
+                                          ptr(st["key"]), ptr(st["ord"]), ptr(st["w"]), ptr(st["norm"]), ptr(st["len"]), ptr(scores),
+                                          stream_ptr()))
+        return scores
+
 
 def loo_baseline_reward(scores, n):
     """Host restatement of icz_ciderd_reward_loo's arithmetic (tests): scores (B n,) float64 -> float32 (B n,) rewards

@@ -619,6 +619,87 @@ class BUTDDetection_Eng(Engine):
             result.append({"image_id": image_id, "caption": " ".join(words), "score": score})
         return result
 
+    # ---- caption sets: consensus reranking and the set report (an extension; caption_sets.py, include/icz.h "Caption sets") -------
+    def _pack_set(self, entries, samples_per_image):
+        from . import caption_sets as cs
+        ids, caps = cs.group_entries(entries, samples_per_image)
+        word2ix = self.caption_vocab.word2ix
+        for grp in caps:                       # every ValueError before any device work: pack_candidates raises the same ones
+            for cap in grp:
+                words = cap.split()
+                if len(words) > cs.MAX_TOKENS:
+                    raise ValueError("caption with %d words: the device scorer handles at most %d" % (len(words), cs.MAX_TOKENS))
+                for w in words:
+                    if w not in word2ix:
+                        raise ValueError("word %r is not in the vocabulary" % (w,))
+        if self._cider_df is None and self._scorer is None:
+            raise ValueError("caption sets are scored with CIDEr-D: the engine needs cider_df (the document-frequency table)")
+        return ids, caps, lambda: cs.pack_candidates(caps, word2ix, self.device)
+
+    def rerank_captions_json(self, entries, samples_per_image):
+        """Consensus (minimum-Bayes-risk) reranking of a caption set: entries = the output of sample_captions_json_generation, or any
+        list of {"image_id", "caption"[, "score"]} with samples_per_image (2..8) consecutive entries per image.  Of every image the
+        caption that agrees most with its siblings is kept: the one with the largest CIDEr-D against the other samples_per_image - 1
+        captions as references (on the scorer's df table; ties: the first).  Returns one {"image_id", "caption", "score",
+        "consensus"} per image in entry order -- "score" is the kept entry's own (None without one) -- which
+        coco_eval.evaluate_captions takes as it is.  Bad arguments raise ValueError before any device work."""
+        ids, caps, pack = self._pack_set(entries, samples_per_image)
+        entries = list(entries)
+        K = int(samples_per_image)
+        with _on_stream(self):
+            _, cons, best = self.scorer().pairwise(pack(), K)
+            cons, best = cons.cpu().numpy(), best.cpu().numpy()
+        out = []
+        for i, image_id in enumerate(ids):
+            e = entries[i * K + int(best[i])]
+            out.append({"image_id": image_id, "caption": e["caption"], "score": e.get("score"), "consensus": float(cons[i, best[i]])})
+        return out
+
+    def consensus_captions_json_generation(self, dataloader, samples_per_image=5, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                                           tqdm_visible=True):
+        """sample_captions_json_generation (same arguments, samples_per_image 2..8) followed by rerank_captions_json: one consensus
+        caption per image."""
+        from .caption_sets import check_k
+        check_k(samples_per_image, 2)
+        if self._cider_df is None and self._scorer is None:
+            raise ValueError("caption sets are scored with CIDEr-D: the engine needs cider_df (the document-frequency table)")
+        entries = self.sample_captions_json_generation(dataloader, samples_per_image, temperature, top_k, top_p, seed, tqdm_visible)
+        return self.rerank_captions_json(entries, samples_per_image)
+
+    def caption_set_report(self, entries, samples_per_image, gts):
+        """The report of a caption set in the style of self-critical.pytorch's eval_multi.  entries as for rerank_captions_json,
+        gts = {image id: [reference strings]} holding every image of the entries.  Returns
+          oracle_CIDErD / mean_CIDErD / picked_CIDErD  mean over the images of the best / the mean / the consensus pick's CIDEr-D against
+                                           the references, on the scorer's df table -- the SCST reward's scale, not the corpus CIDEr
+                                           of coco_eval;
+          Div_1, Div_2                     distinct n-grams / total words of an image's set (caption_sets.div_n);
+          mBleu_1 .. mBleu_4               corpus BLEU of every caption against its siblings (caption_sets.mbleu);
+          pairwise_CIDErD                  mean off-diagonal CIDEr-D between an image's captions (caption_sets.mean_pairwise).
+        Bad arguments raise ValueError before any device work."""
+        from . import caption_sets as cs
+        ids, caps, pack = self._pack_set(entries, samples_per_image)
+        if not hasattr(gts, "__getitem__") or not hasattr(gts, "__contains__"):
+            raise ValueError("gts must map image ids to lists of reference strings")
+        for i in ids:
+            if i not in gts or len(gts[i]) == 0:
+                raise ValueError("image %r has no references in gts" % (i,))
+        K = int(samples_per_image)
+        with _on_stream(self):
+            cands = pack()
+            scorer = self.scorer()
+            pair, _, best = scorer.pairwise(cands, K)
+            pair, best = pair.cpu().numpy(), best.cpu().numpy().astype(np.int64)
+            scores = scorer.scores_csr(cands, K, gts, ids).cpu().numpy()
+            counts = cs.ngram_counts(cands)
+            mb = cs.mbleu(cands)
+        rep = {"oracle_CIDErD": float(np.mean(scores.max(axis=1))), "mean_CIDErD": float(np.mean(scores)),
+               "picked_CIDErD": float(np.mean(scores[np.arange(len(ids)), best])),
+               "Div_1": cs.div_n(counts, 1), "Div_2": cs.div_n(counts, 2)}
+        for k in range(4):
+            rep["mBleu_%d" % (k + 1)] = mb[k]
+        rep["pairwise_CIDErD"] = cs.mean_pairwise(pair)
+        return rep
+
 
 class AoADetection_Eng(BUTDDetection_Eng):
     """ModelEngines/AoA_Engine.py (same visual-input handling as the BUTD engine) + the three hot Engine methods.
