@@ -725,6 +725,7 @@ __global__ __launch_bounds__(256) void embed_argmax_kernel(const float* __restri
     float best = part_val[row * P];
     int bi = part_idx[row * P];
     for (int p = 1; p < P; ++p) argmax_combine(best, bi, part_val[row * P + p], part_idx[row * P + p]);
+    if (bi == 0x7fffffff) bi = 0;       // a row of NaN / -inf logits never updates bi (greedy_select_kernel has the same rule): <pad>, not a wild read
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         it_next[row] = bi;
         if (ids_out) ids_out[(size_t)row * ids_stride + t] = bi;

@@ -1,7 +1,11 @@
 // Host-side machinery shared by the BUTD, AoA and NIC decoder handles: device allocations, the hipGraph cache, side
 // streams, the caption loss head (teacher-forced XE input, packed logits, XE / REINFORCE losses), the decoder seams (DecodeMember)
 // with the drivers that run on them (beam search: beam.hip, sampling: sample_decode.hip) and the greedy select tail.
-// Each rule below ("free => clear graphs", "zero-fill then sync") has this one owner.
+// Each rule below ("free => clear graphs", "zero-fill then sync", "sync => destroy a graph") has this one owner.
+// Destroying a captured graph: a replay of it may still be in flight on the caller's stream, so whoever destroys one synchronises the
+// device first -- GraphCache::run before it evicts (rare: only a working set above the capacity evicts), and the callers of
+// GraphCache::clear (DeviceBuffers::release_training, the rebind and option paths of the handles) before they clear; a handle's
+// destruction (icz_*_destroy right behind a call) through ~GraphCache, which synchronises itself when it still holds a graph.
 #pragma once
 #include <functional>
 #include <vector>
@@ -24,10 +28,12 @@ struct GraphCache {
     GraphCache(const GraphCache&) = delete;
     GraphCache& operator=(const GraphCache&) = delete;
     ~GraphCache() {
+        if (!graphs.empty()) (void)hipDeviceSynchronize();      // the handle is destroyed: a replay may still be in flight
         clear();
         if (cap_st) (void)hipStreamDestroy(cap_st);
     }
     void clear() {                    // captured kernel arguments hold parameter / buffer addresses: drop them when those change
+                                      // (the caller has synchronised, ~GraphCache included: see the rule at the top of this file)
         for (auto& e : graphs) (void)hipGraphExecDestroy(e.exec);
         graphs.clear();
     }
@@ -54,9 +60,15 @@ struct GraphCache {
         hipError_t ie = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (ie != hipSuccess) { set_error("hipGraphInstantiate failed: %s", hipGetErrorString(ie)); return ICZ_ERR_HIP; }
-        if (graphs.size() >= capacity) {      // evict the least recently used entry
+        if (graphs.size() >= capacity) {      // evict the least recently used entry, once no replay of it can still be in flight
             size_t lru = 0;
             for (size_t i = 1; i < graphs.size(); ++i) if (graphs[i].last_use < graphs[lru].last_use) lru = i;
+            const hipError_t se = hipDeviceSynchronize();
+            if (se != hipSuccess) {
+                (void)hipGraphExecDestroy(exec);
+                set_error("hipDeviceSynchronize failed before a graph eviction: %s", hipGetErrorString(se));
+                return ICZ_ERR_HIP;
+            }
             (void)hipGraphExecDestroy(graphs[lru].exec);
             graphs.erase(graphs.begin() + lru);
         }
