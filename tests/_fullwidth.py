@@ -110,24 +110,16 @@ def attention_kink_units(feats64, p64, h1_steps, att_masks, tol=3e-6, active_row
     return hit.numpy()
 
 
-def _butd_scst_case(B, T, seed, sharpen=6.0, options=None, with_reward=False, dims=FULL_DIMS, samples_per_image=1):
-    """device rollouts + REINFORCE gradients of B rows x T steps at full width (or at the widths `dims` = (R, D, H, E, A, V)), and the
-    fp32 / float64 oracle passes on the same inputs (options: {handle option: value} set before the run).  samples_per_image = K > 1:
-    the B rows are K sampled captions of each of B / K images (sample_n; the greedy decode of the images runs beside it).
-    with_reward: the step's CIDEr-D reward as well -- computed on the device from the ids the device produced, bit-exact against the oracle's (Utils.py:319-367) -- and used as the REINFORCE reward (plus a per-row
-    signal: a random-init model scores ~0 against random references)"""
-    from oracle import butd as ob
-    from simpleimagecaptionzoo_amd.butd import ButdHandle, make_rng
+def _butd_scst_inputs(B, T, seed, sharpen=6.0, dims=FULL_DIMS, samples_per_image=1, device="cuda"):
+    """the inputs of _butd_scst_case (every value comes from CPU generators, so the oracle alone can run on them without a GPU):
+    (params on `device`, image features [B / K, R, D], features per decoder row [B, R, D], keep-masks em / am / om, uniforms u [T, B],
+    the RandomState behind them)"""
     from simpleimagecaptionzoo_amd.synth import random_butd_params
     R, D, H, E, A, V = dims
     K = samples_per_image
     assert B % K == 0
-    params = random_butd_params(R, D, H, E, A, V, "cuda", seed=seed)
+    params = random_butd_params(R, D, H, E, A, V, device, seed=seed)
     params["predict.weight_g"].mul_(sharpen)
-    h = ButdHandle(R, D, H, E, A, V, max(B, 8), T)
-    h.bind(params)
-    for name, value in (options or {}).items():
-        h.set_option(name, value)
     g = torch.Generator(device="cpu")
     g.manual_seed(1000 + seed)
     img_feats = torch.relu(torch.randn(B // K, R, D, generator=g))
@@ -135,15 +127,13 @@ def _butd_scst_case(B, T, seed, sharpen=6.0, options=None, with_reward=False, di
     rs = np.random.RandomState(seed)
     em, am, om = rs.rand(T, B, E) < 0.5, rs.rand(T, B, R, A) < 0.5, rs.rand(T, B, H) < 0.5
     u = rs.rand(T, B).astype(np.float32)
-    dev = "cuda"
-    rng = make_rng(0, torch.tensor(u, device=dev), torch.tensor(em.astype(np.uint8), device=dev),
-                   torch.tensor(am.astype(np.uint8), device=dev), torch.tensor(om.astype(np.uint8), device=dev))
-    if K > 1:
-        greedy = h.greedy(img_feats.cuda(), T).clone()
-        seq, lp = h.sample_n(img_feats.cuda(), K, T, rng)
-    else:
-        greedy, seq, lp = h.rollouts(feats_c.cuda(), T, rng)
-    greedy, seq, lp = greedy.cpu().numpy(), seq.cpu().numpy(), lp.cpu().numpy()
+    return params, img_feats, feats_c, em, am, om, u, rs
+
+
+def _butd_scst_oracle(params, img_feats, feats_c, em, am, om, u, T):
+    """the fp32 and the float64 oracle pass of _butd_scst_case: ({"f32" / "f64": (params, seq, log-probs, logits, trace)}, greedy ids
+    and greedy logits of the fp32 pass)"""
+    from oracle import butd as ob
     out = {}
     for name, dt in (("f32", torch.float32), ("f64", torch.float64)):
         torch.set_default_dtype(dt)
@@ -157,11 +147,43 @@ def _butd_scst_case(B, T, seed, sharpen=6.0, options=None, with_reward=False, di
     p32 = out["f32"][0]
     with torch.no_grad():
         w_greedy, _, w_glog = ob.greedy(img_feats, {k: v.detach() for k, v in p32.items()}, T, hoisted=True)
+    return out, w_greedy, w_glog
+
+
+def _butd_scst_case(B, T, seed, sharpen=6.0, options=None, with_reward=False, dims=FULL_DIMS, samples_per_image=1, excused=None):
+    """device rollouts + REINFORCE gradients of B rows x T steps at full width (or at the widths `dims` = (R, D, H, E, A, V)), and the
+    fp32 / float64 oracle passes on the same inputs (options: {handle option: value} set before the run).  samples_per_image = K > 1:
+    the B rows are K sampled captions of each of B / K images (sample_n; the greedy decode of the images runs beside it).
+    with_reward: the step's CIDEr-D reward as well -- computed on the device from the ids the device produced, bit-exact against the oracle's (Utils.py:319-367) -- and used as the REINFORCE reward (plus a per-row
+    signal: a random-init model scores ~0 against random references).  excused: a dict that receives the number of excused greedy rows,
+    of excused sampled rows and of rows left out of the gradient comparison."""
+    from oracle import butd as ob
+    from simpleimagecaptionzoo_amd.butd import ButdHandle, make_rng
+    R, D, H, E, A, V = dims
+    K = samples_per_image
+    params, img_feats, feats_c, em, am, om, u, rs = _butd_scst_inputs(B, T, seed, sharpen, dims, K)
+    h = ButdHandle(R, D, H, E, A, V, max(B, 8), T)
+    h.bind(params)
+    for name, value in (options or {}).items():
+        h.set_option(name, value)
+    dev = "cuda"
+    rng = make_rng(0, torch.tensor(u, device=dev), torch.tensor(em.astype(np.uint8), device=dev),
+                   torch.tensor(am.astype(np.uint8), device=dev), torch.tensor(om.astype(np.uint8), device=dev))
+    if K > 1:
+        greedy = h.greedy(img_feats.cuda(), T).clone()
+        seq, lp = h.sample_n(img_feats.cuda(), K, T, rng)
+    else:
+        greedy, seq, lp = h.rollouts(feats_c.cuda(), T, rng)
+    greedy, seq, lp = greedy.cpu().numpy(), seq.cpu().numpy(), lp.cpu().numpy()
+    out, w_greedy, w_glog = _butd_scst_oracle(params, img_feats, feats_c, em, am, om, u, T)
     limit = max(1, B // 32)
-    _excuse_greedy(greedy, w_greedy, w_glog, limit)
+    ex_greedy = _excuse_greedy(greedy, w_greedy, w_glog, limit)
     ok = _excuse_sampled(seq, out["f32"][1], out["f32"][3], u, limit)
+    ex_sampled = int((~ok).sum())
     ok &= (out["f64"][1].numpy() == seq).all(1)         # rows whose float64 draws agree as well take part in the gradient comparison
     assert ok.sum() >= B - 2 * limit
+    if excused is not None:
+        excused.update(greedy=len(ex_greedy), sampled=ex_sampled, left_out=int((~ok).sum()))
     np.testing.assert_allclose(lp[ok], out["f32"][2].detach().numpy()[ok], atol=1e-4)
     rw = (rs.randn(B, 1).astype(np.float32) * ok[:, None].astype(np.float32)).repeat(T, 1)
     if with_reward:
@@ -235,10 +257,11 @@ def _sharp_params(seed):
     return params
 
 
-def _end_biased_params(seed, p_end, B=64):
-    """full-width parameters whose <end> logit is raised until a sampled step draws <end> with probability ~ p_end"""
+def _end_biased_params(seed, p_end, B=64, dims=FULL_DIMS):
+    """full-width parameters (or at `dims`) whose <end> logit is raised until a sampled step draws <end> with probability ~ p_end"""
     from simpleimagecaptionzoo_amd.butd import ButdHandle, make_rng
     from simpleimagecaptionzoo_amd.synth import random_butd_params
+    R, D, H, E, A, V = dims
     params = random_butd_params(R, D, H, E, A, V, "cuda", seed=seed)
     h = ButdHandle(R, D, H, E, A, V, B, 20)
     h.bind(params)
@@ -381,10 +404,111 @@ def midwidth_routes(name):
     raise KeyError(name)
 
 
-def _ragged_captions(B, V_, seed):
-    """B captions of 5 .. 14 tokens, sorted by length (descending): (captions [B, L] int64, lengths)"""
+# ---- BUTD attention at any region count and attention width ------------------------------------------------------------------------
+# One table for the GPU tests (tests/test_gpu_butd_attention.py) and the CPU test of the table itself (tests/test_cpu_attention_geometry.py):
+# name -> (dims = (R, D, H, E, A, V), what the shape is there for).  The nine attention kernels of csrc/butd_kernels.h branch on R, D and
+# A alone (H, E and V are kept small); `att_geometry_claims` states each purpose as a predicate on those numbers and on the kernels'
+# constants below.  Every case runs ATT_ROWS rows x ATT_STEPS steps: more steps than att_bwd_denc_kernel<TT> keeps in registers, so
+# d enc_ctx is re-read and re-written by a second time pass.
+ATT_PARTS, TT, ATT_CTX_MAX_G = 4, 20, 8          # csrc/butd_impl.h, the <20> of csrc/butd_train.hip, csrc/butd_kernels.h
+ATT_NB, ATT_GROUP_LDS = 3, 60 * 1024             # regions per wave and pass of att_scores_kernel; Butd::step's limit for the grouped scores
+ATT_ROWS, ATT_STEPS = 12, 24
+ATT_GEOMETRY = {
+    "g_r1": ((1, 64, 32, 32, 32, 53),
+             "one region: alpha = 1 and ds = 0 exactly; the empty upper half of att_ctx_kernel (r_lo == r_hi)"),
+    "g_r2": ((2, 36, 32, 16, 20, 53),
+             "Rh = 1: one region per half; A = 20, less than one 32-bit keep word; D = 36, one partly filled column part"),
+    "g_r17": ((17, 512, 64, 32, 1280, 203),
+              "A > 1024: the second c0 pass of the scores and d enc_ctx kernels (the scores kernel's prefetch serves the first only); "
+              "A % 256 == 0: shared Philox words in all three kernels; R = the 16 (part, wave) slots + 1"),
+    "g_r33": ((33, 128, 128, 64, 128, 1237),
+              "A % 128 == 0 but A % 256 != 0: scores and d dec_ctx draw per element, d enc_ctx on shared words; odd R"),
+    "g_r63": ((63, 1028, 64, 64, 256, 203),
+              "R > 48: the second region group of att_scores_kernel; one softmax lane of -inf; D % 512 == 4: a column part of one float4; "
+              "the smallest width with shared words in scores and d dec_ctx"),
+    "g_r64": ((64, 516, 64, 36, 132, 203),
+              "a full wave of regions (no -inf lane); A % 128 != 0: no shared words anywhere, the clamped tail loads"),
+    "g_a2304": ((36, 256, 64, 32, 2304, 203),
+                "beam 8: 4 A 8 bytes of dec_ctx rows exceed the grouped scores kernel's LDS limit (and the 64 KB a launch may ask for without "
+                "an opt-in: without the limit the launch is refused), so scores go per row while the context stays grouped; beam 5: both "
+                "grouped; a third c0 pass"),
+}
+# XE cases (captions of 22..30 tokens): seeds at which no kept attention pre-activation lies within fp32 rounding of zero in float64
+# (relu_band_count; tests/test_cpu_attention_geometry.py).  Such an element switching its relu moves the embedding rows of the one or two
+# tokens that caption was fed beyond check_grads_against_float64 (g_r17 at seed 793: z[22, 0, 0, 727] = -2.9e-8; switched on in float64 it
+# moves rows 93 and 58 by 7.17e-4 and 3.2e-4 of the maximum, the device's figures).  g_a2304 has 29 million pre-activations per pass and
+# always a few in that band; there the 203 embedding rows get the rule's own judgement.
+ATT_XE_SEEDS = {"g_r1": 751, "g_r2": 752, "g_r17": 816, "g_r33": 754, "g_r63": 783, "g_r64": 786, "g_a2304": 827}
+ATT_XE_LENGTHS = (22, 30)
+ATT_SEEDS = {"g_r1": 701, "g_r2": 702, "g_r17": 743, "g_r33": 704, "g_r63": 715, "g_r64": 736, "g_a2304": 777}
+
+
+def att_branches(dims, steps=ATT_STEPS):
+    """{branch condition of the attention kernels: bool} for dims = (R, D, H, E, A, V) -- the conditions the code of csrc/butd_kernels.h,
+    Butd::step and Butd::bptt decides on, written out on the host"""
+    R_, D_, _, _, A_, _ = dims
+    slots = ATT_PARTS * 4                             # (part, wave) pairs of att_scores_kernel's grid
+    return {"scores: a wave holds more than one region": R_ > slots,
+            "scores: second group of regions (R > parts x waves x NB)": R_ > slots * ATT_NB,
+            "ctx: odd R, the halves (R + 1) / 2 and R / 2 differ": R_ % 2 == 1,
+            "ctx: empty upper half": R_ - (R_ + 1) // 2 == 0,
+            "softmax: lanes >= R padded with -inf": R_ < 64,
+            "scores / denc: second 1024-column pass": A_ > 1024,
+            "loads clamped with min(c, A - 4)": A_ % 256 != 0,
+            "ctx / dalpha: more than one 512-column part of D": D_ > 512,
+            "ctx / dalpha: last column part partly filled": D_ % 512 != 0,
+            "denc: second time pass (T > TT)": steps > TT,
+            "grouped scores dropped at beam 8, grouped context kept": 4 * A_ * ATT_CTX_MAX_G > ATT_GROUP_LDS,
+            "Philox words shared in scores and ddec (A % 256 == 0)": A_ % 256 == 0,
+            "Philox words shared in denc (A % 128 == 0)": A_ % 128 == 0}
+
+
+def att_geometry_claims(name):
+    """{claim: bool} -- what ATT_GEOMETRY[name] is there for, as predicates on its numbers and on ATT_PARTS, TT, ATT_CTX_MAX_G"""
+    (R_, D_, H_, E_, A_, V_), _ = ATT_GEOMETRY[name]
+    Rh = (R_ + 1) // 2
+    slots = ATT_PARTS * 4
+    base = {"accepted by icz_butd_create": 1 <= R_ <= 64 and all(x % 4 == 0 for x in (D_, H_, E_, A_)) and V_ > 3,
+            "two time passes of denc": TT < ATT_STEPS <= 2 * TT}
+    if name == "g_r1":
+        own = {"one region": R_ == 1, "upper half of att_ctx_kernel empty": Rh == R_}
+    elif name == "g_r2":
+        own = {"one region per half": Rh == 1 and R_ - Rh == 1,
+               "A below one 32-bit keep word": A_ < 32,
+               "one partly filled column part": D_ < 512}
+    elif name == "g_r17":
+        own = {"second c0 pass, shorter than the first": 1024 < A_ < 2048,
+               "shared words in scores, ddec and denc": A_ % 256 == 0,
+               "R = (part, wave) slots + 1": R_ == slots + 1}
+    elif name == "g_r33":
+        own = {"denc on shared words": A_ % 128 == 0,
+               "scores and ddec per element": A_ % 256 != 0,
+               "odd R": R_ % 2 == 1 and Rh != R_ - Rh}
+    elif name == "g_r63":
+        own = {"second region group of att_scores_kernel": R_ > slots * ATT_NB,
+               "one lane of -inf": 64 - R_ == 1,
+               "a column part of one float4": D_ % 512 == 4,
+               "smallest width with shared words in scores and ddec": A_ == 256}
+    elif name == "g_r64":
+        own = {"a full wave of regions": R_ == 64,
+               "no shared words": A_ % 128 != 0,
+               "clamped tail loads inside the first 256-column strip": A_ % 256 != 0 and A_ < 256,
+               "a column part of one float4": D_ % 512 == 4}
+    elif name == "g_a2304":
+        own = {"beam 8: scores per row": 4 * A_ * 8 > ATT_GROUP_LDS,
+               "beam 8: the grouped request would be above the 64 KB of a launch without opt-in": 4 * A_ * 8 > 64 * 1024,
+               "beam 8: context grouped": 8 <= ATT_CTX_MAX_G,
+               "beam 5: both grouped": 4 * A_ * 5 <= ATT_GROUP_LDS,
+               "a third c0 pass": A_ > 2048 and A_ % 256 == 0}
+    else:
+        raise KeyError(name)
+    return dict(base, **own)
+
+
+def _ragged_captions(B, V_, seed, length_range=(5, 14)):
+    """B captions of 5 .. 14 tokens (or of length_range = (shortest, longest)), sorted by length (descending): (captions [B, L] int64, lengths)"""
     rs = np.random.RandomState(seed)
-    lengths = sorted(rs.randint(5, 15, size=B).tolist(), reverse=True)
+    lengths = sorted(rs.randint(length_range[0], length_range[1] + 1, size=B).tolist(), reverse=True)
     caps = torch.zeros(B, max(lengths) + 1, dtype=torch.int64)
     for b, n in enumerate(lengths):
         caps[b, 0] = 1
@@ -393,33 +517,66 @@ def _ragged_captions(B, V_, seed):
     return caps, lengths
 
 
-def _butd_xe_case(dims, B, seed, via="loss", options=None):
+def _butd_xe_inputs(dims, B, seed, train=False, length_range=(5, 14), device="cuda"):
+    """the inputs of _butd_xe_case, every value from CPU generators: (params on `device`, features, captions, lengths, the upstream
+    gradient G of via = "dlogits", the keep-masks em / am / om [T, B, ...] of training mode or None)"""
+    from simpleimagecaptionzoo_amd.synth import random_butd_params
+    R_, D_, H_, E_, A_, V_ = dims
+    params = random_butd_params(R_, D_, H_, E_, A_, V_, device, seed=seed)
+    params["predict.weight_g"].mul_(6.0)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(2000 + seed)
+    feats = torch.relu(torch.randn(B, R_, D_, generator=g))
+    caps, lengths = _ragged_captions(B, V_, seed, length_range)
+    G = torch.randn(sum(lengths), V_, generator=g) / sum(lengths)
+    em = am = om = None
+    if train:
+        rs, T_ = np.random.RandomState(seed + 1), max(lengths)
+        em, am, om = rs.rand(T_, B, E_) < 0.5, rs.rand(T_, B, R_, A_) < 0.5, rs.rand(T_, B, H_) < 0.5
+    return params, feats, caps, lengths, G, em, am, om
+
+
+def relu_band_count(feats64, p64, h1_steps, att_masks, active_rows, tol=2e-7):
+    """how many kept attention pre-activations z[t, b, r, a] = enc_ctx + dec_ctx_t (float64) lie within `tol` x (|enc_ctx| + |dec_ctx| + 1)
+    of zero: two fp32 evaluations can disagree about the sign of such an element, and its relu switching moves EVERY gradient behind
+    step t of row b by a finite amount -- among them the embedding rows of the few tokens that row was fed, which no rule excuses"""
+    from oracle import butd as ob
+    n = 0
+    with torch.no_grad():
+        enc = feats64 @ ob.wn_weight(p64, "atten.enc_att").t() + p64["atten.enc_att.bias"]
+        w_dec, b_dec = ob.wn_weight(p64, "atten.dec_att"), p64["atten.dec_att.bias"]
+        for t, h1 in enumerate(h1_steps):
+            dec = (h1 @ w_dec.t() + b_dec).unsqueeze(1)
+            near = (enc + dec).abs() <= tol * (enc.abs() + dec.abs() + 1.0)
+            if att_masks is not None:
+                near &= torch.as_tensor(att_masks[t]).reshape(near.shape)
+            near[active_rows[t]:] = False
+            n += int(near.sum())
+    return n
+
+
+def _butd_xe_case(dims, B, seed, via="loss", options=None, train=False, length_range=(5, 14)):
     """Teacher-forced XE forward (evaluation mode, ragged caption lengths: the batch shrinks with t) + backward at the widths `dims`
     against the fp32 / float64 oracle: packed logits 2e-4 / 1e-4 (as the 49-region full-width test), loss 1e-4, every gradient under
     check_grads_against_float64.  via: "loss" = xe_backward with label smoothing 0.1; "callback" = the same with a gradient callback set
     (phases as separate calls, stages 0, 1, 2 in order); "dlogits" = xe_backward_dlogits for a random upstream gradient G, the oracle's
-    loss being sum(logits * G)."""
+    loss being sum(logits * G).  train: training mode with explicit embedding / attention / output keep-masks [T, B, ...], the same
+    masks in the oracle's forward_xe.  length_range: the shortest and the longest caption."""
     from oracle import butd as ob
-    from simpleimagecaptionzoo_amd.butd import ButdHandle
-    from simpleimagecaptionzoo_amd.synth import random_butd_params
+    from simpleimagecaptionzoo_amd.butd import ButdHandle, make_rng
     R_, D_, H_, E_, A_, V_ = dims
-    params = random_butd_params(R_, D_, H_, E_, A_, V_, "cuda", seed=seed)
-    params["predict.weight_g"].mul_(6.0)
+    params, feats, caps, lengths, G, em, am, om = _butd_xe_inputs(dims, B, seed, train, length_range)
     h = ButdHandle(R_, D_, H_, E_, A_, V_, B, 20)
     h.bind(params)
     for name, value in (options or {}).items():
         h.set_option(name, value)
-    g = torch.Generator(device="cpu")
-    g.manual_seed(2000 + seed)
-    feats = torch.relu(torch.randn(B, R_, D_, generator=g))
-    caps, lengths = _ragged_captions(B, V_, seed)
     order = ob.packed_order(lengths)
     tgt = torch.tensor([int(caps[b, t + 1]) for b, t in order])
-    G = torch.randn(len(order), V_, generator=g) / len(order)
     stages = []
     if via == "callback":
         h.set_grad_callback(stages.append)
-    logits = h.xe_forward(feats.cuda(), caps.cuda(), lengths, None, train=False, want_logits=True)
+    rng = make_rng(0, None, *(torch.tensor(m.astype(np.uint8), device="cuda") for m in (em, am, om))) if train else None
+    logits = h.xe_forward(feats.cuda(), caps.cuda(), lengths, rng, train=train, want_logits=True)
     grads = h.new_grads()
     if via == "dlogits":
         h.xe_backward_dlogits(G.cuda(), grads)
@@ -436,7 +593,7 @@ def _butd_xe_case(dims, B, seed, via="loss", options=None):
         try:
             p = {k: v.detach().cpu().to(dt).requires_grad_(True) for k, v in params.items()}
             trace = {}
-            w_logits = ob.forward_xe(feats.to(dt), caps, lengths, p, trace=trace)
+            w_logits = ob.forward_xe(feats.to(dt), caps, lengths, p, em, am, om, trace=trace)
             w_loss = (w_logits * G.to(dt)).sum() if via == "dlogits" else ob.label_smoothing_loss(w_logits, tgt, 0.1)
             w_loss.backward()
             gsets[name] = {k: v.grad.numpy() for k, v in p.items()}
@@ -448,7 +605,7 @@ def _butd_xe_case(dims, B, seed, via="loss", options=None):
                 trace64, p64 = trace, {k: v.detach() for k, v in p.items()}
         finally:
             torch.set_default_dtype(torch.float32)
-    kink = attention_kink_units(feats.double(), p64, trace64["h1"], None, active_rows=[sum(l > t for l in lengths) for t in range(max(lengths))])
+    kink = attention_kink_units(feats.double(), p64, trace64["h1"], am, active_rows=[sum(l > t for l in lengths) for t in range(max(lengths))])
     rep = check_grads_against_float64(grads, gsets["f32"], gsets["f64"], {"atten.enc_att": kink, "atten.dec_att": kink})
     h.close()
     return rep, kink

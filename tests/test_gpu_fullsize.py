@@ -226,28 +226,7 @@ def test_spatial_49_regions_butd_and_aoa_match_oracle():
     assert all(torch.isfinite(g).all() for g in grads.values())
 
 
-def _philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """numpy twin of csrc/rng.h (Philox4x32-10): uint32 arrays in, four uint32 arrays out."""
-    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), 0x9E3779B9, 0xBB67AE85
-    c = [np.asarray(x, dtype=np.uint64) for x in (c0, c1, c2, c3)]
-    k0, k1 = int(k0), int(k1)
-    for _ in range(10):
-        p0, p1 = M0 * c[0], M1 * c[2]
-        hi0, lo0, hi1, lo1 = p0 >> np.uint64(32), p0 & np.uint64(0xFFFFFFFF), p1 >> np.uint64(32), p1 & np.uint64(0xFFFFFFFF)
-        c = [hi1 ^ c[1] ^ np.uint64(k0), lo1, hi0 ^ c[3] ^ np.uint64(k1), lo0]
-        k0, k1 = (k0 + W0) & 0xFFFFFFFF, (k1 + W1) & 0xFFFFFFFF
-    return c
-
-
-def _keep_bits(seed, stream, step, n):
-    """keep flags of elements 0..n-1 of one dropout call: bit (idx & 31) of word (idx >> 5) & 3 of the Philox block idx >> 7."""
-    idx = np.arange(n, dtype=np.uint64)
-    g = idx >> np.uint64(7)
-    gu = np.unique(g)
-    r = _philox4x32_10(gu & np.uint64(0xFFFFFFFF), gu >> np.uint64(32), np.full(gu.shape, step), np.full(gu.shape, stream),
-                       seed & 0xFFFFFFFF, seed >> 32)
-    words = np.stack(r, 1)[g.astype(np.int64), ((idx >> np.uint64(5)) & np.uint64(3)).astype(np.int64)]
-    return ((words >> (idx & np.uint64(31))) & np.uint64(1)).astype(np.uint8)
+from _philox import _keep_bits, _philox4x32_10  # noqa: E402,F401  (moved to tests/_philox.py; importable from here as before)
 
 
 def test_fullsize_philox_masks_regenerated_in_backward_equal_the_forward_ones(full):
