@@ -406,7 +406,8 @@ int icz_aoa_set_scheduled_sampling(icz_aoa_t* h, float ss_prob, const float* gat
  *   which leaves a normalised row's selections unchanged); every option holds, the outputs are those of _diverse.
  * The ensemble does not own its members: they stay alive, bound and refreshed while it decodes; an AoA member's region counts are
  * those of its last icz_aoa_set_regions.  A decode runs each member's step on one stream, then the combine kernel; beam search
- * re-gathers every member's state.  Training and sampling from an ensemble are out of scope.
+ * re-gathers every member's state.  Training through an ensemble is out of scope; its sampling decode is declared below, behind
+ * icz_sample_opts.
  * Argument errors return ICZ_ERR_INVALID before any device work: create -- M outside 1..4, a null array, an unknown kind, a null
  * or repeated member, a bad weight, members of different V; decode -- the options (as _diverse, checked first), a null handle, null
  * features, an unrefreshed member, B (greedy) or n_img x beam (beam) above any member's row capacity.
@@ -468,6 +469,28 @@ int icz_nic_sample_decode(icz_nic_t* h, const float* features, int32_t n_img, in
 int icz_sample_filter_draw(const float* logits, const float* bias, int32_t nsplit, int32_t ld, int32_t rows, int32_t V,
                            const icz_sample_opts* opts, const float* uniforms, int64_t* tok_out, float* logp_out, uint8_t* keep_out,
                            void* stream);
+
+/* The sampling decode of a model ensemble: the rules above applied, per decoder row and step, to the combined row
+ *     x[v] = lp[v] = log( sum_m w_m softmax(logits_m)[v] )
+ * of icz_ensemble_logprob -- temperature divides lp, top-k and the nucleus are cut on it, logp_out is lp[token] - lse(lp) (lp is
+ * normalised up to rounding).  Row img * n + j is sample j of image img; every member runs its per-image work once per image and its
+ * step over all n_img n rows on the shared tokens; then one launch combines the members' logits (read as finished rows or split-K
+ * slabs, the combined row held in LDS only), filters, draws and writes every member's next input embedding.  The Philox uniforms
+ * are keyed by (seed, step, row) as in icz_*_sample_decode: a one-member ensemble and its member see the same uniforms.  feats: HOST
+ * array of M device pointers; every other argument as in icz_butd_sample_decode (uniforms [max_len, n_img n] or NULL).
+ * Argument errors return ICZ_ERR_INVALID before any device work, in this order: the options (as above, without the capacity), null
+ * arguments, null handle, n_img n above the smallest member's row capacity, null features of a member or a member not refreshed. */
+int icz_ensemble_sample_decode(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t n, int32_t max_len,
+                               const icz_sample_opts* opts, uint64_t seed, const float* uniforms, int64_t* ids_out, float* logp_out,
+                               float* score_out, void* stream);
+/* The ensemble instance of the filter-and-draw kernel on its own (tests), the counterpart of icz_sample_filter_draw and
+ * icz_ensemble_logprob: M = 1..4 members' logits as in icz_ensemble_logprob (host arrays of device pointers; bias may be NULL when
+ * every nsplit is 1), weights as in icz_ensemble_create; uniforms [rows]; tok_out [rows] int64; logp_out [rows] = lp[token] -
+ * lse(lp); keep_out [rows][V] (may be NULL) receives 1 for every token that survived the filters.  Errors: the options first, then M,
+ * null / bad arguments, the weights, each member's view. */
+int icz_ensemble_sample_filter_draw(int32_t M, const float* const* logits, const float* const* bias, const int32_t* nsplit,
+                                    const int32_t* ld, const float* weights, int32_t rows, int32_t V, const icz_sample_opts* opts,
+                                    const float* uniforms, int64_t* tok_out, float* logp_out, uint8_t* keep_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Optimiser step: clip_gradient (Utils.py:241-250, value clamp) + torch.optim.Adam(betas=(0.9,0.999),

@@ -188,6 +188,9 @@ def lib():
                                                        vp, vp]),
         "icz_ensemble_logprob": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32, vp, i32,
                                            vp, vp]),
+        "icz_ensemble_sample_decode": (C.c_int, [vp, C.POINTER(vp), i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
+        "icz_ensemble_sample_filter_draw": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32,
+                                                      C.POINTER(SampleOpts), vp, vp, vp, vp, vp]),
         "icz_sample_decode_check": (C.c_int, [C.POINTER(SampleOpts), i32, i32, i32, i32]),
         "icz_butd_sample_decode": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
         "icz_aoa_sample_decode": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),

@@ -1,53 +1,13 @@
 // Model ensembles (beyond the reference; self-critical.pytorch's AttEnsemble): M = 1..4 BUTD / AoA / NIC decoder handles of one
 // vocabulary decode together.  Every step each member runs its own step (DecodeMember, decoder_core.h) on the shared tokens, then
 // ensemble_logprob_kernel combines the members' logits into lp[v] = log(sum_m w_m softmax(logits_m)[v]): greedy takes its argmax in
-// the same launch, beam search hands the rows to the shared driver (beam_search, beam.hip) with every option it has.
+// the same launch, beam search hands the rows to the shared driver (beam_search, beam.hip) with every option it has, and the
+// sampling decode draws from lp in the ensemble instance of sample_decode_kernel (sample_decode.hip), which combines in its pass 1.
 #include <cmath>
 
-#include "decoder_core.h"
+#include "ens_sample.h"
 
 namespace icz {
-
-struct EnsArgs {
-    LogitsView m[ENS_MAX_M];
-    float logw[ENS_MAX_M];            // log of the normalised weights (-inf for a zero weight)
-    int M, V;
-};
-
-__device__ __forceinline__ bool ens_vec_ok(const LogitsView& l) {
-    return ((l.ld | (int)(l.slab_stride & 3)) & 3) == 0 && (((uintptr_t)l.p | (uintptr_t)l.bias) & 15) == 0;
-}
-
-// logits v .. v + 3 of `row` (v % 4 == 0), the slabs summed in slab order then the bias; columns >= V read as -inf
-__device__ __forceinline__ f32x4 ens_load4(const LogitsView& l, int row, int v, int V, bool vec) {
-    const float* r = l.p + (size_t)row * l.ld;
-    f32x4 x;
-    if (vec && v + 4 <= V) {
-        x = *reinterpret_cast<const f32x4*>(r + v);
-        for (int z = 1; z < l.ns; ++z) x += *reinterpret_cast<const f32x4*>(r + (size_t)z * l.slab_stride + v);
-        if (l.ns > 1) x += *reinterpret_cast<const f32x4*>(l.bias + v);
-        return x;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float y = -INFINITY;
-        if (v + j < V) {
-            y = r[v + j];
-            for (int z = 1; z < l.ns; ++z) y += r[(size_t)z * l.slab_stride + v + j];
-            if (l.ns > 1) y += l.bias[v + j];
-        }
-        x[j] = y;
-    }
-    return x;
-}
-
-// running (max, sum of exp(x - max)) pairs
-__device__ __forceinline__ void lse_combine(float& m, float& s, float om, float os) {
-    const float n = fmaxf(m, om);
-    if (n == -INFINITY) return;
-    s = s * expf(m - n) + os * expf(om - n);
-    m = n;
-}
 
 // One workgroup (four waves) per row.  Pass 1: lse_m of every member in one online max / sum-exp pass over its logits (read
 // straight from the member's finished row or its split-K slabs + bias).  Pass 2: lp[v] = log(sum_m w_m exp(x_m[v] - lse_m)), shifted
@@ -165,7 +125,9 @@ static void launch_combine(const EnsArgs& a, int rows, float* out, int ldo, int6
 }
 
 // ------------------------------------------------------------------------------------------------
-// The ensemble: owns the greedy loop's tokens `it`, its beam buffers and the combined rows lp [rows, Vp]; the members stay the caller's.
+// The ensemble: owns the greedy and sampling loops' tokens `it`, its beam buffers, the combined rows lp [rows, Vp] and the sampling
+// decode's finished flags, per-step counts of unfinished rows and image of each row; the members stay the caller's.
+constexpr int ENS_MAX_T = 256;        // steps of a sampling decode (the single-model driver's limit)
 struct Ensemble {
     int M = 0, V = 0, Vp = 0, cap = 0;
     DecodeMember* m[ENS_MAX_M] = {};
@@ -174,6 +136,9 @@ struct Ensemble {
     BeamBuf bm;
     int64_t* it = nullptr;
     float* lp = nullptr;
+    uint8_t* fin = nullptr;
+    int* n_unf = nullptr;
+    int32_t* img_of_row = nullptr;
 
     int init(const int32_t* kinds, void* const* members, const float* weights, int n);
     EnsArgs args(const LogitsView* lv) const {
@@ -183,6 +148,8 @@ struct Ensemble {
         return a;
     }
     int greedy(const float* const* feats, int B, int max_len, int64_t* ids_out, hipStream_t st);
+    int sample_decode(const char* who, const float* const* feats, int n_img, int n, int max_len, const icz_sample_opts* opts, uint64_t seed,
+                      const float* uniforms, int64_t* ids_out, float* logp_out, float* score_out, hipStream_t st);
 };
 
 int Ensemble::init(const int32_t* kinds, void* const* members, const float* weights, int n) {
@@ -209,6 +176,9 @@ int Ensemble::init(const int32_t* kinds, void* const* members, const float* weig
     Vp = pad_vocab(V);
     ICZ_TRY(mem.alloc((void**)&it, sizeof(int64_t) * cap));
     ICZ_TRY(mem.alloc((void**)&lp, sizeof(float) * (size_t)cap * Vp));
+    ICZ_TRY(mem.alloc((void**)&fin, cap));
+    ICZ_TRY(mem.alloc((void**)&n_unf, sizeof(int) * ENS_MAX_T));
+    ICZ_TRY(mem.alloc((void**)&img_of_row, sizeof(int32_t) * cap));
     return mem.synced();
 }
 
@@ -226,6 +196,47 @@ int Ensemble::greedy(const float* const* feats, int B, int max_len, int64_t* ids
         launch_combine(args(lv), B, nullptr, 0, it, ids_out, max_len, t, st);
         cur ^= 1;
     }
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+// The sampling decode (sample_decode(), sample_decode.hip, over M members): row img * n + j is sample j of image img; every member
+// runs its prologue once per image and its step over all rows on the shared tokens, then ONE launch of sample_decode_kernel's
+// ensemble instance combines the members' logits, filters, draws and writes every member's next input embedding.  The caller
+// (icz_ensemble_sample_decode) has checked the options and the null arguments.
+int Ensemble::sample_decode(const char* who, const float* const* feats, int n_img, int n, int max_len, const icz_sample_opts* opts,
+                            uint64_t seed, const float* uniforms, int64_t* ids_out, float* logp_out, float* score_out, hipStream_t st) {
+    ICZ_REQUIRE(n_img > 0 && max_len >= 1 && max_len <= ENS_MAX_T, "%s: n_img / max_len out of range", who);
+    ICZ_REQUIRE((long)n_img * n <= cap, "%s: %d images x %d samples exceed row capacity %d (the smallest member's)", who, n_img, n, cap);
+    const int rows = n_img * n;
+    ICZ_TRY(check_members(who, m, M, feats, rows));
+    launch_sample_decode_init(it, fin, img_of_row, rows, n, n_unf, max_len, st);
+    const int32_t* const rows_img = n > 1 ? img_of_row : nullptr;        // one row per image: row i is image i
+    for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->prologue(feats[i], n_img, n, rows_img, st));
+    EnsSampleDecArgs a = {};
+    a.s.V = V; a.s.temperature = opts->temperature; a.s.top_k = opts->top_k; a.s.top_p = opts->top_p;
+    a.s.seed = seed; a.s.T = max_len;
+    a.s.fin = fin; a.s.n_unf = n_unf;
+    a.s.ids_out = ids_out; a.s.logp_out = logp_out; a.s.score_out = score_out; a.s.it_next = it;
+    for (int i = 0; i < M; ++i) a.emb[i] = m[i]->emb_slot();
+    LogitsView lv[ENS_MAX_M];
+    int cur = 0, status = ICZ_OK;
+    for (int t = 0; t < max_len && status == ICZ_OK; ++t) {
+        for (int i = 0; i < M && status == ICZ_OK; ++i) {
+            m[i]->seam_emb_ready = t > 0;                               // written by the previous step's sample_decode_kernel
+            m[i]->seam_live = t > 0 ? n_unf + (t - 1) : nullptr;
+            status = m[i]->step(rows, it, rows_img, 1, cur, true, &lv[i], st);
+            m[i]->seam_emb_ready = false;
+            m[i]->seam_live = nullptr;
+        }
+        if (status != ICZ_OK) break;
+        a.ens = args(lv);
+        a.s.t = t;
+        a.s.uniforms = uniforms ? uniforms + (size_t)t * rows : nullptr;
+        status = launch_sample_decode(a, rows, st);
+        cur ^= 1;
+    }
+    ICZ_TRY(status);
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
@@ -269,6 +280,41 @@ int icz_ensemble_beam_search_diverse(icz_ensemble_t* h, const float* const* feat
                                  launch_combine(e->args(lv), rows, e->lp, e->Vp, nullptr, nullptr, 0, 0, st);
                              }};
     return beam_search("ensemble", e->m, e->M, &ens, feats, n_img, beam, max_steps, *opts, *div, seqs_out, lens_out, scores_out, st);
+}
+
+int icz_ensemble_sample_decode(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t n, int32_t max_len,
+                               const icz_sample_opts* opts, uint64_t seed, const float* uniforms, int64_t* ids_out, float* logp_out,
+                               float* score_out, void* stream) {
+    const char* who = "icz_ensemble_sample_decode";
+    Ensemble* e = reinterpret_cast<Ensemble*>(h);
+    // the arguments first: no handle needed to report them (the capacity is checked once there is one)
+    ICZ_TRY(check_sample_opts(who, opts, n_img > 0 ? n_img : 1, n, e ? e->V : -1, 0x7fffffff));
+    ICZ_REQUIRE(feats && ids_out && logp_out && score_out, "%s: null argument", who);
+    ICZ_REQUIRE(e, "%s: null handle", who);
+    return e->sample_decode(who, feats, n_img, n, max_len, opts, seed, uniforms, ids_out, logp_out, score_out, (hipStream_t)stream);
+}
+
+int icz_ensemble_sample_filter_draw(int32_t M, const float* const* logits, const float* const* bias, const int32_t* nsplit,
+                                    const int32_t* ld, const float* weights, int32_t rows, int32_t V, const icz_sample_opts* opts,
+                                    const float* uniforms, int64_t* tok_out, float* logp_out, uint8_t* keep_out, void* stream) {
+    const char* who = "icz_ensemble_sample_filter_draw";
+    ICZ_TRY(check_sample_opts(who, opts, 1, 1, V > 0 ? V : 0, 1));
+    ICZ_REQUIRE(M >= 1 && M <= ENS_MAX_M, "%s: %d members outside 1..%d", who, M, ENS_MAX_M);
+    ICZ_REQUIRE(logits && nsplit && ld && uniforms && tok_out && logp_out && rows > 0 && V > 0, "%s: bad arguments", who);
+    EnsSampleDecArgs a = {};
+    ICZ_TRY(ens_log_weights(who, weights, M, a.ens.logw));
+    for (int i = 0; i < M; ++i) {
+        ICZ_REQUIRE(logits[i] && ld[i] >= V && nsplit[i] >= 1, "%s: member %d: null logits, ld < V or nsplit < 1", who, i);
+        ICZ_REQUIRE(nsplit[i] == 1 || (bias && bias[i]), "%s: member %d: split-K slabs need a bias", who, i);
+        a.ens.m[i] = LogitsView{logits[i], nsplit[i] > 1 ? bias[i] : nullptr, (size_t)rows * ld[i], ld[i], nsplit[i]};
+    }
+    a.ens.M = M; a.ens.V = V;
+    a.s.V = V; a.s.temperature = opts->temperature; a.s.top_k = opts->top_k; a.s.top_p = opts->top_p;
+    a.s.uniforms = uniforms; a.s.T = 1;
+    a.s.ids_out = tok_out; a.s.logp_out = logp_out; a.s.keep_out = keep_out;
+    ICZ_TRY(launch_sample_decode(a, rows, (hipStream_t)stream));
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
 }
 
 int icz_ensemble_logprob(int32_t M, const float* const* logits, const float* const* bias, const int32_t* nsplit, const int32_t* ld,

@@ -1,29 +1,17 @@
 // Sampling decode (beyond the reference; include/icz.h: icz_*_sample_decode): n captions per image drawn in evaluation mode with
 // temperature, top-k and nucleus (top-p) filtering.  One kernel per step, sample_decode_kernel, behind the member's own decoder
 // step (DecodeMember, decoder_core.h); the SCST rollout's sample_select_kernel and the greedy / beam kernels are not touched.
+// A model ensemble (ensemble.hip) draws through the same kernel: its second instance fills the row from the members' logits.
 #include <cmath>
+#include <type_traits>
 
-#include "decoder_core.h"
+#include "ens_sample.h"
 
 namespace icz {
 
 constexpr int SD_THREADS = 1024;              // 16 waves per row: the row (40 KB at V = 10 102) sits in LDS, as in sample_select_kernel
 constexpr int SD_NW = SD_THREADS / 64;
 constexpr double SD_FIX = 1099511627776.0;    // 2^40: a survivor's mass exp(y - max y) in (0, 1] as a fixed-point integer
-
-struct SampleDecArgs {
-    LogitsView lv; int V;
-    float temperature; int top_k; float top_p;
-    const float* uniforms;            // [rows] of this step, or null: Philox (seed, t, row) under RNG_DECODE
-    uint64_t seed; int t, T;
-    uint8_t* fin;                     // [rows] in / out: the row has drawn <end>; null (with n_unf): the kernel alone, every row live
-    int* n_unf;                       // [T] rows still unfinished after each step (zeroed in front of the decode)
-    int64_t* ids_out; float* logp_out;        // [rows, T]
-    float* score_out;                 // [rows] (may be null)
-    int64_t* it_next;                 // [rows] (may be null)
-    const float* emb_table; float* emb_next; int E, relu;     // the next step's input embedding (emb_next may be null)
-    uint8_t* keep_out;                // [rows, V] or null: 1 = the token survived the filters
-};
 
 // float -> unsigned key of the same order (-0 = +0)
 __device__ __forceinline__ uint32_t sd_key(float x) {
@@ -144,7 +132,38 @@ __device__ SdCut sd_select(const float* srow, int V, const SdCut dom, unsigned l
 // the survivors' mass as an integer sum, sd_select on masses; (4) the float64 prefix sums of the survivors' masses over contiguous
 // slices (one fixed order) and the inverse-CDF draw; (5) token, log-probability, finished flag, the count of unfinished rows and the
 // next step's input embedding.  With both filters off passes 2 and 3 are skipped.
-__global__ __launch_bounds__(SD_THREADS) void sample_decode_kernel(SampleDecArgs a) {
+// Two instances, one per row source (A).  SampleDecArgs: pass 1 as above.  EnsSampleDecArgs (a model ensemble): pass 1 fills the row
+// with lp[v] = log(sum_m w_m softmax(logits_m)[v]) as ensemble_logprob_kernel defines it -- per member one online max / sum-exp pass
+// over its logits, then one pass that writes lp shifted by the largest term over m; the members' logits are read twice from global
+// memory (L2), the combined row never leaves LDS -- and the tail writes every member's next input embedding.  Passes 2 - 5 are one code.
+__device__ __forceinline__ const SampleDecArgs& sd_args(const SampleDecArgs& a) { return a; }
+__device__ __forceinline__ const SampleDecArgs& sd_args(const EnsSampleDecArgs& a) { return a.s; }
+
+// emb_next[row, :E] = table[tok] (relu: behind a ReLU)
+__device__ __forceinline__ void sd_write_emb(const float* table, float* emb_next, int E, int relu, int row, int tok) {
+    for (int e = threadIdx.x * 4; e < E; e += 4 * SD_THREADS) {
+        f32x4 x = *reinterpret_cast<const f32x4*>(table + (size_t)tok * E + e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j] = relu ? fmaxf(x[j], 0.f) : x[j];
+        *reinterpret_cast<f32x4*>(emb_next + (size_t)row * E + e) = x;
+    }
+}
+template <class A>
+__device__ __forceinline__ void sd_next_emb(const A& args, int row, int tok) {
+    if constexpr (std::is_same_v<A, EnsSampleDecArgs>) {
+        for (int m = 0; m < args.ens.M; ++m) {
+            const DecodeMember::EmbSlot& s = args.emb[m];
+            if (s.emb) sd_write_emb(s.table, s.emb, s.E, s.relu, row, tok);
+        }
+    } else {
+        if (args.emb_next) sd_write_emb(args.emb_table, args.emb_next, args.E, args.relu, row, tok);
+    }
+}
+
+template <class A>
+__global__ __launch_bounds__(SD_THREADS) void sample_decode_kernel(A args) {
+    constexpr bool ENS = std::is_same_v<A, EnsSampleDecArgs>;
+    const SampleDecArgs& a = sd_args(args);
     extern __shared__ __attribute__((aligned(16))) float srow[];     // V floats: the finished logits of the row
     __shared__ unsigned long long hist[256];
     __shared__ unsigned long long s_u64[SD_NW];
@@ -160,21 +179,74 @@ __global__ __launch_bounds__(SD_THREADS) void sample_decode_kernel(SampleDecArgs
             a.logp_out[(size_t)row * a.T + a.t] = 0.f;
             if (a.it_next) a.it_next[row] = 0;
         }
-        if (!all_dead && a.emb_next)              // the others go on: this row keeps running on <pad> (finite, never read)
-            for (int e = tid * 4; e < a.E; e += 4 * SD_THREADS) {
-                f32x4 x = *reinterpret_cast<const f32x4*>(a.emb_table + e);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) x[j] = a.relu ? fmaxf(x[j], 0.f) : x[j];
-                *reinterpret_cast<f32x4*>(a.emb_next + (size_t)row * a.E + e) = x;
-            }
+        if (!all_dead) sd_next_emb(args, row, 0);       // the others go on: this row keeps running on <pad> (finite, never read)
         return;
     }
     const float u = a.uniforms ? a.uniforms[row] : rng_uniform(a.seed, (uint32_t)a.t, (uint64_t)row, RNG_DECODE);
     // pass 1
-    const LogitsView& L = a.lv;
-    const float* l = L.p + (size_t)row * L.ld;
     float mx = -INFINITY;
-    {
+    if constexpr (ENS) {
+        __shared__ float sms[SD_NW];
+        const EnsArgs& en = args.ens;
+        float shift[ENS_MAX_M];           // log w_m - lse_m
+        bool vec[ENS_MAX_M];
+#pragma unroll
+        for (int m = 0; m < ENS_MAX_M; ++m) {
+            shift[m] = -INFINITY;
+            vec[m] = false;
+            if (m >= en.M) continue;
+            const LogitsView& l = en.m[m];
+            vec[m] = ens_vec_ok(l);
+            float mm = -INFINITY, s = 0.f;
+            for (int v = tid * 4; v < V; v += 4 * SD_THREADS) {
+                const f32x4 x = ens_load4(l, row, v, V, vec[m]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float y = x[j];
+                    if (y > mm) { s = s * expf(mm - y) + 1.f; mm = y; }
+                    else if (y != -INFINITY) s += expf(y - mm);
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) lse_combine(mm, s, __shfl_xor(mm, o, 64), __shfl_xor(s, o, 64));
+            if (lane == 0) { smf[wave] = mm; sms[wave] = s; }
+            __syncthreads();
+            mm = smf[0]; s = sms[0];
+            for (int w = 1; w < SD_NW; ++w) lse_combine(mm, s, smf[w], sms[w]);      // one fixed order
+            __syncthreads();              // smf / sms are rewritten by the next member
+            shift[m] = en.logw[m] - (mm + logf(s));
+        }
+        for (int v = tid * 4; v < V; v += 4 * SD_THREADS) {
+            f32x4 term[ENS_MAX_M];
+            f32x4 top = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+            for (int m = 0; m < ENS_MAX_M; ++m) {
+                if (m >= en.M) continue;
+                term[m] = ens_load4(en.m[m], row, v, V, vec[m]) + shift[m];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) top[j] = fmaxf(top[j], term[m][j]);
+            }
+            f32x4 lp;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float s = 0.f;
+#pragma unroll
+                for (int m = 0; m < ENS_MAX_M; ++m)
+                    if (m < en.M && term[m][j] != -INFINITY) s += expf(term[m][j] - top[j]);
+                lp[j] = top[j] == -INFINITY ? -INFINITY : top[j] + logf(s);
+            }
+            if (v + 4 <= V) {
+                *reinterpret_cast<f32x4*>(srow + v) = lp;
+                mx = fmaxf(mx, fmaxf(fmaxf(lp[0], lp[1]), fmaxf(lp[2], lp[3])));
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (v + j < V) { srow[v + j] = lp[j]; mx = fmaxf(mx, lp[j]); }
+            }
+        }
+    } else {
+        const LogitsView& L = a.lv;
+        const float* l = L.p + (size_t)row * L.ld;
         const bool vec = ((L.ld | (int)(L.slab_stride & 3)) & 3) == 0 && (((uintptr_t)L.p | (uintptr_t)L.bias) & 15) == 0;
         const int Vv = vec ? (V & ~3) : 0;
         for (int v = tid * 4; v < Vv; v += 4 * SD_THREADS) {
@@ -291,13 +363,7 @@ __global__ __launch_bounds__(SD_THREADS) void sample_decode_kernel(SampleDecArgs
         if (a.fin) a.fin[row] = unf ? 0 : 1;
         if (a.n_unf && unf) atomicAdd(&a.n_unf[a.t], 1);
     }
-    if (a.emb_next)
-        for (int e = tid * 4; e < a.E; e += 4 * SD_THREADS) {
-            f32x4 x = *reinterpret_cast<const f32x4*>(a.emb_table + (size_t)nxt * a.E + e);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) x[j] = a.relu ? fmaxf(x[j], 0.f) : x[j];
-            *reinterpret_cast<f32x4*>(a.emb_next + (size_t)row * a.E + e) = x;
-        }
+    sd_next_emb(args, row, nxt);
 }
 
 // start of a decode: <sta>, no row finished, row r belongs to image r / n, the per-step counters of unfinished rows = 0
@@ -307,19 +373,26 @@ __global__ void sample_decode_init_kernel(int64_t* it, uint8_t* fin, int32_t* im
     if (i < T) n_unf[i] = 0;
 }
 
-static int launch_sample_decode(const SampleDecArgs& a, int rows, hipStream_t st) {
-    static bool lds_set = false;
+void launch_sample_decode_init(int64_t* it, uint8_t* fin, int32_t* img_of_row, int rows, int n, int* n_unf, int T, hipStream_t st) {
+    hipLaunchKernelGGL(sample_decode_init_kernel, dim3(cdiv(rows > T ? rows : T, 256)), dim3(256), 0, st, it, fin, img_of_row, rows, n, n_unf, T);
+}
+
+template <class A>
+static int launch_sample_decode_t(const A& a, int V, int rows, hipStream_t st) {
+    static bool lds_set = false;          // one per instance
     if (!lds_set) {
-        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sample_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sample_decode_kernel<A>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           160 * 1024 - 4096));
         lds_set = true;
     }
-    hipLaunchKernelGGL(sample_decode_kernel, dim3(rows), dim3(SD_THREADS), sizeof(float) * a.V, st, a);
+    hipLaunchKernelGGL(sample_decode_kernel<A>, dim3(rows), dim3(SD_THREADS), sizeof(float) * V, st, a);
     return ICZ_OK;
 }
+int launch_sample_decode(const SampleDecArgs& a, int rows, hipStream_t st) { return launch_sample_decode_t(a, a.V, rows, st); }
+int launch_sample_decode(const EnsSampleDecArgs& a, int rows, hipStream_t st) { return launch_sample_decode_t(a, a.s.V, rows, st); }
 
 // V < 0: no handle yet, the vocabulary is not known (its rules are checked once it is)
-static int check_sample_opts(const char* who, const icz_sample_opts* o, int n_img, int n, int V, int max_rows) {
+int check_sample_opts(const char* who, const icz_sample_opts* o, int n_img, int n, int V, int max_rows) {
     ICZ_REQUIRE(o, "%s: null options", who);
     ICZ_REQUIRE(n >= 1 && n <= 8, "%s: n=%d samples per image outside 1..8", who, n);
     ICZ_REQUIRE(std::isfinite(o->temperature) && o->temperature > 0.f, "%s: temperature %g not positive or not finite", who, (double)o->temperature);
@@ -357,8 +430,7 @@ int sample_decode(DecodeMember* m, const char* who, const float* feats, int n_im
     const int rows = n_img * n;
     ICZ_TRY(ensure_sample_buf(m, rows, max_len));
     const DecodeMember::SampleBuf& b = m->sb;
-    hipLaunchKernelGGL(sample_decode_init_kernel, dim3(cdiv(rows > max_len ? rows : max_len, 256)), dim3(256), 0, st, b.it, b.fin, b.img_of_row, rows,
-                       n, b.n_unf, max_len);
+    launch_sample_decode_init(b.it, b.fin, b.img_of_row, rows, n, b.n_unf, max_len, st);
     const int32_t* const img_of_row = n > 1 ? b.img_of_row : nullptr;      // one row per image: row i is image i
     ICZ_TRY(m->prologue(feats, n_img, n, img_of_row, st));
     const DecodeMember::EmbSlot es = m->emb_slot();

@@ -902,3 +902,93 @@ def eval_ensemble_captions_json_generation(engines, dataloader, eval_beam_size=-
                 sampled_caption.append(word)
         result.append({"image_id": image_id, "caption": " ".join(sampled_caption)})
     return result
+
+
+def _ensemble_engine_checks(engines, weights):
+    """the engine checks of eval_ensemble_captions_json_generation -> the engines as a list"""
+    from .ensemble import check_members, check_weights
+    engines = list(engines)
+    check_members(len(engines))
+    if len({len(e.caption_vocab) for e in engines}) != 1:
+        raise ValueError("the engines' vocabularies differ in size %s" % [len(e.caption_vocab) for e in engines])
+    if len({str(e.device) for e in engines}) != 1:
+        raise ValueError("the engines sit on different devices %s" % [str(e.device) for e in engines])
+    check_weights(weights, len(engines))
+    return engines
+
+
+def sample_ensemble_captions_json_generation(engines, dataloader, samples_per_image=1, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                                             tqdm_visible=True, *, weights=None):
+    """Engine.sample_captions_json_generation for an ensemble of 1..4 engines (BUTD / AoA / NIC) of one vocabulary (an extension;
+    include/icz.h: icz_ensemble_sample_decode): every engine turns the shared batch into its own features, and `samples_per_image`
+    (1..8) captions per image are drawn from the averaged word probabilities (`weights`: None = uniform) under temperature / top_k /
+    top_p, 20 steps.  Returns {"image_id", "caption", "score"} entries, samples_per_image per image in loader order (the first
+    engine's vocabulary); score = the ensemble's summed log-probability of the caption's tokens.  Batch i draws from Philox seed
+    `seed * 2**20 + i`; sharded over the ranks and gathered as the single-model method.  Arguments are checked before any device
+    work (ValueError)."""
+    from .ensemble import EnsembleHandle
+    engines = _ensemble_engine_checks(engines, weights)
+    make_sample_opts(temperature, top_k, top_p, samples_per_image)
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError("seed %r is not a non-negative integer" % (seed,))
+    lead = engines[0]
+    if top_k > len(lead.caption_vocab):
+        raise ValueError("top_k %d above the vocabulary size %d" % (top_k, len(lead.caption_vocab)))
+    n = int(samples_per_image)
+    with _on_stream(lead):
+        for e in engines:
+            e.model.eval()
+        dp = icz_dist.is_distributed()
+        rank, world = icz_dist.rank(), icz_dist.world_size()
+        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Sampling Process", tqdm_visible)
+        ens = None
+        ids_out, rows_out, keys_out = [], [], []
+        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
+            feats = []
+            for e in engines:
+                vi = e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
+                feats.append(e._features(vi))
+            handles = [e._hot_handle() for e in engines]
+            if ens is None or any(a is not b for a, b in zip(ens.handles, handles)):
+                ens = EnsembleHandle(handles, weights)
+            ids, _, score = ens.sample_decode(feats, n, 20, temperature, top_k, top_p, (seed << 20) + batch_i)
+            ids, bits = ids.cpu().numpy(), score.cpu().numpy().view(np.uint32)
+            for r in range(ids.shape[0]):
+                ids_out.append(int(image_ids[r // n]))
+                rows_out.append(np.concatenate([ids[r], [int(bits[r])]]))      # the score travels as its bit pattern (non-negative)
+                keys_out.append((batch_i << 20) + r)                           # loader order: batch index, then image, then sample
+        if dp:
+            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, lead.device)
+    result = []
+    ix2word = lead.caption_vocab.ix2word
+    for image_id, row in zip(ids_out, rows_out):
+        words = []
+        for word_id in row[:-1]:
+            word = ix2word[int(word_id)]
+            if word == "<end>" or int(word_id) == 0:
+                break
+            elif word != "<sta>":
+                words.append(word)
+        score = float(np.array([int(row[-1])], dtype=np.uint32).view(np.float32)[0])
+        result.append({"image_id": image_id, "caption": " ".join(words), "score": score})
+    return result
+
+
+def consensus_ensemble_captions_json_generation(engines, dataloader, samples_per_image=5, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                                                tqdm_visible=True, *, weights=None):
+    """sample_ensemble_captions_json_generation (same arguments, samples_per_image 2..8) followed by the first engine's
+    rerank_captions_json: one consensus caption per image."""
+    from .caption_sets import check_k
+    engines = _ensemble_engine_checks(engines, weights)
+    check_k(samples_per_image, 2)
+    make_sample_opts(temperature, top_k, top_p, samples_per_image)         # every option error in front of the engines' state
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError("seed %r is not a non-negative integer" % (seed,))
+    lead = engines[0]
+    if top_k > len(lead.caption_vocab):
+        raise ValueError("top_k %d above the vocabulary size %d" % (top_k, len(lead.caption_vocab)))
+    if lead._cider_df is None and lead._scorer is None:
+        raise ValueError("caption sets are scored with CIDEr-D: the engine needs cider_df (the document-frequency table)")
+    entries = sample_ensemble_captions_json_generation(engines, dataloader, samples_per_image, temperature, top_k, top_p, seed, tqdm_visible,
+                                                       weights=weights)
+    return lead.rerank_captions_json(entries, samples_per_image)

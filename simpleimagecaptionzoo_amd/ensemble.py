@@ -1,6 +1,6 @@
 """Model ensembles (beyond the reference; self-critical.pytorch's AttEnsemble): several BUTD / AoA / NIC checkpoints of one
-vocabulary decode together, greedy or with every beam-search option, averaging the members' word probabilities each step
-(include/icz.h: icz_ensemble_*).  The members' steps and the combine kernel run on the device (csrc/ensemble.hip)."""
+vocabulary decode together, greedy, with every beam-search option or by sampling (temperature, top-k, nucleus), averaging the
+members' word probabilities each step (include/icz.h: icz_ensemble_*).  The members' steps and the combine kernel run on the device (csrc/ensemble.hip)."""
 import ctypes as C
 import math
 import numbers
@@ -8,6 +8,7 @@ import numbers
 import torch
 
 from . import beam as _beam
+from . import sampling as _sampling
 from ._lib import check, lib, ptr, stream_ptr
 from .beam import nbest_lists
 from .handle import CaptionerBase, DecoderHandle
@@ -103,6 +104,56 @@ class EnsembleHandle:
                                                       ptr(scores), stream_ptr()))
         return seqs, lens, scores
 
+    @property
+    def max_rows(self):
+        """decoder rows one call may hold: the smallest member capacity"""
+        return min(h.max_rows for h in self.handles)
+
+    def sample_decode(self, feats_list, n=1, max_len=20, temperature=1.0, top_k=0, top_p=1.0, rng=None):
+        """The members' sample_decode on the combined log-probabilities (include/icz.h: icz_ensemble_sample_decode): n = 1..8
+        captions per image drawn from softmax(lp / temperature) restricted to the top_k largest tokens (0 = off) and then to the
+        nucleus of mass top_p (1 = off).  rng: None / an integer Philox seed, or explicit uniforms (max_len, B n) fp32 on the
+        device.  Returns (ids int64 (B n, max_len) with the drawn <end> and 0 behind it, the ensemble's own log-prob of every token
+        (B n, max_len), their sum (B n,)), row img * n + j.  Bad options raise ValueError before the features are looked at."""
+        opts = _sampling.make_sample_opts(temperature, top_k, top_p, n)
+        if top_k > self.V:
+            raise ValueError("top_k %d above the vocabulary size %d" % (top_k, self.V))
+        seed, uniforms = _sampling.rng_args(rng)
+        arr, n_img = self._feats(feats_list)
+        n, max_len = int(n), int(max_len)
+        rows = n_img * n
+        if rows > self.max_rows:
+            raise ValueError("%d images x %d samples exceed the ensemble's row capacity %d" % (n_img, n, self.max_rows))
+        if uniforms is not None and tuple(uniforms.shape) != (max_len, rows):
+            raise ValueError("uniforms must be (%d, %d), got %s" % (max_len, rows, tuple(uniforms.shape)))
+        ids = torch.zeros(rows, max_len, dtype=torch.int64, device=self.device)
+        logp = torch.zeros(rows, max_len, dtype=torch.float32, device=self.device)
+        score = torch.zeros(rows, dtype=torch.float32, device=self.device)
+        check(lib().icz_ensemble_sample_decode(self._h, arr, n_img, n, max_len, C.byref(opts), seed, ptr(uniforms), ptr(ids), ptr(logp),
+                                                ptr(score), stream_ptr()))
+        return ids, logp, score
+
+
+def sample_filter_draw(members, weights, rows, V, uniforms, temperature=1.0, top_k=0, top_p=1.0):
+    """icz_ensemble_sample_filter_draw (the kernel alone, tests): members = [(logits tensor, bias or None, nsplit, ld)], weights =
+    None or one per member -> (tokens (rows,), logp (rows,), keep (rows, V) uint8)"""
+    opts = _sampling.make_sample_opts(temperature, top_k, top_p, 1, V)
+    members = list(members)
+    check_members(len(members))
+    w = check_weights(weights, len(members))
+    M, dev = len(members), members[0][0].device
+    lg = (C.c_void_p * M)(*[t.data_ptr() for t, _, _, _ in members])
+    bs = (C.c_void_p * M)(*[b.data_ptr() if b is not None else None for _, b, _, _ in members])
+    ns = (C.c_int32 * M)(*[int(k) for _, _, k, _ in members])
+    ld = (C.c_int32 * M)(*[int(l) for _, _, _, l in members])
+    arr_w = (C.c_float * M)(*w) if w is not None else None
+    tok = torch.zeros(rows, dtype=torch.int64, device=dev)
+    logp = torch.zeros(rows, dtype=torch.float32, device=dev)
+    keep = torch.zeros(rows, V, dtype=torch.uint8, device=dev)
+    check(lib().icz_ensemble_sample_filter_draw(M, lg, bs, ns, ld, arr_w, rows, V, C.byref(opts), ptr(uniforms), ptr(tok), ptr(logp), ptr(keep),
+                                                 stream_ptr()))
+    return tok, logp, keep
+
 
 def member_features(captioner, visual_inputs):
     """The features `captioner`'s own sampler hands its handle."""
@@ -158,5 +209,13 @@ class CaptionEnsemble:
         feats = self._feats(visual_inputs_list)
         return nbest_lists(*self._handle().beam_search_opts(feats, beam_size, 50, *opts))
 
+    def sample_decode(self, visual_inputs_list, n=1, max_len=20, temperature=1.0, top_k=0, top_p=1.0, rng=None):
+        """n sampled captions per image with temperature / top-k / nucleus filtering (EnsembleHandle.sample_decode) -> (ids (B n,
+        max_len), log-probs (B n, max_len), scores (B n,)), row img * n + j.  Bad options raise ValueError before any device work."""
+        _sampling.make_sample_opts(temperature, top_k, top_p, n)
+        _sampling.rng_args(rng)
+        feats = self._feats(visual_inputs_list)
+        return self._handle().sample_decode(feats, n, max_len, temperature, top_k, top_p, rng)
 
-__all__ = ["EnsembleHandle", "CaptionEnsemble", "check_weights", "member_features"]
+
+__all__ = ["EnsembleHandle", "CaptionEnsemble", "check_weights", "member_features", "sample_filter_draw"]
