@@ -493,6 +493,58 @@ int icz_ensemble_sample_filter_draw(int32_t M, const float* const* logits, const
                                     const float* uniforms, int64_t* tok_out, float* logp_out, uint8_t* keep_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Scoring given captions (beyond the reference; self-critical.pytorch's eval_split reports the perplexity this gives): the
+ * log-probability a model, or an ensemble, assigns to captions it is GIVEN -- teacher forcing in EVALUATION mode (dropout off,
+ * nothing kept for a backward pass).  Decoder row r = img * n + j scores caption j of image img; n = 1..8 captions per image,
+ * n_img n within the handle's row capacity.  The per-image work runs once per image (NIC's image step once per image, expanded
+ * to its n rows).  ids [n_img n, max_len] int64 in the format icz_*_sample_decode / icz_*_greedy WRITE: no leading <sta>, <end> (2)
+ * included, 0 behind it.  For row r with caption c = ids[r, :]:
+ *   1. len(r), the number of scored tokens: the index of the first 2 plus one if a 2 occurs before any 0; else the index of the
+ *      first 0; else max_len.  Whatever lies behind len(r) is ignored; an empty caption (c[0] = 0) is legal.  A token id outside
+ *      [0, V) ends the row as a 0 does and is never used as an index.
+ *   2. step t < len(r): the decoder is fed <sta> (1) at t = 0 and c[t-1] afterwards, and
+ *          logp_out[r, t] = log_softmax(x_t)[c[t]]
+ *      with x_t the row's finished logits (split-K slabs summed in slab order + bias) -- step 5 of the sampling contract above and
+ *      the quantity the beam scores are.  For t >= len(r): logp_out[r, t] = 0.
+ *   3. score_out[r] = the fp32 sum of logp_out[r, :len(r)] in step order (icz_*_sample_decode's score_out); 0 for an empty caption.
+ *   4. an ensemble: logp = log( sum_m w_m softmax(logits_m)[c[t]] ), the definition of icz_ensemble_logprob, evaluated as
+ *      log sum_m exp(log w_m + x_m[c[t]] - lse_m) shifted by the largest term: one pass over each member's logits for lse_m and the
+ *      one logit; the combined row of V entries is never formed.
+ *   5. a row past its length keeps running on <pad> (finite, never read); once every row is past its length the kernels of the
+ *      remaining steps return at entry (the early-out of the sampling decode: the same per-step count of unfinished rows).
+ * One launch per step behind the decoder step (score_tokens_kernel): the online max / sum-exp over V (fp32 terms, float64 sums),
+ * the target's logit, logp and the running score, the finished flag and the count, and every member's next input embedding.  No row
+ * is held in LDS: there is no cap on V.  Reduction orders are fixed and there are no float atomics: two runs give the same bits.
+ * An AoA handle scores on the region counts of its last icz_aoa_set_regions.
+ * Argument errors return ICZ_ERR_INVALID before any device work, in this order: n outside 1..8, max_len outside 1..256, n_img <= 0
+ * or n_img n above the (smallest member's) row capacity, null arguments, null handle, an unrefreshed member or null member features.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* the host-only argument rules above (no handle, no device): max_rows is the handle's row capacity */
+int icz_score_captions_check(int32_t n_img, int32_t n, int32_t max_len, int32_t max_rows);
+/* Score ids under one decoder: logp_out [n_img n, max_len], score_out [n_img n]. */
+int icz_butd_score_captions(icz_butd_t* h, const float* feats, int32_t n_img, int32_t n, int32_t max_len, const int64_t* ids,
+                            float* logp_out, float* score_out, void* stream);
+int icz_aoa_score_captions(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t n, int32_t max_len, const int64_t* ids,
+                           float* logp_out, float* score_out, void* stream);
+int icz_nic_score_captions(icz_nic_t* h, const float* features, int32_t n_img, int32_t n, int32_t max_len, const int64_t* ids,
+                           float* logp_out, float* score_out, void* stream);
+/* Score ids under an ensemble (rule 4): every member steps on the shared fed tokens, then one launch scores the row from all
+ * members' logits and writes every member's next input embedding.  feats: HOST array of M device pointers. */
+int icz_ensemble_score_captions(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t n, int32_t max_len,
+                                const int64_t* ids, float* logp_out, float* score_out, void* stream);
+/* score_tokens_kernel on its own (tests), the counterpart of icz_sample_filter_draw: logits are finished rows [rows][ld] (nsplit 1)
+ * or nsplit split-K slabs [nsplit][rows][ld] summed in slab order + bias; targets [rows] int64; logp_out [rows] =
+ * log_softmax(row)[target] (0 for a target outside [0, V), which is never used as an index). */
+int icz_score_tokens(const float* logits, const float* bias, int32_t nsplit, int32_t ld, int32_t rows, int32_t V,
+                     const int64_t* targets, float* logp_out, void* stream);
+/* The ensemble instance on its own (tests), the counterpart of icz_ensemble_sample_filter_draw: M = 1..4 members' logits and
+ * weights as in icz_ensemble_logprob (host arrays of device pointers; bias may be NULL when every nsplit is 1); logp_out [rows] =
+ * log( sum_m w_m softmax(logits_m)[target] ).  Errors: M, null / bad arguments, the weights, each member's view. */
+int icz_ensemble_score_tokens(int32_t M, const float* const* logits, const float* const* bias, const int32_t* nsplit,
+                              const int32_t* ld, const float* weights, int32_t rows, int32_t V, const int64_t* targets,
+                              float* logp_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser step: clip_gradient (Utils.py:241-250, value clamp) + torch.optim.Adam(betas=(0.9,0.999),
  * eps=1e-8, weight_decay=0) (Utils.py:219-220) fused, one call per parameter tensor.
  * ---------------------------------------------------------------------------------------------------------- */

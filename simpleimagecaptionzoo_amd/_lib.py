@@ -196,6 +196,14 @@ def lib():
         "icz_aoa_sample_decode": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
         "icz_nic_sample_decode": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
         "icz_sample_filter_draw": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(SampleOpts), vp, vp, vp, vp, vp]),
+        "icz_score_captions_check": (C.c_int, [i32, i32, i32, i32]),
+        "icz_butd_score_captions": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "icz_aoa_score_captions": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "icz_nic_score_captions": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "icz_ensemble_score_captions": (C.c_int, [vp, C.POINTER(vp), i32, i32, i32, vp, vp, vp, vp]),
+        "icz_score_tokens": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "icz_ensemble_score_tokens": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32, vp,
+                                                vp, vp]),
         "icz_aoa_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),
         "icz_aoa_scst_rollouts": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp, vp]),
         "icz_aoa_sample_backward": (C.c_int, [vp, vp, C.POINTER(AoaParams), vp, vp, f32, vp]),

@@ -1,6 +1,6 @@
 // Host-side machinery shared by the BUTD, AoA and NIC decoder handles: device allocations, the hipGraph cache, side
 // streams, the caption loss head (teacher-forced XE input, packed logits, XE / REINFORCE losses), the decoder seams (DecodeMember)
-// with the drivers that run on them (beam search: beam.hip, sampling: sample_decode.hip) and the greedy select tail.
+// with the drivers that run on them (beam search: beam.hip, sampling: sample_decode.hip, scoring given captions: score_captions.hip) and the greedy select tail.
 // Each rule below ("free => clear graphs", "zero-fill then sync", "sync => destroy a graph") has this one owner.
 // Destroying a captured graph: a replay of it may still be in flight on the caller's stream, so whoever destroys one synchronises the
 // device first -- GraphCache::run before it evicts (rare: only a working set above the capacity evicts), and the callers of
@@ -299,6 +299,10 @@ void launch_greedy_select(const LogitsView& lv, const DecodeMember::EmbSlot& e, 
 // member's step + sample_decode_kernel (include/icz.h: icz_*_sample_decode; `who` names the entry in its errors).
 int sample_decode(DecodeMember* m, const char* who, const float* feats, int n_img, int n, int max_len, const icz_sample_opts* opts,
                   uint64_t seed, const float* uniforms, int64_t* ids_out, float* logp_out, float* score_out, hipStream_t st);
+// Scoring given captions on a member (score_captions.hip; include/icz.h: icz_*_score_captions): prologue once per image, then
+// max_len steps of the member's step on the fed tokens + score_tokens_kernel.
+int score_captions(DecodeMember* m, const char* who, const float* feats, int n_img, int n, int max_len, const int64_t* ids,
+                   float* logp_out, float* score_out, hipStream_t st);
 enum { ICZ_MEMBER_BUTD = 0, ICZ_MEMBER_AOA = 1, ICZ_MEMBER_NIC = 2 };
 DecodeMember* butd_member(void* handle);        // the seams of an icz_butd_t / icz_aoa_t / icz_nic_t
 DecodeMember* aoa_member(void* handle);

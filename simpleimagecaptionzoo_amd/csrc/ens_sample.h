@@ -1,6 +1,7 @@
-// What ensemble.hip and sample_decode.hip share: the ensemble's view of its members' logits with the device helpers that read and
-// reduce them (ensemble_logprob_kernel and the ensemble instance of sample_decode_kernel), and the arguments / launchers of
-// sample_decode_kernel that the ensemble's sampling driver (Ensemble::sample_decode) needs.
+// What ensemble.hip, sample_decode.hip and score_captions.hip share: the ensemble's view of its members' logits with the device
+// helpers that read and reduce them (ensemble_logprob_kernel and the ensemble instances of sample_decode_kernel and
+// score_tokens_kernel), and the arguments / launchers of those two kernels that the ensemble's drivers (Ensemble::sample_decode,
+// Ensemble::score_captions) need.
 #pragma once
 #include "decoder_core.h"
 
@@ -75,5 +76,36 @@ int check_sample_opts(const char* who, const icz_sample_opts* o, int n_img, int 
 void launch_sample_decode_init(int64_t* it, uint8_t* fin, int32_t* img_of_row, int rows, int n, int* n_unf, int T, hipStream_t st);
 int launch_sample_decode(const SampleDecArgs& a, int rows, hipStream_t st);
 int launch_sample_decode(const EnsSampleDecArgs& a, int rows, hipStream_t st);
+// the member's SampleBuf (tokens, finished flags, per-step counts, image of each row) for `rows` rows and T steps
+int ensure_sample_buf(DecodeMember* m, int rows, int T);
+
+// ---- score_tokens_kernel (score_captions.hip) ----
+struct ScoreArgs {
+    LogitsView lv; int V;             // lv: the single-model instance's row source (the ensemble instance reads EnsScoreArgs::ens)
+    const int64_t* ids;               // [rows, T] the given captions; the kernel alone: [rows] targets with T = 1
+    int t, T;
+    uint8_t* fin;                     // [rows] in / out: the row is past its length; null (with n_unf): the kernel alone, every row live
+    int* n_unf;                       // [T] rows with a token left to score after each step (zeroed in front of the pass)
+    float* logp_out;                  // [rows, T]
+    float* score_out;                 // [rows] (may be null)
+    int64_t* it_next;                 // [rows] (may be null)
+    const float* emb_table; float* emb_next; int E, relu;     // the next step's input embedding (emb_next may be null)
+};
+// The ensemble instance: logp = log(sum_m w_m softmax(logits_m)[target]) of `ens`, and the tail writes the next step's input embedding
+// of every member (emb[m].emb null: none, the kernel alone); s.lv and s.emb_* are not read.
+struct EnsScoreArgs {
+    ScoreArgs s;
+    EnsArgs ens;
+    DecodeMember::EmbSlot emb[ENS_MAX_M];
+};
+// the host-only argument rules of icz_*_score_captions
+int check_score_args(const char* who, int n_img, int n, int max_len, int max_rows);
+// start of a scoring pass: <sta> in `it`, a row whose first token is 0 or outside [0, V) finished, image of each row, counters = 0
+void launch_score_init(const int64_t* ids, int64_t* it, uint8_t* fin, int32_t* img_of_row, int rows, int n, int* n_unf, int T, int V,
+                       hipStream_t st);
+void launch_score_tokens(const ScoreArgs& a, int rows, hipStream_t st);
+void launch_score_tokens(const EnsScoreArgs& a, int rows, hipStream_t st);
+// weights: null = uniform; else finite, >= 0, sum > 0 -> log of the normalised weights (ensemble.hip)
+int ens_log_weights(const char* who, const float* weights, int M, float* logw);
 
 }  // namespace icz

@@ -3,6 +3,7 @@
 // ensemble_logprob_kernel combines the members' logits into lp[v] = log(sum_m w_m softmax(logits_m)[v]): greedy takes its argmax in
 // the same launch, beam search hands the rows to the shared driver (beam_search, beam.hip) with every option it has, and the
 // sampling decode draws from lp in the ensemble instance of sample_decode_kernel (sample_decode.hip), which combines in its pass 1.
+// Given captions are scored by the ensemble instance of score_tokens_kernel (score_captions.hip), which never forms lp.
 #include <cmath>
 
 #include "ens_sample.h"
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(256) void ensemble_logprob_kernel(EnsArgs a, float*
 }
 
 // weights: null = uniform; else finite, >= 0, sum > 0 -> log of the normalised weights
-static int ens_log_weights(const char* who, const float* weights, int M, float* logw) {
+int ens_log_weights(const char* who, const float* weights, int M, float* logw) {
     double sum = 0.0;
     for (int i = 0; i < M; ++i) {
         const double w = weights ? (double)weights[i] : 1.0;
@@ -150,6 +151,8 @@ struct Ensemble {
     int greedy(const float* const* feats, int B, int max_len, int64_t* ids_out, hipStream_t st);
     int sample_decode(const char* who, const float* const* feats, int n_img, int n, int max_len, const icz_sample_opts* opts, uint64_t seed,
                       const float* uniforms, int64_t* ids_out, float* logp_out, float* score_out, hipStream_t st);
+    int score_captions(const char* who, const float* const* feats, int n_img, int n, int max_len, const int64_t* ids, float* logp_out,
+                       float* score_out, hipStream_t st);
 };
 
 int Ensemble::init(const int32_t* kinds, void* const* members, const float* weights, int n) {
@@ -241,6 +244,43 @@ int Ensemble::sample_decode(const char* who, const float* const* feats, int n_im
     return ICZ_OK;
 }
 
+// Scoring given captions (score_captions(), score_captions.hip, over M members): row img * n + j scores caption j of image img;
+// every member runs its prologue once per image and its step over all rows on the shared fed tokens, then ONE launch of
+// score_tokens_kernel's ensemble instance reads every member's logits once (lse_m and the target's logit; the combined row is never
+// formed) and writes every member's next input embedding.  The caller (icz_ensemble_score_captions) has checked the arguments.
+int Ensemble::score_captions(const char* who, const float* const* feats, int n_img, int n, int max_len, const int64_t* ids,
+                             float* logp_out, float* score_out, hipStream_t st) {
+    const int rows = n_img * n;
+    ICZ_TRY(check_members(who, m, M, feats, rows));
+    launch_score_init(ids, it, fin, img_of_row, rows, n, n_unf, max_len, V, st);
+    const int32_t* const rows_img = n > 1 ? img_of_row : nullptr;        // one row per image: row i is image i
+    for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->prologue(feats[i], n_img, n, rows_img, st));
+    EnsScoreArgs a = {};
+    a.s.V = V; a.s.ids = ids; a.s.T = max_len;
+    a.s.fin = fin; a.s.n_unf = n_unf;
+    a.s.logp_out = logp_out; a.s.score_out = score_out; a.s.it_next = it;
+    for (int i = 0; i < M; ++i) a.emb[i] = m[i]->emb_slot();
+    LogitsView lv[ENS_MAX_M];
+    int cur = 0, status = ICZ_OK;
+    for (int t = 0; t < max_len && status == ICZ_OK; ++t) {
+        for (int i = 0; i < M && status == ICZ_OK; ++i) {
+            m[i]->seam_emb_ready = t > 0;                               // written by the previous step's score_tokens_kernel
+            m[i]->seam_live = t > 0 ? n_unf + (t - 1) : nullptr;
+            status = m[i]->step(rows, it, rows_img, 1, cur, true, &lv[i], st);
+            m[i]->seam_emb_ready = false;
+            m[i]->seam_live = nullptr;
+        }
+        if (status != ICZ_OK) break;
+        a.ens = args(lv);
+        a.s.t = t;
+        launch_score_tokens(a, rows, st);
+        cur ^= 1;
+    }
+    ICZ_TRY(status);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
 }  // namespace icz
 
 // ================================================================================================
@@ -292,6 +332,17 @@ int icz_ensemble_sample_decode(icz_ensemble_t* h, const float* const* feats, int
     ICZ_REQUIRE(feats && ids_out && logp_out && score_out, "%s: null argument", who);
     ICZ_REQUIRE(e, "%s: null handle", who);
     return e->sample_decode(who, feats, n_img, n, max_len, opts, seed, uniforms, ids_out, logp_out, score_out, (hipStream_t)stream);
+}
+
+int icz_ensemble_score_captions(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t n, int32_t max_len, const int64_t* ids,
+                                float* logp_out, float* score_out, void* stream) {
+    const char* who = "icz_ensemble_score_captions";
+    Ensemble* e = reinterpret_cast<Ensemble*>(h);
+    // the arguments first: no handle needed to report them (the capacity, the smallest member's, is checked once there is one)
+    ICZ_TRY(check_score_args(who, n_img, n, max_len, e ? e->cap : 0x7fffffff));
+    ICZ_REQUIRE(feats && ids && logp_out && score_out, "%s: null argument", who);
+    ICZ_REQUIRE(e, "%s: null handle", who);
+    return e->score_captions(who, feats, n_img, n, max_len, ids, logp_out, score_out, (hipStream_t)stream);
 }
 
 int icz_ensemble_sample_filter_draw(int32_t M, const float* const* logits, const float* const* bias, const int32_t* nsplit,

@@ -404,7 +404,7 @@ int check_sample_opts(const char* who, const icz_sample_opts* o, int n_img, int 
     return ICZ_OK;
 }
 
-static int ensure_sample_buf(DecodeMember* m, int rows, int T) {
+int ensure_sample_buf(DecodeMember* m, int rows, int T) {
     DecodeMember::SampleBuf& b = m->sb;
     if (b.cap_rows >= rows && b.cap_T >= T) return ICZ_OK;
     DeviceBuffers& mem = m->buffers();

@@ -701,6 +701,42 @@ class BUTDDetection_Eng(Engine):
         return rep
 
 
+    # ---- scoring given captions (an extension; scoring.py, include/icz.h: icz_*_score_captions) ---------------------------------
+    def score_captions_json(self, dataloader, entries, captions_per_image=1, tqdm_visible=True):
+        """The model's log-probability of captions it is handed.  entries: {"image_id", "caption", ...} with captions_per_image
+        (1..8) consecutive entries per image, images in loader order -- what sample_captions_json_generation returns; dataloader: the
+        evaluation loader (image_ids, img_tensors, supp_info_datas).  The words go through the vocabulary's <unk> fallback and
+        <end> is appended.  Returns the entries in order, each extended by "logprob" (the summed log-probability, float), "tokens"
+        (scored tokens, <end> included) and "logprobs" (one per token).  A group whose image_id is not the loader's raises
+        ValueError; every argument error that needs no device is raised before the first batch.  A batch of more than
+        (row capacity // captions_per_image) images is scored in chunks of images.  Not sharded: under torch.distributed every
+        rank scores everything."""
+        entries, n = _check_score_entries(entries, captions_per_image)
+        with _on_stream(self):
+            return _score_entries([self], None, dataloader, entries, n, tqdm_visible)
+
+    def rescore_captions_json(self, dataloader, entries, captions_per_image, length_penalty=None, tqdm_visible=True):
+        """Likelihood reranking: score_captions_json, then of every image the caption with the largest length-penalised
+        log-probability (length_penalty: None, ('avg' | 'wu', alpha), 'avg_<alpha>', 'wu_<alpha>' as beam search's, on the scored
+        tokens with <end> counted, so at least one; ties: the first).  Returns one {"image_id", "caption", "logprob", "rank_score"} per image in
+        entry order, which coco_eval.evaluate_captions takes as it is.  Not sharded: every rank scores everything."""
+        lp = parse_length_penalty(length_penalty)            # a bad penalty raises here, before any device work
+        entries, n = _check_score_entries(entries, captions_per_image)
+        with _on_stream(self):
+            scored = _score_entries([self], None, dataloader, entries, n, tqdm_visible)
+        return _pick_by_likelihood(scored, n, lp)
+
+    def reference_perplexity(self, dataloader, tqdm_visible=True):
+        """The perplexity of a split's reference captions under the model (self-critical.pytorch's eval_split reports it beside
+        CIDEr).  dataloader: the SCST loader (img_ids, img_tensors, img_gts, supp_info_datas) with img_gts[image id] = the image's
+        reference strings.  Every reference of every image is scored; an image with fewer references than its batch's maximum gets
+        empty captions, which score nothing; more than 8 references per image are scored in groups of 8.  Returns {"ppl",
+        "nll_per_token", "tokens", "captions"}: ppl = exp(-sum of log-probabilities / tokens), <end> counted, summed in float64 on
+        the host.  Not sharded: every rank scores everything."""
+        with _on_stream(self):
+            return _reference_perplexity(self, dataloader, tqdm_visible)
+
+
 class AoADetection_Eng(BUTDDetection_Eng):
     """ModelEngines/AoA_Engine.py (same visual-input handling as the BUTD engine) + the three hot Engine methods.
     `use_bu='adaptive'` (10..100 boxes per image, Main.py:158): the handle is sized for 100 regions and every batch carries
@@ -992,3 +1028,153 @@ def consensus_ensemble_captions_json_generation(engines, dataloader, samples_per
     entries = sample_ensemble_captions_json_generation(engines, dataloader, samples_per_image, temperature, top_k, top_p, seed, tqdm_visible,
                                                        weights=weights)
     return lead.rerank_captions_json(entries, samples_per_image)
+
+
+# ---- scoring given captions: what the Engine methods and the ensemble functions share ---------------------------------------------
+def _check_score_entries(entries, captions_per_image):
+    """the argument rules of score_captions_json that need neither an engine nor a device -> (entries as a list, n)"""
+    from .scoring import MAX_WORDS, check_n
+    n = check_n(captions_per_image)
+    try:
+        entries = list(entries)
+    except TypeError:
+        raise ValueError("entries must be a list of {'image_id', 'caption'} dicts") from None
+    if len(entries) % n:
+        raise ValueError("%d entries are not a multiple of %d captions per image" % (len(entries), n))
+    for i, e in enumerate(entries):
+        if not hasattr(e, "keys") or "image_id" not in e or not isinstance(e.get("caption"), str):
+            raise ValueError("entry %d: expected a dict with 'image_id' and a 'caption' string" % i)
+        if len(e["caption"].split()) > MAX_WORDS:
+            raise ValueError("entry %d: caption with %d words: at most %d can be scored" % (i, len(e["caption"].split()), MAX_WORDS))
+        if e["image_id"] != entries[i - i % n]["image_id"]:
+            raise ValueError("entry %d: image_id %r inside the group of image %r" % (i, e["image_id"], entries[i - i % n]["image_id"]))
+    return entries, n
+
+
+def _slice_feats(f, lo, hi):
+    from .aoa import RegionBatch
+    if isinstance(f, RegionBatch):
+        return RegionBatch(f.feats[lo:hi], None if f.counts is None else list(f.counts)[lo:hi])
+    return f[lo:hi]
+
+
+def _score_batch(engines, weights, ens, img_tensors, supp_info_datas, ids, n, ensemble=False):
+    """ids [images x n, T] (numpy) of one loader batch under the one engine, or (ensemble) under the ensemble of the engines ->
+    (logp [rows, T], score [rows]) as numpy arrays, the ensemble handle to keep for the next batch; scored in chunks of images
+    where the rows exceed the handle's capacity"""
+    from .ensemble import EnsembleHandle
+    from .scoring import score_captions
+    feats = []
+    for e in engines:
+        vi = e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
+        feats.append(e._features(vi))
+    handles = [e._hot_handle() for e in engines]
+    if not ensemble:
+        h = handles[0]
+    else:
+        if ens is None or any(a is not b for a, b in zip(ens.handles, handles)):
+            ens = EnsembleHandle(handles, weights)
+        h = ens
+    per = h.max_rows // n
+    if per < 1:
+        raise ValueError("%d captions per image exceed the handle's row capacity %d" % (n, h.max_rows))
+    n_img = ids.shape[0] // n
+    logps, scores = [], []
+    for lo in range(0, n_img, per):
+        hi = min(n_img, lo + per)
+        part = [_slice_feats(f, lo, hi) for f in feats]
+        lp, sc = score_captions(h, part if ensemble else part[0], ids[lo * n:hi * n], n)
+        logps.append(lp.cpu().numpy())
+        scores.append(sc.cpu().numpy())
+    return np.concatenate(logps), np.concatenate(scores), ens
+
+
+def _score_entries(engines, weights, dataloader, entries, n, tqdm_visible, ensemble=False):
+    from .scoring import encode_captions, scored_lengths
+    lead = engines[0]
+    for e in engines:
+        e.model.eval()
+    ens, out, at = None, [], 0
+    for image_ids, img_tensors, supp_info_datas in _monitor(dataloader, "Scoring Process", tqdm_visible):
+        nb = len(image_ids)
+        group = entries[at:at + nb * n]
+        if len(group) != nb * n:
+            raise ValueError("the loader holds more images than the %d entries cover" % len(entries))
+        for j, image_id in enumerate(image_ids):
+            if str(group[j * n]["image_id"]) != str(int(image_id) if not isinstance(image_id, str) else image_id):
+                raise ValueError("entries %d..: image_id %r, but the loader's image is %r" % (at + j * n, group[j * n]["image_id"], image_id))
+        ids = encode_captions([e["caption"] for e in group], lead.caption_vocab)
+        logp, score, ens = _score_batch(engines, weights, ens, img_tensors, supp_info_datas, ids, n, ensemble)
+        lens = scored_lengths(ids)
+        for r, e in enumerate(group):
+            d = dict(e)
+            d["logprob"], d["tokens"], d["logprobs"] = float(score[r]), int(lens[r]), [float(x) for x in logp[r, :lens[r]]]
+            out.append(d)
+        at += nb * n
+    if at != len(entries):
+        raise ValueError("%d entries, but the loader's images cover %d" % (len(entries), at))
+    return out
+
+
+def _pick_by_likelihood(scored, n, lp):
+    kind, alpha = lp
+    out = []
+    for i in range(0, len(scored), n):
+        best, best_rank = None, None
+        for e in scored[i:i + n]:
+            t = e["tokens"]                      # >= 1: <end> is always scored
+            rank = e["logprob"] / (t ** alpha if kind == 1 else ((5 + t) / 6.0) ** alpha if kind == 2 else 1.0)
+            if best is None or rank > best_rank:
+                best, best_rank = e, rank
+        out.append({"image_id": best["image_id"], "caption": best["caption"], "logprob": best["logprob"], "rank_score": float(best_rank)})
+    return out
+
+
+def _reference_perplexity(eng, dataloader, tqdm_visible):
+    from .scoring import MAX_CAPTIONS, encode_captions, scored_lengths
+    eng.model.eval()
+    total, tokens, captions = 0.0, 0, 0
+    for img_ids, img_tensors, img_gts, supp_info_datas in _monitor(dataloader, "Scoring Process", tqdm_visible):
+        refs = [list(img_gts[i]) for i in img_ids]
+        most = max(len(r) for r in refs)
+        for lo in range(0, most, MAX_CAPTIONS):
+            n = min(MAX_CAPTIONS, most - lo)
+            caps = [(r[lo:lo + n] + [None] * n)[:n] for r in refs]
+            ids = encode_captions([c or "" for g in caps for c in g], eng.caption_vocab)
+            for j, c in enumerate(c for g in caps for c in g):
+                if c is None:
+                    ids[j] = 0                   # no reference here: an empty caption, which scores nothing
+            logp, _, _ = _score_batch([eng], None, None, img_tensors, supp_info_datas, ids, n)
+            lens = scored_lengths(ids)
+            total += float(sum(np.sum(logp[r, :lens[r]], dtype=np.float64) for r in range(ids.shape[0])))
+            tokens += int(lens.sum())
+            captions += sum(c is not None for g in caps for c in g)
+    if tokens == 0:
+        raise ValueError("the loader holds no reference caption")
+    nll = -total / tokens
+    return {"ppl": float(np.exp(nll)), "nll_per_token": float(nll), "tokens": tokens, "captions": captions}
+
+
+def score_ensemble_captions_json(engines, dataloader, entries, captions_per_image=1, tqdm_visible=True, *, weights=None):
+    """Engine.score_captions_json for an ensemble of 1..4 engines (BUTD / AoA / NIC) of one vocabulary (an extension; include/icz.h:
+    icz_ensemble_score_captions): every engine turns the shared batch into its own features, and each token's log-probability is
+    that of the averaged word probabilities (`weights`: None = uniform).  Entries, result and errors as the single-model method
+    (the first engine's vocabulary); arguments are checked before any device work (ValueError).  Not sharded: under
+    torch.distributed every rank scores everything."""
+    entries, n = _check_score_entries(entries, captions_per_image)
+    engines = _ensemble_engine_checks(engines, weights)
+    with _on_stream(engines[0]):
+        return _score_entries(engines, weights, dataloader, entries, n, tqdm_visible, ensemble=True)
+
+
+def rescore_ensemble_captions_json(engines, dataloader, entries, captions_per_image, length_penalty=None, tqdm_visible=True, *,
+                                   weights=None):
+    """Engine.rescore_captions_json under an ensemble: of every image the caption the ensemble finds most likely (length_penalty
+    as there; ties: the first) -> one {"image_id", "caption", "logprob", "rank_score"} per image.  Not sharded: every rank scores
+    everything."""
+    lp = parse_length_penalty(length_penalty)
+    entries, n = _check_score_entries(entries, captions_per_image)
+    engines = _ensemble_engine_checks(engines, weights)
+    with _on_stream(engines[0]):
+        scored = _score_entries(engines, weights, dataloader, entries, n, tqdm_visible, ensemble=True)
+    return _pick_by_likelihood(scored, n, lp)
