@@ -268,6 +268,14 @@ int icz_nic_sample(icz_nic_t* h, const float* features, int32_t B, int32_t max_l
                    float* logprobs_out, void* stream);
 int icz_nic_sample_backward(icz_nic_t* h, const float* reward, const icz_nic_params* grads, float* dfeatures_out, float* loss_out,
                             float* mask_sum_out, float mask_sum_global, void* stream);
+/* Beyond the reference (extends icz_nic_sample as icz_butd_sample_n extends icz_butd_sample): the multi-sample rollout -- K = 2..8
+ * sampled captions per image for B images, decoder row = img * K + k, B K <= max_rows.  features [B, E] are expanded to the B K rows on
+ * the device and the rollout runs on those rows: tokens, log-probs and, after icz_nic_sample_backward with a reward [B K, max_len], every
+ * parameter gradient are bitwise those of icz_nic_sample on the features repeated K times (explicit icz_rng arrays are laid out for
+ * B K rows).  seq_out [B K, max_len] int64, logprobs_out [B K, max_len].  dfeatures_out of the backward call is per image, [B, E]: the
+ * K rows' gradients added in k order. */
+int icz_nic_sample_n(icz_nic_t* h, const float* features, int32_t B, int32_t K, int32_t max_len, const icz_rng* rng, int64_t* seq_out,
+                     float* logprobs_out, void* stream);
 /* DecoderRNN.forward, NIC_Model.py:58-98, and LabelSmoothingLoss + backward (Utils.py:268-286) */
 int icz_nic_xe_forward(icz_nic_t* h, const float* features, const int64_t* captions, int32_t B, int32_t L, const int32_t* lengths_host,
                        const icz_rng* rng, int32_t train, float* packed_logits_out, void* stream);
@@ -371,6 +379,18 @@ int icz_aoa_beam_search_diverse(icz_aoa_t* h, const float* feats, int32_t n_img,
                                 float* scores_out, void* stream);
 int icz_aoa_sample(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, const icz_aoa_rng* rng, int64_t* seq_out,
                    float* logprobs_out, void* stream);
+/* Beyond the reference (extends icz_aoa_sample as icz_butd_sample_n extends icz_butd_sample): the multi-sample rollout -- K = 2..8
+ * sampled captions per image for B images, decoder row = img * K + k, B K <= max_rows.  The training-mode refiner pass, the region mean
+ * and the hoisted linear_K / linear_V run ONCE over the B images (the region counts of icz_aoa_set_regions apply); the T decoder steps
+ * run over the B K rows, which find their image through a device index.  Decoder dropout (embedding, ctx, attention, output) and the
+ * draws are indexed by the row in the B K space: explicit masks are [T, B K, ...], uniforms [T, B K]; the refiner's masks are per image.
+ * Row img * K + k draws what row img * K + k of icz_aoa_sample on the features repeated K times (refiner masks repeated too) draws, up to
+ * the rounding of the refiner's GEMMs at another M.  seq_out [B K, max_len] int64, logprobs_out [B K, max_len].
+ * icz_aoa_sample_backward then takes a reward [B K, max_len]: d linear_K / d linear_V are summed per image over its K rows and the steps
+ * in a fixed order, their weight gradients run over the B images' region rows, and with option "train_refiner" the refiner's backward
+ * pass runs over the B images.  Option "graphs" captures the call (K is part of the key, also of the backward pass's). */
+int icz_aoa_sample_n(icz_aoa_t* h, const float* feats, int32_t B, int32_t K, int32_t max_len, const icz_aoa_rng* rng, int64_t* seq_out,
+                     float* logprobs_out, void* stream);
 /* The two decodes of one SCST step (Engine.py:256-261: greedy in eval mode, sampler_rl in train mode) as concurrent chains. */
 int icz_aoa_scst_rollouts(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, const icz_aoa_rng* rng, int64_t* ids_out,
                           int64_t* seq_out, float* logprobs_out, void* stream);

@@ -159,6 +159,7 @@ def lib():
         "icz_nic_refresh_weights": (C.c_int, [vp, vp]),
         "icz_nic_greedy": (C.c_int, [vp, vp, i32, i32, vp, vp]),
         "icz_nic_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(Rng), vp, vp, vp]),
+        "icz_nic_sample_n": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(Rng), vp, vp, vp]),
         "icz_nic_sample_backward": (C.c_int, [vp, vp, C.POINTER(NicParams), vp, vp, vp, f32, vp]),
         "icz_nic_xe_forward": (C.c_int, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Rng), i32, vp, vp]),
         "icz_nic_xe_backward": (C.c_int, [vp, f32, C.POINTER(NicParams), vp, vp, f32, vp]),
@@ -205,6 +206,7 @@ def lib():
         "icz_ensemble_score_tokens": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32, vp,
                                                 vp, vp]),
         "icz_aoa_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),
+        "icz_aoa_sample_n": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),
         "icz_aoa_scst_rollouts": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp, vp]),
         "icz_aoa_sample_backward": (C.c_int, [vp, vp, C.POINTER(AoaParams), vp, vp, f32, vp]),
         "icz_aoa_xe_forward": (C.c_int, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(AoaRng), i32, vp, vp]),

@@ -166,7 +166,7 @@ int Aoa::refine(const float* feats, int n_img, bool train, hipStream_t st, const
     // the input of every layer behind for the backward pass (same kernels, same values)
     const bool store = train && train_refiner;
     if (store) {
-        ICZ_REQUIRE(xs[0] && n_img <= tcap_B, "aoa: the refiner's training buffers are not allocated for %d images", n_img);
+        ICZ_REQUIRE(xs[0] && n_img <= tcap_I, "aoa: the refiner's training buffers are not allocated for %d images", n_img);
         ref_feats = xin; xs_valid = true;
     }
     hipLaunchKernelGGL(relu_drop_kernel, dim3(eb), dim3(256), 0, st, proj ? proj : (const float*)xa, store ? xs[0] : xa, nel,
@@ -223,7 +223,7 @@ int Aoa::refine_pair(int n_img, hipStream_t st, const float* proj) {
     // option "train_refiner": the training half's layer inputs are copied out for the backward pass (7 x nel floats)
     const bool store = train_refiner;
     if (store) {
-        ICZ_REQUIRE(xs[0] && n_img <= tcap_B, "aoa: the refiner's training buffers are not allocated for %d images", n_img);
+        ICZ_REQUIRE(xs[0] && n_img <= tcap_I, "aoa: the refiner's training buffers are not allocated for %d images", n_img);
         ICZ_CHECK_HIP(hipMemcpyAsync(xs[0], w.xa + nel, sizeof(float) * nel, hipMemcpyDeviceToDevice, st));
     }
     const int qc = self_qc(R);

@@ -92,7 +92,7 @@ struct Aoa : CaptionHead, DecodeMember {
     float* amax_val = nullptr; int* amax_idx = nullptr;
     icz_grad_ready_cb grad_cb = nullptr; void* grad_cb_user = nullptr;      // DP overlap hook (icz_aoa_set_grad_callback)
     // training buffers (aoa_train.hip), slot stride = max_rows: th/tm/tctx slot 0 = zeros, slot t+1 = after step t
-    int tcap_B = 0, tcap_T = 0;          // capacity of the training buffers (grown on demand by ensure_train)
+    int tcap_B = 0, tcap_T = 0, tcap_I = 0;      // capacity of the training buffers in decoder rows, steps and images (grown on demand by ensure_train)
     int64_t* tok = nullptr;
     float *th = nullptr, *tm = nullptr, *tctx = nullptr, *temb = nullptr, *tu = nullptr, *tg = nullptr, *tstats = nullptr, *tqn = nullptr,
           *tQp = nullptr, *tP = nullptr, *tPd = nullptr, *tdS = nullptr, *tdX = nullptr, *txatt = nullptr, *tz = nullptr, *tcd = nullptr, *tlogit = nullptr;
@@ -116,7 +116,7 @@ struct Aoa : CaptionHead, DecodeMember {
         rslab_floats = 0; xs_valid = false; ref_feats = nullptr;
     }
     int set_train_refiner(bool on);
-    int alloc_refiner_train(size_t B);
+    int alloc_refiner_train(size_t B, size_t TB);
     int refiner_backward_check(const icz_aoa_params& G) const;      // argument / capacity errors, raised before any launch
     int refiner_backward(const icz_aoa_params& G, hipStream_t st);
     icz_aoa_rng rng = {};
@@ -179,11 +179,18 @@ struct Aoa : CaptionHead, DecodeMember {
         return d;
     }
     // training paths (aoa_train.hip)
-    int ensure_train(int B, int T);
+    int ensure_train(int B, int T, int n_img = 0);
+    // multi-sample SCST rollout (sample_n, beyond the reference): cur_K sampled rows per image, row = img * K + k (1 = every other entry
+    // point; cur_B stays the decoder rows); imgk = the image of each row, allocated by the first sample_n
+    int cur_K = 1;
+    int32_t* imgk = nullptr;
+    int sample_n(const float* feats, int B, int K, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
+    int sample_n_impl(const float* feats, int B, int K, int T, int64_t* seq_out, float* logp_out, hipStream_t st);
     AoaStepIO train_io(int rows, int t, bool train);
     int sample(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
-    int sample_prelude(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
-    int sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st, const float* proj = nullptr, bool refined_ready = false);
+    int sample_prelude(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st, int K = 1);
+    int sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st, const float* proj = nullptr, bool refined_ready = false,
+                    int n_img = 0);
     int sample_backward_impl(const float* reward, const icz_aoa_params& G, float* loss_out, float* msum_out, hipStream_t st);
     int sample_backward(const float* reward, const icz_aoa_params* G, float* loss_out, float* msum_out, float msum_global, hipStream_t st);
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_aoa_rng* r, int train,

@@ -541,15 +541,22 @@ __global__ __launch_bounds__(256) void mean_rows_kernel(const float* __restrict_
 // Each refiner layer is recomputed from its stored input in front of its backward step, so these kernels read the forward buffers of
 // that one layer (ln, qkv, z) and regenerate the dropout draws from the indices the forward pass used.
 
-// d meanf[b, c] = sum over steps (then slabs) of du[t, b, c]: u_t = meanf + drop(ctx) (AoA_Model.py:321-323).  du = slabs [ns][T B][Hd]
-// of d gates . W_ih[:, E:]; rows of steps that never ran / rows b >= rows_t[t] hold exact zeros (their d gates are zero).
-__global__ __launch_bounds__(256) void aoa_dmean_kernel(const float* __restrict__ du, int ns, int T, int B, int Hd, float* __restrict__ dmean) {
+// d meanf[img, c] = sum over steps (then slabs) of du[t, row, c]: u_t = meanf + drop(ctx) (AoA_Model.py:321-323).  du = slabs [ns][T B][Hd]
+// of d gates . W_ih[:, E:] over B decoder rows; rows of steps that never ran / rows b >= rows_t[t] hold exact zeros (their d gates are zero).
+// G > 1 (multi-sample rollout, Aoa::sample_n): the rows img * G + k share the image's meanf -- their time sums are added in k order.
+__global__ __launch_bounds__(256) void aoa_dmean_kernel(const float* __restrict__ du, int ns, int T, int B, int Hd, float* __restrict__ dmean,
+                                                        int G = 1) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)B * Hd) return;
-    const size_t MN = (size_t)T * B * Hd;
-    float s = 0.f;
-    for (int t = 0; t < T; ++t) s += sum_slabs1(du, ns, MN, (size_t)t * B * Hd + i);
-    dmean[i] = s;
+    if (i >= (size_t)(B / G) * Hd) return;
+    const size_t MN = (size_t)T * B * Hd, img = i / Hd, c = i % Hd;
+    float tot = 0.f;
+    for (int k = 0; k < G; ++k) {
+        const size_t o = (img * G + k) * Hd + c;
+        float s = 0.f;
+        for (int t = 0; t < T; ++t) s += sum_slabs1(du, ns, MN, (size_t)t * B * Hd + o);
+        tot = k == 0 ? s : tot + s;
+    }
+    dmean[i] = tot;
 }
 
 // d refined[row, c] = (dKd k_w)[row, c] + (dVd v_w)[row, c] + d meanf[img, c] / count(img)     (grid (Hd / 256, n_img))

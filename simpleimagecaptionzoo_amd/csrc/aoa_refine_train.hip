@@ -16,7 +16,7 @@ int Aoa::set_train_refiner(bool on) {
     ICZ_TRY(mem.release_training(&gc));
     ICZ_CHECK_HIP(hipDeviceSynchronize());
     gc.clear();
-    tcap_B = tcap_T = 0;
+    tcap_B = tcap_T = tcap_I = 0;
     drop_loss_buffers();
     drop_refiner_buffers();
     train_refiner = on;
@@ -24,8 +24,8 @@ int Aoa::set_train_refiner(bool on) {
     return ICZ_OK;
 }
 
-// called inside ensure_train's TrainingScope: released with the other training buffers
-int Aoa::alloc_refiner_train(size_t B) {
+// called inside ensure_train's TrainingScope: released with the other training buffers.  B = images, TB = steps x decoder rows
+int Aoa::alloc_refiner_train(size_t B, size_t TB) {
     const size_t RR = B * dims.R, Hd = dims.Hd;
     for (float*& p : xs) ICZ_TRY(alloc((void**)&p, sizeof(float) * RR * Hd));
     float** one[] = {&rdx[0], &rdx[1], &rdo, &rdln, &rdq, &rprod};
@@ -33,8 +33,10 @@ int Aoa::alloc_refiner_train(size_t B) {
     ICZ_TRY(alloc((void**)&rdz, sizeof(float) * RR * 2 * Hd));
     ICZ_TRY(alloc((void**)&rdqkv, sizeof(float) * RR * 3 * Hd));
     ICZ_TRY(alloc((void**)&rdmean, sizeof(float) * B * Hd));
-    // split-K slabs of the dgrad products: two slabs of the widest one (rows x 2Hd) and the small-launch reserve of the decoder's slabs
-    rslab_floats = (size_t)TARGET_WGS * 4096 * 2 + 2 * RR * 2 * Hd;
+    // split-K slabs of the dgrad products: two slabs of the widest one (rows x 2Hd) -- or one of d u over all (t, row), which the K rows per
+    // image of a multi-sample rollout can make the larger -- and the small-launch reserve of the decoder's slabs
+    const size_t widest = 2 * RR * 2 * Hd > TB * Hd ? 2 * RR * 2 * Hd : TB * Hd;
+    rslab_floats = (size_t)TARGET_WGS * 4096 * 2 + widest;
     ICZ_TRY(alloc((void**)&rslab, sizeof(float) * rslab_floats));
     const size_t lds = sizeof(float) * mha_self_bwd_lds_floats(dims.R, dims.Hd / dims.NH);
     if (lds > 48 * 1024)      // (a narrower batch may fit where the handle's capacity does not: refiner_backward_check decides per call)
@@ -82,17 +84,19 @@ int rnn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, 
 
 int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
     use_bank(1);
-    const int B = cur_B, T = cur_T, Hd = dims.Hd, E = dims.E, NH = dims.NH, R = cur_R, D = dims.D, TB = T * B;
+    // B = images; behind the multi-sample rollout (sample_n) the decoder ran cur_K rows per image: only d meanf tells rows from images
+    const int K = cur_K, B = cur_B / K, T = cur_T, Hd = dims.Hd, E = dims.E, NH = dims.NH, R = cur_R, D = dims.D, TB = T * cur_B;
     const int rows = (int)region_row_count(B);
     const RegionRows rr = region_rows();
     const size_t nel = (size_t)rows * Hd;
     const unsigned eb = (unsigned)((nel + 255) / 256);
     const bool train = cur_train;
-    // ---- 1. d refined = dKd k_w + dVd v_w + d meanf / count;  d meanf[b] = sum_t du_t[b], du = d gates . W_ih[:, E:] over all (t, b) rows
+    // ---- 1. d refined = dKd k_w + dVd v_w + d meanf / count;  d meanf[img] = sum over the image's rows and t of du_t[row], du = d gates . W_ih[:, E:]
+    //         over all (t, row) rows
     //         (the rows of steps that never ran and rows b >= rows_t[t] hold zero d gates: bptt zeroed them in front of its loop)
     int nsu = 1, nsk = 1, nsv = 1;
     ICZ_TRY(rnn(dG, 4 * Hd, TB, 4 * Hd, P.lstm_w_ih + E, E + Hd, Hd, rslab, rslab_floats, &nsu, st));
-    hipLaunchKernelGGL(aoa_dmean_kernel, dim3((unsigned)(((size_t)B * Hd + 255) / 256)), dim3(256), 0, st, rslab, nsu, T, B, Hd, rdmean);
+    hipLaunchKernelGGL(aoa_dmean_kernel, dim3((unsigned)(((size_t)B * Hd + 255) / 256)), dim3(256), 0, st, rslab, nsu, T, cur_B, Hd, rdmean, K);
     const size_t half = rslab_floats / 2;
     ICZ_TRY(rnn(dKd, Hd, rows, Hd, P.dec.k_w, Hd, Hd, rslab, half, &nsk, st));
     ICZ_TRY(rnn(dVd, Hd, rows, Hd, P.dec.v_w, Hd, Hd, rslab + half, half, &nsv, st));

@@ -34,7 +34,8 @@ __global__ __launch_bounds__(256) void aoa_glu_bwd_kernel(const float* __restric
     dz[row * 2 * Hd + Hd + c] = d * a * s * (1.f - s);
 }
 
-// Decoder attention backward, one workgroup per (row, head); row b attends image b (training paths have no beams).
+// Decoder attention backward, one workgroup per (row, head); row b attends image b, or image img_of_row[b] behind the multi-sample
+// rollout (Aoa::sample_n: K rows per image, which share the image's K / V tiles and region count).
 //   dPd_r = dx_h . V_h[r];  dP = keep/(1-p) * dPd;  dS = P (dP - sum P dP);  dQ_h = sum_r dS_r K_h[r] / sqrt(d)
 // dK_h[r] = sum_t dS_t[r] Q_t,h / sqrt(d) and dV_h[r] = sum_t Pd_t[r] dx_t,h are sums over time: the steps only record dS_t
 // (already scaled by 1/sqrt(d)) and dx_t, and aoa_dkv_kernel forms both sums once after the loop -- accumulating them
@@ -44,7 +45,8 @@ __global__ __launch_bounds__(256) void aoa_dec_attn_bwd_kernel(const float* __re
                                                                const float* __restrict__ Pdm, const float* __restrict__ Qp,
                                                                const float* __restrict__ Kd, const float* __restrict__ Vd,
                                                                float* __restrict__ dQp, float* __restrict__ dS_out, float* __restrict__ dx_out, int R, int Hd,
-                                                               int NH, RegionRows rr, float keep_scale, const int* __restrict__ live = nullptr) {
+                                                               int NH, RegionRows rr, float keep_scale, const int* __restrict__ live = nullptr,
+                                                               const int32_t* __restrict__ img_of_row = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float sm_db[];    // K tile, V tile [R][d+1], q [d], dx [d], dS [128], red [4]
     if (step_dead(live)) return;
     const int row = blockIdx.x, hd = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -55,8 +57,9 @@ __global__ __launch_bounds__(256) void aoa_dec_attn_bwd_kernel(const float* __re
     float* sdx = sq + d;
     float* sds = sdx + d;
     float* red = sds + 128;
-    const int len = rr.count(row);
-    const size_t base = rr.first(row) * Hd + (size_t)hd * d;
+    const int img = img_of_row ? img_of_row[row] : row;
+    const int len = rr.count(img);
+    const size_t base = rr.first(img) * Hd + (size_t)hd * d;
     aoa_stage_kv<256>(Kd + base, Vd + base, sk, sv, len, d, Hd, tid);
     const size_t MN = (size_t)rows * 2 * Hd;
     for (int j = tid; j < d; j += 256) {
@@ -90,12 +93,15 @@ __global__ __launch_bounds__(256) void aoa_dec_attn_bwd_kernel(const float* __re
     }
 }
 
-// dKd[img, r, head cols] = sum_t dS_t[img, head, r] Qp_t[img, head cols];  dVd = sum_t Pd_t[r] dx_t   (grid (B, NH), 256 threads).
-// The steps go through LDS in chunks of TC (all of them at the usual 20 steps x 36 regions).
+// dKd[img, r, head cols] = sum_t dS_t[row, head, r] Qp_t[row, head cols];  dVd = sum_t Pd_t[r] dx_t   (grid (n_img, NH), 256 threads).
+// B = decoder rows per step, G = rows per image: the image's rows are img * G + k (G = 1: row b is image b; G > 1: the multi-sample
+// rollout, Aoa::sample_n, whose K rows of an image add into the image's d K / d V).  The (k, t) pairs are walked k-major, t-minor and go
+// through LDS in chunks of TC pairs (all of them at the usual 20 steps x 36 regions of one row): one workgroup owns the (image, head)
+// slice, so the sum has a fixed order and needs no atomics.
 __global__ __launch_bounds__(256) void aoa_dkv_kernel(const float* __restrict__ dS_all, const float* __restrict__ Pd_all,
                                                       const float* __restrict__ Qp_all, const float* __restrict__ dx_all,
                                                       float* __restrict__ dKd, float* __restrict__ dVd, int B, int T, int TC, int R, int Hd, int NH,
-                                                      RegionRows rr) {
+                                                      RegionRows rr, int G) {
     extern __shared__ __attribute__((aligned(16))) float sm_kv[];       // dS [TC][R], Pd [TC][R], Qp [TC][d], dx [TC][d]
     const int img = blockIdx.x, hd = blockIdx.y, tid = threadIdx.x;
     const int d = Hd / NH;
@@ -105,17 +111,18 @@ __global__ __launch_bounds__(256) void aoa_dkv_kernel(const float* __restrict__ 
     float* sdx = sq + TC * d;
     const size_t base = rr.first(img) * Hd + (size_t)hd * d;
     const int len = rr.count(img);
-    for (int t0 = 0; t0 < T; t0 += TC) {
-        const int nt = min(TC, T - t0);
+    const int S = G * T;                // (k, t) pairs of the image: pair s = k * T + t is row img * G + k at step t
+    for (int s0 = 0; s0 < S; s0 += TC) {
+        const int nt = min(TC, S - s0);
         for (int i = tid; i < nt * R; i += 256) {
-            const int t = t0 + i / R, r = i % R;
-            const size_t g = (((size_t)t * B + img) * NH + hd) * R + r;
+            const int sp = s0 + i / R, r = i % R, k = sp / T, t = sp - k * T;
+            const size_t g = (((size_t)t * B + (size_t)img * G + k) * NH + hd) * R + r;
             sds[i] = dS_all[g];
             spd[i] = Pd_all[g];
         }
         for (int i = tid; i < nt * d; i += 256) {
-            const int t = t0 + i / d, j = i % d;
-            const size_t g = ((size_t)t * B + img) * Hd + (size_t)hd * d + j;
+            const int sp = s0 + i / d, j = i % d, k = sp / T, t = sp - k * T;
+            const size_t g = ((size_t)t * B + (size_t)img * G + k) * Hd + (size_t)hd * d + j;
             sq[i] = Qp_all[g];
             sdx[i] = dx_all[g];
         }
@@ -123,7 +130,7 @@ __global__ __launch_bounds__(256) void aoa_dkv_kernel(const float* __restrict__ 
         for (int i = tid; i < len * d; i += 256) {
             const int r = i / d, j = i % d;
             const size_t o = base + (size_t)r * Hd + j;
-            float dk = t0 ? dKd[o] : 0.f, dv = t0 ? dVd[o] : 0.f;
+            float dk = s0 ? dKd[o] : 0.f, dv = s0 ? dVd[o] : 0.f;
             for (int t = 0; t < nt; ++t) {
                 dk += sds[t * R + r] * sq[t * d + j];
                 dv += spd[t * R + r] * sdx[t * d + j];
@@ -203,21 +210,24 @@ __global__ __launch_bounds__(256) void aoa_ln_prod_kernel(const float* __restric
 
 // Training buffers sized by what the batches ask for (the reference never truncates captions, Datasets.py:47-51: the step
 // count of an XE batch is only known when it arrives); growing re-allocates them all.
-int Aoa::ensure_train(int Bq, int Tq) {
-    if (Bq <= tcap_B && Tq <= tcap_T) return ICZ_OK;
+// Bq = decoder rows, Iq = images (< Bq behind the multi-sample rollout, whose per-image tensors stay sized per image; 0 = one row per image)
+int Aoa::ensure_train(int Bq, int Tq, int Iq) {
+    if (Iq <= 0) Iq = Bq;
+    if (Bq <= tcap_B && Tq <= tcap_T && Iq <= tcap_I) return ICZ_OK;
     ICZ_REQUIRE(dims.Hd <= 4096, "aoa: training paths keep a LayerNorm row in registers (hidden size %d > 4096)", dims.Hd);
     ICZ_REQUIRE(Tq <= XE_MAX_T, "aoa: %d steps exceed the limit of %d", Tq, XE_MAX_T);
     if (tcap_B > Bq) Bq = tcap_B;
     if (tcap_T > Tq) Tq = tcap_T;
+    if (tcap_I > Iq) Iq = tcap_I;
     if (dims.max_len > Tq) Tq = dims.max_len;
     if (!mem.training.empty()) {
         ICZ_TRY(mem.release_training(&gc));
-        tcap_B = tcap_T = 0;
+        tcap_B = tcap_T = tcap_I = 0;
         drop_loss_buffers();
         drop_refiner_buffers();
     }
     DeviceBuffers::TrainingScope scope(mem);
-    const size_t B = Bq, T = Tq, Hd = dims.Hd, E = dims.E, R = dims.R, NH = dims.NH;
+    const size_t B = Bq, T = Tq, I = Iq, Hd = dims.Hd, E = dims.E, R = dims.R, NH = dims.NH;
     {
         const size_t dh = Hd / NH, lds_bwd = sizeof(float) * (2 * R * (dh + 1) + 2 * dh + 128 + 4);
         if (lds_bwd > 48 * 1024)
@@ -241,8 +251,8 @@ int Aoa::ensure_train(int Bq, int Tq) {
     ICZ_TRY(alloc((void**)&tdS, sizeof(float) * TB * NH * R));
     ICZ_TRY(alloc((void**)&tlogit, sizeof(float) * TB * Vp));
     ICZ_TRY(alloc((void**)&dEmb, sizeof(float) * TB * E));
-    ICZ_TRY(alloc((void**)&dKd, sizeof(float) * B * R * Hd));
-    ICZ_TRY(alloc((void**)&dVd, sizeof(float) * B * R * Hd));
+    ICZ_TRY(alloc((void**)&dKd, sizeof(float) * I * R * Hd));
+    ICZ_TRY(alloc((void**)&dVd, sizeof(float) * I * R * Hd));
     ICZ_TRY(alloc((void**)&dHln, sizeof(float) * B * Hd));
     ICZ_TRY(alloc((void**)&dcb[0], sizeof(float) * B * Hd));
     ICZ_TRY(alloc((void**)&dcb[1], sizeof(float) * B * Hd));
@@ -251,9 +261,9 @@ int Aoa::ensure_train(int Bq, int Tq) {
     ICZ_TRY(alloc((void**)&X2, sizeof(float) * xfloats));
     ICZ_TRY(alloc((void**)&dWp, sizeof(float) * (size_t)Vp * Hd));
     ICZ_TRY(alloc_loss_buffers(mem, TB, B, T));
-    if (train_refiner) ICZ_TRY(alloc_refiner_train(B));
+    if (train_refiner) ICZ_TRY(alloc_refiner_train(I, TB));
     ICZ_TRY(mem.synced());
-    tcap_B = Bq; tcap_T = Tq;
+    tcap_B = Bq; tcap_T = Tq; tcap_I = Iq;
     return ICZ_OK;
 }
 
@@ -262,7 +272,7 @@ AoaStepIO Aoa::train_io(int rows, int t, bool train) {
     const size_t B = cur_B, Hd = dims.Hd, E = dims.E, NH = dims.NH, R = cur_R;
     const size_t s0 = (size_t)t * B, s1 = s0 + B;
     AoaStepIO s = {};
-    s.rows = rows; s.img_of_row = nullptr; s.it = tok + s0; s.emb_ready = false;
+    s.rows = rows; s.img_of_row = cur_K > 1 ? imgk : nullptr; s.it = tok + s0; s.emb_ready = false;
     s.h_in = th + s0 * Hd; s.m_in = tm + s0 * Hd; s.ctx_in = tctx + s0 * Hd;
     s.h_out = th + s1 * Hd; s.m_out = tm + s1 * Hd; s.ctx_out = tctx + s1 * Hd;
     s.emb = temb + s0 * E; s.u = tu + s0 * Hd; s.gates_out = tg + s0 * 4 * Hd; s.ln_stats = tstats + s0 * 2;
@@ -275,12 +285,18 @@ AoaStepIO Aoa::train_io(int rows, int t, bool train) {
     return s;
 }
 
+static bool aoa_explicit_rng(const icz_aoa_rng& r) {
+    return r.uniforms || r.proj_mask || r.ref_att_mask || r.ref_aoa_mask || r.ref_sc_mask || r.emb_mask || r.ctx_mask || r.att_mask || r.out_mask;
+}
+
 // everything of a sampled rollout that is host state or must not sit inside a captured graph: buffers, the Philox seed in device
 // memory, what the backward pass will read back
-int Aoa::sample_prelude(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st) {
+// B = decoder rows; K > 1: the multi-sample rollout's B / K images with K rows each
+int Aoa::sample_prelude(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st, int K) {
     ICZ_REQUIRE(feats && seq_out && logp_out && r && B > 0 && B <= dims.max_rows && T > 0, "aoa sample: bad arguments");
     ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
-    ICZ_TRY(ensure_train(B, T));
+    ICZ_TRY(ensure_train(B, T, B / K));
+    cur_K = K;
     rng = *r;
     hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
     mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_seq = seq_out; cur_logp = logp_out;
@@ -294,9 +310,43 @@ int Aoa::sample(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t*
     return sample_impl(feats, B, T, seq_out, logp_out, st);
 }
 
-int Aoa::sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st, const float* proj, bool refined_ready) {
+// Multi-sample rollout (beyond the reference: K sampled captions per image, the "new self-critical" variant): the training-mode refiner
+// pass, its region mean and the hoisted linear_K / linear_V run once over the B images, the sampled chain over B K decoder rows,
+// row = img * K + k, whose kernels find their image through imgk (train_io).  Dropout keep-bits and draws are indexed by the row in the
+// B K space -- row img * K + k gets what row img * K + k of sample(feats.repeat_interleave(K, 0)) gets; the refiner's by the image.
+int Aoa::sample_n(const float* feats, int B, int K, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st) {
+    ICZ_REQUIRE(feats && seq_out && logp_out && r, "aoa sample_n: null argument");
+    ICZ_REQUIRE(K >= 2 && K <= SAMPLE_N_MAX_K, "aoa sample_n: K=%d samples per image outside 2..%d", K, SAMPLE_N_MAX_K);
+    ICZ_REQUIRE(B > 0 && T > 0, "aoa sample_n: bad B/T");
+    ICZ_REQUIRE((int64_t)B * K <= dims.max_rows, "aoa sample_n: %d images x %d samples exceed the row capacity %d", B, K, dims.max_rows);
+    ICZ_REQUIRE(!lens || lens_n == B, "aoa: region counts were set for %d images, the batch has %d (icz_aoa_set_regions)", lens_n, B);
+    ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
+    const int rows = B * K;
+    if (!imgk) {
+        ICZ_TRY(alloc((void**)&imgk, sizeof(int32_t) * (size_t)dims.max_rows));
+        ICZ_TRY(mem.synced());
+    }
+    ICZ_TRY(sample_prelude(feats, rows, T, r, seq_out, logp_out, st, K));
+    // host state, outside any captured graph (a replay runs no host code): the bank's own tensors, what the refiner's backward will read
+    point_bank_at_own(1);
     use_bank(1);
-    if (!refined_ready) ICZ_TRY(refine(feats, B, true, st, proj));
+    if (train_refiner && !lens) { ref_feats = feats; xs_valid = true; }
+    if (!use_graphs || lens || aoa_explicit_rng(rng)) return sample_n_impl(feats, B, K, T, seq_out, logp_out, st);
+    const std::vector<uintptr_t> key = {3, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)K, (uintptr_t)T, (uintptr_t)cur_R, (uintptr_t)seq_out,
+                                        (uintptr_t)logp_out, (uintptr_t)train_refiner, (uintptr_t)xs[0]};
+    return gc.run(key, st, [&](hipStream_t s) { return sample_n_impl(feats, B, K, T, seq_out, logp_out, s); });
+}
+
+int Aoa::sample_n_impl(const float* feats, int B, int K, int T, int64_t* seq_out, float* logp_out, hipStream_t st) {
+    hipLaunchKernelGGL(row_image_kernel, dim3(cdiv(B * K, 256)), dim3(256), 0, st, imgk, B * K, K);
+    return sample_impl(feats, B * K, T, seq_out, logp_out, st, nullptr, false, B);
+}
+
+// B = decoder rows of n_img images (0 = one row per image)
+int Aoa::sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st, const float* proj, bool refined_ready,
+                     int n_img) {
+    use_bank(1);
+    if (!refined_ready) ICZ_TRY(refine(feats, n_img > 0 ? n_img : B, true, st, proj));
     const size_t sH = (size_t)B * dims.Hd;
     ICZ_CHECK_HIP(hipMemsetAsync(th, 0, sizeof(float) * sH, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tm, 0, sizeof(float) * sH, st));
@@ -333,10 +383,6 @@ int Aoa::sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* 
     }
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
-}
-
-static bool aoa_explicit_rng(const icz_aoa_rng& r) {
-    return r.uniforms || r.proj_mask || r.ref_att_mask || r.ref_aoa_mask || r.ref_sc_mask || r.emb_mask || r.ctx_mask || r.att_mask || r.out_mask;
 }
 
 // Greedy baseline (evaluation mode, bank 0, side stream) and sampled rollout (training mode, bank 1) of one SCST step
@@ -399,7 +445,7 @@ int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* lo
     // with a DP callback the hook must fire on every call: eager launches (a replayed graph would not call it)
     if (!use_graphs || lens || grad_cb || aoa_explicit_rng(rng)) return sample_backward_impl(reward, *G, loss_out, msum_out, st);
     std::vector<uintptr_t> key = {2, (uintptr_t)reward, (uintptr_t)loss_out, (uintptr_t)msum_out, (uintptr_t)cur_B, (uintptr_t)cur_T, (uintptr_t)cur_R,
-                                  (uintptr_t)cur_seq, (uintptr_t)cur_logp,
+                                  (uintptr_t)cur_seq, (uintptr_t)cur_logp, (uintptr_t)cur_K,      // sample_n of B K rows against sample of B K rows: other launches
                                   (uintptr_t)bank[0].refined, (uintptr_t)bank[0].Kd, (uintptr_t)bank[1].refined, (uintptr_t)bank[1].Kd, (uintptr_t)bank[1].Vd, (uintptr_t)cur_bank,      // paired-refine banks (rollouts) or the handle's own (sample)
                                   (uintptr_t)train_refiner, (uintptr_t)xs[0], (uintptr_t)ref_feats};      // the refiner's backward pass behind bptt
     const float* const* gp = reinterpret_cast<const float* const*>(G);
@@ -421,6 +467,7 @@ int Aoa::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
     int T = 0;
     ICZ_TRY(xe_steps("aoa", lengths, B, L, &T));
     ICZ_TRY(ensure_train(B, T));
+    cur_K = 1;
     use_bank(1);
     if (r) rng = *r; else rng = {};
     begin_xe(lengths, B, T, L, captions, train != 0, rng.seed, st);
@@ -501,6 +548,10 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     const int B = cur_B, T = cur_T, Hd = dims.Hd, E = dims.E, V = dims.V, NH = dims.NH, R = cur_R, dh = Hd / NH;
     const int TB = T * B;
     const size_t sH = (size_t)B * Hd;
+    // behind sample_n: K rows per image (row = img * K + k) -- the attention backward finds the image's K / V tiles through imgk, and
+    // d K / d V are summed per image over its rows and the steps; everything over (t, row) simply sees B = n_img K rows
+    const int K = cur_K, n_img = B / K;
+    const int32_t* const rows_img = K > 1 ? imgk : nullptr;
     int ns = 1;
     // backward of a sampled rollout: the steps behind the reference's break (AoA_Model.py:400) never ran -- their kernels return at
     // entry (the buffers the batched GEMMs read are zeroed in front of the loop) and the GEMMs over all (t, b) stop behind the last live step
@@ -560,7 +611,7 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
         int ns2 = 1, nsq = 1;
         ICZ_TRY(nn(dZ + s0 * 2 * Hd, 2 * Hd, bt, 2 * Hd, P.dec.aoa_w, 2 * Hd, 2 * Hd, X2, xfloats, &ns2, STEP_WGS, st, live));
         hipLaunchKernelGGL(aoa_dec_attn_bwd_kernel, dim3(bt, NH), dim3(256), lds, st, X2, ns2, bt, tP + s0 * NH * R, tPd + s0 * NH * R,
-                           tQp + s0 * Hd, Kd, Vd, dQp + s0 * Hd, tdS + s0 * NH * R, tdX + s0 * Hd, R, Hd, NH, region_rows(), io.d_att.mode ? io.d_att.scale : 1.0f, live);
+                           tQp + s0 * Hd, Kd, Vd, dQp + s0 * Hd, tdS + s0 * NH * R, tdX + s0 * Hd, R, Hd, NH, region_rows(), io.d_att.mode ? io.d_att.scale : 1.0f, live, rows_img);
         ICZ_TRY(nn(dQp + s0 * Hd, Hd, bt, Hd, P.dec.q_w, Hd, Hd, ws, ws_floats, &nsq, STEP_WGS, st, live));
         hipLaunchKernelGGL(aoa_ln_bwd_kernel, dim3(bt), dim3(256), 0, st, ws, nsq, X2, ns2, bt, th + (s0 + B) * Hd, tstats + s0 * 2,
                            P.dec.ln_g, dQn + s0 * Hd, dHln, Hd, live);
@@ -622,11 +673,11 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     ICZ_TRY(tn(dQp, Hd, Hd, tqn, Hd, Hd, TB, G.dec.q_w, Hd, 0, ts, rl));
     ICZ_TRY(colsum(dQp, TB, Hd, Hd, G.dec.q_b, ts));
     {
-        const int tc_fit = (int)(48 * 1024 / (sizeof(float) * 2 * (R + dh))), tc = T < tc_fit ? T : tc_fit;
-        hipLaunchKernelGGL(aoa_dkv_kernel, dim3(B, NH), dim3(256), sizeof(float) * (size_t)tc * 2 * (R + dh), ts, tdS, tPd, tQp, tdX, dKd, dVd, B, T,
-                           tc, R, Hd, NH, region_rows());
+        const int tc_fit = (int)(48 * 1024 / (sizeof(float) * 2 * (R + dh))), tc = K * T < tc_fit ? K * T : tc_fit;
+        hipLaunchKernelGGL(aoa_dkv_kernel, dim3(n_img, NH), dim3(256), sizeof(float) * (size_t)tc * 2 * (R + dh), ts, tdS, tPd, tQp, tdX, dKd, dVd, B, T,
+                           tc, R, Hd, NH, region_rows(), K);
     }
-    const int rrows = (int)region_row_count(B);      // region rows of the batch (packed valid rows with per-image counts)
+    const int rrows = (int)region_row_count(n_img);      // region rows of the batch (packed valid rows with per-image counts)
     ICZ_TRY(tn(dKd, Hd, Hd, refined, Hd, Hd, rrows, G.dec.k_w, Hd, 0, ts));
     ICZ_TRY(colsum(dKd, rrows, Hd, Hd, G.dec.k_b, ts));
     ICZ_TRY(tn(dVd, Hd, Hd, refined, Hd, Hd, rrows, G.dec.v_w, Hd, 0, ts));
@@ -664,6 +715,12 @@ int icz_aoa_sample(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len,
                    float* logprobs_out, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Aoa*>(h)->sample(feats, B, max_len, rng, seq_out, logprobs_out, (hipStream_t)stream);
+}
+int icz_aoa_sample_n(icz_aoa_t* h, const float* feats, int32_t B, int32_t K, int32_t max_len, const icz_aoa_rng* rng, int64_t* seq_out,
+                     float* logprobs_out, void* stream) {
+    ICZ_REQUIRE(K >= 2 && K <= SAMPLE_N_MAX_K, "icz_aoa_sample_n: K=%d samples per image outside 2..%d", K, SAMPLE_N_MAX_K);
+    ICZ_REQUIRE(h, "icz_aoa_sample_n: null handle");
+    return reinterpret_cast<Aoa*>(h)->sample_n(feats, B, K, max_len, rng, seq_out, logprobs_out, (hipStream_t)stream);
 }
 int icz_aoa_scst_rollouts(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, const icz_aoa_rng* rng, int64_t* ids_out,
                           int64_t* seq_out, float* logprobs_out, void* stream) {

@@ -1792,6 +1792,13 @@ __global__ __launch_bounds__(256) void rowgroup_sum_kernel(const float* __restri
     *reinterpret_cast<f32x4*>(out + i) = s;
 }
 
+constexpr int SAMPLE_N_MAX_K = 8;      // rows per image of the AoA / NIC multi-sample rollouts (icz_aoa_sample_n, icz_nic_sample_n)
+// img[row] = row / G: the image of each decoder row of a multi-sample rollout (row = img * G + k; the AoA and NIC rollouts)
+__global__ void row_image_kernel(int32_t* __restrict__ img, int rows, int G) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rows) img[i] = i / G;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // out[n] = sum_k X[k, n] (column sums over K rows; bias gradients) in one launch, fixed order -> reproducible.
 // Grid (N/32), 256 threads = 32 columns x 8 row groups: thread (c, g) adds rows g, g+8, ... of its column (eight independent

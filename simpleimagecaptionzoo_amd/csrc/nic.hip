@@ -30,6 +30,11 @@ struct Nic : CaptionHead, DecodeMember {
     float *dG = nullptr, *dHd = nullptr, *dEmb = nullptr, *dcb[2] = {nullptr, nullptr}, *X = nullptr, *dWp = nullptr;
     size_t xfloats = 0;
     float* feat_rows = nullptr;          // beam search: the image embedding replicated per beam row (prologue)
+    // multi-sample SCST rollout (sample_n, beyond the reference): cur_K sampled rows per image, row = img * K + k (1 = every other entry
+    // point); the rollout runs on the image embeddings expanded to the rows, the backward pass folds d features back onto the images
+    int cur_K = 1;
+    int32_t* imgk = nullptr;             // image of each decoder row
+    float *feat_n = nullptr, *dfeat_n = nullptr;      // [max_rows, E]: the expanded embeddings (kept for the backward pass), their gradient per row
     icz_rng rng = {};
     const float* cur_feats = nullptr;
 
@@ -44,6 +49,7 @@ struct Nic : CaptionHead, DecodeMember {
     int greedy(const float* feats, int B, int T, int64_t* ids_out, hipStream_t st);
     int ensure_train(int B, int T);
     int sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
+    int sample_n(const float* feats, int B, int K, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
     int sample_backward(const float* reward, const icz_nic_params* G, float* dfeats, float* loss_out, float* msum_out, float msum_global, hipStream_t st);
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r, int train,
                    float* packed_out, hipStream_t st);
@@ -211,6 +217,7 @@ int Nic::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq
     rng = *r;
     hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
     mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_feats = feats; cur_seq = seq_out; cur_logp = logp_out;
+    cur_K = 1;
     rows_t.assign(T, B);
     const size_t H = dims.H, E = dims.E, sH = (size_t)B * H;
     ICZ_CHECK_HIP(hipMemsetAsync(th, 0, sizeof(float) * sH, st));
@@ -238,6 +245,29 @@ int Nic::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq
     return ICZ_OK;
 }
 
+// Multi-sample rollout (beyond the reference: K sampled captions per image): the image embeddings are expanded to the B K decoder rows,
+// row = img * K + k, with the kernel the beam-search prologue uses, and the sampled rollout runs on those rows -- every launch is the
+// launch of sample() on the embeddings repeated K times, so tokens, log-probs and parameter gradients are bitwise that call's.
+int Nic::sample_n(const float* feats, int B, int K, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st) {
+    ICZ_REQUIRE(feats && seq_out && logp_out && r, "nic sample_n: null argument");
+    ICZ_REQUIRE(K >= 2 && K <= SAMPLE_N_MAX_K, "nic sample_n: K=%d samples per image outside 2..%d", K, SAMPLE_N_MAX_K);
+    ICZ_REQUIRE(B > 0 && T > 0, "nic sample_n: bad B/T");
+    ICZ_REQUIRE((int64_t)B * K <= dims.max_rows, "nic sample_n: %d images x %d samples exceed the row capacity %d", B, K, dims.max_rows);
+    ICZ_REQUIRE(fresh, "nic: call icz_nic_refresh_weights after binding/updating parameters");
+    const int rows = B * K;
+    if (!imgk) {
+        ICZ_TRY(alloc((void**)&imgk, sizeof(int32_t) * (size_t)dims.max_rows));
+        ICZ_TRY(alloc((void**)&feat_n, sizeof(float) * (size_t)dims.max_rows * dims.E));
+        ICZ_TRY(alloc((void**)&dfeat_n, sizeof(float) * (size_t)dims.max_rows * dims.E));
+        ICZ_TRY(mem.synced());
+    }
+    hipLaunchKernelGGL(row_image_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, imgk, rows, K);
+    hipLaunchKernelGGL(beam_expand_rows_kernel, dim3(cdiv(dims.E, 1024), rows), dim3(256), 0, st, feats, (const int32_t*)imgk, dims.E, feat_n);
+    ICZ_TRY(sample(feat_n, rows, T, r, seq_out, logp_out, st));
+    cur_K = K;
+    return ICZ_OK;
+}
+
 int Nic::sample_backward(const float* reward, const icz_nic_params* G, float* dfeats, float* loss_out, float* msum_out, float msum_global,
                          hipStream_t st) {
     ICZ_TRY(require_mode(1, "nic"));
@@ -246,7 +276,14 @@ int Nic::sample_backward(const float* reward, const icz_nic_params* G, float* df
     ICZ_TRY(reinforce(reward, tlogit, dims.V, Vp, loss_out, msum_out, st));
     mode = 0;
     bptt_early_out = true;
-    return bptt(*G, dfeats, st);
+    if (cur_K == 1 || !dfeats) return bptt(*G, dfeats, st);
+    // behind sample_n: d features of the B K rows, then the K rows of an image added in k order -> [B, E]
+    ICZ_TRY(bptt(*G, dfeat_n, st));
+    const int n_img = cur_B / cur_K;
+    hipLaunchKernelGGL(rowgroup_sum_kernel, dim3(cdiv((int)((size_t)n_img * dims.E / 4), 256)), dim3(256), 0, st, (const float*)dfeat_n, n_img, cur_K,
+                       (size_t)dims.E, dfeats);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
 }
 
 int Nic::xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r, int train,
@@ -430,6 +467,12 @@ int icz_nic_sample(icz_nic_t* h, const float* features, int32_t B, int32_t max_l
                    float* logprobs_out, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Nic*>(h)->sample(features, B, max_len, rng, seq_out, logprobs_out, (hipStream_t)stream);
+}
+int icz_nic_sample_n(icz_nic_t* h, const float* features, int32_t B, int32_t K, int32_t max_len, const icz_rng* rng, int64_t* seq_out,
+                     float* logprobs_out, void* stream) {
+    ICZ_REQUIRE(K >= 2 && K <= SAMPLE_N_MAX_K, "icz_nic_sample_n: K=%d samples per image outside 2..%d", K, SAMPLE_N_MAX_K);
+    ICZ_REQUIRE(h, "icz_nic_sample_n: null handle");
+    return reinterpret_cast<Nic*>(h)->sample_n(features, B, K, max_len, rng, seq_out, logprobs_out, (hipStream_t)stream);
 }
 int icz_nic_sample_backward(icz_nic_t* h, const float* reward, const icz_nic_params* grads, float* dfeatures_out, float* loss_out,
                             float* mask_sum_out, float mask_sum_global, void* stream) {

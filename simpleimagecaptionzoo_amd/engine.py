@@ -19,6 +19,7 @@ import torch
 from ._lib import BUTD_PARAM_KEYS, check, lib, ptr, stream_ptr
 from .beam import make_diversity, parse_length_penalty
 from .sampling import make_sample_opts
+from .multisample import sample_n
 from .captioner import BUTDDetection_Captioner
 from .ciderd import CiderDReward
 from . import dist as icz_dist
@@ -190,6 +191,17 @@ class Engine(object):
                 optimizer.load_state_dict(torch.load(opt_path, map_location=self.device))
             start_epoch = len(cider_his) + 1
         return cider_his, start_epoch
+
+    def SCST_multisample_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=5):
+        """Beyond the reference, for every decoder family (BUTD, AoA -- also with train_refiner -- and NIC): the multi-sample SCST
+        step.  K = samples_per_image (2..8) captions are sampled per image (multisample.sample_n: the per-image work runs once per
+        image), each is baselined by the mean CIDEr-D of the image's other K - 1 (reward_loo), and there is no greedy rollout; the
+        mask-sum exchange, the gradient-reduce hooks, the 0.25 clamp and Adam are SCST_training_epoch's.  B K must fit the handle's
+        row capacity.  ValueError for a K outside 2..8, a bool or a non-integer, before any device work."""
+        from .multisample import check_samples
+        k = check_samples(samples_per_image)
+        with _on_stream(self):
+            return self._scst_training_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs, k)
 
 
 class BUTDDetection_Eng(Engine):
@@ -412,7 +424,8 @@ class BUTDDetection_Eng(Engine):
         return losses
 
     # ---- E2 -------------------------------------------------------------------------------------------------
-    # decoders whose handle has the multi-sample rollout (icz_butd_sample_n); AoA and NIC do not
+    # decoders whose SCST_training_epoch takes samples_per_image (BUTD, where the argument was introduced); the AoA and NIC engines
+    # keep refusing it there and run the multi-sample step through SCST_multisample_training_epoch, which serves all three
     _multi_sample = True
 
     def SCST_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=None):
@@ -422,8 +435,9 @@ class BUTDDetection_Eng(Engine):
         if samples_per_image is not None:
             k = samples_per_image
             if not self._multi_sample:
-                raise ValueError("samples_per_image: the %s decoder has no multi-sample SCST rollout (BUTD only); pass "
-                                 "samples_per_image=None" % type(self).__name__)
+                raise ValueError("samples_per_image: %s.SCST_training_epoch takes it for BUTD decoders only; call "
+                                 "SCST_multisample_training_epoch(..., samples_per_image=K) or pass samples_per_image=None"
+                                 % type(self).__name__)
             if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= int(k) <= 8:
                 raise ValueError("samples_per_image must be None or an integer in 2..8, got %r" % (k,))
             samples_per_image = int(k)
@@ -477,7 +491,7 @@ class BUTDDetection_Eng(Engine):
                 self._mark(marks)
                 rewards = scorer.reward(seq_gen, greedy_res, img_gts, img_ids)
             else:       # K sampled captions per image (rows img * K + k), each baselined by the mean reward of the other K - 1
-                seq_gen, seq_logprobs = h.sample_n(feats, samples_per_image, 20, rng)
+                seq_gen, seq_logprobs = sample_n(h, feats, samples_per_image, 20, rng)
                 self._mark(marks)
                 rewards = scorer.reward_loo(seq_gen, samples_per_image, img_gts, img_ids)
             self._mark(marks)
