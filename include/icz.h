@@ -705,6 +705,26 @@ int icz_gemm_f32(int32_t layout, const float* X, int32_t ldx, const float* W, in
                  float* C, int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t nsplit, float* workspace,
                  size_t workspace_floats, void* stream);
 size_t icz_gemm_workspace_floats(int32_t M, int32_t N);
+/* The same product over nseg = 1..4 K segments, as the decoder steps issue it: C = sum_s A_s B_s (+ bias), segment s with its own
+ * operands, leading dimensions and K[s] (layouts as above; every A_s / B_s may be a column slice of a wider buffer).  Fills the
+ * library's GEMM arguments and launches, nothing more.  nsplit = 0: the split of a decoder step (what icz_gemm_route_for assumes),
+ * cut to the workspace; an explicit nsplit is taken as given (a split that leaves an empty split is an error).  accumulate != 0:
+ * C += product, one split.  live: optional device int32, 0 = the launch returns without writing (a finished rollout's step).
+ * More than one split: slabs [nsplit][M][N] go to `workspace`; with C they are then summed in slab order, with the bias (needs
+ * ldc == N, M * N % 4 == 0, N % 4 == 0 with a bias); C == NULL leaves the raw slabs (one split: the finished product, dense) in
+ * `workspace` for the caller.  *nsplit_used (optional) = the split that ran.  ICZ_ERR, nothing launched, for a null table, nseg
+ * out of range and everything the library's own argument check refuses. */
+int icz_gemm_f32_seg(int32_t layout, int32_t nseg, const float* const* A, const int32_t* lda, const float* const* B, const int32_t* ldb,
+                     const int32_t* K, const float* bias, float* C, int32_t ldc, int32_t M, int32_t N, int32_t nsplit, int32_t accumulate,
+                     const int32_t* live, float* workspace, size_t workspace_floats, int32_t* nsplit_used, void* stream);
+/* Two independent NT products of that kind as ONE launch of the resident-activation kernel (the two recurrent dgrad products of a
+ * BPTT step): 33..64 rows each, whole 64-deep stages, N >= 512, both in the same stage form (512-deep or four-stage k ranges) and
+ * more than one k range each, else ICZ_ERR and nothing is launched.  Slabs [nsplit][M][N] go to slabs_a / slabs_b (no bias);
+ * *nsplit_a / *nsplit_b = their counts.  live as above. */
+int icz_gemm_resident_pair(int32_t nseg_a, const float* const* A_a, const int32_t* lda_a, const float* const* B_a, const int32_t* ldb_a, const int32_t* K_a,
+                           int32_t M_a, int32_t N_a, float* slabs_a, size_t slabs_a_floats, int32_t* nsplit_a,
+                           int32_t nseg_b, const float* const* A_b, const int32_t* lda_b, const float* const* B_b, const int32_t* ldb_b, const int32_t* K_b,
+                           int32_t M_b, int32_t N_b, float* slabs_b, size_t slabs_b_floats, int32_t* nsplit_b, const int32_t* live, void* stream);
 /* Which kernel the many-row split-precision products (>= 128 rows: weight gradients, dgrad over all steps, beam / refiner / XE forward
  * GEMMs) run on: -1 = chosen per shape (default; the environment's ICZ_GEMM_BIG sets the same switch), 0 = the 128 x 128 two-barrier
  * kernel everywhere, 1..5 = one large-tile configuration of gemm_big_x3.hip everywhere, -2 = back to the environment's value.
@@ -736,6 +756,9 @@ int icz_gemm_tn_split(const float* dY, int32_t ldy, int32_t M, const float* X, i
  * (icz_gemm_big_cfg_for says which), 8 = fp32-MFMA NN kernel, 9 = fp32-MFMA TN kernel on 64 x 64 tiles, 10 = fp32 TN kernel on
  * 128 x 128 tiles (ICZ_GEMM_TN_X3=0); -1 = bad arguments or a split the library refuses.  nsplit 0: the split of a decoder step. */
 int icz_gemm_route_for(int32_t layout, int32_t M, int32_t N, int32_t nseg, const int32_t* K, int32_t nsplit);
+/* The split icz_gemm_f32_seg takes for nsplit = 0 with a workspace of that many floats (host logic only, no GPU needed): the split of a
+ * decoder step, cut to the largest one whose slabs fit; -1 = bad arguments. */
+int icz_gemm_split_for(int32_t layout, int32_t M, int32_t N, int32_t nseg, const int32_t* K, size_t workspace_floats);
 /* Whether icz_gemm_tn_grouped takes column groups of these widths over K rows (host logic only, no GPU needed): 1 / 0, -1 = bad arguments. */
 int icz_gemm_tn_grouped_fits(int32_t M, int32_t K, int32_t ngroups, const int32_t* cols);
 /* Live timing of the dominant kernel (the forward GEMMs of a decoder step at 33..64 rows: gemm_resident_x3_kernel, or

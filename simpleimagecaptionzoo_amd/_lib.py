@@ -237,6 +237,8 @@ def lib():
         "icz_prof_stream_rate": (C.c_int, [vp, C.c_size_t, i32, vp, C.POINTER(C.c_double)]),
         "icz_adam_clamp_multi": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), f32, f32, i32, vp]),
         "icz_gemm_f32": (C.c_int, [i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, C.c_size_t, vp]),
+        "icz_gemm_f32_seg": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, C.c_size_t, C.POINTER(i32), vp]),
+        "icz_gemm_resident_pair": (C.c_int, [i32, vp, vp, vp, vp, vp, i32, i32, vp, C.c_size_t, C.POINTER(i32)] * 2 + [vp, vp]),
         "icz_gemm_workspace_floats": (C.c_size_t, [i32, i32]),
         "icz_gemm_set_big_cfg": (C.c_int, [i32]),
         "icz_gemm_big_cfg_for": (C.c_int, [i32, i32, i32, i32, i32]),
@@ -244,6 +246,7 @@ def lib():
         "icz_gemm_tn_split_pick": (C.c_int, [i32, i32, i32]),
         "icz_gemm_tn_split": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, C.c_size_t, vp, vp]),
         "icz_gemm_route_for": (C.c_int, [i32, i32, i32, i32, vp, i32]),
+        "icz_gemm_split_for": (C.c_int, [i32, i32, i32, i32, vp, C.c_size_t]),
         "icz_gemm_tn_grouped_fits": (C.c_int, [i32, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():

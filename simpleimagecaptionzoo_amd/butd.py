@@ -136,6 +136,72 @@ def gemm(layout, X, W, bias=None, nsplit=0):
     return out
 
 
+def _seg_tables(layout, As, Bs):
+    """(nseg, A pointers, lda, B pointers, ldb, K, M, N) of a product over K segments; M, N are None without segments."""
+    n = len(As)
+    if len(Bs) != n:
+        raise _lib.IczError("gemm_seg: %d A segments, %d B segments" % (n, len(Bs)))
+    for t in list(As) + list(Bs):
+        if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1:
+            raise _lib.IczError("gemm_seg: operands must be 2-d fp32 CUDA tensors with unit column stride")
+    M = N = None
+    if n:
+        M = As[0].shape[1] if layout == "tn" else As[0].shape[0]
+        N = Bs[0].shape[0] if layout == "nt" else Bs[0].shape[1]
+    Ks = [a.shape[0] if layout == "tn" else a.shape[1] for a in As]
+    ap = (C.c_void_p * n)(*[a.data_ptr() for a in As])
+    bp = (C.c_void_p * n)(*[b.data_ptr() for b in Bs])
+    lda = (C.c_int32 * n)(*[a.stride(0) for a in As])
+    ldb = (C.c_int32 * n)(*[b.stride(0) for b in Bs])
+    kk = (C.c_int32 * n)(*Ks)
+    return n, ap, lda, bp, ldb, kk, M, N
+
+
+def gemm_seg(layout, As, Bs, bias=None, nsplit=0, out=None, accumulate=False, live=None, workspace=None, raw_slabs=False, info=None):
+    """Test/bench entry for icz_gemm_f32_seg: the product over K segments the way a decoder step issues it, C = sum_s A_s B_s (+ bias).
+    Segment shapes per layout as for gemm(); every tensor's stride(0) is its leading dimension, so column slices of wider tensors
+    work unchanged.  nsplit 0: the split of a decoder step; accumulate: out += product (one split); live: a device int32, 0 = nothing
+    is written.  raw_slabs: no C -- returns the slabs [nsplit, M, N] the launch left in `workspace` (one split: the finished product).
+    Otherwise returns `out` (a new [M, N] tensor when None).  info: a dict that receives the split that ran as info["nsplit"]."""
+    code = {"nt": 0, "nn": 1, "tn": 2}[layout]
+    n, ap, lda, bp, ldb, kk, M, N = _seg_tables(layout, As, Bs)
+    if M is None:      # no segments: the library refuses; the shape is the output's
+        M, N = (int(out.shape[0]), int(out.shape[1])) if out is not None else (1, 1)
+    dev = out.device if out is not None else (As[0].device if n else "cuda")
+    if out is None and not raw_slabs:
+        out = torch.empty(M, N, device=dev, dtype=torch.float32)
+    if workspace is None:
+        workspace = torch.empty(max(lib().icz_gemm_workspace_floats(M, N), max(nsplit, 1) * M * N), device=dev, dtype=torch.float32)
+    used = C.c_int32(0)
+    c = None if raw_slabs else out
+    check(lib().icz_gemm_f32_seg(code, n, ap, lda, bp, ldb, kk, ptr(bias), ptr(c), c.stride(0) if c is not None else N, M, N, int(nsplit),
+                                 1 if accumulate else 0, ptr(live), ptr(workspace), workspace.numel(), C.byref(used), stream_ptr()))
+    if info is not None:
+        info["nsplit"] = used.value
+    return workspace[:used.value * M * N].view(used.value, M, N) if raw_slabs else out
+
+
+def gemm_resident_pair(As_a, Bs_a, As_b, Bs_b, slabs_a=None, slabs_b=None, live=None):
+    """Test/bench entry for icz_gemm_resident_pair: two NT products over K segments (33..64 rows each) as one launch of the
+    resident-activation kernel, what a BPTT step does for its two recurrent dgrad products.  Returns their split-K slabs
+    ([nsplit_a, M_a, N_a], [nsplit_b, M_b, N_b]) as views of slabs_a / slabs_b (flat fp32 buffers, allocated when None).  Raises
+    where the two problems do not share a stage form of the kernel."""
+    ta, tb = _seg_tables("nt", As_a, Bs_a), _seg_tables("nt", As_b, Bs_b)
+    bufs = []
+    for (n, _, _, _, _, kk, M, N), buf, As in ((ta, slabs_a, As_a), (tb, slabs_b, As_b)):
+        if M is None:
+            raise _lib.IczError("gemm_resident_pair: a problem without segments")
+        if buf is None:       # at most one slab per 256-deep k range
+            buf = torch.empty(max(sum(kk) // 256, 1) * M * N, device=As[0].device, dtype=torch.float32)
+        bufs.append(buf)
+    na, nb = C.c_int32(0), C.c_int32(0)
+    args = []
+    for (n, ap, lda, bp, ldb, kk, M, N), buf, used in ((ta, bufs[0], na), (tb, bufs[1], nb)):
+        args += [n, ap, lda, bp, ldb, kk, M, N, ptr(buf), buf.numel(), C.byref(used)]
+    check(lib().icz_gemm_resident_pair(*args, ptr(live), stream_ptr()))
+    return tuple(buf[:u.value * t[6] * t[7]].view(u.value, t[6], t[7]) for t, buf, u in ((ta, bufs[0], na), (tb, bufs[1], nb)))
+
+
 def gemm_set_big_cfg(cfg):
     """icz_gemm_set_big_cfg: -1 per shape (default), 0 the 128 x 128 two-barrier kernel, 1..5 one large-tile configuration, -2 environment."""
     check(lib().icz_gemm_set_big_cfg(int(cfg)))
@@ -186,6 +252,14 @@ def gemm_route_for(layout, M, N, Ks, nsplit=0):
     arr = (C.c_int32 * len(Ks))(*Ks)
     r = int(lib().icz_gemm_route_for({"nt": 0, "nn": 1, "tn": 2}[layout], int(M), int(N), len(Ks), arr, int(nsplit)))
     return GEMM_ROUTES[r] if r >= 0 else None
+
+
+def gemm_split_for(layout, M, N, Ks, workspace_floats=1 << 40):
+    """icz_gemm_split_for (host logic, no GPU): the split gemm_seg takes for nsplit = 0 with that much workspace, None for bad arguments."""
+    Ks = [int(k) for k in (Ks if isinstance(Ks, (list, tuple)) else [Ks])]
+    arr = (C.c_int32 * len(Ks))(*Ks)
+    r = int(lib().icz_gemm_split_for({"nt": 0, "nn": 1, "tn": 2}[layout], int(M), int(N), len(Ks), arr, int(workspace_floats)))
+    return r if r >= 1 else None
 
 
 def gemm_tn_grouped_fits(M, K, cols):

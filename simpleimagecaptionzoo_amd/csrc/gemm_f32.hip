@@ -1402,6 +1402,85 @@ int icz_gemm_f32(int32_t layout, const float* X, int32_t ldx, const float* W, in
     return gemm_f32((GemmLayout)layout, g, st);
 }
 
+// a product over K segments as the decoder handles describe it: table entries -> GemmArgs (shapes and pointers checked before any use)
+static int seg_args(const char* who, int32_t nseg, const float* const* A, const int32_t* lda, const float* const* B, const int32_t* ldb,
+                    const int32_t* K, int32_t M, int32_t N, GemmArgs* g) {
+    ICZ_REQUIRE(nseg >= 1 && nseg <= GEMM_MAX_SEG, "%s: nseg %d outside 1..%d", who, nseg, GEMM_MAX_SEG);
+    ICZ_REQUIRE(A && lda && B && ldb && K, "%s: null segment table", who);
+    ICZ_REQUIRE(M > 0 && N > 0, "%s: bad M/N (%d, %d)", who, M, N);
+    *g = GemmArgs{};
+    g->nseg = nseg;
+    for (int s = 0; s < nseg; ++s) {
+        ICZ_REQUIRE(A[s] && B[s] && K[s] > 0, "%s: segment %d null operand or K<=0", who, s);
+        g->seg[s] = {A[s], B[s], lda[s], ldb[s], K[s], nullptr};
+    }
+    g->M = M; g->N = N;
+    return ICZ_OK;
+}
+
+int icz_gemm_f32_seg(int32_t layout, int32_t nseg, const float* const* A, const int32_t* lda, const float* const* B, const int32_t* ldb,
+                     const int32_t* K, const float* bias, float* C, int32_t ldc, int32_t M, int32_t N, int32_t nsplit, int32_t accumulate,
+                     const int32_t* live, float* workspace, size_t workspace_floats, int32_t* nsplit_used, void* stream) {
+    ICZ_REQUIRE(layout >= 0 && layout <= 2, "icz_gemm_f32_seg: layout %d", layout);
+    ICZ_REQUIRE(nsplit >= 0, "icz_gemm_f32_seg: nsplit %d", nsplit);
+    const GemmLayout lay = (GemmLayout)layout;
+    GemmArgs g;
+    ICZ_TRY(seg_args("icz_gemm_f32_seg", nseg, A, lda, B, ldb, K, M, N, &g));
+    g.accumulate = accumulate != 0;
+    g.live = live;
+    if (g.accumulate) g.nsplit = 1;
+    else g.nsplit = nsplit > 0 ? nsplit : gemm_fit_split(lay, g, gemm_pick_split(g, 256, lay), workspace ? workspace_floats : 0);      // 256: a decoder step's target
+    const size_t MN = (size_t)M * N;
+    hipStream_t st = (hipStream_t)stream;
+    if (g.nsplit > 1 || !C) {
+        // slabs [nsplit][M][N] (one split: the finished product, dense) in the workspace
+        ICZ_REQUIRE(workspace && (size_t)g.nsplit * MN <= workspace_floats, "icz_gemm_f32_seg: workspace of %zu floats too small for %d slabs of %d x %d",
+                    workspace_floats, g.nsplit, M, N);
+        ICZ_REQUIRE(((uintptr_t)workspace & 15) == 0, "icz_gemm_f32_seg: workspace must be 16-byte aligned");
+        if (C && g.nsplit > 1) {
+            ICZ_REQUIRE(ldc == N && MN % 4 == 0 && ((uintptr_t)C & 15) == 0, "icz_gemm_f32_seg: the slab sum needs ldc == N, M*N %% 4 == 0 and an aligned C (ldc %d, %d x %d)", ldc, M, N);
+            ICZ_REQUIRE(!bias || (N % 4 == 0 && ((uintptr_t)bias & 15) == 0), "icz_gemm_f32_seg: the slab sum adds the bias four columns at a time (N %d)", N);
+        }
+        g.out = workspace; g.ldo = N;
+        g.bias = (C && g.nsplit > 1) ? nullptr : bias;       // raw slabs with a bias: refused by gemm_f32
+        ICZ_TRY(gemm_f32(lay, g, st));
+        if (C && g.nsplit > 1) {
+            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, (const float*)workspace, g.nsplit, MN, N, bias, C);
+            ICZ_CHECK_HIP(hipGetLastError());
+        }
+    } else {
+        ICZ_REQUIRE(ldc >= N, "icz_gemm_f32_seg: output row stride %d below N = %d", ldc, N);
+        g.out = C; g.ldo = ldc; g.bias = bias;
+        ICZ_TRY(gemm_f32(lay, g, st));
+    }
+    if (nsplit_used) *nsplit_used = g.nsplit;
+    return ICZ_OK;
+}
+
+int icz_gemm_resident_pair(int32_t nseg_a, const float* const* A_a, const int32_t* lda_a, const float* const* B_a, const int32_t* ldb_a, const int32_t* K_a,
+                           int32_t M_a, int32_t N_a, float* slabs_a, size_t slabs_a_floats, int32_t* nsplit_a,
+                           int32_t nseg_b, const float* const* A_b, const int32_t* lda_b, const float* const* B_b, const int32_t* ldb_b, const int32_t* K_b,
+                           int32_t M_b, int32_t N_b, float* slabs_b, size_t slabs_b_floats, int32_t* nsplit_b, const int32_t* live, void* stream) {
+    GemmArgs ga, gb;
+    ICZ_TRY(seg_args("icz_gemm_resident_pair (first)", nseg_a, A_a, lda_a, B_a, ldb_a, K_a, M_a, N_a, &ga));
+    ICZ_TRY(seg_args("icz_gemm_resident_pair (second)", nseg_b, A_b, lda_b, B_b, ldb_b, K_b, M_b, N_b, &gb));
+    ga.out = slabs_a; ga.ldo = N_a; ga.live = live;
+    gb.out = slabs_b; gb.ldo = N_b; gb.live = live;
+    ICZ_REQUIRE(gemm_resident_x3_pair_fits(ga, gb), "icz_gemm_resident_pair: the two problems do not share a stage form of the resident kernel");
+    ga.nsplit = gemm_resident_x3_nsplit(ga);
+    gb.nsplit = gemm_resident_x3_nsplit(gb);
+    ICZ_REQUIRE(ga.nsplit > 1 && gb.nsplit > 1, "icz_gemm_resident_pair: slab products only (one k range: %d, %d)", ga.nsplit, gb.nsplit);
+    ICZ_TRY(check_args(GEMM_NT, ga));
+    ICZ_TRY(check_args(GEMM_NT, gb));
+    ICZ_REQUIRE(((uintptr_t)slabs_a & 15) == 0 && ((uintptr_t)slabs_b & 15) == 0, "icz_gemm_resident_pair: slabs must be 16-byte aligned");
+    ICZ_REQUIRE(gemm_slab_floats(M_a, N_a, ga.nsplit) <= slabs_a_floats && gemm_slab_floats(M_b, N_b, gb.nsplit) <= slabs_b_floats,
+                "icz_gemm_resident_pair: slab buffers too small (%d x %d x %d, %d x %d x %d)", ga.nsplit, M_a, N_a, gb.nsplit, M_b, N_b);
+    ICZ_TRY(gemm_resident_x3_pair(ga, gb, (hipStream_t)stream));
+    if (nsplit_a) *nsplit_a = ga.nsplit;
+    if (nsplit_b) *nsplit_b = gb.nsplit;
+    return ICZ_OK;
+}
+
 int icz_gemm_set_big_cfg(int32_t cfg) {
     ICZ_REQUIRE(cfg >= -2 && cfg <= 5, "icz_gemm_set_big_cfg: %d", cfg);
     gemm_set_big_cfg(cfg);
@@ -1435,6 +1514,18 @@ int icz_gemm_route_for(int32_t layout, int32_t M, int32_t N, int32_t nseg, const
     g.M = M; g.N = N;
     g.nsplit = nsplit > 0 ? nsplit : gemm_pick_split(g, 256, (GemmLayout)layout);      // 256: the decoder steps' target (STEP_WGS)
     return gemm_route((GemmLayout)layout, g);
+}
+
+int icz_gemm_split_for(int32_t layout, int32_t M, int32_t N, int32_t nseg, const int32_t* K, size_t workspace_floats) {
+    if (layout < 0 || layout > 2 || M <= 0 || N <= 0 || nseg < 1 || nseg > GEMM_MAX_SEG || !K) return -1;
+    GemmArgs g = {};
+    g.nseg = nseg;
+    for (int s = 0; s < nseg; ++s) {
+        if (K[s] <= 0) return -1;
+        g.seg[s].K = K[s];
+    }
+    g.M = M; g.N = N;
+    return gemm_fit_split((GemmLayout)layout, g, gemm_pick_split(g, 256, (GemmLayout)layout), workspace_floats);
 }
 
 int icz_gemm_tn_split_pick(int32_t M, int32_t N, int32_t K) {
