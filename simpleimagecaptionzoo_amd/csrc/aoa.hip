@@ -96,20 +96,6 @@ int Aoa::refresh(hipStream_t st) {
     return ICZ_OK;
 }
 
-static int aoa_linear(Aoa& a, GemmArgs& g, const float* bias, float* out, hipStream_t st) {
-    g.out = out; g.ldo = g.N;
-    g.nsplit = gemm_fit_split(GEMM_NT, g, gemm_pick_split(g, Aoa::STEP_WGS), a.ws_floats);
-    if (g.nsplit == 1) {
-        g.bias = bias;
-        return gemm_f32(GEMM_NT, g, st);
-    }
-    ICZ_REQUIRE(gemm_slab_floats(g.M, g.N, g.nsplit) <= a.ws_floats, "aoa: workspace too small");
-    g.out = a.ws;
-    ICZ_TRY(gemm_f32(GEMM_NT, g, st));
-    const size_t MN = (size_t)g.M * g.N;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, a.ws, g.nsplit, MN, g.N, bias, out);
-    return ICZ_OK;
-}
 
 // refiner self-attention of one layer over n_img images: the matrix-pipe kernel up to 64 regions, the register-blocked one beyond
 void Aoa::launch_mha_self(int n_img, int R, int qc, size_t lds, const RegionRows& rr, const float* qkv_, float* o_, const DropP& dp, hipStream_t st) {
@@ -126,14 +112,13 @@ void Aoa::mha_self_layer(int n_img, int l, bool train, hipStream_t st) {
                     dropp(train, rng.ref_att_mask, (size_t)l * n_img * dims.NH * R * R, AOA_RNG_REF_ATT, l, 0.1f), st);
 }
 
-int Aoa::linear(GemmArgs& g, const float* bias, float* out, hipStream_t st) { return aoa_linear(*this, g, bias, out, st); }
+// (the split is fitted to the workspace: the capacity check of gemm_finished cannot fail)
+int Aoa::linear(GemmArgs g, const float* bias, hipStream_t st) {
+    return gemm_finished(GEMM_NT, g, split_forward(STEP_WGS), bias, ws, ws_floats, st, "aoa");
+}
 
 int Aoa::lin(const float* A, int M, int K, const float* W, const float* bias, int N, float* out, hipStream_t st) {
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.seg[0] = {A, W, K, K, K, nullptr};
-    g.M = M; g.N = N;
-    return aoa_linear(*this, g, bias, out, st);
+    return linear(gemm_args({{A, W, K, K, K}}, M, N, out, N), bias, st);
 }
 
 // img_feats_porjection + AoA_Refine_Core (AoA_Model.py:661-665, 140-162) -> refined [n_img,R,Hd], its region mean, and the
@@ -185,12 +170,7 @@ int Aoa::refine(const float* feats, int n_img, bool train, hipStream_t st, const
                                dropp(true, rng.ref_aoa_mask, (size_t)l * n_img * R * 2 * Hd, AOA_RNG_REF_AOA, l, 0.3f));
             xo = od; xn = nd;
         }
-        GemmArgs g = {};
-        g.nseg = 2;
-        g.seg[0] = {xo, b.aoa_w, Hd, 2 * Hd, Hd, nullptr};
-        g.seg[1] = {xn, b.aoa_w + Hd, Hd, 2 * Hd, Hd, nullptr};
-        g.M = rows; g.N = 2 * Hd;
-        ICZ_TRY(aoa_linear(*this, g, b.aoa_b, z, st));
+        ICZ_TRY(linear(gemm_args({{xo, b.aoa_w, Hd, 2 * Hd, Hd}, {xn, b.aoa_w + Hd, Hd, 2 * Hd, Hd}}, rows, 2 * Hd, z, 2 * Hd), b.aoa_b, st));
         hipLaunchKernelGGL(glu_residual_kernel, dim3(eb), dim3(256), 0, st, z, cur, nxt, (size_t)rows, Hd, rr,
                            dropp(train, rng.ref_sc_mask, (size_t)l * n_img * R * Hd, AOA_RNG_REF_SC, l, 0.1f));
         if (store) { cur = nxt; nxt = l + 2 <= NL ? xs[l + 2] : nullptr; }
@@ -238,12 +218,7 @@ int Aoa::refine_pair(int n_img, hipStream_t st, const float* proj) {
         // dropout of [attention output | normed input] for the training half, in place (each thread rewrites the element it read)
         hipLaunchKernelGGL(drop_concat_kernel, dim3(eb), dim3(256), 0, st, w.o + nel, w.ln + nel, w.o + nel, w.ln + nel, (size_t)rows, Hd, rr,
                            dropp(true, rng.ref_aoa_mask, (size_t)l * n_img * R * 2 * Hd, AOA_RNG_REF_AOA, l, 0.3f));
-        GemmArgs g = {};
-        g.nseg = 2;
-        g.seg[0] = {w.o, b.aoa_w, Hd, 2 * Hd, Hd, nullptr};
-        g.seg[1] = {w.ln, b.aoa_w + Hd, Hd, 2 * Hd, Hd, nullptr};
-        g.M = rows2; g.N = 2 * Hd;
-        ICZ_TRY(aoa_linear(*this, g, b.aoa_b, w.z, st));
+        ICZ_TRY(linear(gemm_args({{w.o, b.aoa_w, Hd, 2 * Hd, Hd}, {w.ln, b.aoa_w + Hd, Hd, 2 * Hd, Hd}}, rows2, 2 * Hd, w.z, 2 * Hd), b.aoa_b, st));
         hipLaunchKernelGGL(glu_residual_kernel, dim3(eb2), dim3(256), 0, st, w.z, cur, nxt, (size_t)rows2, Hd, rr,
                            second(dropp(true, rng.ref_sc_mask, (size_t)l * n_img * R * Hd, AOA_RNG_REF_SC, l, 0.1f), nel));
         if (store) ICZ_CHECK_HIP(hipMemcpyAsync(xs[l + 1], nxt + nel, sizeof(float) * nel, hipMemcpyDeviceToDevice, st));
@@ -268,47 +243,31 @@ int Aoa::step(const AoaStepIO& s, hipStream_t st) {
     const unsigned eb = (unsigned)(((size_t)rows * Hd + 255) / 256);
     if (!s.emb_ready) hipLaunchKernelGGL(embed_kernel, dim3(cdiv(E, 1024), rows), dim3(256), 0, st, P.embed_weight, s.it, s.emb, rows, E, s.d_emb, 1);
     if (!s.u_ready) hipLaunchKernelGGL(aoa_u_kernel, dim3(eb), dim3(256), 0, st, meanf, s.img_of_row, s.ctx_in, s.u, rows, Hd, s.d_ctx);
-    GemmArgs g = {};
-    g.nseg = 3;
-    g.seg[0] = {s.emb, P.lstm_w_ih, E, E + Hd, E, nullptr};
-    g.seg[1] = {s.u, P.lstm_w_ih + E, Hd, E + Hd, Hd, nullptr};
-    g.seg[2] = {s.h_in, P.lstm_w_hh, Hd, Hd, Hd, nullptr};
-    g.M = rows; g.N = 4 * Hd; g.out = ws; g.ldo = 4 * Hd; g.live = s.live;
-    g.nsplit = gemm_fit_split(GEMM_NT, g, gemm_pick_split(g, STEP_WGS), ws_floats);
-    ICZ_REQUIRE(gemm_slab_floats(g.M, g.N, g.nsplit) <= ws_floats, "aoa: workspace too small");
-    ICZ_TRY(gemm_f32(GEMM_NT, g, st));
-    LstmPointArgs a = {ws, g.nsplit, nullptr, nullptr, P.lstm_b_ih, P.lstm_b_hh, s.m_in, s.h_out, s.m_out, s.gates_out, nullptr, rows, Hd, s.live};
+    // the step's products leave slabs [ns][rows][N] in the bank's workspace (one: the dense product) for the kernel behind them to
+    // sum; the split is fitted to the workspace, so the capacity check of gemm_slabs cannot fail
+    int ns;
+    GemmArgs g = gemm_args({{s.emb, P.lstm_w_ih, E, E + Hd, E}, {s.u, P.lstm_w_ih + E, Hd, E + Hd, Hd}, {s.h_in, P.lstm_w_hh, Hd, Hd, Hd}},
+                           rows, 4 * Hd, ws, 4 * Hd, s.live);
+    ICZ_TRY(gemm_slabs(GEMM_NT, g, split_forward(STEP_WGS), ws, ws_floats, &ns, st, "aoa"));
+    LstmPointArgs a = {ws, ns, nullptr, nullptr, P.lstm_b_ih, P.lstm_b_hh, s.m_in, s.h_out, s.m_out, s.gates_out, nullptr, rows, Hd, s.live};
     DropCfg off = {0, nullptr, nullptr, 0, 0};
     launch_lstm_point(a, off, st);
     hipLaunchKernelGGL(layer_norm_kernel, dim3(rows), dim3(64), 0, st, s.h_out, P.dec.ln_g, P.dec.ln_b, s.qn, rows, Hd, s.ln_stats, s.live);
     const size_t lds = sizeof(float) * (2 * R * (dh + 1) + dh + 128 + 4);
     {   // query projection; when it is split over K its slabs go straight to the attention kernel, which sums them
-        GemmArgs qg = {};
-        qg.nseg = 1;
-        qg.seg[0] = {s.qn, P.dec.q_w, Hd, Hd, Hd, nullptr};
-        qg.M = rows; qg.N = Hd; qg.ldo = Hd; qg.live = s.live;
-        qg.nsplit = gemm_fit_split(GEMM_NT, qg, gemm_pick_split(qg, STEP_WGS), ws_floats);
-        if (qg.nsplit == 1) {
-            qg.out = s.Qp; qg.bias = P.dec.q_b;
-            ICZ_TRY(gemm_f32(GEMM_NT, qg, st));
+        GemmArgs qg = gemm_args({{s.qn, P.dec.q_w, Hd, Hd, Hd}}, rows, Hd, s.Qp, Hd, s.live);      // one split: finished in Qp, with the bias
+        qg.bias = P.dec.q_b;
+        ICZ_TRY(gemm_slabs(GEMM_NT, qg, split_forward(STEP_WGS), ws, ws_floats, &ns, st, "aoa"));
+        if (ns == 1)
             hipLaunchKernelGGL(aoa_dec_attn_kernel, dim3(rows, NH), dim3(256), lds, st, s.Qp, Kd, Vd, s.img_of_row, s.xatt, s.P_out, s.Pd_out, R, Hd, NH,
                                region_rows(), s.d_att, 1, (size_t)0, (const float*)nullptr, (float*)nullptr, s.live);
-        } else {
-            qg.out = ws;
-            ICZ_TRY(gemm_f32(GEMM_NT, qg, st));
+        else
             hipLaunchKernelGGL(aoa_dec_attn_kernel, dim3(rows, NH), dim3(256), lds, st, (const float*)ws, Kd, Vd, s.img_of_row, s.xatt, s.P_out, s.Pd_out,
-                               R, Hd, NH, region_rows(), s.d_att, qg.nsplit, (size_t)rows * Hd, (const float*)P.dec.q_b, s.Qp, s.live);
-        }
+                               R, Hd, NH, region_rows(), s.d_att, ns, (size_t)rows * Hd, (const float*)P.dec.q_b, s.Qp, s.live);
     }
-    GemmArgs zg = {};
-    zg.nseg = 2;
-    zg.seg[0] = {s.xatt, P.dec.aoa_w, Hd, 2 * Hd, Hd, nullptr};
-    zg.seg[1] = {s.qn, P.dec.aoa_w + Hd, Hd, 2 * Hd, Hd, nullptr};
-    zg.M = rows; zg.N = 2 * Hd; zg.out = ws; zg.ldo = 2 * Hd; zg.live = s.live;
-    zg.nsplit = gemm_fit_split(GEMM_NT, zg, gemm_pick_split(zg, STEP_WGS), ws_floats);
-    ICZ_REQUIRE(gemm_slab_floats(zg.M, zg.N, zg.nsplit) <= ws_floats, "aoa: workspace too small");
-    ICZ_TRY(gemm_f32(GEMM_NT, zg, st));
-    hipLaunchKernelGGL(aoa_glu_kernel, dim3(eb), dim3(256), 0, st, ws, zg.nsplit, P.dec.aoa_b, s.z_out, s.ctx_out, s.ctxdrop, rows, Hd, s.d_out,
+    GemmArgs zg = gemm_args({{s.xatt, P.dec.aoa_w, Hd, 2 * Hd, Hd}, {s.qn, P.dec.aoa_w + Hd, Hd, 2 * Hd, Hd}}, rows, 2 * Hd, ws, 2 * Hd, s.live);
+    ICZ_TRY(gemm_slabs(GEMM_NT, zg, split_forward(STEP_WGS), ws, ws_floats, &ns, st, "aoa"));
+    hipLaunchKernelGGL(aoa_glu_kernel, dim3(eb), dim3(256), 0, st, ws, ns, P.dec.aoa_b, s.z_out, s.ctx_out, s.ctxdrop, rows, Hd, s.d_out,
                        (const float*)meanf, s.img_of_row, s.u_next, s.d_ctx_next, s.live);
     if (!s.skip_predict) ICZ_TRY(gemm_predict(s.ctxdrop, Hd, w_pred, P.predict_b, rows, dims.V, Vp, s.logits, Vp, ws, ws_floats, s.pred_nsplit, st, s.live));
     ICZ_CHECK_HIP(hipGetLastError());

@@ -197,13 +197,11 @@ struct Aoa : CaptionHead, DecodeMember {
                    float* packed_out, hipStream_t st);
     int xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
     int bptt(const icz_aoa_params& G, hipStream_t st);
-    int colsum(const float* Xm, int K, int N, int ldx, float* out, hipStream_t st);
-    // C = sum_s A_s W_s^T + bias, dense [M,N]; split-K slabs through `ws` when one pass would leave most CUs idle
-    int linear(GemmArgs& g, const float* bias, float* out, hipStream_t st);
-    int nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* slab_out, size_t cap, int* ns, int target, hipStream_t st,
-           const int* live = nullptr, const int* rows_live = nullptr);
-    int tn(const float* dY, int ldy, int M, const float* Xm, int ldx, int N, int K, float* out, int ldo, int accumulate, hipStream_t st,
-           const int* rows_live = nullptr);
+    // g.out (dense [M,N]) = sum_s A_s W_s^T + bias; split-K slabs through `ws` when one pass would leave most CUs idle
+    int linear(GemmArgs g, const float* bias, hipStream_t st);
+    // slabs [ns][M][N] = A[M,K] . B[K,N] (ns == 1: the dense product) in `slab` of `cap` floats, for the consumer to sum
+    static int nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* slab, size_t cap, int* ns, const SplitPolicy& p,
+                  hipStream_t st, const int* live = nullptr, const int* rows_live = nullptr);
 };
 
 }  // namespace icz

@@ -67,17 +67,10 @@ int Aoa::refiner_backward_check(const icz_aoa_params& G) const {
 
 namespace {
 
-// slabs [ns][M][N] = A[M,K] . B[K,N] into `slab` (capacity `cap` floats); the split shrinks to fit
+// slabs [ns][M][N] = A[M,K] . B[K,N] into `slab` (capacity `cap` floats).  The split shrinks to fit on the small branch too (the
+// refiner's slab buffer is sized for its widest products only), so here the capacity check of gemm_slabs can never fail.
 int rnn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* slab, size_t cap, int* ns_out, hipStream_t st) {
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.seg[0] = {A, Bm, lda, ldb, K, nullptr};
-    g.M = M; g.N = N; g.out = slab; g.ldo = N;
-    g.nsplit = M <= 64 ? gemm_fit_split(GEMM_NN, g, gemm_pick_split(g, Aoa::TARGET_WGS, GEMM_NN), cap) : gemm_pick_split_balanced(g, GEMM_NN, cap);
-    ICZ_REQUIRE(gemm_slab_floats(M, N, g.nsplit) <= cap, "aoa: refiner slab buffer too small");
-    ICZ_TRY(gemm_f32(GEMM_NN, g, st));
-    *ns_out = g.nsplit;
-    return ICZ_OK;
+    return Aoa::nn(A, lda, M, K, Bm, ldb, N, slab, cap, ns_out, split_backward(Aoa::TARGET_WGS, true), st);
 }
 
 }  // namespace
@@ -105,8 +98,8 @@ int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
     int c = 0;
     hipLaunchKernelGGL(aoa_ln_bwd_dense_kernel, dim3(rows), dim3(256), 0, st, (const float*)nullptr, 0, (const float*)rdq, rows, (const float*)xs[NL],
                        P.ref_ln_g, (const float*)nullptr, (float*)nullptr, rprod, rdx[c], Hd);
-    ICZ_TRY(colsum(rprod, rows, Hd, Hd, G.ref_ln_g, st));
-    ICZ_TRY(colsum(rdq, rows, Hd, Hd, G.ref_ln_b, st));
+    ICZ_TRY(launch_colsum(rprod, rows, Hd, Hd, G.ref_ln_g, st));
+    ICZ_TRY(launch_colsum(rdq, rows, Hd, Hd, G.ref_ln_b, st));
     // ---- 3. the layers, last to first
     const size_t lds_b = sizeof(float) * mha_self_bwd_lds_floats(R, Hd / NH);
     for (int l = NL - 1; l >= 0; --l) {
@@ -124,25 +117,13 @@ int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
             hipLaunchKernelGGL(drop_concat_kernel, dim3(eb), dim3(256), 0, st, (const float*)o, (const float*)ln, od, nd, (size_t)rows, Hd, rr, d_aoa);
             xo = od; xn = nd;
         }
-        {
-            GemmArgs g = {};
-            g.nseg = 2;
-            g.seg[0] = {xo, b.aoa_w, Hd, 2 * Hd, Hd, nullptr};
-            g.seg[1] = {xn, b.aoa_w + Hd, Hd, 2 * Hd, Hd, nullptr};
-            g.M = rows; g.N = 2 * Hd;
-            ICZ_TRY(linear(g, b.aoa_b, z, st));
-        }
+        ICZ_TRY(linear(gemm_args({{xo, b.aoa_w, Hd, 2 * Hd, Hd}, {xn, b.aoa_w + Hd, Hd, 2 * Hd, Hd}}, rows, 2 * Hd, z, 2 * Hd), b.aoa_b, st));
         // GLU + residual: rdx[c] = d x_{l+1} stays the residual branch's gradient
         hipLaunchKernelGGL(glu_residual_bwd_kernel, dim3(eb), dim3(256), 0, st, (const float*)rdx[c], (const float*)z, rdz, (size_t)rows, Hd, rr, d_sc);
         // AoA linear: weight gradient against the dropped inputs (two column groups of aoa_w), bias, input gradient
         const GemmColGroup groups[2] = {{xo, Hd, Hd, gb.aoa_w, 2 * Hd}, {xn, Hd, Hd, gb.aoa_w + Hd, 2 * Hd}};
-        if (gemm_tn_grouped_fits(2 * Hd, rows, groups, 2)) {
-            ICZ_TRY(gemm_tn_grouped(rdz, 2 * Hd, 2 * Hd, rows, groups, 2, nullptr, st));
-        } else {
-            ICZ_TRY(tn(rdz, 2 * Hd, 2 * Hd, xo, Hd, Hd, rows, gb.aoa_w, 2 * Hd, 0, st));
-            ICZ_TRY(tn(rdz, 2 * Hd, 2 * Hd, xn, Hd, Hd, rows, gb.aoa_w + Hd, 2 * Hd, 0, st));
-        }
-        ICZ_TRY(colsum(rdz, rows, 2 * Hd, 2 * Hd, gb.aoa_b, st));
+        ICZ_TRY(gemm_tn_groups(rdz, 2 * Hd, 2 * Hd, rows, groups, 2, nullptr, 0, nullptr, st));
+        ICZ_TRY(launch_colsum(rdz, rows, 2 * Hd, 2 * Hd, gb.aoa_b, st));
         int ns = 1;
         ICZ_TRY(rnn(rdz, 2 * Hd, rows, 2 * Hd, b.aoa_w, 2 * Hd, 2 * Hd, rslab, rslab_floats, &ns, st));
         hipLaunchKernelGGL(drop_concat_bwd_kernel, dim3(eb), dim3(256), 0, st, (const float*)rslab, ns, rdo, rdln, (size_t)rows, Hd, rr, d_aoa);
@@ -152,21 +133,21 @@ int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
         float* const gw[3] = {gb.q_w, gb.k_w, gb.v_w};
         float* const gbias[3] = {gb.q_b, gb.k_b, gb.v_b};
         for (int w = 0; w < 3; ++w) {
-            ICZ_TRY(tn(rdqkv + (size_t)w * Hd, 3 * Hd, Hd, ln, Hd, Hd, rows, gw[w], Hd, 0, st));
-            ICZ_TRY(colsum(rdqkv + (size_t)w * Hd, rows, Hd, 3 * Hd, gbias[w], st));
+            ICZ_TRY(gemm_tn(rdqkv + (size_t)w * Hd, 3 * Hd, Hd, ln, Hd, Hd, rows, gw[w], Hd, 0, nullptr, st));
+            ICZ_TRY(launch_colsum(rdqkv + (size_t)w * Hd, rows, Hd, 3 * Hd, gbias[w], st));
         }
         ICZ_TRY(rnn(rdqkv, 3 * Hd, rows, 3 * Hd, w_qkv[l], Hd, Hd, rslab, rslab_floats, &ns, st));
         // LayerNorm (its output fed the projection and the [o | ln] concatenation) + the residual
         hipLaunchKernelGGL(aoa_ln_bwd_dense_kernel, dim3(rows), dim3(256), 0, st, (const float*)rslab, ns, (const float*)rdln, rows, (const float*)xs[l],
                            b.ln_g, (const float*)rdx[c], rdq, rprod, rdx[c ^ 1], Hd);
-        ICZ_TRY(colsum(rprod, rows, Hd, Hd, gb.ln_g, st));
-        ICZ_TRY(colsum(rdq, rows, Hd, Hd, gb.ln_b, st));
+        ICZ_TRY(launch_colsum(rprod, rows, Hd, Hd, gb.ln_g, st));
+        ICZ_TRY(launch_colsum(rdq, rows, Hd, Hd, gb.ln_b, st));
         c ^= 1;
     }
     // ---- 4. img_feats_porjection: ReLU + dropout backward from the stored output, weight gradient over the region rows
     hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3(eb), dim3(256), 0, st, (const float*)xs[0], (const float*)rdx[c], rdo, nel, train ? 2.0f : 1.0f);
-    ICZ_TRY(tn(rdo, Hd, Hd, ref_feats, D, D, rows, G.proj_w, D, 0, st));
-    ICZ_TRY(colsum(rdo, rows, Hd, Hd, G.proj_b, st));
+    ICZ_TRY(gemm_tn(rdo, Hd, Hd, ref_feats, D, D, rows, G.proj_w, D, 0, nullptr, st));
+    ICZ_TRY(launch_colsum(rdo, rows, Hd, Hd, G.proj_b, st));
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }

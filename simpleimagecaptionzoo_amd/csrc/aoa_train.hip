@@ -493,10 +493,8 @@ int Aoa::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
         ICZ_TRY(step(io, st));
     }
     if (batched_predict) {
-        GemmArgs g = {};
-        g.nseg = 1;
-        g.seg[0] = {tcd, w_pred, dims.Hd, dims.Hd, dims.Hd, nullptr};
-        g.M = T * B; g.N = dims.V; g.out = tlogit; g.ldo = Vp; g.bias = P.predict_b; g.nsplit = 1;
+        GemmArgs g = gemm_args({{tcd, w_pred, dims.Hd, dims.Hd, dims.Hd}}, T * B, dims.V, tlogit, Vp);
+        g.bias = P.predict_b;
         ICZ_TRY(gemm_f32(GEMM_NT, g, st));
     }
     if (packed_out) ICZ_TRY(gather_packed(tlogit, dims.V, Vp, packed_out, st));
@@ -513,34 +511,11 @@ int Aoa::xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, 
     return bptt(*G, st);
 }
 
-int Aoa::colsum(const float* Xm, int K, int N, int ldx, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(N, 32)), dim3(256), 0, st, Xm, K, N, ldx, out);
-    return ICZ_OK;
-}
-
-// slabs [ns][M][N] = A[M,K] . B[K,N]  (ns == 1: the dense product); `cap` = capacity of slab_out in floats
-int Aoa::nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* slab_out, size_t cap, int* ns_out, int target,
+int Aoa::nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* slab, size_t cap, int* ns_out, const SplitPolicy& p,
             hipStream_t st, const int* live, const int* rows_live) {
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.live = live; g.rows_live = rows_live;
-    g.seg[0] = {A, Bm, lda, ldb, K, nullptr};
-    g.M = M; g.N = N; g.out = slab_out; g.ldo = N;
-    g.nsplit = M <= 64 ? gemm_pick_split(g, target, GEMM_NN) : gemm_pick_split_balanced(g, GEMM_NN, cap);
-    ICZ_REQUIRE(gemm_slab_floats(M, N, g.nsplit) <= cap, "aoa: slab buffer too small");
-    ICZ_TRY(gemm_f32(GEMM_NN, g, st));
-    *ns_out = g.nsplit;
-    return ICZ_OK;
-}
-
-int Aoa::tn(const float* dY, int ldy, int M, const float* Xm, int ldx, int N, int K, float* out, int ldo, int accumulate, hipStream_t st,
-            const int* rows_live) {
-    GemmArgs g = {};
-    g.nseg = 1;
+    GemmArgs g = gemm_args({{A, Bm, lda, ldb, K}}, M, N, slab, N, live);
     g.rows_live = rows_live;
-    g.seg[0] = {dY, Xm, ldy, ldx, K, nullptr};
-    g.M = M; g.N = N; g.out = out; g.ldo = ldo; g.nsplit = 1; g.accumulate = accumulate;
-    return gemm_f32(GEMM_TN, g, st);
+    return gemm_slabs(GEMM_NN, g, p, slab, cap, ns_out, st, "aoa");
 }
 
 int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
@@ -558,11 +533,8 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     const bool eo = bptt_early_out && early_out;
     const int* const rl = eo ? live_rows : nullptr;
     // ---- predict layer over all time steps: d(dropped ctx), weight-norm gradients
-    ICZ_TRY(nn(tlogit, Vp, TB, Vp, w_pred, Hd, Hd, X, xfloats, &ns, TARGET_WGS, st, nullptr, rl));
-    {
-        const size_t MN = (size_t)TB * Hd;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, X, ns, MN, Hd, (const float*)nullptr, dCd);
-    }
+    ICZ_TRY(nn(tlogit, Vp, TB, Vp, w_pred, Hd, Hd, X, xfloats, &ns, split_backward(TARGET_WGS), st, nullptr, rl));
+    ICZ_TRY(launch_slab_reduce(X, ns, TB, Hd, nullptr, dCd, st));      // (one slab: a copy)
     // The predict layer's weight / bias gradients need dlogits only.  Without a DP callback they go to a side stream,
     // ISSUED behind the d(ctx) product above (the head of the critical chain, as in Butd::bptt) and joined behind the loop; with a
     // callback they stay in line, because stage 0 reports them complete in stream order right here.
@@ -576,9 +548,9 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
         ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, low.fork[0], 0));
         ps = low.st;
     }
-    const int s_tn = tn(tlogit, Vp, Vp, tcd, Hd, Hd, TB, dWp, Hd, 0, ps, rl);
+    const int s_tn = gemm_tn(tlogit, Vp, Vp, tcd, Hd, Hd, TB, dWp, Hd, 0, rl, ps);
     if (s_tn == ICZ_OK) {
-        (void)colsum(tlogit, TB, V, Vp, G.predict_b, ps);
+        (void)launch_colsum(tlogit, TB, V, Vp, G.predict_b, ps);
         hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, ps, dWp, Hd, P.predict_v, P.predict_g, n_pred, G.predict_v,
                            G.predict_g, V, Hd);
     }
@@ -609,10 +581,10 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
         hipLaunchKernelGGL(aoa_glu_bwd_kernel, dim3(eb), dim3(256), 0, st, dCd + s0 * Hd, io.d_out, bnext ? (const float*)X : nullptr, nsx, bnext,
                            io_next.d_ctx, tz + s0 * 2 * Hd, dZ + s0 * 2 * Hd, bt, Hd, live, carry_live);
         int ns2 = 1, nsq = 1;
-        ICZ_TRY(nn(dZ + s0 * 2 * Hd, 2 * Hd, bt, 2 * Hd, P.dec.aoa_w, 2 * Hd, 2 * Hd, X2, xfloats, &ns2, STEP_WGS, st, live));
+        ICZ_TRY(nn(dZ + s0 * 2 * Hd, 2 * Hd, bt, 2 * Hd, P.dec.aoa_w, 2 * Hd, 2 * Hd, X2, xfloats, &ns2, split_backward(STEP_WGS), st, live));
         hipLaunchKernelGGL(aoa_dec_attn_bwd_kernel, dim3(bt, NH), dim3(256), lds, st, X2, ns2, bt, tP + s0 * NH * R, tPd + s0 * NH * R,
                            tQp + s0 * Hd, Kd, Vd, dQp + s0 * Hd, tdS + s0 * NH * R, tdX + s0 * Hd, R, Hd, NH, region_rows(), io.d_att.mode ? io.d_att.scale : 1.0f, live, rows_img);
-        ICZ_TRY(nn(dQp + s0 * Hd, Hd, bt, Hd, P.dec.q_w, Hd, Hd, ws, ws_floats, &nsq, STEP_WGS, st, live));
+        ICZ_TRY(nn(dQp + s0 * Hd, Hd, bt, Hd, P.dec.q_w, Hd, Hd, ws, ws_floats, &nsq, split_backward(STEP_WGS), st, live));
         hipLaunchKernelGGL(aoa_ln_bwd_kernel, dim3(bt), dim3(256), 0, st, ws, nsq, X2, ns2, bt, th + (s0 + B) * Hd, tstats + s0 * 2,
                            P.dec.ln_g, dQn + s0 * Hd, dHln, Hd, live);
         LstmBwdArgs a = {};
@@ -625,7 +597,7 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
         a.rows = bt; a.H = Hd; a.live = live; a.carry_live = carry_live;
         hipLaunchKernelGGL(lstm_bwd_point_kernel, dim3(cdiv(Hd, 256), bt), dim3(256), 0, st, a, off);
         // [du_t | dh_{t-1}] = dgates_t . [W_ih[:, E:] | W_hh]
-        if (t > 0) ICZ_TRY(nn(dG + s0 * 4 * Hd, 4 * Hd, bt, 4 * Hd, w_rec, 2 * Hd, 2 * Hd, X, xfloats, &nsx, STEP_WGS, st, live));
+        if (t > 0) ICZ_TRY(nn(dG + s0 * 4 * Hd, 4 * Hd, bt, 4 * Hd, w_rec, 2 * Hd, 2 * Hd, X, xfloats, &nsx, split_backward(STEP_WGS), st, live));
         bnext = bt;
         cur ^= 1;
     }
@@ -638,56 +610,42 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     const bool tail_side = side && tail_side_on;
     if (tail_side) ICZ_CHECK_HIP(hipEventRecord(low.fork[1], st));
     // ---- embedding gradient
-    ICZ_TRY(nn(dG, 4 * Hd, TB, 4 * Hd, P.lstm_w_ih, E + Hd, E, X, xfloats, &ns, TARGET_WGS, st, nullptr, rl));
-    {
-        const size_t MN = (size_t)TB * E;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, X, ns, MN, E, (const float*)nullptr, dEmb);
-    }
+    ICZ_TRY(nn(dG, 4 * Hd, TB, 4 * Hd, P.lstm_w_ih, E + Hd, E, X, xfloats, &ns, split_backward(TARGET_WGS), st, nullptr, rl));
+    ICZ_TRY(launch_slab_reduce(X, ns, TB, E, nullptr, dEmb, st));      // (one slab: a copy)
     ICZ_CHECK_HIP(embed_grad_launch(st, tok, TB, dEmb, 1, (size_t)0, temb, cur_train ? 2.0f : 1.0f, E, G.embed_weight, V, 1, rl));
     // ---- weight gradients: one TN GEMM each over all (t, b) rows
     // (round 5) products that share d y go as one launch over column groups where the shape is taken (gemm_big_x3.hip)
     const GemmColGroup lstm_groups[3] = {{temb, E, E, G.lstm_w_ih, E + Hd}, {tu, Hd, Hd, G.lstm_w_ih + E, E + Hd}, {th, Hd, Hd, G.lstm_w_hh, Hd}};
-    if (gemm_tn_grouped_fits(4 * Hd, TB, lstm_groups, 3)) {
-        ICZ_TRY(gemm_tn_grouped(dG, 4 * Hd, 4 * Hd, TB, lstm_groups, 3, rl, st));
-    } else {
-        ICZ_TRY(tn(dG, 4 * Hd, 4 * Hd, temb, E, E, TB, G.lstm_w_ih, E + Hd, 0, st, rl));
-        ICZ_TRY(tn(dG, 4 * Hd, 4 * Hd, tu, Hd, Hd, TB, G.lstm_w_ih + E, E + Hd, 0, st, rl));
-        ICZ_TRY(tn(dG, 4 * Hd, 4 * Hd, th, Hd, Hd, TB, G.lstm_w_hh, Hd, 0, st, rl));
-    }
-    ICZ_TRY(colsum(dG, TB, 4 * Hd, 4 * Hd, G.lstm_b_ih, st));
+    ICZ_TRY(gemm_tn_groups(dG, 4 * Hd, 4 * Hd, TB, lstm_groups, 3, nullptr, 0, rl, st));
+    ICZ_TRY(launch_colsum(dG, TB, 4 * Hd, 4 * Hd, G.lstm_b_ih, st));
     ICZ_CHECK_HIP(hipMemcpyAsync(G.lstm_b_hh, G.lstm_b_ih, sizeof(float) * 4 * Hd, hipMemcpyDeviceToDevice, st));
     if (grad_cb) grad_cb(grad_cb_user, 1);      // embed + lstm.*: reduced beside the attention block's weight gradients
     const GemmColGroup aoa_groups[2] = {{txatt, Hd, Hd, G.dec.aoa_w, 2 * Hd}, {tqn, Hd, Hd, G.dec.aoa_w + Hd, 2 * Hd}};
-    if (gemm_tn_grouped_fits(2 * Hd, TB, aoa_groups, 2)) {
-        ICZ_TRY(gemm_tn_grouped(dZ, 2 * Hd, 2 * Hd, TB, aoa_groups, 2, rl, st));
-    } else {
-        ICZ_TRY(tn(dZ, 2 * Hd, 2 * Hd, txatt, Hd, Hd, TB, G.dec.aoa_w, 2 * Hd, 0, st, rl));
-        ICZ_TRY(tn(dZ, 2 * Hd, 2 * Hd, tqn, Hd, Hd, TB, G.dec.aoa_w + Hd, 2 * Hd, 0, st, rl));
-    }
-    ICZ_TRY(colsum(dZ, TB, 2 * Hd, 2 * Hd, G.dec.aoa_b, st));
+    ICZ_TRY(gemm_tn_groups(dZ, 2 * Hd, 2 * Hd, TB, aoa_groups, 2, nullptr, 0, rl, st));
+    ICZ_TRY(launch_colsum(dZ, TB, 2 * Hd, 2 * Hd, G.dec.aoa_b, st));
     // ---- the attention block's small products (three Hd x Hd weight gradients, d K / d V, seven column sums: 240 us of kernels that fill a
     //      fraction of the chip, eager timeline round 6) depend on the loop only: without a DP callback they run on the side stream beside
     //      the embedding / LSTM / AoA-linear gradients above -- forked at the loop's end, ISSUED last, joined here (as Butd::bptt's tail)
     hipStream_t ts = tail_side ? low.st : st;
     auto tail = [&]() -> int {
-    ICZ_TRY(tn(dQp, Hd, Hd, tqn, Hd, Hd, TB, G.dec.q_w, Hd, 0, ts, rl));
-    ICZ_TRY(colsum(dQp, TB, Hd, Hd, G.dec.q_b, ts));
+    ICZ_TRY(gemm_tn(dQp, Hd, Hd, tqn, Hd, Hd, TB, G.dec.q_w, Hd, 0, rl, ts));
+    ICZ_TRY(launch_colsum(dQp, TB, Hd, Hd, G.dec.q_b, ts));
     {
         const int tc_fit = (int)(48 * 1024 / (sizeof(float) * 2 * (R + dh))), tc = K * T < tc_fit ? K * T : tc_fit;
         hipLaunchKernelGGL(aoa_dkv_kernel, dim3(n_img, NH), dim3(256), sizeof(float) * (size_t)tc * 2 * (R + dh), ts, tdS, tPd, tQp, tdX, dKd, dVd, B, T,
                            tc, R, Hd, NH, region_rows(), K);
     }
     const int rrows = (int)region_row_count(n_img);      // region rows of the batch (packed valid rows with per-image counts)
-    ICZ_TRY(tn(dKd, Hd, Hd, refined, Hd, Hd, rrows, G.dec.k_w, Hd, 0, ts));
-    ICZ_TRY(colsum(dKd, rrows, Hd, Hd, G.dec.k_b, ts));
-    ICZ_TRY(tn(dVd, Hd, Hd, refined, Hd, Hd, rrows, G.dec.v_w, Hd, 0, ts));
-    ICZ_TRY(colsum(dVd, rrows, Hd, Hd, G.dec.v_b, ts));
+    ICZ_TRY(gemm_tn(dKd, Hd, Hd, refined, Hd, Hd, rrows, G.dec.k_w, Hd, 0, nullptr, ts));
+    ICZ_TRY(launch_colsum(dKd, rrows, Hd, Hd, G.dec.k_b, ts));
+    ICZ_TRY(gemm_tn(dVd, Hd, Hd, refined, Hd, Hd, rrows, G.dec.v_w, Hd, 0, nullptr, ts));
+    ICZ_TRY(launch_colsum(dVd, rrows, Hd, Hd, G.dec.v_b, ts));
     // ---- h_norm gain / bias
     {
         const size_t n = (size_t)TB * Hd;
         hipLaunchKernelGGL(aoa_ln_prod_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ts, dQn, th + sH, tstats, prod, (size_t)TB, Hd);
-        ICZ_TRY(colsum(prod, TB, Hd, Hd, G.dec.ln_g, ts));
-        ICZ_TRY(colsum(dQn, TB, Hd, Hd, G.dec.ln_b, ts));
+        ICZ_TRY(launch_colsum(prod, TB, Hd, Hd, G.dec.ln_g, ts));
+        ICZ_TRY(launch_colsum(dQn, TB, Hd, Hd, G.dec.ln_b, ts));
     }
     return ICZ_OK;
     };

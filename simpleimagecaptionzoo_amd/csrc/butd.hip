@@ -80,13 +80,9 @@ int Butd::refresh(hipStream_t st) {
 
 // the transposed copies serve 33..64-row dgrad steps through gemm_resident_x3: K = 4H in whole k ranges, N = D + H / H wide enough
 bool Butd::wt_possible() const {
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.seg[0] = {w_enc, w_enc, 4 * dims.H, 4 * dims.H, 4 * dims.H, nullptr};     // placeholders: only the shape is looked at
-    g.M = 64; g.N = dims.D + dims.H;
-    GemmArgs p = g, q = g;
-    p.N = q.N = dims.H;
-    p.nseg = 2; p.seg[1] = p.seg[0];
+    const GemmSeg s = {w_enc, w_enc, 4 * dims.H, 4 * dims.H, 4 * dims.H};       // placeholders: only the shape is looked at
+    const GemmArgs g = gemm_args({s}, 64, dims.D + dims.H, nullptr, 0);
+    const GemmArgs p = gemm_args({s, s}, 64, dims.H, nullptr, 0), q = gemm_args({s}, 64, dims.H, nullptr, 0);
     return dims.H % 64 == 0 && dims.D % 64 == 0 && gemm_resident_x3_fits(g) && gemm_resident_x3_pair_fits(p, q);
 }
 
@@ -109,16 +105,10 @@ int Butd::refresh_transposes(hipStream_t st) {
     return ICZ_OK;
 }
 
-// generic "y = x W^T" with automatic split-K into the workspace; returns the split used (1 = direct into out)
-int Butd::gemm_nt(GemmArgs& g, int* nsplit_out, hipStream_t st) {
-    g.nsplit = gemm_fit_split(GEMM_NT, g, gemm_pick_split(g, TARGET_WGS), ws_floats);
-    if (g.nsplit > 1) {
-        ICZ_REQUIRE(gemm_slab_floats(g.M, g.N, g.nsplit) <= ws_floats, "butd: workspace too small for %dx%dx%d slabs", g.nsplit, g.M, g.N);
-        g.out = ws;
-        g.bias = nullptr;
-    }
-    *nsplit_out = g.nsplit;
-    return gemm_f32(GEMM_NT, g, st);
+// generic "y = x W^T + bias" into g.out, with automatic split-K through the workspace (the split is fitted to it: the capacity
+// check of gemm_finished cannot fail here)
+int Butd::gemm_nt(GemmArgs& g, const float* bias, hipStream_t st) {
+    return gemm_finished(GEMM_NT, g, split_forward(TARGET_WGS), bias, ws, ws_floats, st, "butd");
 }
 
 // Once per batch of images (K0 in SURVEY.md 2.3): mean features, the time-invariant part of the TD-LSTM gates
@@ -129,29 +119,12 @@ int Butd::prologue(const float* feats, int n_img, hipStream_t st) {
     ICZ_REQUIRE(n_img > 0 && n_img <= dims.max_rows, "butd: %d images exceed capacity %d", n_img, dims.max_rows);
     hipLaunchKernelGGL(mean_feats_kernel, dim3(cdiv(D, 1024), n_img), dim3(256), 0, st, feats, mean, R, D);
     {   // premean = mean . W_ih[:, H:H+D]^T   [n_img, 4H]
-        GemmArgs g = {};
-        g.nseg = 1;
-        g.seg[0] = {mean, P.td_w_ih + H, D, H + D + E, D, nullptr};
-        g.M = n_img; g.N = 4 * H; g.out = premean; g.ldo = 4 * H;
-        int ns;
-        ICZ_TRY(gemm_nt(g, &ns, st));
-        if (ns > 1) {
-            size_t MN = (size_t)n_img * 4 * H;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, ws, ns, MN, 4 * H, (const float*)nullptr, premean);
-        }
+        GemmArgs g = gemm_args({{mean, P.td_w_ih + H, D, H + D + E, D}}, n_img, 4 * H, premean, 4 * H);
+        ICZ_TRY(gemm_nt(g, nullptr, st));
     }
     {   // enc_ctx = feats . w_enc^T + b_enc   [n_img*R, A]
-        GemmArgs g = {};
-        g.nseg = 1;
-        g.seg[0] = {feats, w_enc, D, D, D, nullptr};
-        g.M = n_img * R; g.N = A; g.out = enc_ctx; g.ldo = A; g.bias = P.enc_att_b;
-        int ns;
-        const float* bias = g.bias;
-        ICZ_TRY(gemm_nt(g, &ns, st));
-        if (ns > 1) {
-            size_t MN = (size_t)n_img * R * A;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, ws, ns, MN, A, bias, enc_ctx);
-        }
+        GemmArgs g = gemm_args({{feats, w_enc, D, D, D}}, n_img * R, A, enc_ctx, A);
+        ICZ_TRY(gemm_nt(g, P.enc_att_b, st));
     }
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
@@ -169,21 +142,16 @@ int Butd::step(const StepIO& s, hipStream_t st) {
     if (!s.emb_ready)
         hipLaunchKernelGGL(embed_kernel, dim3(cdiv(E, 1024), rows), dim3(256), 0, st, P.embed_weight, s.it, s.emb_out ? s.emb_out : emb, rows, E, s.drop_emb);
     const float* embp = s.emb_out ? s.emb_out : emb;
+    const size_t ws_cap = s.ws_alt ? (tb.xfloats < ws_floats ? tb.xfloats : ws_floats) : ws_floats;      // ws_alt = tb.X[0]
+    // the gates of an LSTM as slabs [ns][rows][4H] in the chain's workspace (one slab: the dense product); the split is fitted to it
+    auto gates = [&](GemmArgs g, int* ns) -> int {
+        ICZ_REQUIRE((size_t)rows * 4 * H <= ws_cap, "butd: workspace too small");
+        return gemm_slabs(GEMM_NT, g, split_forward(STEP_WGS), ws, ws_cap, ns, st, "butd");
+    };
     int ns;
     {   // TD-attention LSTM: [h2, mean, emb] W_ih^T + h1 W_hh^T  (mean part hoisted into premean)
-        GemmArgs g = {};
-        g.nseg = 3;
-        g.seg[0] = {s.h2_in, P.td_w_ih, H, H + D + E, H, nullptr};
-        g.seg[1] = {embp, P.td_w_ih + H + D, E, H + D + E, E, nullptr};
-        g.seg[2] = {s.h1_in, P.td_w_hh, H, H, H, nullptr};
-        g.M = rows; g.N = 4 * H; g.out = ws; g.ldo = 4 * H;
-        g.live = s.live;
-        const size_t ws_cap = s.ws_alt ? (tb.xfloats < ws_floats ? tb.xfloats : ws_floats) : ws_floats;      // ws_alt = tb.X[0]
-        g.nsplit = gemm_fit_split(GEMM_NT, g, gemm_pick_split(g, STEP_WGS), ws_cap);
-        ns = g.nsplit;
-        ICZ_REQUIRE(gemm_slab_floats(rows, 4 * H, ns) <= ws_cap && (size_t)rows * 4 * H <= ws_cap, "butd: workspace too small");
-        if (ns == 1) { g.out = ws; }
-        ICZ_TRY(gemm_f32(GEMM_NT, g, st));
+        ICZ_TRY(gates(gemm_args({{s.h2_in, P.td_w_ih, H, H + D + E, H}, {embp, P.td_w_ih + H + D, E, H + D + E, E}, {s.h1_in, P.td_w_hh, H, H, H}},
+                                rows, 4 * H, ws, 4 * H, s.live), &ns));
         LstmPointArgs a = {ws, ns, premean, s.img_of_row, P.td_b_ih, P.td_b_hh, s.c1_in, s.h1_out, s.c1_out, s.gates_td_out, nullptr, rows, H, s.live};
         kprof_mark(KP_LSTM_POINT, true, st);
         launch_lstm_point(a, off, st);
@@ -191,14 +159,9 @@ int Butd::step(const StepIO& s, hipStream_t st) {
     }
     {   // attention
         kprof_mark(KP_ATTENTION, true, st);
-        GemmArgs g = {};
-        g.nseg = 1;
-        g.seg[0] = {s.h1_out, w_dec, H, H, H, nullptr};
-        g.M = rows; g.N = A; g.out = ws; g.ldo = A;
-        g.live = s.live;
-        g.nsplit = gemm_pick_split(g, STEP_WGS);
-        ns = g.nsplit;
-        ICZ_TRY(gemm_f32(GEMM_NT, g, st));
+        GemmArgs g = gemm_args({{s.h1_out, w_dec, H, H, H}}, rows, A, ws, A, s.live);
+        ns = gemm_pick_split(g, STEP_WGS);
+        ICZ_TRY(gemm_slabs(GEMM_NT, g, ns, ws, ws_cap, st, "butd"));
         AttScoreArgs a = {enc_ctx, s.img_of_row, ws, ns, P.dec_att_b, w_aff, P.affine_b, s.dec_ctx_out, scores, rows, R, A, s.live};
         const int G = s.rows_per_img;
         // compare the accumulation order: the per-row kernel sums a region row in the lane order of three regions at a time, the
@@ -220,24 +183,13 @@ int Butd::step(const StepIO& s, hipStream_t st) {
     }
     const float* ctxp = s.ctx_out ? s.ctx_out : ctx;
     {   // language LSTM: [ctx, h1] W_ih^T + h2 W_hh^T
-        GemmArgs g = {};
-        g.nseg = 3;
-        g.seg[0] = {ctxp, P.lm_w_ih, D, D + H, D, nullptr};
-        g.seg[1] = {s.h1_out, P.lm_w_ih + D, H, D + H, H, nullptr};
-        g.seg[2] = {s.h2_in, P.lm_w_hh, H, H, H, nullptr};
-        g.M = rows; g.N = 4 * H; g.out = ws; g.ldo = 4 * H;
-        g.live = s.live;
-        const size_t ws_cap = s.ws_alt ? (tb.xfloats < ws_floats ? tb.xfloats : ws_floats) : ws_floats;
-        g.nsplit = gemm_fit_split(GEMM_NT, g, gemm_pick_split(g, STEP_WGS), ws_cap);
-        ns = g.nsplit;
-        ICZ_REQUIRE(gemm_slab_floats(rows, 4 * H, ns) <= ws_cap && (size_t)rows * 4 * H <= ws_cap, "butd: workspace too small");
-        ICZ_TRY(gemm_f32(GEMM_NT, g, st));
+        ICZ_TRY(gates(gemm_args({{ctxp, P.lm_w_ih, D, D + H, D}, {s.h1_out, P.lm_w_ih + D, H, D + H, H}, {s.h2_in, P.lm_w_hh, H, H, H}},
+                                rows, 4 * H, ws, 4 * H, s.live), &ns));
         LstmPointArgs a = {ws, ns, nullptr, nullptr, P.lm_b_ih, P.lm_b_hh, s.c2_in, s.h2_out, s.c2_out, s.gates_lm_out,
                            s.h2drop_out ? s.h2drop_out : h2drop, rows, H, s.live};
         launch_lstm_point(a, s.drop_out, st);
     }
     if (!s.skip_predict) {   // predict: logits = drop(h2) w_pred^T + b  (finished logits, or split-K slabs in the chain's workspace for a consumer that sums them)
-        const size_t ws_cap = s.ws_alt ? (tb.xfloats < ws_floats ? tb.xfloats : ws_floats) : ws_floats;      // ws_alt = tb.X[0]
         ICZ_TRY(gemm_predict(s.h2drop_out ? s.h2drop_out : h2drop, H, w_pred, P.predict_b, rows, V, Vp, s.logits_out ? s.logits_out : logits,
                              s.logits_ld ? s.logits_ld : Vp, ws, ws_cap, s.pred_nsplit, st, s.live));
     }

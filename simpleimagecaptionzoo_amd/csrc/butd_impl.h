@@ -90,7 +90,7 @@ struct Butd : CaptionHead, DecodeMember {
     int alloc(void** p, size_t bytes) { return mem.alloc(p, bytes); }
     int init(const icz_butd_dims& d);
     int refresh(hipStream_t st);
-    int gemm_nt(GemmArgs& g, int* nsplit_out, hipStream_t st);
+    int gemm_nt(GemmArgs& g, const float* bias, hipStream_t st);
     int prologue(const float* feats, int n_img, hipStream_t st);
     int step(const StepIO& s, hipStream_t st);
     int zero_state(int rows, int which, hipStream_t st);
@@ -165,9 +165,10 @@ struct Butd : CaptionHead, DecodeMember {
     int xe_backward_dlogits(const float* dpacked, const icz_butd_params* G, hipStream_t st);
     int xe_backward(float smoothing, const icz_butd_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
     int gemm_auto(GemmLayout layout, GemmArgs& g, float* slab, size_t slab_floats, int* ns_out, hipStream_t st);
+    // the wgrad slab region of the stream a product is issued on: never shared between streams (TrainBuf::wslab)
+    int wslab_of(hipStream_t st) const { return st == low.st ? 1 : 0; }
     int wgrad(const float* dY, int ldy, int M, const float* X, int ldx, int N, int K, float* out, int ldo, hipStream_t st, const int* rows_live = nullptr);
     int bptt_prelude(hipStream_t st);
-    int colsum(const float* X, int K, int N, int ldx, float* out, hipStream_t st);
     int bptt(const icz_butd_params& G, hipStream_t st, int phases = 0xF, bool fire_cb = true);
 };
 

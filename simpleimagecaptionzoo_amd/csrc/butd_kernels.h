@@ -80,21 +80,6 @@ __global__ __launch_bounds__(256) void mean_feats_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// sum split-K slabs (+ bias):  out[m, n] = sum_z slab[z, m, n] + bias[n]
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slab, int nsplit, size_t MN, int N,
-                                                          const float* __restrict__ bias, float* __restrict__ out) {
-    size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= MN) return;
-    f32x4 s = *reinterpret_cast<const f32x4*>(slab + i);
-    for (int z = 1; z < nsplit; ++z) s += *reinterpret_cast<const f32x4*>(slab + (size_t)z * MN + i);
-    if (bias) {
-        int n = (int)(i % N);
-        s += *reinterpret_cast<const f32x4*>(bias + n);
-    }
-    *reinterpret_cast<f32x4*>(out + i) = s;
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // Embedding -> ReLU -> Dropout (:77-81):  emb[row,:] = relu(E[it[row],:]) * keep * 2
 __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ table, const int64_t* __restrict__ it,
                                                     float* __restrict__ emb, int rows, int E, DropCfg dc, int relu = 1,
@@ -1800,37 +1785,8 @@ __global__ void row_image_kernel(int32_t* __restrict__ img, int rows, int G) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// out[n] = sum_k X[k, n] (column sums over K rows; bias gradients) in one launch, fixed order -> reproducible.
-// Grid (N/32), 256 threads = 32 columns x 8 row groups: thread (c, g) adds rows g, g+8, ... of its column (eight independent
-// loads in flight), the eight groups meet in LDS and are added in group order.
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X, int K, int N, int ldx, float* __restrict__ out) {
-    __shared__ float part[8][33];
-    const int c = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const int n = blockIdx.x * 32 + c;
-    float s = 0.f;
-    if (n < N) {
-        const float* x = X + n;
-        int k = g;
-        for (; k + 56 < K; k += 64) {
-            float v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = x[(size_t)(k + 8 * u) * ldx];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; k < K; k += 8) s += x[(size_t)k * ldx];
-    }
-    part[g][c] = s;
-    __syncthreads();
-    if (g == 0 && n < N) {
-        float t = part[0][c];
-#pragma unroll
-        for (int q = 1; q < 8; ++q) t += part[q][c];
-        out[n] = t;
-    }
-}
-
-// Several column sums in ONE launch (the bias gradients at the end of BPTT): blocks laid out job after job; out2 (optional)
+// Several column sums in ONE launch (the bias gradients at the end of BPTT; a single sum is launch_colsum, gemm_ops.h, with the same
+// scheme: 32 columns x 8 row groups per block, the groups added in group order): blocks laid out job after job; out2 (optional)
 // receives a copy (b_ih and b_hh have the same gradient); a job with K = 0 writes zeros.
 struct ColsumJob { const float* X; int K, N, ldx; float* out; float* out2; int block0; };
 struct ColsumTable { ColsumJob j[8]; int count; };

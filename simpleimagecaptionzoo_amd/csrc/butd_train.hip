@@ -7,8 +7,6 @@
 
 namespace icz {
 
-static inline int round4(int x) { return pad_vocab(x); }   // (historic name) padded vocabulary size
-
 __global__ void sample_init_kernel(uint8_t* unf, int* nunf, int64_t* tok, int B, int T) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < B) { unf[i] = 1; tok[i] = 1; }
@@ -41,7 +39,7 @@ int Butd::ensure_train(int B, int T) {
     }
     DeviceBuffers::TrainingScope scope(mem);
     const size_t H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = dims.R, V = dims.V;
-    const size_t Vp = round4(dims.V);
+    const size_t Vp = pad_vocab(dims.V);
     const size_t TB = (size_t)T * B;
     ICZ_TRY(alloc((void**)&tb.tok, sizeof(int64_t) * (TB + B)));
     ICZ_TRY(alloc((void**)&tb.emb, sizeof(float) * TB * E));
@@ -124,7 +122,7 @@ static DropCfg make_drop(const uint64_t* seed_p, bool train, const uint8_t* base
 int Butd::train_step(const float* feats, int rows, int Bs, int t, bool train, hipStream_t st, bool emb_ready, int* pred_nsplit, bool skip_predict,
                      const int* live, int row0) {
     const size_t H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = dims.R;
-    const size_t Vp = round4(dims.V);
+    const size_t Vp = pad_vocab(dims.V);
     const size_t slot = (size_t)t * Bs;
     StepIO s = {};
     s.emb_ready = emb_ready;         // written by the previous step's sample_select_kernel
@@ -176,11 +174,6 @@ int Butd::sample_impl(const float* feats, int B, int T, int64_t* seq_out, float*
     return sample_chain(feats, B, T, seq_out, logp_out, st);
 }
 
-__global__ void imgk_init_kernel(int32_t* imgk, int rows, int K) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < rows) imgk[i] = i / K;
-}
-
 // Multi-sample SCST rollout (beyond the reference: the "new self-critical" variant, K sampled captions per image): the per-image
 // prologue runs once over the B images, the sampled chain over B K decoder rows, row = img * K + k, whose kernels find their image's
 // hoisted tensors / features through tb.imgk (the grouped attention kernels take the K rows of an image in one workgroup).  Dropout
@@ -208,7 +201,7 @@ int Butd::sample_n(const float* feats, int B, int K, int T, const icz_rng* r, in
 
 int Butd::sample_n_impl(const float* feats, int B, int K, int T, int64_t* seq_out, float* logp_out, hipStream_t st) {
     ICZ_TRY(prologue(feats, B, st));
-    hipLaunchKernelGGL(imgk_init_kernel, dim3(cdiv(B * K, 256)), dim3(256), 0, st, tb.imgk, B * K, K);
+    hipLaunchKernelGGL(row_image_kernel, dim3(cdiv(B * K, 256)), dim3(256), 0, st, tb.imgk, B * K, K);
     return sample_chain(feats, B * K, T, seq_out, logp_out, st);
 }
 
@@ -270,7 +263,7 @@ __global__ void merged_init_kernel(int32_t* img2, int B, int* nany, int T, int64
 // sample_select_kernel<true>); the slots hold 2 B rows per step, the backward pass works on the second half (Butd::bptt).
 int Butd::sample_chain(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st, int row0, int64_t* ids_out) {
     const size_t H = dims.H;
-    const size_t Vp = round4(dims.V);
+    const size_t Vp = pad_vocab(dims.V);
     const int Bs = B + row0;
     // slot 0 of the state buffers = zeros; unfinished flags = 1, counters = 0, first token = <sta>
     {
@@ -359,7 +352,7 @@ int Butd::sample_backward(const float* reward, const icz_butd_params* G, float* 
 
 int Butd::sample_backward_impl(const float* reward, const icz_butd_params& G, float* loss_out, float* mask_sum_out, hipStream_t st,
                                int phases, bool fire_cb) {
-    if (phases & 1) ICZ_TRY(reinforce(reward, tb.logit, dims.V, round4(dims.V), loss_out, mask_sum_out, st, cur_rows, cur_row0));
+    if (phases & 1) ICZ_TRY(reinforce(reward, tb.logit, dims.V, pad_vocab(dims.V), loss_out, mask_sum_out, st, cur_rows, cur_row0));
     return bptt(G, st, phases, fire_cb);
 }
 
@@ -376,7 +369,7 @@ int Butd::xe_forward(const float* feats, const int64_t* captions, int B, int L, 
     cur_feats = feats;
     cur_rows = B; cur_row0 = 0; cur_K = 1; cur_nimg = B;
     const size_t H = dims.H;
-    const size_t Vp = round4(dims.V);
+    const size_t Vp = pad_vocab(dims.V);
     ICZ_TRY(prologue(feats, B, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tb.h1, 0, sizeof(float) * B * H, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tb.c1, 0, sizeof(float) * B * H, st));
@@ -404,10 +397,8 @@ int Butd::xe_forward(const float* feats, const int64_t* captions, int B, int L, 
         // logits of all (t, b) rows at once: [T B, H] x w_pred^T + b through the 128 x 128 split-precision kernel (one pass over the
         // vocabulary matrix instead of T).  Rows b >= rows_t[t] hold whatever their h2 slots held: nothing reads them before
         // xe_loss_dlogits_kernel / scatter_packed_kernel overwrite them with zeros.
-        GemmArgs g = {};
-        g.nseg = 1;
-        g.seg[0] = {tb.h2d, w_pred, (int)H, (int)H, (int)H, nullptr};
-        g.M = T * B; g.N = dims.V; g.out = tb.logit; g.ldo = (int)Vp; g.bias = P.predict_b; g.nsplit = 1;
+        GemmArgs g = gemm_args({{tb.h2d, w_pred, (int)H, (int)H, (int)H}}, T * B, dims.V, tb.logit, (int)Vp);
+        g.bias = P.predict_b;
         ICZ_TRY(gemm_f32(GEMM_NT, g, st));
     }
     if (packed_out) ICZ_TRY(gather_packed(tb.logit, dims.V, (int)Vp, packed_out, st));
@@ -418,23 +409,18 @@ int Butd::xe_forward(const float* feats, const int64_t* captions, int B, int L, 
 int Butd::xe_backward_dlogits(const float* dpacked, const icz_butd_params* G, hipStream_t st) {
     ICZ_TRY(require_mode(2, "butd"));
     ICZ_REQUIRE(dpacked && G, "butd xe_backward_dlogits: null argument");
-    ICZ_TRY(scatter_packed(dpacked, dims.V, round4(dims.V), tb.logit, st));
+    ICZ_TRY(scatter_packed(dpacked, dims.V, pad_vocab(dims.V), tb.logit, st));
     mode = 0;
     bptt_early_out = false;
     ICZ_TRY(bptt_prelude(st));
     return bptt(*G, st);
 }
 
-__global__ void transpose_coef_kernel(const float* __restrict__ dlogp, int n, float* __restrict__ coef) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) coef[i] = dlogp[i];
-}
-
 int Butd::sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hipStream_t st) {
     ICZ_TRY(require_mode(1, "butd"));
     ICZ_REQUIRE(dlogp && G, "butd sample_backward_dlogp: null argument");
     const int B = cur_B, T = cur_T;
-    const int Vp = round4(dims.V);
+    const int Vp = pad_vocab(dims.V);
     ICZ_CHECK_HIP(hipMemcpyAsync(coef, dlogp, sizeof(float) * B * T, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(reinforce_dlogits_kernel, dim3(cdiv(Vp, 256), T * cur_rows), dim3(256), 0, st, tb.logit, dims.V, Vp,
                        draw, lse, coef, B, T, cur_rows, cur_row0);
@@ -448,7 +434,7 @@ int Butd::sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hi
 int Butd::xe_backward(float smoothing, const icz_butd_params* G, float* loss_out, float n_tokens_global, hipStream_t st) {
     ICZ_TRY(require_mode(2, "butd"));
     ICZ_REQUIRE(G, "butd xe_backward: null grads");
-    ICZ_TRY(xe_loss(smoothing, n_tokens_global, tb.logit, dims.V, round4(dims.V), loss_out, st));
+    ICZ_TRY(xe_loss(smoothing, n_tokens_global, tb.logit, dims.V, pad_vocab(dims.V), loss_out, st));
     bptt_early_out = false;
     ICZ_TRY(bptt_prelude(st));
     return bptt(*G, st);
@@ -456,44 +442,17 @@ int Butd::xe_backward(float smoothing, const icz_butd_params* G, float* loss_out
 
 // ------------------------------------------------------------------------------------------------
 // helpers for the backward GEMMs
+// direct output (ns = 1, where g.out points) if there are already enough tiles, else slabs in `slab` (null: never split above 64 rows)
 int Butd::gemm_auto(GemmLayout layout, GemmArgs& g, float* slab, size_t slab_floats, int* ns_out, hipStream_t st) {
-    // direct output (nsplit 1) if there are already enough tiles, else slabs
-    g.nsplit = g.M <= 64 ? gemm_pick_split(g, STEP_WGS, layout) : gemm_pick_split_balanced(g, layout, slab ? slab_floats : 0);
-    if (g.nsplit > 1) {
-        ICZ_REQUIRE(slab && gemm_slab_floats(g.M, g.N, g.nsplit) <= slab_floats, "butd: slab buffer too small (%d x %d x %d)", g.nsplit, g.M, g.N);
-        g.out = slab; g.ldo = g.N; g.bias = nullptr; g.accumulate = 0;
-    }
-    if (ns_out) *ns_out = g.nsplit;
-    return gemm_f32(layout, g, st);
+    return gemm_slabs(layout, g, split_backward(STEP_WGS), slab, slab_floats, ns_out, st, "butd");
 }
 
-// C (ldc) = A^T B over K rows, written directly (no split): weight gradients
+// C (ldc) = A^T B over K rows: weight gradients.  Too few 128 x 128 tiles to fill the chip (at full width the attention projections):
+// split K on the large-tile split-precision kernel, sum the slabs (gemm_tn_auto) -- in the slab region of the stream the product is
+// issued on (no two streams share slab memory: the side stream's products have a region of their own, see ensure_train)
 int Butd::wgrad(const float* dY, int ldy, int M, const float* X, int ldx, int N, int K, float* out, int ldo, hipStream_t st, const int* rows_live) {
-    // too few 128 x 128 tiles to fill the chip (at full width the attention projections): split K on the large-tile split-precision kernel, sum the slabs
-    // (no two streams share slab memory: the side stream's products have a region of their own, see ensure_train)
-    float* const slab = tb.wslab[st == low.st ? 1 : 0];
-    const size_t slab_floats = tb.wslab_floats[st == low.st ? 1 : 0];
-    if (slab && ldo == N) {
-        const int ns = gemm_tn_split_pick(M, N, K);
-        if (ns > 1 && (size_t)ns * M * N <= slab_floats && ((size_t)M * N) % 4 == 0) {
-            ICZ_TRY(gemm_tn_split(dY, ldy, M, X, ldx, N, K, ns, slab, rows_live, st));
-            const size_t MN = (size_t)M * N;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, (const float*)slab, ns, MN, N, (const float*)nullptr, out);
-            ICZ_CHECK_HIP(hipGetLastError());
-            return ICZ_OK;
-        }
-    }
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.rows_live = rows_live;
-    g.seg[0] = {dY, X, ldy, ldx, K, nullptr};
-    g.M = M; g.N = N; g.out = out; g.ldo = ldo; g.nsplit = 1;
-    return gemm_f32(GEMM_TN, g, st);
-}
-
-int Butd::colsum(const float* X, int K, int N, int ldx, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(N, 32)), dim3(256), 0, st, X, K, N, ldx, out);
-    return ICZ_OK;
+    const int r = wslab_of(st);
+    return gemm_tn_auto(dY, ldy, M, X, ldx, N, K, out, ldo, tb.wslab[r], tb.wslab_floats[r], rows_live, st);
 }
 
 // The transposed weight copies of the per-step dgrad products are rebuilt lazily, by the first backward call after an optimizer
@@ -515,7 +474,7 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     // except behind a merged chain, whose evaluation-mode rows in front carry zero gradient rows through the GEMMs over all steps)
     const int B = cur_B, T = cur_T, Bs = cur_rows, roff = cur_row0;
     const int H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = dims.R, V = dims.V;
-    const int Vp = round4(V);
+    const int Vp = pad_vocab(V);
     const int TB = T * Bs;
     const float* feats = cur_feats;
     const size_t sH = (size_t)Bs * H;
@@ -541,7 +500,7 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
         ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, ev_fork, 0));
         hipStream_t sb = concurrent ? low.st : st;   // low priority: the big GEMM only fills CUs the BPTT chain leaves idle
         int s1 = wgrad(tb.logit, Vp, Vp, tb.h2d, H, H, TB, tb.dWp, H, sb, rl);
-        hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(V, 32)), dim3(256), 0, sb, tb.logit, TB, V, (int)Vp, G.predict_b);
+        (void)launch_colsum(tb.logit, TB, V, Vp, G.predict_b, sb);
         hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, sb, tb.dWp, H, P.predict_v, P.predict_g, n_pred,
                            G.predict_v, G.predict_g, V, H);
         ICZ_CHECK_HIP(hipEventRecord(ev_join, sb));
@@ -550,17 +509,10 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     };
     ICZ_CHECK_HIP(hipEventRecord(ev_fork, st));
     {
-        GemmArgs g = {};
-        g.nseg = 1;
-        g.seg[0] = {tb.logit, w_pred, Vp, H, Vp, nullptr};
-        g.M = TB; g.N = H; g.out = tb.dH2d; g.ldo = H; g.rows_live = rl;
-        int ns;
-        const int sg = gemm_auto(GEMM_NN, g, ws, ws_floats, &ns, st);
-        if (sg != ICZ_OK) return sg;          // nothing is forked yet: the side branch is issued behind this product
-        if (ns > 1) {
-            size_t MN = (size_t)TB * H;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, ws, ns, MN, H, (const float*)nullptr, tb.dH2d);
-        }
+        GemmArgs g = gemm_args({{tb.logit, w_pred, Vp, H, Vp}}, TB, H, tb.dH2d, H);
+        g.rows_live = rl;
+        // nothing is forked yet: the side branch is issued behind this product
+        ICZ_TRY(gemm_finished(GEMM_NN, g, split_backward(STEP_WGS), nullptr, ws, ws_floats, st, "butd"));
     }
     ICZ_TRY(side_branch());
     // ---- XE only: rows that dropped out of the batch must contribute zero (the sample path writes every row, and its
@@ -608,37 +560,28 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
         // <= 32 rows (small batches, the tail of a ragged XE batch): the NN kernel streams W[k][n] at ~2 TB/s there, the fp32 NT kernel
         // the transposed copies at 3.4 - 4.4 (profiles/r05_scst_b8_*: 12 us for 26 MB against 12 us for 40 MB)
         const bool tdg = small_nt && wt_lm_ih && wt_fresh && bt <= 32;
-        if (rdg) {   // X1 = dG_lm . W_ih_lm   [bt, D+H]
-            GemmArgs g = {};
-            g.nseg = 1;
-            g.seg[0] = {tb.dGlm + slot * 4 * H, wt_lm_ih, 4 * H, 4 * H, 4 * H, nullptr};
-            g.M = bt; g.N = D + H; g.out = tb.X[0]; g.ldo = D + H; g.live = live;
-            g.nsplit = ns1 = gemm_resident_x3_nsplit(g);
-            ICZ_REQUIRE(gemm_slab_floats(bt, D + H, ns1) <= tb.xfloats, "butd: slab buffer too small for the dgrad slabs");
-            ICZ_TRY(gemm_f32(GEMM_NT, g, st));
-        } else if (tdg) {   // <= 32 rows: the same product on the transposed copy through the fp32 NT kernel
-            GemmArgs g = {};
-            g.nseg = 1;
-            g.seg[0] = {tb.dGlm + slot * 4 * H, wt_lm_ih, 4 * H, 4 * H, 4 * H, nullptr};
-            g.M = bt; g.N = D + H; g.out = tb.X[0]; g.ldo = D + H; g.live = live;
-            ICZ_TRY(gemm_auto(GEMM_NT, g, tb.X[0], tb.xfloats, &ns1, st));
-        } else {
-            GemmArgs g = {};
-            g.nseg = 1;
-            g.seg[0] = {tb.dGlm + slot * 4 * H, P.lm_w_ih, 4 * H, D + H, 4 * H, nullptr};
-            g.M = bt; g.N = D + H; g.out = tb.X[0]; g.ldo = D + H; g.live = live;
-            ICZ_TRY(gemm_auto(GEMM_NN, g, tb.X[0], tb.xfloats, &ns1, st));
-        }
+        // The route selects only the weight operand and the layout of a per-step dgrad product dx = d gates . W over K = 4H: rdg and tdg
+        // take the transposed copy (NT), else W itself (NN).  Each product leaves ns slabs [bt, N] (one: dense) in its tb.X buffer.
+        const GemmLayout lay = (rdg || tdg) ? GEMM_NT : GEMM_NN;
+        const float* const dglm = tb.dGlm + slot * 4 * H;
+        const float* const dgtd = tb.dGtd + slot * 4 * H;      // (written by this step's TD-LSTM kernel below, before the products that read it)
+        auto wseg = [&](const float* dg, const float* w_t, const float* w, int ldw) -> GemmSeg {
+            return lay == GEMM_NT ? GemmSeg{dg, w_t, 4 * H, 4 * H, 4 * H} : GemmSeg{dg, w, 4 * H, ldw, 4 * H};
+        };
+        auto dgrad = [&](GemmArgs g, float* slab, int* ns) -> int {
+            if (!rdg) return gemm_auto(lay, g, slab, tb.xfloats, ns, st);
+            *ns = gemm_resident_x3_nsplit(g);      // the resident kernel's fixed decomposition (sized by the rdg condition above)
+            return gemm_slabs(GEMM_NT, g, *ns, slab, tb.xfloats, st, "butd");
+        };
+        // X1 = dG_lm . W_ih_lm   [bt, D+H]
+        ICZ_TRY(dgrad(gemm_args({wseg(dglm, wt_lm_ih, P.lm_w_ih, D + H)}, bt, D + H, tb.X[0], D + H, live), tb.X[0], &ns1));
         {   // attention backward
             const int dparts = cdiv(D, DALPHA_COLS);
             hipLaunchKernelGGL(att_bwd_dalpha_kernel, dim3(bt, dparts), dim3(256), 0, st, tb.X[0], ns1, D + H, bt, feats, R, D, tb.dalpha, live, imgk);
             AttBwdDdecArgs da = {enc_ctx, tb.dec + slot * A, w_aff, tb.alpha + slot * R, tb.dalpha, tb.dDec + slot * A, tb.dS + slot * R, R, A, dparts, live, imgk};
             hipLaunchKernelGGL(att_bwd_ddec_kernel, dim3(bt, cdiv(A, 256)), dim3(256), 0, st, da, d_att);
             // X2 = dDec . w_dec   [bt, H]
-            GemmArgs g = {};
-            g.nseg = 1;
-            g.seg[0] = {tb.dDec + slot * A, w_dec, A, H, A, nullptr};
-            g.M = bt; g.N = H; g.out = tb.X[1]; g.ldo = H; g.live = live;
+            GemmArgs g = gemm_args({{tb.dDec + slot * A, w_dec, A, H, A}}, bt, H, tb.X[1], H, live);
             ICZ_TRY(gemm_auto(GEMM_NN, g, tb.X[1], tb.xfloats, &ns2, st));
         }
         {   // TD LSTM backward (pointwise): dh1 = carry + X1[:, D:] + X2
@@ -653,49 +596,17 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
             a.rows = bt; a.H = H; a.live = live; a.carry_live = carry_live;
             hipLaunchKernelGGL(lstm_bwd_point_kernel, dim3(cdiv(H, 256), bt), dim3(256), 0, st, a, d_off);
         }
-        if (t > 0 && rdg) {   // d h2_{t-1} (X3) and d h1_{t-1} (X4) in one launch
-            GemmArgs g3 = {}, g4 = {};
-            g3.nseg = 2;
-            g3.seg[0] = {tb.dGlm + slot * 4 * H, wt_lm_hh, 4 * H, 4 * H, 4 * H, nullptr};
-            g3.seg[1] = {tb.dGtd + slot * 4 * H, wt_td_ih_h2, 4 * H, 4 * H, 4 * H, nullptr};
-            g3.M = bt; g3.N = H; g3.out = tb.X[2]; g3.ldo = H; g3.live = live;
-            g4.nseg = 1; g4.live = live;
-            g4.seg[0] = {tb.dGtd + slot * 4 * H, wt_td_hh, 4 * H, 4 * H, 4 * H, nullptr};
-            g4.M = bt; g4.N = H; g4.out = tb.X[3]; g4.ldo = H;
-            ns3 = gemm_resident_x3_nsplit(g3); ns4 = gemm_resident_x3_nsplit(g4);
-            ICZ_REQUIRE(gemm_slab_floats(bt, H, ns3) <= tb.xfloats, "butd: slab buffer too small for the dgrad slabs");
-            ICZ_TRY(gemm_resident_x3_pair(g3, g4, st));
-        } else if (t > 0 && tdg) {
-            {
-                GemmArgs g = {};
-                g.nseg = 2;
-                g.seg[0] = {tb.dGlm + slot * 4 * H, wt_lm_hh, 4 * H, 4 * H, 4 * H, nullptr};
-                g.seg[1] = {tb.dGtd + slot * 4 * H, wt_td_ih_h2, 4 * H, 4 * H, 4 * H, nullptr};
-                g.M = bt; g.N = H; g.out = tb.X[2]; g.ldo = H; g.live = live;
-                ICZ_TRY(gemm_auto(GEMM_NT, g, tb.X[2], tb.xfloats, &ns3, st));
-            }
-            {
-                GemmArgs g = {};
-                g.nseg = 1;
-                g.seg[0] = {tb.dGtd + slot * 4 * H, wt_td_hh, 4 * H, 4 * H, 4 * H, nullptr};
-                g.M = bt; g.N = H; g.out = tb.X[3]; g.ldo = H; g.live = live;
-                ICZ_TRY(gemm_auto(GEMM_NT, g, tb.X[3], tb.xfloats, &ns4, st));
-            }
-        } else if (t > 0) {
-            {   // X3 = dG_lm . W_hh_lm + dG_td . W_ih_td[:, :H]   -> d h2_{t-1}
-                GemmArgs g = {};
-                g.nseg = 2;
-                g.seg[0] = {tb.dGlm + slot * 4 * H, P.lm_w_hh, 4 * H, H, 4 * H, nullptr};
-                g.seg[1] = {tb.dGtd + slot * 4 * H, P.td_w_ih, 4 * H, H + D + E, 4 * H, nullptr};
-                g.M = bt; g.N = H; g.out = tb.X[2]; g.ldo = H; g.live = live;
-                ICZ_TRY(gemm_auto(GEMM_NN, g, tb.X[2], tb.xfloats, &ns3, st));
-            }
-            {   // X4 = dG_td . W_hh_td   -> d h1_{t-1}
-                GemmArgs g = {};
-                g.nseg = 1;
-                g.seg[0] = {tb.dGtd + slot * 4 * H, P.td_w_hh, 4 * H, H, 4 * H, nullptr};
-                g.M = bt; g.N = H; g.out = tb.X[3]; g.ldo = H; g.live = live;
-                ICZ_TRY(gemm_auto(GEMM_NN, g, tb.X[3], tb.xfloats, &ns4, st));
+        if (t > 0) {
+            // X3 = dG_lm . W_hh_lm + dG_td . W_ih_td[:, :H]   -> d h2_{t-1};   X4 = dG_td . W_hh_td   -> d h1_{t-1}
+            const GemmArgs g3 = gemm_args({wseg(dglm, wt_lm_hh, P.lm_w_hh, H), wseg(dgtd, wt_td_ih_h2, P.td_w_ih, H + D + E)}, bt, H, tb.X[2], H, live);
+            const GemmArgs g4 = gemm_args({wseg(dgtd, wt_td_hh, P.td_w_hh, H)}, bt, H, tb.X[3], H, live);
+            if (rdg) {   // both in one launch
+                ns3 = gemm_resident_x3_nsplit(g3); ns4 = gemm_resident_x3_nsplit(g4);
+                ICZ_REQUIRE(gemm_slab_floats(bt, H, ns3) <= tb.xfloats, "butd: slab buffer too small for the dgrad slabs");
+                ICZ_TRY(gemm_resident_x3_pair(g3, g4, st));
+            } else {
+                ICZ_TRY(dgrad(g3, tb.X[2], &ns3));
+                ICZ_TRY(dgrad(g4, tb.X[3], &ns4));
             }
         }
         bnext = bt;
@@ -726,16 +637,9 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     if (phases & 2) {
     // ---- embedding gradient: dEmb = dG_td . W_ih_td[:, H+D:] for all steps, then ordered scatter
     {
-        GemmArgs g = {};
-        g.nseg = 1;
-        g.seg[0] = {tb.dGtd, P.td_w_ih + H + D, 4 * H, H + D + E, 4 * H, nullptr};
-        g.M = TB; g.N = E; g.out = tb.dEmb; g.ldo = E; g.rows_live = rl;
-        int ns;
-        ICZ_TRY(gemm_auto(GEMM_NN, g, ws, ws_floats, &ns, st));
-        if (ns > 1) {
-            size_t MN = (size_t)TB * E;
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, ws, ns, MN, E, (const float*)nullptr, tb.dEmb);
-        }
+        GemmArgs g = gemm_args({{tb.dGtd, P.td_w_ih + H + D, 4 * H, H + D + E, 4 * H}}, TB, E, tb.dEmb, E);
+        g.rows_live = rl;
+        ICZ_TRY(gemm_finished(GEMM_NN, g, split_backward(STEP_WGS), nullptr, ws, ws_floats, st, "butd"));
         // inactive (t,b) rows have dG = 0 -> dEmb = 0; their token ids are whatever the buffer held (valid ids)
         ICZ_CHECK_HIP(embed_grad_launch(st, tb.tok, TB, tb.dEmb, 1, (size_t)0, tb.emb, cur_train ? 2.0f : 1.0f, E, G.embed_weight, V, 1, rl));
     }
@@ -766,13 +670,8 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     const GemmColGroup lm_groups[3] = {{tb.ctx, D, D, G.lm_w_ih, ldlm},                      // ctx_t
                                        {tb.h1 + sH, H, H, G.lm_w_ih + D, ldlm},              // h1_t
                                        {tb.h2, H, H, G.lm_w_hh, H}};                         // h2_{t-1}
-    if (gemm_tn_grouped_fits(4 * H, TB, lm_groups, 3)) {
-        ICZ_TRY(gemm_tn_grouped(tb.dGlm, 4 * H, 4 * H, TB, lm_groups, 3, rl, st));            // 4096 x 4096: 227 us against 123 + 2 x 85
-    } else {
-        ICZ_TRY(wgrad(tb.dGlm, 4 * H, 4 * H, tb.ctx, D, D, TB, G.lm_w_ih, ldlm, st, rl));
-        ICZ_TRY(wgrad(tb.dGlm, 4 * H, 4 * H, tb.h1 + sH, H, H, TB, G.lm_w_ih + D, ldlm, st, rl));
-        ICZ_TRY(wgrad(tb.dGlm, 4 * H, 4 * H, tb.h2, H, H, TB, G.lm_w_hh, H, st, rl));
-    }
+    const int r = wslab_of(st);
+    ICZ_TRY(gemm_tn_groups(tb.dGlm, 4 * H, 4 * H, TB, lm_groups, 3, tb.wslab[r], tb.wslab_floats[r], rl, st));   // grouped at 4096 x 4096: 227 us against 123 + 2 x 85
     }   // phase 2
     if ((phases & 4) && grad_cb && fire_cb) grad_cb(grad_cb_user, 2);
     if (phases & 8) {

@@ -12,7 +12,7 @@
 #include <stdint.h>
 
 #include "butd_kernels.h"
-#include "gemm_f32.h"
+#include "gemm_ops.h"
 
 namespace icz {
 

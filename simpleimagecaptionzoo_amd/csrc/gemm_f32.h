@@ -23,8 +23,12 @@
 //   * NN mirrors NT (the weight tile goes through LDS, interleaved column tiles); TN streams both operands as float4
 //     along their output index (2 loads -> 16 MFMAs), and for large outputs uses a 128 x 128 tile with both operand
 //     tiles in LDS (half the operand bytes per MFMA).
-// Split-K partials go to slabs [z][M][N]; the consumer kernels (LSTM pointwise, attention, argmax ...) sum
-// the slabs in fixed z order, so results are bitwise reproducible run to run (no float atomics).
+// Split-K partials go to slabs [z][M][N], summed in fixed z order, so results are bitwise reproducible run to run (no float atomics).
+//
+// Calling convention: gemm_f32 takes a finished GemmArgs -- the split is already chosen, `out` already points at C or at a slab buffer
+// large enough -- and only launches.  Callers do not do that by hand: gemm_ops.h owns "describe the product, pick a split, write slabs,
+// sum them" (gemm_args, gemm_split, gemm_slabs for a consumer kernel that sums the slabs itself -- LSTM pointwise, attention, argmax ...
+// -- and gemm_finished, which sums them into the output with launch_slab_reduce), and the weight-gradient forms on top of it.
 #pragma once
 #include "icz_common.h"
 
@@ -116,8 +120,9 @@ int gemm_tn_grouped(const float* dY, int ldy, int M, int K, const GemmColGroup* 
 // ICZ_GEMM_BIG (unset / -1: gemm_big_cfg's choice per shape; 0: the 128 x 128 two-barrier kernel everywhere; 1..5: that large-tile configuration everywhere).
 // (round 6) TN products too small to fill the chip on 128 x 128 tiles (fewer than 256 of them: at full width the weight gradients of the two
 // attention projections, 1024 x 1024 over 1280 rows and 1024 x 2048 over 2304; at other widths W_hh of the LSTMs and predict as well) on the large-tile split-precision kernel with split-K slabs
-// [nsplit][M][N] (the caller sums them: slab_reduce_kernel) instead of the fp32-MFMA 64 x 64 kernel.  gemm_tn_split_pick: the split (1 =
-// shape not taken); gemm_tn_split: the launch (K a multiple of 16, splits on 128-deep chunk boundaries, rows_live as in gemm_tn_grouped).
+// [nsplit][M][N] instead of the fp32-MFMA 64 x 64 kernel.  gemm_tn_split_pick: the split (1 = shape not taken); gemm_tn_split: the launch
+// alone (K a multiple of 16, splits on 128-deep chunk boundaries, rows_live as in gemm_tn_grouped) -- call it through gemm_tn_split_sum /
+// gemm_tn_auto (gemm_ops.h), which sum the slabs.
 int gemm_tn_split_pick(int M, int N, int K);
 int gemm_tn_split(const float* dY, int ldy, int M, const float* X, int ldx, int N, int K, int nsplit, float* slabs, const int* rows_live, hipStream_t st);
 struct GemmSwitches { bool tn_x3, nn_x3, nt_x3big, resident_x3, resident_m128, predict_slabs, resident_k512; unsigned prof_every; int big_cfg; };

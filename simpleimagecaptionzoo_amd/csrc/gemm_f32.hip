@@ -6,8 +6,7 @@
 #include <set>
 #include <vector>
 
-#include "gemm_f32.h"
-#include "butd_kernels.h"      // slab_reduce_kernel (icz_gemm_f32)
+#include "gemm_ops.h"
 
 namespace icz {
 
@@ -1380,26 +1379,16 @@ int icz_gemm_f32(int32_t layout, const float* X, int32_t ldx, const float* W, in
                  float* C, int32_t ldc, int32_t M, int32_t N, int32_t K, int32_t nsplit, float* workspace,
                  size_t workspace_floats, void* stream) {
     ICZ_REQUIRE(layout >= 0 && layout <= 2, "icz_gemm_f32: layout %d", layout);
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.seg[0] = {X, W, ldx, ldw, K, nullptr};
-    g.M = M; g.N = N; g.out = C; g.ldo = ldc; g.bias = bias;
-    g.nsplit = nsplit > 0 ? nsplit : gemm_fit_split((GemmLayout)layout, g, gemm_pick_split(g, ABI_TARGET_WGS, (GemmLayout)layout), workspace_floats);
-    g.nsplit = gemm_normalize_split((GemmLayout)layout, g, g.nsplit);   // no empty splits
-    hipStream_t st = (hipStream_t)stream;
-    if (g.nsplit > 1) {
+    const GemmLayout lay = (GemmLayout)layout;
+    GemmArgs g = gemm_args({{X, W, ldx, ldw, K}}, M, N, C, ldc);
+    const int ns = gemm_normalize_split(lay, g, nsplit > 0 ? nsplit : gemm_split(lay, g, split_forward(ABI_TARGET_WGS), workspace_floats));   // no empty splits
+    if (ns > 1) {      // (refused before anything is launched)
         ICZ_REQUIRE(workspace, "icz_gemm_f32: split-K needs a workspace");
-        ICZ_REQUIRE(gemm_slab_floats(M, N, g.nsplit) <= workspace_floats, "icz_gemm_f32: workspace of %zu floats too small for %d slabs of %dx%d", workspace_floats, g.nsplit, M, N);
+        ICZ_REQUIRE(gemm_slab_floats(M, N, ns) <= workspace_floats, "icz_gemm_f32: workspace of %zu floats too small for %d slabs of %dx%d", workspace_floats, ns, M, N);
         ICZ_REQUIRE(ldc == N, "icz_gemm_f32: split-K path needs ldc == N");
-        g.out = workspace; g.bias = nullptr;
-        ICZ_TRY(gemm_f32((GemmLayout)layout, g, st));
-        size_t MN = (size_t)M * N;
-        ICZ_REQUIRE(MN % 4 == 0, "icz_gemm_f32: M*N must be a multiple of 4 for the split-K reduce");
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, workspace, g.nsplit, MN, N, bias, C);
-        ICZ_CHECK_HIP(hipGetLastError());
-        return ICZ_OK;
+        ICZ_REQUIRE(((size_t)M * N) % 4 == 0, "icz_gemm_f32: M*N must be a multiple of 4 for the split-K reduce");
     }
-    return gemm_f32((GemmLayout)layout, g, st);
+    return gemm_finished(lay, g, ns, bias, workspace, workspace_floats, (hipStream_t)stream, "icz_gemm_f32");
 }
 
 // a product over K segments as the decoder handles describe it: table entries -> GemmArgs (shapes and pointers checked before any use)
@@ -1428,32 +1417,30 @@ int icz_gemm_f32_seg(int32_t layout, int32_t nseg, const float* const* A, const 
     ICZ_TRY(seg_args("icz_gemm_f32_seg", nseg, A, lda, B, ldb, K, M, N, &g));
     g.accumulate = accumulate != 0;
     g.live = live;
-    if (g.accumulate) g.nsplit = 1;
-    else g.nsplit = nsplit > 0 ? nsplit : gemm_fit_split(lay, g, gemm_pick_split(g, 256, lay), workspace ? workspace_floats : 0);      // 256: a decoder step's target
+    int ns = 1;
+    if (!g.accumulate) ns = nsplit > 0 ? nsplit : gemm_split(lay, g, split_forward(256), workspace ? workspace_floats : 0);      // 256: a decoder step's target
     const size_t MN = (size_t)M * N;
     hipStream_t st = (hipStream_t)stream;
-    if (g.nsplit > 1 || !C) {
+    if (ns > 1 || !C) {
         // slabs [nsplit][M][N] (one split: the finished product, dense) in the workspace
-        ICZ_REQUIRE(workspace && (size_t)g.nsplit * MN <= workspace_floats, "icz_gemm_f32_seg: workspace of %zu floats too small for %d slabs of %d x %d",
-                    workspace_floats, g.nsplit, M, N);
+        ICZ_REQUIRE(workspace && (size_t)ns * MN <= workspace_floats, "icz_gemm_f32_seg: workspace of %zu floats too small for %d slabs of %d x %d",
+                    workspace_floats, ns, M, N);
         ICZ_REQUIRE(((uintptr_t)workspace & 15) == 0, "icz_gemm_f32_seg: workspace must be 16-byte aligned");
-        if (C && g.nsplit > 1) {
+        if (C) {
             ICZ_REQUIRE(ldc == N && MN % 4 == 0 && ((uintptr_t)C & 15) == 0, "icz_gemm_f32_seg: the slab sum needs ldc == N, M*N %% 4 == 0 and an aligned C (ldc %d, %d x %d)", ldc, M, N);
             ICZ_REQUIRE(!bias || (N % 4 == 0 && ((uintptr_t)bias & 15) == 0), "icz_gemm_f32_seg: the slab sum adds the bias four columns at a time (N %d)", N);
         }
-        g.out = workspace; g.ldo = N;
-        g.bias = (C && g.nsplit > 1) ? nullptr : bias;       // raw slabs with a bias: refused by gemm_f32
-        ICZ_TRY(gemm_f32(lay, g, st));
-        if (C && g.nsplit > 1) {
-            hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, (const float*)workspace, g.nsplit, MN, N, bias, C);
-            ICZ_CHECK_HIP(hipGetLastError());
-        }
     } else {
         ICZ_REQUIRE(ldc >= N, "icz_gemm_f32_seg: output row stride %d below N = %d", ldc, N);
-        g.out = C; g.ldo = ldc; g.bias = bias;
+    }
+    if (C) {
+        g.out = C; g.ldo = ldc;
+        ICZ_TRY(gemm_finished(lay, g, ns, bias, workspace, workspace_floats, st, "icz_gemm_f32_seg"));
+    } else {      // raw slabs for the caller's own consumer; with a bias and more than one: refused by gemm_f32
+        g.out = workspace; g.ldo = N; g.bias = bias; g.nsplit = ns;
         ICZ_TRY(gemm_f32(lay, g, st));
     }
-    if (nsplit_used) *nsplit_used = g.nsplit;
+    if (nsplit_used) *nsplit_used = ns;
     return ICZ_OK;
 }
 
@@ -1525,7 +1512,7 @@ int icz_gemm_split_for(int32_t layout, int32_t M, int32_t N, int32_t nseg, const
         g.seg[s].K = K[s];
     }
     g.M = M; g.N = N;
-    return gemm_fit_split((GemmLayout)layout, g, gemm_pick_split(g, 256, (GemmLayout)layout), workspace_floats);
+    return gemm_split((GemmLayout)layout, g, split_forward(256), workspace_floats);
 }
 
 int icz_gemm_tn_split_pick(int32_t M, int32_t N, int32_t K) {
@@ -1542,11 +1529,7 @@ int icz_gemm_tn_split(const float* dY, int32_t ldy, int32_t M, const float* X, i
     const size_t MN = (size_t)M * N;
     ICZ_REQUIRE(workspace && (size_t)ns * MN <= workspace_floats, "icz_gemm_tn_split: workspace of %zu floats too small for %d slabs of %d x %d", workspace_floats, ns, M, N);
     ICZ_REQUIRE(((uintptr_t)out & 15) == 0, "icz_gemm_tn_split: output must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    ICZ_TRY(gemm_tn_split(dY, ldy, M, X, ldx, N, K, ns, workspace, rows_live, st));
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, (const float*)workspace, ns, MN, N, (const float*)nullptr, out);
-    ICZ_CHECK_HIP(hipGetLastError());
-    return ICZ_OK;
+    return gemm_tn_split_sum(dY, ldy, M, X, ldx, N, K, ns, workspace, rows_live, out, (hipStream_t)stream);
 }
 
 int icz_gemm_tn_grouped(const float* dY, int32_t ldy, int32_t M, int32_t K, int32_t ngroups, const float* const* X, const int32_t* ldx,

@@ -55,10 +55,8 @@ struct Nic : CaptionHead, DecodeMember {
                    float* packed_out, hipStream_t st);
     int xe_backward(float smoothing, const icz_nic_params* G, float* dfeats, float* loss_out, float n_tokens_global, hipStream_t st);
     int bptt(const icz_nic_params& G, float* dfeats, hipStream_t st);
-    int colsum(const float* Xm, int K, int N, int ldx, float* out, hipStream_t st);
     int nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* out, int* ns, int target, hipStream_t st,
            const int* live = nullptr);
-    int tn(const float* dY, int ldy, int M, const float* Xm, int ldx, int N, int K, float* out, int ldo, int accumulate, hipStream_t st);
     // decoder seams (DecodeMember, decoder_core.h): the image step, one token step, the beam-state gather
     int vocab() const override { return dims.V; }
     int row_capacity() const override { return dims.max_rows; }
@@ -110,14 +108,10 @@ int Nic::refresh(hipStream_t st) {
 // h, c = LSTMCell(features, (0, 0))   (NIC_Model.py:52-56)
 int Nic::image_step(const float* feats, int rows, float* h_out, float* c_out, float* gates_out, hipStream_t st) {
     const int H = dims.H, E = dims.E;
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.seg[0] = {feats, P.w_ih, E, E, E, nullptr};
-    g.M = rows; g.N = 4 * H; g.out = ws; g.ldo = 4 * H;
-    g.nsplit = gemm_fit_split(GEMM_NT, g, gemm_pick_split(g, STEP_WGS), ws_floats);
-    ICZ_REQUIRE(gemm_slab_floats(g.M, g.N, g.nsplit) <= ws_floats, "nic: workspace too small");
-    ICZ_TRY(gemm_f32(GEMM_NT, g, st));
-    LstmPointArgs a = {ws, g.nsplit, nullptr, nullptr, P.b_ih, P.b_hh, zeros, h_out, c_out, gates_out, nullptr, rows, H};
+    int ns;      // (the split is fitted to the workspace: the capacity check cannot fail)
+    GemmArgs g = gemm_args({{feats, P.w_ih, E, E, E}}, rows, 4 * H, ws, 4 * H);
+    ICZ_TRY(gemm_slabs(GEMM_NT, g, split_forward(STEP_WGS), ws, ws_floats, &ns, st, "nic"));
+    LstmPointArgs a = {ws, ns, nullptr, nullptr, P.b_ih, P.b_hh, zeros, h_out, c_out, gates_out, nullptr, rows, H};
     DropCfg off = {0, nullptr, nullptr, 0, 0};
     launch_lstm_point(a, off, st);
     return ICZ_OK;
@@ -131,16 +125,10 @@ int Nic::token_step(int rows, const int64_t* tokens, bool emb_ready, const float
     const int H = dims.H, E = dims.E, V = dims.V;
     DropCfg off = {0, nullptr, nullptr, 0, 0};
     if (!emb_ready) hipLaunchKernelGGL(embed_kernel, dim3(cdiv(E, 1024), rows), dim3(256), 0, st, P.embed_weight, tokens, emb_out, rows, E, off, 0, live);
-    GemmArgs g = {};
-    g.nseg = 2;
-    g.live = live;
-    g.seg[0] = {emb_out, P.w_ih, E, E, E, nullptr};
-    g.seg[1] = {h_in, P.w_hh, H, H, H, nullptr};
-    g.M = rows; g.N = 4 * H; g.out = ws; g.ldo = 4 * H;
-    g.nsplit = gemm_fit_split(GEMM_NT, g, gemm_pick_split(g, STEP_WGS), ws_floats);
-    ICZ_REQUIRE(gemm_slab_floats(g.M, g.N, g.nsplit) <= ws_floats, "nic: workspace too small");
-    ICZ_TRY(gemm_f32(GEMM_NT, g, st));
-    LstmPointArgs a = {ws, g.nsplit, nullptr, nullptr, P.b_ih, P.b_hh, c_in, h_out, c_out, gates_out, hdrop_out, rows, H, live};
+    int ns;      // (fitted split, as in image_step)
+    GemmArgs g = gemm_args({{emb_out, P.w_ih, E, E, E}, {h_in, P.w_hh, H, H, H}}, rows, 4 * H, ws, 4 * H, live);
+    ICZ_TRY(gemm_slabs(GEMM_NT, g, split_forward(STEP_WGS), ws, ws_floats, &ns, st, "nic"));
+    LstmPointArgs a = {ws, ns, nullptr, nullptr, P.b_ih, P.b_hh, c_in, h_out, c_out, gates_out, hdrop_out, rows, H, live};
     launch_lstm_point(a, drop_out, st);
     ICZ_TRY(gemm_predict(hdrop_out, H, w_pred, P.predict_b, rows, V, Vp, logits_out, Vp, ws, ws_floats, pred_nsplit, st, live));
     ICZ_CHECK_HIP(hipGetLastError());
@@ -324,40 +312,13 @@ int Nic::xe_backward(float smoothing, const icz_nic_params* G, float* dfeats, fl
     return bptt(*G, dfeats, st);
 }
 
-int Nic::colsum(const float* Xm, int K, int N, int ldx, float* out, hipStream_t st) {
-    hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(N, 32)), dim3(256), 0, st, Xm, K, N, ldx, out);
-    return ICZ_OK;
-}
-
-// out (dense [M,N]) = A[M,K] . B[K,N]; split-K slabs go to `ws`/`X` and are reduced into `out` unless ns is requested
+// A[M,K] . B[K,N]: with ns_out, slabs [ns][M][N] in `out` (= X, one slab: the dense product) for the consumer to sum; without, the
+// finished dense product in `out`, split-K slabs going through `ws`
 int Nic::nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* out, int* ns_out, int target, hipStream_t st,
             const int* live) {
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.live = live;
-    g.seg[0] = {A, Bm, lda, ldb, K, nullptr};
-    g.M = M; g.N = N; g.out = out; g.ldo = N;
-    g.nsplit = M <= 64 ? gemm_pick_split(g, target, GEMM_NN) : gemm_pick_split_balanced(g, GEMM_NN, ns_out ? xfloats : ws_floats);
-    float* slab = ns_out ? out : ws;
-    if (g.nsplit > 1) {
-        ICZ_REQUIRE(gemm_slab_floats(M, N, g.nsplit) <= (ns_out ? xfloats : ws_floats), "nic: slab buffer too small");
-        g.out = slab;
-    }
-    ICZ_TRY(gemm_f32(GEMM_NN, g, st));
-    if (ns_out) { *ns_out = g.nsplit; return ICZ_OK; }
-    if (g.nsplit > 1) {
-        const size_t MN = (size_t)M * N;
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv((int)(MN / 4), 256)), dim3(256), 0, st, ws, g.nsplit, MN, N, (const float*)nullptr, out);
-    }
-    return ICZ_OK;
-}
-
-int Nic::tn(const float* dY, int ldy, int M, const float* Xm, int ldx, int N, int K, float* out, int ldo, int accumulate, hipStream_t st) {
-    GemmArgs g = {};
-    g.nseg = 1;
-    g.seg[0] = {dY, Xm, ldy, ldx, K, nullptr};
-    g.M = M; g.N = N; g.out = out; g.ldo = ldo; g.nsplit = 1; g.accumulate = accumulate;
-    return gemm_f32(GEMM_TN, g, st);
+    GemmArgs g = gemm_args({{A, Bm, lda, ldb, K}}, M, N, out, N, live);
+    if (ns_out) return gemm_slabs(GEMM_NN, g, split_backward(target), out, xfloats, ns_out, st, "nic");
+    return gemm_finished(GEMM_NN, g, split_backward(target), nullptr, ws, ws_floats, st, "nic");
 }
 
 int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st) {
@@ -366,8 +327,8 @@ int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st) {
     const size_t sH = (size_t)B * H;
     // predict layer over all time steps
     ICZ_TRY(nn(tlogit, Vp, TB, Vp, w_pred, H, H, dHd, nullptr, TARGET_WGS, st));
-    ICZ_TRY(tn(tlogit, Vp, Vp, thd, H, H, TB, dWp, H, 0, st));
-    ICZ_TRY(colsum(tlogit, TB, V, Vp, G.predict_b, st));
+    ICZ_TRY(gemm_tn(tlogit, Vp, Vp, thd, H, H, TB, dWp, H, 0, nullptr, st));
+    ICZ_TRY(launch_colsum(tlogit, TB, V, Vp, G.predict_b, st));
     hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, st, dWp, H, P.predict_v, P.predict_g, n_pred, G.predict_v,
                        G.predict_g, V, H);
     const bool ragged = rows_t[T - 1] < B;
@@ -400,10 +361,10 @@ int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st) {
     ICZ_CHECK_HIP(embed_grad_launch(st, tok, TB, dEmb, 1, (size_t)0, temb, 1.0f, E, G.embed_weight, V, 0));
     if (dfeats) ICZ_TRY(nn(dG, 4 * H, B, 4 * H, P.w_ih, E, E, dfeats, nullptr, TARGET_WGS, st));
     // weight gradients
-    ICZ_TRY(tn(dG + (size_t)B * 4 * H, 4 * H, 4 * H, temb, E, E, TB, G.w_ih, E, 0, st));
-    ICZ_TRY(tn(dG, 4 * H, 4 * H, cur_feats, E, E, B, G.w_ih, E, 1, st));
-    ICZ_TRY(tn(dG, 4 * H, 4 * H, th, H, H, TB + B, G.w_hh, H, 0, st));
-    ICZ_TRY(colsum(dG, TB + B, 4 * H, 4 * H, G.b_ih, st));
+    ICZ_TRY(gemm_tn(dG + (size_t)B * 4 * H, 4 * H, 4 * H, temb, E, E, TB, G.w_ih, E, 0, nullptr, st));
+    ICZ_TRY(gemm_tn(dG, 4 * H, 4 * H, cur_feats, E, E, B, G.w_ih, E, 1, nullptr, st));
+    ICZ_TRY(gemm_tn(dG, 4 * H, 4 * H, th, H, H, TB + B, G.w_hh, H, 0, nullptr, st));
+    ICZ_TRY(launch_colsum(dG, TB + B, 4 * H, 4 * H, G.b_ih, st));
     ICZ_CHECK_HIP(hipMemcpyAsync(G.b_hh, G.b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, st));
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
