@@ -761,6 +761,13 @@ int icz_gemm_route_for(int32_t layout, int32_t M, int32_t N, int32_t nseg, const
 int icz_gemm_split_for(int32_t layout, int32_t M, int32_t N, int32_t nseg, const int32_t* K, size_t workspace_floats);
 /* Whether icz_gemm_tn_grouped takes column groups of these widths over K rows (host logic only, no GPU needed): 1 / 0, -1 = bad arguments. */
 int icz_gemm_tn_grouped_fits(int32_t M, int32_t K, int32_t ngroups, const int32_t* cols);
+/* Test entry for the fork / join rule of the decoders' side streams (SideStream::Branch, decoder_core.h): as one captured graph of its
+ * own cache (a call that fails nowhere is replayed by the next such call with the same inline_branch and out2), a branch is forked off `stream`, one tiny kernel writes
+ * out2[0] = 1 on `stream` and one writes out2[1] = 2 on the branch's stream (inline_branch != 0: the branch runs in line on `stream`),
+ * and the branch is joined.  fail_at = 0..3: the call returns ICZ_ERR_INVALID with "side-branch test: stage <fail_at>" behind the fork
+ * point (0), behind the branch's start (1), behind its launch (2), behind its finish (3) -- the branch is still joined, so the error
+ * is reported as itself and `stream` is left usable; fail_at = -1 fails nowhere.  out2: two device floats. */
+int icz_test_side_branch(int32_t fail_at, int32_t inline_branch, float* out2, void* stream);
 /* Live timing of the dominant kernel (the forward GEMMs of a decoder step at 33..64 rows: gemm_resident_x3_kernel, or
  * gemm_nt_kernel<4, ...> with ICZ_GEMM_RESIDENT_X3=0; see icz_prof_select) with HIP events on its launch stream, for bench.py's
  * roofline line.  Between begin and end every launch is bracketed by an event

@@ -248,6 +248,7 @@ def lib():
         "icz_gemm_route_for": (C.c_int, [i32, i32, i32, i32, vp, i32]),
         "icz_gemm_split_for": (C.c_int, [i32, i32, i32, i32, vp, C.c_size_t]),
         "icz_gemm_tn_grouped_fits": (C.c_int, [i32, i32, i32, vp]),
+        "icz_test_side_branch": (C.c_int, [i32, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         try:

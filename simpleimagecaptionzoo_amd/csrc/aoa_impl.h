@@ -196,7 +196,13 @@ struct Aoa : CaptionHead, DecodeMember {
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_aoa_rng* r, int train,
                    float* packed_out, hipStream_t st);
     int xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
-    int bptt(const icz_aoa_params& G, hipStream_t st);
+    int bptt(const icz_aoa_params& G, hipStream_t st);      // the driver over the parts below, then refiner_backward
+    struct BpttCall;
+    int bptt_predict(BpttCall& c);              // d(dropped ctx) and the predict layer's gradients (side branch)
+    int bptt_loop(BpttCall& c);                 // the reverse-time loop
+    int bptt_embed_lstm_wgrad(BpttCall& c);     // embedding gradient, LSTM weight / bias gradients
+    int bptt_aoa_wgrad(BpttCall& c);            // the AoA linear layer's gradients
+    int bptt_attention_tail(BpttCall& c);       // the attention block's small products (tail branch)
     // g.out (dense [M,N]) = sum_s A_s W_s^T + bias; split-K slabs through `ws` when one pass would leave most CUs idle
     int linear(GemmArgs g, const float* bias, hipStream_t st);
     // slabs [ns][M][N] = A[M,K] . B[K,N] (ns == 1: the dense product) in `slab` of `cap` floats, for the consumer to sum

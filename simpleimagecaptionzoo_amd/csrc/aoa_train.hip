@@ -425,13 +425,12 @@ int Aoa::rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int64
     }
     const bool pair = proj && pair_refine && dual.xa;
     if (pair) ICZ_TRY(refine_pair(B, st, proj));          // both refiner passes in one, in front of the fork
-    ICZ_CHECK_HIP(hipEventRecord(side.fork[0], st));
-    ICZ_CHECK_HIP(hipStreamWaitEvent(side.st, side.fork[0], 0));
-    const int sg = greedy(feats, B, T, ids_out, side.st, proj, true, pair);
-    const int ss = sg == ICZ_OK ? sample_impl(feats, B, T, seq_out, logp_out, st, proj, pair) : sg;
-    ICZ_CHECK_HIP(hipEventRecord(side.join[0], side.st));       // always join, also on error (a capture must be closed)
-    ICZ_CHECK_HIP(hipStreamWaitEvent(st, side.join[0], 0));
-    return ss;
+    SideStream::Branch baseline(&side, 0);
+    ICZ_TRY(baseline.fork(st));
+    ICZ_TRY(baseline.start());
+    ICZ_TRY(greedy(feats, B, T, ids_out, baseline.st(), proj, true, pair));
+    ICZ_TRY(sample_impl(feats, B, T, seq_out, logp_out, st, proj, pair));
+    return baseline.join();
 }
 
 int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* loss_out, float* msum_out, float msum_global, hipStream_t st) {
@@ -441,7 +440,9 @@ int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* lo
     set_msum_global(msum_global, st);      // < 0: keep the device value handed over by icz_aoa_set_norm_global
     mode = 0;
     bptt_early_out = true;
-    ICZ_TRY(low.ensure());          // the side stream of bptt: created here, outside any capture
+    // the side stream of bptt, created here, outside any capture.  A plain stream: eager launches on a PRIORITISED stream beside other
+    // streams' work can serialise on this runtime (EXPERIMENTS.md, round 4, section 8), and the AoA paths are eager
+    ICZ_TRY(low.ensure());
     // with a DP callback the hook must fire on every call: eager launches (a replayed graph would not call it)
     if (!use_graphs || lens || grad_cb || aoa_explicit_rng(rng)) return sample_backward_impl(reward, *G, loss_out, msum_out, st);
     std::vector<uintptr_t> key = {2, (uintptr_t)reward, (uintptr_t)loss_out, (uintptr_t)msum_out, (uintptr_t)cur_B, (uintptr_t)cur_T, (uintptr_t)cur_R,
@@ -508,6 +509,7 @@ int Aoa::xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, 
     if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
     ICZ_TRY(xe_loss(smoothing, n_tokens_global, tlogit, dims.V, Vp, loss_out, st));
     bptt_early_out = false;
+    ICZ_TRY(low.ensure());          // as in sample_backward
     return bptt(*G, st);
 }
 
@@ -518,45 +520,75 @@ int Aoa::nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int
     return gemm_slabs(GEMM_NN, g, p, slab, cap, ns_out, st, "aoa");
 }
 
-int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
-    use_bank(1);
-    const int B = cur_B, T = cur_T, Hd = dims.Hd, E = dims.E, V = dims.V, NH = dims.NH, R = cur_R, dh = Hd / NH;
-    const int TB = T * B;
-    const size_t sH = (size_t)B * Hd;
+// What the parts of one bptt() call share.  The two branches live as long as the call: whatever a part returns, a branch it has
+// started is joined before bptt() returns (SideStream::Branch).
+struct Aoa::BpttCall {
+    const icz_aoa_params& G;
+    hipStream_t st;
+    int B, T, TB;
     // behind sample_n: K rows per image (row = img * K + k) -- the attention backward finds the image's K / V tiles through imgk, and
     // d K / d V are summed per image over its rows and the steps; everything over (t, row) simply sees B = n_img K rows
-    const int K = cur_K, n_img = B / K;
-    const int32_t* const rows_img = K > 1 ? imgk : nullptr;
-    int ns = 1;
+    int K, n_img;
     // backward of a sampled rollout: the steps behind the reference's break (AoA_Model.py:400) never ran -- their kernels return at
     // entry (the buffers the batched GEMMs read are zeroed in front of the loop) and the GEMMs over all (t, b) stop behind the last live step
-    const bool eo = bptt_early_out && early_out;
-    const int* const rl = eo ? live_rows : nullptr;
-    // ---- predict layer over all time steps: d(dropped ctx), weight-norm gradients
-    ICZ_TRY(nn(tlogit, Vp, TB, Vp, w_pred, Hd, Hd, X, xfloats, &ns, split_backward(TARGET_WGS), st, nullptr, rl));
-    ICZ_TRY(launch_slab_reduce(X, ns, TB, Hd, nullptr, dCd, st));      // (one slab: a copy)
-    // The predict layer's weight / bias gradients need dlogits only.  Without a DP callback they go to a side stream,
-    // ISSUED behind the d(ctx) product above (the head of the critical chain, as in Butd::bptt) and joined behind the loop; with a
-    // callback they stay in line, because stage 0 reports them complete in stream order right here.
+    bool eo;
+    const int* rl;
+    SideStream::Branch predict;      // the predict layer's weight / bias gradients beside the reverse-time loop
+    SideStream::Branch tail;         // the attention block's small products beside the batched weight gradients
+};
+
+int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
+    use_bank(1);
+    // Without a DP callback the two branches go to the side stream (a plain one, see sample_backward); with a callback they stay in line,
+    // because the stages report their gradients complete in stream order.
     const bool side = !grad_cb;
-    hipStream_t ps = st;
-    if (side) {
-        // a plain stream: eager launches on a PRIORITISED stream beside other streams' work can serialise on this runtime
-        // (EXPERIMENTS.md, round 4, section 8), and the AoA paths are eager
-        ICZ_TRY(low.ensure());
-        ICZ_CHECK_HIP(hipEventRecord(low.fork[0], st));
-        ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, low.fork[0], 0));
-        ps = low.st;
-    }
-    const int s_tn = gemm_tn(tlogit, Vp, Vp, tcd, Hd, Hd, TB, dWp, Hd, 0, rl, ps);
-    if (s_tn == ICZ_OK) {
-        (void)launch_colsum(tlogit, TB, V, Vp, G.predict_b, ps);
-        hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, ps, dWp, Hd, P.predict_v, P.predict_g, n_pred, G.predict_v,
-                           G.predict_g, V, Hd);
-    }
-    if (side) ICZ_CHECK_HIP(hipEventRecord(low.join[0], low.st));
-    if (s_tn != ICZ_OK) { if (side) (void)hipStreamWaitEvent(st, low.join[0], 0); return s_tn; }
+    static const bool tail_side_on = [] { const char* e = getenv("ICZ_AOA_TAIL_SIDE"); return e ? atoi(e) != 0 : true; }();      // A/B switch (read once)
+    const bool eo = bptt_early_out && early_out;
+    BpttCall c = {G, st, cur_B, cur_T, cur_T * cur_B, cur_K, cur_B / cur_K, eo, eo ? live_rows : nullptr,
+                  {side ? &low : nullptr, 0}, {side && tail_side_on ? &low : nullptr, 1}};
+    ICZ_TRY(bptt_predict(c));
     if (grad_cb) grad_cb(grad_cb_user, 0);      // predict.* complete in stream order: reduced beside the reverse-time loop
+    ICZ_TRY(bptt_loop(c));
+    ICZ_TRY(c.predict.join());                  // the predict branch has long finished beside the loop
+    // the attention block's tail depends on the loop only: forked at the loop's end, ISSUED last, joined behind it (as Butd::bptt's tail)
+    ICZ_TRY(c.tail.fork(st));
+    ICZ_TRY(bptt_embed_lstm_wgrad(c));
+    if (grad_cb) grad_cb(grad_cb_user, 1);      // embed + lstm.*: reduced beside the attention block's weight gradients
+    ICZ_TRY(bptt_aoa_wgrad(c));
+    ICZ_TRY(c.tail.start());
+    ICZ_TRY(bptt_attention_tail(c));
+    ICZ_TRY(c.tail.join());
+    ICZ_CHECK_HIP(hipGetLastError());
+    // option "train_refiner": d refined -> the refiner and the feature projection, on the caller's stream behind every join above
+    // (dKd / dVd from the tail, d gates from the loop)
+    if (train_refiner) return refiner_backward(G, st);
+    return ICZ_OK;
+}
+
+// ---- predict layer over all time steps: d(dropped ctx), weight-norm gradients
+int Aoa::bptt_predict(BpttCall& c) {
+    const int TB = c.TB, Hd = dims.Hd, V = dims.V;
+    int ns = 1;
+    ICZ_TRY(nn(tlogit, Vp, TB, Vp, w_pred, Hd, Hd, X, xfloats, &ns, split_backward(TARGET_WGS), c.st, nullptr, c.rl));
+    ICZ_TRY(launch_slab_reduce(X, ns, TB, Hd, nullptr, dCd, c.st));      // (one slab: a copy)
+    // The predict layer's weight / bias gradients need dlogits only: their branch is forked and ISSUED behind the d(ctx) product above
+    // (the head of the critical chain, as in Butd::bptt) and joined behind the loop.
+    ICZ_TRY(c.predict.fork(c.st));
+    ICZ_TRY(c.predict.start());
+    hipStream_t const ps = c.predict.st();
+    ICZ_TRY(gemm_tn(tlogit, Vp, Vp, tcd, Hd, Hd, TB, dWp, Hd, 0, c.rl, ps));
+    (void)launch_colsum(tlogit, TB, V, Vp, c.G.predict_b, ps);
+    hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, ps, dWp, Hd, P.predict_v, P.predict_g, n_pred, c.G.predict_v,
+                       c.G.predict_g, V, Hd);
+    return c.predict.finish();
+}
+
+// ---- the reverse-time loop
+int Aoa::bptt_loop(BpttCall& c) {
+    const int B = c.B, T = c.T, TB = c.TB, Hd = dims.Hd, NH = dims.NH, R = cur_R, dh = Hd / NH;
+    const bool eo = c.eo;
+    const int32_t* const rows_img = c.K > 1 ? imgk : nullptr;
+    hipStream_t const st = c.st;
     if (rows_t[T - 1] < B || eo) {      // ragged batch / steps that never ran: those rows contribute exact zeros to the batched GEMMs
         ICZ_CHECK_HIP(hipMemsetAsync(dZ, 0, sizeof(float) * (size_t)TB * 2 * Hd, st));
         ICZ_CHECK_HIP(hipMemsetAsync(dQp, 0, sizeof(float) * (size_t)TB * Hd, st));
@@ -567,8 +599,6 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     }
     const size_t lds = sizeof(float) * (2 * R * (dh + 1) + 2 * dh + 128 + 4);
     DropCfg off = {0, nullptr, nullptr, 0, 0};
-    // the reverse-time loop in a lambda: whatever it returns, the side stream is joined behind it (a capture must be closed)
-    auto loop = [&]() -> int {
     int cur = 0, nsx = 1, bnext = 0;
     for (int t = T - 1; t >= 0; --t) {
         const int bt = rows_t[t];
@@ -602,14 +632,15 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
         cur ^= 1;
     }
     return ICZ_OK;
-    };
-    const int s_loop = loop();
-    if (side) ICZ_CHECK_HIP(hipStreamWaitEvent(st, low.join[0], 0));      // the predict branch has long finished beside the loop
-    if (s_loop != ICZ_OK) return s_loop;
-    static const bool tail_side_on = [] { const char* e = getenv("ICZ_AOA_TAIL_SIDE"); return e ? atoi(e) != 0 : true; }();      // A/B switch (read once)
-    const bool tail_side = side && tail_side_on;
-    if (tail_side) ICZ_CHECK_HIP(hipEventRecord(low.fork[1], st));
-    // ---- embedding gradient
+}
+
+// ---- embedding gradient and the LSTM's weight gradients
+int Aoa::bptt_embed_lstm_wgrad(BpttCall& c) {
+    const int TB = c.TB, Hd = dims.Hd, E = dims.E, V = dims.V;
+    const icz_aoa_params& G = c.G;
+    const int* const rl = c.rl;
+    hipStream_t const st = c.st;
+    int ns = 1;
     ICZ_TRY(nn(dG, 4 * Hd, TB, 4 * Hd, P.lstm_w_ih, E + Hd, E, X, xfloats, &ns, split_backward(TARGET_WGS), st, nullptr, rl));
     ICZ_TRY(launch_slab_reduce(X, ns, TB, E, nullptr, dEmb, st));      // (one slab: a copy)
     ICZ_CHECK_HIP(embed_grad_launch(st, tok, TB, dEmb, 1, (size_t)0, temb, cur_train ? 2.0f : 1.0f, E, G.embed_weight, V, 1, rl));
@@ -619,15 +650,26 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
     ICZ_TRY(gemm_tn_groups(dG, 4 * Hd, 4 * Hd, TB, lstm_groups, 3, nullptr, 0, rl, st));
     ICZ_TRY(launch_colsum(dG, TB, 4 * Hd, 4 * Hd, G.lstm_b_ih, st));
     ICZ_CHECK_HIP(hipMemcpyAsync(G.lstm_b_hh, G.lstm_b_ih, sizeof(float) * 4 * Hd, hipMemcpyDeviceToDevice, st));
-    if (grad_cb) grad_cb(grad_cb_user, 1);      // embed + lstm.*: reduced beside the attention block's weight gradients
-    const GemmColGroup aoa_groups[2] = {{txatt, Hd, Hd, G.dec.aoa_w, 2 * Hd}, {tqn, Hd, Hd, G.dec.aoa_w + Hd, 2 * Hd}};
-    ICZ_TRY(gemm_tn_groups(dZ, 2 * Hd, 2 * Hd, TB, aoa_groups, 2, nullptr, 0, rl, st));
-    ICZ_TRY(launch_colsum(dZ, TB, 2 * Hd, 2 * Hd, G.dec.aoa_b, st));
-    // ---- the attention block's small products (three Hd x Hd weight gradients, d K / d V, seven column sums: 240 us of kernels that fill a
-    //      fraction of the chip, eager timeline round 6) depend on the loop only: without a DP callback they run on the side stream beside
-    //      the embedding / LSTM / AoA-linear gradients above -- forked at the loop's end, ISSUED last, joined here (as Butd::bptt's tail)
-    hipStream_t ts = tail_side ? low.st : st;
-    auto tail = [&]() -> int {
+    return ICZ_OK;
+}
+
+// ---- the AoA linear layer's gradients
+int Aoa::bptt_aoa_wgrad(BpttCall& c) {
+    const int Hd = dims.Hd;
+    const GemmColGroup aoa_groups[2] = {{txatt, Hd, Hd, c.G.dec.aoa_w, 2 * Hd}, {tqn, Hd, Hd, c.G.dec.aoa_w + Hd, 2 * Hd}};
+    ICZ_TRY(gemm_tn_groups(dZ, 2 * Hd, 2 * Hd, c.TB, aoa_groups, 2, nullptr, 0, c.rl, c.st));
+    return launch_colsum(dZ, c.TB, 2 * Hd, 2 * Hd, c.G.dec.aoa_b, c.st);
+}
+
+// ---- the attention block's small products (three Hd x Hd weight gradients, d K / d V, seven column sums: 240 us of kernels that fill a
+//      fraction of the chip, eager timeline round 6) depend on the loop only: without a DP callback they run on the side stream beside
+//      the embedding / LSTM / AoA-linear gradients
+int Aoa::bptt_attention_tail(BpttCall& c) {
+    const int B = c.B, T = c.T, TB = c.TB, K = c.K, n_img = c.n_img, Hd = dims.Hd, NH = dims.NH, R = cur_R, dh = Hd / NH;
+    const size_t sH = (size_t)B * Hd;
+    const icz_aoa_params& G = c.G;
+    const int* const rl = c.rl;
+    hipStream_t const ts = c.tail.st();
     ICZ_TRY(gemm_tn(dQp, Hd, Hd, tqn, Hd, Hd, TB, G.dec.q_w, Hd, 0, rl, ts));
     ICZ_TRY(launch_colsum(dQp, TB, Hd, Hd, G.dec.q_b, ts));
     {
@@ -647,19 +689,6 @@ int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
         ICZ_TRY(launch_colsum(prod, TB, Hd, Hd, G.dec.ln_g, ts));
         ICZ_TRY(launch_colsum(dQn, TB, Hd, Hd, G.dec.ln_b, ts));
     }
-    return ICZ_OK;
-    };
-    if (tail_side) ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, low.fork[1], 0));
-    const int s_tail = tail();
-    if (tail_side) {       // joined also on an error (inside a capture an unjoined side stream would hide it behind a capture failure)
-        ICZ_CHECK_HIP(hipEventRecord(low.join[1], low.st));
-        ICZ_CHECK_HIP(hipStreamWaitEvent(st, low.join[1], 0));
-    }
-    if (s_tail != ICZ_OK) return s_tail;
-    ICZ_CHECK_HIP(hipGetLastError());
-    // option "train_refiner": d refined -> the refiner and the feature projection, on the caller's stream behind every join above
-    // (dKd / dVd from the tail, d gates from the loop)
-    if (train_refiner) return refiner_backward(G, st);
     return ICZ_OK;
 }
 

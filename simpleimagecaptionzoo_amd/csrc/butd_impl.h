@@ -114,7 +114,6 @@ struct Butd : CaptionHead, DecodeMember {
     icz_grad_ready_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // DP overlap hook (icz_butd_set_grad_callback)
     int sample_backward_impl(const float* reward, const icz_butd_params& G, float* loss_out, float* mask_sum_out, hipStream_t st,
                              int phases = 0xF, bool fire_cb = true);
-    bool bptt_joined = false;            // the predict-gradient branch has been joined (bptt phases)
     int merge_small = 8;                 // option "merge_small" = n: SCST rollouts of <= n images (n <= 32) run as ONE chain of 2 B decoder rows
                                          // (sample_chain with row0 = B); 0 = never.  Default 8: measured round 5 (EXPERIMENTS.md), the
                                          // merged chain saves 0.2 ms of rollouts at every size but costs the backward pass 0.06 / 0.15 /
@@ -169,7 +168,16 @@ struct Butd : CaptionHead, DecodeMember {
     int wslab_of(hipStream_t st) const { return st == low.st ? 1 : 0; }
     int wgrad(const float* dY, int ldy, int M, const float* X, int ldx, int N, int K, float* out, int ldo, hipStream_t st, const int* rows_live = nullptr);
     int bptt_prelude(hipStream_t st);
+    // phases: one bit per phase function below.  A call joins every branch it forked before it returns.  Values other than 0xF arise
+    // only in the callback path of sample_backward (one captured graph per phase), where the only branch, phase 0's predict branch,
+    // is joined behind the loop of that same call.
     int bptt(const icz_butd_params& G, hipStream_t st, int phases = 0xF, bool fire_cb = true);
+    struct BpttCall;
+    int bptt_predict(BpttCall& c);              // bit 0: d h2drop, the predict layer's gradients (side branch) ...
+    int bptt_loop(BpttCall& c);                 //        ... and the reverse-time loop
+    int bptt_embed_td_wgrad(BpttCall& c);       // bit 1: embedding gradient, TD-LSTM weight gradients
+    int bptt_lm_wgrad(BpttCall& c);             // bit 2: LM-LSTM weight gradients
+    int bptt_attention_tail(BpttCall& c);       // bit 3: attention block, bias sums, weight-norm backward
 };
 
 }  // namespace icz

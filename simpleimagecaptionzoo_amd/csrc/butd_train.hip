@@ -237,15 +237,15 @@ int Butd::rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int6
         ICZ_TRY(greedy_chain(feats, B, T, ids_out, nullptr, st, true));
         return sample_chain(feats, B, T, seq_out, logp_out, st);
     }
-    ICZ_CHECK_HIP(hipEventRecord(side.fork[0], st));
-    ICZ_CHECK_HIP(hipStreamWaitEvent(side.st, side.fork[0], 0));
+    SideStream::Branch baseline(&side, 0);
+    ICZ_TRY(baseline.fork(st));
+    ICZ_TRY(baseline.start());
     // the sampled chain (the longer one: multinomial draw, dropout) is issued -- and captured -- first: when kernels of both chains are
     // ready the runtime then takes its first.  Measured round 4, three same-box rounds: rollouts 2.758 / 2.774 / 2.769 ms against
     // 2.783 / 2.785 / 2.806 ms with the greedy chain first (profiles/r04_chain_issue_order.log)
     const int ss = sample_chain(feats, B, T, seq_out, logp_out, st);
-    const int sg = greedy_chain(feats, B, T, ids_out, nullptr, side.st, true);
-    ICZ_CHECK_HIP(hipEventRecord(side.join[0], side.st));       // always join, also on error (a capture must be closed)
-    ICZ_CHECK_HIP(hipStreamWaitEvent(st, side.join[0], 0));
+    const int sg = greedy_chain(feats, B, T, ids_out, nullptr, baseline.st(), true);
+    ICZ_TRY(baseline.join());
     return sg != ICZ_OK ? sg : ss;
 }
 
@@ -459,74 +459,115 @@ int Butd::wgrad(const float* dY, int ldy, int M, const float* X, int ldx, int N,
 // step: every entry point calls this in front of bptt(), OUTSIDE its captured graph (a replayed graph must not rebuild them).
 int Butd::bptt_prelude(hipStream_t st) {
     if (wt_lm_ih && !wt_fresh) ICZ_TRY(refresh_transposes(st));
+    // the side stream of bptt, created here, outside any capture.  Lowest priority: its big GEMMs only fill CUs the BPTT chain leaves idle
+    ICZ_TRY(low.ensure(true));
     return ICZ_OK;
 }
 
-// phases: bit 0 = predict layer + reverse-time loop, bit 1 = embedding and TD-LSTM weight gradients, bit 2 = LM-LSTM weight
-// gradients, bit 3 = attention block, biases, joins.  After each of the first three the corresponding gradient group is complete
-// in stream order (icz_butd_set_grad_callback); fire_cb = false leaves the callbacks to the caller, which replays every phase
-// as its own captured graph and calls them in between.
-//
-// Every ICZ_TRY inside the loop / behind it sits in a lambda: whatever fails, the side stream is joined before the status is
-// returned (inside a capture an unjoined fork would hide the original error behind a capture failure).
-int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_cb) {
+// What the phases of one bptt() call share.  The two branches live as long as the call: whatever a phase returns, a branch it has
+// started is joined before bptt() returns (SideStream::Branch).
+struct Butd::BpttCall {
+    const icz_butd_params& G;
+    hipStream_t st;
     // B rows are worked on per step; the buffers hold Bs rows per step, of which those are rows [roff, roff + B) (Bs = B, roff = 0
     // except behind a merged chain, whose evaluation-mode rows in front carry zero gradient rows through the GEMMs over all steps)
-    const int B = cur_B, T = cur_T, Bs = cur_rows, roff = cur_row0;
-    const int H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = dims.R, V = dims.V;
-    const int Vp = pad_vocab(V);
-    const int TB = T * Bs;
-    const float* feats = cur_feats;
-    const size_t sH = (size_t)Bs * H;
+    int B, T, Bs, roff, TB;
     // backward of a sampled rollout: the GEMMs over all (t, b) rows stop behind the last step the rollout ran (GemmArgs::rows_live)
-    const int* const rl = (bptt_early_out && early_out) ? live_rows : nullptr;
+    const int* rl;
     // behind sample_n: K rows per image (row = img * K + k) -- the kernels that read the image's features / enc_ctx per row find it
     // through tb.imgk, and the image-side products (d enc_ctx, the mean-feature weights) are folded onto the n_img images first
-    const int K = cur_K, n_img = K > 1 ? cur_nimg : B;
-    const int32_t* const imgk = K > 1 ? tb.imgk : nullptr;
+    int K, n_img;
+    const int32_t* imgk;
+    SideStream::Branch predict;      // the predict layer's weight / bias gradients beside the reverse-time loop
+    SideStream::Branch tail;         // the attention block's tail beside the LSTM weight gradients
+};
 
-    // ---- predict layer, all time steps at once.  d h2drop feeds the BPTT chain; the weight / bias gradients of
-    //      `predict` depend only on dlogits, so they run on the side stream concurrently with the (skinny,
-    //      latency-bound) BPTT chain and are joined at the end.
-    ICZ_TRY(low.ensure(true));
-    hipEvent_t ev_fork = low.fork[0], ev_join = low.join[0];
+// phases: bit 0 = predict layer + reverse-time loop, bit 1 = embedding and TD-LSTM weight gradients, bit 2 = LM-LSTM weight
+// gradients, bit 3 = attention block, biases.  After each of the first three the corresponding gradient group is complete
+// in stream order (icz_butd_set_grad_callback); fire_cb = false leaves the callbacks to the caller, which replays every phase
+// as its own captured graph and calls them in between.
+int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_cb) {
+    const bool cb = grad_cb && fire_cb;
+    // The attention block's tail (phase 3: d enc_ctx, two small weight gradients, bias sums, weight-norm backward: ~0.2 ms of kernels
+    // that fill a fraction of the chip) depends on the loop only.  When the whole backward is one call without a DP callback it is
+    // forked at the loop's end and issued LAST, on the low-priority stream, beside the LSTM weight gradients: backward 2.685 / 2.684 /
+    // 2.698 -> 2.659 / 2.662 / 2.649 ms in three same-box rounds (profiles/r04_backward_issue_order.log; forked behind the TD gradients
+    // instead: slower, 2.73 - 2.75 ms; round 2 had issued such a branch FIRST and lost 0.25 ms).  With a callback the phases are
+    // separate graphs and stay in line.
+    const bool tail_side = phases == 0xF && !grad_cb && concurrent;
+    const int K = cur_K;
+    BpttCall c = {G, st, cur_B, cur_T, cur_rows, cur_row0, cur_T * cur_rows, (bptt_early_out && early_out) ? live_rows : nullptr,
+                  K, K > 1 ? cur_nimg : cur_B, K > 1 ? tb.imgk : nullptr, {concurrent ? &low : nullptr, 0}, {tail_side ? &low : nullptr, 1}};
     if (phases & 1) {
-    bptt_joined = false;
+        ICZ_TRY(bptt_predict(c));
+        ICZ_TRY(bptt_loop(c));
+        // with a DP callback the predict branch, long finished beside the loop, is joined here: its gradients are complete in stream
+        // order when the hook fires, and each phase is its own captured graph
+        if (grad_cb) ICZ_TRY(c.predict.join());
+        if (cb) grad_cb(grad_cb_user, 0);
+    }
+    ICZ_TRY(c.tail.fork(st));
+    if (phases & 2) {
+        ICZ_TRY(bptt_embed_td_wgrad(c));
+        if (cb) grad_cb(grad_cb_user, 1);
+    }
+    if (phases & 4) {
+        ICZ_TRY(bptt_lm_wgrad(c));
+        if (cb) grad_cb(grad_cb_user, 2);
+    }
+    if (phases & 8) {
+        ICZ_TRY(c.tail.start());
+        ICZ_TRY(bptt_attention_tail(c));
+    }
+    ICZ_TRY(c.tail.join());
+    ICZ_TRY(c.predict.join());
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+// ---- predict layer, all time steps at once.  d h2drop feeds the BPTT chain; the weight / bias gradients of `predict` depend only
+//      on dlogits, so they run on the side stream concurrently with the (skinny, latency-bound) BPTT chain.
+int Butd::bptt_predict(BpttCall& c) {
+    const int H = dims.H, A = dims.A, R = dims.R, V = dims.V, Vp = pad_vocab(V), TB = c.TB;
+    hipStream_t const st = c.st;
     // The side branch is forked here (it depends on dlogits only) but ISSUED behind the d h2drop GEMM below, the head of the critical
     // chain: issued first, its 10112 x 1024 x 1280 GEMM took the CUs ahead of that product.  Round 4, three same-box rounds: backward
     // 2.738 / 2.718 / 2.729 ms against 2.777 / 2.828 / 2.803 ms (profiles/r04_backward_issue_order.log); forking it behind the
     // product as well (no overlap with it at all): 2.762 / 2.779 / 2.750 ms.
-    auto side_branch = [&]() -> int {
-        ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, ev_fork, 0));
-        hipStream_t sb = concurrent ? low.st : st;   // low priority: the big GEMM only fills CUs the BPTT chain leaves idle
-        int s1 = wgrad(tb.logit, Vp, Vp, tb.h2d, H, H, TB, tb.dWp, H, sb, rl);
-        (void)launch_colsum(tb.logit, TB, V, Vp, G.predict_b, sb);
-        hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, sb, tb.dWp, H, P.predict_v, P.predict_g, n_pred,
-                           G.predict_v, G.predict_g, V, H);
-        ICZ_CHECK_HIP(hipEventRecord(ev_join, sb));
-        if (s1 != ICZ_OK) { (void)hipStreamWaitEvent(st, ev_join, 0); return s1; }
-        return ICZ_OK;
-    };
-    ICZ_CHECK_HIP(hipEventRecord(ev_fork, st));
+    ICZ_TRY(c.predict.fork(st));
     {
         GemmArgs g = gemm_args({{tb.logit, w_pred, Vp, H, Vp}}, TB, H, tb.dH2d, H);
-        g.rows_live = rl;
+        g.rows_live = c.rl;
         // nothing is forked yet: the side branch is issued behind this product
         ICZ_TRY(gemm_finished(GEMM_NN, g, split_backward(STEP_WGS), nullptr, ws, ws_floats, st, "butd"));
     }
-    ICZ_TRY(side_branch());
+    ICZ_TRY(c.predict.start());
+    hipStream_t const sb = c.predict.st();
+    ICZ_TRY(wgrad(tb.logit, Vp, Vp, tb.h2d, H, H, TB, tb.dWp, H, sb, c.rl));
+    (void)launch_colsum(tb.logit, TB, V, Vp, c.G.predict_b, sb);
+    hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, sb, tb.dWp, H, P.predict_v, P.predict_g, n_pred,
+                       c.G.predict_v, c.G.predict_g, V, H);
+    ICZ_TRY(c.predict.finish());
     // ---- XE only: rows that dropped out of the batch must contribute zero (the sample path writes every row, and its
     //      accumulators are initialised by the first processed step)
-    const bool ragged = rows_t[T - 1] < B || roff > 0;
+    const bool ragged = rows_t[c.T - 1] < c.B || c.roff > 0;
     if (ragged) {
         ICZ_CHECK_HIP(hipMemsetAsync(tb.dGtd, 0, sizeof(float) * (size_t)TB * 4 * H, st));
         ICZ_CHECK_HIP(hipMemsetAsync(tb.dGlm, 0, sizeof(float) * (size_t)TB * 4 * H, st));
         ICZ_CHECK_HIP(hipMemsetAsync(tb.dDec, 0, sizeof(float) * (size_t)TB * A, st));
         ICZ_CHECK_HIP(hipMemsetAsync(tb.dS, 0, sizeof(float) * (size_t)TB * R, st));
     }
+    return ICZ_OK;
+}
 
-    // ---- reverse-time loop (a lambda: whatever it returns, the side stream is joined behind it)
-    auto loop = [&]() -> int {
+// ---- the reverse-time loop: per step the pointwise LSTM / attention backward kernels and the dgrad products between them
+int Butd::bptt_loop(BpttCall& c) {
+    const int B = c.B, T = c.T, Bs = c.Bs, roff = c.roff;
+    const int H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = dims.R;
+    const size_t sH = (size_t)Bs * H;
+    const float* const feats = cur_feats;
+    const int32_t* const imgk = c.imgk;
+    hipStream_t const st = c.st;
     int cur = 0;
     int ns1 = 1, ns2 = 1, ns3 = 1, ns4 = 1;
     int bnext = 0;
@@ -613,28 +654,15 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
         cur ^= 1;
     }
     return ICZ_OK;
-    };
-    const int s_loop = loop();
-    if (grad_cb || s_loop != ICZ_OK) {      // the predict branch has long finished beside the loop: join it now so that its gradients can be reduced
-        ICZ_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0));
-        bptt_joined = true;
-    }
-    if (s_loop != ICZ_OK) return s_loop;
-    }   // phase 0
-    if ((phases & 1) && grad_cb && fire_cb) grad_cb(grad_cb_user, 0);
-    const int ldtd = H + D + E, ldlm = D + H;
-    // The attention block's tail (phase 3: d enc_ctx, two small weight gradients, bias sums, weight-norm backward: ~0.2 ms of kernels
-    // that fill a fraction of the chip) depends on the loop only.  When the whole backward is one call without a DP callback it is
-    // forked HERE and issued LAST, on the low-priority stream, beside the LSTM weight gradients: backward 2.685 / 2.684 / 2.698 ->
-    // 2.659 / 2.662 / 2.649 ms in three same-box rounds (profiles/r04_backward_issue_order.log; forked behind the TD gradients
-    // instead: slower, 2.73 - 2.75 ms; round 2 had issued such a branch FIRST and lost 0.25 ms).  With a callback the phases are
-    // separate graphs and stay in line.
-    const bool tail_side = phases == 0xF && !grad_cb && concurrent;
-    if (tail_side) ICZ_CHECK_HIP(hipEventRecord(low.fork[1], st));
-    bool tail_forked = false;
-    hipStream_t const main_st = st;
-    auto behind_loop = [&]() -> int {
-    if (phases & 2) {
+}
+
+// ---- embedding gradient and the TD-LSTM weight gradients
+int Butd::bptt_embed_td_wgrad(BpttCall& c) {
+    const int B = c.B, T = c.T, Bs = c.Bs, roff = c.roff, TB = c.TB, K = c.K, n_img = c.n_img;
+    const int H = dims.H, D = dims.D, E = dims.E, V = dims.V, ldtd = H + D + E;
+    const icz_butd_params& G = c.G;
+    const int* const rl = c.rl;
+    hipStream_t const st = c.st;
     // ---- embedding gradient: dEmb = dG_td . W_ih_td[:, H+D:] for all steps, then ordered scatter
     {
         GemmArgs g = gemm_args({{tb.dGtd, P.td_w_ih + H + D, 4 * H, H + D + E, 4 * H}}, TB, E, tb.dEmb, E);
@@ -664,22 +692,31 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
         ICZ_TRY(wgrad(tb.dGtd, 4 * H, 4 * H, tb.emb, E, E, TB, G.td_w_ih + H + D, ldtd, st, rl));
         ICZ_TRY(wgrad(tb.dGtd, 4 * H, 4 * H, tb.h1, H, H, TB, G.td_w_hh, H, st, rl));
     }
-    }   // phase 1
-    if ((phases & 2) && grad_cb && fire_cb) grad_cb(grad_cb_user, 1);
-    if (phases & 4) {
+    return ICZ_OK;
+}
+
+// ---- the LM-LSTM weight gradients
+int Butd::bptt_lm_wgrad(BpttCall& c) {
+    const int H = dims.H, D = dims.D, ldlm = D + H;
+    const size_t sH = (size_t)c.Bs * H;
+    const icz_butd_params& G = c.G;
     const GemmColGroup lm_groups[3] = {{tb.ctx, D, D, G.lm_w_ih, ldlm},                      // ctx_t
                                        {tb.h1 + sH, H, H, G.lm_w_ih + D, ldlm},              // h1_t
                                        {tb.h2, H, H, G.lm_w_hh, H}};                         // h2_{t-1}
-    const int r = wslab_of(st);
-    ICZ_TRY(gemm_tn_groups(tb.dGlm, 4 * H, 4 * H, TB, lm_groups, 3, tb.wslab[r], tb.wslab_floats[r], rl, st));   // grouped at 4096 x 4096: 227 us against 123 + 2 x 85
-    }   // phase 2
-    if ((phases & 4) && grad_cb && fire_cb) grad_cb(grad_cb_user, 2);
-    if (phases & 8) {
-    if (tail_side) {
-        ICZ_CHECK_HIP(hipStreamWaitEvent(low.st, low.fork[1], 0));
-        tail_forked = true;
-        st = low.st;
-    }
+    const int r = wslab_of(c.st);
+    return gemm_tn_groups(tb.dGlm, 4 * H, 4 * H, c.TB, lm_groups, 3, tb.wslab[r], tb.wslab_floats[r], c.rl, c.st);   // grouped at 4096 x 4096: 227 us against 123 + 2 x 85
+}
+
+// ---- the attention block's tail, on the tail branch's stream: its two weight gradients, d enc_ctx, the bias sums of every layer
+//      below `predict` and weight-norm backward of the block's three layers
+int Butd::bptt_attention_tail(BpttCall& c) {
+    const int B = c.B, T = c.T, Bs = c.Bs, roff = c.roff, TB = c.TB, K = c.K, n_img = c.n_img;
+    const int H = dims.H, D = dims.D, A = dims.A, R = dims.R;
+    const size_t sH = (size_t)Bs * H;
+    const icz_butd_params& G = c.G;
+    const float* const feats = cur_feats;
+    const int32_t* const imgk = c.imgk;
+    hipStream_t const st = c.tail.st();
     ICZ_TRY(wgrad(tb.dDec, A, A, tb.h1 + sH, H, H, TB, tb.dWdec, H, st));
     {   // d enc_ctx (sum over time) and the affine-weight partials, from the ds_t recorded by the loop
         AttBwdDencArgs ea = {enc_ctx, tb.dec + (size_t)roff * A, tb.dS + (size_t)roff * R, w_aff, tb.dEnc, tb.dwaff, B, R, A, T,
@@ -727,22 +764,6 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
         add(tb.dWaff, A, P.affine_v, P.affine_g, n_aff, G.affine_v, G.affine_g, 1, A);
         hipLaunchKernelGGL(weight_norm_bwd_multi_kernel, dim3(nb), dim3(256), 0, st, wt);
     }
-    }   // phase 3
-    return ICZ_OK;
-    };
-    const int s_tail = behind_loop();
-    st = main_st;
-    // joins, also on an error (inside a capture an unjoined side stream would hide the original error behind a capture failure)
-    if (tail_forked) {
-        ICZ_CHECK_HIP(hipEventRecord(low.join[1], low.st));
-        ICZ_CHECK_HIP(hipStreamWaitEvent(st, low.join[1], 0));
-    }
-    if (((phases & 8) || s_tail != ICZ_OK) && !bptt_joined) {      // join the predict-gradient branch
-        ICZ_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0));
-        bptt_joined = true;
-    }
-    if (s_tail != ICZ_OK) return s_tail;
-    ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
 

@@ -153,6 +153,43 @@ struct SideStream {
         }
         return ICZ_OK;
     }
+    // One fork / join pair of a side stream for the life of one branch beside the caller's stream, and the owner of the rule
+    // "a forked branch is joined on every way out": inside a capture an unjoined fork would hide the error that caused the early
+    // return behind a capture failure, so the destructor closes whatever a started branch still has open (statuses dropped, the
+    // error text of the first failure kept).  The four moments are apart because the call sites keep them apart: a branch is forked
+    // at one point of the caller's stream and issued behind later work of it.
+    // side null: the branch runs in line -- st() is the caller's stream and nothing is recorded or waited on.
+    struct Branch {
+        Branch(SideStream* side, int pair) : s(side), i(pair) {}
+        Branch(const Branch&) = delete;
+        Branch& operator=(const Branch&) = delete;
+        ~Branch() {
+            if (started && !finished) (void)hipEventRecord(s->join[i], s->st);
+            if (started && !joined) (void)hipStreamWaitEvent(main, s->join[i], 0);
+        }
+        hipStream_t st() const { return s ? s->st : main; }      // where the branch's launches go (behind fork())
+        int fork(hipStream_t caller) {      // the fork point on the caller's stream
+            main = caller;
+            if (s) ICZ_CHECK_HIP(hipEventRecord(s->fork[i], main));
+            return ICZ_OK;
+        }
+        int start() {                       // the side stream waits for the fork point: the branch is issued behind this
+            if (s) { ICZ_CHECK_HIP(hipStreamWaitEvent(s->st, s->fork[i], 0)); started = true; }
+            return ICZ_OK;
+        }
+        int finish() {                      // behind the branch's last launch
+            if (started && !finished) { finished = true; ICZ_CHECK_HIP(hipEventRecord(s->join[i], s->st)); }
+            return ICZ_OK;
+        }
+        int join() {                        // the caller's stream waits for the branch (finished here if it is not yet); idempotent
+            ICZ_TRY(finish());
+            if (started && !joined) { joined = true; ICZ_CHECK_HIP(hipStreamWaitEvent(main, s->join[i], 0)); }
+            return ICZ_OK;
+        }
+      private:
+        SideStream* s; int i; hipStream_t main = nullptr;
+        bool started = false, finished = false, joined = false;
+    };
 };
 
 // The caption loss head: host-side state of a stored training-mode forward pass and the loss buffers of all three decoders.

@@ -198,6 +198,32 @@ int set_norm_global(const char* who, CaptionHead* h, const float* norm_dev, void
 }  // namespace icz
 
 extern "C" {
+int icz_test_side_branch(int32_t fail_at, int32_t inline_branch, float* out2, void* stream) {
+    using namespace icz;
+    ICZ_REQUIRE(out2 && fail_at >= -1 && fail_at <= 3, "icz_test_side_branch: bad arguments");
+    static SideStream* const side = new SideStream();      // (never destroyed: they would outlive the runtime at process exit)
+    static GraphCache* const gc = new GraphCache(4);
+    ICZ_TRY(side->ensure());
+    // (fail_at in the key: a failing call must capture, not replay the graph of an earlier call; it leaves no entry behind)
+    return gc->run({(uintptr_t)(fail_at + 1), (uintptr_t)(inline_branch != 0), (uintptr_t)out2}, (hipStream_t)stream, [&](hipStream_t st) -> int {
+        int stage = 0;
+        auto behind = [&]() -> int {
+            ICZ_REQUIRE(stage++ != fail_at, "side-branch test: stage %d", fail_at);
+            return ICZ_OK;
+        };
+        SideStream::Branch b(inline_branch ? nullptr : side, 0);
+        ICZ_TRY(b.fork(st));
+        hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, (uint64_t*)nullptr, (uint64_t)0, out2, 1.0f);
+        ICZ_TRY(behind());
+        ICZ_TRY(b.start());
+        ICZ_TRY(behind());
+        hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, b.st(), (uint64_t*)nullptr, (uint64_t)0, out2 + 1, 2.0f);
+        ICZ_TRY(behind());
+        ICZ_TRY(b.finish());
+        ICZ_TRY(behind());
+        return b.join();
+    });
+}
 const char* icz_last_error(void) { return icz::g_err; }
 const char* icz_version(void) { return "libicz 0.1 (gfx950)"; }
 }
