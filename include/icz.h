@@ -38,7 +38,9 @@ const char* icz_version(void);
 typedef struct icz_butd icz_butd_t;
 
 typedef struct {
-    int32_t R;        /* regions per image (36 bottom-up boxes, 49 for the 7x7 spatial grid) */
+    int32_t R;        /* regions per image (36 bottom-up boxes, 49 for the 7x7 spatial grid): 1..64 through icz_butd_create; a
+                         capacity of 1..128 through icz_butd_create_regions (100 for the 'adaptive' bottom-up sets), where the
+                         layout of a batch is set by icz_butd_set_regions */
     int32_t D;        /* region feature size (2048)                                          */
     int32_t H;        /* LSTM hidden size (Configs/Models/BUTDDetection.json: 1024)          */
     int32_t E;        /* embedding size                                                      */
@@ -62,6 +64,9 @@ typedef struct {
 } icz_butd_params;
 
 int icz_butd_create(const icz_butd_dims* dims, icz_butd_t** out);
+/* The same handle with dims.R as a region capacity of up to 128 (icz_butd_create keeps refusing R > 64): for the 'adaptive' bottom-up
+ * sets of 10..100 boxes and any fixed set of 65..128 regions.  Every other entry takes either handle. */
+int icz_butd_create_regions(const icz_butd_dims* dims, icz_butd_t** out);
 int icz_butd_destroy(icz_butd_t* h);
 /* Bind the (caller-owned, device-resident) parameters; pointers must stay valid while the handle is used. */
 int icz_butd_bind_params(icz_butd_t* h, const icz_butd_params* params);
@@ -104,8 +109,22 @@ int icz_butd_set_grad_callback(icz_butd_t* h, icz_grad_ready_cb cb, void* user);
  * loops refresh per batch and never need them. */
 int icz_butd_refresh_weights(icz_butd_t* h, void* stream);
 
+/* Region layout of the batches that follow (sticky; a new handle has regions = dims.R and no counts): `feats` of every
+ * later call is [B, regions, D] with regions <= dims.R (the handle's capacity), and every alpha output is [.., regions].
+ * counts = the number of valid leading regions of each image, i.e. bu_masks.sum(1) of the prefix masks the reference's engine
+ * builds (BUTD_Engine.py:35-46), in device memory (read by the kernels of the following calls -- keep it alive until they
+ * have run) and in host memory (validated here: 1 <= counts[i] <= regions); both NULL = every region valid.  Beyond the
+ * reference (whose model drops the mask and attends over the zero padding): image i behaves exactly as it would alone at
+ * R = counts[i] -- regions r >= counts[i] get attention weight 0 (alphas come back with zeros there), the mean feature
+ * averages the valid rows, pad rows are never loaded and take no part in any gradient.  The rows of one image (beam rows, the
+ * K rows of icz_butd_sample_n, both halves of a merged SCST chain) share its count.  The explicit attention-dropout mask and
+ * the Philox keep-bit index stay ((row * regions + r) * A + c).  A later call with more images than n_img while counts are
+ * set returns ICZ_ERR_INVALID.  Calls made while counts are set run eagerly (option "graphs" does not capture them); the
+ * captured graphs of fixed region sets are keyed by `regions`.  A forward pass stored for a backward call is dropped. */
+int icz_butd_set_regions(icz_butd_t* h, int32_t regions, const int32_t* counts_dev, const int32_t* counts_host, int32_t n_img);
+
 /* DecoderRNN.sample (BUTD_Model.py:153-189): greedy decode.
- * feats [B,R,D]; ids_out [B,max_len] int64; alphas_out [B,max_len,R] or NULL. */
+ * feats [B,R,D]; ids_out [B,max_len] int64; alphas_out [B,max_len,R] or NULL (R = the regions of icz_butd_set_regions). */
 int icz_butd_greedy(icz_butd_t* h, const float* feats, int32_t B, int32_t max_len, int64_t* ids_out,
                     float* alphas_out, void* stream);
 

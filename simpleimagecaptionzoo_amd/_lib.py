@@ -128,6 +128,7 @@ def lib():
         "icz_last_error": (C.c_char_p, []),
         "icz_version": (C.c_char_p, []),
         "icz_butd_create": (C.c_int, [C.POINTER(ButdDims), C.POINTER(vp)]),
+        "icz_butd_create_regions": (C.c_int, [C.POINTER(ButdDims), C.POINTER(vp)]),
         "icz_butd_destroy": (C.c_int, [vp]),
         "icz_butd_bind_params": (C.c_int, [vp, C.POINTER(ButdParams)]),
         "icz_butd_set_option": (C.c_int, [vp, C.c_char_p, i32]),
@@ -135,6 +136,7 @@ def lib():
         "icz_aoa_set_grad_callback": (C.c_int, [vp, GRAD_READY_CB, vp]),
         "icz_butd_set_mask_sum_global": (C.c_int, [vp, vp, vp]),
         "icz_butd_refresh_weights": (C.c_int, [vp, vp]),
+        "icz_butd_set_regions": (C.c_int, [vp, i32, vp, vp, i32]),
         "icz_butd_greedy": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         "icz_butd_step": (C.c_int, [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "icz_butd_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(Rng), vp, vp, vp]),

@@ -3,9 +3,7 @@
 Region sets: `'fixed'` (36 boxes, `bu_masks` None), the 7x7 grid (49) and `'adaptive'` (10..100 boxes per image, padded to
 the batch's largest count with prefix `bu_masks`, AoA_Engine.py:33-46) -- the handle is created for the largest region
 count it will see (`num_regions`) and every batch may be narrower."""
-import collections
 import copy
-import ctypes as C
 
 import torch
 import torch.nn as nn
@@ -13,6 +11,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import AOA_DECODER_KEYS, AOA_PARAM_KEYS, AoaDims, AoaParams, AoaRng, check, ptr, stream_ptr
 from .handle import CaptionerBase, GraphDecoderHandle
+from .regions import RegionBatch, RegionSets, counts_from_masks, region_features  # noqa: F401  (RegionBatch / counts_from_masks: this module's names)
 
 _MASKS = ("proj", "ref_att", "ref_aoa", "ref_sc", "emb", "ctx", "att", "out")
 
@@ -42,22 +41,7 @@ def make_aoa_rng(seed=0, uniforms=None, masks=None):
     return r
 
 
-# features [B, R, D] + the valid region count of each image (host ints; None = all R valid)
-RegionBatch = collections.namedtuple("RegionBatch", "feats counts")
-
-
-def counts_from_masks(bu_masks):
-    """bu_masks [B, R] (1 = valid) -> per-image counts.  The reference builds prefix masks (AoA_Engine.py:37-40) and itself
-    reads them as lengths (pack_wrapper, AoA_Model.py:652); anything else is rejected."""
-    m = bu_masks.detach()
-    counts = m.long().sum(1)
-    prefix = torch.arange(m.shape[1], device=m.device).unsqueeze(0) < counts.unsqueeze(1)
-    if not bool(((m != 0) == prefix).all()):
-        raise ValueError("bu_masks must mark a leading run of valid regions per image (AoA_Engine.py:37-40)")
-    return counts.tolist()
-
-
-class AoaHandle(GraphDecoderHandle):
+class AoaHandle(RegionSets, GraphDecoderHandle):
     family, kind = "aoa", 1
     _Params, _param_keys = AoaParams, AOA_PARAM_KEYS            # icz_aoa_params as the flat table p0..p81
     _frozen_keys = frozenset(AOA_PARAM_KEYS) - frozenset(AOA_DECODER_KEYS)
@@ -66,8 +50,7 @@ class AoaHandle(GraphDecoderHandle):
 
     def __init__(self, R, D, Hd, E, V, NH, max_rows, max_len=20, device="cuda:0"):
         self._create(AoaDims(R, D, Hd, E, V, NH, max_rows, max_len), device)
-        self._regions = (R, None)
-        self._counts_dev = None
+        self._regions_init()
 
     def _option_set(self, name, value):
         if name == "train_refiner":       # on: new_grads / _grad_struct cover every key, the refiner's buffers are required
@@ -75,29 +58,7 @@ class AoaHandle(GraphDecoderHandle):
 
     def set_regions(self, regions, counts=None):
         """icz_aoa_set_regions: the batches that follow are [B, regions, D]; counts = valid regions per image or None."""
-        if counts is None:
-            if self._regions != (regions, None):
-                check(self._e.set_regions(self._h, int(regions), None, None, 0))
-                self._regions, self._counts_dev = (regions, None), None
-            return
-        counts = [int(c) for c in counts]
-        host = (C.c_int32 * len(counts))(*counts)
-        dev = torch.tensor(counts, dtype=torch.int32, device=self.device)
-        check(self._e.set_regions(self._h, int(regions), ptr(dev), host, len(counts)))
-        # the kernels of the following calls read `dev`: it stays referenced until the next set_regions, and torch's
-        # caching allocator hands its memory out again only in stream order
-        self._regions, self._counts_dev = (regions, tuple(counts)), dev
-
-    def _feats(self, f):
-        counts = None
-        if isinstance(f, RegionBatch):
-            f, counts = f
-        if f.dtype != torch.float32 or not f.is_cuda or f.dim() != 3 or f.shape[2] != self.D or not 1 <= f.shape[1] <= self.R:
-            raise _lib.IczError("bu_feats must be an fp32 CUDA tensor (B, 1..%d, %d)" % (self.R, self.D))
-        if counts is not None and len(counts) != f.shape[0]:
-            raise _lib.IczError("%d region counts for %d images" % (len(counts), f.shape[0]))
-        self.set_regions(f.shape[1], counts)
-        return f.contiguous()
+        self._set_regions(regions, counts)
 
     def refine(self, feats):
         feats = self._feats(feats)
@@ -197,12 +158,7 @@ class AoADetection_Captioner(CaptionerBase, nn.Module):
     def _features(self, visual_inputs):
         """bu_feats (+ the region counts behind bu_masks: `bu_counts` when the Engine supplies them, else read back from the
         mask)."""
-        feats = visual_inputs["bu_feats"].detach()
-        masks = visual_inputs.get("bu_masks")
-        if masks is None:
-            return feats
-        counts = visual_inputs.get("bu_counts")
-        return RegionBatch(feats, list(counts) if counts is not None else counts_from_masks(masks))
+        return region_features(visual_inputs)
 
     def eval_test_image(self, visual_inputs, caption_vocab, max_len=20, eval_beam_size=-1):
         """AoA_Model.py:755-786 -> (caption words, [alphas (1, steps, regions)]): the decoder block's attention weights

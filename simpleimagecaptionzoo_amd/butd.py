@@ -6,6 +6,7 @@ import torch
 from . import _lib
 from ._lib import BUTD_PARAM_KEYS, ButdDims, ButdParams, Rng, check, lib, ptr, stream_ptr
 from .handle import GraphDecoderHandle
+from .regions import RegionSets
 
 
 def make_rng(seed=0, uniforms=None, emb_mask=None, att_mask=None, out_mask=None):
@@ -24,18 +25,23 @@ def make_rng(seed=0, uniforms=None, emb_mask=None, att_mask=None, out_mask=None)
     return r
 
 
-class ButdHandle(GraphDecoderHandle):
-    """Wraps icz_butd_* for a fixed architecture (R, D, H, E, A, V) and row / step capacity."""
+class ButdHandle(RegionSets, GraphDecoderHandle):
+    """Wraps icz_butd_* for a fixed architecture (D, H, E, A, V), a region capacity R (<= 128) and row / step capacity.  Features are
+    (B, 1..R, D) tensors, or a RegionBatch with the valid count of each image (`regions.py`, icz_butd_set_regions: an image then
+    behaves as it would alone at R = its count); the layout is set by the feature check of every call, there is no method to call
+    for it.  Alpha outputs are as wide as the batch."""
 
     family, kind = "butd", 0
     _Params, _param_keys = ButdParams, BUTD_PARAM_KEYS
     _make_rng = staticmethod(make_rng)
-    _own_entries = ("step", "sample_n", "sample_mask_sum", "saved_alphas", "sample_backward_dlogp", "xe_backward_dlogits")
+    _own_entries = ("create_regions", "set_regions", "step", "sample_n", "sample_mask_sum", "saved_alphas", "sample_backward_dlogp", "xe_backward_dlogits")
     _entry_names = {"set_norm_global": "set_mask_sum_global"}
     _sample_bufs = True
 
     def __init__(self, R, D, H, E, A, V, max_rows, max_len=20, device="cuda:0"):
-        self._create(ButdDims(R, D, H, E, A, V, max_rows, max_len), device)
+        # icz_butd_create keeps its bound of 64 regions; a larger capacity (the 'adaptive' sets) goes through icz_butd_create_regions
+        self._create(ButdDims(R, D, H, E, A, V, max_rows, max_len), device, "create_regions" if R > 64 else "create")
+        self._regions_init()
 
     def enable_graphs(self, on=True):
         """Capture greedy / sample / sample_backward into hipGraphs and replay them.  Implies persistent output
@@ -45,19 +51,12 @@ class ButdHandle(GraphDecoderHandle):
     def set_concurrent(self, on=True):
         self.set_option("concurrent", 1 if on else 0)
 
-    def _feats(self, feats):
-        if feats.dtype != torch.float32 or not feats.is_cuda:
-            raise _lib.IczError("feats must be an fp32 CUDA tensor")
-        if feats.dim() != 3 or feats.shape[1] != self.R or feats.shape[2] != self.D:
-            raise _lib.IczError("feats must be (B,%d,%d), got %s" % (self.R, self.D, tuple(feats.shape)))
-        return feats.contiguous()
-
     def greedy(self, feats, max_len=20, want_alphas=False):
-        """DecoderRNN.sample (Models/BUTD_Model.py:153-189) -> ids (B,max_len) int64 [, alphas (B,max_len,R)]."""
+        """DecoderRNN.sample (Models/BUTD_Model.py:153-189) -> ids (B,max_len) int64 [, alphas (B,max_len,regions)]."""
         feats = self._feats(feats)
         B = feats.shape[0]
         ids = self._buf("greedy_ids", (B, max_len), torch.int64)
-        alphas = self._buf("greedy_alphas", (B, max_len, self.R), torch.float32) if want_alphas else None
+        alphas = self._buf("greedy_alphas", (B, max_len, feats.shape[1]), torch.float32) if want_alphas else None
         check(self._e.greedy(self._h, ptr(feats), B, max_len, ptr(ids), ptr(alphas), stream_ptr()))
         return (ids, alphas) if want_alphas else ids
 
@@ -91,8 +90,8 @@ class ButdHandle(GraphDecoderHandle):
         check(self._e.sample_backward_dlogp(self._h, ptr(dlogp), C.byref(gs), stream_ptr()))
 
     def saved_alphas(self, B, T):
-        """Attention maps [B, T, R] of the forward pass the handle holds (the last xe_forward / sample of B rows, T steps)."""
-        out = torch.empty(B, T, self.R, device=self.device)
+        """Attention maps [B, T, regions] of the forward pass the handle holds (the last xe_forward / sample of B rows, T steps)."""
+        out = torch.empty(B, T, self.regions, device=self.device)
         check(self._e.saved_alphas(self._h, ptr(out), stream_ptr()))
         return out
 
@@ -109,7 +108,7 @@ class ButdHandle(GraphDecoderHandle):
         B = feats.shape[0]
         dev = feats.device
         ctx = torch.empty(B, self.D, device=dev)
-        alpha = torch.empty(B, self.R, device=dev)
+        alpha = torch.empty(B, feats.shape[1], device=dev)
         logits = torch.empty(B, self.V, device=dev)
         check(self._e.step(self._h, ptr(feats), B, ptr(it), ptr(h1), ptr(c1), ptr(h2), ptr(c2), ptr(ctx), ptr(alpha), ptr(logits),
                            stream_ptr()))

@@ -15,6 +15,7 @@ import torch.nn as nn
 from ._lib import BUTD_PARAM_KEYS
 from .butd import ButdHandle
 from .handle import CaptionerBase
+from .regions import RegionBatch, region_features
 
 
 class _Holder(nn.Module):
@@ -96,9 +97,16 @@ class _XEFunction(torch.autograd.Function):
 
 class BUTDDetection_Captioner(CaptionerBase, nn.Module):
     """Models/BUTD_Model.py:443-544 on libicz (sampler :478-489, beam_search_sampler :505-517).  enc_dim / num_regions default to
-    the bottom-up 36 x 2048 layout (49 regions = BUTDSpatial's 7x7 grid features, the same decoder, BUTD_Model.py:321-440)."""
+    the bottom-up 36 x 2048 layout (49 regions = BUTDSpatial's 7x7 grid features, the same decoder, BUTD_Model.py:321-440).
+    num_regions is the handle's capacity (up to 128); a batch may be narrower.
+
+    region_masks (beyond the reference; a plain attribute, like ss_prob, set after construction): False, the default, keeps the reference's behaviour -- its model drops `bu_masks` (:458-517), so a padded
+    'adaptive' batch attends over the zero padding and divides the region mean by the padded length.  True hands the handle the
+    region count of each image (`bu_counts`, or read back from the prefix `bu_masks`; a non-prefix mask raises ValueError): an
+    image then decodes and trains exactly as it would alone with its own boxes."""
 
     _Handle = ButdHandle
+    region_masks = False
 
     def __init__(self, atten_dim, embed_dim, hidden_dim, vocab_size, dropout=0.5, device="cuda:0", enc_dim=2048,
                  num_regions=36, max_batch=128, max_beam=5, max_len=20):
@@ -117,7 +125,7 @@ class BUTDDetection_Captioner(CaptionerBase, nn.Module):
         return ButdHandle(d["R"], d["D"], d["H"], d["E"], d["A"], d["V"], max_rows, max_len, device)
 
     def _features(self, visual_inputs):
-        return visual_inputs["bu_feats"]
+        return region_features(visual_inputs) if self.region_masks else visual_inputs["bu_feats"]
 
     def _grad_buffers(self):
         if self._grads is None or next(iter(self._grads.values())).device != next(self.parameters()).device:
@@ -130,7 +138,7 @@ class BUTDDetection_Captioner(CaptionerBase, nn.Module):
     # ---- the two methods Engine calls that are wired into autograd -------------------------------
     def forward(self, visual_inputs, captions, lengths, rng=None):
         """XE forward (BUTD_Model.py:458-476): returns an object whose [0] is the packed logits (sum(lengths), V)."""
-        feats = visual_inputs["bu_feats"]
+        feats = self._features(visual_inputs)
         train = self.training
         if train and rng is None:
             rng = self._next_rng()
@@ -143,7 +151,7 @@ class BUTDDetection_Captioner(CaptionerBase, nn.Module):
 
     def sampler_rl(self, visual_inputs, max_len=20, rng=None):
         """Multinomial rollout (BUTD_Model.py:491-503) -> (seq LongTensor (B,T), seqLogprobs (B,T) with grad)."""
-        feats = visual_inputs["bu_feats"]
+        feats = self._features(visual_inputs)
         rng = rng or self._next_rng()
         params = list(self._named().values())
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
@@ -151,14 +159,15 @@ class BUTDDetection_Captioner(CaptionerBase, nn.Module):
         return self._handle().sample(feats, max_len, rng)
 
     def eval_test_image(self, visual_inputs, caption_vocab, max_len=20, eval_beam_size=-1):
-        """BUTD_Model.py:519-544 -> (caption words, [alphas (1, steps, R)]).  Greedy: the attention maps come out of the decode
+        """BUTD_Model.py:519-544 -> (caption words, [alphas (1, steps, regions of the batch)]).  Greedy: the attention maps come out of the decode
         itself.  Beam search: the decoder state of a beam is a function of its token prefix, so the maps of the returned
         sentence are those of an evaluation-mode teacher-forced pass over it.  (The reference means to carry them along beam
         by beam, :282,:309-317, but appends every step's maps without the beam permutation -- `alpha.unsqueeze(1)` is not
         indexed by prev_word_inds and the history is never compacted with incomplete_inds -- so for beam > 1 its result mixes
         the maps of different beams; for beam 1 both agree, tests/test_gpu_round2.py.)"""
-        feats = visual_inputs["bu_feats"]
-        assert feats.size(0) == 1
+        feats = self._features(visual_inputs)
+        raw = feats.feats if isinstance(feats, RegionBatch) else feats
+        assert raw.size(0) == 1
         h = self._handle()
         if eval_beam_size != -1:
             seqs, lens = h.beam_search(feats, eval_beam_size, 50)
@@ -170,7 +179,7 @@ class BUTDDetection_Captioner(CaptionerBase, nn.Module):
                 rh.xe_forward(feats, ids.long(), [steps], None, train=False)
                 alphas = rh.saved_alphas(1, steps)
             else:
-                alphas = torch.zeros(1, 0, self.dims["R"], device=feats.device)
+                alphas = torch.zeros(1, 0, raw.shape[1], device=raw.device)
         else:
             ids, alphas = h.greedy(feats, max_len, want_alphas=True)
             ids, alphas = ids.clone(), alphas.clone()

@@ -6,9 +6,11 @@
 namespace icz {
 
 // ------------------------------------------------------------------------------------------------
-int Butd::init(const icz_butd_dims& d) {
+int Butd::init(const icz_butd_dims& d, int r_max) {
     dims = d;
-    ICZ_REQUIRE(d.R > 0 && d.R <= 64, "butd: R=%d must be in 1..64 (36 boxes / 49 grid cells)", d.R);
+    ICZ_REQUIRE(d.R > 0 && d.R <= r_max, "butd: R=%d must be in 1..%d (36 boxes / 49 grid cells; icz_butd_create_regions: adaptive sets, up to %d)",
+                d.R, r_max, ATT_MAX_R);
+    cur_R = d.R;
     ICZ_REQUIRE(d.D % 4 == 0 && d.H % 4 == 0 && d.E % 4 == 0 && d.A % 4 == 0, "butd: D,H,E,A must be multiples of 4");
     ICZ_REQUIRE(d.V > 3 && d.max_rows > 0 && d.max_len > 0, "butd: bad V/max_rows/max_len");
     const size_t rows = d.max_rows, H = d.H, D = d.D, E = d.E, A = d.A, V = d.V, R = d.R;
@@ -114,15 +116,17 @@ int Butd::gemm_nt(GemmArgs& g, const float* bias, hipStream_t st) {
 // Once per batch of images (K0 in SURVEY.md 2.3): mean features, the time-invariant part of the TD-LSTM gates
 // (mean . W_ih[:, H:H+D]^T) and enc_att(feats) -- the reference recomputes the latter every step (:57).
 int Butd::prologue(const float* feats, int n_img, hipStream_t st) {
-    const int R = dims.R, D = dims.D, H = dims.H, E = dims.E, A = dims.A;
+    const int R = cur_R, D = dims.D, H = dims.H, E = dims.E, A = dims.A;
     ICZ_REQUIRE(fresh, "butd: call icz_butd_refresh_weights after binding/updating parameters");
     ICZ_REQUIRE(n_img > 0 && n_img <= dims.max_rows, "butd: %d images exceed capacity %d", n_img, dims.max_rows);
-    hipLaunchKernelGGL(mean_feats_kernel, dim3(cdiv(D, 1024), n_img), dim3(256), 0, st, feats, mean, R, D);
+    ICZ_TRY(check_counts(n_img));
+    if (cnt) hipLaunchKernelGGL(mean_feats_counts_kernel, dim3(cdiv(D, 1024), n_img), dim3(256), 0, st, feats, mean, R, D, cnt);
+    else hipLaunchKernelGGL(mean_feats_kernel, dim3(cdiv(D, 1024), n_img), dim3(256), 0, st, feats, mean, R, D);
     {   // premean = mean . W_ih[:, H:H+D]^T   [n_img, 4H]
         GemmArgs g = gemm_args({{mean, P.td_w_ih + H, D, H + D + E, D}}, n_img, 4 * H, premean, 4 * H);
         ICZ_TRY(gemm_nt(g, nullptr, st));
     }
-    {   // enc_ctx = feats . w_enc^T + b_enc   [n_img*R, A]
+    {   // enc_ctx = feats . w_enc^T + b_enc   [n_img*R, A]  (over the padded rows too: the counted kernels never read those of enc_ctx)
         GemmArgs g = gemm_args({{feats, w_enc, D, D, D}}, n_img * R, A, enc_ctx, A);
         ICZ_TRY(gemm_nt(g, P.enc_att_b, st));
     }
@@ -132,9 +136,10 @@ int Butd::prologue(const float* feats, int n_img, hipStream_t st) {
 
 // One decoder step (:172-182) for `rows` decoder rows.  State is read from s.*_in and written to s.*_out.
 int Butd::step(const StepIO& s, hipStream_t st) {
-    const int R = dims.R, D = dims.D, H = dims.H, E = dims.E, A = dims.A, V = dims.V;
+    const int R = cur_R, D = dims.D, H = dims.H, E = dims.E, A = dims.A, V = dims.V;
     const int Vp = pad_vocab(V);
     const int rows = s.rows;
+    const bool ad = adaptive();
     float* const ws = s.ws_alt ? s.ws_alt : this->ws;
     float* const scores = s.scores_alt ? s.scores_alt : this->scores;
     DropCfg off = {0, nullptr, nullptr, 0, 0};
@@ -162,23 +167,27 @@ int Butd::step(const StepIO& s, hipStream_t st) {
         GemmArgs g = gemm_args({{s.h1_out, w_dec, H, H, H}}, rows, A, ws, A, s.live);
         ns = gemm_pick_split(g, STEP_WGS);
         ICZ_TRY(gemm_slabs(GEMM_NT, g, ns, ws, ws_cap, st, "butd"));
-        AttScoreArgs a = {enc_ctx, s.img_of_row, ws, ns, P.dec_att_b, w_aff, P.affine_b, s.dec_ctx_out, scores, rows, R, A, s.live};
+        AttScoreArgs a = {enc_ctx, s.img_of_row, ws, ns, P.dec_att_b, w_aff, P.affine_b, s.dec_ctx_out, scores, rows, R, A, s.live, cnt};
         const int G = s.rows_per_img;
         // compare the accumulation order: the per-row kernel sums a region row in the lane order of three regions at a time, the
         // grouped one region by region -- identical per (row, region): a wave's lanes cover the same columns in the same order
         const bool grouped = G > 1 && G <= ATT_CTX_MAX_G && rows % G == 0 && sizeof(float) * A * G <= 60 * 1024;
+        // (the <true> instances: per-image counts or more than 64 regions, Butd::adaptive)
         if (grouped && s.drop_att.mode == 0 && !s.live)          // beam search
-            hipLaunchKernelGGL(att_scores_group_kernel, dim3(rows / G, ATT_PARTS), dim3(256), sizeof(float) * A * G, st, a, G);
+            hipLaunchKernelGGL(ad ? att_scores_group_kernel<true> : att_scores_group_kernel<false>, dim3(rows / G, ATT_PARTS), dim3(256),
+                               sizeof(float) * A * G, st, a, G);
         else if (grouped)                                        // the multi-sample rollout (sample_n): dropout per row, early-out
-            hipLaunchKernelGGL(att_scores_group_train_kernel, dim3(rows / G, ATT_PARTS), dim3(256), sizeof(float) * A * G, st, a, s.drop_att, G);
+            hipLaunchKernelGGL(ad ? att_scores_group_train_kernel<true> : att_scores_group_train_kernel<false>, dim3(rows / G, ATT_PARTS), dim3(256),
+                               sizeof(float) * A * G, st, a, s.drop_att, G);
         else
-            hipLaunchKernelGGL(att_scores_kernel, dim3(rows, ATT_PARTS), dim3(256), sizeof(float) * A, st, a, s.drop_att);
+            hipLaunchKernelGGL(ad ? att_scores_kernel<true> : att_scores_kernel<false>, dim3(rows, ATT_PARTS), dim3(256), sizeof(float) * A, st, a, s.drop_att);
         if (G > 1 && G <= ATT_CTX_MAX_G && rows % G == 0 && !s.alpha_out2)
-            hipLaunchKernelGGL(att_ctx_group_kernel, dim3(rows / G, cdiv(D, 512)), dim3(256), 0, st, s.feats, (const float*)scores,
-                               s.alpha_out ? s.alpha_out : alpha, s.ctx_out ? s.ctx_out : ctx, R, D, G, s.live);
+            hipLaunchKernelGGL(ad ? att_ctx_group_kernel<true> : att_ctx_group_kernel<false>, dim3(rows / G, cdiv(D, 512)), dim3(256), 0, st, s.feats,
+                               (const float*)scores, s.alpha_out ? s.alpha_out : alpha, s.ctx_out ? s.ctx_out : ctx, R, D, G, s.live, cnt);
         else
-            hipLaunchKernelGGL(att_ctx_kernel, dim3(rows, cdiv(D, 512)), dim3(256), 0, st, s.feats, s.img_of_row, (const float*)scores,
-                               s.alpha_out ? s.alpha_out : alpha, s.alpha_out2, s.alpha2_stride, s.ctx_out ? s.ctx_out : ctx, R, D, s.live);
+            hipLaunchKernelGGL(ad ? att_ctx_kernel<true> : att_ctx_kernel<false>, dim3(rows, cdiv(D, 512)), dim3(256), 0, st, s.feats, s.img_of_row,
+                               (const float*)scores, s.alpha_out ? s.alpha_out : alpha, s.alpha_out2, s.alpha2_stride, s.ctx_out ? s.ctx_out : ctx, R, D,
+                               s.live, cnt);
         kprof_mark(KP_ATTENTION, false, st);
     }
     const float* ctxp = s.ctx_out ? s.ctx_out : ctx;
@@ -207,7 +216,8 @@ int Butd::zero_state(int rows, int which, hipStream_t st) {
 int Butd::greedy(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st) {
     ICZ_REQUIRE(feats && ids_out && B > 0 && B <= dims.max_rows && max_len > 0, "butd greedy: bad arguments");
     ICZ_REQUIRE(fresh, "butd: call icz_butd_refresh_weights after binding/updating parameters");
-    if (!use_graphs) return greedy_impl(feats, B, max_len, ids_out, alphas_out, st);
+    ICZ_TRY(check_counts(B));
+    if (!graphs_on()) return greedy_impl(feats, B, max_len, ids_out, alphas_out, st);
     const std::vector<uintptr_t> key = {1, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)max_len, (uintptr_t)ids_out, (uintptr_t)alphas_out, opt_bits()};
     return gc.run(key, st, [&](hipStream_t s) { return greedy_impl(feats, B, max_len, ids_out, alphas_out, s); });
 }
@@ -235,7 +245,7 @@ int Butd::greedy_chain(const float* feats, int B, int max_len, int64_t* ids_out,
         s.emb_ready = t > 0;           // produced by the previous step's embed_argmax_kernel
         s.h1_in = h1[cur]; s.c1_in = c1[cur]; s.h2_in = h2[cur]; s.c2_in = c2[cur];
         s.h1_out = h1[cur ^ 1]; s.c1_out = c1[cur ^ 1]; s.h2_out = h2[cur ^ 1]; s.c2_out = c2[cur ^ 1];
-        if (alphas_out) { s.alpha_out2 = alphas_out + (size_t)t * dims.R; s.alpha2_stride = max_len * dims.R; }
+        if (alphas_out) { s.alpha_out2 = alphas_out + (size_t)t * cur_R; s.alpha2_stride = max_len * cur_R; }
         int pns = 1;
         s.pred_nsplit = &pns;
         if (track && t > 0) s.live = gn + (t - 1);
@@ -290,6 +300,16 @@ extern "C" {
 
 int icz_butd_create(const icz_butd_dims* dims, icz_butd_t** out) { return abi_create<Butd>("icz_butd_create", dims, out); }
 
+// a handle whose dims.R is a region capacity of up to ATT_MAX_R (icz_butd_create keeps its bound of 64)
+int icz_butd_create_regions(const icz_butd_dims* dims, icz_butd_t** out) {
+    ICZ_REQUIRE(dims && out, "icz_butd_create_regions: null argument");
+    Butd* h = new Butd();
+    const int s = h->init(*dims, ATT_MAX_R);
+    if (s != ICZ_OK) { delete h; return s; }
+    *out = reinterpret_cast<icz_butd_t*>(h);
+    return ICZ_OK;
+}
+
 int icz_butd_destroy(icz_butd_t* h) {
     delete reinterpret_cast<Butd*>(h);
     return ICZ_OK;
@@ -342,6 +362,21 @@ int icz_butd_set_grad_callback(icz_butd_t* h, icz_grad_ready_cb cb, void* user) 
 int icz_butd_refresh_weights(icz_butd_t* h, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Butd*>(h)->refresh((hipStream_t)stream);
+}
+
+int icz_butd_set_regions(icz_butd_t* h, int32_t regions, const int32_t* counts_dev, const int32_t* counts_host, int32_t n_img) {
+    ICZ_REQUIRE(h, "null handle");
+    Butd* b = reinterpret_cast<Butd*>(h);
+    ICZ_REQUIRE(regions >= 1 && regions <= b->dims.R, "icz_butd_set_regions: %d regions outside 1..%d (the handle's capacity)", regions, b->dims.R);
+    ICZ_REQUIRE((counts_dev == nullptr) == (counts_host == nullptr), "icz_butd_set_regions: pass the counts on both sides or on neither");
+    if (counts_host) {
+        ICZ_REQUIRE(n_img >= 1 && n_img <= b->dims.max_rows, "icz_butd_set_regions: %d images out of range", n_img);
+        for (int i = 0; i < n_img; ++i)
+            ICZ_REQUIRE(counts_host[i] >= 1 && counts_host[i] <= regions, "icz_butd_set_regions: image %d has %d regions (1..%d)", i, counts_host[i], regions);
+    }
+    b->cur_R = regions; b->cnt = counts_dev; b->cnt_n = counts_dev ? n_img : 0;
+    b->mode = 0;         // a stored forward pass was laid out with the previous stride
+    return ICZ_OK;
 }
 
 int icz_butd_greedy(icz_butd_t* h, const float* feats, int32_t B, int32_t max_len, int64_t* ids_out,

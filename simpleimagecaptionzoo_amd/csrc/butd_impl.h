@@ -88,7 +88,7 @@ struct Butd : CaptionHead, DecodeMember {
     int refresh_transposes(hipStream_t st);
 
     int alloc(void** p, size_t bytes) { return mem.alloc(p, bytes); }
-    int init(const icz_butd_dims& d);
+    int init(const icz_butd_dims& d, int r_max = 64);      // r_max: 64 through icz_butd_create, ATT_MAX_R through icz_butd_create_regions
     int refresh(hipStream_t st);
     int gemm_nt(GemmArgs& g, const float* bias, hipStream_t st);
     int prologue(const float* feats, int n_img, hipStream_t st);
@@ -96,11 +96,24 @@ struct Butd : CaptionHead, DecodeMember {
     int zero_state(int rows, int which, hipStream_t st);
     int greedy(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st);
 
-    GraphCache gc{24};                   // keys end with opt_bits(); bypassed unless use_graphs
+    // regions per image of the current batch (icz_butd_set_regions): row stride cur_R <= dims.R of feats and of every per-image
+    // buffer and, for the 'adaptive' bottom-up features (10..100 boxes), the valid count per image (device, caller-owned; null = all
+    // cur_R).  adaptive(): the launches take the <true> instances of the attention kernels (butd_kernels.h) -- with no counts and
+    // cur_R <= 64 every launch is the fixed-set instance.
+    int cur_R = 0, cnt_n = 0;
+    const int32_t* cnt = nullptr;
+    bool adaptive() const { return cnt != nullptr || cur_R > 64; }
+    int check_counts(int n_img) const {
+        ICZ_REQUIRE(!cnt || n_img <= cnt_n, "butd: region counts were set for %d images, the batch has %d (icz_butd_set_regions)", cnt_n, n_img);
+        return ICZ_OK;
+    }
+
+    GraphCache gc{24};                   // keys end with opt_bits(); bypassed unless graphs_on()
     bool use_graphs = false;
+    bool graphs_on() const { return use_graphs && !cnt; }       // calls made while counts are set stay eager (as AoA's do)
     bool concurrent = true;      // run independent chains on side streams (off: one stream, for per-kernel timing)
-    uintptr_t opt_bits() const {         // the options that change the captured launch sequence
-        return (concurrent ? 1 : 0) + (early_out ? 2 : 0) + 4 * merge_small + (small_nt ? 256 : 0) + (group_att ? 512 : 0);
+    uintptr_t opt_bits() const {         // the options that change the captured launch sequence, and the row stride of the region tensors
+        return (concurrent ? 1 : 0) + (early_out ? 2 : 0) + 4 * merge_small + (small_nt ? 256 : 0) + (group_att ? 512 : 0) + ((uintptr_t)cur_R << 16);
     }
     int greedy_impl(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st);
     int sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st);

@@ -79,6 +79,22 @@ __global__ __launch_bounds__(256) void mean_feats_kernel(const float* __restrict
     *reinterpret_cast<f32x4*>(mean + (size_t)b * D + d) = o;
 }
 
+// The same over an adaptive region set (icz_butd_set_regions): image b has counts[b] valid leading rows of its R-row block; the
+// mean is their sum, in row order, over counts[b] -- what the kernel above gives the image alone at R = counts[b].  Pad rows are not read.
+__global__ __launch_bounds__(256) void mean_feats_counts_kernel(const float* __restrict__ feats, float* __restrict__ mean,
+                                                                int R, int D, const int32_t* __restrict__ counts) {
+    const int b = blockIdx.y;
+    const int d = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (d >= D) return;
+    const int Rc = counts ? counts[b] : R;
+    const float* f = feats + (size_t)b * R * D + d;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    for (int r = 0; r < Rc; ++r) s += *reinterpret_cast<const f32x4*>(f + (size_t)r * D);
+    const float fr = (float)Rc;
+    f32x4 o = {s[0] / fr, s[1] / fr, s[2] / fr, s[3] / fr};
+    *reinterpret_cast<f32x4*>(mean + (size_t)b * D + d) = o;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Embedding -> ReLU -> Dropout (:77-81):  emb[row,:] = relu(E[it[row],:]) * keep * 2
 __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ table, const int64_t* __restrict__ it,
@@ -280,10 +296,19 @@ struct AttScoreArgs {
     float* scores;               // [rows, R]
     int rows, R, A;
     const int* live;             // step_dead(live): return at entry
+    const int32_t* counts;       // <true> instances only: valid leading regions per image (null = all R); R stays the row stride
 };
+// Adaptive region sets (icz_butd_set_regions).  The attention kernels below are templates on AD: <false> is the fixed-set kernel of
+// R <= 64 regions ("lane r holds score r"); <true> serves per-image counts and sets of up to 128 regions.  A <true> kernel reads its
+// image's count c with one scalar load and uses it as the bound of every region loop -- pad rows of feats / enc_ctx are never
+// loaded -- while R remains the row stride of every tensor and of the mask / Philox index; what it writes at r >= c (scores, alpha,
+// ds, d enc_ctx) is zero.  Softmax, dot and ds hold two regions per lane (lane, lane + 64): at c <= 64 the second is the
+// identity of every reduction, so an image gets bit for bit what <false> gives it alone at R = c.
+constexpr int ATT_MAX_R = 128;
 // Grid (rows, parts), 256 threads.  Part p owns regions p, p + parts, p + 2 parts, ...; a wave takes up to three of them
 // at a time and issues all their loads (3 regions x 4 float4 per lane) before the first use: the kernel moves
 // R*A*4 bytes per row once and is bound by how many bytes each CU keeps in flight, not by arithmetic.
+template <bool AD>
 __global__ __launch_bounds__(256) void att_scores_kernel(AttScoreArgs a, DropCfg dc) {
     extern __shared__ __attribute__((aligned(16))) float sdec[];   // A floats
     const int lflag = live_flag(a.live);
@@ -291,15 +316,16 @@ __global__ __launch_bounds__(256) void att_scores_kernel(AttScoreArgs a, DropCfg
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t MN = (size_t)a.rows * a.A;
     const int img = a.img_of_row ? a.img_of_row[row] : row;
+    const int Rc = (AD && a.counts) ? a.counts[img] : a.R;
     constexpr int NB = 3;
     // the projected features do not depend on dec_ctx: the loads of the wave's first group of regions (its only one at 36
     // regions, A <= 1024) are issued before the split-K slabs are summed, so both round trips overlap
     f32x4 xf[NB][4];
-    if (part + nparts * wave < a.R) {
+    if (part + nparts * wave < Rc) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             const int r = part + nparts * (wave + 4 * b);
-            const float* e = a.enc_ctx + ((size_t)img * a.R + (r < a.R ? r : part + nparts * wave)) * a.A;
+            const float* e = a.enc_ctx + ((size_t)img * a.R + (r < Rc ? r : part + nparts * wave)) * a.A;
 #pragma unroll
             for (int u = 0; u < 4; ++u) xf[b][u] = *reinterpret_cast<const f32x4*>(e + min(lane * 4 + 256 * u, a.A - 4));
         }
@@ -319,7 +345,7 @@ __global__ __launch_bounds__(256) void att_scores_kernel(AttScoreArgs a, DropCfg
     if (drow < 0) dc.mode = 0;
     const float sc = dc.mode ? 2.0f : 1.0f;
     const bool shared_bits = dc.mode == 2 && (a.A & 255) == 0;       // whole 256-column strips: every lane runs every c0 iteration
-    for (int i0 = wave; part + nparts * i0 < a.R; i0 += 4 * NB) {
+    for (int i0 = wave; part + nparts * i0 < Rc; i0 += 4 * NB) {
         int rr[NB];
         bool ok[NB];
         const float* e[NB];
@@ -327,7 +353,7 @@ __global__ __launch_bounds__(256) void att_scores_kernel(AttScoreArgs a, DropCfg
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             const int r = part + nparts * (i0 + 4 * b);
-            ok[b] = r < a.R;
+            ok[b] = r < Rc;
             rr[b] = ok[b] ? r : part + nparts * i0;
             e[b] = a.enc_ctx + ((size_t)img * a.R + rr[b]) * a.A;
             acc[b] = 0.f;
@@ -391,6 +417,10 @@ __global__ __launch_bounds__(256) void att_scores_kernel(AttScoreArgs a, DropCfg
             if (lane == 0 && ok[b]) a.scores[(size_t)row * a.R + rr[b]] = v + baff;
         }
     }
+    if constexpr (AD) {
+        if (part == 0)
+            for (int r = Rc + tid; r < a.R; r += 256) a.scores[(size_t)row * a.R + r] = 0.f;
+    }
 }
 
 constexpr int ATT_CTX_MAX_G = 8;
@@ -399,9 +429,11 @@ constexpr int ATT_CTX_MAX_G = 8;
 // region row of enc_ctx (A floats) is fetched once instead of G times (at 640 rows the per-row kernel re-reads 47 MB per
 // step through the caches).  Evaluation mode only (beam search has no dropout); same arithmetic and summation order per
 // row as att_scores_kernel.  Grid (n_img, parts).
+template <bool AD>
 __global__ __launch_bounds__(256) void att_scores_group_kernel(AttScoreArgs a, int G) {
     extern __shared__ __attribute__((aligned(16))) float sdec[];   // [G][A]
     const int img = blockIdx.x, part = blockIdx.y, nparts = gridDim.y;
+    const int Rc = (AD && a.counts) ? a.counts[img] : a.R;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t MN = (size_t)a.rows * a.A;
     for (int g = 0; g < G; ++g) {
@@ -417,7 +449,7 @@ __global__ __launch_bounds__(256) void att_scores_group_kernel(AttScoreArgs a, i
     }
     __syncthreads();
     const float baff = a.b_aff[0];
-    for (int i0 = wave; part + nparts * i0 < a.R; i0 += 4) {
+    for (int i0 = wave; part + nparts * i0 < Rc; i0 += 4) {
         const int r = part + nparts * i0;
         const float* e = a.enc_ctx + ((size_t)img * a.R + r) * a.A;
         float acc[ATT_CTX_MAX_G];
@@ -449,15 +481,21 @@ __global__ __launch_bounds__(256) void att_scores_group_kernel(AttScoreArgs a, i
                 if (lane == 0) a.scores[(size_t)(img * G + g) * a.R + r] = v + baff;
             }
     }
+    if constexpr (AD) {
+        if (part == 0)
+            for (int i = tid; i < G * (a.R - Rc); i += 256) a.scores[(size_t)(img * G + i / (a.R - Rc)) * a.R + Rc + i % (a.R - Rc)] = 0.f;
+    }
 }
 
 // Training-mode form of the grouped kernel, for the multi-sample SCST rollout (Butd::sample_n: the G = K sampled rows of an image,
 // row = img * G + k): attention dropout per row (the row's own keep-bits, indexed as att_scores_kernel indexes them) and the
 // early-out flag.  Same arithmetic and summation order per row as att_scores_kernel with the same DropCfg.  Grid (n_img, parts).
+template <bool AD>
 __global__ __launch_bounds__(256) void att_scores_group_train_kernel(AttScoreArgs a, DropCfg dc, int G) {
     extern __shared__ __attribute__((aligned(16))) float sdec[];   // [G][A]
     const int lflag = live_flag(a.live);
     const int img = blockIdx.x, part = blockIdx.y, nparts = gridDim.y;
+    const int Rc = (AD && a.counts) ? a.counts[img] : a.R;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t MN = (size_t)a.rows * a.A;
     if (flag_dead(lflag)) return;
@@ -475,7 +513,7 @@ __global__ __launch_bounds__(256) void att_scores_group_train_kernel(AttScoreArg
     __syncthreads();
     const float baff = a.b_aff[0];
     const float sc = dc.mode ? 2.0f : 1.0f;
-    for (int i0 = wave; part + nparts * i0 < a.R; i0 += 4) {
+    for (int i0 = wave; part + nparts * i0 < Rc; i0 += 4) {
         const int r = part + nparts * i0;
         const float* e = a.enc_ctx + ((size_t)img * a.R + r) * a.A;
         float acc[ATT_CTX_MAX_G];
@@ -513,6 +551,10 @@ __global__ __launch_bounds__(256) void att_scores_group_train_kernel(AttScoreArg
                 if (lane == 0) a.scores[(size_t)(img * G + g) * a.R + r] = v + baff;
             }
     }
+    if constexpr (AD) {
+        if (part == 0)
+            for (int i = tid; i < G * (a.R - Rc); i += 256) a.scores[(size_t)(img * G + i / (a.R - Rc)) * a.R + Rc + i % (a.R - Rc)] = 0.f;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -520,11 +562,14 @@ __global__ __launch_bounds__(256) void att_scores_group_train_kernel(AttScoreArg
 //   alpha = softmax_r(score[row,:]);  ctx[row, d] = sum_r alpha[r] * feats[img, r, d]
 // Grid (rows, D/512), 256 threads: thread (half, cg) sums one half of the regions for 4 consecutive d (16-byte loads,
 // 9 in flight per thread); the two halves meet in LDS.  Every wave recomputes the R <= 64 softmax (lane r holds score r).
+// <true> (see AttScoreArgs): the halves are cut at (c + 1) / 2 of the image's count c, so the row sums as it would at R = c.
+template <bool AD>
 __global__ __launch_bounds__(256) void att_ctx_kernel(const float* __restrict__ feats, const int32_t* __restrict__ img_of_row,
                                                       const float* __restrict__ scores, float* __restrict__ alpha_out,
                                                       float* __restrict__ alpha_out2, int alpha2_stride,
-                                                      float* __restrict__ ctx, int R, int D, const int* __restrict__ live) {
-    __shared__ float sal[64];
+                                                      float* __restrict__ ctx, int R, int D, const int* __restrict__ live,
+                                                      const int32_t* __restrict__ counts) {
+    __shared__ float sal[AD ? ATT_MAX_R : 64];
     __shared__ __attribute__((aligned(16))) float spart[128 * 4];
     const int lflag = live_flag(live);
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -532,8 +577,9 @@ __global__ __launch_bounds__(256) void att_ctx_kernel(const float* __restrict__ 
     const int d = blockIdx.y * 512 + cg * 4;
     const bool valid = d < D;
     const int img = img_of_row ? img_of_row[row] : row;
-    const int Rh = (R + 1) / 2;
-    const int r_lo = half ? Rh : 0, r_hi = half ? R : Rh;
+    const int Rc = (AD && counts) ? counts[img] : R;
+    const int Rh = (Rc + 1) / 2;
+    const int r_lo = half ? Rh : 0, r_hi = half ? Rc : Rh;
     const float* f = feats + (size_t)img * R * D + (valid ? d : 0);
     // the feature loads do not depend on the weights: the first two rounds (all of them at 36 regions) are issued before the
     // scores are read, so the softmax runs while they are in flight instead of in front of them
@@ -544,16 +590,37 @@ __global__ __launch_bounds__(256) void att_ctx_kernel(const float* __restrict__ 
 #pragma unroll
     for (int u = 0; u < RB; ++u) x1[u] = *reinterpret_cast<const f32x4*>(f + (size_t)min(r_lo + RB + u, r_hi - 1) * D);
     if (flag_dead(lflag)) return;                 // behind the first loads, in front of the first write (icz_common.h)
-    const float scv = lane < R ? scores[(size_t)row * R + lane] : -INFINITY;
-    const float mx = wave_max(scv);
-    const float ex = lane < R ? expf(scv - mx) : 0.f;
-    const float sum = wave_sum(ex);
-    const float al = ex / sum;
-    if (tid < 64) {
-        sal[tid] = al;
-        if (blockIdx.y == 0 && tid < R) {
-            alpha_out[(size_t)row * R + tid] = al;
-            if (alpha_out2) alpha_out2[(size_t)row * alpha2_stride + tid] = al;
+    if constexpr (AD) {          // two regions per lane; the weights of r >= c are exact zeros, and are written as such
+        const float scv = lane < Rc ? scores[(size_t)row * R + lane] : -INFINITY;
+        const float scw = lane + 64 < Rc ? scores[(size_t)row * R + lane + 64] : -INFINITY;
+        const float mx = wave_max(fmaxf(scv, scw));
+        const float ex = lane < Rc ? expf(scv - mx) : 0.f;
+        const float ew = lane + 64 < Rc ? expf(scw - mx) : 0.f;
+        const float sum = wave_sum(ex + ew);
+        const float al[2] = {ex / sum, ew / sum};
+        if (tid < 64) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int r = tid + 64 * q;
+                sal[r] = al[q];
+                if (blockIdx.y == 0 && r < R) {
+                    alpha_out[(size_t)row * R + r] = al[q];
+                    if (alpha_out2) alpha_out2[(size_t)row * alpha2_stride + r] = al[q];
+                }
+            }
+        }
+    } else {
+        const float scv = lane < R ? scores[(size_t)row * R + lane] : -INFINITY;
+        const float mx = wave_max(scv);
+        const float ex = lane < R ? expf(scv - mx) : 0.f;
+        const float sum = wave_sum(ex);
+        const float al = ex / sum;
+        if (tid < 64) {
+            sal[tid] = al;
+            if (blockIdx.y == 0 && tid < R) {
+                alpha_out[(size_t)row * R + tid] = al;
+                if (alpha_out2) alpha_out2[(size_t)row * alpha2_stride + tid] = al;
+            }
         }
     }
     __syncthreads();
@@ -583,29 +650,47 @@ __global__ __launch_bounds__(256) void att_ctx_kernel(const float* __restrict__ 
 // features: one workgroup does the G rows of one image for its 512 columns, so every feature vector is fetched once
 // instead of G times (at 640 rows the per-row kernel moves 189 MB through the caches per step).  Same arithmetic and
 // summation order per row as att_ctx_kernel.  Grid (n_img, D/512).  `live`: the multi-sample rollout's early-out (null for beam search).
+template <bool AD>
 __global__ __launch_bounds__(256) void att_ctx_group_kernel(const float* __restrict__ feats, const float* __restrict__ scores,
                                                             float* __restrict__ alpha_out, float* __restrict__ ctx, int R, int D, int G,
-                                                            const int* __restrict__ live) {
-    __shared__ float sal[ATT_CTX_MAX_G][64];
+                                                            const int* __restrict__ live, const int32_t* __restrict__ counts) {
+    __shared__ float sal[ATT_CTX_MAX_G][AD ? ATT_MAX_R : 64];
     __shared__ __attribute__((aligned(16))) float spart[ATT_CTX_MAX_G][128 * 4];
     if (step_dead(live)) return;
     const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int Rc = (AD && counts) ? counts[img] : R;
     for (int g = wave; g < G; g += 4) {                 // wave w: softmax of rows w, w + 4
         const int row = img * G + g;
-        const float scv = lane < R ? scores[(size_t)row * R + lane] : -INFINITY;
-        const float mx = wave_max(scv);
-        const float ex = lane < R ? expf(scv - mx) : 0.f;
-        const float sum = wave_sum(ex);
-        const float al = ex / sum;
-        sal[g][lane] = al;
-        if (blockIdx.y == 0 && lane < R) alpha_out[(size_t)row * R + lane] = al;
+        if constexpr (AD) {      // two regions per lane, as in att_ctx_kernel<true>
+            const float scv = lane < Rc ? scores[(size_t)row * R + lane] : -INFINITY;
+            const float scw = lane + 64 < Rc ? scores[(size_t)row * R + lane + 64] : -INFINITY;
+            const float mx = wave_max(fmaxf(scv, scw));
+            const float ex = lane < Rc ? expf(scv - mx) : 0.f;
+            const float ew = lane + 64 < Rc ? expf(scw - mx) : 0.f;
+            const float sum = wave_sum(ex + ew);
+            const float al[2] = {ex / sum, ew / sum};
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int r = lane + 64 * q;
+                sal[g][r] = al[q];
+                if (blockIdx.y == 0 && r < R) alpha_out[(size_t)row * R + r] = al[q];
+            }
+        } else {
+            const float scv = lane < R ? scores[(size_t)row * R + lane] : -INFINITY;
+            const float mx = wave_max(scv);
+            const float ex = lane < R ? expf(scv - mx) : 0.f;
+            const float sum = wave_sum(ex);
+            const float al = ex / sum;
+            sal[g][lane] = al;
+            if (blockIdx.y == 0 && lane < R) alpha_out[(size_t)row * R + lane] = al;
+        }
     }
     __syncthreads();
     const int cg = tid & 127, half = tid >> 7;
     const int d = blockIdx.y * 512 + cg * 4;
     const bool valid = d < D;
-    const int Rh = (R + 1) / 2;
-    const int r_lo = half ? Rh : 0, r_hi = half ? R : Rh;
+    const int Rh = (Rc + 1) / 2;
+    const int r_lo = half ? Rh : 0, r_hi = half ? Rc : Rh;
     const float* f = feats + (size_t)img * R * D + (valid ? d : 0);
     f32x4 acc[ATT_CTX_MAX_G];
 #pragma unroll
@@ -1432,10 +1517,13 @@ __global__ __launch_bounds__(256) void lstm_bwd_point_kernel(LstmBwdArgs a, Drop
 // those columns for all regions; att_bwd_ddec_kernel adds the parts in order.  Wave w takes regions w, w + 4, ...: two 16-byte
 // feature loads per lane and region, all of a wave's loads independent.
 constexpr int DALPHA_COLS = 512;
+// <true> (see AttScoreArgs): the passes stop at the image's count; dalpha_part at r >= c is neither written nor read.
+template <bool AD>
 __global__ __launch_bounds__(256) void att_bwd_dalpha_kernel(const float* __restrict__ dctx, int ns, int ldc, int rows,
                                                              const float* __restrict__ feats, int R, int D,
                                                              float* __restrict__ dalpha_part, const int* __restrict__ live,
-                                                             const int32_t* __restrict__ img_of_row) {     // null = identity
+                                                             const int32_t* __restrict__ img_of_row,       // null = identity
+                                                             const int32_t* __restrict__ counts) {
     __shared__ __attribute__((aligned(16))) float sd[DALPHA_COLS];
     const int lflag = live_flag(live);
     const int row = blockIdx.x, part = blockIdx.y, nparts = gridDim.y;
@@ -1445,12 +1533,14 @@ __global__ __launch_bounds__(256) void att_bwd_dalpha_kernel(const float* __rest
     constexpr int NR = 5;                         // regions per wave and pass (R <= 64: at most 16 per wave)
     const int ca = c0 + 4 * lane, cb = ca + 256;
     const bool va = ca < D, vb = cb < D;
-    const float* frow = feats + (size_t)(img_of_row ? img_of_row[row] : row) * R * D;
+    const int img = img_of_row ? img_of_row[row] : row;
+    const int Rc = (AD && counts) ? counts[img] : R;
+    const float* frow = feats + (size_t)img * R * D;
     f32x4 xa[NR], xb[NR];
     auto load_pass = [&](int r0) {                // clamped: a pass past the last region re-reads it and is not stored
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
-            const int r = min(r0 + 4 * u, R - 1);
+            const int r = min(r0 + 4 * u, Rc - 1);
             xa[u] = *reinterpret_cast<const f32x4*>(frow + (size_t)r * D + (va ? ca : 0));
             xb[u] = *reinterpret_cast<const f32x4*>(frow + (size_t)r * D + (vb ? cb : 0));
         }
@@ -1465,7 +1555,7 @@ __global__ __launch_bounds__(256) void att_bwd_dalpha_kernel(const float* __rest
     }
     __syncthreads();
     const f32x4 ga = *reinterpret_cast<const f32x4*>(sd + 4 * lane), gb = *reinterpret_cast<const f32x4*>(sd + 256 + 4 * lane);
-    for (int r0 = wave; r0 < R; r0 += 4 * NR) {
+    for (int r0 = wave; r0 < Rc; r0 += 4 * NR) {
         if (r0 != wave) load_pass(r0);
 #pragma unroll
         for (int u = 0; u < NR; ++u) {
@@ -1474,7 +1564,7 @@ __global__ __launch_bounds__(256) void att_bwd_dalpha_kernel(const float* __rest
             if (vb) acc += xb[u][0] * gb[0] + xb[u][1] * gb[1] + xb[u][2] * gb[2] + xb[u][3] * gb[3];
             acc = wave_sum(acc);
             const int r = r0 + 4 * u;
-            if (lane == 0 && r < R) dalpha_part[((size_t)row * nparts + part) * R + r] = acc;
+            if (lane == 0 && r < Rc) dalpha_part[((size_t)row * nparts + part) * R + r] = acc;
         }
     }
 }
@@ -1487,15 +1577,26 @@ struct AttBwdDdecArgs {
     int R, A, nparts;
     const int* live;              // step_dead(live): ddec and ds rows of this step are ZERO (read by the GEMMs / kernels over all steps)
     const int32_t* img_of_row;    // image of each row (enc_ctx row); null = identity
+    const int32_t* counts;        // <true> only: valid leading regions per image (null = all R)
 };
+// <true> (see AttScoreArgs): alpha, dalpha and ds of regions lane and lane + 64; ds at r >= c is written as zero.
+template <bool AD>
 __global__ __launch_bounds__(256) void att_bwd_ddec_kernel(AttBwdDdecArgs a, DropCfg dc) {
-    __shared__ float sds[64];
+    __shared__ float sds[AD ? ATT_MAX_R : 64];
     __shared__ __attribute__((aligned(16))) float spart[3 * 64 * 4];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wq = tid >> 6;
     const int lflag = live_flag(a.live);
     const int img = a.img_of_row ? a.img_of_row[row] : row;
-    const float al = lane < a.R ? a.alpha[(size_t)row * a.R + lane] : 0.f;
-    const float da0 = lane < a.R ? a.dalpha[(size_t)row * a.nparts * a.R + lane] : 0.f;
+    const int Rc = (AD && a.counts) ? a.counts[img] : a.R;
+    const float al = lane < Rc ? a.alpha[(size_t)row * a.R + lane] : 0.f;
+    const float da0 = lane < Rc ? a.dalpha[(size_t)row * a.nparts * a.R + lane] : 0.f;
+    float al2 = 0.f, da2 = 0.f;                   // <true>: region lane + 64
+    if constexpr (AD) {
+        if (lane + 64 < Rc) {
+            al2 = a.alpha[(size_t)row * a.R + lane + 64];
+            da2 = a.dalpha[(size_t)row * a.nparts * a.R + lane + 64];
+        }
+    }
     if (flag_dead(lflag)) {                       // behind the first loads (icz_common.h); a dead step's d dec / ds rows are zeros
         if (blockIdx.y == 0 && tid < a.R) a.ds_out[(size_t)row * a.R + tid] = 0.f;
         const int c = blockIdx.y * 256 + tid;
@@ -1503,13 +1604,39 @@ __global__ __launch_bounds__(256) void att_bwd_ddec_kernel(AttBwdDdecArgs a, Dro
         return;
     }
     float da = da0;
-    if (lane < a.R)
+    if (lane < Rc)
         for (int p = 1; p < a.nparts; ++p) da += a.dalpha[((size_t)row * a.nparts + p) * a.R + lane];
-    const float dot = wave_sum(al * da);
-    const float ds_l = al * (da - dot);
-    if (tid < 64) {
-        sds[tid] = ds_l;
-        if (blockIdx.y == 0 && tid < a.R) a.ds_out[(size_t)row * a.R + tid] = ds_l;
+    if constexpr (AD) {
+        if (lane + 64 < Rc)
+            for (int p = 1; p < a.nparts; ++p) da2 += a.dalpha[((size_t)row * a.nparts + p) * a.R + lane + 64];
+        // Up to 64 regions the sum must come out as the fixed-set instance's wave_sum(al * da) does, bit for bit.  There the compiler
+        // fuses the product into the reduction's first add (v_fmac on the shuffled rounded product); spelled out here, because next to
+        // the two-region form it would share one rounded product between the branches and add it unfused (one ulp apart; seen in the
+        // saved assembly and on the device).  tests/test_gpu_butd_adaptive.py holds the two instances together.  Rc is uniform.
+        float dot;
+        if (Rc <= 64) {
+            dot = __builtin_fmaf(al, da, __shfl_xor(al * da, 32, 64));
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+        } else {
+            dot = wave_sum(al * da + al2 * da2);
+        }
+        const float ds_l[2] = {al * (da - dot), al2 * (da2 - dot)};
+        if (tid < 64) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int r = tid + 64 * q;
+                sds[r] = ds_l[q];
+                if (blockIdx.y == 0 && r < a.R) a.ds_out[(size_t)row * a.R + r] = r < Rc ? ds_l[q] : 0.f;
+            }
+        }
+    } else {
+        const float dot = wave_sum(al * da);
+        const float ds_l = al * (da - dot);
+        if (tid < 64) {
+            sds[tid] = ds_l;
+            if (blockIdx.y == 0 && tid < a.R) a.ds_out[(size_t)row * a.R + tid] = ds_l;
+        }
     }
     __syncthreads();
     const int c = blockIdx.y * 256 + lane * 4;
@@ -1521,18 +1648,18 @@ __global__ __launch_bounds__(256) void att_bwd_ddec_kernel(AttBwdDdecArgs a, Dro
         const float sc = dc.mode ? 2.0f : 1.0f;
         constexpr int RB = 9;
         const bool shared_bits = dc.mode == 2 && (a.A & 255) == 0;      // every lane of the wave is valid and takes every iteration
-        for (int r0 = wq; r0 < a.R; r0 += 4 * RB) {
+        for (int r0 = wq; r0 < Rc; r0 += 4 * RB) {
             f32x4 x[RB];
 #pragma unroll
             for (int u = 0; u < RB; ++u) {
-                const int r = min(r0 + 4 * u, a.R - 1);
+                const int r = min(r0 + 4 * u, Rc - 1);
                 x[u] = *reinterpret_cast<const f32x4*>(a.enc_ctx + ((size_t)img * a.R + r) * a.A + c);
             }
             // Philox keep-bits, shared as in att_scores_kernel: lane 2 u + half computes the block of region u's half-strip
             uint32_t kq[RB];
             if (shared_bits) {
                 const int pu = min(lane >> 1, RB - 1), ph = lane & 1;
-                const int pr = min(r0 + 4 * pu, a.R - 1);
+                const int pr = min(r0 + 4 * pu, Rc - 1);
                 const uint64_t g = (((uint64_t)row * a.R + pr) * a.A + blockIdx.y * 256 + 128 * ph) >> 7;
                 const uint64_t seed = *dc.seed_p;
                 uint4_ ctr = {(uint32_t)g, (uint32_t)(g >> 32), dc.step, dc.stream};
@@ -1549,7 +1676,7 @@ __global__ __launch_bounds__(256) void att_bwd_ddec_kernel(AttBwdDdecArgs a, Dro
 #pragma unroll
             for (int u = 0; u < RB; ++u) {
                 const int r = r0 + 4 * u;
-                if (r < a.R) {
+                if (r < Rc) {
                     const float ds = sds[r];
                     const uint32_t k = shared_bits ? kq[u] : (dc.mode ? dc.keep4(((uint64_t)row * a.R + r) * a.A + c) : 0xFu);
 #pragma unroll
@@ -1581,8 +1708,11 @@ struct AttBwdDencArgs {
     int mode; const uint8_t* mask; size_t mask_step; const uint64_t* seed_p; uint32_t stream;
     int Bs;          // rows per time step in dec_all / ds_all (0 = B; a merged chain stores 2 B, the pointers then start at its second half)
     const int32_t* img_of_row;   // image of each row (enc_ctx row); null = identity.  denc, the masks and the Philox index stay per row
+    const int32_t* counts;       // <.., true> only: valid leading regions per image (null = all R)
 };
-template <int TT>
+// <TT, true> (see AttScoreArgs): the region walk stops at the image's count; d enc_ctx rows at r >= c are written as zeros (the
+// enc_att weight-gradient GEMM and the bias sum run over all B R rows).
+template <int TT, bool AD = false>
 __global__ __launch_bounds__(256) void att_bwd_denc_kernel(AttBwdDencArgs a) {
     static_assert(TT <= 32, "one half-wave computes the TT Philox words of its 128-column group");
     extern __shared__ __attribute__((aligned(16))) float sds_t[];     // [T][R] ds of this row
@@ -1594,6 +1724,7 @@ __global__ __launch_bounds__(256) void att_bwd_denc_kernel(AttBwdDencArgs a) {
     const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, hl = lane & 31;
     const int Bst = a.Bs > 0 ? a.Bs : a.B;
     const int img = a.img_of_row ? a.img_of_row[row] : row;
+    const int Rc = (AD && a.counts) ? a.counts[img] : a.R;
     for (int i = tid; i < a.T * a.R; i += 256) {
         const int t = i / a.R, r = i % a.R;
         sds_t[i] = a.ds_all[((size_t)t * Bst + row) * a.R + r];
@@ -1615,6 +1746,10 @@ __global__ __launch_bounds__(256) void att_bwd_denc_kernel(AttBwdDencArgs a) {
             }
             for (int r = part; r < a.R; r += nparts) {
                 const size_t eoff = ((size_t)row * a.R + r) * a.A + c;
+                if (AD && r >= Rc) {            // pad rows (uniform over the workgroup): zeros, once
+                    if (cv && t0 == 0) *reinterpret_cast<f32x4*>(a.denc + eoff) = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    continue;
+                }
                 if (shared_bits) {
                     __syncthreads();            // the previous region's words have been read
                     if (cv && hl < TT && t0 + hl < a.T) {
@@ -1667,7 +1802,8 @@ __global__ __launch_bounds__(256) void att_bwd_denc_kernel(AttBwdDencArgs a) {
 // into denc[img] (the per-row route, att_bwd_denc_kernel + rowgroup_sum_kernel, gets the same sums).  dwaff_part[img, part] = the
 // rows' partials added in k order.  Grid (n_img, parts) with parts * DENC_GROUP_REGS >= R; a.B = rows, a.img_of_row unused.
 constexpr int DENC_GROUP_REGS = 16;
-template <int TT>
+// <TT, true> (see AttScoreArgs): regions at or behind the image's count are neither loaded nor walked; their d enc_ctx rows are zeros.
+template <int TT, bool AD = false>
 __global__ __launch_bounds__(256) void att_bwd_denc_group_kernel(AttBwdDencArgs a, int G) {
     static_assert(TT <= 32, "one half-wave computes the TT Philox words of its 128-column group");
     extern __shared__ __attribute__((aligned(16))) float sds_t[];     // [T][R] ds of the current row
@@ -1675,6 +1811,7 @@ __global__ __launch_bounds__(256) void att_bwd_denc_group_kernel(AttBwdDencArgs 
     const int img = blockIdx.x, part = blockIdx.y, nparts = gridDim.y, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, hl = lane & 31;
     const int Bst = a.Bs > 0 ? a.Bs : a.B;
+    const int Rc = (AD && a.counts) ? a.counts[img] : a.R;
     const float sc = a.mode ? 2.0f : 1.0f;
     const bool shared_bits = a.mode == 2 && (a.A & 127) == 0;
     for (int c0 = 0; c0 < a.A; c0 += 1024) {          // uniform over the workgroup (barriers inside)
@@ -1685,7 +1822,7 @@ __global__ __launch_bounds__(256) void att_bwd_denc_group_kernel(AttBwdDencArgs 
 #pragma unroll
         for (int i = 0; i < DENC_GROUP_REGS; ++i) {
             const int r = part + i * nparts;
-            x[i] = (cv && r < a.R) ? *reinterpret_cast<const f32x4*>(a.enc_ctx + ((size_t)img * a.R + r) * a.A + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+            x[i] = (cv && r < Rc) ? *reinterpret_cast<const f32x4*>(a.enc_ctx + ((size_t)img * a.R + r) * a.A + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
         }
         f32x4 dwsum = {0.f, 0.f, 0.f, 0.f};
         for (int k = 0; k < G; ++k) {
@@ -1710,7 +1847,7 @@ __global__ __launch_bounds__(256) void att_bwd_denc_group_kernel(AttBwdDencArgs 
 #pragma unroll
                 for (int i = 0; i < DENC_GROUP_REGS; ++i) {
                     const int r = part + i * nparts;
-                    if (r >= a.R) break;                // uniform
+                    if (r >= Rc) break;                 // uniform
                     const size_t eoff = ((size_t)row * a.R + r) * a.A + c;      // the row's element: mask / Philox index
                     if (shared_bits) {
                         __syncthreads();

@@ -121,7 +121,7 @@ static DropCfg make_drop(const uint64_t* seed_p, bool train, const uint8_t* base
 // row0 > 0: the merged chain -- rows [0, row0) are evaluation-mode rows, the dropout arrays / Philox indices belong to the Bs - row0 rows behind
 int Butd::train_step(const float* feats, int rows, int Bs, int t, bool train, hipStream_t st, bool emb_ready, int* pred_nsplit, bool skip_predict,
                      const int* live, int row0) {
-    const size_t H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = dims.R;
+    const size_t H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = cur_R;
     const size_t Vp = pad_vocab(dims.V);
     const size_t slot = (size_t)t * Bs;
     StepIO s = {};
@@ -155,6 +155,7 @@ int Butd::train_step(const float* feats, int rows, int Bs, int t, bool train, hi
 int Butd::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st) {
     ICZ_REQUIRE(feats && seq_out && logp_out && r, "butd sample: null argument");
     ICZ_REQUIRE(B > 0 && T > 0, "butd sample: bad B/T");
+    ICZ_TRY(check_counts(B));
     ICZ_REQUIRE(fresh, "butd: call icz_butd_refresh_weights after binding/updating parameters");
     ICZ_TRY(ensure_train(B, T));
     rng = *r;
@@ -164,7 +165,7 @@ int Butd::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* se
     rows_t.assign(T, B);
     cur_seq = seq_out; cur_logp = logp_out;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
-    if (explicit_rng || !use_graphs) return sample_impl(feats, B, T, seq_out, logp_out, st);
+    if (explicit_rng || !graphs_on()) return sample_impl(feats, B, T, seq_out, logp_out, st);
     const std::vector<uintptr_t> key = {2, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)T, (uintptr_t)seq_out, (uintptr_t)logp_out, opt_bits()};
     return gc.run(key, st, [&](hipStream_t s) { return sample_impl(feats, B, T, seq_out, logp_out, s); });
 }
@@ -183,6 +184,7 @@ int Butd::sample_n(const float* feats, int B, int K, int T, const icz_rng* r, in
     ICZ_REQUIRE(feats && seq_out && logp_out && r, "butd sample_n: null argument");
     ICZ_REQUIRE(K >= 2 && K <= ATT_CTX_MAX_G, "butd sample_n: K=%d samples per image outside 2..%d", K, ATT_CTX_MAX_G);
     ICZ_REQUIRE(B > 0 && T > 0, "butd sample_n: bad B/T");
+    ICZ_TRY(check_counts(B));
     ICZ_REQUIRE((int64_t)B * K <= dims.max_rows, "butd sample_n: %d images x %d samples exceed the row capacity %d", B, K, dims.max_rows);
     ICZ_REQUIRE(fresh, "butd: call icz_butd_refresh_weights after binding/updating parameters");
     const int rows = B * K;
@@ -194,7 +196,7 @@ int Butd::sample_n(const float* feats, int B, int K, int T, const icz_rng* r, in
     rows_t.assign(T, rows);
     cur_seq = seq_out; cur_logp = logp_out;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
-    if (explicit_rng || !use_graphs) return sample_n_impl(feats, B, K, T, seq_out, logp_out, st);
+    if (explicit_rng || !graphs_on()) return sample_n_impl(feats, B, K, T, seq_out, logp_out, st);
     const std::vector<uintptr_t> key = {5, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)K, (uintptr_t)T, (uintptr_t)seq_out, (uintptr_t)logp_out, opt_bits()};
     return gc.run(key, st, [&](hipStream_t s) { return sample_n_impl(feats, B, K, T, seq_out, logp_out, s); });
 }
@@ -213,6 +215,7 @@ int Butd::rollouts(const float* feats, int B, int T, const icz_rng* r, int64_t* 
                    hipStream_t st) {
     ICZ_REQUIRE(feats && ids_out && seq_out && logp_out && r, "butd rollouts: null argument");
     ICZ_REQUIRE(B > 0 && T > 0 && B <= dims.max_rows, "butd rollouts: bad B/T");
+    ICZ_TRY(check_counts(B));
     ICZ_REQUIRE(fresh, "butd: call icz_butd_refresh_weights after binding/updating parameters");
     // <= 32 images: ONE chain of 2 B decoder rows (sample_chain with row0 = B) instead of two chains that each stream the weights
     const bool merged = B <= merge_small;
@@ -225,7 +228,7 @@ int Butd::rollouts(const float* feats, int B, int T, const icz_rng* r, int64_t* 
     rows_t.assign(T, B);
     cur_seq = seq_out; cur_logp = logp_out;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
-    if (explicit_rng || !use_graphs) return rollouts_impl(feats, B, T, ids_out, seq_out, logp_out, st);
+    if (explicit_rng || !graphs_on()) return rollouts_impl(feats, B, T, ids_out, seq_out, logp_out, st);
     const std::vector<uintptr_t> key = {4, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)T, (uintptr_t)ids_out, (uintptr_t)seq_out, (uintptr_t)logp_out, opt_bits()};
     return gc.run(key, st, [&](hipStream_t s) { return rollouts_impl(feats, B, T, ids_out, seq_out, logp_out, s); });
 }
@@ -325,7 +328,7 @@ int Butd::sample_backward(const float* reward, const icz_butd_params* G, float* 
     bptt_early_out = true;
     ICZ_TRY(bptt_prelude(st));      // outside the captured graph
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
-    if (explicit_rng || !use_graphs) return sample_backward_impl(reward, *G, loss_out, mask_sum_out, st);
+    if (explicit_rng || !graphs_on()) return sample_backward_impl(reward, *G, loss_out, mask_sum_out, st);
     std::vector<uintptr_t> key = {3, (uintptr_t)reward, (uintptr_t)loss_out, (uintptr_t)mask_sum_out, (uintptr_t)cur_B, (uintptr_t)cur_T,
                                   (uintptr_t)cur_feats, (uintptr_t)cur_seq, (uintptr_t)cur_logp,
                                   (uintptr_t)cur_rows, (uintptr_t)cur_row0,       // merged / unmerged rollouts share the caller's buffers: slot strides differ
@@ -360,6 +363,7 @@ int Butd::sample_backward_impl(const float* reward, const icz_butd_params& G, fl
 int Butd::xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r,
                      int train, float* packed_out, hipStream_t st) {
     ICZ_REQUIRE(feats && captions && lengths && B > 0 && L > 1, "butd xe_forward: bad arguments");
+    ICZ_TRY(check_counts(B));
     int T = 0;
     ICZ_TRY(xe_steps("butd", lengths, B, L, &T));
     ICZ_TRY(ensure_train(B, T));
@@ -563,7 +567,8 @@ int Butd::bptt_predict(BpttCall& c) {
 // ---- the reverse-time loop: per step the pointwise LSTM / attention backward kernels and the dgrad products between them
 int Butd::bptt_loop(BpttCall& c) {
     const int B = c.B, T = c.T, Bs = c.Bs, roff = c.roff;
-    const int H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = dims.R;
+    const int H = dims.H, D = dims.D, E = dims.E, A = dims.A, R = cur_R;
+    const bool ad = adaptive();
     const size_t sH = (size_t)Bs * H;
     const float* const feats = cur_feats;
     const int32_t* const imgk = c.imgk;
@@ -618,9 +623,10 @@ int Butd::bptt_loop(BpttCall& c) {
         ICZ_TRY(dgrad(gemm_args({wseg(dglm, wt_lm_ih, P.lm_w_ih, D + H)}, bt, D + H, tb.X[0], D + H, live), tb.X[0], &ns1));
         {   // attention backward
             const int dparts = cdiv(D, DALPHA_COLS);
-            hipLaunchKernelGGL(att_bwd_dalpha_kernel, dim3(bt, dparts), dim3(256), 0, st, tb.X[0], ns1, D + H, bt, feats, R, D, tb.dalpha, live, imgk);
-            AttBwdDdecArgs da = {enc_ctx, tb.dec + slot * A, w_aff, tb.alpha + slot * R, tb.dalpha, tb.dDec + slot * A, tb.dS + slot * R, R, A, dparts, live, imgk};
-            hipLaunchKernelGGL(att_bwd_ddec_kernel, dim3(bt, cdiv(A, 256)), dim3(256), 0, st, da, d_att);
+            hipLaunchKernelGGL(ad ? att_bwd_dalpha_kernel<true> : att_bwd_dalpha_kernel<false>, dim3(bt, dparts), dim3(256), 0, st, tb.X[0], ns1, D + H, bt,
+                               feats, R, D, tb.dalpha, live, imgk, cnt);
+            AttBwdDdecArgs da = {enc_ctx, tb.dec + slot * A, w_aff, tb.alpha + slot * R, tb.dalpha, tb.dDec + slot * A, tb.dS + slot * R, R, A, dparts, live, imgk, cnt};
+            hipLaunchKernelGGL(ad ? att_bwd_ddec_kernel<true> : att_bwd_ddec_kernel<false>, dim3(bt, cdiv(A, 256)), dim3(256), 0, st, da, d_att);
             // X2 = dDec . w_dec   [bt, H]
             GemmArgs g = gemm_args({{tb.dDec + slot * A, w_dec, A, H, A}}, bt, H, tb.X[1], H, live);
             ICZ_TRY(gemm_auto(GEMM_NN, g, tb.X[1], tb.xfloats, &ns2, st));
@@ -711,7 +717,11 @@ int Butd::bptt_lm_wgrad(BpttCall& c) {
 //      below `predict` and weight-norm backward of the block's three layers
 int Butd::bptt_attention_tail(BpttCall& c) {
     const int B = c.B, T = c.T, Bs = c.Bs, roff = c.roff, TB = c.TB, K = c.K, n_img = c.n_img;
-    const int H = dims.H, D = dims.D, A = dims.A, R = dims.R;
+    const int H = dims.H, D = dims.D, A = dims.A, R = cur_R;
+    const bool ad = adaptive();
+    // parts of the grouped d enc_ctx kernel: DENC_GROUP_REGS regions each (more than ATT_PARTS only above 64 regions; n_img <= B / 2
+    // images there, so tb.dwaff's B x ATT_PARTS blocks still hold them)
+    const int gparts = ATT_PARTS * DENC_GROUP_REGS >= R ? ATT_PARTS : cdiv(R, DENC_GROUP_REGS);
     const size_t sH = (size_t)Bs * H;
     const icz_butd_params& G = c.G;
     const float* const feats = cur_feats;
@@ -720,12 +730,13 @@ int Butd::bptt_attention_tail(BpttCall& c) {
     ICZ_TRY(wgrad(tb.dDec, A, A, tb.h1 + sH, H, H, TB, tb.dWdec, H, st));
     {   // d enc_ctx (sum over time) and the affine-weight partials, from the ds_t recorded by the loop
         AttBwdDencArgs ea = {enc_ctx, tb.dec + (size_t)roff * A, tb.dS + (size_t)roff * R, w_aff, tb.dEnc, tb.dwaff, B, R, A, T,
-                             cur_train ? (rng.att_mask ? 1 : 2) : 0, rng.att_mask, (size_t)B * R * A, d_seed, (uint32_t)RNG_ATT, Bs, imgk};
+                             cur_train ? (rng.att_mask ? 1 : 2) : 0, rng.att_mask, (size_t)B * R * A, d_seed, (uint32_t)RNG_ATT, Bs, imgk, cnt};
         if (K > 1 && group_att) {       // sample_n, grouped: the K rows of an image in one workgroup, summed into d enc_ctx[img]
             ea.denc = tb.dEncImg;
-            hipLaunchKernelGGL(att_bwd_denc_group_kernel<20>, dim3(n_img, ATT_PARTS), dim3(256), sizeof(float) * T * R, st, ea, K);
+            hipLaunchKernelGGL((ad ? att_bwd_denc_group_kernel<20, true> : att_bwd_denc_group_kernel<20, false>), dim3(n_img, gparts), dim3(256),
+                               sizeof(float) * T * R, st, ea, K);
         } else {
-            hipLaunchKernelGGL(att_bwd_denc_kernel<20>, dim3(B, ATT_PARTS), dim3(256), sizeof(float) * T * R, st, ea);
+            hipLaunchKernelGGL((ad ? att_bwd_denc_kernel<20, true> : att_bwd_denc_kernel<20, false>), dim3(B, ATT_PARTS), dim3(256), sizeof(float) * T * R, st, ea);
             if (K > 1) {                // sample_n, per row: d enc_ctx of the B K rows, then the K rows of an image added in k order
                 const size_t N = (size_t)R * A;
                 hipLaunchKernelGGL(rowgroup_sum_kernel, dim3(cdiv((int)((size_t)n_img * N / 4), 256)), dim3(256), 0, st, (const float*)tb.dEnc,
@@ -735,7 +746,7 @@ int Butd::bptt_attention_tail(BpttCall& c) {
     }
     const float* const denc = K > 1 ? tb.dEncImg : tb.dEnc;
     // d affine partials: one [parts, A] block per decoder row, or per image behind the grouped kernel
-    const int waff_rows = (K > 1 && group_att ? n_img : B) * ATT_PARTS;
+    const int waff_rows = K > 1 && group_att ? n_img * gparts : B * ATT_PARTS;
     ICZ_TRY(wgrad(denc, A, A, feats, D, D, n_img * R, tb.dWenc, D, st));
     {   // bias gradients: five column sums (+ the b_hh copies, + the identically zero affine bias: softmax shift invariance) in one launch
         ColsumTable ct = {};
@@ -811,8 +822,8 @@ int icz_butd_saved_alphas(icz_butd_t* h, float* alphas_out, void* stream) {
     Butd* b = reinterpret_cast<Butd*>(h);
     ICZ_REQUIRE(b->mode != 0 && b->tb.alpha, "icz_butd_saved_alphas: no forward pass stored");
     ICZ_REQUIRE(b->cur_row0 == 0, "icz_butd_saved_alphas: not available behind a merged SCST rollout (set option merge_small = 0)");
-    const int n = b->cur_B * b->cur_T * b->dims.R;
-    hipLaunchKernelGGL(saved_alphas_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, b->tb.alpha, b->cur_T, b->cur_B, 1, b->dims.R, alphas_out);
+    const int n = b->cur_B * b->cur_T * b->cur_R;
+    hipLaunchKernelGGL(saved_alphas_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, b->tb.alpha, b->cur_T, b->cur_B, 1, b->cur_R, alphas_out);
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }

@@ -205,15 +205,19 @@ class Engine(object):
 
 
 class BUTDDetection_Eng(Engine):
-    """ModelEngines/BUTD_Engine.py:21-47 + the three hot Engine methods on libicz."""
+    """ModelEngines/BUTD_Engine.py:21-47 + the three hot Engine methods on libicz.
+    `use_bu='adaptive'` (10..100 boxes per image, Main.py:158; beyond the reference, whose BUTD model drops the mask this engine
+    builds): the handle is sized for `num_regions` (default 100) and every batch carries its region counts."""
 
     def model_construction(self, max_batch):
         s = self.settings
         assert s["model_type"] in ("BUTDDetection", "BUTDSpatial")
-        return BUTDDetection_Captioner(atten_dim=s["atten_dim"], embed_dim=s["embed_dim"], hidden_dim=s["hidden_dim"],
-                                       vocab_size=len(self.caption_vocab), device=str(self.device),
-                                       num_regions=s.get("num_regions", 36), enc_dim=s.get("enc_dim", 2048),
-                                       max_batch=max_batch)
+        model = BUTDDetection_Captioner(atten_dim=s["atten_dim"], embed_dim=s["embed_dim"], hidden_dim=s["hidden_dim"],
+                                        vocab_size=len(self.caption_vocab), device=str(self.device),
+                                        num_regions=s.get("num_regions", 100 if self.use_bu == "adaptive" else 36), enc_dim=s.get("enc_dim", 2048),
+                                        max_batch=max_batch)
+        model.region_masks = self.use_bu == "adaptive"
+        return model
 
     # ---- E4 -------------------------------------------------------------------------------------------------
     def modify_visual_inputs(self, img_tensors, supp_info_datas=None):
@@ -1066,7 +1070,7 @@ def _check_score_entries(entries, captions_per_image):
 
 
 def _slice_feats(f, lo, hi):
-    from .aoa import RegionBatch
+    from .regions import RegionBatch
     if isinstance(f, RegionBatch):
         return RegionBatch(f.feats[lo:hi], None if f.counts is None else list(f.counts)[lo:hi])
     return f[lo:hi]

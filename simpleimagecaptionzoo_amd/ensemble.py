@@ -71,7 +71,7 @@ class EnsembleHandle:
             pass
 
     def _feats(self, feats_list):
-        """each member's features through its handle's own checks (an AoA member's RegionBatch sets its region counts) ->
+        """each member's features through its handle's own checks (a BUTD or AoA member's RegionBatch sets its region counts) ->
         (the host pointer array, the batch size)"""
         feats_list = list(feats_list)
         if len(feats_list) != len(self.handles):

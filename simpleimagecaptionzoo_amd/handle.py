@@ -45,8 +45,9 @@ class DecoderHandle:
             cls._table = table
         return table
 
-    def _create(self, dims, device):
-        """The tail of a subclass's __init__: the fields of its dims struct become attributes (R, D, ..., max_rows, max_len)."""
+    def _create(self, dims, device, entry="create"):
+        """The tail of a subclass's __init__: the fields of its dims struct become attributes (R, D, ..., max_rows, max_len).
+        entry: the family's creating entry (BUTD: "create_regions" for a region capacity above 64)."""
         for name, _ in dims._fields_:
             setattr(self, name, getattr(dims, name))
         self.device = torch.device(device)
@@ -56,7 +57,7 @@ class DecoderHandle:
         self._bufs = {}
         self._e = self._entries()
         with torch.cuda.device(self.device):
-            check(self._e.create(C.byref(dims), C.byref(self._h)))
+            check(getattr(self._e, entry)(C.byref(dims), C.byref(self._h)))
 
     def close(self):
         if self._h:
