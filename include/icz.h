@@ -584,6 +584,57 @@ int icz_ensemble_score_tokens(int32_t M, const float* const* logits, const float
                               float* logp_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Word-level knowledge distillation (beyond the reference): the XE training step of one student decoder on the word distribution of
+ * an ensemble of M = 1..4 teachers of the same vocabulary (csrc/distill.hip).  For a token row with student logits s, teacher logits
+ * z_1..z_M, normalised weights w, target c, label smoothing sigma, mixing weight alpha in [0, 1] and temperature tau in [0.25, 8]:
+ *     q[v]  = sum_m w_m softmax(z_m / tau)[v]                  (the probabilities averaged, as the ensemble decodes)
+ *     hard  = LabelSmoothingLoss(s, c; sigma)                  (the per-row term of icz_*_xe_backward)
+ *     kd    = tau^2 KL(q || softmax(s / tau)) = tau^2 sum_v q[v] (log q[v] - log_softmax(s / tau)[v])     (terms with q[v] = 0 are 0)
+ *     loss  = ((1 - alpha) sum_rows hard + alpha sum_rows kd) / N
+ *     d s   = ((1 - alpha) (softmax(s) - true) + alpha tau (softmax(s / tau) - q)) / N
+ * N is the token normaliser of icz_*_xe_backward: the local token count, n_tokens_global > 0, or (n_tokens_global < 0) the device
+ * scalar of icz_*_set_norm_global.  teacher[m] is a device tensor [N_tokens, ld[m]] of packed logits in the order of
+ * packed_logits_out -- what the teacher's icz_*_xe_forward(train = 0, packed_logits_out) writes for the same captions and lengths;
+ * ld[m] >= V lets the caller pad the rows to a 16-byte multiple (ld = V = 10 102 is not one; unaligned rows take a scalar path).
+ * teacher, ld and weights are HOST arrays; weights NULL = uniform, else the rules of icz_ensemble_create; a member of weight 0 is
+ * never read.  One launch (distill_loss_dlogits_kernel) replaces the loss kernel of icz_*_xe_backward: one workgroup per (b, t), an
+ * online max / sum-exp per row in pass 1, q formed in registers in pass 2 (never written to memory), d s written over the stored
+ * logits; every exponent is taken behind its row's maximum; per-row losses are summed in fixed order, no float atomics: two runs give
+ * the same bits.  loss_out3 = {loss, sum hard / N, sum kd / N} (device).
+ * alpha = 0 runs the launches of icz_*_xe_backward (bit for bit its gradients and loss; no teacher is read).
+ * Errors return ICZ_ERR_INVALID before any device work, in this order: 1. null opts; 2. M outside 1..4; 3. alpha; 4. temperature;
+ * 5. smoothing outside [0, 1); 6. null teacher or ld, or a null member; 7. ld[m] < V; 8. the weights; 9. null grads or loss;
+ * 10. null handle; 11. no XE forward stored; 12. the stored forward ran with scheduled sampling (ss_prob > 0): the teachers were fed
+ * other tokens than the student (also at alpha = 0).  (With a null handle V is unknown and rule 7 is not applied.)
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t M;
+    const float* const* teacher;
+    const int32_t* ld;
+    const float* weights;          /* NULL = uniform */
+    float alpha, temperature, smoothing;
+} icz_distill_opts;
+/* rules 1 - 8 above on their own (host only: no handle, no device) */
+int icz_distill_check(const icz_distill_opts* opts, int32_t V);
+/* icz_*_xe_backward with the distillation loss in the place of LabelSmoothingLoss (for AoA with the refiner's backward pass when
+ * train_refiner is on; for NIC with dfeatures_out [B, E] or NULL). */
+int icz_butd_xe_backward_distill(icz_butd_t* h, const icz_distill_opts* opts, const icz_butd_params* grads, float* loss_out3,
+                                 float n_tokens_global, void* stream);
+int icz_aoa_xe_backward_distill(icz_aoa_t* h, const icz_distill_opts* opts, const icz_aoa_params* grads, float* loss_out3,
+                                float n_tokens_global, void* stream);
+int icz_nic_xe_backward_distill(icz_nic_t* h, const icz_distill_opts* opts, const icz_nic_params* grads, float* dfeatures_out,
+                                float* loss_out3, float n_tokens_global, void* stream);
+/* The kernel alone (tests, tools): student [rows, ld_s], the teachers' rows [rows, ld[m]], targets [rows] int64 (one outside [0, V)
+ * matches no column and is never used as an index), N = n_tokens > 0; dlogits_out [rows, ld_out] (columns [V, ld_out) are written
+ * as zeros), loss_out3 as above.  alpha = 0 reads no teacher (kd = 0). */
+int icz_distill_loss(const float* student, int32_t ld_s, const icz_distill_opts* opts, const int64_t* targets, int32_t rows, int32_t V,
+                     float n_tokens, float* dlogits_out, int32_t ld_out, float* loss_out3, void* stream);
+/* icz_butd_xe_backward_dlogits for the other two families: the backward pass of the stored XE forward driven by an upstream gradient
+ * w.r.t. the packed logits [sum(lengths), V] (NIC: with dfeatures_out [B, E] or NULL). */
+int icz_aoa_xe_backward_dlogits(icz_aoa_t* h, const float* dpacked, const icz_aoa_params* grads, void* stream);
+int icz_nic_xe_backward_dlogits(icz_nic_t* h, const float* dpacked, const icz_nic_params* grads, float* dfeatures_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser step: clip_gradient (Utils.py:241-250, value clamp) + torch.optim.Adam(betas=(0.9,0.999),
  * eps=1e-8, weight_decay=0) (Utils.py:219-220) fused, one call per parameter tensor.
  * ---------------------------------------------------------------------------------------------------------- */

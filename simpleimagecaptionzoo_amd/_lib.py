@@ -107,6 +107,11 @@ class SampleOpts(C.Structure):     # icz_sample_opts
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
 
 
+class DistillOpts(C.Structure):    # icz_distill_opts
+    _fields_ = [("M", C.c_int32), ("teacher", C.POINTER(C.c_void_p)), ("ld", C.POINTER(C.c_int32)), ("weights", C.POINTER(C.c_float)),
+                ("alpha", C.c_float), ("temperature", C.c_float), ("smoothing", C.c_float)]
+
+
 _lib = None
 
 
@@ -207,6 +212,13 @@ def lib():
         "icz_score_tokens": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "icz_ensemble_score_tokens": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32, vp,
                                                 vp, vp]),
+        "icz_distill_check": (C.c_int, [C.POINTER(DistillOpts), i32]),
+        "icz_butd_xe_backward_distill": (C.c_int, [vp, C.POINTER(DistillOpts), C.POINTER(ButdParams), vp, f32, vp]),
+        "icz_aoa_xe_backward_distill": (C.c_int, [vp, C.POINTER(DistillOpts), C.POINTER(AoaParams), vp, f32, vp]),
+        "icz_nic_xe_backward_distill": (C.c_int, [vp, C.POINTER(DistillOpts), C.POINTER(NicParams), vp, vp, f32, vp]),
+        "icz_distill_loss": (C.c_int, [vp, i32, C.POINTER(DistillOpts), vp, i32, i32, f32, vp, i32, vp, vp]),
+        "icz_aoa_xe_backward_dlogits": (C.c_int, [vp, vp, C.POINTER(AoaParams), vp]),
+        "icz_nic_xe_backward_dlogits": (C.c_int, [vp, vp, C.POINTER(NicParams), vp, vp]),
         "icz_aoa_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),
         "icz_aoa_sample_n": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),
         "icz_aoa_scst_rollouts": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp, vp]),

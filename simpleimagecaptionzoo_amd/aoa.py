@@ -46,7 +46,7 @@ class AoaHandle(RegionSets, GraphDecoderHandle):
     _Params, _param_keys = AoaParams, AOA_PARAM_KEYS            # icz_aoa_params as the flat table p0..p81
     _frozen_keys = frozenset(AOA_PARAM_KEYS) - frozenset(AOA_DECODER_KEYS)
     _make_rng = staticmethod(make_aoa_rng)
-    _own_entries = ("set_regions", "refine", "saved_alphas", "sample_n")
+    _own_entries = ("set_regions", "refine", "saved_alphas", "sample_n", "xe_backward_dlogits")
 
     def __init__(self, R, D, Hd, E, V, NH, max_rows, max_len=20, device="cuda:0"):
         self._create(AoaDims(R, D, Hd, E, V, NH, max_rows, max_len), device)

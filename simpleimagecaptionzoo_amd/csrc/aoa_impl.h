@@ -196,6 +196,8 @@ struct Aoa : CaptionHead, DecodeMember {
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_aoa_rng* r, int train,
                    float* packed_out, hipStream_t st);
     int xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
+    int xe_backward_distill(const DistillArgs& a, const icz_aoa_params* G, float* loss_out3, float n_tokens_global, hipStream_t st);
+    int xe_backward_dlogits(const float* dpacked, const icz_aoa_params* G, hipStream_t st);
     int bptt(const icz_aoa_params& G, hipStream_t st);      // the driver over the parts below, then refiner_backward
     struct BpttCall;
     int bptt_predict(BpttCall& c);              // d(dropped ctx) and the predict layer's gradients (side branch)

@@ -6,6 +6,7 @@
 // one TN GEMM over all (t, b) rows after the loop.  The gradients of the hoisted linear_K / linear_V outputs are
 // accumulated per image over time by the one workgroup that owns the (image, head) slice (no atomics, fixed order).
 #include "aoa_impl.h"
+#include "ens_sample.h"
 
 namespace icz {
 namespace {
@@ -513,6 +514,29 @@ int Aoa::xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, 
     return bptt(*G, st);
 }
 
+// xe_backward with the distillation loss (distill.hip) in the place of xe_loss
+int Aoa::xe_backward_distill(const DistillArgs& a, const icz_aoa_params* G, float* loss_out3, float n_tokens_global, hipStream_t st) {
+    ICZ_TRY(require_mode(2, "aoa"));
+    ICZ_TRY(require_teacher_forced("aoa xe_backward_distill"));
+    if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
+    ICZ_TRY(distill_loss(a, n_tokens_global, tlogit, dims.V, Vp, loss_out3, st));
+    bptt_early_out = false;
+    ICZ_TRY(low.ensure());
+    return bptt(*G, st);
+}
+
+// xe_backward driven by an upstream gradient w.r.t. the packed logits (Butd::xe_backward_dlogits)
+int Aoa::xe_backward_dlogits(const float* dpacked, const icz_aoa_params* G, hipStream_t st) {
+    ICZ_TRY(require_mode(2, "aoa"));
+    ICZ_REQUIRE(dpacked && G, "aoa xe_backward_dlogits: null argument");
+    if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
+    ICZ_TRY(scatter_packed(dpacked, dims.V, Vp, tlogit, st));
+    mode = 0;
+    bptt_early_out = false;
+    ICZ_TRY(low.ensure());
+    return bptt(*G, st);
+}
+
 int Aoa::nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* slab, size_t cap, int* ns_out, const SplitPolicy& p,
             hipStream_t st, const int* live, const int* rows_live) {
     GemmArgs g = gemm_args({{A, Bm, lda, ldb, K}}, M, N, slab, N, live);
@@ -748,6 +772,19 @@ int icz_aoa_set_norm_global(icz_aoa_t* h, const float* norm_dev, void* stream) {
 int icz_aoa_xe_backward(icz_aoa_t* h, float smoothing, const icz_aoa_params* grads, float* loss_out, float n_tokens_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Aoa*>(h)->xe_backward(smoothing, grads, loss_out, n_tokens_global, (hipStream_t)stream);
+}
+int icz_aoa_xe_backward_distill(icz_aoa_t* h, const icz_distill_opts* opts, const icz_aoa_params* grads, float* loss_out3, float n_tokens_global,
+                                void* stream) {
+    Aoa* a = reinterpret_cast<Aoa*>(h);
+    DistillArgs d;
+    ICZ_TRY(distill_args("icz_aoa_xe_backward_distill", opts, a ? a->dims.V : -1, &d));
+    ICZ_REQUIRE(grads && loss_out3, "icz_aoa_xe_backward_distill: null grads or loss");
+    ICZ_REQUIRE(h, "icz_aoa_xe_backward_distill: null handle");
+    return a->xe_backward_distill(d, grads, loss_out3, n_tokens_global, (hipStream_t)stream);
+}
+int icz_aoa_xe_backward_dlogits(icz_aoa_t* h, const float* dpacked, const icz_aoa_params* grads, void* stream) {
+    ICZ_REQUIRE(h, "null handle");
+    return reinterpret_cast<Aoa*>(h)->xe_backward_dlogits(dpacked, grads, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include <math.h>
 
 #include "butd_impl.h"
+#include "ens_sample.h"
 
 namespace icz {
 
@@ -444,6 +445,16 @@ int Butd::xe_backward(float smoothing, const icz_butd_params* G, float* loss_out
     return bptt(*G, st);
 }
 
+// xe_backward with the distillation loss (distill.hip) in the place of xe_loss
+int Butd::xe_backward_distill(const DistillArgs& a, const icz_butd_params* G, float* loss_out3, float n_tokens_global, hipStream_t st) {
+    ICZ_TRY(require_mode(2, "butd"));
+    ICZ_TRY(require_teacher_forced("butd xe_backward_distill"));
+    ICZ_TRY(distill_loss(a, n_tokens_global, tb.logit, dims.V, pad_vocab(dims.V), loss_out3, st));
+    bptt_early_out = false;
+    ICZ_TRY(bptt_prelude(st));
+    return bptt(*G, st);
+}
+
 // ------------------------------------------------------------------------------------------------
 // helpers for the backward GEMMs
 // direct output (ns = 1, where g.out points) if there are already enough tiles, else slabs in `slab` (null: never split above 64 rows)
@@ -840,6 +851,15 @@ int icz_butd_xe_backward(icz_butd_t* h, float smoothing, const icz_butd_params* 
                          float n_tokens_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Butd*>(h)->xe_backward(smoothing, grads, loss_out, n_tokens_global, (hipStream_t)stream);
+}
+int icz_butd_xe_backward_distill(icz_butd_t* h, const icz_distill_opts* opts, const icz_butd_params* grads, float* loss_out3,
+                                 float n_tokens_global, void* stream) {
+    Butd* b = reinterpret_cast<Butd*>(h);
+    DistillArgs a;
+    ICZ_TRY(distill_args("icz_butd_xe_backward_distill", opts, b ? b->dims.V : -1, &a));
+    ICZ_REQUIRE(grads && loss_out3, "icz_butd_xe_backward_distill: null grads or loss");
+    ICZ_REQUIRE(h, "icz_butd_xe_backward_distill: null handle");
+    return b->xe_backward_distill(a, grads, loss_out3, n_tokens_global, (hipStream_t)stream);
 }
 
 int icz_adam_clamp_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,

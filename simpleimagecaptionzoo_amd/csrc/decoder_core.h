@@ -192,6 +192,7 @@ struct SideStream {
     };
 };
 
+struct DistillArgs;                   // ens_sample.h: the teachers' packed logits and the options of a distillation step
 // The caption loss head: host-side state of a stored training-mode forward pass and the loss buffers of all three decoders.
 struct CaptionHead {
     int mode = 0;                 // 0 none, 1 sample rollout stored, 2 XE forward stored
@@ -200,11 +201,12 @@ struct CaptionHead {
     const int64_t* cur_seq = nullptr; const float* cur_logp = nullptr; const int64_t* cur_captions = nullptr;
     std::vector<int> rows_t;      // active rows per step of the XE batch (lengths sorted in decreasing order)
     float ss_prob = 0.f;          // scheduled sampling in xe_forward (icz_*_set_scheduled_sampling)
+    float cur_ss_prob = 0.f;      // ss_prob of the stored XE forward pass
     const float* ss_gate = nullptr; const float* ss_draw = nullptr;      // explicit [T, B] uniforms (device) or Philox
     uint64_t* d_seed = nullptr;   // Philox seed of the current training-mode call (device resident)
     float* d_msum = nullptr;      // data-parallel loss normaliser (0 = use the local one)
     // training buffers (alloc_loss_buffers): TB = steps x rows
-    float *coef = nullptr, *lse = nullptr, *loss_rows = nullptr;
+    float *coef = nullptr, *lse = nullptr, *loss_rows = nullptr, *kd_rows = nullptr;
     int32_t* draw = nullptr;
     uint8_t* unf = nullptr; int* nunf = nullptr;
     uint8_t* gunf = nullptr; int* gnunf = nullptr;     // the same for the greedy baseline of an SCST step
@@ -225,6 +227,10 @@ struct CaptionHead {
     int scatter_packed(const float* dpacked, int V, int ldl, float* logit, hipStream_t st);
     // LabelSmoothingLoss: loss and dlogits (in place) of the stored XE forward pass
     int xe_loss(float smoothing, float n_tokens_global, float* logits, int V, int ldl, float* loss_out, hipStream_t st);
+    // Distillation (distill.hip): the mixed hard / soft-target loss and dlogits (in place) of the stored XE forward pass against the
+    // teachers' packed logits; loss_out3 = {loss, sum hard / N, sum kd / N}.  alpha = 0 is xe_loss.
+    int distill_loss(const DistillArgs& a, float n_tokens_global, float* logits, int V, int ldl, float* loss_out3, hipStream_t st);
+    int require_teacher_forced(const char* who) const;      // the stored XE forward pass fed the captions' own tokens (no scheduled sampling)
     // REINFORCE: loss, mask sum and dlogits (in place) of the stored rollout; rows / row0: rows per step slot and the first of the
     // sampled rollout's (a merged SCST chain stores 2 B rows per slot)
     int reinforce(const float* reward, float* logits, int V, int ldl, float* loss_out, float* msum_out, hipStream_t st, int rows = 0, int row0 = 0);

@@ -49,6 +49,7 @@ int CaptionHead::alloc_loss_buffers(DeviceBuffers& m, size_t TB, size_t B, size_
     ICZ_TRY(m.alloc((void**)&coef, sizeof(float) * TB));
     ICZ_TRY(m.alloc((void**)&lse, sizeof(float) * TB));
     ICZ_TRY(m.alloc((void**)&loss_rows, sizeof(float) * TB));
+    ICZ_TRY(m.alloc((void**)&kd_rows, sizeof(float) * TB));
     ICZ_TRY(m.alloc((void**)&draw, sizeof(int32_t) * TB));
     ICZ_TRY(m.alloc((void**)&unf, B));
     ICZ_TRY(m.alloc((void**)&nunf, sizeof(int) * T));
@@ -61,7 +62,7 @@ int CaptionHead::alloc_loss_buffers(DeviceBuffers& m, size_t TB, size_t B, size_
 }
 
 void CaptionHead::drop_loss_buffers() {
-    coef = lse = loss_rows = nullptr; draw = nullptr; unf = gunf = nullptr; nunf = gnunf = live_rows = pack_idx = nullptr;
+    coef = lse = loss_rows = kd_rows = nullptr; draw = nullptr; unf = gunf = nullptr; nunf = gnunf = live_rows = pack_idx = nullptr;
     pack_cap = 0;
     mode = 0;
 }
@@ -85,7 +86,7 @@ int CaptionHead::xe_steps(const char* who, const int32_t* lengths, int B, int L,
 
 void CaptionHead::begin_xe(const int32_t* lengths, int B, int T, int L, const int64_t* captions, bool train, uint64_t seed, hipStream_t st) {
     hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, seed, (float*)nullptr, 0.f);
-    mode = 2; cur_B = B; cur_T = T; cur_L = L; cur_train = train; cur_captions = captions;
+    mode = 2; cur_B = B; cur_T = T; cur_L = L; cur_train = train; cur_captions = captions; cur_ss_prob = ss_prob;
     rows_t.assign(T, 0);
     n_tokens = 0;
     for (int t = 0; t < T; ++t) {

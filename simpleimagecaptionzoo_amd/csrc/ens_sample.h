@@ -1,4 +1,4 @@
-// What ensemble.hip, sample_decode.hip and score_captions.hip share: the ensemble's view of its members' logits with the device
+// What ensemble.hip, sample_decode.hip, score_captions.hip and distill.hip share: the ensemble's view of its members' logits with the device
 // helpers that read and reduce them (ensemble_logprob_kernel and the ensemble instances of sample_decode_kernel and
 // score_tokens_kernel), and the arguments / launchers of those two kernels that the ensemble's drivers (Ensemble::sample_decode,
 // Ensemble::score_captions) need.
@@ -107,5 +107,14 @@ void launch_score_tokens(const ScoreArgs& a, int rows, hipStream_t st);
 void launch_score_tokens(const EnsScoreArgs& a, int rows, hipStream_t st);
 // weights: null = uniform; else finite, >= 0, sum > 0 -> log of the normalised weights (ensemble.hip)
 int ens_log_weights(const char* who, const float* weights, int M, float* logw);
+
+// ---- distill_loss_dlogits_kernel (distill.hip) ----
+// ens: the teachers' packed logits [N, ld_m] as finished rows (ns 1) with the log of their normalised weights
+struct DistillArgs {
+    EnsArgs ens;
+    float alpha, temperature, smoothing;
+};
+// the argument rules 1 - 8 of icz_distill_opts in their documented order (V < 0: no handle yet, rule 7 waits for one) -> the kernel's view
+int distill_args(const char* who, const icz_distill_opts* o, int V, DistillArgs* out);
 
 }  // namespace icz

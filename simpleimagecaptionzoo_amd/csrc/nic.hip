@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "butd_impl.h"
+#include "ens_sample.h"
 
 namespace icz {
 
@@ -54,6 +55,8 @@ struct Nic : CaptionHead, DecodeMember {
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r, int train,
                    float* packed_out, hipStream_t st);
     int xe_backward(float smoothing, const icz_nic_params* G, float* dfeats, float* loss_out, float n_tokens_global, hipStream_t st);
+    int xe_backward_distill(const DistillArgs& a, const icz_nic_params* G, float* dfeats, float* loss_out3, float n_tokens_global, hipStream_t st);
+    int xe_backward_dlogits(const float* dpacked, const icz_nic_params* G, float* dfeats, hipStream_t st);
     int bptt(const icz_nic_params& G, float* dfeats, hipStream_t st);
     int nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* out, int* ns, int target, hipStream_t st,
            const int* live = nullptr);
@@ -312,6 +315,25 @@ int Nic::xe_backward(float smoothing, const icz_nic_params* G, float* dfeats, fl
     return bptt(*G, dfeats, st);
 }
 
+// xe_backward with the distillation loss (distill.hip) in the place of xe_loss
+int Nic::xe_backward_distill(const DistillArgs& a, const icz_nic_params* G, float* dfeats, float* loss_out3, float n_tokens_global, hipStream_t st) {
+    ICZ_TRY(require_mode(2, "nic"));
+    ICZ_TRY(require_teacher_forced("nic xe_backward_distill"));
+    ICZ_TRY(distill_loss(a, n_tokens_global, tlogit, dims.V, Vp, loss_out3, st));
+    bptt_early_out = false;
+    return bptt(*G, dfeats, st);
+}
+
+// xe_backward driven by an upstream gradient w.r.t. the packed logits (Butd::xe_backward_dlogits)
+int Nic::xe_backward_dlogits(const float* dpacked, const icz_nic_params* G, float* dfeats, hipStream_t st) {
+    ICZ_TRY(require_mode(2, "nic"));
+    ICZ_REQUIRE(dpacked && G, "nic xe_backward_dlogits: null argument");
+    ICZ_TRY(scatter_packed(dpacked, dims.V, Vp, tlogit, st));
+    mode = 0;
+    bptt_early_out = false;
+    return bptt(*G, dfeats, st);
+}
+
 // A[M,K] . B[K,N]: with ns_out, slabs [ns][M][N] in `out` (= X, one slab: the dense product) for the consumer to sum; without, the
 // finished dense product in `out`, split-K slabs going through `ws`
 int Nic::nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* out, int* ns_out, int target, hipStream_t st,
@@ -461,5 +483,18 @@ int icz_nic_xe_backward(icz_nic_t* h, float smoothing, const icz_nic_params* gra
                         float n_tokens_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Nic*>(h)->xe_backward(smoothing, grads, dfeatures_out, loss_out, n_tokens_global, (hipStream_t)stream);
+}
+int icz_nic_xe_backward_distill(icz_nic_t* h, const icz_distill_opts* opts, const icz_nic_params* grads, float* dfeatures_out,
+                                float* loss_out3, float n_tokens_global, void* stream) {
+    Nic* n = reinterpret_cast<Nic*>(h);
+    DistillArgs a;
+    ICZ_TRY(distill_args("icz_nic_xe_backward_distill", opts, n ? n->dims.V : -1, &a));
+    ICZ_REQUIRE(grads && loss_out3, "icz_nic_xe_backward_distill: null grads or loss");
+    ICZ_REQUIRE(h, "icz_nic_xe_backward_distill: null handle");
+    return n->xe_backward_distill(a, grads, dfeatures_out, loss_out3, n_tokens_global, (hipStream_t)stream);
+}
+int icz_nic_xe_backward_dlogits(icz_nic_t* h, const float* dpacked, const icz_nic_params* grads, float* dfeatures_out, void* stream) {
+    ICZ_REQUIRE(h, "null handle");
+    return reinterpret_cast<Nic*>(h)->xe_backward_dlogits(dpacked, grads, dfeatures_out, (hipStream_t)stream);
 }
 }  // extern "C"

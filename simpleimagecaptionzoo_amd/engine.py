@@ -393,6 +393,19 @@ class BUTDDetection_Eng(Engine):
         with _on_stream(self):
             return self._training_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs)
 
+    def _xe_token_norm(self, h, lengths):
+        """The `n_tokens_global` of an XE backward call: 0 (the local count) for one process.  Data-parallel, G2: every
+        rank scales by 1 / (global token count); the count is all-reduced on the device and handed to the library as a device scalar
+        (-1: no host round trip between forward and backward)."""
+        if not icz_dist.is_distributed():
+            return 0.0
+        n_dev = torch.full((1,), float(sum(lengths)), dtype=torch.float32, device=self.device)
+        if hasattr(h, "set_mask_sum_global"):
+            icz_dist.all_reduce_sum_(n_dev)
+            h.set_mask_sum_global(n_dev)
+            return -1.0
+        return icz_dist.all_reduce_scalar(n_dev)
+
     def _training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None):
         """Engine.py:169-188.  `criterion` is the reference's LabelSmoothingLoss (only its .smoothing is read: the
         loss and its gradient are fused into the backward kernels).  `rngs` (tests) supplies one icz_rng per batch."""
@@ -407,22 +420,69 @@ class BUTDDetection_Eng(Engine):
             rng = rngs[batch_i] if rngs is not None else self.model._next_rng()
             h.xe_forward(self._features(visual_inputs), captions, lengths, rng, train=True)
             grads = self._grads()
-            n_glob = 0.0
-            if icz_dist.is_distributed():
-                # G2: every rank scales by 1 / (global token count).  The count is all-reduced on the device
-                # and handed to the library as a device scalar: no host round trip between forward and backward
-                n_dev = torch.full((1,), float(sum(lengths)), dtype=torch.float32, device=self.device)
-                if hasattr(h, "set_mask_sum_global"):
-                    icz_dist.all_reduce_sum_(n_dev)
-                    h.set_mask_sum_global(n_dev)
-                    n_glob = -1.0
-                else:
-                    n_glob = icz_dist.all_reduce_scalar(n_dev)
+            n_glob = self._xe_token_norm(h, lengths)
             ov = self._reduce_grads_begin(h)
             loss = h.xe_backward(grads, smoothing, n_glob)
             self._reduce_grads_end(ov)
             self._apply(optimizer, 0.1)
             losses.append(loss)
+            if tqdm_visible:
+                monitor.set_postfix(Loss=np.round(loss.item(), decimals=4))
+        return losses
+
+    def distill_training_epoch(self, dataloader, optimizer, criterion, teachers, tqdm_visible=True, rngs=None, *, alpha=0.5, temperature=1.0,
+                               weights=None):
+        """Beyond the reference: training_epoch with the word-level distillation loss of distill.py in the place of the XE loss.
+        `teachers` = 1..4 other Engines of the same vocabulary on the same device, any mix of families, in evaluation mode for
+        the epoch; every step each turns the shared batch into its own features (its modify_visual_inputs and _features, as
+        eval_ensemble_captions_json_generation does) and runs a teacher-forced forward on the batch's captions, and the student's
+        backward pass starts from loss = ((1 - alpha) hard + alpha temperature^2 KL(q || softmax(s / temperature))) / N with q the
+        `weights`-averaged (None = uniform) teacher distribution at `temperature`.  The token-count exchange, the gradient-reduce
+        hooks, the 0.1 clamp, Adam and criterion.smoothing are training_epoch's.  Returns the losses; the per-step (hard, kd) terms
+        stay in self.last_distill_terms.  ValueError, before any device work, for 0 or more than 4 teachers, this engine among
+        them, a vocabulary or device mismatch, a bad alpha, temperature or weights, or scheduled sampling live on the student (the
+        teachers would be fed other tokens than the student)."""
+        from .distill import check_opts
+        teachers = list(teachers)
+        check_opts(len(teachers), weights, alpha, temperature, float(getattr(criterion, "smoothing", 0.0)))
+        if any(t is self or t.model is self.model for t in teachers):
+            raise ValueError("the student is among its teachers: a teacher's forward pass would replace the student's stored one")
+        if len({len(e.caption_vocab) for e in teachers + [self]}) != 1:
+            raise ValueError("the vocabularies differ in size: student %d, teachers %s" % (len(self.caption_vocab), [len(e.caption_vocab) for e in teachers]))
+        if len({str(e.device) for e in teachers + [self]}) != 1:
+            raise ValueError("the engines sit on different devices %s" % [str(e.device) for e in [self] + teachers])
+        for e in [self] + teachers:
+            if e.model.scheduled_sampling and float(e.model.ss_prob) > 0.0:
+                raise ValueError("scheduled sampling is live on %s (ss_prob %g): student and teachers would be fed different tokens"
+                                 % ("the student" if e is self else "a teacher", float(e.model.ss_prob)))
+        with _on_stream(self):
+            return self._distill_training_epoch(dataloader, optimizer, criterion, teachers, tqdm_visible, rngs, alpha, temperature, weights)
+
+    def _distill_training_epoch(self, dataloader, optimizer, criterion, teachers, tqdm_visible, rngs, alpha, temperature, weights):
+        """_training_epoch with the teachers' forward passes in front of the backward call and xe_backward_distill in its place"""
+        from .distill import teacher_logits, xe_backward_distill
+        self.model.train()
+        for e in teachers:
+            e.model.eval()
+        smoothing = float(getattr(criterion, "smoothing", 0.0))
+        monitor = _monitor(dataloader, "Distillation Process", tqdm_visible)
+        losses, self.last_distill_terms = [], []
+        for batch_i, (img_ids, img_tensors, captions, lengths, supp_info_datas) in enumerate(monitor):
+            visual_inputs = self.modify_visual_inputs(img_tensors, supp_info_datas)
+            lengths = [cap_len - 1 for cap_len in lengths]
+            t_feats = [e._features(e.modify_visual_inputs(img_tensors, supp_info_datas)) for e in teachers]
+            t_logits = teacher_logits([e.model._handle() for e in teachers], t_feats, captions, lengths)
+            h = self.model._handle()
+            rng = rngs[batch_i] if rngs is not None else self.model._next_rng()
+            h.xe_forward(self._features(visual_inputs), captions, lengths, rng, train=True)
+            grads = self._grads()
+            n_glob = self._xe_token_norm(h, lengths)
+            ov = self._reduce_grads_begin(h)
+            loss, hard, kd = xe_backward_distill(h, grads, t_logits, weights, alpha, temperature, smoothing, n_glob)
+            self._reduce_grads_end(ov)
+            self._apply(optimizer, 0.1)
+            losses.append(loss)
+            self.last_distill_terms.append((hard, kd))
             if tqdm_visible:
                 monitor.set_postfix(Loss=np.round(loss.item(), decimals=4))
         return losses

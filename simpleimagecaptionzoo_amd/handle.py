@@ -16,7 +16,7 @@ from .scheduled import ScheduledSamplingState
 # the icz_<family>_<name> entries the shared methods call; a family lists the ones only it has in `_own_entries`
 _ENTRIES = ("create", "destroy", "bind_params", "refresh_weights", "set_option", "set_grad_callback", "set_scheduled_sampling",
             "set_norm_global", "greedy", "sample", "scst_rollouts", "sample_backward", "xe_forward", "xe_backward", "beam_search",
-            "beam_search_opts", "beam_search_diverse", "sample_decode", "score_captions")
+            "beam_search_opts", "beam_search_diverse", "sample_decode", "score_captions", "xe_backward_distill")
 
 
 class DecoderHandle:
@@ -178,6 +178,7 @@ class DecoderHandle:
         check(self._e.xe_forward(self._h, ptr(feats), ptr(captions), B, L, lens, C.byref(rng) if rng is not None else None,
                                  1 if train else 0, ptr(out), stream_ptr()))
         self._live = (feats, rng, captions)
+        self._xe_tokens = sum(int(x) for x in lengths)      # rows of the packed logits (distill.py checks the teachers' against it)
         return out
 
     def set_scheduled_sampling(self, ss_prob, gate=None, draw=None):

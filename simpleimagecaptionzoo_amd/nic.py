@@ -14,7 +14,7 @@ class NicHandle(DecoderHandle):
     family, kind = "nic", 2
     _Params, _param_keys = NicParams, NIC_PARAM_KEYS
     _make_rng = staticmethod(make_rng)
-    _own_entries = ("sample_n",)
+    _own_entries = ("sample_n", "xe_backward_dlogits")
 
     def __init__(self, E, H, V, max_rows, max_len=20, device="cuda:0"):
         self._create(NicDims(E, H, V, max_rows, max_len), device)
