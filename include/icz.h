@@ -838,6 +838,41 @@ int icz_gemm_tn_grouped_fits(int32_t M, int32_t K, int32_t ngroups, const int32_
  * point (0), behind the branch's start (1), behind its launch (2), behind its finish (3) -- the branch is still joined, so the error
  * is reported as itself and `stream` is left usable; fail_at = -1 fails nowhere.  out2: two device floats. */
 int icz_test_side_branch(int32_t fail_at, int32_t inline_branch, float* out2, void* stream);
+/* Test entries for the kernels that finish a backward pass and the weight refresh, each on its own (tests/test_gpu_support_kernels.py):
+ * the library's kernel through the library's launch code, arguments filled as the decoders fill them (tables: blocks job after
+ * job).  Every entry checks on the host what its kernel needs of the shape and the pointers -- columns in whole groups of 4,
+ * 16-byte alignment wherever the kernel moves four floats at a time, table sizes -- and returns ICZ_ERR_INVALID without launching
+ * otherwise.  All data pointers are DEVICE pointers; the tables (v[], rows[], ...) are HOST arrays of `count` entries.
+ *
+ * Embedding gradient: dE[v, :] = sum over i < n_tok with tok[i] == v, in list order, of (sum_{z < ns} demb[z * slab_stride + i * E + :])
+ * * (relu ? (emb[i * E + :] > 0 ? scale : 0) : scale); every row of dE [V, E] is written.  rows_live: optional device int32, only the
+ * first min(n_tok, *rows_live) list entries count (and are read).  route 0 = the form the decoders' launch picks for n_tok, 1 = the
+ * form that holds the whole list in LDS (lists of up to ~4500 tokens), 2 = the windowed form (E <= 1024); a forced form that cannot
+ * take the shape is an error.  Both forms add the same numbers in the same order: the same bits. */
+int icz_test_embed_grad(const int64_t* tok, int32_t n_tok, const float* demb, int32_t ns, int64_t slab_stride, const float* emb, float scale,
+                        int32_t E, float* dE, int32_t V, int32_t relu, const int32_t* rows_live, int32_t route, void* stream);
+/* The form route 0 takes (host logic only, no GPU needed): 1 or 2, *lds_bytes_out (optional) = dynamic LDS bytes of the launch (form 2:
+ * 0); ICZ_ERR_INVALID for bad arguments and for a list that needs the windowed form at E > 1024. */
+int icz_embed_grad_route_for(int32_t n_tok, int32_t E, size_t* lds_bytes_out);
+/* w_j[r, :] = v_j[r, :] g_j[r] / ||v_j[r, :]||, norm_j[r] = ||v_j[r, :]|| for `count` matrices [rows[j], cols[j]] (dense).  multi != 0:
+ * the table kernel, 1..4 jobs in one launch; multi == 0: the single-matrix kernel, count == 1. */
+int icz_test_weight_norm(int32_t multi, int32_t count, const float* const* v, const float* const* g, float* const* w, float* const* norm,
+                         const int32_t* rows, const int32_t* cols, void* stream);
+/* Its backward: dg_j[r] = dw_j[r, :] . v_j[r, :] / norm_j[r], dv_j[r, :] = (g_j[r] / norm_j[r]) (dw_j[r, :] - (dg_j[r] / norm_j[r]) v_j[r, :]);
+ * dw_j has row stride lddw[j] >= cols[j] (a multiple of 4), everything else is dense.  multi / count as above. */
+int icz_test_weight_norm_bwd(int32_t multi, int32_t count, const float* const* dw, const int32_t* lddw, const float* const* v, const float* const* g,
+                             const float* const* norm, float* const* dv, float* const* dg, const int32_t* rows, const int32_t* cols, void* stream);
+/* dst_j[c, r] = src_j[r * ld[j] + c], r < rows[j], c < cols[j] (both multiples of 64; dst row stride rows[j]), 1..4 jobs in one launch. */
+int icz_test_transpose(int32_t count, const float* const* src, const int32_t* ld, const int32_t* rows, const int32_t* cols, float* const* dst,
+                       void* stream);
+/* out_j[n] = sum_{k < K[j]} X_j[k * ldx[j] + n], n < N[j]; K[j] = 0 writes zeros.  multi != 0: 1..8 jobs in one launch, out2 (optional
+ * table, entries may be NULL) receives a copy of out_j; multi == 0: the single sum behind every bias gradient, count == 1, no out2. */
+int icz_test_colsum(int32_t multi, int32_t count, const float* const* X, const int32_t* K, const int32_t* N, const int32_t* ldx, float* const* out,
+                    float* const* out2, void* stream);
+/* out[i] = sum_{t < T} X[t * BN + i], i < BN, added in t order (BN a multiple of 4). */
+int icz_test_timesum(const float* X, int32_t T, int64_t BN, float* out, void* stream);
+/* out[i, n] = sum_{k < G} X[(i * G + k) * N + n], i < n_img, n < N, added in k order (N a multiple of 4). */
+int icz_test_rowgroup_sum(const float* X, int32_t n_img, int32_t G, int64_t N, float* out, void* stream);
 /* Live timing of the dominant kernel (the forward GEMMs of a decoder step at 33..64 rows: gemm_resident_x3_kernel, or
  * gemm_nt_kernel<4, ...> with ICZ_GEMM_RESIDENT_X3=0; see icz_prof_select) with HIP events on its launch stream, for bench.py's
  * roofline line.  Between begin and end every launch is bracketed by an event

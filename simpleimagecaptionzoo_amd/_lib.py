@@ -263,6 +263,14 @@ def lib():
         "icz_gemm_split_for": (C.c_int, [i32, i32, i32, i32, vp, C.c_size_t]),
         "icz_gemm_tn_grouped_fits": (C.c_int, [i32, i32, i32, vp]),
         "icz_test_side_branch": (C.c_int, [i32, i32, vp, vp]),
+        "icz_test_embed_grad": (C.c_int, [vp, i32, vp, i32, i64, vp, f32, i32, vp, i32, i32, vp, i32, vp]),
+        "icz_embed_grad_route_for": (C.c_int, [i32, i32, C.POINTER(C.c_size_t)]),
+        "icz_test_weight_norm": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_test_weight_norm_bwd": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_test_transpose": (C.c_int, [i32, vp, vp, vp, vp, vp, vp]),
+        "icz_test_colsum": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_test_timesum": (C.c_int, [vp, i32, i64, vp, vp]),
+        "icz_test_rowgroup_sum": (C.c_int, [vp, i32, i32, i64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         try:

@@ -180,6 +180,80 @@ def gemm_seg(layout, As, Bs, bias=None, nsplit=0, out=None, accumulate=False, li
     return workspace[:used.value * M * N].view(used.value, M, N) if raw_slabs else out
 
 
+def _ptrs(ts):
+    """Host array of the tensors' pointers (None -> NULL)."""
+    return (C.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _i32s(xs):
+    return (C.c_int32 * len(xs))(*[int(x) for x in xs])
+
+
+def embed_grad_route_for(n_tok, E):
+    """icz_embed_grad_route_for (host logic, no GPU): (form, dynamic LDS bytes) of the embedding gradient over n_tok list entries --
+    1 = the list in LDS, 2 = windowed -- or None where the library refuses."""
+    lds = C.c_size_t(0)
+    r = int(lib().icz_embed_grad_route_for(int(n_tok), int(E), C.byref(lds)))
+    return (r, int(lds.value)) if r > 0 else None
+
+
+def embed_grad(tok, n_tok, demb, emb, scale, E, dE, V, relu, ns=1, slab_stride=0, rows_live=None, route=0):
+    """Test entry for icz_test_embed_grad: dE [V, E] from the list tok [n_tok], demb (ns slabs of stride slab_stride) and emb; the
+    tensors are taken as they are (views at any offset), the library checks them."""
+    check(lib().icz_test_embed_grad(ptr(tok), int(n_tok), ptr(demb), int(ns), int(slab_stride), ptr(emb), float(scale), int(E), ptr(dE),
+                                    int(V), int(relu), ptr(rows_live), int(route), stream_ptr()))
+
+
+def weight_norm(jobs, multi=True):
+    """Test entry for icz_test_weight_norm: jobs = [(v, g, w, norm, rows, cols)]; multi: the table kernel, else the single-matrix one."""
+    c = list(zip(*jobs)) if jobs else [()] * 6
+    check(lib().icz_test_weight_norm(int(multi), len(jobs), _ptrs(c[0]), _ptrs(c[1]), _ptrs(c[2]), _ptrs(c[3]), _i32s(c[4]), _i32s(c[5]),
+                                     stream_ptr()))
+
+
+def weight_norm_bwd(jobs, multi=True):
+    """Test entry for icz_test_weight_norm_bwd: jobs = [(dw, lddw, v, g, norm, dv, dg, rows, cols)]."""
+    c = list(zip(*jobs)) if jobs else [()] * 9
+    check(lib().icz_test_weight_norm_bwd(int(multi), len(jobs), _ptrs(c[0]), _i32s(c[1]), _ptrs(c[2]), _ptrs(c[3]), _ptrs(c[4]), _ptrs(c[5]),
+                                         _ptrs(c[6]), _i32s(c[7]), _i32s(c[8]), stream_ptr()))
+
+
+def transpose_multi(jobs):
+    """Test entry for icz_test_transpose: jobs = [(src, ld, rows, cols, dst)], dst[c, r] = src[r * ld + c]."""
+    c = list(zip(*jobs)) if jobs else [()] * 5
+    check(lib().icz_test_transpose(len(jobs), _ptrs(c[0]), _i32s(c[1]), _i32s(c[2]), _i32s(c[3]), _ptrs(c[4]), stream_ptr()))
+
+
+def colsum(jobs, multi=True):
+    """Test entry for icz_test_colsum: jobs = [(X, K, N, ldx, out, out2 or None)]; multi: the table kernel, else the single sum."""
+    c = list(zip(*jobs)) if jobs else [()] * 6
+    check(lib().icz_test_colsum(int(multi), len(jobs), _ptrs(c[0]), _i32s(c[1]), _i32s(c[2]), _i32s(c[3]), _ptrs(c[4]), _ptrs(c[5]),
+                                stream_ptr()))
+
+
+def timesum(X, T, BN, out):
+    """Test entry for icz_test_timesum: out[i] = sum_t X[t * BN + i]."""
+    check(lib().icz_test_timesum(ptr(X), int(T), int(BN), ptr(out), stream_ptr()))
+
+
+def rowgroup_sum(X, n_img, G, N, out):
+    """Test entry for icz_test_rowgroup_sum: out[i, n] = sum_k X[(i * G + k) * N + n]."""
+    check(lib().icz_test_rowgroup_sum(ptr(X), int(n_img), int(G), int(N), ptr(out), stream_ptr()))
+
+
+def adam_clamp_step(p, g, m, v, n, lr, clip, step):
+    """icz_adam_clamp_step on the first n floats of four tensors (views at any offset)."""
+    check(lib().icz_adam_clamp_step(ptr(p), ptr(g), ptr(m), ptr(v), int(n), float(lr), float(clip), int(step), stream_ptr()))
+
+
+def adam_clamp_multi(tensors, lr, clip, step):
+    """icz_adam_clamp_multi: tensors = [(p, g, m, v, n)], one launch."""
+    c = list(zip(*tensors)) if tensors else [()] * 5
+    numel = (C.c_int64 * len(tensors))(*[int(n) for n in c[4]])
+    check(lib().icz_adam_clamp_multi(len(tensors), _ptrs(c[0]), _ptrs(c[1]), _ptrs(c[2]), _ptrs(c[3]), numel, float(lr), float(clip), int(step),
+                                     stream_ptr()))
+
+
 def gemm_resident_pair(As_a, Bs_a, As_b, Bs_b, slabs_a=None, slabs_b=None, live=None):
     """Test/bench entry for icz_gemm_resident_pair: two NT products over K segments (33..64 rows each) as one launch of the
     resident-activation kernel, what a BPTT step does for its two recurrent dgrad products.  Returns their split-K slabs

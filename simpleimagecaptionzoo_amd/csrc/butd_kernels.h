@@ -2032,7 +2032,8 @@ __global__ __launch_bounds__(256) void embed_grad_kernel(const int64_t* __restri
 // The same for token lists longer than embed_grad_kernel's LDS holds (more than ~4500 (t, b) pairs: the multi-sample rollout's B K rows
 // x T steps).  The list is walked in windows of EG_WIN tokens: per window each wave finds the occurrences of two of the rows (ballot,
 // list order), then every wave adds them for its columns; the partial sums are carried across windows in registers -- the same
-// additions in the same order as embed_grad_kernel.  E <= 1024 (one group of four columns per lane).
+// additions in the same order as embed_grad_kernel (the same bits: tests/test_gpu_support_kernels.py runs both on one list).  E <= 1024
+// (one group of four columns per lane).
 constexpr int EG_WIN = 1024;
 __global__ __launch_bounds__(256) void embed_grad_win_kernel(const int64_t* __restrict__ tok, int n_tok,
                                                              const float* __restrict__ demb, int ns, size_t slab_stride,
@@ -2094,11 +2095,20 @@ __global__ __launch_bounds__(256) void embed_grad_win_kernel(const int64_t* __re
     }
 }
 
-// host side: grid, LDS size (above the 64 KB default the kernel needs the explicit opt-in); longer token lists: the windowed form
+// host side: grid, LDS size (above the 64 KB default the kernel needs the explicit opt-in); longer token lists: the windowed form.
+// route: 0 = by the list's length (every decoder), 1 = embed_grad_kernel, 2 = embed_grad_win_kernel (icz_test_embed_grad); a forced
+// form that cannot take the shape is refused.
+constexpr int EG_ROUTE_LDS = 1, EG_ROUTE_WIN = 2;
+constexpr size_t EG_LDS_MAX = 160 * 1024 - 1024;
+inline size_t embed_grad_lds(int n_tok) { return sizeof(int) * (1 + EG_ROWS) * (size_t)n_tok; }
+inline int embed_grad_route(int n_tok) { return embed_grad_lds(n_tok) > EG_LDS_MAX ? EG_ROUTE_WIN : EG_ROUTE_LDS; }
 inline hipError_t embed_grad_launch(hipStream_t st, const int64_t* tok, int n_tok, const float* demb, int ns, size_t slab_stride,
-                                    const float* emb, float scale, int E, float* dE, int V, int relu, const int* rows_live = nullptr) {
-    const size_t lds = sizeof(int) * (1 + EG_ROWS) * (size_t)n_tok;
-    if (lds > 160 * 1024 - 1024) {
+                                    const float* emb, float scale, int E, float* dE, int V, int relu, const int* rows_live = nullptr,
+                                    int route = 0) {
+    const size_t lds = embed_grad_lds(n_tok);
+    if (route == 0) route = embed_grad_route(n_tok);
+    if (route != EG_ROUTE_WIN && lds > EG_LDS_MAX) return hipErrorInvalidValue;
+    if (route == EG_ROUTE_WIN) {
         if (E > 1024 || E % 4 != 0) return hipErrorInvalidValue;
         hipLaunchKernelGGL(embed_grad_win_kernel, dim3((V + EG_ROWS - 1) / EG_ROWS), dim3(256), 0, st, tok, n_tok, demb, ns, slab_stride, emb, scale,
                            E, dE, V, relu, rows_live);
@@ -2177,7 +2187,19 @@ __global__ __launch_bounds__(256) void weight_norm_bwd_multi_kernel(WeightNormBw
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// clip_gradient + Adam over a table of tensors in ONE launch (21 parameter tensors per step otherwise cost 21 launches).
+// clip_gradient (Utils.py:241-250) + Adam (Utils.py:219-220) of ONE element, the only statement of the update: adam_clamp_kernel and
+// both paths of adam_clamp_multi_kernel call it, and the three fused multiply-adds are written out -- left to the compiler's
+// contraction, the 16-byte path fused m and v while the one-element sites did not, and the same element came out with other bits
+// depending on its tensor's alignment (tests/test_gpu_support_kernels.py).  These are the bits of the 16-byte path.
+__device__ __forceinline__ void adam_clamp_update(float g, float& m, float& v, float& p, float lr, float clip, float bc1, float sqrt_bc2) {
+    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+    const float gv = fminf(fmaxf(g, -clip), clip);
+    m = __builtin_fmaf(m, b1, gv * (1.f - b1));
+    v = __builtin_fmaf(v, b2, (gv * gv) * (1.f - b2));
+    p = __builtin_fmaf(-(lr / bc1), m / (sqrtf(v) / sqrt_bc2 + eps), p);
+}
+
+// The update over a table of tensors in ONE launch (21 parameter tensors per step otherwise cost 21 launches).
 struct AdamTensor { float* p; const float* g; float* m; float* v; size_t n; size_t block0; };
 constexpr int ADAM_MAX_TENSORS = 32;
 struct AdamTable { AdamTensor t[ADAM_MAX_TENSORS]; int count; };
@@ -2190,45 +2212,38 @@ __global__ __launch_bounds__(256) void adam_clamp_multi_kernel(AdamTable tab, fl
     const AdamTensor T = tab.t[k];
     const size_t i = ((size_t)blockIdx.x - T.block0) * 1024 + threadIdx.x * 4;
     if (i >= T.n) return;
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
     if (i + 4 <= T.n && (((uintptr_t)(T.p + i) | (uintptr_t)(T.g + i) | (uintptr_t)(T.m + i) | (uintptr_t)(T.v + i)) & 15) == 0) {
         f32x4 g = *reinterpret_cast<const f32x4*>(T.g + i), m = *reinterpret_cast<f32x4*>(T.m + i);
         f32x4 v = *reinterpret_cast<f32x4*>(T.v + i), p = *reinterpret_cast<f32x4*>(T.p + i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float gv = fminf(fmaxf(g[e], -clip), clip);
-            m[e] = m[e] * b1 + gv * (1.f - b1);
-            v[e] = v[e] * b2 + (gv * gv) * (1.f - b2);
-            p[e] = p[e] - (lr / bc1) * (m[e] / (sqrtf(v[e]) / sqrt_bc2 + eps));
+            float me = m[e], ve = v[e], pe = p[e];
+            adam_clamp_update(g[e], me, ve, pe, lr, clip, bc1, sqrt_bc2);
+            m[e] = me; v[e] = ve; p[e] = pe;
         }
         *reinterpret_cast<f32x4*>(T.m + i) = m;
         *reinterpret_cast<f32x4*>(T.v + i) = v;
         *reinterpret_cast<f32x4*>(T.p + i) = p;
-    } else {
+    } else {      // a tensor's tail, or a tensor that is not 16-byte aligned
         for (size_t e = i; e < T.n && e < i + 4; ++e) {
-            const float gv = fminf(fmaxf(T.g[e], -clip), clip);
-            const float mn = T.m[e] * b1 + gv * (1.f - b1);
-            const float vn = T.v[e] * b2 + (gv * gv) * (1.f - b2);
-            T.m[e] = mn; T.v[e] = vn;
-            T.p[e] = T.p[e] - (lr / bc1) * (mn / (sqrtf(vn) / sqrt_bc2 + eps));
+            float me = T.m[e], ve = T.v[e], pe = T.p[e];
+            adam_clamp_update(T.g[e], me, ve, pe, lr, clip, bc1, sqrt_bc2);
+            T.m[e] = me; T.v[e] = ve; T.p[e] = pe;
         }
     }
 }
 
-// clip_gradient (Utils.py:241-250) + Adam (Utils.py:219-220) fused, elementwise.
+// The update of one tensor, one element per thread.
 __global__ __launch_bounds__(256) void adam_clamp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, size_t n, float lr, float clip, float bc1,
                                                          float sqrt_bc2) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    float gv = fminf(fmaxf(g[i], -clip), clip);
-    const float mn = m[i] * b1 + gv * (1.f - b1);
-    const float vn = v[i] * b2 + (gv * gv) * (1.f - b2);
-    m[i] = mn;
-    v[i] = vn;
-    const float denom = sqrtf(vn) / sqrt_bc2 + eps;
-    p[i] = p[i] - (lr / bc1) * (mn / denom);
+    float me = m[i], ve = v[i], pe = p[i];
+    adam_clamp_update(g[i], me, ve, pe, lr, clip, bc1, sqrt_bc2);
+    m[i] = me;
+    v[i] = ve;
+    p[i] = pe;
 }
 
 }  // namespace
