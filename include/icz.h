@@ -873,6 +873,63 @@ int icz_test_colsum(int32_t multi, int32_t count, const float* const* X, const i
 int icz_test_timesum(const float* X, int32_t T, int64_t BN, float* out, void* stream);
 /* out[i, n] = sum_{k < G} X[(i * G + k) * N + n], i < n_img, n < N, added in k order (N a multiple of 4). */
 int icz_test_rowgroup_sum(const float* X, int32_t n_img, int32_t G, int64_t N, float* out, void* stream);
+/* Test entries for the kernels of one beam-search step and of the final selection, each on given logits and a given search state
+ * (tests/test_gpu_beam_step.py): the library's kernels through the launch code and the grids of every icz_*_beam_search entry.  All data
+ * pointers are DEVICE pointers.  Every entry checks its arguments on the host and returns ICZ_ERR_INVALID without launching on: k outside
+ * 1..8, groups not dividing k, step (steps_done) outside 1..256 or L <= step, ngram not in {0, 2, 3, 4}, compact other than 0 or (1 at
+ * step 1), V < 1 or ldl < V, a forced route that cannot take the shape, null pointers.  (n_act holds device data: at most k per image, at
+ * most k / groups per group.)
+ *
+ * The kernel that picks a row's candidates: route 1 = beam_rowtopk_reg_kernel<3> (V <= 3072), 2 = beam_rowtopk_reg_kernel<10>
+ * (V <= 10240), both with 16-byte loads: ldl % 4 == 0, ldl >= V rounded up to 4, a 16-byte aligned base; 3 = the sweep kernel
+ * beam_rowtopk_kernel (any V, ldl and base; compiled with the ban test from step ngram on).  Route 0 = what a search takes, the first
+ * of 1, 2, 3 that fits -- icz_beam_rowtopk_route_for says which (host logic only, no GPU needed; base_aligned: whether the logits start
+ * on 16 bytes); ICZ_ERR_INVALID for V < 1 or ldl < V. */
+int icz_beam_rowtopk_route_for(int32_t V, int32_t ldl, int32_t base_aligned);
+/* Row top-k of step `step`: for every scored row (row = img * k + r; plain: r < n_act[img], at step 1 row 0 only; grouped: n_act
+ * [n_img, groups], see icz_beam_diversity) its best n candidates by (run[row] + log_softmax(logits[row, :V]) descending, token
+ * ascending), n = n_act[img] (grouped: min(k, n_act[img, 0] + ... + n_act[img, g]); step 1: k), into cand_val / cand_idx [n_img * k, 8];
+ * a slot without an admissible token holds index 0x7fffffff; every other slot is left untouched.  logits [rows, ldl] (compact = 1, step 1
+ * only: one row per image); run is not read at step 1; ngram > 0: tokens banned by the prefixes seqs_in [n_img * k, L] score -inf. */
+int icz_test_beam_rowtopk(int32_t route, const float* logits, int32_t n_img, int32_t k, int32_t V, int32_t ldl, int32_t step, const int32_t* n_act,
+                          const float* run, int32_t compact, const int32_t* seqs_in, int32_t L, int32_t ngram, int32_t groups, float* cand_val,
+                          int32_t* cand_idx, void* stream);
+/* The state one step of a search reads and writes (BeamBuf, csrc/decoder_core.h): n_act [n_img] (grouped [n_img, groups]), run [n_img * k],
+ * seqs_in / seqs_out [n_img * k, L] (distinct), src_row [n_img * k], it_next [n_img * k], best_* / has_complete per image (best_seq
+ * [n_img, L]), n_live one word the step adds its live images to, the n-best list hyp_seq [n_img * k, L], hyp_score / hyp_len [n_img * k],
+ * hyp_cnt [n_img] (all four null: no list; a grouped step needs it), and the candidate scratch cand_val / cand_idx [n_img * k, 8]. */
+typedef struct {
+    const float* logits;
+    int32_t* n_act;
+    float* run;
+    const int32_t* seqs_in;
+    int32_t* seqs_out;
+    int32_t* src_row;
+    int64_t* it_next;
+    float* best_score;
+    int32_t* best_len;
+    int32_t* best_seq;
+    int32_t* has_complete;
+    int32_t* n_live;
+    int32_t* hyp_seq;
+    float* hyp_score;
+    int32_t* hyp_len;
+    int32_t* hyp_cnt;
+    float* cand_val;
+    int32_t* cand_idx;
+} icz_beam_step_state;
+/* One whole step: the row top-k (route as above), then beam_merge_kernel (groups == 1, lambda == 0) or beam_merge_groups_kernel (groups
+ * > 1, lambda = the diversity penalty, >= 0 and finite). */
+int icz_test_beam_step(int32_t route, const icz_beam_step_state* s, int32_t n_img, int32_t k, int32_t V, int32_t ldl, int32_t step, int32_t L,
+                       int32_t compact, int32_t ngram, int32_t groups, float lambda, void* stream);
+/* The final selection on a given state: form 0 = beam_finalize_kernel (n_best 1; scores may be null), 1 = beam_finalize_nbest_kernel<false>,
+ * 2 = beam_finalize_nbest_kernel<true> (n_act [n_img, groups]); forms 1 and 2 check n_best, lp_kind and lp_alpha as icz_beam_opts.  seqs
+ * [n_img * k, L] = the live beams after steps_done steps; out [n_img, n_best, L] float32, lens / scores [n_img, n_best].  Pointers a form
+ * does not read may be null. */
+int icz_test_beam_finalize(int32_t form, int32_t n_img, int32_t k, int32_t L, int32_t steps_done, int32_t n_best, int32_t lp_kind, float lp_alpha,
+                           int32_t groups, const int32_t* n_act, const float* run, const int32_t* seqs, const int32_t* has_complete,
+                           const float* best_score, const int32_t* best_len, const int32_t* best_seq, const int32_t* hyp_cnt, const float* hyp_score,
+                           const int32_t* hyp_len, const int32_t* hyp_seq, float* out, int32_t* lens, float* scores, void* stream);
 /* Live timing of the dominant kernel (the forward GEMMs of a decoder step at 33..64 rows: gemm_resident_x3_kernel, or
  * gemm_nt_kernel<4, ...> with ICZ_GEMM_RESIDENT_X3=0; see icz_prof_select) with HIP events on its launch stream, for bench.py's
  * roofline line.  Between begin and end every launch is bracketed by an event

@@ -103,6 +103,14 @@ class BeamDiversity(C.Structure):  # icz_beam_diversity
     _fields_ = [("groups", C.c_int32), ("diversity", C.c_float)]
 
 
+BEAM_STEP_FIELDS = ("logits", "n_act", "run", "seqs_in", "seqs_out", "src_row", "it_next", "best_score", "best_len", "best_seq",
+                    "has_complete", "n_live", "hyp_seq", "hyp_score", "hyp_len", "hyp_cnt", "cand_val", "cand_idx")
+
+
+class BeamStepState(C.Structure):  # icz_beam_step_state
+    _fields_ = [(n, C.c_void_p) for n in BEAM_STEP_FIELDS]
+
+
 class SampleOpts(C.Structure):     # icz_sample_opts
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
 
@@ -271,6 +279,10 @@ def lib():
         "icz_test_colsum": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "icz_test_timesum": (C.c_int, [vp, i32, i64, vp, vp]),
         "icz_test_rowgroup_sum": (C.c_int, [vp, i32, i32, i64, vp, vp]),
+        "icz_beam_rowtopk_route_for": (C.c_int, [i32, i32, i32]),
+        "icz_test_beam_rowtopk": (C.c_int, [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
+        "icz_test_beam_step": (C.c_int, [i32, C.POINTER(BeamStepState), i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
+        "icz_test_beam_finalize": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, f32, i32] + [vp] * 15),
     }
     for name, (res, args) in sig.items():
         try:

@@ -7,7 +7,7 @@ import numbers
 
 import torch
 
-from ._lib import BeamDiversity, BeamOpts, check, ptr, stream_ptr
+from ._lib import BEAM_STEP_FIELDS, BeamDiversity, BeamOpts, BeamStepState, check, lib, ptr, stream_ptr
 
 LP_KINDS = {"avg": 1, "wu": 2}
 
@@ -87,6 +87,37 @@ def search(entries, handle, feats, beam_size, max_steps, opts, div):
     if div.groups == 1:
         return search_opts(entries.beam_search_opts, handle, feats, beam_size, max_steps, opts)
     return search_diverse(entries.beam_search_diverse, handle, feats, beam_size, max_steps, opts, div)
+
+
+def rowtopk_route_for(V, ldl, base_aligned=True):
+    """The kernel a search's row top-k takes (icz_beam_rowtopk_route_for, host only): 1 register <3>, 2 register <10>, 3 sweep."""
+    r = lib().icz_beam_rowtopk_route_for(int(V), int(ldl), int(bool(base_aligned)))
+    if r < 0:
+        check(r)
+    return r
+
+
+def entry_rowtopk(route, logits, n_img, k, V, ldl, step, n_act, run, compact, seqs_in, L, ngram, groups, cand_val, cand_idx):
+    """Test entry icz_test_beam_rowtopk: the row top-k kernel of `route` on device tensors (include/icz.h)."""
+    check(lib().icz_test_beam_rowtopk(int(route), ptr(logits), int(n_img), int(k), int(V), int(ldl), int(step), ptr(n_act), ptr(run), int(compact),
+                                      ptr(seqs_in), int(L), int(ngram), int(groups), ptr(cand_val), ptr(cand_idx), stream_ptr()))
+
+
+def entry_step(route, state, n_img, k, V, ldl, step, L, compact=0, ngram=0, groups=1, lam=0.0):
+    """Test entry icz_test_beam_step: row top-k + merge on `state`, a dict of device tensors keyed as icz_beam_step_state (a missing or
+    None entry is a null pointer)."""
+    s = BeamStepState(*[None if state.get(n) is None else state[n].data_ptr() for n in BEAM_STEP_FIELDS])
+    check(lib().icz_test_beam_step(int(route), C.byref(s), int(n_img), int(k), int(V), int(ldl), int(step), int(L), int(compact), int(ngram),
+                                   int(groups), float(lam), stream_ptr()))
+
+
+def entry_finalize(form, n_img, k, L, steps_done, n_best, lp_kind, lp_alpha, groups, n_act, run, seqs, has_complete, best_score, best_len,
+                  best_seq, hyp_cnt, hyp_score, hyp_len, hyp_seq, out, lens, scores):
+    """Test entry icz_test_beam_finalize: form 0 best hypothesis, 1 n-best, 2 grouped n-best, on device tensors (None: null)."""
+    check(lib().icz_test_beam_finalize(int(form), int(n_img), int(k), int(L), int(steps_done), int(n_best), int(lp_kind), float(lp_alpha),
+                                       int(groups), ptr(n_act), ptr(run), ptr(seqs), ptr(has_complete), ptr(best_score), ptr(best_len),
+                                       ptr(best_seq), ptr(hyp_cnt), ptr(hyp_score), ptr(hyp_len), ptr(hyp_seq), ptr(out), ptr(lens), ptr(scores),
+                                       stream_ptr()))
 
 
 def nbest_lists(seqs, lens, scores):

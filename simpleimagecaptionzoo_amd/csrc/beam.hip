@@ -100,7 +100,7 @@ int BeamBuf::search(DecodeMember* const* m, int M, const BeamCombine* ens, int n
         BeamArgs a = {ens ? ens->lp : lv[0].p, V, ens ? ens->ld : lv[0].ld, k, s, L, n_act, run, seqs[sb], seqs[sb ^ 1], src_row, it, best_score,
                       best_len, best_seq, has_complete, n_live + s, listed ? hyp_seq : nullptr, hyp_score, hyp_len, listed ? hyp_cnt : nullptr};
         launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)n_act, (const float*)run, cand_val, cand_idx,
-                            compact ? 1 : 0, seqs[sb], L, o.block_ngram, G);
+                            compact ? 1 : 0, seqs[sb], L, o.block_ngram, G, BEAM_ROUTE_AUTO);
         if (G > 1)
             hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(n_img), dim3(64), 0, st, a, G, d.diversity, (const float*)cand_val,
                                (const int*)cand_idx);
@@ -225,6 +225,103 @@ int icz_nic_beam_search_diverse(icz_nic_t* h, const float* features, int32_t n_i
                                 const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
     return beam_entry(BEAM_DIVERSE, "icz_nic_beam_search_diverse", "nic", nic_member(h), features, n_img, beam, max_steps, opts, div, seqs_out, lens_out,
                       scores_out, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Test entries of the beam step's kernels (include/icz.h): the arguments are checked on the host, then the kernels are launched through
+// launch_beam_rowtopk and with the grids of BeamBuf::search, nothing more.
+static int beam_test_shape(const char* who, int route, const float* logits, int n_img, int k, int V, int ldl, int step, int L, int compact,
+                           int ngram, int groups) {
+    ICZ_REQUIRE(k >= 1 && k <= BEAM_MAX_K, "%s: beam size k=%d outside 1..%d", who, k, BEAM_MAX_K);
+    ICZ_REQUIRE(groups >= 1 && groups <= k && k % groups == 0, "%s: groups=%d outside 1..k (%d) or not dividing it", who, groups, k);
+    ICZ_REQUIRE(n_img >= 1 && (long)n_img * k <= (1 << 20), "%s: n_img=%d", who, n_img);
+    ICZ_REQUIRE(step >= 1 && step <= 256 && L > step, "%s: step=%d outside 1..256 or not below L=%d", who, step, L);
+    ICZ_REQUIRE(ngram == 0 || (ngram >= 2 && ngram <= 4), "%s: ngram=%d not 0, 2, 3 or 4", who, ngram);
+    ICZ_REQUIRE(compact == 0 || (compact == 1 && step == 1), "%s: compact=%d at step %d (0, or 1 at step 1)", who, compact, step);
+    ICZ_REQUIRE(V >= 1 && ldl >= V && (long)V * k < 0x7fffffff, "%s: V=%d, ldl=%d", who, V, ldl);
+    ICZ_REQUIRE(route >= BEAM_ROUTE_AUTO && route <= BEAM_ROUTE_SWEEP, "%s: route=%d", who, route);
+    ICZ_REQUIRE(beam_rowtopk_route_fits(route, V, ldl, ((uintptr_t)logits & 15) == 0),
+                "%s: route %d cannot take V=%d, ldl=%d, base %s (register kernels: 16-byte rows of at least V rounded up to 4, V <= %d)", who,
+                route, V, ldl, ((uintptr_t)logits & 15) == 0 ? "aligned" : "not 16-byte aligned", route == BEAM_ROUTE_REG3 ? 3072 : 10240);
+    return ICZ_OK;
+}
+
+int icz_beam_rowtopk_route_for(int32_t V, int32_t ldl, int32_t base_aligned) {
+    ICZ_REQUIRE(V >= 1 && ldl >= V, "icz_beam_rowtopk_route_for: V=%d, ldl=%d", V, ldl);
+    return beam_rowtopk_route(V, ldl, base_aligned != 0);
+}
+
+int icz_test_beam_rowtopk(int32_t route, const float* logits, int32_t n_img, int32_t k, int32_t V, int32_t ldl, int32_t step, const int32_t* n_act,
+                          const float* run, int32_t compact, const int32_t* seqs_in, int32_t L, int32_t ngram, int32_t groups, float* cand_val,
+                          int32_t* cand_idx, void* stream) {
+    const char* who = "icz_test_beam_rowtopk";
+    ICZ_REQUIRE(logits && n_act && run && cand_val && cand_idx && (seqs_in || !ngram), "%s: null argument", who);
+    ICZ_TRY(beam_test_shape(who, route, logits, n_img, k, V, ldl, step, L, compact, ngram, groups));
+    launch_beam_rowtopk((hipStream_t)stream, n_img * k, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups,
+                        route);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int icz_test_beam_step(int32_t route, const icz_beam_step_state* s, int32_t n_img, int32_t k, int32_t V, int32_t ldl, int32_t step, int32_t L,
+                       int32_t compact, int32_t ngram, int32_t groups, float lambda, void* stream) {
+    const char* who = "icz_test_beam_step";
+    ICZ_REQUIRE(s, "%s: null state", who);
+    ICZ_REQUIRE(s->logits && s->n_act && s->run && s->seqs_in && s->seqs_out && s->src_row && s->it_next && s->best_score && s->best_len &&
+                    s->best_seq && s->has_complete && s->n_live && s->cand_val && s->cand_idx,
+                "%s: null argument", who);
+    const bool listed = s->hyp_seq && s->hyp_score && s->hyp_len && s->hyp_cnt;
+    ICZ_REQUIRE(listed || (!s->hyp_seq && !s->hyp_score && !s->hyp_len && !s->hyp_cnt), "%s: the n-best list is four pointers or none", who);
+    ICZ_REQUIRE(s->seqs_in != s->seqs_out, "%s: seqs_in and seqs_out are the same buffer", who);
+    ICZ_TRY(beam_test_shape(who, route, s->logits, n_img, k, V, ldl, step, L, compact, ngram, groups));
+    ICZ_REQUIRE(groups == 1 || listed, "%s: a grouped step needs the n-best list", who);
+    ICZ_REQUIRE(std::isfinite(lambda) && lambda >= 0.f && (groups > 1 || lambda == 0.f), "%s: lambda=%g negative, not finite, or without groups", who,
+                (double)lambda);
+    hipStream_t st = (hipStream_t)stream;
+    BeamArgs a = {s->logits, V, ldl, k, step, L, s->n_act, s->run, s->seqs_in, s->seqs_out, s->src_row, s->it_next, s->best_score, s->best_len,
+                  s->best_seq, s->has_complete, s->n_live, s->hyp_seq, s->hyp_score, s->hyp_len, s->hyp_cnt};
+    launch_beam_rowtopk(st, n_img * k, a.logits, V, ldl, k, step, (const int*)s->n_act, (const float*)s->run, s->cand_val, s->cand_idx, compact,
+                        s->seqs_in, L, ngram, groups, route);
+    if (groups > 1)
+        hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(n_img), dim3(64), 0, st, a, groups, lambda, (const float*)s->cand_val,
+                           (const int*)s->cand_idx);
+    else
+        hipLaunchKernelGGL(beam_merge_kernel, dim3(n_img), dim3(64), 0, st, a, (const float*)s->cand_val, (const int*)s->cand_idx);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int icz_test_beam_finalize(int32_t form, int32_t n_img, int32_t k, int32_t L, int32_t steps_done, int32_t n_best, int32_t lp_kind, float lp_alpha,
+                           int32_t groups, const int32_t* n_act, const float* run, const int32_t* seqs, const int32_t* has_complete,
+                           const float* best_score, const int32_t* best_len, const int32_t* best_seq, const int32_t* hyp_cnt, const float* hyp_score,
+                           const int32_t* hyp_len, const int32_t* hyp_seq, float* out, int32_t* lens, float* scores, void* stream) {
+    const char* who = "icz_test_beam_finalize";
+    ICZ_REQUIRE(form >= 0 && form <= 2, "%s: form=%d (0 best, 1 n-best, 2 grouped n-best)", who, form);
+    ICZ_REQUIRE(k >= 1 && k <= BEAM_MAX_K, "%s: beam size k=%d outside 1..%d", who, k, BEAM_MAX_K);
+    ICZ_REQUIRE(groups >= 1 && groups <= k && k % groups == 0 && (form == 2 || groups == 1), "%s: groups=%d outside 1..k (%d), not dividing it, or on form %d",
+                who, groups, k, form);
+    ICZ_REQUIRE(n_img >= 1 && (long)n_img * k <= (1 << 20), "%s: n_img=%d", who, n_img);
+    ICZ_REQUIRE(steps_done >= 1 && steps_done <= 256 && L > steps_done, "%s: steps_done=%d outside 1..256 or not below L=%d", who, steps_done, L);
+    ICZ_REQUIRE(n_act && run && seqs && out && lens, "%s: null argument", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (form == 0) {
+        ICZ_REQUIRE(has_complete && best_len && best_seq && (best_score || !scores), "%s: null argument", who);
+        ICZ_REQUIRE(n_best == 1, "%s: n_best=%d on form 0", who, n_best);
+        hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_act, run, seqs, has_complete, best_len, best_seq,
+                           out, lens, best_score, scores);
+    } else {
+        const icz_beam_opts o = {n_best, 0, lp_kind, lp_alpha};
+        ICZ_TRY(BeamBuf::check_opts(who, k, &o));
+        ICZ_REQUIRE(hyp_cnt && hyp_score && hyp_len && hyp_seq && scores, "%s: null argument", who);
+        if (form == 2)
+            hipLaunchKernelGGL(beam_finalize_nbest_kernel<true>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_best, lp_kind, lp_alpha, n_act, run,
+                               seqs, hyp_cnt, hyp_score, hyp_len, hyp_seq, out, lens, scores, groups);
+        else
+            hipLaunchKernelGGL(beam_finalize_nbest_kernel<false>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_best, lp_kind, lp_alpha, n_act, run,
+                               seqs, hyp_cnt, hyp_score, hyp_len, hyp_seq, out, lens, scores, 1);
+    }
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
 }
 
 }  // extern "C"

@@ -346,21 +346,34 @@ __global__ __launch_bounds__(256) void beam_rowtopk_reg_kernel(const float* __re
 
 // per-row candidates of one beam step: the register kernel where the vocabulary fits it, else the sweep kernel
 // (ngram > 0: n-gram blocking on the prefixes seqs_in [rows, L]; groups > 1: the grouped instances, n_act [n_img, groups])
+// The one owner of that choice (icz_beam_rowtopk_route_for is its host entry): the register kernels move 16 bytes at a time, so
+// they need rows that start on 16 bytes (aligned base, ldl % 4 == 0) and a vocabulary of at most 1024 NV4 tokens.
+enum { BEAM_ROUTE_AUTO = 0, BEAM_ROUTE_REG3 = 1, BEAM_ROUTE_REG10 = 2, BEAM_ROUTE_SWEEP = 3 };
+inline int beam_rowtopk_route(int V, int ldl, bool base_aligned) {
+    const bool ok = ldl % 4 == 0 && base_aligned;
+    return ok && V <= 1024 * 3 ? BEAM_ROUTE_REG3 : ok && V <= 1024 * 10 ? BEAM_ROUTE_REG10 : BEAM_ROUTE_SWEEP;
+}
+inline bool beam_rowtopk_route_fits(int route, int V, int ldl, bool base_aligned) {      // whether a forced route can take the shape
+    if (route == BEAM_ROUTE_REG3 || route == BEAM_ROUTE_REG10)
+        return ldl % 4 == 0 && ldl >= ((V + 3) & ~3) && base_aligned && V <= 1024 * (route == BEAM_ROUTE_REG3 ? 3 : 10);
+    return route == BEAM_ROUTE_AUTO || route == BEAM_ROUTE_SWEEP;
+}
+// route: BEAM_ROUTE_AUTO (every search) or a kernel forced by icz_test_beam_rowtopk / icz_test_beam_step, which check that it fits
 template <bool GROUPED>
 inline void launch_beam_rowtopk_t(hipStream_t st, int rows, const float* logits, int V, int ldl, int k, int step, const int* n_act,
                                   const float* run, float* cand_val, int* cand_idx, int compact, const int32_t* seqs_in, int L,
-                                  int ngram, int groups) {
-    const bool ok = ldl % 4 == 0 && ((uintptr_t)logits & 15) == 0;
-    if (ok && V <= 1024 * 3) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<3, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 3, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
-    else if (ok && V <= 1024 * 10) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<10, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 10, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
+                                  int ngram, int groups, int route) {
+    const int r = route != BEAM_ROUTE_AUTO ? route : beam_rowtopk_route(V, ldl, ((uintptr_t)logits & 15) == 0);
+    if (r == BEAM_ROUTE_REG3) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<3, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 3, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
+    else if (r == BEAM_ROUTE_REG10) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<10, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 10, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
     else if (ngram && step >= ngram) hipLaunchKernelGGL((beam_rowtopk_kernel<true, GROUPED>), dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
     else hipLaunchKernelGGL((beam_rowtopk_kernel<false, GROUPED>), dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
 }
 inline void launch_beam_rowtopk(hipStream_t st, int rows, const float* logits, int V, int ldl, int k, int step, const int* n_act,
                                 const float* run, float* cand_val, int* cand_idx, int compact = 0, const int32_t* seqs_in = nullptr,
-                                int L = 0, int ngram = 0, int groups = 1) {
-    if (groups > 1) launch_beam_rowtopk_t<true>(st, rows, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
-    else launch_beam_rowtopk_t<false>(st, rows, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, 1);
+                                int L = 0, int ngram = 0, int groups = 1, int route = BEAM_ROUTE_AUTO) {
+    if (groups > 1) launch_beam_rowtopk_t<true>(st, rows, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups, route);
+    else launch_beam_rowtopk_t<false>(st, rows, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, 1, route);
 }
 
 __global__ __launch_bounds__(64) void beam_merge_kernel(BeamArgs a, const float* __restrict__ cand_val, const int* __restrict__ cand_idx) {
