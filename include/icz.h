@@ -85,6 +85,9 @@ int icz_butd_bind_params(icz_butd_t* h, const icz_butd_params* params);
  * "small_nt" (default 1): BPTT steps of <= 32 rows (small batches, the short tail of an XE batch) take their per-step dgrad products on
  * the transposed LSTM weight copies through the fp32 NT kernel instead of NN products on the weights (which stream at half the rate
  * at so few rows); 0 = the NN products of rounds 1 - 4.  Gradients agree to fp32 rounding.
+ * "fused_dh1" (default 1, ICZ_BPTT_FUSED_DH1): BPTT steps of <= 64 rows whose widths the kernel takes (H in whole groups of 16, A of 64)
+ * form X2 = d dec . w_dec inside the TD-LSTM backward launch instead of writing it as split-K slabs for that launch to read back: six
+ * launches per step, not seven; 0 = the two launches.  Every gradient and the loss are bitwise the same: an A/B switch.
  * "group_att" (default 0): 1 = icz_butd_sample_n's attention runs on the grouped kernels (the K rows of an image in one workgroup:
  * scores, context and, in its backward, d enc_ctx read each image's features / projected features once); 0 = the per-row kernels,
  * which find the image of each row through an index (measured faster).  Ids and log-probs are bitwise the same;
@@ -873,6 +876,21 @@ int icz_test_colsum(int32_t multi, int32_t count, const float* const* X, const i
 int icz_test_timesum(const float* X, int32_t T, int64_t BN, float* out, void* stream);
 /* out[i, n] = sum_{k < G} X[(i * G + k) * N + n], i < n_img, n < N, added in k order (N a multiple of 4). */
 int icz_test_rowgroup_sum(const float* X, int32_t n_img, int32_t G, int64_t N, float* out, void* stream);
+/* One "X2 = d dec . w_dec, then the TD-LSTM backward" step of the BUTD reverse-time loop on given buffers (tests/test_gpu_bptt_fused_step.py):
+ * arguments filled as the loop fills them, and either lstm_bwd_dh1_fused_kernel (route 1; ICZ_ERR_INVALID unless rows <= 64, H % 16 == 0,
+ * A % 64 == 0) or the NN product into split-K slabs followed by lstm_bwd_point_kernel (route 0), or whichever the loop takes with the
+ * option "fused_dh1" on (route -1), reported in *route_out (optional).  *nsplit_out (optional): the K ranges the library cuts the
+ * product into for the shape, which both routes follow.  With dh1 = (carry ? sum of the ns_carry slabs carry[z][rows_carry][H] at rows <
+ * rows_carry : 0) + sum of the ns_x1 slabs x1[z][rows][ld_x1] (columns 0..H of each row: pass the pointer at the column offset) + sum
+ * over the ranges of d dec[rows, A] . w_dec[A, H]:  dc = (dc_in [rows_carry, H], optional, rows < rows_carry) + dh1 o (1 - tanh^2 c_cur),
+ * dgates [rows, 4H] = d(pre-activation i, f, g, o) from the activated gates [rows, 4H], c_prev [rows, H] (optional: zeros) and c_cur,
+ * dc_prev [rows, H] = dc f.  live / carry_live: optional device int32 flags; *live == 0 writes zero dgates rows and nothing else,
+ * *carry_live == 0 drops carry and dc_in.  x2_slabs / x2_floats: the two-launch route's slab buffer (route 1 does not touch it).
+ * rows 1..64, H and A multiples of 4, ld_x1 >= H, ddec / w_dec / x2_slabs 16-byte aligned. */
+int icz_test_bptt_dh1_step(int32_t route, int32_t rows, int32_t H, int32_t A, const float* ddec, const float* w_dec, const float* carry,
+                           int32_t ns_carry, int32_t rows_carry, const float* x1, int32_t ns_x1, int32_t ld_x1, const float* dc_in,
+                           const float* gates, const float* c_prev, const float* c_cur, float* dgates, float* dc_prev, const int32_t* live,
+                           const int32_t* carry_live, float* x2_slabs, size_t x2_floats, int32_t* nsplit_out, int32_t* route_out, void* stream);
 /* Test entries for the kernels of one beam-search step and of the final selection, each on given logits and a given search state
  * (tests/test_gpu_beam_step.py): the library's kernels through the launch code and the grids of every icz_*_beam_search entry.  All data
  * pointers are DEVICE pointers.  Every entry checks its arguments on the host and returns ICZ_ERR_INVALID without launching on: k outside

@@ -279,6 +279,7 @@ def lib():
         "icz_test_colsum": (C.c_int, [i32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "icz_test_timesum": (C.c_int, [vp, i32, i64, vp, vp]),
         "icz_test_rowgroup_sum": (C.c_int, [vp, i32, i32, i64, vp, vp]),
+        "icz_test_bptt_dh1_step": (C.c_int, [i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, i32, i32] + [vp] * 9 + [C.c_size_t, C.POINTER(i32), C.POINTER(i32), vp]),
         "icz_beam_rowtopk_route_for": (C.c_int, [i32, i32, i32]),
         "icz_test_beam_rowtopk": (C.c_int, [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
         "icz_test_beam_step": (C.c_int, [i32, C.POINTER(BeamStepState), i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),

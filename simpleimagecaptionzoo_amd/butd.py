@@ -241,6 +241,18 @@ def rowgroup_sum(X, n_img, G, N, out):
     check(lib().icz_test_rowgroup_sum(ptr(X), int(n_img), int(G), int(N), ptr(out), stream_ptr()))
 
 
+def bptt_dh1_step(route, rows, H, A, ddec, w_dec, x1, ns_x1, ld_x1, gates, c_cur, dgates, dc_prev, carry=None, ns_carry=0, rows_carry=0,
+                  dc_in=None, c_prev=None, live=None, carry_live=None, x2_slabs=None):
+    """Test entry for icz_test_bptt_dh1_step: one "X2, then the TD-LSTM backward" step of the BUTD reverse-time loop; route 1 = the fused
+    kernel, 0 = the two launches, -1 = as the loop picks.  Returns (K ranges the library picks for the shape, route taken)."""
+    ns, taken = C.c_int32(0), C.c_int32(-1)
+    check(lib().icz_test_bptt_dh1_step(int(route), int(rows), int(H), int(A), ptr(ddec), ptr(w_dec), ptr(carry), int(ns_carry), int(rows_carry),
+                                       ptr(x1), int(ns_x1), int(ld_x1), ptr(dc_in), ptr(gates), ptr(c_prev), ptr(c_cur), ptr(dgates), ptr(dc_prev),
+                                       ptr(live), ptr(carry_live), ptr(x2_slabs), 0 if x2_slabs is None else x2_slabs.numel(), C.byref(ns),
+                                       C.byref(taken), stream_ptr()))
+    return int(ns.value), int(taken.value)
+
+
 def adam_clamp_step(p, g, m, v, n, lr, clip, step):
     """icz_adam_clamp_step on the first n floats of four tensors (views at any offset)."""
     check(lib().icz_adam_clamp_step(ptr(p), ptr(g), ptr(m), ptr(v), int(n), float(lr), float(clip), int(step), stream_ptr()))

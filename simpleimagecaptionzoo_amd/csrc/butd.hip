@@ -53,8 +53,9 @@ int Butd::init(const icz_butd_dims& d, int r_max) {
     }
     ICZ_TRY(alloc((void**)&ws, sizeof(float) * ws_floats));
     ICZ_TRY(mem.synced());
-    // defaults of the options "early_out" / "merge_small" from the environment (A/B runs of whole programs; icz_butd_set_option overrides)
+    // defaults of the options "early_out" / "fused_dh1" / "merge_small" from the environment (A/B runs of whole programs; icz_butd_set_option overrides)
     if (const char* e = getenv("ICZ_EARLY_OUT")) early_out = atoi(e) != 0;
+    if (const char* e = getenv("ICZ_BPTT_FUSED_DH1")) fused_dh1 = atoi(e) != 0;
     if (const char* e = getenv("ICZ_MERGE_SMALL")) { const int n = atoi(e); if (n >= 0 && n <= 32) merge_small = n; }
     return ICZ_OK;
 }
@@ -338,6 +339,7 @@ int icz_butd_set_option(icz_butd_t* h, const char* name, int32_t value) {
     if (strcmp(name, "concurrent") == 0) { b->concurrent = value != 0; return ICZ_OK; }
     if (strcmp(name, "early_out") == 0) { b->early_out = value != 0; return ICZ_OK; }
     if (strcmp(name, "small_nt") == 0) { b->small_nt = value != 0; return ICZ_OK; }
+    if (strcmp(name, "fused_dh1") == 0) { b->fused_dh1 = value != 0; return ICZ_OK; }
     if (strcmp(name, "group_att") == 0) { b->group_att = value != 0; return ICZ_OK; }
     if (strcmp(name, "merge_small") == 0) {
         ICZ_REQUIRE(value >= 0 && value <= 32, "icz_butd_set_option: merge_small %d outside 0..32", value);

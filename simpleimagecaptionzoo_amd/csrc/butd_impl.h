@@ -113,7 +113,7 @@ struct Butd : CaptionHead, DecodeMember {
     bool graphs_on() const { return use_graphs && !cnt; }       // calls made while counts are set stay eager (as AoA's do)
     bool concurrent = true;      // run independent chains on side streams (off: one stream, for per-kernel timing)
     uintptr_t opt_bits() const {         // the options that change the captured launch sequence, and the row stride of the region tensors
-        return (concurrent ? 1 : 0) + (early_out ? 2 : 0) + 4 * merge_small + (small_nt ? 256 : 0) + (group_att ? 512 : 0) + ((uintptr_t)cur_R << 16);
+        return (concurrent ? 1 : 0) + (early_out ? 2 : 0) + 4 * merge_small + (small_nt ? 256 : 0) + (group_att ? 512 : 0) + (fused_dh1 ? 1024 : 0) + ((uintptr_t)cur_R << 16);
     }
     int greedy_impl(const float* feats, int B, int max_len, int64_t* ids_out, float* alphas_out, hipStream_t st);
     int sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st);
@@ -136,6 +136,9 @@ struct Butd : CaptionHead, DecodeMember {
     bool early_out = true;               // option "early_out": 0 = run the steps behind the reference's break as rounds 1 - 4 did (A/B)
     bool bptt_early_out = false;         // backward of a sampled rollout: steps behind the reference's break return at entry (bptt)
     bool small_nt = true;                // option "small_nt": BPTT steps of <= 32 rows take their dgrad products on the transposed weight copies (fp32 NT kernel)
+    bool fused_dh1 = true;               // option "fused_dh1": BPTT steps of <= 64 rows at widths lstm_bwd_dh1_fused_takes accepts form X2 = d dec . w_dec
+                                         // inside the TD-LSTM backward launch (six launches per step); 0 = the product and the pointwise
+                                         // kernel as two launches (seven).  The same bits either way
     // multi-sample SCST rollout (sample_n, beyond the reference): K sampled rows per image, row = img * K + k, sharing the image's
     // hoisted tensors.  cur_K = rows per image of the stored rollout (1 = every other entry point), cur_nimg = its image count.
     int cur_K = 1, cur_nimg = 0;

@@ -575,6 +575,26 @@ int Butd::bptt_predict(BpttCall& c) {
     return ICZ_OK;
 }
 
+// ---- "X2 = d dec . w_dec, then the TD-LSTM backward" as one launch (lstm_bwd_dh1_fused_kernel, butd_kernels.h).  Its K ranges are
+//      the two-launch route's: the split gemm_auto gives the same product, in the stage depth gemm_f32 takes for it.
+static int dh1_split(int rows, int H, int A) {
+    const GemmArgs g = gemm_args({{nullptr, nullptr, A, H, A}}, rows, H, nullptr, H);      // shapes only
+    return gemm_split(GEMM_NN, g, split_backward(Butd::STEP_WGS), 0);
+}
+static int launch_dh1_fused(const LstmBwdArgs& p, const float* ddec, const float* w_dec, int A, hipStream_t st) {
+    ICZ_REQUIRE(lstm_bwd_dh1_fused_takes(p.rows, p.H, A), "butd: the fused d h1 step does not take rows=%d, H=%d, A=%d", p.rows, p.H, A);
+    const int bkc = lstm_bwd_dh1_stage_k(A), tot = A / bkc, ns = dh1_split(p.rows, p.H, A);
+    ICZ_REQUIRE(ns >= 1 && ns <= DH1_MAX_SPLIT && ns <= tot, "butd: the fused d h1 step cannot mirror %d K ranges over %d stages", ns, tot);
+    const int cps = cdiv(tot, ns);
+    ICZ_REQUIRE(cdiv(tot, cps) == ns, "butd: the fused d h1 step cannot mirror %d K ranges over %d stages", ns, tot);
+    const Dh1FusedArgs f = {p, ddec, w_dec, A, ns, cps};
+    const dim3 grid(p.H / DH1_TILE, cdiv(p.rows, DH1_TILE));
+    if (bkc == 128) hipLaunchKernelGGL(lstm_bwd_dh1_fused_kernel<128>, grid, dim3(256), 0, st, f);
+    else hipLaunchKernelGGL(lstm_bwd_dh1_fused_kernel<64>, grid, dim3(256), 0, st, f);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
 // ---- the reverse-time loop: per step the pointwise LSTM / attention backward kernels and the dgrad products between them
 int Butd::bptt_loop(BpttCall& c) {
     const int B = c.B, T = c.T, Bs = c.Bs, roff = c.roff;
@@ -620,6 +640,9 @@ int Butd::bptt_loop(BpttCall& c) {
         // The route selects only the weight operand and the layout of a per-step dgrad product dx = d gates . W over K = 4H: rdg and tdg
         // take the transposed copy (NT), else W itself (NN).  Each product leaves ns slabs [bt, N] (one: dense) in its tb.X buffer.
         const GemmLayout lay = (rdg || tdg) ? GEMM_NT : GEMM_NN;
+        // X2 and the TD-LSTM backward as one launch (option "fused_dh1"), whatever route the other products take; steps the kernel
+        // does not take -- more than 64 rows, other widths -- keep the two launches
+        const bool fdh = fused_dh1 && lstm_bwd_dh1_fused_takes(bt, H, A);
         const float* const dglm = tb.dGlm + slot * 4 * H;
         const float* const dgtd = tb.dGtd + slot * 4 * H;      // (written by this step's TD-LSTM kernel below, before the products that read it)
         auto wseg = [&](const float* dg, const float* w_t, const float* w, int ldw) -> GemmSeg {
@@ -638,21 +661,25 @@ int Butd::bptt_loop(BpttCall& c) {
                                feats, R, D, tb.dalpha, live, imgk, cnt);
             AttBwdDdecArgs da = {enc_ctx, tb.dec + slot * A, w_aff, tb.alpha + slot * R, tb.dalpha, tb.dDec + slot * A, tb.dS + slot * R, R, A, dparts, live, imgk, cnt};
             hipLaunchKernelGGL(ad ? att_bwd_ddec_kernel<true> : att_bwd_ddec_kernel<false>, dim3(bt, cdiv(A, 256)), dim3(256), 0, st, da, d_att);
-            // X2 = dDec . w_dec   [bt, H]
-            GemmArgs g = gemm_args({{tb.dDec + slot * A, w_dec, A, H, A}}, bt, H, tb.X[1], H, live);
-            ICZ_TRY(gemm_auto(GEMM_NN, g, tb.X[1], tb.xfloats, &ns2, st));
+            // X2 = dDec . w_dec   [bt, H] (the fused route forms it inside the TD-LSTM launch below: tb.X[1] is not written then, and
+            // nothing else reads it)
+            if (!fdh) {
+                GemmArgs g = gemm_args({{tb.dDec + slot * A, w_dec, A, H, A}}, bt, H, tb.X[1], H, live);
+                ICZ_TRY(gemm_auto(GEMM_NN, g, tb.X[1], tb.xfloats, &ns2, st));
+            }
         }
         {   // TD LSTM backward (pointwise): dh1 = carry + X1[:, D:] + X2
             LstmBwdArgs a = {};
             a.dh_a = bnext ? tb.X[3] : nullptr; a.ns_a = ns4; a.lda_a = H; a.rows_a = bnext;
             a.dh_b = tb.X[0] + D; a.ns_b = ns1; a.lda_b = D + H; a.rows_b = bt;
-            a.dh_c = tb.X[1]; a.ns_c = ns2; a.lda_c = H; a.rows_c = bt;
+            if (!fdh) { a.dh_c = tb.X[1]; a.ns_c = ns2; a.lda_c = H; a.rows_c = bt; }
             a.dc_in = bnext ? tb.dc1[cur] : nullptr; a.dc_in_rows = bnext;
             a.gates = tb.gtd + slot * 4 * H;
             a.c_prev = tb.c1 + slot * H; a.c_cur = tb.c1 + slot * H + sH;
             a.dgates = tb.dGtd + slot * 4 * H; a.dc_prev = tb.dc1[cur ^ 1];
             a.rows = bt; a.H = H; a.live = live; a.carry_live = carry_live;
-            hipLaunchKernelGGL(lstm_bwd_point_kernel, dim3(cdiv(H, 256), bt), dim3(256), 0, st, a, d_off);
+            if (fdh) ICZ_TRY(launch_dh1_fused(a, tb.dDec + slot * A, w_dec, A, st));
+            else hipLaunchKernelGGL(lstm_bwd_point_kernel, dim3(cdiv(H, 256), bt), dim3(256), 0, st, a, d_off);
         }
         if (t > 0) {
             // X3 = dG_lm . W_hh_lm + dG_td . W_ih_td[:, :H]   -> d h2_{t-1};   X4 = dG_td . W_hh_td   -> d h1_{t-1}
@@ -1023,6 +1050,44 @@ int icz_test_rowgroup_sum(const float* X, int32_t n_img, int32_t G, int64_t N, f
                 "icz_test_rowgroup_sum: n_img=%d, G=%d, N=%lld (whole groups of 4 floats)", n_img, G, (long long)N);
     ICZ_REQUIRE(al16(X) && al16(out), "icz_test_rowgroup_sum: X and out must be 16-byte aligned");
     hipLaunchKernelGGL(rowgroup_sum_kernel, dim3(cdiv((int)((size_t)n_img * N / 4), 256)), dim3(256), 0, (hipStream_t)stream, X, n_img, G, (size_t)N, out);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+// One "X2 = d dec . w_dec, then the TD-LSTM backward" step of Butd::bptt_loop on given buffers (include/icz.h)
+int icz_test_bptt_dh1_step(int32_t route, int32_t rows, int32_t H, int32_t A, const float* ddec, const float* w_dec, const float* carry,
+                           int32_t ns_carry, int32_t rows_carry, const float* x1, int32_t ns_x1, int32_t ld_x1, const float* dc_in,
+                           const float* gates, const float* c_prev, const float* c_cur, float* dgates, float* dc_prev, const int32_t* live,
+                           const int32_t* carry_live, float* x2_slabs, size_t x2_floats, int32_t* nsplit_out, int32_t* route_out, void* stream) {
+    const char* who = "icz_test_bptt_dh1_step";
+    ICZ_REQUIRE(route >= -1 && route <= 1, "%s: route=%d (-1: as the loop picks, 0: two launches, 1: fused)", who, route);
+    ICZ_REQUIRE(rows >= 1 && rows <= 64 && H >= 4 && H % 4 == 0 && A >= 4 && A % 4 == 0, "%s: rows=%d (1..64), H=%d, A=%d (H and A in whole groups of 4)", who, rows, H, A);
+    ICZ_REQUIRE(ddec && w_dec && x1 && gates && c_cur && dgates && dc_prev, "%s: null argument", who);
+    ICZ_REQUIRE(al16(ddec) && al16(w_dec), "%s: ddec and w_dec must be 16-byte aligned", who);
+    ICZ_REQUIRE(ns_x1 >= 1 && ld_x1 >= H, "%s: ns_x1=%d, ld_x1=%d (at least H)", who, ns_x1, ld_x1);
+    ICZ_REQUIRE(!carry || (ns_carry >= 1 && rows_carry >= 1), "%s: ns_carry=%d, rows_carry=%d", who, ns_carry, rows_carry);
+    ICZ_REQUIRE(!dc_in || rows_carry >= 1, "%s: dc_in with rows_carry=%d", who, rows_carry);
+    const bool takes = lstm_bwd_dh1_fused_takes(rows, H, A);
+    ICZ_REQUIRE(route != 1 || takes, "%s: the fused kernel does not take rows=%d, H=%d, A=%d", who, rows, H, A);
+    const bool fdh = route == 1 || (route == -1 && takes);
+    const int ns = dh1_split(rows, H, A);
+    if (nsplit_out) *nsplit_out = ns;
+    if (route_out) *route_out = fdh ? 1 : 0;
+    hipStream_t const st = (hipStream_t)stream;
+    LstmBwdArgs a = {};
+    a.dh_a = carry; a.ns_a = ns_carry; a.lda_a = H; a.rows_a = rows_carry;
+    a.dh_b = x1; a.ns_b = ns_x1; a.lda_b = ld_x1; a.rows_b = rows;
+    a.dc_in = dc_in; a.dc_in_rows = rows_carry;
+    a.gates = gates; a.c_prev = c_prev; a.c_cur = c_cur; a.dgates = dgates; a.dc_prev = dc_prev;
+    a.rows = rows; a.H = H; a.live = live; a.carry_live = carry_live;
+    if (fdh) return launch_dh1_fused(a, ddec, w_dec, A, st);
+    ICZ_REQUIRE(x2_slabs && al16(x2_slabs) && gemm_slab_floats(rows, H, ns) <= x2_floats, "%s: the two-launch route needs %d slabs of rows x H floats (16-byte aligned)", who, ns);
+    GemmArgs g = gemm_args({{ddec, w_dec, A, H, A}}, rows, H, x2_slabs, H, live);
+    int ns2 = 1;
+    ICZ_TRY(gemm_slabs(GEMM_NN, g, split_backward(Butd::STEP_WGS), x2_slabs, x2_floats, &ns2, st, who));
+    a.dh_c = x2_slabs; a.ns_c = ns2; a.lda_c = H; a.rows_c = rows;
+    const DropCfg d_off = {0, nullptr, nullptr, 0, 0};
+    hipLaunchKernelGGL(lstm_bwd_point_kernel, dim3(cdiv(H, 256), rows), dim3(256), 0, st, a, d_off);
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
