@@ -948,6 +948,69 @@ int icz_test_beam_finalize(int32_t form, int32_t n_img, int32_t k, int32_t L, in
                            int32_t groups, const int32_t* n_act, const float* run, const int32_t* seqs, const int32_t* has_complete,
                            const float* best_score, const int32_t* best_len, const int32_t* best_seq, const int32_t* hyp_cnt, const float* hyp_score,
                            const int32_t* hyp_len, const int32_t* hyp_seq, float* out, int32_t* lens, float* scores, void* stream);
+/* Test entries for the kernels that turn a row of logits into a token, a log-probability or a gradient, each on given logits
+ * (tests/test_gpu_token_choice.py): the library's kernels through the launch helpers of the decoders, arguments filled as the decoders
+ * fill them.  All data pointers are DEVICE pointers (rows_t of icz_test_xe_loss is a HOST array).  Every entry checks its arguments on
+ * the host and returns ICZ_ERR_INVALID without launching on: V < 1 or ldl < V (V < 2 for the XE loss), rows < 1, ns outside 1..16 or
+ * slabs that overlap, E < 4 or E % 4, a table / emb that is not 16-byte aligned, t outside 0..T-1, T above 128 for the XE loss, a row that
+ * does not fit in LDS (icz_sample_select_max_vocab), null pointers.
+ *
+ * The logits: ns == 1 finished rows [rows, ldl]; ns > 1 the ns split-K slabs of the vocabulary projection, slab z at logits + z *
+ * slab_stride, and the finished logit is slab0 + slab1 + ... + bias[v] in fp32, in that order.  Any ldl >= V, slab_stride and alignment
+ * of logits / bias / logits_store is taken: 16-byte loads need ldl % 4 == 0, slab_stride % 4 == 0 and 16-byte aligned bases, every other
+ * layout goes through the scalar loads and gives the same bits.
+ *
+ * Greedy choice: ids = argmax_v, the lowest index among equal maxima, 0 for a row without any logit above -inf (NaN rows too);
+ * it_next[row] = id, ids_out[row, t] = id (optional, [rows, T]), emb[row, :] = relu ? max(table[id, :], 0) : table[id, :].
+ * route 1 = argmax_part_kernel + embed_argmax_kernel (ns == 1, bias == NULL, no counters; part_val / part_idx [rows, 8] scratch),
+ * route 2 = greedy_select_kernel (any ns, bias optional; unfinished [rows] / n_unfinished [T] optional, both or none: the SCST baseline's
+ * <end> bookkeeping -- token 2 clears unfinished[row], n_unfinished[t] counts the rows still unfinished, and at t > 0 with
+ * n_unfinished[t - 1] == 0 the kernel writes ids_out[row, t] = 0 and nothing else), route 0 = what the decoders' launch_greedy_select
+ * takes: route 2 for ns > 1, else route 1. */
+int icz_test_greedy_select(int32_t route, const float* logits, int32_t rows, int32_t V, int32_t ldl, int32_t ns, int64_t slab_stride,
+                           const float* bias, const float* table, int32_t E, int32_t relu, int32_t t, int32_t T, int64_t* ids_out,
+                           int64_t* it_next, float* emb, uint8_t* unfinished, int32_t* n_unfinished, float* part_val, int32_t* part_idx,
+                           void* stream);
+/* The longest row sample_select_kernel and ss_select_kernel take: the row lies in dynamic LDS, whose limit both launch helpers raise once;
+ * a longer row is refused on the host by the rollouts of all three decoders, by scheduled sampling and by the two entries below (host
+ * logic only, no GPU needed). */
+int icz_sample_select_max_vocab(void);
+/* The fields of the multinomial step (sample_select_kernel) that a caller owns.  Per sampled row r (rows - row0 of them): uniforms [.] or
+ * NULL (Philox: seed, a device uint64, stream RNG_UNIFORM, step t), unfinished [.] in/out, seq_out / logp_out [., T], n_unfinished [T].
+ * Per launched row: it_next, draw_out, lse_out [rows], emb_next [rows, E] (optional: emb_table [V, E]; emb_mode 0 no dropout, 1 emb_mask
+ * = keep flags [rows - row0, E] of step t + 1, 2 Philox RNG_EMB at step t + 1; kept elements are doubled), logits_store [rows, ldl]
+ * (ns > 1).  live_rows: optional int32, receives (t + 1) * rows.  row0 > 0: the merged kernel, rows [0, row0) are greedy rows (ids_out
+ * [row0, T], g_unfinished [row0], n_any [T]). */
+typedef struct {
+    const float* logits; int32_t V, ldl, ns; int64_t slab_stride; const float* bias; float* logits_store;
+    const float* uniforms; const uint64_t* seed; int32_t t, T;
+    uint8_t* unfinished; int32_t* n_unfinished; int64_t* seq_out; float* logp_out; int64_t* it_next; int32_t* draw_out; float* lse_out;
+    const float* emb_table; float* emb_next; int32_t E, emb_mode; const uint8_t* emb_mask;
+    int32_t* live_rows;
+    int32_t row0; int64_t* ids_out; uint8_t* g_unfinished; int32_t* n_any;
+} icz_sample_select_args;
+/* One multinomial step: logp = log_softmax(logits), draw = the smallest v with cumsum(exp(logp))[v] > u * sum (float64 sums, clamped to
+ * V - 1), logp_out = logp[draw], lse_out = log-sum-exp, unfinished &= (draw != 2), seq_out = it_next = draw * unfinished; at t > 0 with
+ * the gate counter of step t - 1 at zero the zeros of a finished rollout are written instead. */
+int icz_test_sample_select(const icz_sample_select_args* a, int32_t rows, void* stream);
+/* Scheduled sampling (ss_select_kernel): for the `rows` active rows of XE step t, tok[row] = a draw from softmax(logits_prev[row, :V]) where
+ * gate[t * B + row] < ss_prob, else left as it is.  gate / draw: explicit [T, B] arrays (row t is read), or NULL: Philox streams RNG_SS_GATE /
+ * RNG_SS_DRAW of *seed at step t. */
+int icz_test_ss_select(const float* logits_prev, int32_t rows, int32_t B, int32_t V, int32_t ldl, int32_t t, float ss_prob, const float* gate,
+                       const float* draw, const uint64_t* seed, int64_t* tok, void* stream);
+/* LabelSmoothingLoss and its gradient over all steps (xe_loss_dlogits_kernel + sum_scale_kernel): logits [T B, ldl] in (row t * B + b), the
+ * gradient (softmax - true) / N out, in place; rows b >= rows_t[t] and the pad columns [V, ldl) become zero.  captions [B, L], target =
+ * captions[b, t + 1]; N = *n_dev if n_dev is given and positive, else n_tokens.  loss_rows [T B] per-row losses (zeroed first),
+ * loss_out (optional) = their sum / N. */
+int icz_test_xe_loss(float* logits, int32_t V, int32_t ldl, const int64_t* captions, int32_t L, int32_t B, int32_t T, const int32_t* rows_t,
+                     float smoothing, float n_tokens, const float* n_dev, float* loss_rows, float* loss_out, void* stream);
+/* RewardCriterion and its gradient (reinforce_loss_kernel + reinforce_dlogits_kernel): logp, seq, reward, coef [B, T]; mask[b, 0] = 1,
+ * mask[b, t] = seq[b, t - 1] > 0; denominator = *mask_sum_global if given and positive, else sum(mask); loss_out / mask_sum_out optional.
+ * logits [T Bs', ldl] (Bs' = Bs or B), draw / lse [T Bs']: dlogits[row, v] = coef[b, t] (1[v == draw] - exp(logits - lse)) in place, zero
+ * where draw < 0 or coef == 0 and in the pad columns.  Bs > 0: Bs rows per step of which [row0, row0 + B) are the rollout's. */
+int icz_test_reinforce(const float* logp, const int64_t* seq, const float* reward, int32_t B, int32_t T, const float* mask_sum_global, float* coef,
+                       float* loss_out, float* mask_sum_out, float* logits, int32_t V, int32_t ldl, const int32_t* draw, const float* lse, int32_t Bs,
+                       int32_t row0, void* stream);
 /* Live timing of the dominant kernel (the forward GEMMs of a decoder step at 33..64 rows: gemm_resident_x3_kernel, or
  * gemm_nt_kernel<4, ...> with ICZ_GEMM_RESIDENT_X3=0; see icz_prof_select) with HIP events on its launch stream, for bench.py's
  * roofline line.  Between begin and end every launch is bracketed by an event

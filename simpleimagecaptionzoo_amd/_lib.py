@@ -111,6 +111,15 @@ class BeamStepState(C.Structure):  # icz_beam_step_state
     _fields_ = [(n, C.c_void_p) for n in BEAM_STEP_FIELDS]
 
 
+class SampleSelectArgs(C.Structure):   # icz_sample_select_args
+    _fields_ = [("logits", C.c_void_p), ("V", C.c_int32), ("ldl", C.c_int32), ("ns", C.c_int32), ("slab_stride", C.c_int64),
+                ("bias", C.c_void_p), ("logits_store", C.c_void_p), ("uniforms", C.c_void_p), ("seed", C.c_void_p), ("t", C.c_int32),
+                ("T", C.c_int32), ("unfinished", C.c_void_p), ("n_unfinished", C.c_void_p), ("seq_out", C.c_void_p), ("logp_out", C.c_void_p),
+                ("it_next", C.c_void_p), ("draw_out", C.c_void_p), ("lse_out", C.c_void_p), ("emb_table", C.c_void_p), ("emb_next", C.c_void_p),
+                ("E", C.c_int32), ("emb_mode", C.c_int32), ("emb_mask", C.c_void_p), ("live_rows", C.c_void_p), ("row0", C.c_int32),
+                ("ids_out", C.c_void_p), ("g_unfinished", C.c_void_p), ("n_any", C.c_void_p)]
+
+
 class SampleOpts(C.Structure):     # icz_sample_opts
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
 
@@ -284,6 +293,12 @@ def lib():
         "icz_test_beam_rowtopk": (C.c_int, [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
         "icz_test_beam_step": (C.c_int, [i32, C.POINTER(BeamStepState), i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
         "icz_test_beam_finalize": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, f32, i32] + [vp] * 15),
+        "icz_test_greedy_select": (C.c_int, [i32, vp, i32, i32, i32, i32, i64, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "icz_sample_select_max_vocab": (C.c_int, []),
+        "icz_test_sample_select": (C.c_int, [C.POINTER(SampleSelectArgs), i32, vp]),
+        "icz_test_ss_select": (C.c_int, [vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+        "icz_test_xe_loss": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, C.POINTER(i32), f32, f32, vp, vp, vp, vp]),
+        "icz_test_reinforce": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         try:

@@ -380,7 +380,7 @@ int Aoa::sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* 
             a.emb_table = P.embed_weight; a.emb_next = temb + (slot + B) * dims.E; a.E = dims.E;
             a.emb_drop = dropbits(true, rng.emb_mask, (slot + B) * dims.E, RNG_EMB, t + 1);
         }
-        launch_sample_select(st, B, a);
+        ICZ_TRY(launch_sample_select(st, B, a));
     }
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;

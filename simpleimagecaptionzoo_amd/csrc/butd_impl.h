@@ -27,7 +27,7 @@ struct StepIO {
     float* h2drop_out;               // [rows,H]
     float* logits_out;               // [rows,V]
     int logits_ld;                   // row stride of logits_out (0 = V)
-    int* pred_nsplit;                // non-null: the caller's consumer of the logits can sum split-K slabs (argmax_part_kernel,
+    int* pred_nsplit;                // non-null: the caller's consumer of the logits can sum split-K slabs (greedy_select_kernel,
                                      // sample_select_kernel): step() may leave the predict GEMM's slabs [ns][rows][Vp] in the
                                      // chain's workspace instead of finished logits and reports ns here (1 = logits_out is final)
     float* ws_alt;                   // split-K slab workspace / attention scores of this chain (null = the handle's):

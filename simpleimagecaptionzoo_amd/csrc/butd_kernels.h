@@ -739,11 +739,9 @@ __device__ __forceinline__ f32x4 sum_slabs4(const float* p, int ns, size_t slab_
 __device__ __forceinline__ void argmax_combine(float& best, int& bi, float ob, int oi) {
     if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
 }
-// ns > 1: `logits` holds the ns split-K slabs of the predict GEMM (slab z at + z * slab_stride, no bias yet): the logit is their
-// sum in slab order + bias[v] (the resident-activation GEMM of gemm_resident_x3.hip leaves four slabs at 33 - 64 rows).
+// (finished rows only: a step whose predict GEMM left split-K slabs goes to greedy_select_kernel, launch_greedy_select)
 __global__ __launch_bounds__(256) void argmax_part_kernel(const float* __restrict__ logits, int V, int ldl, int P,
-                                                          float* __restrict__ part_val, int* __restrict__ part_idx,
-                                                          int ns = 1, size_t slab_stride = 0, const float* __restrict__ bias = nullptr) {
+                                                          float* __restrict__ part_val, int* __restrict__ part_idx) {
     __shared__ float sv[4];
     __shared__ int si[4];
     const int row = blockIdx.x, p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -752,29 +750,9 @@ __global__ __launch_bounds__(256) void argmax_part_kernel(const float* __restric
     const float* l = logits + (size_t)row * ldl;
     float best = -INFINITY;
     int bi = 0x7fffffff;
-    if (ns > 1) {
-        // 16-byte loads where the row, the slab stride and the slice start allow it (v0 is a multiple of 4 by construction)
-        const bool vec = ((ldl | (int)(slab_stride & 3)) & 3) == 0 && (((uintptr_t)logits | (uintptr_t)bias) & 15) == 0;
-        const int v1v = vec ? v0 + ((v1 - v0) & ~3) : v0;
-        for (int v = v0 + tid * 4; v < v1v; v += 1024) {
-            f32x4 x = *reinterpret_cast<const f32x4*>(l + v);
-            for (int z = 1; z < ns; ++z) x += *reinterpret_cast<const f32x4*>(l + (size_t)z * slab_stride + v);
-            x += *reinterpret_cast<const f32x4*>(bias + v);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (x[j] > best) { best = x[j]; bi = v + j; }
-        }
-        for (int v = v1v + tid; v < v1; v += 256) {
-            float x = l[v];
-            for (int z = 1; z < ns; ++z) x += l[(size_t)z * slab_stride + v];
-            x += bias[v];
-            if (x > best || (x == best && v < bi)) { best = x; bi = v; }
-        }
-    } else {
-        for (int v = v0 + tid; v < v1; v += 256) {
-            const float x = l[v];
-            if (x > best) { best = x; bi = v; }
-        }
+    for (int v = v0 + tid; v < v1; v += 256) {
+        const float x = l[v];
+        if (x > best) { best = x; bi = v; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) argmax_combine(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
@@ -844,7 +822,10 @@ __global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __rest
         float x = l[v];
         for (int z = 1; z < ns; ++z) x += l[(size_t)z * slab_stride + v];
         if (bias) x += bias[v];
-        if (x > best || (x == best && v < bi)) { best = x; bi = v; }
+        // strictly greater, as in the body: a thread meets its elements in ascending order, so an equal value is never at a lower index
+        // -- an "equal and lower" clause here only ever fired for -inf against the start value, and sent a row of -inf logits to
+        // token V & ~3 instead of <pad> whenever V % 4 != 0 on the 16-byte path
+        if (x > best) { best = x; bi = v; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) argmax_combine(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
@@ -1019,6 +1000,10 @@ struct SampleSelArgs {
     int row0; int64_t* ids_out; uint8_t* g_unfinished; int* n_any;
 };
 constexpr int SEL_THREADS = 1024;       // 16 waves per row: the row (40 KB) sits in LDS
+// the largest row of the select kernels (sample_select_kernel, ss_select_kernel): dynamic LDS beside their static arrays in the 160 KB
+// of a workgroup; both launch helpers raise the kernels' dynamic-LDS limit to it once and refuse a longer row on the host
+constexpr size_t SEL_LDS_MAX = 159 * 1024;
+inline bool sel_row_fits_lds(int V) { return V >= 1 && sizeof(float) * (size_t)V <= SEL_LDS_MAX; }
 __device__ __forceinline__ float block_max_n(float v, float* sm, int nw) {
     v = wave_max(v);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
@@ -1124,10 +1109,10 @@ inline int ss_select_launch(hipStream_t st, int rows, const float* logits_prev, 
                             const float* gate, const float* draw, const uint64_t* seed_p, int64_t* tok_t) {
     static bool lds_set = false;
     if (!lds_set) {
-        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ss_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
+        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ss_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEL_LDS_MAX));
         lds_set = true;
     }
-    ICZ_REQUIRE(sizeof(float) * (size_t)V <= 159 * 1024, "scheduled sampling: a row of %d logits does not fit in LDS", V);
+    ICZ_REQUIRE(sel_row_fits_lds(V), "scheduled sampling: a row of %d logits does not fit in LDS (at most %d)", V, (int)(SEL_LDS_MAX / sizeof(float)));
     SsSelArgs sa = {};
     sa.logits_prev = logits_prev; sa.ldl = ldl; sa.V = V; sa.t = t; sa.ss_prob = ss_prob;
     sa.gate = gate ? gate + (size_t)t * B : nullptr;
@@ -1320,9 +1305,23 @@ __global__ __launch_bounds__(SEL_THREADS) void sample_select_kernel(SampleSelArg
             *reinterpret_cast<f32x4*>(a.emb_next + (size_t)row * a.E + e) = x;
         }
 }
-inline void launch_sample_select(hipStream_t st, int rows, const SampleSelArgs& a) {
+// One rule for every caller (the rollouts of the three decoders and icz_test_sample_select): the row sits in dynamic LDS beside the
+// kernel's 256 bytes of static arrays, the dynamic limit is raised once to SEL_LDS_MAX (as ss_select_launch does), and a row above it is
+// refused on the host -- without the raised limit a vocabulary above 16384 (64 KB) could not launch, and nothing said so.
+// (`lds_set` is the project's pattern for such attributes, ss_select_launch and the GEMMs included: once per translation unit and
+// process, for the device current at the first call, unsynchronised -- one GPU and one launching thread per process, as every
+// caller here is; a process that drove a second device would have to raise the limit there itself.)
+inline int launch_sample_select(hipStream_t st, int rows, const SampleSelArgs& a) {
+    static bool lds_set = false;
+    ICZ_REQUIRE(sel_row_fits_lds(a.V), "sample select: a row of %d logits does not fit in LDS (at most %d)", a.V, (int)(SEL_LDS_MAX / sizeof(float)));
+    if (!lds_set) {
+        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sample_select_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEL_LDS_MAX));
+        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sample_select_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SEL_LDS_MAX));
+        lds_set = true;
+    }
     if (a.row0 > 0) hipLaunchKernelGGL(sample_select_kernel<true>, dim3(rows), dim3(SEL_THREADS), sizeof(float) * a.V, st, a);
     else hipLaunchKernelGGL(sample_select_kernel<false>, dim3(rows), dim3(SEL_THREADS), sizeof(float) * a.V, st, a);
+    return ICZ_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------

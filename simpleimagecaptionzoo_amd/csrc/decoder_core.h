@@ -238,8 +238,16 @@ struct CaptionHead {
     int upload_pack_index(hipStream_t st);
 };
 
+// The launch sites of the two loss heads, shared by CaptionHead::xe_loss / reinforce and the test entries icz_test_xe_loss /
+// icz_test_reinforce (include/icz.h).  xe: rows_t[T] active rows per step, 1 / n the host normaliser, n_dev the optional device one;
+// loss_rows [T B] is zeroed first.  reinforce: rows / row0 as CaptionHead::reinforce.
+int launch_xe_loss(float* logits, int V, int ldl, const int64_t* captions, int L, int B, int T, const int* rows_t, float smoothing, float n,
+                   const float* n_dev, float* loss_rows, float* loss_out, hipStream_t st);
+int launch_reinforce(const float* logp, const int64_t* seq, const float* reward, int B, int T, const float* msum_dev, float* coef, float* loss_out,
+                     float* msum_out, float* logits, int V, int ldl, const int32_t* draw, const float* lse, int rows, int row0, hipStream_t st);
+
 // Where one decoder step left its logits: ns == 1 finished rows [rows][ld]; ns > 1 the predict GEMM's split-K slabs [ns][rows][ld]
-// (slab z at p + z * slab_stride, no bias yet) + bias[v], summed in slab order as argmax_part_kernel / greedy_select_kernel do.
+// (slab z at p + z * slab_stride, no bias yet) + bias[v], summed in slab order as greedy_select_kernel / sample_select_kernel do.
 struct LogitsView { const float* p; const float* bias; size_t slab_stride; int ld; int ns; };
 // the view of a step whose predict GEMM (gemm_predict) reported `pns` slabs in `ws`, or finished rows in `logits`
 inline LogitsView logits_view(const float* ws, const float* bias, const float* logits, int rows, int Vp, int pns) {
@@ -337,7 +345,7 @@ int beam_search(const char* who, DecodeMember* const* m, int M, const BeamCombin
 // two-kernel argmax over ARGMAX_PARTS slices of the vocabulary (amax_val / amax_idx [rows, ARGMAX_PARTS]), which does not.
 constexpr int ARGMAX_PARTS = 8;
 void launch_greedy_select(const LogitsView& lv, const DecodeMember::EmbSlot& e, int rows, int V, float* amax_val, int* amax_idx, int64_t* it,
-                          int64_t* ids_out, int T, int t, uint8_t* gunf, int* gn, hipStream_t st);
+                          int64_t* ids_out, int T, int t, uint8_t* gunf, int* gn, hipStream_t st, int route = 0);
 // The sampling decode on a member: prologue once per image, the rows expanded through img_of_row, then max_len steps of the
 // member's step + sample_decode_kernel (include/icz.h: icz_*_sample_decode; `who` names the entry in its errors).
 int sample_decode(DecodeMember* m, const char* who, const float* feats, int n_img, int n, int max_len, const icz_sample_opts* opts,

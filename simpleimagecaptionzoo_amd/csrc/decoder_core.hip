@@ -130,18 +130,23 @@ int CaptionHead::scatter_packed(const float* dpacked, int V, int ldl, float* log
     return ICZ_OK;
 }
 
-int CaptionHead::xe_loss(float smoothing, float n_tokens_global, float* logits, int V, int ldl, float* loss_out, hipStream_t st) {
-    const int B = cur_B, T = cur_T;
-    const float n = n_tokens_global > 0.f ? n_tokens_global : (float)n_tokens;
-    const float* n_dev = n_tokens_global < 0.f ? d_msum : nullptr;      // < 0: the device scalar handed over by *_set_*_global
+int launch_xe_loss(float* logits, int V, int ldl, const int64_t* captions, int L, int B, int T, const int* rows_t, float smoothing, float n,
+                   const float* n_dev, float* loss_rows, float* loss_out, hipStream_t st) {
     ICZ_CHECK_HIP(hipMemsetAsync(loss_rows, 0, sizeof(float) * T * B, st));
     ICZ_REQUIRE(T <= XE_MAX_T, "xe_backward: %d steps exceed %d", T, XE_MAX_T);
     XeRows xr = {};
     for (int t = 0; t < T; ++t) xr.n[t] = rows_t[t];
-    hipLaunchKernelGGL(xe_loss_dlogits_kernel, dim3(B, T), dim3(256), 0, st, logits, V, ldl, cur_captions, cur_L, B, xr, smoothing, 1.0f / n, n_dev,
+    hipLaunchKernelGGL(xe_loss_dlogits_kernel, dim3(B, T), dim3(256), 0, st, logits, V, ldl, captions, L, B, xr, smoothing, 1.0f / n, n_dev,
                        loss_rows);
     if (loss_out) hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, st, loss_rows, T * B, 1.0f / n, n_dev, loss_out);
     ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int CaptionHead::xe_loss(float smoothing, float n_tokens_global, float* logits, int V, int ldl, float* loss_out, hipStream_t st) {
+    const float n = n_tokens_global > 0.f ? n_tokens_global : (float)n_tokens;
+    const float* n_dev = n_tokens_global < 0.f ? d_msum : nullptr;      // < 0: the device scalar handed over by *_set_*_global
+    ICZ_TRY(launch_xe_loss(logits, V, ldl, cur_captions, cur_L, cur_B, cur_T, rows_t.data(), smoothing, n, n_dev, loss_rows, loss_out, st));
     mode = 0;
     return ICZ_OK;
 }
@@ -151,19 +156,25 @@ void CaptionHead::set_msum_global(float msum_global, hipStream_t st) const {
         hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, (uint64_t*)nullptr, (uint64_t)0, d_msum, msum_global);
 }
 
-int CaptionHead::reinforce(const float* reward, float* logits, int V, int ldl, float* loss_out, float* msum_out, hipStream_t st, int rows, int row0) {
-    const int B = cur_B, T = cur_T;
-    hipLaunchKernelGGL(reinforce_loss_kernel, dim3(1), dim3(256), 0, st, cur_logp, cur_seq, reward, B, T, (const float*)d_msum, coef, loss_out, msum_out);
-    hipLaunchKernelGGL(reinforce_dlogits_kernel, dim3(cdiv(ldl, 256), T * (rows ? rows : B)), dim3(256), 0, st, logits, V, ldl, draw, lse, coef, B, T,
-                       rows, row0);
+int launch_reinforce(const float* logp, const int64_t* seq, const float* reward, int B, int T, const float* msum_dev, float* coef, float* loss_out,
+                     float* msum_out, float* logits, int V, int ldl, const int32_t* draw, const float* lse, int rows, int row0, hipStream_t st) {
+    hipLaunchKernelGGL(reinforce_loss_kernel, dim3(1), dim3(256), 0, st, logp, seq, reward, B, T, msum_dev, coef, loss_out, msum_out);
+    hipLaunchKernelGGL(reinforce_dlogits_kernel, dim3(cdiv(ldl, 256), T * (rows ? rows : B)), dim3(256), 0, st, logits, V, ldl, draw, lse,
+                       (const float*)coef, B, T, rows, row0);
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
 
+int CaptionHead::reinforce(const float* reward, float* logits, int V, int ldl, float* loss_out, float* msum_out, hipStream_t st, int rows, int row0) {
+    return launch_reinforce(cur_logp, cur_seq, reward, cur_B, cur_T, d_msum, coef, loss_out, msum_out, logits, V, ldl, draw, lse, rows, row0, st);
+}
+
 // ------------------------------------------------------------------------------------------------
+// route: 0 = by the view (every decoder), 1 = the two-kernel form, 2 = greedy_select_kernel (icz_test_greedy_select, which checks that
+// the form can take the view: the two-kernel form reads finished rows only and keeps no <end> counters)
 void launch_greedy_select(const LogitsView& lv, const DecodeMember::EmbSlot& e, int rows, int V, float* amax_val, int* amax_idx, int64_t* it,
-                          int64_t* ids_out, int T, int t, uint8_t* gunf, int* gn, hipStream_t st) {
-    if (lv.ns > 1)         // 33 - 64 rows: the slabs of the vocabulary projection -> token + next embedding in one launch
+                          int64_t* ids_out, int T, int t, uint8_t* gunf, int* gn, hipStream_t st, int route) {
+    if (route == 2 || (route == 0 && lv.ns > 1))         // 33 - 64 rows: the slabs of the vocabulary projection -> token + next embedding in one launch
         hipLaunchKernelGGL(greedy_select_kernel, dim3(rows), dim3(1024), 0, st, lv.p, V, lv.ld, lv.ns, lv.slab_stride, lv.bias, e.table, e.E, e.emb,
                            it, ids_out, T, t, e.relu, gunf, gn);
     else {
@@ -224,6 +235,125 @@ int icz_test_side_branch(int32_t fail_at, int32_t inline_branch, float* out2, vo
         ICZ_TRY(behind());
         return b.join();
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Test entries of the token-choice and loss kernels (include/icz.h): the arguments are checked on the host, then the kernels go through
+// the launch helpers the decoders use (launch_greedy_select, launch_sample_select, ss_select_launch, launch_xe_loss, launch_reinforce).
+static inline bool tc_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static int tc_embed_shape(const char* who, const float* table, const float* emb, int E) {
+    ICZ_REQUIRE(table && emb, "%s: null embedding table or output", who);
+    ICZ_REQUIRE(E >= 4 && E % 4 == 0, "%s: E=%d is not a positive multiple of 4", who, E);
+    ICZ_REQUIRE(tc_al16(table) && tc_al16(emb), "%s: table and emb must be 16-byte aligned", who);
+    return ICZ_OK;
+}
+static int tc_logits_shape(const char* who, const float* logits, int rows, int V, int ldl, int ns, int64_t slab_stride) {
+    ICZ_REQUIRE(logits, "%s: null logits", who);
+    ICZ_REQUIRE(rows >= 1 && rows <= (1 << 20), "%s: rows=%d", who, rows);
+    ICZ_REQUIRE(V >= 1 && ldl >= V, "%s: V=%d, ldl=%d", who, V, ldl);
+    ICZ_REQUIRE(ns >= 1 && ns <= 16, "%s: ns=%d outside 1..16", who, ns);
+    ICZ_REQUIRE(ns == 1 || slab_stride >= (int64_t)(rows - 1) * ldl + V, "%s: slab_stride=%lld overlaps the rows of a slab", who, (long long)slab_stride);
+    return ICZ_OK;
+}
+
+int icz_test_greedy_select(int32_t route, const float* logits, int32_t rows, int32_t V, int32_t ldl, int32_t ns, int64_t slab_stride,
+                           const float* bias, const float* table, int32_t E, int32_t relu, int32_t t, int32_t T, int64_t* ids_out,
+                           int64_t* it_next, float* emb, uint8_t* unfinished, int32_t* n_unfinished, float* part_val, int32_t* part_idx,
+                           void* stream) {
+    using namespace icz;
+    const char* who = "icz_test_greedy_select";
+    ICZ_REQUIRE(route >= 0 && route <= 2, "%s: route=%d (0 as the decoders, 1 two kernels, 2 one kernel)", who, route);
+    ICZ_TRY(tc_logits_shape(who, logits, rows, V, ldl, ns, slab_stride));
+    ICZ_TRY(tc_embed_shape(who, table, emb, E));
+    ICZ_REQUIRE(it_next, "%s: null it_next", who);
+    ICZ_REQUIRE(T >= 1 && t >= 0 && t < T, "%s: t=%d outside 0..T-1 (T=%d)", who, t, T);
+    ICZ_REQUIRE((unfinished == nullptr) == (n_unfinished == nullptr), "%s: unfinished and n_unfinished go together", who);
+    const bool one_kernel = route == 2 || (route == 0 && ns > 1);
+    if (!one_kernel) {
+        ICZ_REQUIRE(ns == 1 && !bias && !unfinished, "%s: the two-kernel form reads finished rows (ns = 1, no bias) and keeps no <end> counters", who);
+        ICZ_REQUIRE(part_val && part_idx, "%s: the two-kernel form needs part_val / part_idx [rows, %d]", who, ARGMAX_PARTS);
+    }
+    const LogitsView lv = {logits, bias, (size_t)slab_stride, ldl, ns};
+    const DecodeMember::EmbSlot e = {table, emb, E, relu != 0};
+    launch_greedy_select(lv, e, rows, V, part_val, part_idx, it_next, ids_out, T, t, unfinished, n_unfinished, (hipStream_t)stream, route);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int icz_sample_select_max_vocab(void) { return (int)(icz::SEL_LDS_MAX / sizeof(float)); }
+
+int icz_test_sample_select(const icz_sample_select_args* s, int32_t rows, void* stream) {
+    using namespace icz;
+    const char* who = "icz_test_sample_select";
+    ICZ_REQUIRE(s, "%s: null arguments", who);
+    ICZ_TRY(tc_logits_shape(who, s->logits, rows, s->V, s->ldl, s->ns, s->slab_stride));
+    ICZ_REQUIRE(sel_row_fits_lds(s->V), "%s: a row of %d logits does not fit in LDS (at most %d)", who, s->V, icz_sample_select_max_vocab());
+    ICZ_REQUIRE(s->ns == 1 || (s->bias && s->logits_store), "%s: slabs need bias and logits_store", who);
+    ICZ_REQUIRE(s->T >= 1 && s->t >= 0 && s->t < s->T, "%s: t=%d outside 0..T-1 (T=%d)", who, s->t, s->T);
+    ICZ_REQUIRE(s->unfinished && s->n_unfinished && s->seq_out && s->logp_out && s->it_next && s->draw_out && s->lse_out, "%s: null argument", who);
+    ICZ_REQUIRE(s->uniforms || s->seed, "%s: uniforms or a seed", who);
+    ICZ_REQUIRE(s->row0 >= 0 && s->row0 < rows, "%s: row0=%d outside 0..rows-1 (rows=%d)", who, s->row0, rows);
+    ICZ_REQUIRE(s->row0 == 0 || (s->ids_out && s->g_unfinished && s->n_any), "%s: a merged launch needs ids_out, g_unfinished and n_any", who);
+    ICZ_REQUIRE(s->emb_mode >= 0 && s->emb_mode <= 2, "%s: emb_mode=%d (0 none, 1 mask, 2 Philox)", who, s->emb_mode);
+    SampleSelArgs a = {};
+    a.logits = s->logits; a.V = s->V; a.ldl = s->ldl;
+    if (s->ns > 1) { a.ns = s->ns; a.slab_stride = (size_t)s->slab_stride; a.bias = s->bias; a.logits_store = s->logits_store; }
+    a.uniforms = s->uniforms; a.seed_p = s->seed; a.t = s->t; a.T = s->T;
+    a.unfinished = s->unfinished; a.n_unfinished = s->n_unfinished; a.seq_out = s->seq_out; a.logp_out = s->logp_out;
+    a.it_next = s->it_next; a.draw_out = s->draw_out; a.lse_out = s->lse_out; a.live_rows = s->live_rows;
+    a.row0 = s->row0; a.ids_out = s->ids_out; a.g_unfinished = s->g_unfinished; a.n_any = s->n_any;
+    if (s->emb_next) {
+        ICZ_TRY(tc_embed_shape(who, s->emb_table, s->emb_next, s->E));
+        ICZ_REQUIRE(s->emb_mode != 1 || (s->emb_mask && ((uintptr_t)s->emb_mask & 3) == 0), "%s: emb_mask null or not 4-byte aligned", who);
+        ICZ_REQUIRE(s->emb_mode != 2 || s->seed, "%s: Philox keep bits need a seed", who);
+        a.emb_table = s->emb_table; a.emb_next = s->emb_next; a.E = s->E;
+        a.emb_drop = DropCfg{s->emb_mode, s->emb_mask, s->seed, RNG_EMB, (uint32_t)(s->t + 1), 0};     // step t + 1's embedding dropout
+    }
+    ICZ_TRY(launch_sample_select((hipStream_t)stream, rows, a));
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int icz_test_ss_select(const float* logits_prev, int32_t rows, int32_t B, int32_t V, int32_t ldl, int32_t t, float ss_prob, const float* gate,
+                       const float* draw, const uint64_t* seed, int64_t* tok, void* stream) {
+    using namespace icz;
+    const char* who = "icz_test_ss_select";
+    ICZ_TRY(tc_logits_shape(who, logits_prev, rows, V, ldl, 1, 0));
+    ICZ_REQUIRE(sel_row_fits_lds(V), "%s: a row of %d logits does not fit in LDS (at most %d)", who, V, icz_sample_select_max_vocab());
+    ICZ_REQUIRE(B >= rows && t >= 0 && t <= 65535, "%s: B=%d below rows=%d, or t=%d", who, B, rows, t);
+    ICZ_REQUIRE(ss_prob >= 0.f && ss_prob <= 1.f, "%s: ss_prob %g outside [0, 1]", who, (double)ss_prob);
+    ICZ_REQUIRE(tok && ((gate && draw) || seed), "%s: null argument (tok; gate and draw, or a seed)", who);
+    ICZ_TRY(ss_select_launch((hipStream_t)stream, rows, logits_prev, ldl, V, t, B, ss_prob, gate, draw, seed, tok));
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int icz_test_xe_loss(float* logits, int32_t V, int32_t ldl, const int64_t* captions, int32_t L, int32_t B, int32_t T, const int32_t* rows_t,
+                     float smoothing, float n_tokens, const float* n_dev, float* loss_rows, float* loss_out, void* stream) {
+    using namespace icz;
+    const char* who = "icz_test_xe_loss";
+    ICZ_REQUIRE(logits && captions && rows_t && loss_rows, "%s: null argument", who);
+    ICZ_REQUIRE(V >= 2 && ldl >= V, "%s: V=%d (at least 2: the smoothing mass is spread over V - 1 tokens), ldl=%d", who, V, ldl);
+    ICZ_REQUIRE(T >= 1 && T <= XE_MAX_T && L > T, "%s: T=%d outside 1..%d or not below L=%d", who, T, XE_MAX_T, L);
+    ICZ_REQUIRE(B >= 1 && (long)B * T <= (1 << 20), "%s: B=%d", who, B);
+    for (int t = 0; t < T; ++t) ICZ_REQUIRE(rows_t[t] >= 0 && rows_t[t] <= B, "%s: rows_t[%d]=%d outside 0..B", who, t, rows_t[t]);
+    ICZ_REQUIRE(smoothing >= 0.f && smoothing <= 1.f && n_tokens > 0.f, "%s: smoothing=%g outside [0, 1] or n_tokens=%g not positive", who,
+                (double)smoothing, (double)n_tokens);
+    return launch_xe_loss(logits, V, ldl, captions, L, B, T, rows_t, smoothing, n_tokens, n_dev, loss_rows, loss_out, (hipStream_t)stream);
+}
+
+int icz_test_reinforce(const float* logp, const int64_t* seq, const float* reward, int32_t B, int32_t T, const float* mask_sum_global, float* coef,
+                       float* loss_out, float* mask_sum_out, float* logits, int32_t V, int32_t ldl, const int32_t* draw, const float* lse, int32_t Bs,
+                       int32_t row0, void* stream) {
+    using namespace icz;
+    const char* who = "icz_test_reinforce";
+    ICZ_REQUIRE(logp && seq && reward && coef && logits && draw && lse, "%s: null argument", who);
+    ICZ_REQUIRE(V >= 1 && ldl >= V, "%s: V=%d, ldl=%d", who, V, ldl);
+    ICZ_REQUIRE(B >= 1 && T >= 1 && (long)B * T <= (1 << 20), "%s: B=%d, T=%d", who, B, T);
+    ICZ_REQUIRE((Bs == 0 && row0 == 0) || (row0 >= 0 && Bs == row0 + B), "%s: Bs=%d rows per step are not row0=%d + B=%d", who, Bs, row0, B);
+    ICZ_REQUIRE((long)T * (Bs ? Bs : B) <= 65535, "%s: %ld logits rows exceed the grid", who, (long)T * (Bs ? Bs : B));
+    return launch_reinforce(logp, seq, reward, B, T, mask_sum_global, coef, loss_out, mask_sum_out, logits, V, ldl, draw, lse, Bs, row0,
+                            (hipStream_t)stream);
 }
 const char* icz_last_error(void) { return icz::g_err; }
 const char* icz_version(void) { return "libicz 0.1 (gfx950)"; }

@@ -230,7 +230,7 @@ int Nic::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq
         a.seed_p = d_seed; a.t = t; a.T = T;
         a.unfinished = unf; a.n_unfinished = nunf; a.seq_out = seq_out; a.logp_out = logp_out;
         a.it_next = tok + slot + B; a.draw_out = draw + slot; a.lse_out = lse + slot;
-        launch_sample_select(st, B, a);
+        ICZ_TRY(launch_sample_select(st, B, a));
     }
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;

@@ -4,6 +4,7 @@ rollout / XE pass built from a seed."""
 import numpy as np
 
 RNG_EMB, RNG_ATT, RNG_OUT, RNG_UNIFORM = 1, 2, 3, 4       # csrc/rng.h: RngStream
+RNG_SS_GATE, RNG_SS_DRAW = 5, 6                           # the gate and the draw of scheduled sampling (ss_select_kernel)
 
 
 def _philox4x32_10(c0, c1, c2, c3, k0, k1):
