@@ -1,6 +1,9 @@
 // AoADetection captioner, inference paths: feature projection + AoA refiner, decoder step, greedy and beam decoding
 // (Models/AoA_Model.py:122-162, 319-336, 403-502, 698-753).  Training paths live in aoa_train.hip.
 #include "aoa_impl.h"
+#include "lstm_kernels.h"
+#include "support_kernels.h"
+#include "token_kernels.h"
 
 namespace icz {
 
@@ -80,7 +83,7 @@ __global__ __launch_bounds__(256) void aoa_pack_rec_kernel(const float* __restri
 
 int Aoa::refresh(hipStream_t st) {
     ICZ_REQUIRE(bound, "aoa: parameters not bound");
-    hipLaunchKernelGGL(weight_norm_kernel, dim3(cdiv(dims.V, 4)), dim3(256), 0, st, P.predict_v, P.predict_g, w_pred, n_pred, dims.V, dims.Hd);
+    launch_weight_norm(P.predict_v, P.predict_g, w_pred, n_pred, dims.V, dims.Hd, st);
     const size_t n = (size_t)4 * dims.Hd * 2 * dims.Hd;
     hipLaunchKernelGGL(aoa_pack_rec_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P.lstm_w_ih, P.lstm_w_hh, w_rec, dims.Hd, dims.E);
     QkvPackTable qt = {};

@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "aoa_kernels.h"
-#include "butd_impl.h"
+#include "decoder_core.h"
 
 namespace icz {
 

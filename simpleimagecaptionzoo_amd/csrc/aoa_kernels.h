@@ -1,7 +1,8 @@
 // Kernels specific to the AoA model family (Models/AoA_Model.py): custom LayerNorm, multi-head dot-product attention
 // (R x R self-attention in the refiner, 1 x R in the decoder; R = 36, 49, or up to 128 with per-image counts), GLU gate, general-p dropout.
 #pragma once
-#include "butd_kernels.h"
+#include "icz_common.h"
+#include "rng.h"
 
 namespace icz {
 namespace {
@@ -210,11 +211,9 @@ __global__ __launch_bounds__(256) void mha_self_mfma_kernel(const float* __restr
     // ---- softmax over the valid keys of every query row (one wave per row, one key per lane), dropout, zeros behind the last key
     for (int q = wave; q < RP; q += 4) {
         const float v = lane < len ? sp[q * lp + lane] : -INFINITY;
-        const float mx = wave_max(v);
-        const float e = lane < len ? expf(v - mx) : 0.f;
-        const float sum = wave_sum(e);
+        const float p = wave_softmax(v, lane < len);
         const uint64_t idx = (((uint64_t)img * NH + hd) * R + q) * R;
-        if (lane < RP) sp[q * lp + lane] = (lane < len && q < nrow) ? dp.apply(e / sum, idx + lane) : 0.f;
+        if (lane < RP) sp[q * lp + lane] = (lane < len && q < nrow) ? dp.apply(p, idx + lane) : 0.f;
     }
     __syncthreads();
     // ---- O = P V: tile (qt, dt), dt over the head dimension in blocks of 16
@@ -330,13 +329,11 @@ __global__ __launch_bounds__(256) void mha_self_kernel(const float* __restrict__
             const int r1 = lane + 64;
             const float v0 = lane < len ? sp[q * lp + lane] : -INFINITY;
             const float v1 = r1 < len ? sp[q * lp + r1] : -INFINITY;
-            const float mx = wave_max(fmaxf(v0, v1));
-            const float e0 = lane < len ? expf(v0 - mx) : 0.f;
-            const float e1 = r1 < len ? expf(v1 - mx) : 0.f;
-            const float sum = wave_sum(e0 + e1);
+            float p0, p1;
+            wave_softmax2(v0, lane < len, v1, r1 < len, p0, p1);
             const uint64_t idx = (((uint64_t)img * NH + hd) * R + (q0 + q)) * R;
-            if (lane < len4) sp[q * lp + lane] = lane < len ? dp.apply(e0 / sum, idx + lane) : 0.f;
-            if (r1 < len4) sp[q * lp + r1] = r1 < len ? dp.apply(e1 / sum, idx + r1) : 0.f;
+            if (lane < len4) sp[q * lp + lane] = lane < len ? dp.apply(p0, idx + lane) : 0.f;
+            if (r1 < len4) sp[q * lp + r1] = r1 < len ? dp.apply(p1, idx + r1) : 0.f;
         }
         __syncthreads();
         for (int i = tid; i < nqt * d4; i += 256) {
@@ -734,12 +731,9 @@ __global__ __launch_bounds__(256) void mha_self_bwd_kernel(const float* __restri
         const int k1 = lane + 64;
         const float v0 = lane < n ? p1[q * lp + lane] : -INFINITY;
         const float v1 = k1 < n ? p1[q * lp + k1] : -INFINITY;
-        const float mx = wave_max(fmaxf(v0, v1));
-        const float e0 = lane < n ? expf(v0 - mx) : 0.f;
-        const float e1 = k1 < n ? expf(v1 - mx) : 0.f;
-        const float sum = wave_sum(e0 + e1);
+        float P0, P1;
+        wave_softmax2(v0, lane < n, v1, k1 < n, P0, P1);
         const uint64_t idx = (((uint64_t)img * NH + hd) * R + q) * R;
-        const float P0 = e0 / sum, P1 = e1 / sum;
         // dp.apply(1, i) = the keep factor of draw i: 1 / (1 - p) or 0 (1 without dropout)
         const float f0 = lane < n ? dp.apply(1.f, idx + lane) : 0.f, f1 = k1 < n ? dp.apply(1.f, idx + k1) : 0.f;
         const float dP0 = lane < n ? f0 * p2[q * lp + lane] : 0.f, dP1 = k1 < n ? f1 * p2[q * lp + k1] : 0.f;

@@ -6,7 +6,11 @@
 // one TN GEMM over all (t, b) rows after the loop.  The gradients of the hoisted linear_K / linear_V outputs are
 // accumulated per image over time by the one workgroup that owns the (image, head) slice (no atomics, fixed order).
 #include "aoa_impl.h"
+#include "butd_kernels.h"
 #include "ens_sample.h"
+#include "lstm_kernels.h"
+#include "support_kernels.h"
+#include "token_kernels.h"
 
 namespace icz {
 namespace {
@@ -602,8 +606,7 @@ int Aoa::bptt_predict(BpttCall& c) {
     hipStream_t const ps = c.predict.st();
     ICZ_TRY(gemm_tn(tlogit, Vp, Vp, tcd, Hd, Hd, TB, dWp, Hd, 0, c.rl, ps));
     (void)launch_colsum(tlogit, TB, V, Vp, c.G.predict_b, ps);
-    hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, ps, dWp, Hd, P.predict_v, P.predict_g, n_pred, c.G.predict_v,
-                       c.G.predict_g, V, Hd);
+    launch_weight_norm_bwd(dWp, Hd, P.predict_v, P.predict_g, n_pred, c.G.predict_v, c.G.predict_g, V, Hd, ps);
     return c.predict.finish();
 }
 

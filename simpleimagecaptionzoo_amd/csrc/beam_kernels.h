@@ -1,7 +1,7 @@
 // Per-image beam expand / prune kernels of the shared beam-search driver (beam.hip); the state re-gather and the row expansion the
-// decoders launch from their seams live in butd_kernels.h.
+// decoders launch from their seams live in token_kernels.h.
 #pragma once
-#include "butd_kernels.h"
+#include "icz_common.h"
 
 namespace icz {
 namespace {

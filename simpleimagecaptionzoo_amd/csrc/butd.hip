@@ -2,6 +2,10 @@
 #include <vector>
 
 #include "butd_impl.h"
+#include "butd_kernels.h"
+#include "lstm_kernels.h"
+#include "support_kernels.h"
+#include "token_kernels.h"
 
 namespace icz {
 

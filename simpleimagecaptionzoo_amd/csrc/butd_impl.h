@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "decoder_core.h"
+#include "rng.h"
 
 namespace icz {
 

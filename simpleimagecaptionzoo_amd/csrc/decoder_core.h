@@ -11,8 +11,8 @@
 #include <vector>
 #include <stdint.h>
 
-#include "butd_kernels.h"
 #include "gemm_ops.h"
+#include "icz_common.h"
 
 namespace icz {
 

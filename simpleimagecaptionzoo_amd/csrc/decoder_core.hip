@@ -2,6 +2,8 @@
 #include <stdarg.h>
 
 #include "decoder_core.h"
+#include "support_kernels.h"
+#include "token_kernels.h"
 
 namespace icz {
 

@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "ens_sample.h"
+#include "token_kernels.h"
 
 namespace icz {
 

@@ -7,6 +7,8 @@
 #include <cmath>
 
 #include "ens_sample.h"
+#include "support_kernels.h"
+#include "token_kernels.h"
 
 namespace icz {
 

@@ -55,7 +55,7 @@ int gemm_finished(GemmLayout layout, GemmArgs& g, const SplitPolicy& p, const fl
 // out[m, n] = sum_z slab[z][m][n] (+ bias[n]), fixed z order.  M N % 4 == 0 (and N % 4 == 0 with a bias: four columns at a time).
 // ns == 1 copies (+ bias): callers rely on it where a dense product sits in a slab buffer.
 int launch_slab_reduce(const float* slab, int ns, int M, int N, const float* bias, float* out, hipStream_t st);
-// out[n] = sum_k X[k, n] over K rows of stride ldx (bias gradients), fixed order
+// out[n] = sum_k X[k, n] over K rows of stride ldx (bias gradients), fixed order; several sums in one launch: colsum_multi_kernel, support_kernels.h
 int launch_colsum(const float* X, int K, int N, int ldx, float* out, hipStream_t st);
 
 // ---- weight gradients: out[M x N] (ldo) (+)= dY^T X over K rows, unsplit; rows_live as in GemmArgs

@@ -60,7 +60,65 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// block-wide helpers (256 threads)
+__device__ __forceinline__ float block_max_256(float v, float* sm) {
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ float block_sum_256(float v, float* sm) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+    __syncthreads();
+    return r;
+}
+
+// Softmax over the entries a wave holds, one per lane: x is the lane's entry, or -inf where the lane holds none (in = false), and
+// the lane's weight comes back (0 without an entry).  The attention kernels of BUTD and of the AoA refiner share this expression.
+__device__ __forceinline__ float wave_softmax(float x, bool in) {
+    const float mx = wave_max(x);
+    const float e = in ? expf(x - mx) : 0.f;
+    const float sum = wave_sum(e);
+    return e / sum;
+}
+// The same with two entries per lane (lane and lane + 64): with no second entry anywhere it is wave_softmax bit for bit, the
+// second entry being the identity of both reductions.
+__device__ __forceinline__ void wave_softmax2(float x0, bool in0, float x1, bool in1, float& p0, float& p1) {
+    const float mx = wave_max(fmaxf(x0, x1));
+    const float e0 = in0 ? expf(x0 - mx) : 0.f;
+    const float e1 = in1 ? expf(x1 - mx) : 0.f;
+    const float sum = wave_sum(e0 + e1);
+    p0 = e0 / sum;
+    p1 = e1 / sum;
+}
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// sum of ns split-K slabs at one element, loads issued four at a time (independent), added in slab order
+__device__ __forceinline__ float sum_slabs1(const float* __restrict__ p, int ns, size_t stride, size_t off) {
+    float s = 0.f;
+    int z = 0;
+    for (; z + 4 <= ns; z += 4) {
+        const float a = p[(size_t)z * stride + off], b = p[(size_t)(z + 1) * stride + off];
+        const float c = p[(size_t)(z + 2) * stride + off], d = p[(size_t)(z + 3) * stride + off];
+        s += a; s += b; s += c; s += d;
+    }
+    for (; z < ns; ++z) s += p[(size_t)z * stride + off];
+    return s;
+}
+// four consecutive elements (16-byte loads): slab 0, then slabs 1 .. ns - 1 added in slab order; no slabs (p null): zeros
+__device__ __forceinline__ f32x4 sum_slabs4(const float* p, int ns, size_t slab_stride, size_t off) {
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    if (!p) return s;
+    s = *reinterpret_cast<const f32x4*>(p + off);
+    for (int z = 1; z < ns; ++z) s += *reinterpret_cast<const f32x4*>(p + (size_t)z * slab_stride + off);
+    return s;
+}
 
 // Early-out of the rollout / BPTT steps behind the reference's break (`if unfinished.sum() == 0: break`, BUTD_Model.py:233,
 // AoA_Model.py:400, NIC_Model.py:150): `live` points at the number of rows still unfinished after the PREVIOUS step of the

@@ -5,8 +5,10 @@
 
 #include <vector>
 
-#include "butd_impl.h"
 #include "ens_sample.h"
+#include "lstm_kernels.h"
+#include "support_kernels.h"
+#include "token_kernels.h"
 
 namespace icz {
 
@@ -102,7 +104,7 @@ int Nic::init(const icz_nic_dims& d) {
 
 int Nic::refresh(hipStream_t st) {
     ICZ_REQUIRE(bound, "nic: parameters not bound");
-    hipLaunchKernelGGL(weight_norm_kernel, dim3(cdiv(dims.V, 4)), dim3(256), 0, st, P.predict_v, P.predict_g, w_pred, n_pred, dims.V, dims.H);
+    launch_weight_norm(P.predict_v, P.predict_g, w_pred, n_pred, dims.V, dims.H, st);
     ICZ_CHECK_HIP(hipGetLastError());
     fresh = true;
     return ICZ_OK;
@@ -271,8 +273,7 @@ int Nic::sample_backward(const float* reward, const icz_nic_params* G, float* df
     // behind sample_n: d features of the B K rows, then the K rows of an image added in k order -> [B, E]
     ICZ_TRY(bptt(*G, dfeat_n, st));
     const int n_img = cur_B / cur_K;
-    hipLaunchKernelGGL(rowgroup_sum_kernel, dim3(cdiv((int)((size_t)n_img * dims.E / 4), 256)), dim3(256), 0, st, (const float*)dfeat_n, n_img, cur_K,
-                       (size_t)dims.E, dfeats);
+    launch_rowgroup_sum(dfeat_n, n_img, cur_K, (size_t)dims.E, dfeats, st);
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
@@ -351,8 +352,7 @@ int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st) {
     ICZ_TRY(nn(tlogit, Vp, TB, Vp, w_pred, H, H, dHd, nullptr, TARGET_WGS, st));
     ICZ_TRY(gemm_tn(tlogit, Vp, Vp, thd, H, H, TB, dWp, H, 0, nullptr, st));
     ICZ_TRY(launch_colsum(tlogit, TB, V, Vp, G.predict_b, st));
-    hipLaunchKernelGGL(weight_norm_bwd_kernel, dim3(cdiv(V, 4)), dim3(256), 0, st, dWp, H, P.predict_v, P.predict_g, n_pred, G.predict_v,
-                       G.predict_g, V, H);
+    launch_weight_norm_bwd(dWp, H, P.predict_v, P.predict_g, n_pred, G.predict_v, G.predict_g, V, H, st);
     const bool ragged = rows_t[T - 1] < B;
     if (ragged) ICZ_CHECK_HIP(hipMemsetAsync(dG, 0, sizeof(float) * (size_t)(TB + B) * 4 * H, st));
     DropCfg off = {0, nullptr, nullptr, 0, 0};

@@ -52,6 +52,12 @@ __host__ __device__ inline float rng_uniform(uint64_t seed, uint32_t step, uint6
     return (float)(r.x >> 8) * (1.0f / 16777216.0f);
 }
 
+// keep nibble of 4 consecutive mask bytes (4-byte aligned): bit j set = byte j is non-zero
+__device__ __forceinline__ uint32_t mask_keep4(const uint8_t* mask4) {
+    const uint32_t m = *reinterpret_cast<const uint32_t*>(mask4);
+    return ((m & 0xFFu) ? 1u : 0u) | ((m & 0xFF00u) ? 2u : 0u) | ((m & 0xFF0000u) ? 4u : 0u) | ((m & 0xFF000000u) ? 8u : 0u);
+}
+
 // How a kernel obtains a dropout keep-mask.
 struct DropCfg {
     int mode;               // 0 = eval (no dropout), 1 = explicit mask array, 2 = Philox
@@ -66,10 +72,7 @@ struct DropCfg {
     }
     // 4 consecutive elements starting at idx (idx % 4 == 0): bit j set = keep element idx + j
     __device__ __forceinline__ uint32_t keep4(uint64_t idx) const {
-        if (mode == 1) {
-            uint32_t m = *reinterpret_cast<const uint32_t*>(mask + idx);
-            return ((m & 0xFFu) ? 1u : 0u) | ((m & 0xFF00u) ? 2u : 0u) | ((m & 0xFF0000u) ? 4u : 0u) | ((m & 0xFF000000u) ? 8u : 0u);
-        }
+        if (mode == 1) return mask_keep4(mask + idx);
         return (rng_group_bits(*seed_p, stream, step, idx) >> (idx & 31)) & 0xFu;
     }
 };

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "ens_sample.h"
+#include "token_kernels.h"
 
 namespace icz {
 

@@ -1,5 +1,5 @@
 """Case tables and float64 reference of the kernels that turn a row of logits into a token, a log-probability or a gradient
-(csrc/butd_kernels.h: argmax_part_kernel + embed_argmax_kernel, greedy_select_kernel, sample_select_kernel<false / true>,
+(csrc/token_kernels.h: argmax_part_kernel + embed_argmax_kernel, greedy_select_kernel, sample_select_kernel<false / true>,
 ss_select_kernel, xe_loss_dlogits_kernel + sum_scale_kernel, reinforce_loss_kernel + reinforce_dlogits_kernel), each on given logits
 (tests/test_cpu_token_choice.py holds every case to its stated purpose; tests/test_gpu_token_choice.py runs the tables through the
 icz_test_* entries of include/icz.h).  Plain numpy, not collected by pytest.
