@@ -261,6 +261,46 @@ int icz_butd_beam_search_diverse(icz_butd_t* h, const float* feats, int32_t n_im
                                  const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out,
                                  float* scores_out, void* stream);
 
+/* Constrained beam search (Anderson, Fernando, Johnson, Gould, "Guided Open Vocabulary Image Captioning with Constrained Beam Search",
+ * EMNLP 2017) for the icz_*_beam_search_constrained entries: every returned caption is steered to contain given words.
+ *   Constraints.  Image img has c constraints, 0 <= c <= max_constraints = C <= 3; a constraint is a set of 1..max_alts = A <= 4
+ *     alternative word ids (singular / plural, synonyms) and is satisfied once the hypothesis contains any of them.  words_dev (a
+ *     DEVICE array) and words_host (its HOST copy, read for the checks; the dev + host contract of icz_*_set_regions) are both
+ *     [n_img, C, A] int32 with -1 for an empty slot, constraints and alternatives filled from the left.  A word id lies in [3, V)
+ *     (not <pad>, <sta>, <end>) and appears at most once among the words of its image.  Multi-word phrases are not supported.
+ *   States.  A hypothesis's state is the bit mask of its satisfied constraints: S = 2^C states, each owning `beam` row slots; an
+ *     image has K = S * beam decoder rows, state-major (row img * K + s * beam + j).  beam in 1..8, K <= 32, n_img * K within
+ *     the row capacity.  Every state runs the search of icz_*_beam_search_opts: its own capacity cap[s] (beam minus its <end>
+ *     retirements) and its own live beams.  Before step 1 only state 0 is live, with the hypothesis [<sta>] at score 0 (one
+ *     row is scored at step 1); an image with c < C constraints never sets bits >= c, so those states stay empty.
+ *   A step.  Every live row (s, j) is scored over all tokens v as run + log_softmax(logits)[v] (on the device
+ *     rs + ((x - mx) - ls)); under block_ngram a banned token scores -inf as icz_beam_opts says.  Candidate (s, j, v) has target
+ *     state s | bit(v), bit(v) = 0 for a word in none of the image's constraints.  Then, for every target t in ascending order:
+ *     t takes the best cap[t] finite candidates whose target is t, ties to the lower flat index (s * beam + j) * V + v; a pick of
+ *     <end> retires into the image's list (with t, the step, the raw score and the tokens) and lowers cap[t] by one; every other
+ *     pick becomes a live beam of t, compacted into t's slots in pick order.
+ *   The search ends at max_steps or when no state of any image has a live beam.
+ *   Result.  The image's hypotheses are its retirements in order (step, target state, merge rank) followed by the beams live at
+ *     the limit in (state, slot) order, ranked by (1) the popcount of the state, descending, (2) finished before live, (3) the
+ *     length-normalised score of icz_beam_opts, descending, (4) that order.  The first n_best (1..beam) are returned with raw summed
+ *     log-probabilities (seqs_out / lens_out / scores_out as _opts) and their states in sat_out [n_img, n_best] int32; a rank past the
+ *     image's hypotheses has length 0, score -inf and state 0.
+ *   When no image has a constraint (C = 0 or every slot -1) the call is icz_*_beam_search_opts bit for bit (its kernels; sat_out 0).
+ *   Diverse groups cannot be combined with constraints: the entries take no icz_beam_diversity.
+ * Argument errors return ICZ_ERR_INVALID before any device work (a refused call queues nothing), checked in this order: the options
+ * (as _opts); the constraints (null struct, C outside 0..3, A outside 1..4, a null word array with C > 0, beam outside 1..8,
+ * 2^C * beam above 32, n_img < 1, a slot filled behind an empty one, an id below -1, <pad> / <sta> / <end>, a repeated id); null
+ * arguments; a null handle; then, with the handle, max_steps, n_img * K above the row capacity, an id >= V, an unrefreshed handle. */
+typedef struct {
+    int32_t max_constraints;      /* C */
+    int32_t max_alts;             /* A */
+    const int32_t* words_dev;     /* [n_img, C, A] device */
+    const int32_t* words_host;    /* [n_img, C, A] host */
+} icz_beam_constraints;
+int icz_butd_beam_search_constrained(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                                     const icz_beam_opts* opts, const icz_beam_constraints* cons, float* seqs_out, int32_t* lens_out,
+                                     float* scores_out, int32_t* sat_out, void* stream);
+
 /* One decoder step from an explicit state (BUTD_Model.py:172-182) -- exposed for the per-kernel parity tests.
  * it [B] int64; state tensors [B,H] are updated in place; ctx_out [B,D], alpha_out [B,R], logits_out [B,V]. */
 int icz_butd_step(icz_butd_t* h, const float* feats, int32_t B, const int64_t* it, float* h1, float* c1,
@@ -320,6 +360,11 @@ int icz_nic_beam_search_opts(icz_nic_t* h, const float* features, int32_t n_img,
 int icz_nic_beam_search_diverse(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps,
                                 const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out,
                                 float* scores_out, void* stream);
+/* ... with constraints: captions that must contain given words (icz_beam_constraints states the search; see
+ * icz_butd_beam_search_constrained) */
+int icz_nic_beam_search_constrained(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps,
+                                    const icz_beam_opts* opts, const icz_beam_constraints* cons, float* seqs_out, int32_t* lens_out,
+                                    float* scores_out, int32_t* sat_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * AoADetection captioner (Models/AoA_Model.py:657-753): img_feats_porjection (Linear 2048->Hd + ReLU + Dropout) ->
@@ -399,6 +444,11 @@ int icz_aoa_beam_search_opts(icz_aoa_t* h, const float* feats, int32_t n_img, in
 int icz_aoa_beam_search_diverse(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
                                 const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out,
                                 float* scores_out, void* stream);
+/* ... with constraints: captions that must contain given words (icz_beam_constraints states the search; see
+ * icz_butd_beam_search_constrained) */
+int icz_aoa_beam_search_constrained(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                                    const icz_beam_opts* opts, const icz_beam_constraints* cons, float* seqs_out, int32_t* lens_out,
+                                    float* scores_out, int32_t* sat_out, void* stream);
 int icz_aoa_sample(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, const icz_aoa_rng* rng, int64_t* seq_out,
                    float* logprobs_out, void* stream);
 /* Beyond the reference (extends icz_aoa_sample as icz_butd_sample_n extends icz_butd_sample): the multi-sample rollout -- K = 2..8
@@ -462,6 +512,14 @@ int icz_ensemble_greedy(icz_ensemble_t* h, const float* const* feats, int32_t B,
 int icz_ensemble_beam_search_diverse(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t beam, int32_t max_steps,
                                      const icz_beam_opts* opts, const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out,
                                      float* scores_out, void* stream);
+/* The constrained search of icz_beam_constraints (see icz_butd_beam_search_constrained) on the combined log-probabilities: the same
+ * specification, outputs and order of argument errors, with the ensemble's features (a HOST array of M device pointers) and, behind
+ * the null handle, the member checks of the other decode entries on n_img * 2^C * beam rows.  An ensemble of one member runs the
+ * member's own search (its weight normalises to 1): the result is icz_<family>_beam_search_constrained's bit for bit, and its handle
+ * errors are the family's. */
+int icz_ensemble_beam_search_constrained(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                                         const icz_beam_opts* opts, const icz_beam_constraints* cons, float* seqs_out, int32_t* lens_out,
+                                         float* scores_out, int32_t* sat_out, void* stream);
 /* The combine kernel on its own (tests): member m's logits are finished rows [rows][ld_m] (nsplit 1) or nsplit split-K slabs
  * [nsplit][rows][ld_m] summed in slab order + bias_m.  lp_out [rows][ldo] receives lp; or, argmax_out != NULL, the greedy variant
  * writes each row's argmax there instead.  Host arrays of device pointers; bias may be NULL when every nsplit is 1. */
@@ -948,6 +1006,49 @@ int icz_test_beam_finalize(int32_t form, int32_t n_img, int32_t k, int32_t L, in
                            int32_t groups, const int32_t* n_act, const float* run, const int32_t* seqs, const int32_t* has_complete,
                            const float* best_score, const int32_t* best_len, const int32_t* best_seq, const int32_t* hyp_cnt, const float* hyp_score,
                            const int32_t* hyp_len, const int32_t* hyp_seq, float* out, int32_t* lens, float* scores, void* stream);
+/* Test entries of the constrained step's kernels (tests/test_gpu_beam_constrained_step.py), on given logits and a given state as the
+ * entries above: rows state-major (row img * K + s * beam + j, K = 2^C * beam <= 32), n_act / cap [n_img, 2^C] (cap = a state's
+ * remaining capacity, n_act <= cap <= beam its live beams), words [n_img, C, A] device word ids (-1 empty; may be null for C = 0).
+ * Host checks as above with beam in 1..8, C in 0..3, A in 1..4 (the device data is the caller's: word ids below V).
+ * Row top-k, constrained instances of the three routes: for every live row (j < n_act[img, s]) its best cap[img, s] candidates over the
+ * tokens that are no constraint word of the image into cand_val / cand_idx [n_img * K, 8] (an empty slot: index 0x7fffffff), and the
+ * score rs + ((x - mx) - ls) of constraint word c, alternative a into force_val [n_img * K, 12] slot c * 4 + a (-inf: n-gram-banned
+ * or an empty slot); rows that are not live are left untouched. */
+int icz_test_beam_rowtopk_constrained(int32_t route, const float* logits, int32_t n_img, int32_t beam, int32_t C, int32_t A, const int32_t* words,
+                                      int32_t V, int32_t ldl, int32_t step, const int32_t* n_act, const int32_t* cap, const float* run,
+                                      int32_t compact, const int32_t* seqs_in, int32_t L, int32_t ngram, float* cand_val, int32_t* cand_idx,
+                                      float* force_val, void* stream);
+/* The state one constrained step reads and writes: icz_beam_step_state without the single best hypothesis, plus words, cap, hyp_state
+ * [n_img * K] (the state of every listed retirement; the list is always kept, hyp_cnt [n_img] <= K) and force_val [n_img * K, 12]. */
+typedef struct {
+    const float* logits;
+    const int32_t* words;
+    int32_t* n_act;
+    int32_t* cap;
+    float* run;
+    const int32_t* seqs_in;
+    int32_t* seqs_out;
+    int32_t* src_row;
+    int64_t* it_next;
+    int32_t* n_live;
+    int32_t* hyp_seq;
+    float* hyp_score;
+    int32_t* hyp_len;
+    int32_t* hyp_state;
+    int32_t* hyp_cnt;
+    float* cand_val;
+    int32_t* cand_idx;
+    float* force_val;
+} icz_beam_constrained_state;
+/* One whole constrained step: the constrained row top-k (route as above), then beam_merge_states_kernel (icz_beam_constraints: "A step"). */
+int icz_test_beam_constrained_step(int32_t route, const icz_beam_constrained_state* s, int32_t n_img, int32_t beam, int32_t C, int32_t A, int32_t V,
+                                   int32_t ldl, int32_t step, int32_t L, int32_t compact, int32_t ngram, void* stream);
+/* The final ranking of a constrained search on a given state (beam_finalize_states_kernel; icz_beam_constraints: "Result"); n_best, lp_kind
+ * and lp_alpha checked as icz_beam_opts.  out [n_img, n_best, L] float32, lens / scores / sat [n_img, n_best]. */
+int icz_test_beam_finalize_states(int32_t n_img, int32_t beam, int32_t C, int32_t L, int32_t steps_done, int32_t n_best, int32_t lp_kind,
+                                  float lp_alpha, const int32_t* n_act, const float* run, const int32_t* seqs, const int32_t* hyp_cnt,
+                                  const float* hyp_score, const int32_t* hyp_len, const int32_t* hyp_state, const int32_t* hyp_seq, float* out,
+                                  int32_t* lens, float* scores, int32_t* sat, void* stream);
 /* Test entries for the kernels that turn a row of logits into a token, a log-probability or a gradient, each on given logits
  * (tests/test_gpu_token_choice.py): the library's kernels through the launch helpers of the decoders, arguments filled as the decoders
  * fill them.  All data pointers are DEVICE pointers (rows_t of icz_test_xe_loss is a HOST array).  Every entry checks its arguments on

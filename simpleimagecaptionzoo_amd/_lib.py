@@ -111,6 +111,18 @@ class BeamStepState(C.Structure):  # icz_beam_step_state
     _fields_ = [(n, C.c_void_p) for n in BEAM_STEP_FIELDS]
 
 
+class BeamConstraints(C.Structure):  # icz_beam_constraints
+    _fields_ = [("max_constraints", C.c_int32), ("max_alts", C.c_int32), ("words_dev", C.c_void_p), ("words_host", C.c_void_p)]
+
+
+BEAM_CONSTRAINED_FIELDS = ("logits", "words", "n_act", "cap", "run", "seqs_in", "seqs_out", "src_row", "it_next", "n_live", "hyp_seq",
+                           "hyp_score", "hyp_len", "hyp_state", "hyp_cnt", "cand_val", "cand_idx", "force_val")
+
+
+class BeamConstrainedState(C.Structure):  # icz_beam_constrained_state
+    _fields_ = [(n, C.c_void_p) for n in BEAM_CONSTRAINED_FIELDS]
+
+
 class SampleSelectArgs(C.Structure):   # icz_sample_select_args
     _fields_ = [("logits", C.c_void_p), ("V", C.c_int32), ("ldl", C.c_int32), ("ns", C.c_int32), ("slab_stride", C.c_int64),
                 ("bias", C.c_void_p), ("logits_store", C.c_void_p), ("uniforms", C.c_void_p), ("seed", C.c_void_p), ("t", C.c_int32),
@@ -170,6 +182,7 @@ def lib():
         "icz_butd_beam_search": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "icz_butd_beam_search_opts": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), vp, vp, vp, vp]),
         "icz_butd_beam_search_diverse": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamDiversity), vp, vp, vp, vp]),
+        "icz_butd_beam_search_constrained": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamConstraints), vp, vp, vp, vp, vp]),
         "icz_butd_sample_mask_sum": (C.c_int, [vp, vp, vp]),
         "icz_butd_xe_forward": (C.c_int, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Rng), i32, vp, vp]),
         "icz_butd_xe_backward": (C.c_int, [vp, f32, C.POINTER(ButdParams), vp, f32, vp]),
@@ -194,6 +207,7 @@ def lib():
         "icz_nic_beam_search": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "icz_nic_beam_search_opts": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), vp, vp, vp, vp]),
         "icz_nic_beam_search_diverse": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamDiversity), vp, vp, vp, vp]),
+        "icz_nic_beam_search_constrained": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamConstraints), vp, vp, vp, vp, vp]),
         "icz_aoa_create": (C.c_int, [C.POINTER(AoaDims), C.POINTER(vp)]),
         "icz_aoa_destroy": (C.c_int, [vp]),
         "icz_aoa_bind_params": (C.c_int, [vp, C.POINTER(AoaParams)]),
@@ -206,11 +220,14 @@ def lib():
         "icz_aoa_beam_search": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "icz_aoa_beam_search_opts": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), vp, vp, vp, vp]),
         "icz_aoa_beam_search_diverse": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamDiversity), vp, vp, vp, vp]),
+        "icz_aoa_beam_search_constrained": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamConstraints), vp, vp, vp, vp, vp]),
         "icz_ensemble_create": (C.c_int, [C.POINTER(i32), C.POINTER(vp), C.POINTER(f32), i32, C.POINTER(vp)]),
         "icz_ensemble_destroy": (C.c_int, [vp]),
         "icz_ensemble_greedy": (C.c_int, [vp, C.POINTER(vp), i32, i32, vp, vp]),
         "icz_ensemble_beam_search_diverse": (C.c_int, [vp, C.POINTER(vp), i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamDiversity), vp, vp,
                                                        vp, vp]),
+        "icz_ensemble_beam_search_constrained": (C.c_int, [vp, C.POINTER(vp), i32, i32, i32, C.POINTER(BeamOpts), C.POINTER(BeamConstraints), vp,
+                                                           vp, vp, vp, vp]),
         "icz_ensemble_logprob": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), i32, i32, vp, i32,
                                            vp, vp]),
         "icz_ensemble_sample_decode": (C.c_int, [vp, C.POINTER(vp), i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
@@ -293,6 +310,9 @@ def lib():
         "icz_test_beam_rowtopk": (C.c_int, [i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
         "icz_test_beam_step": (C.c_int, [i32, C.POINTER(BeamStepState), i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp]),
         "icz_test_beam_finalize": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, f32, i32] + [vp] * 15),
+        "icz_test_beam_rowtopk_constrained": (C.c_int, [i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+        "icz_test_beam_constrained_step": (C.c_int, [i32, C.POINTER(BeamConstrainedState), i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "icz_test_beam_finalize_states": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, f32] + [vp] * 13),
         "icz_test_greedy_select": (C.c_int, [i32, vp, i32, i32, i32, i32, i64, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "icz_sample_select_max_vocab": (C.c_int, []),
         "icz_test_sample_select": (C.c_int, [C.POINTER(SampleSelectArgs), i32, vp]),

@@ -41,6 +41,47 @@ int BeamBuf::check_diversity(const char* who, int k, const icz_beam_diversity* d
     return ICZ_OK;
 }
 
+int BeamBuf::check_constraints(const char* who, int n_img, int beam, const icz_beam_constraints* c, bool* any) {
+    ICZ_REQUIRE(c, "%s: null constraints", who);
+    const int C = c->max_constraints, A = c->max_alts;
+    ICZ_REQUIRE(C >= 0 && C <= BEAM_CONS_MAX_C, "%s: max_constraints %d outside 0..%d", who, C, BEAM_CONS_MAX_C);
+    ICZ_REQUIRE(A >= 1 && A <= BEAM_CONS_MAX_A, "%s: max_alts %d outside 1..%d", who, A, BEAM_CONS_MAX_A);
+    ICZ_REQUIRE(C == 0 || (c->words_dev && c->words_host), "%s: null constraint words (device and host copies are both needed)", who);
+    ICZ_REQUIRE(beam >= 1 && beam <= BEAM_MAX_K, "%s: beam size %d out of range 1..%d", who, beam, BEAM_MAX_K);
+    ICZ_REQUIRE((beam << C) <= BEAM_CONS_MAX_ROWS, "%s: 2^%d states x %d beams exceed %d rows per image", who, C, beam, BEAM_CONS_MAX_ROWS);
+    ICZ_REQUIRE(n_img > 0, "%s: n_img %d", who, n_img);
+    *any = false;
+    for (int img = 0; img < n_img && C > 0; ++img) {
+        const int32_t* w = c->words_host + (size_t)img * C * A;
+        bool ended = false;                        // constraints filled from the left
+        for (int q = 0; q < C; ++q) {
+            const bool empty = w[q * A] < 0;
+            ICZ_REQUIRE(!(ended && !empty), "%s: image %d: constraint %d behind an empty one (fill from the left)", who, img, q);
+            ended = ended || empty;
+            bool gap = false;                      // alternatives filled from the left
+            for (int a = 0; a < A; ++a) {
+                const int v = w[q * A + a];
+                ICZ_REQUIRE(v >= -1, "%s: image %d: word id %d", who, img, v);
+                ICZ_REQUIRE(!(gap && v >= 0), "%s: image %d, constraint %d: word behind an empty slot (fill from the left)", who, img, q);
+                gap = gap || v < 0;
+                if (v < 0) continue;
+                ICZ_REQUIRE(v > 2, "%s: image %d: word id %d is <pad>, <sta> or <end>", who, img, v);
+                for (int p = 0; p < q * A + a; ++p) ICZ_REQUIRE(w[p] != v, "%s: image %d: word id %d appears twice", who, img, v);
+                *any = true;
+            }
+        }
+    }
+    return ICZ_OK;
+}
+
+int BeamBuf::check_constraint_vocab(const char* who, int n_img, int V, const icz_beam_constraints* c) {
+    const size_t n = (size_t)n_img * c->max_constraints * c->max_alts;
+    for (size_t i = 0; i < n; ++i)
+        ICZ_REQUIRE(c->words_host[i] < V, "%s: constraint word id %d outside the vocabulary (%d)", who, c->words_host[i], V);
+    ICZ_REQUIRE(((long)V << c->max_constraints) * BEAM_MAX_K < 0x7fffffff, "%s: vocabulary %d too large for %d constraints", who, V, c->max_constraints);
+    return ICZ_OK;
+}
+
 // sized for the handle's row capacity and at least 51 columns; a longer search re-allocates (the old buffers stay in the
 // handle's persistent list), the pinned read-back word is allocated once
 int BeamBuf::ensure(DeviceBuffers& m, int max_rows, int L) {
@@ -64,6 +105,9 @@ int BeamBuf::ensure(DeviceBuffers& m, int max_rows, int L) {
     ICZ_TRY(m.alloc((void**)&hyp_len, sizeof(int) * R_));
     ICZ_TRY(m.alloc((void**)&hyp_cnt, sizeof(int) * R_));
     ICZ_TRY(m.alloc((void**)&it, sizeof(int64_t) * R_));
+    ICZ_TRY(m.alloc((void**)&cap, sizeof(int) * R_));
+    ICZ_TRY(m.alloc((void**)&force_val, sizeof(float) * R_ * BEAM_CONS_SLOTS));
+    ICZ_TRY(m.alloc((void**)&hyp_state, sizeof(int32_t) * R_));
     if (!n_live_host) ICZ_CHECK_HIP(hipHostMalloc((void**)&n_live_host, sizeof(int) * 4, 0));
     ICZ_TRY(m.synced());
     cap_rows = (int)R_;
@@ -71,19 +115,24 @@ int BeamBuf::ensure(DeviceBuffers& m, int max_rows, int L) {
     return ICZ_OK;
 }
 
-int BeamBuf::begin(int n_img, int k, int L, hipStream_t st) {
+int BeamBuf::begin(int n_img, int k, int L, hipStream_t st, int states) {
     const int rows = n_img * k;
     ICZ_CHECK_HIP(hipMemsetAsync(n_live, 0, sizeof(int) * 260, st));
     ICZ_CHECK_HIP(hipMemsetAsync(run, 0, sizeof(float) * rows, st));
     hipLaunchKernelGGL(beam_init_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, n_img, k, L, n_act, seqs[0], img_of_row, it, has_complete, best_score,
                        hyp_cnt);
+    if (states > 1)
+        hipLaunchKernelGGL(beam_init_states_kernel, dim3(cdiv(n_img * states, 256)), dim3(256), 0, st, n_img * states, states, k / states, n_act, cap);
     return ICZ_OK;
 }
 
 int BeamBuf::search(DecodeMember* const* m, int M, const BeamCombine* ens, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out,
-                    const icz_beam_opts& o, const icz_beam_diversity& d, float* scores_out, hipStream_t st) {
+                    const icz_beam_opts& o, const icz_beam_diversity& d, float* scores_out, hipStream_t st, const icz_beam_constraints* cons,
+                    int32_t* sat_out) {
     const int rows = n_img * k, L = max_steps + 1, G = d.groups, V = m[0]->vocab();
-    const bool listed = o.n_best > 1 || o.lp_kind != 0 || G > 1;
+    const bool listed = o.n_best > 1 || o.lp_kind != 0 || G > 1 || cons;
+    const BeamCons cn = cons ? BeamCons{cons->words_dev, cons->max_constraints, cons->max_alts, k >> cons->max_constraints, cap, force_val, hyp_state}
+                             : BeamCons{};
     bool compact_first = true;
     for (int i = 0; i < M; ++i) compact_first = compact_first && m[i]->compact_step();
     if (G > 1) hipLaunchKernelGGL(beam_init_groups_kernel, dim3(cdiv(n_img * G, 256)), dim3(256), 0, st, n_img * G, k / G, n_act);
@@ -99,9 +148,15 @@ int BeamBuf::search(DecodeMember* const* m, int M, const BeamCombine* ens, int n
         if (ens) ens->run(lv, r);
         BeamArgs a = {ens ? ens->lp : lv[0].p, V, ens ? ens->ld : lv[0].ld, k, s, L, n_act, run, seqs[sb], seqs[sb ^ 1], src_row, it, best_score,
                       best_len, best_seq, has_complete, n_live + s, listed ? hyp_seq : nullptr, hyp_score, hyp_len, listed ? hyp_cnt : nullptr};
-        launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)n_act, (const float*)run, cand_val, cand_idx,
-                            compact ? 1 : 0, seqs[sb], L, o.block_ngram, G, BEAM_ROUTE_AUTO);
-        if (G > 1)
+        if (cons)
+            launch_beam_rowtopk_cons(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)n_act, (const float*)run, cand_val, cand_idx,
+                                     compact ? 1 : 0, seqs[sb], L, o.block_ngram, BEAM_ROUTE_AUTO, cn);
+        else
+            launch_beam_rowtopk(st, rows, a.logits, a.V, a.ldl, a.k, a.step, (const int*)n_act, (const float*)run, cand_val, cand_idx,
+                                compact ? 1 : 0, seqs[sb], L, o.block_ngram, G, BEAM_ROUTE_AUTO);
+        if (cons)
+            hipLaunchKernelGGL(beam_merge_states_kernel, dim3(n_img), dim3(64), 0, st, a, cn, (const float*)cand_val, (const int*)cand_idx);
+        else if (G > 1)
             hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(n_img), dim3(64), 0, st, a, G, d.diversity, (const float*)cand_val,
                                (const int*)cand_idx);
         else
@@ -115,7 +170,11 @@ int BeamBuf::search(DecodeMember* const* m, int M, const BeamCombine* ens, int n
             if (n_live_host[0] == 0) break;
         }
     }
-    if (G > 1)
+    if (cons)
+        hipLaunchKernelGGL(beam_finalize_states_kernel, dim3(n_img), dim3(64), 0, st, k, cn.beam, 1 << cn.C, L, steps_done, o.n_best, o.lp_kind,
+                           o.lp_alpha, (const int*)n_act, (const float*)run, (const int32_t*)seqs[sb], (const int*)hyp_cnt, (const float*)hyp_score,
+                           (const int*)hyp_len, (const int32_t*)hyp_state, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out, sat_out);
+    else if (G > 1)
         hipLaunchKernelGGL(beam_finalize_nbest_kernel<true>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, o.n_best, o.lp_kind, o.lp_alpha,
                            (const int*)n_act, (const float*)run, (const int32_t*)seqs[sb], (const int*)hyp_cnt, (const float*)hyp_score,
                            (const int*)hyp_len, (const int32_t*)hyp_seq, seqs_out, lens_out, scores_out, G);
@@ -145,17 +204,42 @@ int check_members(const char* who, DecodeMember* const* m, int M, const float* c
 // per-image tensors and state, so for BUTD and AoA the order of the two is free.
 int beam_search(const char* who, DecodeMember* const* m, int M, const BeamCombine* ens, const float* const* feats, int n_img, int k,
                 int max_steps, const icz_beam_opts& o, const icz_beam_diversity& d, float* seqs_out, int32_t* lens_out, float* scores_out,
-                hipStream_t st) {
+                hipStream_t st, const icz_beam_constraints* cons, int32_t* sat_out) {
     if (!ens) ICZ_REQUIRE(feats[0] && seqs_out && lens_out, "%s beam: null argument", who);
-    ICZ_TRY(BeamBuf::check(who, n_img, k, max_steps, ens ? 1 << 30 : m[0]->row_capacity()));
+    const int S = cons ? 1 << cons->max_constraints : 1, beam = k;
+    ICZ_TRY(BeamBuf::check(who, n_img, beam, max_steps, (ens ? 1 << 30 : m[0]->row_capacity()) / S));
+    if (cons) ICZ_TRY(BeamBuf::check_constraint_vocab(who, n_img, m[0]->vocab(), cons));
+    k = S * beam;                                  // decoder rows per image
     if (ens) ICZ_TRY(check_members(ens->who, m, M, feats, n_img * k));
     else ICZ_REQUIRE(m[0]->refreshed(), "%s: call icz_%s_refresh_weights after binding/updating parameters", who, who);
     BeamBuf& bm = ens ? *ens->bm : m[0]->bm;
     const int L = max_steps + 1;
     ICZ_TRY(bm.ensure(ens ? *ens->mem : m[0]->buffers(), ens ? ens->cap : m[0]->row_capacity(), L));
-    ICZ_TRY(bm.begin(n_img, k, L, st));
+    ICZ_TRY(bm.begin(n_img, k, L, st, S));
     for (int i = 0; i < M; ++i) ICZ_TRY(m[i]->prologue(feats[i], n_img, k, bm.img_of_row, st));
-    return bm.search(m, M, ens, n_img, k, max_steps, seqs_out, lens_out, o, d, scores_out, st);
+    if (sat_out && !cons) ICZ_CHECK_HIP(hipMemsetAsync(sat_out, 0, sizeof(int32_t) * n_img * o.n_best, st));      // no constraints: every state is 0
+    return bm.search(m, M, ens, n_img, k, max_steps, seqs_out, lens_out, o, d, scores_out, st, cons, sat_out);
+}
+
+int beam_constrained_args(const char* entry, int n_img, int beam, const icz_beam_opts* opts, const icz_beam_constraints* cons, bool ptrs_ok,
+                          const icz_beam_constraints** cons_out) {
+    ICZ_TRY(BeamBuf::check_opts(entry, beam, opts));
+    bool any = false;
+    ICZ_TRY(BeamBuf::check_constraints(entry, n_img, beam, cons, &any));
+    ICZ_REQUIRE(ptrs_ok, "%s: null argument", entry);
+    *cons_out = any ? cons : nullptr;
+    return ICZ_OK;
+}
+
+// A family's icz_*_beam_search_constrained on its member m (null for a null handle)
+static int beam_constrained_entry(const char* entry, const char* who, DecodeMember* m, const float* feats, int n_img, int beam, int max_steps,
+                                  const icz_beam_opts* opts, const icz_beam_constraints* cons, float* seqs_out, int32_t* lens_out,
+                                  float* scores_out, int32_t* sat_out, void* stream) {
+    const icz_beam_constraints* use = nullptr;
+    ICZ_TRY(beam_constrained_args(entry, n_img, beam, opts, cons, feats && seqs_out && lens_out && scores_out && sat_out, &use));
+    ICZ_REQUIRE(m, "%s: null handle", entry);
+    return beam_search(who, &m, 1, nullptr, &feats, n_img, beam, max_steps, *opts, BeamBuf::no_diversity, seqs_out, lens_out, scores_out,
+                       (hipStream_t)stream, use, sat_out);
 }
 
 // The three beam entries of a family on its member m (null for a null handle): plain (the default options, scores_out may be
@@ -225,6 +309,25 @@ int icz_nic_beam_search_diverse(icz_nic_t* h, const float* features, int32_t n_i
                                 const icz_beam_diversity* div, float* seqs_out, int32_t* lens_out, float* scores_out, void* stream) {
     return beam_entry(BEAM_DIVERSE, "icz_nic_beam_search_diverse", "nic", nic_member(h), features, n_img, beam, max_steps, opts, div, seqs_out, lens_out,
                       scores_out, stream);
+}
+
+int icz_butd_beam_search_constrained(icz_butd_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                                     const icz_beam_constraints* cons, float* seqs_out, int32_t* lens_out, float* scores_out, int32_t* sat_out,
+                                     void* stream) {
+    return beam_constrained_entry("icz_butd_beam_search_constrained", "butd", butd_member(h), feats, n_img, beam, max_steps, opts, cons, seqs_out,
+                                  lens_out, scores_out, sat_out, stream);
+}
+int icz_aoa_beam_search_constrained(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                                    const icz_beam_constraints* cons, float* seqs_out, int32_t* lens_out, float* scores_out, int32_t* sat_out,
+                                    void* stream) {
+    return beam_constrained_entry("icz_aoa_beam_search_constrained", "aoa", aoa_member(h), feats, n_img, beam, max_steps, opts, cons, seqs_out,
+                                  lens_out, scores_out, sat_out, stream);
+}
+int icz_nic_beam_search_constrained(icz_nic_t* h, const float* features, int32_t n_img, int32_t beam, int32_t max_steps, const icz_beam_opts* opts,
+                                    const icz_beam_constraints* cons, float* seqs_out, int32_t* lens_out, float* scores_out, int32_t* sat_out,
+                                    void* stream) {
+    return beam_constrained_entry("icz_nic_beam_search_constrained", "nic", nic_member(h), features, n_img, beam, max_steps, opts, cons, seqs_out,
+                                  lens_out, scores_out, sat_out, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -320,6 +423,80 @@ int icz_test_beam_finalize(int32_t form, int32_t n_img, int32_t k, int32_t L, in
             hipLaunchKernelGGL(beam_finalize_nbest_kernel<false>, dim3(n_img), dim3(64), 0, st, k, L, steps_done, n_best, lp_kind, lp_alpha, n_act, run,
                                seqs, hyp_cnt, hyp_score, hyp_len, hyp_seq, out, lens, scores, 1);
     }
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+// ---- the constrained step's kernels: the shape rules of beam_test_shape on k = 2^C * beam rows per image
+static int beam_test_states_shape(const char* who, int route, const float* logits, int n_img, int beam, int C, int A, int V, int ldl, int step,
+                                  int L, int compact, int ngram) {
+    ICZ_REQUIRE(beam >= 1 && beam <= BEAM_MAX_K, "%s: beam=%d outside 1..%d", who, beam, BEAM_MAX_K);
+    ICZ_REQUIRE(C >= 0 && C <= BEAM_CONS_MAX_C && (beam << C) <= BEAM_CONS_MAX_ROWS, "%s: C=%d outside 0..%d or 2^C * beam above %d", who, C,
+                BEAM_CONS_MAX_C, BEAM_CONS_MAX_ROWS);
+    ICZ_REQUIRE(A >= 1 && A <= BEAM_CONS_MAX_A, "%s: A=%d outside 1..%d", who, A, BEAM_CONS_MAX_A);
+    ICZ_REQUIRE(n_img >= 1 && (long)n_img * (beam << C) <= (1 << 20), "%s: n_img=%d", who, n_img);
+    ICZ_REQUIRE(step >= 1 && step <= 256 && L > step, "%s: step=%d outside 1..256 or not below L=%d", who, step, L);
+    ICZ_REQUIRE(ngram == 0 || (ngram >= 2 && ngram <= 4), "%s: ngram=%d not 0, 2, 3 or 4", who, ngram);
+    ICZ_REQUIRE(compact == 0 || (compact == 1 && step == 1), "%s: compact=%d at step %d (0, or 1 at step 1)", who, compact, step);
+    ICZ_REQUIRE(V >= 1 && ldl >= V && ((long)V << C) * beam < 0x7fffffff, "%s: V=%d, ldl=%d", who, V, ldl);
+    ICZ_REQUIRE(route >= BEAM_ROUTE_AUTO && route <= BEAM_ROUTE_SWEEP, "%s: route=%d", who, route);
+    ICZ_REQUIRE(beam_rowtopk_route_fits(route, V, ldl, ((uintptr_t)logits & 15) == 0), "%s: route %d cannot take V=%d, ldl=%d, base %s", who, route,
+                V, ldl, ((uintptr_t)logits & 15) == 0 ? "aligned" : "not 16-byte aligned");
+    return ICZ_OK;
+}
+
+int icz_test_beam_rowtopk_constrained(int32_t route, const float* logits, int32_t n_img, int32_t beam, int32_t C, int32_t A, const int32_t* words,
+                                      int32_t V, int32_t ldl, int32_t step, const int32_t* n_act, const int32_t* cap, const float* run,
+                                      int32_t compact, const int32_t* seqs_in, int32_t L, int32_t ngram, float* cand_val, int32_t* cand_idx,
+                                      float* force_val, void* stream) {
+    const char* who = "icz_test_beam_rowtopk_constrained";
+    ICZ_REQUIRE(logits && n_act && cap && run && cand_val && cand_idx && force_val && (words || C == 0) && (seqs_in || !ngram), "%s: null argument",
+                who);
+    ICZ_TRY(beam_test_states_shape(who, route, logits, n_img, beam, C, A, V, ldl, step, L, compact, ngram));
+    const BeamCons cn = {words, C, A, beam, const_cast<int*>(cap), force_val, nullptr};
+    launch_beam_rowtopk_cons((hipStream_t)stream, n_img * (beam << C), logits, V, ldl, beam << C, step, n_act, run, cand_val, cand_idx, compact,
+                             seqs_in, L, ngram, route, cn);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int icz_test_beam_constrained_step(int32_t route, const icz_beam_constrained_state* s, int32_t n_img, int32_t beam, int32_t C, int32_t A, int32_t V,
+                                   int32_t ldl, int32_t step, int32_t L, int32_t compact, int32_t ngram, void* stream) {
+    const char* who = "icz_test_beam_constrained_step";
+    ICZ_REQUIRE(s, "%s: null state", who);
+    ICZ_REQUIRE(s->logits && s->n_act && s->cap && s->run && s->seqs_in && s->seqs_out && s->src_row && s->it_next && s->n_live && s->hyp_seq &&
+                    s->hyp_score && s->hyp_len && s->hyp_state && s->hyp_cnt && s->cand_val && s->cand_idx && s->force_val && (s->words || C == 0),
+                "%s: null argument", who);
+    ICZ_REQUIRE(s->seqs_in != s->seqs_out, "%s: seqs_in and seqs_out are the same buffer", who);
+    ICZ_TRY(beam_test_states_shape(who, route, s->logits, n_img, beam, C, A, V, ldl, step, L, compact, ngram));
+    hipStream_t st = (hipStream_t)stream;
+    const int k = beam << C;
+    BeamArgs a = {s->logits, V, ldl, k, step, L, s->n_act, s->run, s->seqs_in, s->seqs_out, s->src_row, s->it_next, nullptr, nullptr,
+                  nullptr, nullptr, s->n_live, s->hyp_seq, s->hyp_score, s->hyp_len, s->hyp_cnt};
+    const BeamCons cn = {s->words, C, A, beam, s->cap, s->force_val, s->hyp_state};
+    launch_beam_rowtopk_cons(st, n_img * k, a.logits, V, ldl, k, step, (const int*)s->n_act, (const float*)s->run, s->cand_val, s->cand_idx, compact,
+                             s->seqs_in, L, ngram, route, cn);
+    hipLaunchKernelGGL(beam_merge_states_kernel, dim3(n_img), dim3(64), 0, st, a, cn, (const float*)s->cand_val, (const int*)s->cand_idx);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int icz_test_beam_finalize_states(int32_t n_img, int32_t beam, int32_t C, int32_t L, int32_t steps_done, int32_t n_best, int32_t lp_kind,
+                                  float lp_alpha, const int32_t* n_act, const float* run, const int32_t* seqs, const int32_t* hyp_cnt,
+                                  const float* hyp_score, const int32_t* hyp_len, const int32_t* hyp_state, const int32_t* hyp_seq, float* out,
+                                  int32_t* lens, float* scores, int32_t* sat, void* stream) {
+    const char* who = "icz_test_beam_finalize_states";
+    ICZ_REQUIRE(beam >= 1 && beam <= BEAM_MAX_K, "%s: beam=%d outside 1..%d", who, beam, BEAM_MAX_K);
+    ICZ_REQUIRE(C >= 0 && C <= BEAM_CONS_MAX_C && (beam << C) <= BEAM_CONS_MAX_ROWS, "%s: C=%d outside 0..%d or 2^C * beam above %d", who, C,
+                BEAM_CONS_MAX_C, BEAM_CONS_MAX_ROWS);
+    ICZ_REQUIRE(n_img >= 1 && (long)n_img * (beam << C) <= (1 << 20), "%s: n_img=%d", who, n_img);
+    ICZ_REQUIRE(steps_done >= 1 && steps_done <= 256 && L > steps_done, "%s: steps_done=%d outside 1..256 or not below L=%d", who, steps_done, L);
+    const icz_beam_opts o = {n_best, 0, lp_kind, lp_alpha};
+    ICZ_TRY(BeamBuf::check_opts(who, beam, &o));
+    ICZ_REQUIRE(n_act && run && seqs && hyp_cnt && hyp_score && hyp_len && hyp_state && hyp_seq && out && lens && scores && sat, "%s: null argument",
+                who);
+    hipLaunchKernelGGL(beam_finalize_states_kernel, dim3(n_img), dim3(64), 0, (hipStream_t)stream, beam << C, beam, 1 << C, L, steps_done, n_best,
+                       lp_kind, lp_alpha, n_act, run, seqs, hyp_cnt, hyp_score, hyp_len, hyp_state, hyp_seq, out, lens, scores, sat);
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }

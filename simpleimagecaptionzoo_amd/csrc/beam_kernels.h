@@ -4,6 +4,17 @@
 #include "icz_common.h"
 
 namespace icz {
+
+// A constrained search's side of one step (icz_beam_constraints): the image's k = 2^C * beam rows are 2^C states of `beam` slots.
+constexpr int BEAM_CONS_MAX_C = 3, BEAM_CONS_MAX_A = 4, BEAM_CONS_SLOTS = BEAM_CONS_MAX_C * BEAM_CONS_MAX_A, BEAM_CONS_MAX_ROWS = 32;
+struct BeamCons {
+    const int32_t* words;   // [n_img, C, A] word ids, -1 = empty slot
+    int C, A, beam;
+    int* cap;               // [n_img, 2^C] capacity of a state: beam minus its <end> retirements (n_act [n_img, 2^C] <= cap)
+    float* force_val;       // [rows, 12] score of constraint word c * 4 + a on every scored row (-inf: n-gram-banned or empty slot)
+    int32_t* hyp_state;     // [rows] state of every listed retirement, beside hyp_seq / hyp_score / hyp_len
+};
+
 namespace {
 
 constexpr int BEAM_MAX_K = 8;
@@ -44,6 +55,24 @@ __device__ inline bool beam_banned(int v, const int* s_ban, int nban) {
     return b;
 }
 
+// Constrained search (BeamCons, decoder_core.h): the image's constraint words in LDS, slot c * 4 + a (-1: empty).  Every thread calls
+// it; the caller synchronises before reading s_cw.
+__device__ inline void beam_cons_words(const BeamCons& cn, int img, int* s_cw) {
+    const int t = threadIdx.x;
+    if (t < BEAM_CONS_SLOTS) {
+        const int c = t / BEAM_CONS_MAX_A, a = t % BEAM_CONS_MAX_A;
+        s_cw[t] = (c < cn.C && a < cn.A) ? cn.words[((size_t)img * cn.C + c) * cn.A + a] : -1;
+    }
+}
+
+// Constrained search, rows state-major (row img * k + s * beam + j, k = 2^C * beam), n_act / cap [n_img, 2^C]: a live row of state s
+// emits cap[s] ordinary candidates (the state's remaining capacity; its live beams never exceed it).  Step 1 needs no special case:
+// the search starts with n_act = 1 in state 0 and 0 elsewhere.
+__device__ inline int beam_row_cands_states(const int* __restrict__ n_act, const BeamCons& cn, int img, int r) {
+    const int S = 1 << cn.C, s = r / cn.beam, j = r % cn.beam;
+    return j < n_act[img * S + s] ? min(max(cn.cap[img * S + s], 0), BEAM_MAX_K) : 0;
+}
+
 // Candidates the row-top-k emits for row `row` (r = its slot within its image) this step; 0: the row is not scored.
 // Plain search: every live row emits n_act[img]; step 1 scores row 0 only (:273-274).
 // Grouped (diverse) search, rows group-major (row img * k + g * kg + j, kg = k / groups), n_act [n_img, groups]: a live row of
@@ -72,19 +101,32 @@ __device__ inline int beam_row_cands(const int* __restrict__ n_act, int img, int
 // Blocking (ngram > 0, from step ngram on; seqs_in / L: the rows' prefixes): a banned token scores -inf after the log-softmax,
 // whose normaliser still runs over the whole row.  Here a banned token is skipped where it would enter a thread's list; BAN = false
 // (no list this step) compiles the kernel without the test (the list check costs it 20 VGPRs and its occupancy).
-template <bool BAN, bool GROUPED>
+// CONS (a constrained search, always with BAN): the image's constraint words join the list behind the n-gram bans (at most 255 + 12
+// entries), so the row's top cap[state] covers the other tokens only, and the score of every constraint word goes to force_val
+// [rows, 12] (slot c * 4 + a; -inf: n-gram-banned or an empty slot) with the mx / ls of the row's top-k.
+template <bool BAN, bool GROUPED, bool CONS = false>
 __global__ __launch_bounds__(256) void beam_rowtopk_kernel(const float* __restrict__ logits, int V, int ldl, int k, int step,
                                                            const int* __restrict__ n_act, const float* __restrict__ run,
                                                            float* __restrict__ cand_val, int* __restrict__ cand_idx, int compact,
-                                                           const int32_t* __restrict__ seqs_in, int L, int ngram, int groups) {
+                                                           const int32_t* __restrict__ seqs_in, int L, int ngram, int groups, BeamCons cn) {
     __shared__ float smf[4];
     __shared__ float s_val[4];
     __shared__ int s_idx[4], s_who[4];
-    __shared__ int s_ban[256], s_nban;
+    __shared__ int s_ban[256 + BEAM_CONS_SLOTS], s_nban, s_cw[BEAM_CONS_SLOTS];
     const int row = blockIdx.x, img = row / k, r = row % k, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int na = beam_row_cands<GROUPED>(n_act, img, r, k, groups, step);     // candidates of this row (0: not scored)
+    const int na = CONS ? beam_row_cands_states(n_act, cn, img, r) : beam_row_cands<GROUPED>(n_act, img, r, k, groups, step);     // candidates of this row (0: not scored)
     if (na == 0) return;
-    const int nban = BAN ? beam_ban_list(seqs_in + (size_t)row * L, step, ngram, s_ban, &s_nban) : 0;
+    int nban = 0, nban_ngram = 0;          // entries of the list; those of them that are n-gram bans (the first ones)
+    if (CONS) {
+        beam_cons_words(cn, img, s_cw);
+        if (ngram && step >= ngram) nban_ngram = beam_ban_list(seqs_in + (size_t)row * L, step, ngram, s_ban, &s_nban);
+        else { if (tid == 0) s_nban = 0; __syncthreads(); }
+        if (tid < BEAM_CONS_SLOTS && s_cw[tid] >= 0) s_ban[atomicAdd(&s_nban, 1)] = s_cw[tid];
+        __syncthreads();
+        nban = s_nban;
+    } else if (BAN) {
+        nban = beam_ban_list(seqs_in + (size_t)row * L, step, ngram, s_ban, &s_nban);
+    }
     const float* l = logits + (size_t)(compact ? img : row) * ldl;      // compact (step 1 only): one decoder row per image
     // Every sweep fetches the thread's strided slice (40 logits at V = 10102) in batches of U independent loads: one memory
     // latency per batch instead of one per element.  (All 40 in registers across the three sweeps: the unrolled kernel
@@ -112,6 +154,11 @@ __global__ __launch_bounds__(256) void beam_rowtopk_kernel(const float* __restri
     se = block_sum_256(se, smf);
     const float ls = logf(se);
     const float rs = (step == 1) ? 0.f : run[row];
+    if (CONS && tid < BEAM_CONS_SLOTS) {
+        const int w = s_cw[tid];
+        const bool ok = w >= 0 && w < V && !beam_banned(w, s_ban, nban_ngram);
+        cn.force_val[(size_t)row * BEAM_CONS_SLOTS + tid] = ok ? rs + ((l[w] - mx) - ls) : -INFINITY;
+    }
     // thread-local best `na` of its strided slice (sorted: value descending, index ascending on ties)
     float tv[BEAM_MAX_K];
     int ti[BEAM_MAX_K];
@@ -185,22 +232,26 @@ __global__ __launch_bounds__(256) void beam_rowtopk_kernel(const float* __restri
 // Blocking: the thread that owns a banned token sets its score to -inf before its maximum is taken (a fully unrolled select:
 // no dynamic register index), so tau, the candidate list and the overflow path never see it.  The ban list lives at the
 // start of the overflow path's LDS row, which is written only after the list has been read.
+// CONS (a constrained search): behind the n-gram bans the thread that owns a constraint word of the image writes its score to
+// force_val [rows, 12] (slot c * 4 + a; an n-gram-banned word is -inf by then, an empty slot is written as -inf) and sets it to
+// -inf in its registers, the same unrolled select: tau, the list and the overflow path see the other tokens only.
 constexpr int BEAM_CAND_CAP = 128;
-template <int NV4, bool GROUPED>
+template <int NV4, bool GROUPED, bool CONS = false>
 __global__ __launch_bounds__(256) void beam_rowtopk_reg_kernel(const float* __restrict__ logits, int V, int ldl, int k, int step,
                                                                const int* __restrict__ n_act, const float* __restrict__ run,
                                                                float* __restrict__ cand_val, int* __restrict__ cand_idx, int compact,
-                                                               const int32_t* __restrict__ seqs_in, int L, int ngram, int groups) {
+                                                               const int32_t* __restrict__ seqs_in, int L, int ngram, int groups, BeamCons cn) {
     __shared__ float smf[4];
     __shared__ float s_val[4];
     __shared__ int s_idx[4], s_who[4];
-    __shared__ int s_cnt, s_taken, s_nban;
+    __shared__ int s_cnt, s_taken, s_nban, s_cw[BEAM_CONS_SLOTS];
     __shared__ float s_cv[BEAM_CAND_CAP];
     __shared__ int s_ci[BEAM_CAND_CAP];
     extern __shared__ __attribute__((aligned(16))) float s_row[];          // overflow path only: 1024 NV4 floats
     const int row = blockIdx.x, img = row / k, r = row % k, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int na = beam_row_cands<GROUPED>(n_act, img, r, k, groups, step);     // candidates of this row (0: not scored)
+    const int na = CONS ? beam_row_cands_states(n_act, cn, img, r) : beam_row_cands<GROUPED>(n_act, img, r, k, groups, step);     // candidates of this row (0: not scored)
     if (na == 0) return;
+    if (CONS) beam_cons_words(cn, img, s_cw);      // read behind the barriers of the block reductions below
     const float* l = logits + (size_t)(compact ? img : row) * ldl;      // compact (step 1 only): one decoder row per image
     f32x4 x[NV4];
 #pragma unroll
@@ -237,6 +288,25 @@ __global__ __launch_bounds__(256) void beam_rowtopk_reg_kernel(const float* __re
             for (int u = 0; u < NV4; ++u)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) x[u][j] = (u == bu && j == bj) ? -INFINITY : x[u][j];
+        }
+    }
+    if (CONS) {
+        for (int q = 0; q < BEAM_CONS_SLOTS; ++q) {
+            const int w = s_cw[q];
+            float* fv = cn.force_val + (size_t)row * BEAM_CONS_SLOTS + q;
+            if (w < 0 || w >= V) { if (tid == 0) *fv = -INFINITY; continue; }
+            const int e = w >> 2, bu = e >> 8, bj = w & 3;
+            if ((e & 255) != tid) continue;
+            float got = -INFINITY;
+#pragma unroll
+            for (int u = 0; u < NV4; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool hit = u == bu && j == bj;
+                    got = hit ? x[u][j] : got;
+                    x[u][j] = hit ? -INFINITY : x[u][j];
+                }
+            *fv = got;
         }
     }
     float tmax = -INFINITY;
@@ -364,16 +434,26 @@ inline void launch_beam_rowtopk_t(hipStream_t st, int rows, const float* logits,
                                   const float* run, float* cand_val, int* cand_idx, int compact, const int32_t* seqs_in, int L,
                                   int ngram, int groups, int route) {
     const int r = route != BEAM_ROUTE_AUTO ? route : beam_rowtopk_route(V, ldl, ((uintptr_t)logits & 15) == 0);
-    if (r == BEAM_ROUTE_REG3) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<3, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 3, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
-    else if (r == BEAM_ROUTE_REG10) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<10, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 10, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
-    else if (ngram && step >= ngram) hipLaunchKernelGGL((beam_rowtopk_kernel<true, GROUPED>), dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
-    else hipLaunchKernelGGL((beam_rowtopk_kernel<false, GROUPED>), dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups);
+    const BeamCons cn = {};
+    if (r == BEAM_ROUTE_REG3) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<3, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 3, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups, cn);
+    else if (r == BEAM_ROUTE_REG10) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<10, GROUPED>), dim3(rows), dim3(256), sizeof(float) * 1024 * 10, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups, cn);
+    else if (ngram && step >= ngram) hipLaunchKernelGGL((beam_rowtopk_kernel<true, GROUPED>), dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups, cn);
+    else hipLaunchKernelGGL((beam_rowtopk_kernel<false, GROUPED>), dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups, cn);
 }
 inline void launch_beam_rowtopk(hipStream_t st, int rows, const float* logits, int V, int ldl, int k, int step, const int* n_act,
                                 const float* run, float* cand_val, int* cand_idx, int compact = 0, const int32_t* seqs_in = nullptr,
                                 int L = 0, int ngram = 0, int groups = 1, int route = BEAM_ROUTE_AUTO) {
     if (groups > 1) launch_beam_rowtopk_t<true>(st, rows, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, groups, route);
     else launch_beam_rowtopk_t<false>(st, rows, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, 1, route);
+}
+// the constrained instances of the same three routes (k = 2^C * beam rows per image, n_act / cn.cap [n_img, 2^C])
+inline void launch_beam_rowtopk_cons(hipStream_t st, int rows, const float* logits, int V, int ldl, int k, int step, const int* n_act,
+                                     const float* run, float* cand_val, int* cand_idx, int compact, const int32_t* seqs_in, int L, int ngram,
+                                     int route, const BeamCons& cn) {
+    const int r = route != BEAM_ROUTE_AUTO ? route : beam_rowtopk_route(V, ldl, ((uintptr_t)logits & 15) == 0);
+    if (r == BEAM_ROUTE_REG3) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<3, false, true>), dim3(rows), dim3(256), sizeof(float) * 1024 * 3, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, 1, cn);
+    else if (r == BEAM_ROUTE_REG10) hipLaunchKernelGGL((beam_rowtopk_reg_kernel<10, false, true>), dim3(rows), dim3(256), sizeof(float) * 1024 * 10, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, 1, cn);
+    else hipLaunchKernelGGL((beam_rowtopk_kernel<true, false, true>), dim3(rows), dim3(256), 0, st, logits, V, ldl, k, step, n_act, run, cand_val, cand_idx, compact, seqs_in, L, ngram, 1, cn);
 }
 
 __global__ __launch_bounds__(64) void beam_merge_kernel(BeamArgs a, const float* __restrict__ cand_val, const int* __restrict__ cand_idx) {
@@ -705,6 +785,203 @@ __global__ void beam_init_kernel(int n_img, int k, int L, int* n_act, int32_t* s
 __global__ void beam_init_groups_kernel(int n, int kg, int* n_act) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) n_act[i] = kg;
+}
+
+// ---- constrained beam search (Anderson et al., "Guided Open Vocabulary Image Captioning with Constrained Beam Search", EMNLP 2017) ----
+// The k = S * beam rows of an image are S = 2^C states of `beam` slots (state-major); a hypothesis's state is the bit mask of the
+// constraints it has satisfied.  Every state runs the search of beam_merge_kernel on its own capacity cap[s] (beam minus its <end>
+// retirements) and live count n_act[s] <= cap[s]; a candidate (row of state s, token v) belongs to target state s | bit(v).
+
+// constrained search: n_act [n_img, S] = 1 for state 0 (the hypothesis [<sta>]) and 0 elsewhere, cap [n_img, S] = beam, after
+// beam_init_kernel (which wrote n_act [n_img] = k)
+__global__ void beam_init_states_kernel(int n, int S, int beam, int* n_act, int* cap) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { n_act[i] = (i % S) == 0 ? 1 : 0; cap[i] = beam; }
+}
+
+// The per-image merge of a constrained step, one wave per image.  The targets select in ascending order.  The candidates of target t
+// sit at fixed LDS positions (no atomics): 64 ordinary slots -- candidate cj of live row cr of t's own rows, the row's top cap[t]
+// over the tokens that are no constraint word of the image -- and k * 12 forced slots -- force_val[row, q] of every live row of a
+// state s with s | bit(word q) == t, which covers every move between states and every re-use of a satisfied word.  t takes its
+// best cap[t] finite candidates, ties to the lower flat index (s * beam + j) * V + v (beam_merge_kernel's rule over the image's k
+// rows); an <end> pick retires into the image's list with its state and lowers cap[t], every other pick is compacted into t's slots
+// in pick order.  n_act and cap are read once when the step begins: a target's sources are states s <= t, rewritten by then.
+constexpr int BEAM_STATES_CAND = BEAM_MAX_K * BEAM_MAX_K + BEAM_CONS_MAX_ROWS * BEAM_CONS_SLOTS;
+__global__ __launch_bounds__(64) void beam_merge_states_kernel(BeamArgs a, BeamCons cn, const float* __restrict__ cand_val,
+                                                               const int* __restrict__ cand_idx) {
+    __shared__ float s_cv[BEAM_STATES_CAND];
+    __shared__ int s_cf[BEAM_STATES_CAND];
+    __shared__ float pick_val[BEAM_MAX_K];
+    __shared__ int pick_idx[BEAM_MAX_K];
+    __shared__ int new_src[BEAM_MAX_K], new_tok[BEAM_MAX_K], s_newn;
+    __shared__ float new_run[BEAM_MAX_K];
+    __shared__ int s_na[1 << BEAM_CONS_MAX_C], s_cap[1 << BEAM_CONS_MAX_C], s_cw[BEAM_CONS_SLOTS];
+    const int img = blockIdx.x, lane = threadIdx.x;
+    const int k = a.k, V = a.V, beam = cn.beam, S = 1 << cn.C, row0 = img * k;
+    if (lane < S) {
+        s_na[lane] = min(max(a.n_act[img * S + lane], 0), beam);
+        s_cap[lane] = min(max(cn.cap[img * S + lane], 0), beam);
+    }
+    beam_cons_words(cn, img, s_cw);
+    __syncthreads();
+    const int cr = lane / BEAM_MAX_K, cj = lane % BEAM_MAX_K, nslot = BEAM_MAX_K * BEAM_MAX_K + k * BEAM_CONS_SLOTS;
+    int live = 0;
+    for (int t = 0; t < S; ++t) {                                // uniform: the LDS words it branches on are read after a barrier
+        const int capt = s_cap[t], tr0 = row0 + t * beam;
+        {
+            float val = -INFINITY;
+            int idx = 0x7fffffff;
+            if (cr < s_na[t] && cj < capt) {
+                const int ci = cand_idx[(tr0 + cr) * BEAM_MAX_K + cj];
+                if (ci >= 0 && ci < V) {          // a row with fewer than cap[t] admissible tokens leaves empty slots
+                    val = cand_val[(tr0 + cr) * BEAM_MAX_K + cj];
+                    idx = (t * beam + cr) * V + ci;
+                }
+            }
+            if (!(val > -INFINITY)) idx = 0x7fffffff;
+            s_cv[lane] = val; s_cf[lane] = idx;
+        }
+        for (int p = lane; p < k * BEAM_CONS_SLOTS; p += 64) {
+            const int r = p / BEAM_CONS_SLOTS, q = p % BEAM_CONS_SLOTS, s = r / beam, j = r % beam, w = s_cw[q];
+            float val = -INFINITY;
+            int idx = 0x7fffffff;
+            if (w >= 0 && w < V && j < s_na[s] && (s | (1 << (q / BEAM_CONS_MAX_A))) == t) {
+                val = cn.force_val[(size_t)(row0 + r) * BEAM_CONS_SLOTS + q];
+                if (val > -INFINITY) idx = r * V + w;
+            }
+            s_cv[BEAM_MAX_K * BEAM_MAX_K + p] = idx == 0x7fffffff ? -INFINITY : val;
+            s_cf[BEAM_MAX_K * BEAM_MAX_K + p] = idx;
+        }
+        // a lane reads and clears only the positions it wrote: no barrier inside the rounds
+        for (int j = 0; j < capt; ++j) {
+            float best = -INFINITY;
+            int bi = 0x7fffffff;
+            for (int p = lane; p < nslot; p += 64) {
+                const float v = s_cv[p];
+                const int f = s_cf[p];
+                if (v > best || (v == best && f < bi)) { best = v; bi = f; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ob = __shfl_xor(best, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+            }
+            if (bi != 0x7fffffff)
+                for (int p = lane; p < nslot; p += 64)
+                    if (s_cf[p] == bi) { s_cv[p] = -INFINITY; s_cf[p] = 0x7fffffff; }      // taken (flat indices are unique)
+            if (lane == 0) { pick_val[j] = best; pick_idx[j] = bi; }
+        }
+        __syncthreads();
+        if (lane == 0) {
+            int nn = 0, left = capt;
+            for (int j = 0; j < capt; ++j) {
+                if (pick_idx[j] == 0x7fffffff) continue;       // fewer finite candidates than capacity: the slot stays empty
+                const int src = pick_idx[j] / V, tok = pick_idx[j] % V;
+                if (tok == 2) {
+                    --left;
+                    if (a.hyp_cnt[img] < k) {
+                        const int32_t* ss = a.seqs_in + (size_t)(row0 + src) * a.L;
+                        const int slot = row0 + a.hyp_cnt[img]++;
+                        a.hyp_score[slot] = pick_val[j];
+                        a.hyp_len[slot] = a.step + 1;
+                        cn.hyp_state[slot] = t;
+                        int32_t* hs = a.hyp_seq + (size_t)slot * a.L;
+                        for (int i = 0; i < a.step; ++i) hs[i] = ss[i];
+                        hs[a.step] = 2;
+                    }
+                } else {
+                    new_src[nn] = src; new_tok[nn] = tok; new_run[nn] = pick_val[j];
+                    ++nn;
+                }
+            }
+            s_newn = nn;
+            a.n_act[img * S + t] = nn;
+            cn.cap[img * S + t] = left;
+            live += nn;
+        }
+        __syncthreads();
+        const int nn = s_newn;
+        for (int j = 0; j < beam; ++j) {
+            if (j < nn) {
+                const int32_t* ss = a.seqs_in + (size_t)(row0 + new_src[j]) * a.L;
+                int32_t* so = a.seqs_out + (size_t)(tr0 + j) * a.L;
+                for (int i = lane; i < a.step; i += 64) so[i] = ss[i];
+                if (lane == 0) {
+                    so[a.step] = new_tok[j];
+                    a.run[tr0 + j] = new_run[j];
+                    a.src_row[tr0 + j] = row0 + new_src[j];
+                    a.it_next[tr0 + j] = new_tok[j];
+                }
+            } else if (lane == 0) {
+                a.src_row[tr0 + j] = tr0 + j;
+                a.it_next[tr0 + j] = 0;
+            }
+        }
+        __syncthreads();                                         // the next target overwrites the candidates and pick_* / new_*
+    }
+    if (lane == 0 && live > 0) atomicAdd(a.n_live, 1);
+}
+
+// n-best selection of a constrained search, one wave per image: the image's at most k hypotheses are its retirements (hyp_*, in
+// order of step, target state, merge rank) and the beams live at the limit in (state, slot) order.  Ranked: more satisfied
+// constraints first (popcount of the state), then finished before live, then by the length-normalised score (descending), then
+// by that order.  Writes the first n_best as beam_finalize_nbest_kernel does, and each one's state to sat [n_img, n_best] (0 for a
+// rank past the image's hypotheses).
+__global__ __launch_bounds__(64) void beam_finalize_states_kernel(int k, int beam, int S, int L, int steps_done, int n_best, int lp_kind,
+                                                                  float lp_alpha, const int* __restrict__ n_act, const float* __restrict__ run,
+                                                                  const int32_t* __restrict__ seqs, const int* __restrict__ hyp_cnt,
+                                                                  const float* __restrict__ hyp_score, const int* __restrict__ hyp_len,
+                                                                  const int32_t* __restrict__ hyp_state, const int32_t* __restrict__ hyp_seq,
+                                                                  float* __restrict__ out, int32_t* __restrict__ lens,
+                                                                  float* __restrict__ scores, int32_t* __restrict__ sat) {
+    __shared__ int s_pick[BEAM_CONS_MAX_ROWS], s_src[BEAM_CONS_MAX_ROWS], s_state[BEAM_CONS_MAX_ROWS];
+    const int img = blockIdx.x, lane = threadIdx.x, row0 = img * k;
+    const int nf = min(max(hyp_cnt[img], 0), k);
+    int nl = 0;
+    for (int s = 0; s < S; ++s) nl += min(max(n_act[img * S + s], 0), beam);
+    const int tot = min(nf + nl, k);
+    const bool fin = lane < nf;
+    float raw = -INFINITY;
+    int len = 1, state = 0, src = row0;
+    if (lane < tot) {
+        if (fin) {
+            src = row0 + lane;
+            raw = hyp_score[src]; len = hyp_len[src]; state = hyp_state[src];
+        } else {
+            int q = lane - nf;
+            for (int s = 0; s < S; ++s) {
+                const int na = min(max(n_act[img * S + s], 0), beam);
+                if (q < na) { state = s; src = row0 + s * beam + q; break; }
+                q -= na;
+            }
+            raw = run[src]; len = steps_done + 1;
+        }
+    }
+    const float ns = beam_lp_norm(raw, len - 1, lp_kind, lp_alpha);
+    const int pc = __popc(state);
+    int rank = 0;
+    for (int f = 0; f < tot; ++f) {
+        const float f_ns = __shfl(ns, f, 64);
+        const int f_pc = __shfl(pc, f, 64);
+        const bool f_fin = f < nf;
+        rank += f_pc > pc || (f_pc == pc && ((f_fin && !fin) || (f_fin == fin && (f_ns > ns || (f_ns == ns && f < lane)))));
+    }
+    if (lane < BEAM_CONS_MAX_ROWS) s_pick[lane] = -1;
+    __syncthreads();
+    if (lane < tot) { s_pick[rank] = lane; s_src[lane] = src; s_state[lane] = state; }
+    __syncthreads();
+    for (int m = 0; m < n_best; ++m) {
+        const int e = s_pick[m], o = img * n_best + m;
+        const int32_t* sp = e < 0 ? nullptr : e < nf ? hyp_seq + (size_t)s_src[e] * L : seqs + (size_t)s_src[e] * L;
+        const int ln = e < 0 ? 0 : e < nf ? hyp_len[s_src[e]] : steps_done + 1;
+        for (int i = lane; i < L; i += 64) out[(size_t)o * L + i] = i < ln ? (float)sp[i] : 0.f;
+        if (lane == 0) {
+            lens[o] = ln;
+            scores[o] = e < 0 ? -INFINITY : e < nf ? hyp_score[s_src[e]] : run[s_src[e]];
+            sat[o] = e < 0 ? 0 : s_state[e];
+        }
+    }
 }
 
 }  // namespace

@@ -277,6 +277,8 @@ struct BeamBuf {
     int64_t* it = nullptr;            // the token rows of the search: every member steps on them
     float* cand_val = nullptr; int* cand_idx = nullptr;     // [rows, BEAM_MAX_K] per-row candidates of one step
     int32_t* hyp_seq = nullptr; float* hyp_score = nullptr; int *hyp_len = nullptr, *hyp_cnt = nullptr;    // n-best list (BeamArgs)
+    // constrained search (BeamCons, beam_kernels.h): capacity per (image, state), forced-candidate scores [rows, 12], state of a retirement
+    int* cap = nullptr; float* force_val = nullptr; int32_t* hyp_state = nullptr;
     BeamBuf() = default;
     BeamBuf(const BeamBuf&) = delete;
     BeamBuf& operator=(const BeamBuf&) = delete;
@@ -287,8 +289,15 @@ struct BeamBuf {
     static const icz_beam_opts defaults;                                       // n_best 1, no blocking, no length penalty
     static int check_diversity(const char* who, int k, const icz_beam_diversity* d);   // the icz_*_beam_search_diverse rules
     static const icz_beam_diversity no_diversity;                             // one group: the plain search
+    // The icz_*_beam_search_constrained rules that need no handle, in their documented order: the struct (C in 0..3, A in 1..4, the
+    // host words), beam in 1..8, 2^C * beam <= 32, and every image's words (filled from the left, in no constraint twice, not
+    // <pad> / <sta> / <end>).  *any = whether some image has a constraint (none: the call is the _opts search).
+    static int check_constraints(const char* who, int n_img, int beam, const icz_beam_constraints* c, bool* any);
+    static int check_constraint_vocab(const char* who, int n_img, int V, const icz_beam_constraints* c);      // every word below V
     int ensure(DeviceBuffers& m, int max_rows, int L);
-    int begin(int n_img, int k, int L, hipStream_t st);       // scores, live counts and the <sta> rows of every image
+    // scores, live counts and the <sta> rows of every image; states > 1 (a constrained search, k = states * beam): state 0 starts
+    // with one live beam, the others empty, every capacity at beam
+    int begin(int n_img, int k, int L, hipStream_t st, int states = 1);
     // The step loop (DecoderRNN.beam_search_sample, BUTD_Model.py:236-318, batched over images): every member's step runs the
     // decoder on `it`; the rows scored are the one member's finished logits or the ensemble's combined rows (BeamCombine); then a
     // row-top-k, the per-image merge and every member's gather re-gathering the model state by source row; every few steps one
@@ -299,8 +308,12 @@ struct BeamBuf {
     // [n_img, n_best]).  At the defaults the launches are today's; scores_out (may be null) receives the raw score of the caption.
     // Diversity (icz_beam_diversity, checked by check_diversity): groups > 1 keeps n_act per (image, group), runs the grouped
     // row-top-k instances and beam_merge_groups_kernel, and always keeps the n-best list; one group launches the plain kernels.
+    // Constraints (icz_beam_constraints, checked by check_constraints; null = none, with one group only): k = 2^C * beam rows per
+    // image, state-major; n_act and cap per (image, state); the constrained row-top-k instances, beam_merge_states_kernel and
+    // beam_finalize_states_kernel, which also writes sat_out [n_img, n_best].  The decoder steps are the same.
     int search(DecodeMember* const* m, int M, const BeamCombine* ens, int n_img, int k, int max_steps, float* seqs_out, int32_t* lens_out,
-               const icz_beam_opts& o, const icz_beam_diversity& d, float* scores_out, hipStream_t st);
+               const icz_beam_opts& o, const icz_beam_diversity& d, float* scores_out, hipStream_t st,
+               const icz_beam_constraints* cons = nullptr, int32_t* sat_out = nullptr);
 };
 
 // The per-image work, one decoder step and the beam-state gather of a decoder: the BUTD, AoA and NIC handles implement it, the
@@ -336,9 +349,15 @@ int check_members(const char* who, DecodeMember* const* m, int M, const float* c
 // Beam search over M >= 1 members on the caller's stream (include/icz.h: icz_*_beam_search*): every check, then BeamBuf::ensure,
 // begin, every member's prologue, the step loop and the final selection (BeamBuf::search).  `who` names the family in the errors.
 // ens null: M = 1, a handle's own search, scoring the member's finished logits.
+// cons (null = none): a constrained search of `k` beams per state (icz_*_beam_search_constrained), its words checked against the
+// vocabulary here; sat_out [n_img, n_best] receives the states.
 int beam_search(const char* who, DecodeMember* const* m, int M, const BeamCombine* ens, const float* const* feats, int n_img, int k,
                 int max_steps, const icz_beam_opts& o, const icz_beam_diversity& d, float* seqs_out, int32_t* lens_out, float* scores_out,
-                hipStream_t st);
+                hipStream_t st, const icz_beam_constraints* cons = nullptr, int32_t* sat_out = nullptr);
+// The argument checks of an icz_*_beam_search_constrained entry that come before its handle: the options as _opts, the constraints
+// (BeamBuf::check_constraints), null arguments.  *cons_out = `cons` if some image has a constraint, else null (the _opts search).
+int beam_constrained_args(const char* entry, int n_img, int beam, const icz_beam_opts* opts, const icz_beam_constraints* cons, bool ptrs_ok,
+                          const icz_beam_constraints** cons_out);
 // The greedy select tail of a decoder step: the argmax of the step's logits becomes it[row] and ids_out[row, t] (row stride T) and its
 // embedding row goes to the member's EmbSlot for the next step.  Split-K slabs (lv.ns > 1; 33 - 64 rows): one launch of
 // greedy_select_kernel, which also keeps the SCST baseline's count of unfinished rows (gunf / gn, may be null); finished rows: the

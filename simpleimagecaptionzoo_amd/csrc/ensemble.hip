@@ -134,6 +134,7 @@ constexpr int ENS_MAX_T = 256;        // steps of a sampling decode (the single-
 struct Ensemble {
     int M = 0, V = 0, Vp = 0, cap = 0;
     DecodeMember* m[ENS_MAX_M] = {};
+    const char* family[ENS_MAX_M] = {};      // "butd" / "aoa" / "nic": names a member in the errors of a search it runs on its own
     float logw[ENS_MAX_M] = {};
     DeviceBuffers mem;
     BeamBuf bm;
@@ -171,6 +172,7 @@ int Ensemble::init(const int32_t* kinds, void* const* members, const float* weig
     ICZ_TRY(ens_log_weights(who, weights, n, logw));
     for (int i = 0; i < n; ++i)
         m[i] = kinds[i] == ICZ_MEMBER_BUTD ? butd_member(members[i]) : kinds[i] == ICZ_MEMBER_AOA ? aoa_member(members[i]) : nic_member(members[i]);
+    for (int i = 0; i < n; ++i) family[i] = kinds[i] == ICZ_MEMBER_BUTD ? "butd" : kinds[i] == ICZ_MEMBER_AOA ? "aoa" : "nic";
     V = m[0]->vocab();
     cap = m[0]->row_capacity();
     for (int i = 1; i < n; ++i) {
@@ -322,6 +324,29 @@ int icz_ensemble_beam_search_diverse(icz_ensemble_t* h, const float* const* feat
                                  launch_combine(e->args(lv), rows, e->lp, e->Vp, nullptr, nullptr, 0, 0, st);
                              }};
     return beam_search("ensemble", e->m, e->M, &ens, feats, n_img, beam, max_steps, *opts, *div, seqs_out, lens_out, scores_out, st);
+}
+
+int icz_ensemble_beam_search_constrained(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t beam, int32_t max_steps,
+                                         const icz_beam_opts* opts, const icz_beam_constraints* cons, float* seqs_out, int32_t* lens_out,
+                                         float* scores_out, int32_t* sat_out, void* stream) {
+    const char* who = "icz_ensemble_beam_search_constrained";
+    const icz_beam_constraints* use = nullptr;
+    ICZ_TRY(beam_constrained_args(who, n_img, beam, opts, cons, seqs_out && lens_out && scores_out && sat_out, &use));
+    ICZ_REQUIRE(h, "%s: null handle", who);
+    Ensemble* e = reinterpret_cast<Ensemble*>(h);
+    hipStream_t st = (hipStream_t)stream;
+    // One member: its weight normalises to 1, so the combined row is its own log-softmax.  The search runs on the member's finished
+    // logits as the member's own entry does -- the same launches, so the same bits -- and the combine kernel is not launched.
+    if (e->M == 1) {
+        ICZ_REQUIRE(feats, "%s: null features", who);
+        return beam_search(e->family[0], e->m, 1, nullptr, feats, n_img, beam, max_steps, *opts, BeamBuf::no_diversity, seqs_out, lens_out,
+                           scores_out, st, use, sat_out);
+    }
+    const BeamCombine ens = {who, &e->bm, &e->mem, e->cap, e->lp, e->Vp, [=](const LogitsView* lv, int rows) {
+                                 launch_combine(e->args(lv), rows, e->lp, e->Vp, nullptr, nullptr, 0, 0, st);
+                             }};
+    return beam_search("ensemble", e->m, e->M, &ens, feats, n_img, beam, max_steps, *opts, BeamBuf::no_diversity, seqs_out, lens_out, scores_out, st,
+                       use, sat_out);
 }
 
 int icz_ensemble_sample_decode(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t n, int32_t max_len,

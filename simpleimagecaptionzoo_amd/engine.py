@@ -650,6 +650,19 @@ class BUTDDetection_Eng(Engine):
             result.append({"image_id": image_id, "caption": " ".join(sampled_caption)})
         return result
 
+    def constrained_captions_json_generation(self, dataloader, constraints, eval_beam_size=3, tqdm_visible=True, *, length_penalty=None,
+                                             block_ngram=0):
+        """Captions that must contain given words (an extension; include/icz.h: icz_beam_constraints, constrained.py): constrained beam
+        search with eval_beam_size beams per set of satisfied constraints.  constraints: {image id: [constraint, ...]}, a constraint
+        a word or a list of alternative words (up to 3 constraints of up to 4 words each); an image that is absent is unconstrained,
+        out-of-vocabulary alternatives are dropped and a constraint left without a word counts as unsatisfied.  Returns the JSON list
+        of eval_captions_json_generation with "satisfied" added: one boolean per constraint of the image, in the order given.  Sharded
+        over the ranks and gathered the same way; a batch above the handle's row capacity / (2^C * eval_beam_size) is decoded in
+        chunks.  With an empty dict the captions are eval_captions_json_generation's at that beam size.  Bad arguments raise
+        ValueError before any device work."""
+        return _constrained_captions_json_generation([self], None, False, dataloader, constraints, eval_beam_size, tqdm_visible, length_penalty,
+                                                     block_ngram)
+
     def sample_captions_json_generation(self, dataloader, samples_per_image=1, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                                         tqdm_visible=True):
         """Sampled captions for evaluation (an extension; include/icz.h: icz_*_sample_decode): `samples_per_image` (1..8) captions
@@ -1016,6 +1029,91 @@ def eval_ensemble_captions_json_generation(engines, dataloader, eval_beam_size=-
                 sampled_caption.append(word)
         result.append({"image_id": image_id, "caption": " ".join(sampled_caption)})
     return result
+
+
+def _constrained_captions_json_generation(engines, weights, ensemble, dataloader, constraints, beam, tqdm_visible, length_penalty, block_ngram,
+                                          max_chunk=None):
+    """The constrained search of Engine.constrained_captions_json_generation under the one engine or (ensemble) the ensemble of the
+    engines.  max_chunk (tests): at most that many images per call."""
+    from . import constrained as cst
+    from .ensemble import EnsembleHandle
+    from .handle import CaptionerBase
+    lead = engines[0]
+    if not isinstance(constraints, dict):
+        raise ValueError("constraints must map image ids to lists of constraints, got %s" % type(constraints).__name__)
+    parse_length_penalty(length_penalty)
+    if int(block_ngram) not in (0, 2, 3, 4):
+        raise ValueError("block_ngram %d not 0, 2, 3 or 4" % int(block_ngram))
+    # every image's words -> ids now, so that a bad constraint is refused before the first batch is decoded
+    given = {int(k): [[c] if isinstance(c, str) else list(c) for c in (v or [])] for k, v in constraints.items()}
+    keys = list(given)
+    enc, dropped = cst.encode_constraints([given[k] for k in keys], lead.caption_vocab)
+    packed = cst.make_constraints(enc, len(keys), len(lead.caption_vocab))
+    cst.check_beam(beam, packed.shape[1])
+    lost = {}
+    for img, q, _ in dropped:
+        lost.setdefault(keys[img], set()).add(q)
+    ids_of = dict(zip(keys, enc))
+    with _on_stream(lead):
+        for e in engines:
+            e.model.eval()
+        dp = icz_dist.is_distributed()
+        rank, world = icz_dist.rank(), icz_dist.world_size()
+        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Generating Process", tqdm_visible)
+        ens = None
+        ids_out, rows_out, keys_out = [], [], []
+        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
+            nb = len(image_ids)
+            feats = []
+            for e in engines:
+                vi = e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
+                feats.append(e._features(vi))
+            handles = [e._hot_handle() for e in engines]
+            if ensemble and (ens is None or any(a is not b for a, b in zip(ens.handles, handles))):
+                ens = EnsembleHandle(handles, weights)
+            h = ens if ensemble else handles[0]
+            words = cst.make_constraints([ids_of.get(int(i), []) for i in image_ids], nb, h.V)
+            # One C for the whole batch: a chunk with a constrained image searches the states the batch does.  A chunk without any
+            # (as a batch without any) is the plain options search on eval_beam_size rows per image, which is what an unconstrained
+            # image's state 0 runs inside a constrained call; its caption is the same as far as the decoder's GEMMs agree between
+            # the two row counts (they do on every case tested), not by construction.
+            per = h.max_rows // cst.rows_per_image(words, beam)
+            if per < 1:
+                raise ValueError("one image takes %d rows, the handle's row capacity is %d" % (cst.rows_per_image(words, beam), h.max_rows))
+            per = per if max_chunk is None else min(per, max_chunk)
+            for lo in range(0, nb, per):
+                hi = min(nb, lo + per)
+                part = [_slice_feats(f, lo, hi) for f in feats]
+                seqs, lens, _, sat = cst.beam_search(h, part if ensemble else part[0], words[lo:hi], beam, 50, 1, length_penalty, int(block_ngram))
+                seqs, lens, sat = seqs[:, 0].cpu().numpy(), lens[:, 0].cpu().numpy(), sat[:, 0].cpu().numpy()
+                # the state rides behind the tokens through the gather
+                rows_out += [np.concatenate([seqs[i, :lens[i]], [np.float32(sat[i])]]) for i in range(hi - lo)]
+            ids_out += [int(i) for i in image_ids]
+            keys_out += [(batch_i << 20) + j for j in range(nb)]      # loader order: batch index, then row
+        if dp:
+            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, lead.device)
+    result = []
+    for image_id, row in zip(ids_out, rows_out):
+        caption = CaptionerBase._words(torch.as_tensor(np.asarray(row[:-1])), lead.caption_vocab)
+        sat, q, flags = int(row[-1]), 0, []
+        for c in range(len(given.get(image_id, []))):          # a dropped constraint took no bit
+            if c in lost.get(image_id, ()):
+                flags.append(False)
+            else:
+                flags.append(bool((sat >> q) & 1))
+                q += 1
+        result.append({"image_id": image_id, "caption": " ".join(caption), "satisfied": flags})
+    return result
+
+
+def constrained_ensemble_captions_json_generation(engines, dataloader, constraints, eval_beam_size=3, tqdm_visible=True, *, weights=None,
+                                                  length_penalty=None, block_ngram=0):
+    """Engine.constrained_captions_json_generation for an ensemble of 1..4 engines (BUTD / AoA / NIC) of one vocabulary: the members
+    decode together on the averaged word probabilities (`weights`: None = uniform); the first engine's vocabulary encodes the
+    constraints and words the captions."""
+    engines = _ensemble_engine_checks(engines, weights)
+    return _constrained_captions_json_generation(engines, weights, True, dataloader, constraints, eval_beam_size, tqdm_visible, length_penalty,
+                                                 block_ngram)
 
 
 def _ensemble_engine_checks(engines, weights):
