@@ -1112,6 +1112,89 @@ int icz_test_xe_loss(float* logits, int32_t V, int32_t ldl, const int64_t* capti
 int icz_test_reinforce(const float* logp, const int64_t* seq, const float* reward, int32_t B, int32_t T, const float* mask_sum_global, float* coef,
                        float* loss_out, float* mask_sum_out, float* logits, int32_t V, int32_t ldl, const int32_t* draw, const float* lse, int32_t Bs,
                        int32_t row0, void* stream);
+/* Test entries for the kernels of the AoA family, each on given operands (tests/test_gpu_aoa_kernels.py): the library's kernels through
+ * the launch helpers of the AoA handle (route, query chunk, LDS bytes and the dynamic-LDS opt-in above 48 KB are the handle's).  All data
+ * pointers are DEVICE pointers.  Every entry checks on the host what its kernel needs -- 1..128 regions, heads of a multiple of 4 columns,
+ * 16-byte alignment wherever the kernel loads 16 bytes, the LDS budget of 156 KB, the dropout and region arguments below -- and returns
+ * ICZ_ERR_INVALID without launching otherwise.
+ *
+ * Dropout: mode 0 off, 1 keep flags (uint8, nonzero = keep; element i of the draw reads mask[i - idx0]), 2 Philox (*seed a device uint64;
+ * stream, step as the AoA handle numbers them: word (i - idx0) & 3 of counter ((i - idx0) >> 2, step, stream) >= floor(p 2^32) keeps).
+ * Kept values are multiplied by 1 / (1 - p).  Elements in front of idx0 pass unchanged: the evaluation-mode half of a paired refiner
+ * pass.  A null icz_test_dropp is mode 0.
+ *
+ * Region counts: `counts` [n_img] device int32, each 1..R (read back and checked), or NULL = R regions everywhere.  With counts the
+ * region rows are PACKED -- image i owns rows off[i] .. off[i] + counts[i] of qkv / o / Kd / Vd -- while the dropout index of a draw
+ * keeps the padded strides (R); the entry builds off / rowmap as the handle does and waits for the stream before it returns. */
+typedef struct {
+    int32_t mode;
+    const uint8_t* mask;
+    const uint64_t* seed;
+    uint32_t stream, step;
+    float p;
+    uint64_t idx0;
+} icz_test_dropp;
+/* layer_norm_kernel: y = gain (x - mean) / (std + 1e-6) + bias per row of n >= 2 columns, std unbiased (AoA_Model.py:14-25); stats
+ * (optional) [rows, 2] = (mean, 1 / (std + 1e-6)); live (optional) device int32: 0 = the launch writes nothing.  geometry 0: four rows per
+ * workgroup (the refiner's launch), 1: one wave per workgroup (the decoder's).  n <= 2048 with n % 4 == 0 keeps the row in registers
+ * (16-byte aligned x, gain, bias, y); any other n re-reads the row with scalar loads. */
+int icz_test_aoa_layer_norm(int32_t geometry, const float* x, const float* gain, const float* bias, float* y, int32_t rows, int32_t n, float* stats,
+                            const int32_t* live, void* stream);
+/* Which kernel the refiner self-attention of R regions takes, and how (host logic only, no GPU needed): returns 2 = mha_self_mfma_kernel
+ * (mha_mfma != 0, R <= 64, heads of a multiple of 64 columns), 1 = mha_self_kernel; *qc_out = query rows per pass of mha_self_kernel (R when
+ * everything fits the LDS budget, else the largest multiple of 4 that does), *lds_out = dynamic LDS bytes of the launch.  ICZ_ERR_INVALID
+ * for a shape the handle refuses. */
+int icz_aoa_self_attn_route_for(int32_t R, int32_t Hd, int32_t NH, int32_t mha_mfma, int32_t* qc_out, size_t* lds_out);
+/* Refiner self-attention of n_img images: qkv [region rows, 3 Hd] = [Q | K | V], head h in columns [h d, (h + 1) d) of each block;
+ * S = Q_h K_h^T / sqrt(d) over the image's valid keys, P = softmax_rows(S), Pd = drop(P) with draw index ((img NH + h) R + q) R + k,
+ * o [region rows, Hd] = Pd V_h.  route 0: the handle's choice, 1: mha_self_kernel, 2: mha_self_mfma_kernel (refused unless R <= 64 and
+ * d % 64 == 0).  qc 0: the handle's chunk; else a forced chunk of query rows for mha_self_kernel (R, or a multiple of 4 below R whose LDS
+ * fits the budget).  route_out / qc_out (optional, host): what was launched. */
+int icz_test_aoa_self_attn(int32_t route, const float* qkv, float* o, int32_t n_img, int32_t R, int32_t Hd, int32_t NH, const int32_t* counts,
+                           int32_t qc, const icz_test_dropp* dropp, int32_t* route_out, int32_t* qc_out, void* stream);
+/* aoa_dec_attn_kernel, one query per decoder row: row b attends image img_of_row[b] (NULL: image b; read back and checked against n_img);
+ * s_r = Qp_h . Kd_h[r] / sqrt(d), P = softmax over the image's valid regions, Pd = drop(P) with draw index (b NH + h) R + r,
+ * xatt [rows, Hd] = sum_r Pd_r Vd_h[r].  P_out / Pd_out (optional) [rows, NH, R]: exact zeros behind the image's count.  qns == 1: Qp
+ * [rows, Hd] is the finished query projection; qns > 1 (up to 16): Qp holds qns slabs, q_stride >= rows Hd floats apart, and the kernel
+ * leaves slab0 + slab1 + ... + q_bias (fp32, in that order) in Qp_store [rows, Hd].  live as above. */
+int icz_test_aoa_dec_attn(const float* Qp, int32_t qns, int64_t q_stride, const float* q_bias, float* Qp_store, const float* Kd, const float* Vd,
+                          const int32_t* img_of_row, float* xatt, float* P_out, float* Pd_out, int32_t rows, int32_t n_img, int32_t R, int32_t Hd,
+                          int32_t NH, const int32_t* counts, const icz_test_dropp* dropp, const int32_t* live, void* stream);
+/* The two LayerNorm backward kernels, one workgroup per row of n columns (a multiple of 4, at most 4096: refused otherwise); every tensor
+ * 16-byte aligned.  With xh = x - mean, inv = 1 / (std + 1e-6), dy = dq gain:
+ *   dx = dy inv - inv^2 sum(dy xh) xh / (std (n - 1)) - inv sum(dy) / n
+ * form 0, aoa_ln_bwd_kernel (the decoder's h_norm): dq = the ns_a (1..16) slabs dq_a [ns_a][rows][n] + columns [n, 2 n) of the ns_b slabs
+ *   dq_b [ns_b][rows][2 n], each summed in slab order; stats [rows, 2] = (mean, inv) of the forward pass; dq_tot [rows, n] = dq and dx out;
+ *   live (optional): 0 = nothing is written.  res and prod must be NULL.
+ * form 1, aoa_ln_bwd_dense_kernel (the refiner's norms; mean and std recomputed from x): dq = slabs dq_a (NULL with ns_a = 0: none) + the dense
+ *   dq_b [rows][n] (may be NULL; ns_b must be 0); dq_tot (optional) = dq, prod [rows, n] = dq xh inv, dx = res (optional) + the formula.
+ *   stats and live must be NULL. */
+int icz_test_aoa_ln_bwd(int32_t form, const float* dq_a, int32_t ns_a, const float* dq_b, int32_t ns_b, int32_t rows, const float* x, const float* stats,
+                        const float* gain, const float* res, float* dq_tot, float* prod, float* dx, int32_t n, const int32_t* live, void* stream);
+/* mha_self_bwd_kernel, the backward of icz_test_aoa_self_attn on the same qkv, counts and dropout draw: P is recomputed, Pd = drop(P);
+ *   dV = Pd^T dO;  dP = drop'(dO V^T);  dS = P (dP - sum_k P dP) / sqrt(d);  dQ = dS K;  dK = dS^T Q
+ * dO [region rows, Hd], dqkv [region rows, 3 Hd] = [dQ | dK | dV].  Three head tiles [R][d + 1] and two [R][R + 1] floats of LDS: above
+ * 156 KB the call is refused with the handle's message. */
+int icz_test_aoa_self_attn_bwd(const float* qkv, const float* dO, float* dqkv, int32_t n_img, int32_t R, int32_t Hd, int32_t NH, const int32_t* counts,
+                               const icz_test_dropp* dropp, void* stream);
+/* aoa_dec_attn_bwd_kernel, the backward of icz_test_aoa_dec_attn for one step: dx = columns [0, Hd) of the ns (1..16) slabs dxq
+ * [ns][rows][2 Hd] summed in slab order (dx_out [rows, Hd]); with P, Pd [rows, NH, R] of the forward pass and Qp [rows, Hd]:
+ *   dPd_r = dx_h . Vd_h[r];  dP_r = Pd_r != 0 ? keep_scale dPd_r : 0;  dS_r = P_r (dP_r - sum_k P_k dP_k) / sqrt(d);  dQp_h = sum_r dS_r Kd_h[r]
+ * dS_out [rows, NH, R] (already scaled by 1 / sqrt(d); zero behind the image's count), dQp [rows, Hd].  keep_scale: 1 without dropout,
+ * else 1 / (1 - p).  counts, img_of_row (checked against n_img) and live as for icz_test_aoa_dec_attn. */
+int icz_test_aoa_dec_attn_bwd(const float* dxq, int32_t ns, int32_t rows, const float* P, const float* Pd, const float* Qp, const float* Kd,
+                              const float* Vd, float* dQp, float* dS_out, float* dx_out, int32_t n_img, int32_t R, int32_t Hd, int32_t NH,
+                              const int32_t* counts, float keep_scale, const int32_t* live, const int32_t* img_of_row, void* stream);
+/* aoa_dkv_kernel, the gradients of the hoisted decoder keys and values summed over the decoder rows and steps of every image:
+ *   dKd[img, r, head cols] = sum_k sum_t dS[t, img G + k, head, r] Qp[t, img G + k, head cols],   dVd likewise from Pd and dx
+ * dS_all, Pd_all [T, B, NH, R], Qp_all, dx_all [T, B, Hd], dKd, dVd [region rows, Hd] (packed with counts; rows behind a count are not
+ * written).  B must be n_img * G -- the handle's decoder rows are the images' rows, row img * G + k, and nothing else -- any other B is
+ * refused.  The (k, t) pairs are added k-major, t-minor in one fp32 accumulation that passes through dKd / dVd between chunks of tc
+ * pairs, so every tc gives the same bits.  tc 0: the handle's rule (all G T pairs when they fit 48 KB of LDS, else as many as do); else a
+ * forced chunk of 1..G T pairs within 48 KB.  tc_out (optional, host): the chunk that was launched. */
+int icz_test_aoa_dkv(const float* dS_all, const float* Pd_all, const float* Qp_all, const float* dx_all, float* dKd, float* dVd, int32_t n_img,
+                     int32_t B, int32_t T, int32_t tc, int32_t R, int32_t Hd, int32_t NH, const int32_t* counts, int32_t G, int32_t* tc_out,
+                     void* stream);
 /* Live timing of the dominant kernel (the forward GEMMs of a decoder step at 33..64 rows: gemm_resident_x3_kernel, or
  * gemm_nt_kernel<4, ...> with ICZ_GEMM_RESIDENT_X3=0; see icz_prof_select) with HIP events on its launch stream, for bench.py's
  * roofline line.  Between begin and end every launch is bracketed by an event

@@ -141,6 +141,11 @@ class DistillOpts(C.Structure):    # icz_distill_opts
                 ("alpha", C.c_float), ("temperature", C.c_float), ("smoothing", C.c_float)]
 
 
+class DropPArgs(C.Structure):      # icz_test_dropp
+    _fields_ = [("mode", C.c_int32), ("mask", C.c_void_p), ("seed", C.c_void_p), ("stream", C.c_uint32), ("step", C.c_uint32),
+                ("p", C.c_float), ("idx0", C.c_uint64)]
+
+
 _lib = None
 
 
@@ -319,6 +324,14 @@ def lib():
         "icz_test_ss_select": (C.c_int, [vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
         "icz_test_xe_loss": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, C.POINTER(i32), f32, f32, vp, vp, vp, vp]),
         "icz_test_reinforce": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp]),
+        "icz_test_aoa_layer_norm": (C.c_int, [i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+        "icz_aoa_self_attn_route_for": (C.c_int, [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_size_t)]),
+        "icz_test_aoa_self_attn": (C.c_int, [i32, vp, vp, i32, i32, i32, i32, vp, i32, C.POINTER(DropPArgs), C.POINTER(i32), C.POINTER(i32), vp]),
+        "icz_test_aoa_dec_attn_bwd": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, f32, vp, vp, vp]),
+        "icz_test_aoa_ln_bwd": (C.c_int, [i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+        "icz_test_aoa_self_attn_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, C.POINTER(DropPArgs), vp]),
+        "icz_test_aoa_dkv": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(i32), vp]),
+        "icz_test_aoa_dec_attn": (C.c_int, [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.POINTER(DropPArgs), vp, vp]),
     }
     for name, (res, args) in sig.items():
         try:

@@ -1,6 +1,9 @@
 // AoADetection captioner, inference paths: feature projection + AoA refiner, decoder step, greedy and beam decoding
 // (Models/AoA_Model.py:122-162, 319-336, 403-502, 698-753).  Training paths live in aoa_train.hip.
+#include <mutex>
+
 #include "aoa_impl.h"
+#include "aoa_test_support.h"
 #include "lstm_kernels.h"
 #include "support_kernels.h"
 #include "token_kernels.h"
@@ -18,12 +21,8 @@ int Aoa::init(const icz_aoa_dims& d) {
     // 128 columns: 86 KB; 100 regions: K and V take 103 KB and the queries go through in chunks, see self_qc())
     cur_R = d.R;
     ICZ_REQUIRE(self_qc(d.R) >= 1, "aoa: K and V head tiles of %d regions do not fit the LDS budget", d.R);
-    const size_t lds_self = self_lds(d.R, self_qc(d.R));
-    const size_t lds_dec = (2 * d.R * (dh + 1) + dh + 128 + 4) * sizeof(float);
-    if (lds_self > 48 * 1024)
-        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mha_self_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_self));
-    if (lds_dec > 48 * 1024)
-        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(aoa_dec_attn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dec));
+    ICZ_TRY(aoa_self_attn_optin(self_lds(d.R, self_qc(d.R))));
+    ICZ_TRY(aoa_dec_attn_optin(aoa_dec_attn_lds(d.R, (int)dh)));
     Vp = pad_vocab(d.V);
     const size_t rows = d.max_rows, Hd = d.Hd, E = d.E, RR = rows * d.R;
     ICZ_TRY(alloc((void**)&w_pred, sizeof(float) * Vp * Hd));
@@ -101,12 +100,54 @@ int Aoa::refresh(hipStream_t st) {
 
 
 // refiner self-attention of one layer over n_img images: the matrix-pipe kernel up to 64 regions, the register-blocked one beyond
-void Aoa::launch_mha_self(int n_img, int R, int qc, size_t lds, const RegionRows& rr, const float* qkv_, float* o_, const DropP& dp, hipStream_t st) {
-    const int Hd = dims.Hd, NH = dims.NH;
-    if (mha_mfma && R <= 64 && (Hd / NH) % 64 == 0)
-        hipLaunchKernelGGL(mha_self_mfma_kernel, dim3(n_img, NH), dim3(256), sizeof(float) * 64 * 68, st, qkv_, qkv_ + Hd, qkv_ + 2 * Hd, o_, R, Hd, NH, rr, dp, 3 * Hd);
+void aoa_launch_mha_self(int n_img, int R, int Hd, int NH, bool mha_mfma, int qc, size_t lds, const RegionRows& rr, const float* qkv_, float* o_,
+                         const DropP& dp, hipStream_t st) {
+    if (aoa_self_route(R, Hd, NH, mha_mfma) == 2)
+        hipLaunchKernelGGL(mha_self_mfma_kernel, dim3(n_img, NH), dim3(256), AOA_SELF_MFMA_LDS, st, qkv_, qkv_ + Hd, qkv_ + 2 * Hd, o_, R, Hd, NH, rr, dp, 3 * Hd);
     else
         hipLaunchKernelGGL(mha_self_kernel, dim3(n_img, NH), dim3(256), lds, st, qkv_, qkv_ + Hd, qkv_ + 2 * Hd, o_, R, Hd, NH, qc, rr, dp, 3 * Hd);
+}
+
+// The dynamic-LDS limit of a kernel is process-wide: it is raised to the largest launch any handle or test entry has asked for and never
+// lowered (a second, smaller handle must not take the limit away from under the first one's launches).  One mutex for all kernels:
+// handles may be created from several threads.
+int aoa_raise_lds_limit(const void* kernel, size_t lds, size_t* raised) {
+    static std::mutex mu;
+    if (lds <= 48 * 1024) return ICZ_OK;
+    int dev = 0;
+    ICZ_CHECK_HIP(hipGetDevice(&dev));
+    const bool known = dev >= 0 && dev < AOA_LDS_LIMIT_DEVICES;
+    std::lock_guard<std::mutex> lock(mu);
+    if (known && lds <= raised[dev]) return ICZ_OK;
+    ICZ_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (known) raised[dev] = lds;
+    return ICZ_OK;
+}
+int aoa_self_attn_optin(size_t lds) {
+    static size_t raised[AOA_LDS_LIMIT_DEVICES] = {};
+    return aoa_raise_lds_limit(reinterpret_cast<const void*>(mha_self_kernel), lds, raised);
+}
+int aoa_dec_attn_optin(size_t lds) {
+    static size_t raised[AOA_LDS_LIMIT_DEVICES] = {};
+    return aoa_raise_lds_limit(reinterpret_cast<const void*>(aoa_dec_attn_kernel), lds, raised);
+}
+
+void aoa_launch_layer_norm(int geometry, const float* x, const float* gain, const float* bias, float* y, int rows, int n, float* stats,
+                           const int* live, hipStream_t st) {
+    if (geometry == 0) hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, gain, bias, y, rows, n, stats, live);
+    else hipLaunchKernelGGL(layer_norm_kernel, dim3(rows), dim3(64), 0, st, x, gain, bias, y, rows, n, stats, live);
+}
+
+void aoa_launch_dec_attn(const float* Qp, int qns, size_t q_stride, const float* q_bias, float* Qp_store, const float* Kd, const float* Vd,
+                         const int32_t* img_of_row, float* xatt, float* P_out, float* Pd_out, int rows, int R, int Hd, int NH, const RegionRows& rr,
+                         const DropP& dp, const int* live, hipStream_t st) {
+    const size_t lds = aoa_dec_attn_lds(R, Hd / NH);
+    if (qns == 1)
+        hipLaunchKernelGGL(aoa_dec_attn_kernel, dim3(rows, NH), dim3(256), lds, st, Qp, Kd, Vd, img_of_row, xatt, P_out, Pd_out, R, Hd, NH, rr, dp, 1,
+                           (size_t)0, (const float*)nullptr, (float*)nullptr, live);
+    else
+        hipLaunchKernelGGL(aoa_dec_attn_kernel, dim3(rows, NH), dim3(256), lds, st, Qp, Kd, Vd, img_of_row, xatt, P_out, Pd_out, R, Hd, NH, rr, dp, qns,
+                           q_stride, q_bias, Qp_store, live);
 }
 
 void Aoa::mha_self_layer(int n_img, int l, bool train, hipStream_t st) {
@@ -164,7 +205,7 @@ int Aoa::refine(const float* feats, int n_img, bool train, hipStream_t st, const
     float *cur = store ? xs[0] : xa, *nxt = store ? xs[1] : xb;
     for (int l = 0; l < NL; ++l) {
         const icz_aoa_block& b = P.layer[l];
-        hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, cur, b.ln_g, b.ln_b, ln, rows, Hd, (float*)nullptr);
+        aoa_launch_layer_norm(0, cur, b.ln_g, b.ln_b, ln, rows, Hd, nullptr, nullptr, st);
         ICZ_TRY(lin(ln, rows, Hd, w_qkv[l], b_qkv[l], 3 * Hd, qkv, st));         // linear_Q | linear_K | linear_V in one GEMM
         launch_mha_self(n_img, R, qc, lds, rr, qkv, o, dropp(train, rng.ref_att_mask, (size_t)l * n_img * NH * R * R, AOA_RNG_REF_ATT, l, 0.1f), st);
         const float *xo = o, *xn = ln;
@@ -179,7 +220,7 @@ int Aoa::refine(const float* feats, int n_img, bool train, hipStream_t st, const
         if (store) { cur = nxt; nxt = l + 2 <= NL ? xs[l + 2] : nullptr; }
         else { float* t_ = cur; cur = nxt; nxt = t_; }
     }
-    hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, cur, P.ref_ln_g, P.ref_ln_b, refined, rows, Hd, (float*)nullptr);
+    aoa_launch_layer_norm(0, cur, P.ref_ln_g, P.ref_ln_b, refined, rows, Hd, nullptr, nullptr, st);
     hipLaunchKernelGGL(mean_rows_kernel, dim3(cdiv(Hd, 256), n_img), dim3(256), 0, st, refined, meanf, Hd, rr);
     ICZ_TRY(lin(refined, rows, Hd, P.dec.k_w, P.dec.k_b, Hd, Kd, st));
     ICZ_TRY(lin(refined, rows, Hd, P.dec.v_w, P.dec.v_b, Hd, Vd, st));
@@ -214,7 +255,7 @@ int Aoa::refine_pair(int n_img, hipStream_t st, const float* proj) {
     float *cur = w.xa, *nxt = w.xb;
     for (int l = 0; l < NL; ++l) {
         const icz_aoa_block& b = P.layer[l];
-        hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows2, 4)), dim3(256), 0, st, cur, b.ln_g, b.ln_b, w.ln, rows2, Hd, (float*)nullptr);
+        aoa_launch_layer_norm(0, cur, b.ln_g, b.ln_b, w.ln, rows2, Hd, nullptr, nullptr, st);
         ICZ_TRY(lin(w.ln, rows2, Hd, w_qkv[l], b_qkv[l], 3 * Hd, w.qkv, st));
         launch_mha_self(n2, R, qc, lds, rr, w.qkv, w.o,
                         second(dropp(true, rng.ref_att_mask, (size_t)l * n_img * NH * R * R, AOA_RNG_REF_ATT, l, 0.1f), (size_t)n_img * NH * R * R), st);
@@ -227,7 +268,7 @@ int Aoa::refine_pair(int n_img, hipStream_t st, const float* proj) {
         if (store) ICZ_CHECK_HIP(hipMemcpyAsync(xs[l + 1], nxt + nel, sizeof(float) * nel, hipMemcpyDeviceToDevice, st));
         float* t_ = cur; cur = nxt; nxt = t_;
     }
-    hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows2, 4)), dim3(256), 0, st, cur, P.ref_ln_g, P.ref_ln_b, w.refined, rows2, Hd, (float*)nullptr);
+    aoa_launch_layer_norm(0, cur, P.ref_ln_g, P.ref_ln_b, w.refined, rows2, Hd, nullptr, nullptr, st);
     hipLaunchKernelGGL(mean_rows_kernel, dim3(cdiv(Hd, 256), n2), dim3(256), 0, st, w.refined, w.meanf, Hd, rr);
     ICZ_TRY(lin(w.refined, rows2, Hd, P.dec.k_w, P.dec.k_b, Hd, w.Kd, st));
     ICZ_TRY(lin(w.refined, rows2, Hd, P.dec.v_w, P.dec.v_b, Hd, w.Vd, st));
@@ -242,7 +283,7 @@ int Aoa::project(const float* feats, int n_img, float* out, hipStream_t st) {
 
 // One decoder step (AoA_Model.py:319-336)
 int Aoa::step(const AoaStepIO& s, hipStream_t st) {
-    const int rows = s.rows, Hd = dims.Hd, E = dims.E, NH = dims.NH, R = cur_R, dh = Hd / NH;
+    const int rows = s.rows, Hd = dims.Hd, E = dims.E, NH = dims.NH, R = cur_R;
     const unsigned eb = (unsigned)(((size_t)rows * Hd + 255) / 256);
     if (!s.emb_ready) hipLaunchKernelGGL(embed_kernel, dim3(cdiv(E, 1024), rows), dim3(256), 0, st, P.embed_weight, s.it, s.emb, rows, E, s.d_emb, 1);
     if (!s.u_ready) hipLaunchKernelGGL(aoa_u_kernel, dim3(eb), dim3(256), 0, st, meanf, s.img_of_row, s.ctx_in, s.u, rows, Hd, s.d_ctx);
@@ -255,18 +296,13 @@ int Aoa::step(const AoaStepIO& s, hipStream_t st) {
     LstmPointArgs a = {ws, ns, nullptr, nullptr, P.lstm_b_ih, P.lstm_b_hh, s.m_in, s.h_out, s.m_out, s.gates_out, nullptr, rows, Hd, s.live};
     DropCfg off = {0, nullptr, nullptr, 0, 0};
     launch_lstm_point(a, off, st);
-    hipLaunchKernelGGL(layer_norm_kernel, dim3(rows), dim3(64), 0, st, s.h_out, P.dec.ln_g, P.dec.ln_b, s.qn, rows, Hd, s.ln_stats, s.live);
-    const size_t lds = sizeof(float) * (2 * R * (dh + 1) + dh + 128 + 4);
+    aoa_launch_layer_norm(1, s.h_out, P.dec.ln_g, P.dec.ln_b, s.qn, rows, Hd, s.ln_stats, s.live, st);
     {   // query projection; when it is split over K its slabs go straight to the attention kernel, which sums them
         GemmArgs qg = gemm_args({{s.qn, P.dec.q_w, Hd, Hd, Hd}}, rows, Hd, s.Qp, Hd, s.live);      // one split: finished in Qp, with the bias
         qg.bias = P.dec.q_b;
         ICZ_TRY(gemm_slabs(GEMM_NT, qg, split_forward(STEP_WGS), ws, ws_floats, &ns, st, "aoa"));
-        if (ns == 1)
-            hipLaunchKernelGGL(aoa_dec_attn_kernel, dim3(rows, NH), dim3(256), lds, st, s.Qp, Kd, Vd, s.img_of_row, s.xatt, s.P_out, s.Pd_out, R, Hd, NH,
-                               region_rows(), s.d_att, 1, (size_t)0, (const float*)nullptr, (float*)nullptr, s.live);
-        else
-            hipLaunchKernelGGL(aoa_dec_attn_kernel, dim3(rows, NH), dim3(256), lds, st, (const float*)ws, Kd, Vd, s.img_of_row, s.xatt, s.P_out, s.Pd_out,
-                               R, Hd, NH, region_rows(), s.d_att, ns, (size_t)rows * Hd, (const float*)P.dec.q_b, s.Qp, s.live);
+        aoa_launch_dec_attn(ns == 1 ? s.Qp : ws, ns, (size_t)rows * Hd, P.dec.q_b, s.Qp, Kd, Vd, s.img_of_row, s.xatt, s.P_out, s.Pd_out, rows, R, Hd, NH,
+                            region_rows(), s.d_att, s.live, st);
     }
     GemmArgs zg = gemm_args({{s.xatt, P.dec.aoa_w, Hd, 2 * Hd, Hd}, {s.qn, P.dec.aoa_w + Hd, Hd, 2 * Hd, Hd}}, rows, 2 * Hd, ws, 2 * Hd, s.live);
     ICZ_TRY(gemm_slabs(GEMM_NT, zg, split_forward(STEP_WGS), ws, ws_floats, &ns, st, "aoa"));
@@ -434,6 +470,93 @@ int icz_aoa_set_regions(icz_aoa_t* h, int32_t regions, const int32_t* counts_dev
     n->mode = 0;
     return ICZ_OK;
 }
+// ------------------------------------------------------------------------------------------------
+// Test entries of the forward AoA kernels (include/icz.h): each checks on the host what its kernel needs, fills the kernel's arguments
+// the way the handle does and goes through the handle's launch helper, nothing more.
+int icz_test_aoa_layer_norm(int32_t geometry, const float* x, const float* gain, const float* bias, float* y, int32_t rows, int32_t n, float* stats,
+                            const int32_t* live, void* stream) {
+    const char* who = "icz_test_aoa_layer_norm";
+    ICZ_REQUIRE(x && gain && bias && y, "%s: null argument", who);
+    ICZ_REQUIRE(geometry == 0 || geometry == 1, "%s: geometry %d (0: four rows per workgroup, 1: one wave per workgroup)", who, geometry);
+    ICZ_REQUIRE(rows >= 1 && n >= 2, "%s: %d rows of %d columns (the unbiased std needs two)", who, rows, n);
+    if (n <= 2048 && n % 4 == 0)       // the register path reads and writes 16 bytes at a time
+        ICZ_REQUIRE(aoa_al16(x) && aoa_al16(gain) && aoa_al16(bias) && aoa_al16(y), "%s: x, gain, bias and y must be 16-byte aligned", who);
+    aoa_launch_layer_norm(geometry, x, gain, bias, y, rows, n, stats, live, (hipStream_t)stream);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int icz_aoa_self_attn_route_for(int32_t R, int32_t Hd, int32_t NH, int32_t mha_mfma, int32_t* qc_out, size_t* lds_out) {
+    const char* who = "icz_aoa_self_attn_route_for";
+    ICZ_TRY(aoa_test_heads(who, R, Hd, NH));
+    const int d = Hd / NH, qc = aoa_self_qc(R, d), route = aoa_self_route(R, Hd, NH, mha_mfma != 0);
+    ICZ_REQUIRE(qc >= 1, "%s: K and V head tiles of %d regions x %d columns do not fit the LDS budget", who, R, d);
+    if (qc_out) *qc_out = qc;
+    if (lds_out) *lds_out = route == 2 ? AOA_SELF_MFMA_LDS : aoa_self_lds(R, d, qc);
+    return route;
+}
+
+int icz_test_aoa_self_attn(int32_t route, const float* qkv, float* o, int32_t n_img, int32_t R, int32_t Hd, int32_t NH, const int32_t* counts,
+                           int32_t qc, const icz_test_dropp* dropp, int32_t* route_out, int32_t* qc_out, void* stream) {
+    const char* who = "icz_test_aoa_self_attn";
+    ICZ_REQUIRE(qkv && o && n_img >= 1, "%s: null argument or no image", who);
+    ICZ_TRY(aoa_test_heads(who, R, Hd, NH));
+    ICZ_REQUIRE(route >= 0 && route <= 2, "%s: route %d (0: the handle's choice, 1: mha_self_kernel, 2: mha_self_mfma_kernel)", who, route);
+    ICZ_REQUIRE(aoa_al16(qkv) && aoa_al16(o), "%s: qkv and o must be 16-byte aligned", who);
+    const int d = Hd / NH;
+    const int r = route ? route : aoa_self_route(R, Hd, NH, true);
+    ICZ_REQUIRE(r != 2 || aoa_self_route(R, Hd, NH, true) == 2, "%s: mha_self_mfma_kernel takes at most 64 regions and heads of a multiple of 64 columns "
+                "(%d regions, %d columns)", who, R, d);
+    int q = qc;
+    if (q == 0) q = aoa_self_qc(R, d);
+    else ICZ_REQUIRE(q == R || (q >= 4 && q % 4 == 0 && q < R), "%s: a forced chunk of %d query rows (a multiple of 4 up to %d regions)", who, q, R);
+    ICZ_REQUIRE(q >= 1 && aoa_self_lds(R, d, q) <= AOA_LDS_BUDGET, "%s: %d regions x %d columns in chunks of %d rows need %zu bytes of LDS (limit %zu)", who,
+                R, d, q, aoa_self_lds(R, d, q), AOA_LDS_BUDGET);
+    DropP dp;
+    ICZ_TRY(aoa_test_dropp(who, dropp, &dp));
+    if (route_out) *route_out = r;
+    if (qc_out) *qc_out = q;
+    const size_t lds = aoa_self_lds(R, d, q);
+    if (r == 1) ICZ_TRY(aoa_self_attn_optin(lds));
+    AoaTestRegions reg;
+    RegionRows rr;
+    ICZ_TRY(reg.build(who, counts, n_img, R, (hipStream_t)stream, &rr));
+    aoa_launch_mha_self(n_img, R, Hd, NH, r == 2, q, lds, rr, qkv, o, dp, (hipStream_t)stream);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int icz_test_aoa_dec_attn(const float* Qp, int32_t qns, int64_t q_stride, const float* q_bias, float* Qp_store, const float* Kd, const float* Vd,
+                          const int32_t* img_of_row, float* xatt, float* P_out, float* Pd_out, int32_t rows, int32_t n_img, int32_t R, int32_t Hd,
+                          int32_t NH, const int32_t* counts, const icz_test_dropp* dropp, const int32_t* live, void* stream) {
+    const char* who = "icz_test_aoa_dec_attn";
+    ICZ_REQUIRE(Qp && Kd && Vd && xatt && rows >= 1 && n_img >= 1, "%s: null argument, no row or no image", who);
+    ICZ_TRY(aoa_test_heads(who, R, Hd, NH));
+    ICZ_REQUIRE(aoa_al16(Kd) && aoa_al16(Vd), "%s: Kd and Vd must be 16-byte aligned", who);
+    ICZ_REQUIRE(qns >= 1 && qns <= 16, "%s: %d slabs of the query projection (1..16)", who, qns);
+    ICZ_REQUIRE(qns == 1 || (q_bias && Qp_store && q_stride >= (int64_t)rows * Hd), "%s: %d slabs need q_bias, Qp_store and a stride of at least rows * Hd "
+                "(%lld)", who, qns, (long long)q_stride);
+    ICZ_REQUIRE(img_of_row || rows <= n_img, "%s: %d rows over %d images need img_of_row", who, rows, n_img);
+    const size_t lds = aoa_dec_attn_lds(R, Hd / NH);
+    ICZ_REQUIRE(lds <= AOA_LDS_BUDGET, "%s: K and V head tiles of %d regions x %d columns need %zu bytes of LDS (limit %zu)", who, R, Hd / NH, lds,
+                AOA_LDS_BUDGET);
+    DropP dp;
+    ICZ_TRY(aoa_test_dropp(who, dropp, &dp));
+    if (img_of_row) {
+        std::vector<int32_t> ior;
+        ICZ_TRY(aoa_test_read_i32(img_of_row, rows, &ior));
+        for (int i = 0; i < rows; ++i) ICZ_REQUIRE(ior[i] >= 0 && ior[i] < n_img, "%s: row %d decodes image %d of %d", who, i, ior[i], n_img);
+    }
+    ICZ_TRY(aoa_dec_attn_optin(lds));
+    AoaTestRegions reg;
+    RegionRows rr;
+    ICZ_TRY(reg.build(who, counts, n_img, R, (hipStream_t)stream, &rr));
+    aoa_launch_dec_attn(Qp, qns, (size_t)q_stride, q_bias, Qp_store, Kd, Vd, img_of_row, xatt, P_out, Pd_out, rows, R, Hd, NH, rr, dp, live,
+                        (hipStream_t)stream);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
 int icz_aoa_greedy(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, int64_t* ids_out, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Aoa*>(h)->greedy(feats, B, max_len, ids_out, (hipStream_t)stream);

@@ -36,6 +36,77 @@ struct AoaStepIO {
                                      // entry (step_dead, icz_common.h: the reference's break, AoA_Model.py:400)
 };
 
+// ---- launch code of the AoA kernels, shared by the handle and the kernel-alone test entries (icz_test_aoa_*, include/icz.h) -------
+// They take the shape, never a handle: what they decide (route, chunk, LDS bytes, opt-in) is a function of their arguments alone.
+constexpr size_t AOA_LDS_BUDGET = 156 * 1024;
+// the one owner of a DropP: mode 0 off, 1 explicit keep-mask, 2 Philox word >= floor(p 2^32) of (*seed, stream, step)
+inline DropP aoa_dropp(int mode, const uint8_t* mask, const uint64_t* seed, uint32_t stream, int step, float p, uint64_t idx0 = 0) {
+    DropP d = {0, nullptr, seed, stream, (uint32_t)step, (uint32_t)((double)p * 4294967296.0), 1.0f / (1.0f - p)};
+    d.idx0 = idx0;
+    if (mode == 0) return d;
+    if (mode == 1) { d.mode = 1; d.mask = mask; } else d.mode = 2;
+    return d;
+}
+// mha_self_kernel's LDS for heads of d columns: K, V [R4][ld] + Q chunk [qc4][ld] + P [qc4][lp]
+inline size_t aoa_self_lds(int R, int d, int qc) {
+    const size_t ld = aoa_pitch(d), lp = aoa_pitch(R), R4 = (R + 3) & ~3, q4 = (qc + 3) & ~3;
+    return sizeof(float) * (2 * R4 * ld + q4 * ld + q4 * lp);
+}
+// query rows per pass of mha_self_kernel: all of them when the tiles fit, else the largest multiple of 4 that does (0: none)
+inline int aoa_self_qc(int R, int d) {
+    if (aoa_self_lds(R, d, R) <= AOA_LDS_BUDGET) return R;
+    int qc = R & ~3;
+    while (qc >= 4 && aoa_self_lds(R, d, qc) > AOA_LDS_BUDGET) qc -= 4;
+    return qc >= 4 ? qc : 0;
+}
+constexpr size_t AOA_SELF_MFMA_LDS = sizeof(float) * 64 * 68;      // mha_self_mfma_kernel: [RP][RP + 4], RP <= 64
+// the refiner self-attention's kernel: 2 = mha_self_mfma_kernel (<= 64 regions, heads of whole 64-column trips), 1 = mha_self_kernel
+inline int aoa_self_route(int R, int Hd, int NH, bool mha_mfma) { return mha_mfma && R <= 64 && (Hd / NH) % 64 == 0 ? 2 : 1; }
+inline size_t aoa_dec_attn_lds(int R, int d) { return sizeof(float) * (2 * (size_t)R * (d + 1) + d + 128 + 4); }
+// The one owner of the kernels' dynamic-LDS limits (aoa.hip): a launch of `lds` bytes above the 48 KB default needs its kernel's limit
+// raised first.  The limit is a property of the process, not of a handle, so it only ever grows: `raised` (one slot per device, owned by
+// the caller, one array per kernel) remembers what was set; calls are serialised.
+constexpr int AOA_LDS_LIMIT_DEVICES = 64;
+int aoa_raise_lds_limit(const void* kernel, size_t lds, size_t* raised);
+int aoa_self_attn_optin(size_t lds);
+int aoa_dec_attn_optin(size_t lds);
+void aoa_launch_mha_self(int n_img, int R, int Hd, int NH, bool mha_mfma, int qc, size_t lds, const RegionRows& rr, const float* qkv_, float* o_,
+                         const DropP& dp, hipStream_t st);
+// geometry 0: four rows per workgroup (the refiner); 1: one wave per workgroup, with stats and live (the decoder)
+void aoa_launch_layer_norm(int geometry, const float* x, const float* gain, const float* bias, float* y, int rows, int n, float* stats,
+                           const int* live, hipStream_t st);
+// Qp: the finished query projection (qns == 1) or its qns split-K slabs, q_stride apart, summed with q_bias into Qp_store
+void aoa_launch_dec_attn(const float* Qp, int qns, size_t q_stride, const float* q_bias, float* Qp_store, const float* Kd, const float* Vd,
+                         const int32_t* img_of_row, float* xatt, float* P_out, float* Pd_out, int rows, int R, int Hd, int NH, const RegionRows& rr,
+                         const DropP& dp, const int* live, hipStream_t st);
+
+// LayerNorm backward, one workgroup per row (n % 4 == 0, n <= 4096): aoa_ln_bwd_kernel on stored statistics (the decoder's h_norm;
+// aoa_train.hip) and aoa_ln_bwd_dense_kernel on recomputed ones (the refiner's norms; aoa_refine_train.hip)
+void aoa_launch_ln_bwd(const float* dq_a, int ns_a, const float* dq_b, int ns_b, int rows, const float* x, const float* stats, const float* gain,
+                       float* dq_tot, float* dx, int n, const int* live, hipStream_t st);
+void aoa_launch_ln_bwd_dense(const float* dq_a, int ns_a, const float* dq_b, int rows, const float* x, const float* gain, const float* res,
+                             float* dq_tot, float* prod, float* dx, int n, hipStream_t st);
+// mha_self_bwd_kernel (aoa_refine_train.hip): LDS bytes for images of up to R regions, the opt-in (capped at the budget: a narrower batch
+// may fit where a handle's capacity does not) and the launch
+inline size_t aoa_self_bwd_lds(int R, int d) { return sizeof(float) * mha_self_bwd_lds_floats(R, d); }
+int aoa_self_attn_bwd_optin(size_t lds);
+void aoa_launch_mha_self_bwd(const float* qkv, const float* dO, float* dqkv, int n_img, int R, int Hd, int NH, const RegionRows& rr, const DropP& dp,
+                             hipStream_t st);
+// aoa_dec_attn_bwd_kernel (aoa_train.hip): K tile, V tile [R][d + 1], q [d], dx [d], dS [128], red [4]
+inline size_t aoa_dec_attn_bwd_lds(int R, int d) { return sizeof(float) * (2 * (size_t)R * (d + 1) + 2 * (size_t)d + 128 + 4); }
+int aoa_dec_attn_bwd_optin(size_t lds);
+void aoa_launch_dec_attn_bwd(const float* dxq, int ns, int rows, const float* Pm, const float* Pdm, const float* Qp, const float* Kd, const float* Vd,
+                             float* dQp, float* dS_out, float* dx_out, int R, int Hd, int NH, const RegionRows& rr, float keep_scale, const int* live,
+                             const int32_t* img_of_row, hipStream_t st);
+// aoa_dkv_kernel: (k, t) pairs per pass -- all `pairs` of an image when their dS / Pd / Qp / dx rows fit 48 KB of LDS, else as many as do
+inline size_t aoa_dkv_lds(int tc, int R, int d) { return sizeof(float) * (size_t)tc * 2 * (R + d); }
+inline int aoa_dkv_tc(int pairs, int R, int d) {
+    const int tc_fit = (int)(48 * 1024 / (sizeof(float) * 2 * (R + d)));
+    return pairs < tc_fit ? pairs : tc_fit;
+}
+void aoa_launch_dkv(const float* dS_all, const float* Pd_all, const float* Qp_all, const float* dx_all, float* dKd, float* dVd, int n_img, int B, int T,
+                    int tc, int R, int Hd, int NH, const RegionRows& rr, int G, hipStream_t st);
+
 struct Aoa : CaptionHead, DecodeMember {
     static constexpr int STEP_WGS = 256, TARGET_WGS = 512, NL = 6;
     icz_aoa_dims dims;
@@ -127,17 +198,9 @@ struct Aoa : CaptionHead, DecodeMember {
     int32_t *off = nullptr, *rowmap = nullptr;     // per bank: row offsets / padded indices of the packed rows (RegionRows)
     RegionRows region_rows() const { return lens ? RegionRows{off, rowmap, lens, cur_R} : RegionRows{nullptr, nullptr, nullptr, cur_R}; }
     size_t region_row_count(int n_img) const { return lens ? (size_t)cur_total : (size_t)n_img * cur_R; }
-    static constexpr size_t LDS_BUDGET = 156 * 1024;
-    size_t self_lds(int R, int qc) const {       // mha_self_kernel: K, V [R4][ld] + Q chunk [qc4][ld] + P [qc4][lp]
-        const size_t ld = aoa_pitch(dims.Hd / dims.NH), lp = aoa_pitch(R), R4 = (R + 3) & ~3, q4 = (qc + 3) & ~3;
-        return sizeof(float) * (2 * R4 * ld + q4 * ld + q4 * lp);
-    }
-    int self_qc(int R) const {       // query rows per pass of mha_self_kernel: all of them when the tiles fit
-        if (self_lds(R, R) <= LDS_BUDGET) return R;
-        int qc = R & ~3;
-        while (qc >= 4 && self_lds(R, qc) > LDS_BUDGET) qc -= 4;
-        return qc >= 4 ? qc : 0;
-    }
+    static constexpr size_t LDS_BUDGET = AOA_LDS_BUDGET;
+    size_t self_lds(int R, int qc) const { return aoa_self_lds(R, dims.Hd / dims.NH, qc); }
+    int self_qc(int R) const { return aoa_self_qc(R, dims.Hd / dims.NH); }
 
     int alloc(void** p, size_t bytes) { return mem.alloc(p, bytes); }
     int init(const icz_aoa_dims& d);
@@ -147,7 +210,9 @@ struct Aoa : CaptionHead, DecodeMember {
     int refine(const float* feats, int n_img, bool train, hipStream_t st, const float* proj = nullptr);
     int refine_pair(int n_img, hipStream_t st, const float* proj);
     bool mha_mfma = true;                // icz_aoa_set_option("mha_mfma"): refiner self-attention on the fp32 matrix pipe (<= 64 regions)
-    void launch_mha_self(int n_img, int R, int qc, size_t lds, const RegionRows& rr, const float* qkv_, float* o_, const DropP& dp, hipStream_t st);
+    void launch_mha_self(int n_img, int R, int qc, size_t lds, const RegionRows& rr, const float* qkv_, float* o_, const DropP& dp, hipStream_t st) {
+        aoa_launch_mha_self(n_img, R, dims.Hd, dims.NH, mha_mfma, qc, lds, rr, qkv_, o_, dp, st);
+    }
     // layer l's self-attention of a pass of its own over n_img images, qkv -> o of the current bank (the backward pass's recompute)
     void mha_self_layer(int n_img, int l, bool train, hipStream_t st);
     int project(const float* feats, int n_img, float* out, hipStream_t st);
@@ -167,10 +232,7 @@ struct Aoa : CaptionHead, DecodeMember {
              hipStream_t st) override;
     void gather(const int32_t* src_row, int rows, int fan, hipStream_t st) override;
     DropP dropp(bool train, const uint8_t* mask, size_t off, uint32_t stream, int step, float p) const {
-        DropP d = {0, nullptr, d_seed, stream, (uint32_t)step, (uint32_t)((double)p * 4294967296.0), 1.0f / (1.0f - p)};
-        if (!train) return d;
-        if (mask) { d.mode = 1; d.mask = mask + off; } else d.mode = 2;
-        return d;
+        return aoa_dropp(!train ? 0 : mask ? 1 : 2, mask ? mask + off : nullptr, d_seed, stream, step, p);
     }
     DropCfg dropbits(bool train, const uint8_t* mask, size_t off, uint32_t stream, int step) const {
         DropCfg d = {0, nullptr, d_seed, stream, (uint32_t)step};

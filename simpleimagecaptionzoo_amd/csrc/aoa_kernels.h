@@ -5,8 +5,9 @@
 #include "rng.h"
 
 namespace icz {
-namespace {
 
+// The two argument structs are named types of the library (not of one translation unit): the launch helpers of aoa_impl.h, defined in
+// aoa.hip and called from the training files and the test entries, take them.
 // Dropout with an arbitrary drop probability p (AoA uses 0.1 / 0.3 / 0.5): explicit keep-mask or Philox word >= p*2^32.
 struct DropP {
     int mode;                 // 0 off, 1 explicit, 2 Philox
@@ -47,6 +48,8 @@ struct RegionRows {
     __device__ __forceinline__ int count(int img) const { return lens ? lens[img] : R; }
     __device__ __forceinline__ size_t padded(size_t row) const { return rowmap ? (size_t)rowmap[row] : row; }
 };
+
+namespace {
 
 // off = exclusive prefix sum of the counts, rowmap = padded index of every packed row (one workgroup)
 __global__ __launch_bounds__(256) void aoa_offsets_kernel(const int32_t* __restrict__ lens, int n_img, int R, int32_t* __restrict__ off,
@@ -171,7 +174,8 @@ __host__ __device__ __forceinline__ int aoa_pitch(int n) {
 // from 16-byte row loads of Q and K (lane (i, g) holds row i, k = 16 j + 4 g + e -- the k order of a fragment is free as long as both
 // operands use it), the scaled scores through a small LDS tile for the row softmax (one key per lane) and dropout, then O = P V with P
 // fragments from LDS and V fragments as dword loads along the head dimension.  LDS: RP x (RP + 4) floats (10 KB at 36 regions).
-// Same index for the dropout draw of P[q][k] as above.  d = Hd / NH must be a multiple of 16.
+// Same index for the dropout draw of P[q][k] as above.  d = Hd / NH must be a multiple of 64: the S loop reads 64 columns per trip
+// (aoa_self_route, aoa_impl.h, sends every other head width to mha_self_kernel).
 __global__ __launch_bounds__(256) void mha_self_mfma_kernel(const float* __restrict__ Q, const float* __restrict__ K, const float* __restrict__ V,
                                                             float* __restrict__ O, int R, int Hd, int NH, RegionRows rr, DropP dp, int ldi) {
     extern __shared__ __attribute__((aligned(16))) float sm_mha2[];

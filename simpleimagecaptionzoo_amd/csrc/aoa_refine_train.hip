@@ -7,6 +7,7 @@
 // or the explicit mask pointers with the indices the forward pass used, as the decoder's backward regenerates its own.
 // Everything runs on the caller's stream behind the joins of bptt: every workspace here has one writer at a time.
 #include "aoa_impl.h"
+#include "aoa_test_support.h"
 
 namespace icz {
 
@@ -38,11 +39,8 @@ int Aoa::alloc_refiner_train(size_t B, size_t TB) {
     const size_t widest = 2 * RR * 2 * Hd > TB * Hd ? 2 * RR * 2 * Hd : TB * Hd;
     rslab_floats = (size_t)TARGET_WGS * 4096 * 2 + widest;
     ICZ_TRY(alloc((void**)&rslab, sizeof(float) * rslab_floats));
-    const size_t lds = sizeof(float) * mha_self_bwd_lds_floats(dims.R, dims.Hd / dims.NH);
-    if (lds > 48 * 1024)      // (a narrower batch may fit where the handle's capacity does not: refiner_backward_check decides per call)
-        ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mha_self_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)(lds < LDS_BUDGET ? lds : LDS_BUDGET)));
-    return ICZ_OK;
+    // (a narrower batch may fit where the handle's capacity does not: refiner_backward_check decides per call)
+    return aoa_self_attn_bwd_optin(aoa_self_bwd_lds(dims.R, dims.Hd / dims.NH));
 }
 
 int Aoa::refiner_backward_check(const icz_aoa_params& G) const {
@@ -75,6 +73,19 @@ int rnn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, 
 
 }  // namespace
 
+void aoa_launch_ln_bwd_dense(const float* dq_a, int ns_a, const float* dq_b, int rows, const float* x, const float* gain, const float* res,
+                             float* dq_tot, float* prod, float* dx, int n, hipStream_t st) {
+    hipLaunchKernelGGL(aoa_ln_bwd_dense_kernel, dim3(rows), dim3(256), 0, st, dq_a, ns_a, dq_b, rows, x, gain, res, dq_tot, prod, dx, n);
+}
+int aoa_self_attn_bwd_optin(size_t lds) {
+    static size_t raised[AOA_LDS_LIMIT_DEVICES] = {};
+    return aoa_raise_lds_limit(reinterpret_cast<const void*>(mha_self_bwd_kernel), lds < AOA_LDS_BUDGET ? lds : AOA_LDS_BUDGET, raised);
+}
+void aoa_launch_mha_self_bwd(const float* qkv, const float* dO, float* dqkv, int n_img, int R, int Hd, int NH, const RegionRows& rr, const DropP& dp,
+                             hipStream_t st) {
+    hipLaunchKernelGGL(mha_self_bwd_kernel, dim3(n_img, NH), dim3(256), aoa_self_bwd_lds(R, Hd / NH), st, qkv, dO, dqkv, R, Hd, NH, rr, dp);
+}
+
 int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
     use_bank(1);
     // B = images; behind the multi-sample rollout (sample_n) the decoder ran cur_K rows per image: only d meanf tells rows from images
@@ -96,12 +107,10 @@ int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
     hipLaunchKernelGGL(aoa_dref_kernel, dim3(cdiv(Hd, 256), B), dim3(256), 0, st, rslab, nsk, rslab + half, nsv, nel, rdmean, rdq, Hd, rr);
     // ---- 2. aoa_refine.norm
     int c = 0;
-    hipLaunchKernelGGL(aoa_ln_bwd_dense_kernel, dim3(rows), dim3(256), 0, st, (const float*)nullptr, 0, (const float*)rdq, rows, (const float*)xs[NL],
-                       P.ref_ln_g, (const float*)nullptr, (float*)nullptr, rprod, rdx[c], Hd);
+    aoa_launch_ln_bwd_dense(nullptr, 0, rdq, rows, xs[NL], P.ref_ln_g, nullptr, nullptr, rprod, rdx[c], Hd, st);
     ICZ_TRY(launch_colsum(rprod, rows, Hd, Hd, G.ref_ln_g, st));
     ICZ_TRY(launch_colsum(rdq, rows, Hd, Hd, G.ref_ln_b, st));
     // ---- 3. the layers, last to first
-    const size_t lds_b = sizeof(float) * mha_self_bwd_lds_floats(R, Hd / NH);
     for (int l = NL - 1; l >= 0; --l) {
         const icz_aoa_block& b = P.layer[l];
         const icz_aoa_block& gb = G.layer[l];
@@ -109,7 +118,7 @@ int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
         const DropP d_aoa = dropp(train, rng.ref_aoa_mask, (size_t)l * B * R * 2 * Hd, AOA_RNG_REF_AOA, l, 0.3f);
         const DropP d_sc = dropp(train, rng.ref_sc_mask, (size_t)l * B * R * Hd, AOA_RNG_REF_SC, l, 0.1f);
         // forward of layer l from its stored input (Aoa::refine's launches)
-        hipLaunchKernelGGL(layer_norm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, (const float*)xs[l], b.ln_g, b.ln_b, ln, rows, Hd, (float*)nullptr);
+        aoa_launch_layer_norm(0, xs[l], b.ln_g, b.ln_b, ln, rows, Hd, nullptr, nullptr, st);
         ICZ_TRY(lin(ln, rows, Hd, w_qkv[l], b_qkv[l], 3 * Hd, qkv, st));
         mha_self_layer(B, l, train, st);
         const float *xo = o, *xn = ln;
@@ -128,7 +137,7 @@ int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
         ICZ_TRY(rnn(rdz, 2 * Hd, rows, 2 * Hd, b.aoa_w, 2 * Hd, 2 * Hd, rslab, rslab_floats, &ns, st));
         hipLaunchKernelGGL(drop_concat_bwd_kernel, dim3(eb), dim3(256), 0, st, (const float*)rslab, ns, rdo, rdln, (size_t)rows, Hd, rr, d_aoa);
         // self-attention
-        hipLaunchKernelGGL(mha_self_bwd_kernel, dim3(B, NH), dim3(256), lds_b, st, (const float*)qkv, (const float*)rdo, rdqkv, R, Hd, NH, rr, d_att);
+        aoa_launch_mha_self_bwd(qkv, rdo, rdqkv, B, R, Hd, NH, rr, d_att, st);
         // fused Q/K/V projection: the three weight gradients go to the separate reference tensors
         float* const gw[3] = {gb.q_w, gb.k_w, gb.v_w};
         float* const gbias[3] = {gb.q_b, gb.k_b, gb.v_b};
@@ -138,8 +147,7 @@ int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
         }
         ICZ_TRY(rnn(rdqkv, 3 * Hd, rows, 3 * Hd, w_qkv[l], Hd, Hd, rslab, rslab_floats, &ns, st));
         // LayerNorm (its output fed the projection and the [o | ln] concatenation) + the residual
-        hipLaunchKernelGGL(aoa_ln_bwd_dense_kernel, dim3(rows), dim3(256), 0, st, (const float*)rslab, ns, (const float*)rdln, rows, (const float*)xs[l],
-                           b.ln_g, (const float*)rdx[c], rdq, rprod, rdx[c ^ 1], Hd);
+        aoa_launch_ln_bwd_dense(rslab, ns, rdln, rows, xs[l], b.ln_g, rdx[c], rdq, rprod, rdx[c ^ 1], Hd, st);
         ICZ_TRY(launch_colsum(rprod, rows, Hd, Hd, gb.ln_g, st));
         ICZ_TRY(launch_colsum(rdq, rows, Hd, Hd, gb.ln_b, st));
         c ^= 1;
@@ -153,3 +161,30 @@ int Aoa::refiner_backward(const icz_aoa_params& G, hipStream_t st) {
 }
 
 }  // namespace icz
+
+// ================================================================================================
+using namespace icz;
+extern "C" {
+
+// Test entry of mha_self_bwd_kernel (include/icz.h): host checks (the library's refusal above the LDS budget), the handle's opt-in and launch.
+int icz_test_aoa_self_attn_bwd(const float* qkv, const float* dO, float* dqkv, int32_t n_img, int32_t R, int32_t Hd, int32_t NH, const int32_t* counts,
+                               const icz_test_dropp* dropp, void* stream) {
+    const char* who = "icz_test_aoa_self_attn_bwd";
+    ICZ_REQUIRE(qkv && dO && dqkv && n_img >= 1, "%s: null argument or no image", who);
+    ICZ_TRY(aoa_test_heads(who, R, Hd, NH));
+    ICZ_REQUIRE(aoa_al16(qkv) && aoa_al16(dO), "%s: qkv and dO must be 16-byte aligned", who);
+    const size_t lds = aoa_self_bwd_lds(R, Hd / NH);
+    ICZ_REQUIRE(lds <= AOA_LDS_BUDGET, "aoa: train_refiner: the self-attention backward needs %zu bytes of LDS for %d regions and heads of %d "
+                "columns (limit %zu)", lds, R, Hd / NH, AOA_LDS_BUDGET);
+    DropP dp;
+    ICZ_TRY(aoa_test_dropp(who, dropp, &dp));
+    ICZ_TRY(aoa_self_attn_bwd_optin(lds));
+    AoaTestRegions reg;
+    RegionRows rr;
+    ICZ_TRY(reg.build(who, counts, n_img, R, (hipStream_t)stream, &rr));
+    aoa_launch_mha_self_bwd(qkv, dO, dqkv, n_img, R, Hd, NH, rr, dp, (hipStream_t)stream);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+}  // extern "C"

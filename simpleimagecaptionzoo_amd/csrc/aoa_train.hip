@@ -6,6 +6,7 @@
 // one TN GEMM over all (t, b) rows after the loop.  The gradients of the hoisted linear_K / linear_V outputs are
 // accumulated per image over time by the one workgroup that owns the (image, head) slice (no atomics, fixed order).
 #include "aoa_impl.h"
+#include "aoa_test_support.h"
 #include "butd_kernels.h"
 #include "ens_sample.h"
 #include "lstm_kernels.h"
@@ -233,12 +234,7 @@ int Aoa::ensure_train(int Bq, int Tq, int Iq) {
     }
     DeviceBuffers::TrainingScope scope(mem);
     const size_t B = Bq, T = Tq, I = Iq, Hd = dims.Hd, E = dims.E, R = dims.R, NH = dims.NH;
-    {
-        const size_t dh = Hd / NH, lds_bwd = sizeof(float) * (2 * R * (dh + 1) + 2 * dh + 128 + 4);
-        if (lds_bwd > 48 * 1024)
-            ICZ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(aoa_dec_attn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              (int)lds_bwd));
-    }
+    ICZ_TRY(aoa_dec_attn_bwd_optin(aoa_dec_attn_bwd_lds((int)R, (int)(Hd / NH))));
     const size_t TB = T * B;
     ICZ_TRY(alloc((void**)&tok, sizeof(int64_t) * (TB + B)));
     float** st1[] = {&th, &tm, &tctx};
@@ -612,7 +608,7 @@ int Aoa::bptt_predict(BpttCall& c) {
 
 // ---- the reverse-time loop
 int Aoa::bptt_loop(BpttCall& c) {
-    const int B = c.B, T = c.T, TB = c.TB, Hd = dims.Hd, NH = dims.NH, R = cur_R, dh = Hd / NH;
+    const int B = c.B, T = c.T, TB = c.TB, Hd = dims.Hd, NH = dims.NH, R = cur_R;
     const bool eo = c.eo;
     const int32_t* const rows_img = c.K > 1 ? imgk : nullptr;
     hipStream_t const st = c.st;
@@ -624,7 +620,6 @@ int Aoa::bptt_loop(BpttCall& c) {
         ICZ_CHECK_HIP(hipMemsetAsync(tdS, 0, sizeof(float) * (size_t)TB * NH * R, st));
         ICZ_CHECK_HIP(hipMemsetAsync(tdX, 0, sizeof(float) * (size_t)TB * Hd, st));
     }
-    const size_t lds = sizeof(float) * (2 * R * (dh + 1) + 2 * dh + 128 + 4);
     DropCfg off = {0, nullptr, nullptr, 0, 0};
     int cur = 0, nsx = 1, bnext = 0;
     for (int t = T - 1; t >= 0; --t) {
@@ -639,11 +634,10 @@ int Aoa::bptt_loop(BpttCall& c) {
                            io_next.d_ctx, tz + s0 * 2 * Hd, dZ + s0 * 2 * Hd, bt, Hd, live, carry_live);
         int ns2 = 1, nsq = 1;
         ICZ_TRY(nn(dZ + s0 * 2 * Hd, 2 * Hd, bt, 2 * Hd, P.dec.aoa_w, 2 * Hd, 2 * Hd, X2, xfloats, &ns2, split_backward(STEP_WGS), st, live));
-        hipLaunchKernelGGL(aoa_dec_attn_bwd_kernel, dim3(bt, NH), dim3(256), lds, st, X2, ns2, bt, tP + s0 * NH * R, tPd + s0 * NH * R,
-                           tQp + s0 * Hd, Kd, Vd, dQp + s0 * Hd, tdS + s0 * NH * R, tdX + s0 * Hd, R, Hd, NH, region_rows(), io.d_att.mode ? io.d_att.scale : 1.0f, live, rows_img);
+        aoa_launch_dec_attn_bwd(X2, ns2, bt, tP + s0 * NH * R, tPd + s0 * NH * R, tQp + s0 * Hd, Kd, Vd, dQp + s0 * Hd, tdS + s0 * NH * R, tdX + s0 * Hd, R,
+                                Hd, NH, region_rows(), io.d_att.mode ? io.d_att.scale : 1.0f, live, rows_img, st);
         ICZ_TRY(nn(dQp + s0 * Hd, Hd, bt, Hd, P.dec.q_w, Hd, Hd, ws, ws_floats, &nsq, split_backward(STEP_WGS), st, live));
-        hipLaunchKernelGGL(aoa_ln_bwd_kernel, dim3(bt), dim3(256), 0, st, ws, nsq, X2, ns2, bt, th + (s0 + B) * Hd, tstats + s0 * 2,
-                           P.dec.ln_g, dQn + s0 * Hd, dHln, Hd, live);
+        aoa_launch_ln_bwd(ws, nsq, X2, ns2, bt, th + (s0 + B) * Hd, tstats + s0 * 2, P.dec.ln_g, dQn + s0 * Hd, dHln, Hd, live, st);
         LstmBwdArgs a = {};
         a.dh_a = bnext ? X + Hd : nullptr; a.ns_a = nsx; a.lda_a = 2 * Hd; a.rows_a = bnext;
         a.dh_b = dHln; a.ns_b = 1; a.lda_b = Hd; a.rows_b = bt;
@@ -699,11 +693,7 @@ int Aoa::bptt_attention_tail(BpttCall& c) {
     hipStream_t const ts = c.tail.st();
     ICZ_TRY(gemm_tn(dQp, Hd, Hd, tqn, Hd, Hd, TB, G.dec.q_w, Hd, 0, rl, ts));
     ICZ_TRY(launch_colsum(dQp, TB, Hd, Hd, G.dec.q_b, ts));
-    {
-        const int tc_fit = (int)(48 * 1024 / (sizeof(float) * 2 * (R + dh))), tc = K * T < tc_fit ? K * T : tc_fit;
-        hipLaunchKernelGGL(aoa_dkv_kernel, dim3(n_img, NH), dim3(256), sizeof(float) * (size_t)tc * 2 * (R + dh), ts, tdS, tPd, tQp, tdX, dKd, dVd, B, T,
-                           tc, R, Hd, NH, region_rows(), K);
-    }
+    aoa_launch_dkv(tdS, tPd, tQp, tdX, dKd, dVd, n_img, B, T, aoa_dkv_tc(K * T, R, dh), R, Hd, NH, region_rows(), K, ts);
     const int rrows = (int)region_row_count(n_img);      // region rows of the batch (packed valid rows with per-image counts)
     ICZ_TRY(gemm_tn(dKd, Hd, Hd, refined, Hd, Hd, rrows, G.dec.k_w, Hd, 0, nullptr, ts));
     ICZ_TRY(launch_colsum(dKd, rrows, Hd, Hd, G.dec.k_b, ts));
@@ -719,11 +709,109 @@ int Aoa::bptt_attention_tail(BpttCall& c) {
     return ICZ_OK;
 }
 
+void aoa_launch_ln_bwd(const float* dq_a, int ns_a, const float* dq_b, int ns_b, int rows, const float* x, const float* stats, const float* gain,
+                       float* dq_tot, float* dx, int n, const int* live, hipStream_t st) {
+    hipLaunchKernelGGL(aoa_ln_bwd_kernel, dim3(rows), dim3(256), 0, st, dq_a, ns_a, dq_b, ns_b, rows, x, stats, gain, dq_tot, dx, n, live);
+}
+
+// decoder attention backward of one step (the limit of its dynamic LDS: aoa_raise_lds_limit, aoa.hip)
+int aoa_dec_attn_bwd_optin(size_t lds) {
+    static size_t raised[AOA_LDS_LIMIT_DEVICES] = {};
+    return aoa_raise_lds_limit(reinterpret_cast<const void*>(aoa_dec_attn_bwd_kernel), lds, raised);
+}
+void aoa_launch_dec_attn_bwd(const float* dxq, int ns, int rows, const float* Pm, const float* Pdm, const float* Qp, const float* Kd, const float* Vd,
+                             float* dQp, float* dS_out, float* dx_out, int R, int Hd, int NH, const RegionRows& rr, float keep_scale, const int* live,
+                             const int32_t* img_of_row, hipStream_t st) {
+    hipLaunchKernelGGL(aoa_dec_attn_bwd_kernel, dim3(rows, NH), dim3(256), aoa_dec_attn_bwd_lds(R, Hd / NH), st, dxq, ns, rows, Pm, Pdm, Qp, Kd, Vd, dQp,
+                       dS_out, dx_out, R, Hd, NH, rr, keep_scale, live, img_of_row);
+}
+
+// d K / d V of the hoisted projections: the (k, t) pairs of an image go through LDS in chunks of tc pairs (aoa_dkv_tc: all of them when they
+// fit 48 KB)
+void aoa_launch_dkv(const float* dS_all, const float* Pd_all, const float* Qp_all, const float* dx_all, float* dKd, float* dVd, int n_img, int B, int T,
+                    int tc, int R, int Hd, int NH, const RegionRows& rr, int G, hipStream_t st) {
+    hipLaunchKernelGGL(aoa_dkv_kernel, dim3(n_img, NH), dim3(256), aoa_dkv_lds(tc, R, Hd / NH), st, dS_all, Pd_all, Qp_all, dx_all, dKd, dVd, B, T, tc,
+                       R, Hd, NH, rr, G);
+}
+
 }  // namespace icz
 
 // ================================================================================================
 using namespace icz;
 extern "C" {
+
+// Test entry of aoa_dec_attn_bwd_kernel (include/icz.h): host checks, the handle's opt-in and launch.
+int icz_test_aoa_dec_attn_bwd(const float* dxq, int32_t ns, int32_t rows, const float* P, const float* Pd, const float* Qp, const float* Kd,
+                              const float* Vd, float* dQp, float* dS_out, float* dx_out, int32_t n_img, int32_t R, int32_t Hd, int32_t NH,
+                              const int32_t* counts, float keep_scale, const int32_t* live, const int32_t* img_of_row, void* stream) {
+    const char* who = "icz_test_aoa_dec_attn_bwd";
+    ICZ_REQUIRE(dxq && P && Pd && Qp && Kd && Vd && dQp && dS_out && dx_out && rows >= 1 && n_img >= 1, "%s: null argument, no row or no image", who);
+    ICZ_TRY(aoa_test_heads(who, R, Hd, NH));
+    ICZ_REQUIRE(aoa_al16(Kd) && aoa_al16(Vd), "%s: Kd and Vd must be 16-byte aligned", who);
+    ICZ_REQUIRE(ns >= 1 && ns <= 16, "%s: %d slabs of the GLU-input gradient (1..16)", who, ns);
+    ICZ_REQUIRE(keep_scale >= 1.0f, "%s: keep_scale %g (1 without dropout, else 1 / (1 - p))", who, (double)keep_scale);
+    ICZ_REQUIRE(img_of_row || rows <= n_img, "%s: %d rows over %d images need img_of_row", who, rows, n_img);
+    const size_t lds = aoa_dec_attn_bwd_lds(R, Hd / NH);
+    ICZ_REQUIRE(lds <= AOA_LDS_BUDGET, "%s: K and V head tiles of %d regions x %d columns need %zu bytes of LDS (limit %zu)", who, R, Hd / NH, lds,
+                AOA_LDS_BUDGET);
+    if (img_of_row) {
+        std::vector<int32_t> ior;
+        ICZ_TRY(aoa_test_read_i32(img_of_row, rows, &ior));
+        for (int i = 0; i < rows; ++i) ICZ_REQUIRE(ior[i] >= 0 && ior[i] < n_img, "%s: row %d decodes image %d of %d", who, i, ior[i], n_img);
+    }
+    ICZ_TRY(aoa_dec_attn_bwd_optin(lds));
+    AoaTestRegions reg;
+    RegionRows rr;
+    ICZ_TRY(reg.build(who, counts, n_img, R, (hipStream_t)stream, &rr));
+    aoa_launch_dec_attn_bwd(dxq, ns, rows, P, Pd, Qp, Kd, Vd, dQp, dS_out, dx_out, R, Hd, NH, rr, keep_scale, live, img_of_row, (hipStream_t)stream);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+// Test entry of the two LayerNorm backward kernels (include/icz.h): form 0 aoa_ln_bwd_kernel, form 1 aoa_ln_bwd_dense_kernel.
+int icz_test_aoa_ln_bwd(int32_t form, const float* dq_a, int32_t ns_a, const float* dq_b, int32_t ns_b, int32_t rows, const float* x, const float* stats,
+                        const float* gain, const float* res, float* dq_tot, float* prod, float* dx, int32_t n, const int32_t* live, void* stream) {
+    const char* who = "icz_test_aoa_ln_bwd";
+    ICZ_REQUIRE(form == 0 || form == 1, "%s: form %d (0: aoa_ln_bwd_kernel, 1: aoa_ln_bwd_dense_kernel)", who, form);
+    ICZ_REQUIRE(x && gain && dx && rows >= 1, "%s: null argument or no row", who);
+    ICZ_REQUIRE(n >= 4 && n % 4 == 0 && n <= 4096, "%s: a row of %d columns (a multiple of 4, at most 4096: the row is kept in registers)", who, n);
+    ICZ_REQUIRE(aoa_al16(dq_a) && aoa_al16(dq_b) && aoa_al16(x) && aoa_al16(gain) && aoa_al16(res) && aoa_al16(dq_tot) && aoa_al16(prod) && aoa_al16(dx),
+                "%s: every tensor must be 16-byte aligned", who);
+    if (form == 0) {
+        ICZ_REQUIRE(dq_a && dq_b && stats && dq_tot && !res && !prod, "%s: form 0 takes dq_a, dq_b, stats and dq_tot, and neither res nor prod", who);
+        ICZ_REQUIRE(ns_a >= 1 && ns_a <= 16 && ns_b >= 1 && ns_b <= 16, "%s: form 0 with %d and %d slabs (1..16 each)", who, ns_a, ns_b);
+        aoa_launch_ln_bwd(dq_a, ns_a, dq_b, ns_b, rows, x, stats, gain, dq_tot, dx, n, live, (hipStream_t)stream);
+    } else {
+        ICZ_REQUIRE(prod && !stats && !live && ns_b == 0, "%s: form 1 takes prod, and neither stats nor live nor slabs of dq_b", who);
+        ICZ_REQUIRE(dq_a ? (ns_a >= 1 && ns_a <= 16) : ns_a == 0, "%s: form 1 with %d slabs of %s dq_a", who, ns_a, dq_a ? "a given" : "a null");
+        aoa_launch_ln_bwd_dense(dq_a, ns_a, dq_b, rows, x, gain, res, dq_tot, prod, dx, n, (hipStream_t)stream);
+    }
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+// Test entry of aoa_dkv_kernel (include/icz.h): host checks, the handle's chunk rule or a forced chunk, the handle's launch.
+int icz_test_aoa_dkv(const float* dS_all, const float* Pd_all, const float* Qp_all, const float* dx_all, float* dKd, float* dVd, int32_t n_img,
+                     int32_t B, int32_t T, int32_t tc, int32_t R, int32_t Hd, int32_t NH, const int32_t* counts, int32_t G, int32_t* tc_out,
+                     void* stream) {
+    const char* who = "icz_test_aoa_dkv";
+    ICZ_REQUIRE(dS_all && Pd_all && Qp_all && dx_all && dKd && dVd, "%s: null argument", who);
+    ICZ_TRY(aoa_test_heads(who, R, Hd, NH));
+    ICZ_REQUIRE(n_img >= 1 && G >= 1 && T >= 1, "%s: n_img=%d, G=%d, T=%d", who, n_img, G, T);
+    // the handle's decoder rows are the images' rows and nothing else (row img * G + k): any other row count is not the library's layout
+    ICZ_REQUIRE((int64_t)B == (int64_t)n_img * G, "%s: %d decoder rows per step are not %d images x %d rows", who, B, n_img, G);
+    const int d = Hd / NH, pairs = G * T;
+    const int chunk = tc ? tc : aoa_dkv_tc(pairs, R, d);
+    ICZ_REQUIRE(chunk >= 1 && chunk <= pairs && aoa_dkv_lds(chunk, R, d) <= 48 * 1024, "%s: a chunk of %d of the %d (k, t) pairs (0: the handle's rule, "
+                "else 1..%d; at most 48 KB of LDS: %zu bytes)", who, chunk, pairs, pairs, chunk > 0 ? aoa_dkv_lds(chunk, R, d) : (size_t)0);
+    if (tc_out) *tc_out = chunk;
+    AoaTestRegions reg;
+    RegionRows rr;
+    ICZ_TRY(reg.build(who, counts, n_img, R, (hipStream_t)stream, &rr));
+    aoa_launch_dkv(dS_all, Pd_all, Qp_all, dx_all, dKd, dVd, n_img, B, T, chunk, R, Hd, NH, rr, G, (hipStream_t)stream);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
 
 int icz_aoa_sample(icz_aoa_t* h, const float* feats, int32_t B, int32_t max_len, const icz_aoa_rng* rng, int64_t* seq_out,
                    float* logprobs_out, void* stream) {
