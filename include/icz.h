@@ -1195,6 +1195,74 @@ int icz_test_aoa_dec_attn_bwd(const float* dxq, int32_t ns, int32_t rows, const 
 int icz_test_aoa_dkv(const float* dS_all, const float* Pd_all, const float* Qp_all, const float* dx_all, float* dKd, float* dVd, int32_t n_img,
                      int32_t B, int32_t T, int32_t tc, int32_t R, int32_t Hd, int32_t NH, const int32_t* counts, int32_t G, int32_t* tc_out,
                      void* stream);
+/* Test entries for the kernels of an LSTM decoder step shared by BUTD, AoA and NIC (csrc/lstm_kernels.h), each on given operands
+ * (tests/test_gpu_lstm_kernels.py): the library's kernel with the grid the decoders launch it with.  All data pointers are DEVICE
+ * pointers (rows_t of icz_test_embed_steps is a HOST array).  Every entry checks its arguments on the host and returns ICZ_ERR_INVALID
+ * without launching otherwise; device index arrays (token ids, pre_row) are read back and checked too, for which the entry waits for
+ * the stream.
+ *
+ * Dropout (p = 0.5, kept values are doubled), the library's DropCfg: mode 0 off, 1 keep flags (uint8, nonzero = keep), 2 Philox (*seed a
+ * device uint64; stream and step as the decoders number them, csrc/rng.h).  The forward kernels take row r >= row0 as row r - row0 of
+ * the draw and leave rows < row0 undropped (the evaluation-mode rows of a merged chain); the backward and the all-steps embedding run over
+ * the sampled rows alone and refuse row0 != 0.  The embedding kernels read four keep flags at once: their mask must be 4-byte aligned.  A
+ * null icz_test_drop is mode 0. */
+typedef struct {
+    int32_t mode;
+    const uint8_t* mask;
+    const uint64_t* seed;
+    uint32_t stream, step;
+    int32_t row0;
+} icz_test_drop;
+/* embed_kernel: emb[row, :] = drop((relu ? max(table[it[row], :], 0) : table[it[row], :])), keep index (row - row0) E + e; table [V, E], it
+ * [rows] (each 0..V-1), emb [rows, E].  E a multiple of 4 (at least 4), table and emb 16-byte aligned, rows >= 1.  live (optional) device
+ * int32: 0 = the launch writes nothing. */
+int icz_test_embed(const float* table, int32_t V, int32_t E, const int64_t* it, int32_t rows, float* emb, int32_t relu, const icz_test_drop* drop,
+                   const int32_t* live, void* stream);
+/* embed_steps_kernel, every step of a teacher-forced pass in one launch: emb[t B + b, :] = drop_t(max(table[tok[t B + b], :], 0)) for
+ * b < rows_t[t], every other row left untouched; drop_t = Philox step t (the struct's step is not read) or the slice t of a mask [T, B, E],
+ * keep index b E + e.  T in 1..128, rows_t [T] in 0..B and never increasing with t; all T B tokens are checked, the unused ones too. */
+int icz_test_embed_steps(const float* table, int32_t V, int32_t E, const int64_t* tok, int32_t T, int32_t B, const int32_t* rows_t, float* emb,
+                         const icz_test_drop* drop, void* stream);
+/* The LSTMCell pointwise part behind the gate GEMMs (gate order i, f, g, o):
+ *   p[row, :] = slab[0][row, :] + ... + slab[ns - 1][row, :] + pre[pre_row[row], :] + b_ih + b_hh   (fp32, in that order)
+ *   c' = sig(p_f) c_prev + sig(p_i) tanh(p_g);  h' = sig(p_o) tanh(c')
+ * slab [ns][rows][4H] dense with ns in 1..32; pre (optional) [n_pre, 4H] with pre_row (optional) [rows] int32, each 0..n_pre-1 (null:
+ * row r reads pre row r, n_pre >= rows); gates_out (optional) [rows, 4H] the activated gates; hdrop_out (optional) [rows, H] = drop(h'),
+ * keep index (row - row0) H + j; live as above. */
+typedef struct {
+    const float* slab; int32_t ns;
+    const float* pre; int32_t n_pre; const int32_t* pre_row;
+    const float* b_ih; const float* b_hh;
+    const float* c_prev; float* h_out; float* c_out;
+    float* gates_out; float* hdrop_out;
+    int32_t rows, H;
+    const int32_t* live;
+} icz_test_lstm_point_args;
+/* route 0 = what launch_lstm_point takes (the gate-per-wave kernel wherever H % 4 == 0), 1 = lstm_point_kernel (any H), 2 =
+ * lstm_point_gw_kernel, refused unless H % 4 == 0 with 16-byte aligned slab, pre and biases (route 0 needs the same where it takes
+ * that kernel).  Both kernels add the same numbers in the same order: the same bits.  *route_out (optional, host): the kernel taken. */
+int icz_test_lstm_point(int32_t route, const icz_test_lstm_point_args* a, const icz_test_drop* drop, int32_t* route_out, void* stream);
+/* lstm_bwd_point_kernel with every field of its arguments:
+ *   dh = set a (if *carry_live != 0) + set b + set c + drop(dhdrop), each set summed in slab order first; set x = ns_x slabs of rows_x
+ *        rows of lda_x floats (lda_x >= H; columns 0..H of each row: pass the pointer at the column offset), rows >= rows_x add nothing
+ *   dc = (dc_in [.., H] at rows < dc_in_rows, if *carry_live != 0) + dh o (1 - tanh^2 c_cur)
+ *   dgates [rows, 4H] = d(pre-activation i, f, g, o) from the activated gates [rows, 4H], c_prev [rows, H] (null: zeros) and c_cur;
+ *   dc_prev [rows, H] = dc f.
+ * Absent sets, dhdrop, dc_in: null pointers.  drop(dhdrop): doubled where kept, else 0, keep index row H + j.  live / carry_live:
+ * optional device int32; *live == 0 writes zero dgates rows and nothing else.  Refused: lda_x < H, rows_x outside 1..rows, a set with
+ * a pointer but ns_x outside 1..32, dc_in_rows outside 1..rows, null gates / c_cur / dgates / dc_prev. */
+typedef struct {
+    const float* dh_a; int32_t ns_a, lda_a, rows_a;
+    const float* dh_b; int32_t ns_b, lda_b, rows_b;
+    const float* dh_c; int32_t ns_c, lda_c, rows_c;
+    const float* dhdrop;
+    const float* dc_in; int32_t dc_in_rows;
+    const float* gates; const float* c_prev; const float* c_cur;
+    float* dgates; float* dc_prev;
+    int32_t rows, H;
+    const int32_t* live; const int32_t* carry_live;
+} icz_test_lstm_bwd_args;
+int icz_test_lstm_bwd_point(const icz_test_lstm_bwd_args* a, const icz_test_drop* drop, void* stream);
 /* Live timing of the dominant kernel (the forward GEMMs of a decoder step at 33..64 rows: gemm_resident_x3_kernel, or
  * gemm_nt_kernel<4, ...> with ICZ_GEMM_RESIDENT_X3=0; see icz_prof_select) with HIP events on its launch stream, for bench.py's
  * roofline line.  Between begin and end every launch is bracketed by an event

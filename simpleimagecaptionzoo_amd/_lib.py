@@ -146,6 +146,32 @@ class DropPArgs(C.Structure):      # icz_test_dropp
                 ("p", C.c_float), ("idx0", C.c_uint64)]
 
 
+class DropArgs(C.Structure):       # icz_test_drop
+    _fields_ = [("mode", C.c_int32), ("mask", C.c_void_p), ("seed", C.c_void_p), ("stream", C.c_uint32), ("step", C.c_uint32),
+                ("row0", C.c_int32)]
+
+
+LSTM_POINT_POINTERS = ("slab", "pre", "pre_row", "b_ih", "b_hh", "c_prev", "h_out", "c_out", "gates_out", "hdrop_out", "live")
+
+
+class LstmPointArgs(C.Structure):  # icz_test_lstm_point_args
+    _fields_ = [("slab", C.c_void_p), ("ns", C.c_int32), ("pre", C.c_void_p), ("n_pre", C.c_int32), ("pre_row", C.c_void_p),
+                ("b_ih", C.c_void_p), ("b_hh", C.c_void_p), ("c_prev", C.c_void_p), ("h_out", C.c_void_p), ("c_out", C.c_void_p),
+                ("gates_out", C.c_void_p), ("hdrop_out", C.c_void_p), ("rows", C.c_int32), ("H", C.c_int32), ("live", C.c_void_p)]
+
+
+LSTM_BWD_POINTERS = ("dh_a", "dh_b", "dh_c", "dhdrop", "dc_in", "gates", "c_prev", "c_cur", "dgates", "dc_prev", "live", "carry_live")
+
+
+class LstmBwdArgs(C.Structure):    # icz_test_lstm_bwd_args
+    _fields_ = [("dh_a", C.c_void_p), ("ns_a", C.c_int32), ("lda_a", C.c_int32), ("rows_a", C.c_int32),
+                ("dh_b", C.c_void_p), ("ns_b", C.c_int32), ("lda_b", C.c_int32), ("rows_b", C.c_int32),
+                ("dh_c", C.c_void_p), ("ns_c", C.c_int32), ("lda_c", C.c_int32), ("rows_c", C.c_int32),
+                ("dhdrop", C.c_void_p), ("dc_in", C.c_void_p), ("dc_in_rows", C.c_int32), ("gates", C.c_void_p), ("c_prev", C.c_void_p),
+                ("c_cur", C.c_void_p), ("dgates", C.c_void_p), ("dc_prev", C.c_void_p), ("rows", C.c_int32), ("H", C.c_int32),
+                ("live", C.c_void_p), ("carry_live", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -332,6 +358,10 @@ def lib():
         "icz_test_aoa_self_attn_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, C.POINTER(DropPArgs), vp]),
         "icz_test_aoa_dkv": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(i32), vp]),
         "icz_test_aoa_dec_attn": (C.c_int, [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, C.POINTER(DropPArgs), vp, vp]),
+        "icz_test_embed": (C.c_int, [vp, i32, i32, vp, i32, vp, i32, C.POINTER(DropArgs), vp, vp]),
+        "icz_test_embed_steps": (C.c_int, [vp, i32, i32, vp, i32, i32, C.POINTER(i32), vp, C.POINTER(DropArgs), vp]),
+        "icz_test_lstm_point": (C.c_int, [i32, C.POINTER(LstmPointArgs), C.POINTER(DropArgs), C.POINTER(i32), vp]),
+        "icz_test_lstm_bwd_point": (C.c_int, [C.POINTER(LstmBwdArgs), C.POINTER(DropArgs), vp]),
     }
     for name, (res, args) in sig.items():
         try:

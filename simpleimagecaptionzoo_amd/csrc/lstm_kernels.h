@@ -113,7 +113,9 @@ __global__ __launch_bounds__(256) void lstm_point_kernel(LstmPointArgs a, DropCf
 // resident-activation gate GEMM (gemm_resident_x3.hip) leaves 12 - 16 split-K slabs (16.8 MB at 64 rows): the one-unit kernel
 // above then issues 64 four-byte wave loads per thread (8.3 us), a four-units-per-thread form with one wave per workgroup
 // has ONE wave per compute unit waiting on 64 KB (9.5 us in the SCST trace); here four waves per compute unit wait on 16 KB
-// each (5.1 us).  Same summation order per element (slabs ascending, pre, b_ih, b_hh): bit-identical to the kernel above.
+// each (5.1 us).  Same summation order per element (slabs ascending, pre, b_ih, b_hh): bit-identical to the kernel above, which
+// tests/test_gpu_lstm_kernels.py::test_lstm_point_kernels_agree_bit_for_bit_and_are_near_float64 asserts in every output, for every
+// combination of the three slab loops below (through icz_test_lstm_point, routes 1 and 2).
 __global__ __launch_bounds__(256) void lstm_point_gw_kernel(LstmPointArgs a, DropCfg dc) {
     __shared__ __attribute__((aligned(16))) float sg[4][256];
     const int row = blockIdx.y, tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
