@@ -645,6 +645,99 @@ int icz_ensemble_score_tokens(int32_t M, const float* const* logits, const float
                               float* logp_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Sampling without replacement: stochastic beam search (beyond the reference; Kool, van Hoof and Welling, "Stochastic Beams and
+ * Where to Find Them", ICML 2019).  n = 1..8 DISTINCT captions per image that are exactly a sample without replacement from the
+ * model's (tempered) sequence distribution, for the cost of one beam search of width n, with the perturbed values the unbiased
+ * without-replacement estimators need (Kool et al., ICLR 2020).  EVALUATION mode; csrc/stochastic_beam.hip, csrc/sbs_kernels.h.
+ * Per image there are n slots; decoder row img * n + slot holds a hypothesis: its tokens, phi (the fp32 running sum of its token
+ * log-probs in step order, as the beam search's running score), G (its perturbed value, float64) and a frozen flag, set once it
+ * has emitted <end> (2).  The occupied slots are kept sorted by G descending after every step: slot 0 is the best.
+ *   1. Root: phi = 0, G_root = gumbel(u_root[img]) with gumbel(u) = -log(-log(u)); only slot 0 is occupied.  Step 1 runs one decoder
+ *      row per image where every member allows it (the beam search's compact step).
+ *   2. Row scoring, for a live (occupied, not frozen) row at step s = 1, 2, ... with finished logits x (split-K slabs summed in
+ *      slab order + bias):  lp[v] = x[v] / T - lse(x / T);  phi_c[v] = phi + lp[v] (fp32);  g[v] = phi_c[v] + gumbel(u[s, img, slot, v])
+ *      (fp32).  The row emits its min(n, V) largest g with phi_c and v, ties to the lower v; Z = the row maximum of g.  A token whose
+ *      g is -inf is never emitted: a row may emit fewer than n.
+ *   3. Conditioning on the parent, in float64 with Tp = the parent's G:  w = Tp - g + log1mexp(g - Z);
+ *      G~ = Tp - max(0, w) - log1p(exp(-|w|)) -- the stable form of -log(exp(-Tp) - exp(-Z) + exp(-g)); the row's argmax gets exactly
+ *      Tp.  The map is monotone in g, so only the emitted candidates are ever transformed.  A frozen row emits one candidate: itself,
+ *      with G, phi and tokens unchanged and next input <pad>; its logits are never read.
+ *   4. Merge, per image: of the <= n n candidates the n largest G~ become the new slots 0 .. n-1 in that order, ties to the lower
+ *      (parent slot, v) (a frozen parent counts as v = 0).  A candidate whose token is <end> is frozen on entry.  The step also counts
+ *      the occupied slots per image and, over all images, the rows that are occupied and not frozen: every third step from step 6
+ *      on one 4-byte read-back ends the search once that count is 0 (the result is that of all max_len steps).
+ *   5. After max_len steps the outputs per image are in slot order, G descending (icz_sample_distinct_out): ids [n_img n, max_len]
+ *      int64 in the format icz_*_sample_decode writes (no <sta>, <end> included, 0 behind it), lens, finished (0 for a hypothesis cut
+ *      at max_len), phi fp32 and g float64.  An unoccupied slot (an image with fewer than n sequences: only at toy vocabularies)
+ *      writes length 0, finished 0, phi = g = -inf and zeros.  <pad> (0) is a token like any other and may be sampled inside a
+ *      caption: in ids it cannot be told from the padding, only lens says where the caption ends.  icz_*_score_captions and the
+ *      Engine's caption strings end a caption at its first 0, so such a hypothesis is scored and printed up to there only -- its phi is
+ *      the whole sequence's -- and two distinct hypotheses may print as one string.  A trained model gives <pad> no mass to speak of.
+ *   6. Noise: uniforms == NULL: Philox4x32-10 with counter {v >> 2, img * 8 + slot, step, 8} (stream tag 8, no other stream changes),
+ *      key = seed, word v & 3, and u = ((r >> 9) + 0.5) * 2^-23, exact in fp32 and strictly inside (0, 1); the root uses step 0, slot 0,
+ *      v = 0.  `img` in the counter is first_image + the image's index in the call (first_image >= 0, first_image + n_img <= 2^28): a batch
+ *      decoded in chunks with first_image = the chunk's offset draws the noise of the whole batch.  The slot stride is the constant 8, not n: since slots are sorted, the first j hypotheses of a run are the run with
+ *      n = j on the same seed.  Explicit noise (tests): uniforms [max_len, n_img, n, V] fp32 and root_uniforms [n_img], every value
+ *      strictly inside (0, 1); both or neither.
+ *   7. Temperature T > 0, finite, is the only option: phi is the log-probability under the tempered distribution, the one sampled
+ *      from.  Top-k, nucleus, n-gram blocking and length penalties would change what "without replacement from the model" means.
+ * Reduction orders are fixed and no float is accumulated atomically: one seed gives the same bits run to run.  An ensemble samples
+ * from x = lp of icz_ensemble_logprob (the combined rows); an ensemble of one member runs that member's own search, bit for bit.
+ * Argument errors return ICZ_ERR_INVALID before any device work, in this order: (1) n outside 1..8 or above V, (2) a temperature
+ * that is not finite or not positive, (3) max_len outside 1..256, (4) null arguments, exactly one of uniforms / root_uniforms
+ * included, (5) a null handle, (6) n_img <= 0 or n_img n above the (smallest member's) row capacity, or first_image out of range, (7) unrefreshed weights (an
+ * ensemble: null features of a member, a member not refreshed or short of rows).
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int64_t* ids;        /* [n_img n, max_len] */
+    int32_t* lens;       /* [n_img n] */
+    int32_t* finished;   /* [n_img n] */
+    float* phi;          /* [n_img n] */
+    double* g;           /* [n_img n] */
+} icz_sample_distinct_out;
+/* rules 1 - 3 and 6 above on the host alone (no handle, no device): V and max_rows are the handle's */
+int icz_sample_distinct_check(int32_t n_img, int32_t n, int32_t max_len, float temperature, int32_t V, int32_t max_rows);
+int icz_butd_sample_distinct(icz_butd_t* h, const float* feats, int32_t n_img, int32_t n, int32_t max_len, float temperature, uint64_t seed,
+                             int32_t first_image, const float* uniforms, const float* root_uniforms, const icz_sample_distinct_out* out,
+                             void* stream);
+int icz_aoa_sample_distinct(icz_aoa_t* h, const float* feats, int32_t n_img, int32_t n, int32_t max_len, float temperature, uint64_t seed,
+                            int32_t first_image, const float* uniforms, const float* root_uniforms, const icz_sample_distinct_out* out,
+                            void* stream);
+int icz_nic_sample_distinct(icz_nic_t* h, const float* features, int32_t n_img, int32_t n, int32_t max_len, float temperature, uint64_t seed,
+                            int32_t first_image, const float* uniforms, const float* root_uniforms, const icz_sample_distinct_out* out,
+                            void* stream);
+/* feats: HOST array of M device pointers */
+int icz_ensemble_sample_distinct(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t n, int32_t max_len, float temperature,
+                                 uint64_t seed, int32_t first_image, const float* uniforms, const float* root_uniforms,
+                                 const icz_sample_distinct_out* out, void* stream);
+/* The kernels alone (tests), launched with the grids of the search.  Rows: img * n + slot.  logits: finished rows [R][ld] (nsplit 1) or
+ * nsplit split-K slabs [nsplit][R][ld] + bias, R = n_img n, or n_img when compact (step 1 only).  occ [n_img], frozen [rows] uint8, phi
+ * [rows]; uniforms [n_img, n, V] of this step or NULL (Philox: seed, step); cand_g / cand_phi / cand_idx [rows, 8]: the first n entries
+ * of every scored row are written (an empty entry: idx -1, g = phi = -inf), nothing else. */
+int icz_test_sbs_rowtopk(const float* logits, const float* bias, int32_t nsplit, int32_t ld, int32_t n_img, int32_t n, int32_t V, int32_t step,
+                         int32_t compact, float temperature, const int32_t* occ, const uint8_t* frozen, const float* phi,
+                         const float* uniforms, uint64_t seed, int32_t first_image, float* cand_g, float* cand_phi, int32_t* cand_idx,
+                         void* stream);
+/* The state one step reads and writes: the row kernel, then the merge.  occ, frozen, phi, G [rows] float64 and len [rows] are
+ * rewritten in place; seqs_in / seqs_out [rows, L] (tokens without <sta>); src_row [rows], it_next [rows] int64; n_live [1] is
+ * incremented by the rows occupied and not frozen after the step. */
+typedef struct {
+    const float* logits; const float* bias; const float* uniforms;
+    int32_t* occ; uint8_t* frozen; float* phi; double* G; int32_t* len;
+    const int32_t* seqs_in; int32_t* seqs_out; int32_t* src_row; int64_t* it_next; int32_t* n_live;
+    float* cand_g; float* cand_phi; int32_t* cand_idx;
+} icz_sbs_step_state;
+int icz_test_sbs_step(const icz_sbs_step_state* s, int32_t nsplit, int32_t ld, int32_t n_img, int32_t n, int32_t V, int32_t step, int32_t L,
+                      int32_t compact, float temperature, uint64_t seed, int32_t first_image, void* stream);
+/* the start state (rule 1) of n_img images: root_uniforms [n_img] or NULL (Philox); it [rows] int64, img_of_row / src_row [rows] */
+int icz_test_sbs_init(int32_t n_img, int32_t n, const float* root_uniforms, uint64_t seed, int32_t first_image, int32_t* occ, uint8_t* frozen,
+                      float* phi, double* G,
+                      int32_t* len, int64_t* it, int32_t* img_of_row, int32_t* src_row, void* stream);
+/* the outputs (rule 5) of a given state; seqs [rows, L] */
+int icz_test_sbs_finalize(int32_t n_img, int32_t n, int32_t L, const int32_t* occ, const uint8_t* frozen, const float* phi, const double* G,
+                          const int32_t* len, const int32_t* seqs, const icz_sample_distinct_out* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Word-level knowledge distillation (beyond the reference): the XE training step of one student decoder on the word distribution of
  * an ensemble of M = 1..4 teachers of the same vocabulary (csrc/distill.hip).  For a token row with student logits s, teacher logits
  * z_1..z_M, normalised weights w, target c, label smoothing sigma, mixing weight alpha in [0, 1] and temperature tau in [0.25, 8]:

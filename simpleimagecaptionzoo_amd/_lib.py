@@ -136,6 +136,18 @@ class SampleOpts(C.Structure):     # icz_sample_opts
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float)]
 
 
+class SampleDistinctOut(C.Structure):  # icz_sample_distinct_out
+    _fields_ = [(n, C.c_void_p) for n in ("ids", "lens", "finished", "phi", "g")]
+
+
+SBS_STEP_FIELDS = ("logits", "bias", "uniforms", "occ", "frozen", "phi", "G", "len", "seqs_in", "seqs_out", "src_row", "it_next", "n_live",
+                   "cand_g", "cand_phi", "cand_idx")
+
+
+class SbsStepState(C.Structure):   # icz_sbs_step_state
+    _fields_ = [(n, C.c_void_p) for n in SBS_STEP_FIELDS]
+
+
 class DistillOpts(C.Structure):    # icz_distill_opts
     _fields_ = [("M", C.c_int32), ("teacher", C.POINTER(C.c_void_p)), ("ld", C.POINTER(C.c_int32)), ("weights", C.POINTER(C.c_float)),
                 ("alpha", C.c_float), ("temperature", C.c_float), ("smoothing", C.c_float)]
@@ -269,6 +281,15 @@ def lib():
         "icz_aoa_sample_decode": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
         "icz_nic_sample_decode": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(SampleOpts), C.c_uint64, vp, vp, vp, vp, vp]),
         "icz_sample_filter_draw": (C.c_int, [vp, vp, i32, i32, i32, i32, C.POINTER(SampleOpts), vp, vp, vp, vp, vp]),
+        "icz_sample_distinct_check": (C.c_int, [i32, i32, i32, f32, i32, i32]),
+        "icz_butd_sample_distinct": (C.c_int, [vp, vp, i32, i32, i32, f32, C.c_uint64, i32, vp, vp, C.POINTER(SampleDistinctOut), vp]),
+        "icz_aoa_sample_distinct": (C.c_int, [vp, vp, i32, i32, i32, f32, C.c_uint64, i32, vp, vp, C.POINTER(SampleDistinctOut), vp]),
+        "icz_nic_sample_distinct": (C.c_int, [vp, vp, i32, i32, i32, f32, C.c_uint64, i32, vp, vp, C.POINTER(SampleDistinctOut), vp]),
+        "icz_ensemble_sample_distinct": (C.c_int, [vp, C.POINTER(vp), i32, i32, i32, f32, C.c_uint64, i32, vp, vp, C.POINTER(SampleDistinctOut), vp]),
+        "icz_test_sbs_rowtopk": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, C.c_uint64, i32, vp, vp, vp, vp]),
+        "icz_test_sbs_step": (C.c_int, [C.POINTER(SbsStepState), i32, i32, i32, i32, i32, i32, i32, i32, f32, C.c_uint64, i32, vp]),
+        "icz_test_sbs_init": (C.c_int, [i32, i32, vp, C.c_uint64, i32] + [vp] * 9),
+        "icz_test_sbs_finalize": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(SampleDistinctOut), vp]),
         "icz_score_captions_check": (C.c_int, [i32, i32, i32, i32]),
         "icz_butd_score_captions": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "icz_aoa_score_captions": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),

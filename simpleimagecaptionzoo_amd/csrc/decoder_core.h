@@ -258,6 +258,7 @@ struct DecodeMember;
 constexpr int ENS_MAX_M = 4;          // members of one beam search / ensemble
 
 struct BeamBuf;
+struct SbsBuf;
 // An ensemble's side of a beam search (ensemble.hip): its own beam buffers, allocated from `mem` for `cap` rows, and its route to the
 // rows the search scores: run(lv, rows) combines the members' views of one step into lp [rows, ld].  A single handle has none: the
 // search runs on the member's own bm / buffers() / row_capacity() and reads its finished rows.
@@ -266,6 +267,7 @@ struct BeamCombine {
     BeamBuf* bm; DeviceBuffers* mem; int cap;
     const float* lp; int ld;
     std::function<void(const LogitsView* lv, int rows)> run;
+    SbsBuf* sbs = nullptr;            // its stochastic-beam buffers (sample_distinct); the beam searches leave it unset
 };
 
 // Beam-search buffers and the step loop shared by the decoders (beam.hip).
@@ -316,6 +318,24 @@ struct BeamBuf {
                const icz_beam_constraints* cons = nullptr, int32_t* sat_out = nullptr);
 };
 
+// Buffers of stochastic beam search (stochastic_beam.hip, sbs_kernels.h): per row the hypothesis (tokens ping-pong, phi, G, frozen,
+// length), per image the occupied slots, the per-row candidates of one step and the per-step counts of live rows with their pinned
+// read-back word; sized once for the owner's row capacity and 256 steps.  Allocated from a handle's or an ensemble's DeviceBuffers, beside its beam buffers.
+struct SbsBuf {
+    int cap_rows = 0;
+    int *occ = nullptr, *len = nullptr, *n_live = nullptr, *n_live_host = nullptr;
+    uint8_t* frozen = nullptr; float* phi = nullptr; double* G = nullptr;
+    int32_t* seqs[2] = {nullptr, nullptr};
+    int32_t *src_row = nullptr, *img_of_row = nullptr;
+    int64_t* it = nullptr;
+    float *cand_g = nullptr, *cand_phi = nullptr; int* cand_idx = nullptr;
+    SbsBuf() = default;
+    SbsBuf(const SbsBuf&) = delete;
+    SbsBuf& operator=(const SbsBuf&) = delete;
+    ~SbsBuf() { if (n_live_host) (void)hipHostFree(n_live_host); }
+    int ensure(DeviceBuffers& m, int max_rows);
+};
+
 // The per-image work, one decoder step and the beam-state gather of a decoder: the BUTD, AoA and NIC handles implement it, the
 // drivers below run on it -- beam_search on one member (a handle's own search) or on several at once (the model ensemble, ensemble.hip).
 // State: a step reads slot `cur` of the recurrent state and writes slot cur ^ 1; gather() moves slot 1 into slot 0 by source row.
@@ -343,6 +363,7 @@ struct DecodeMember {
     const int* seam_live = nullptr;
     struct SampleBuf { int cap_rows = 0, cap_T = 0; int64_t* it = nullptr; uint8_t* fin = nullptr; int* n_unf = nullptr; int32_t* img_of_row = nullptr; } sb;
     BeamBuf bm;                                 // a handle's own beam search (beam_search with no BeamCombine); an ensemble keeps its own
+    SbsBuf sbs;                                 // a handle's own stochastic beam search (sample_distinct), likewise
 };
 // an ensemble call of `rows` decoder rows: features, refreshed weights and row capacity of every member (`who` names the entry)
 int check_members(const char* who, DecodeMember* const* m, int M, const float* const* feats, int rows);
@@ -369,6 +390,17 @@ void launch_greedy_select(const LogitsView& lv, const DecodeMember::EmbSlot& e, 
 // member's step + sample_decode_kernel (include/icz.h: icz_*_sample_decode; `who` names the entry in its errors).
 int sample_decode(DecodeMember* m, const char* who, const float* feats, int n_img, int n, int max_len, const icz_sample_opts* opts,
                   uint64_t seed, const float* uniforms, int64_t* ids_out, float* logp_out, float* score_out, hipStream_t st);
+// Stochastic beam search over M >= 1 members (stochastic_beam.hip; include/icz.h: icz_*_sample_distinct): n distinct captions per
+// image, a sample without replacement from the (tempered) sequence distribution.  On the seams of beam_search: every check, then
+// SbsBuf::ensure, the start state, every member's prologue, and per step every member's step, the ensemble's run (ens non-null: the
+// combined rows; null: M = 1, the member's own logits, split-K slabs included), sbs_rowtopk_kernel, sbs_merge_kernel and every
+// member's gather.  `who` names the entry in the errors.  The argument rules that need no handle: sample_distinct_check.
+// first_image: the index of this call's image 0 within its batch, added to the image index of the Philox counter, so that a batch
+// decoded in chunks draws the noise of the whole batch (explicit uniforms ignore it).
+int sample_distinct_check(const char* who, int n_img, int n, int max_len, float temperature, int V, int max_rows, int first_image);
+int sample_distinct(const char* who, DecodeMember* const* m, int M, const BeamCombine* ens, const float* const* feats, int n_img, int n,
+                    int max_len, float temperature, uint64_t seed, int first_image, const float* uniforms, const float* root_uniforms,
+                    const icz_sample_distinct_out* out, hipStream_t st);
 // Scoring given captions on a member (score_captions.hip; include/icz.h: icz_*_score_captions): prologue once per image, then
 // max_len steps of the member's step on the fed tokens + score_tokens_kernel.
 int score_captions(DecodeMember* m, const char* who, const float* feats, int n_img, int n, int max_len, const int64_t* ids,

@@ -138,6 +138,7 @@ struct Ensemble {
     float logw[ENS_MAX_M] = {};
     DeviceBuffers mem;
     BeamBuf bm;
+    SbsBuf sbs;
     int64_t* it = nullptr;
     float* lp = nullptr;
     uint8_t* fin = nullptr;
@@ -359,6 +360,30 @@ int icz_ensemble_sample_decode(icz_ensemble_t* h, const float* const* feats, int
     ICZ_REQUIRE(feats && ids_out && logp_out && score_out, "%s: null argument", who);
     ICZ_REQUIRE(e, "%s: null handle", who);
     return e->sample_decode(who, feats, n_img, n, max_len, opts, seed, uniforms, ids_out, logp_out, score_out, (hipStream_t)stream);
+}
+
+int icz_ensemble_sample_distinct(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t n, int32_t max_len, float temperature,
+                                 uint64_t seed, int32_t first_image, const float* uniforms, const float* root_uniforms,
+                                 const icz_sample_distinct_out* out, void* stream) {
+    const char* who = "icz_ensemble_sample_distinct";
+    Ensemble* e = reinterpret_cast<Ensemble*>(h);
+    // the arguments first: no handle needed to report them (the vocabulary and the capacity are checked once there is one)
+    ICZ_TRY(sample_distinct_check(who, n_img, n, max_len, temperature, e ? e->V : -1, -1, 0));
+    ICZ_REQUIRE(feats && out && out->ids && out->lens && out->finished && out->phi && out->g && (uniforms == nullptr) == (root_uniforms == nullptr),
+                "%s: null argument (uniforms and root_uniforms: both or neither)", who);
+    ICZ_REQUIRE(e, "%s: null handle", who);
+    hipStream_t st = (hipStream_t)stream;
+    // One member: its weight normalises to 1, so the combined row is its own log-softmax.  The search runs on the member's own
+    // logits as the member's entry does -- the same launches, so the same bits -- and the combine kernel is not launched.
+    if (e->M == 1) {
+        ICZ_REQUIRE(feats[0], "%s: null features of member 0", who);
+        return sample_distinct(who, e->m, 1, nullptr, feats, n_img, n, max_len, temperature, seed, first_image, uniforms, root_uniforms, out, st);
+    }
+    BeamCombine ens = {who, &e->bm, &e->mem, e->cap, e->lp, e->Vp, [=](const LogitsView* lv, int rows) {
+                           launch_combine(e->args(lv), rows, e->lp, e->Vp, nullptr, nullptr, 0, 0, st);
+                       }};
+    ens.sbs = &e->sbs;
+    return sample_distinct(who, e->m, e->M, &ens, feats, n_img, n, max_len, temperature, seed, first_image, uniforms, root_uniforms, out, st);
 }
 
 int icz_ensemble_score_captions(icz_ensemble_t* h, const float* const* feats, int32_t n_img, int32_t n, int32_t max_len, const int64_t* ids,

@@ -7,7 +7,8 @@
 namespace icz {
 
 enum RngStream : uint32_t { RNG_EMB = 1, RNG_ATT = 2, RNG_OUT = 3, RNG_UNIFORM = 4, RNG_SS_GATE = 5, RNG_SS_DRAW = 6,
-                            RNG_DECODE = 7 };      // the draws of the evaluation-mode sampling decode (sample_decode.hip)
+                            RNG_DECODE = 7,        // the draws of the evaluation-mode sampling decode (sample_decode.hip)
+                            RNG_GUMBEL = 8 };      // the Gumbel noise of stochastic beam search (sbs_kernels.h)
 
 struct uint4_ { uint32_t x, y, z, w; };
 

@@ -757,6 +757,31 @@ class BUTDDetection_Eng(Engine):
         entries = self.sample_captions_json_generation(dataloader, samples_per_image, temperature, top_k, top_p, seed, tqdm_visible)
         return self.rerank_captions_json(entries, samples_per_image)
 
+    def sample_distinct_captions_json_generation(self, dataloader, samples_per_image=5, temperature=1.0, seed=0, tqdm_visible=True):
+        """Captions sampled WITHOUT replacement (an extension; include/icz.h: icz_*_sample_distinct, stochastic_beam.py): stochastic
+        beam search returns `samples_per_image` (1..8) distinct captions per image that are exactly a sample without replacement from
+        softmax(logits / temperature) over whole captions, 20 steps, for the cost of one beam search of that width.  Returns
+        {"image_id", "caption", "score", "perturbed"} entries, samples_per_image per image in loader order, an image's entries sorted
+        by "perturbed" descending; score = the caption's summed log-probability under the tempered distribution, perturbed = its
+        Gumbel-perturbed value G (float64; what the without-replacement estimators of Kool et al., ICLR 2020, take).  Batch i of the
+        loader draws from Philox seed `seed * 2**20 + i`; a batch above the handle's row capacity / samples_per_image is decoded in
+        chunks that draw the whole batch's noise (chunked = whole); sharded over the ranks and gathered as
+        sample_captions_json_generation does.  "caption" ends at <end> or at the first <pad> (0): a hypothesis that sampled <pad> as a
+        token prints up to there while its score is the whole sequence's, and two distinct hypotheses may then print alike (a trained
+        model gives <pad> no mass to speak of).  An image with fewer than samples_per_image sequences in all has its empty slots dropped -- this cannot happen at a
+        real vocabulary (V^20 sequences).  Bad arguments raise ValueError before any device work."""
+        return _sample_distinct_captions_json_generation([self], None, False, dataloader, samples_per_image, temperature, seed, tqdm_visible)
+
+    def consensus_distinct_captions_json_generation(self, dataloader, samples_per_image=5, temperature=1.0, seed=0, tqdm_visible=True):
+        """sample_distinct_captions_json_generation (same arguments, samples_per_image 2..8) followed by rerank_captions_json: one
+        consensus caption per image, voted by distinct candidates."""
+        from .caption_sets import check_k
+        check_k(samples_per_image, 2)
+        if self._cider_df is None and self._scorer is None:
+            raise ValueError("caption sets are scored with CIDEr-D: the engine needs cider_df (the document-frequency table)")
+        entries = self.sample_distinct_captions_json_generation(dataloader, samples_per_image, temperature, seed, tqdm_visible)
+        return self.rerank_captions_json(entries, samples_per_image)
+
     def caption_set_report(self, entries, samples_per_image, gts):
         """The report of a caption set in the style of self-critical.pytorch's eval_multi.  entries as for rerank_captions_json,
         gts = {image id: [reference strings]} holding every image of the entries.  Returns
@@ -1204,6 +1229,75 @@ def consensus_ensemble_captions_json_generation(engines, dataloader, samples_per
     entries = sample_ensemble_captions_json_generation(engines, dataloader, samples_per_image, temperature, top_k, top_p, seed, tqdm_visible,
                                                        weights=weights)
     return lead.rerank_captions_json(entries, samples_per_image)
+
+
+def _sample_distinct_captions_json_generation(engines, weights, ensemble, dataloader, samples_per_image, temperature, seed, tqdm_visible):
+    """Engine.sample_distinct_captions_json_generation over one engine's own handle, or (ensemble) an EnsembleHandle over the engines'"""
+    from . import stochastic_beam as sbs
+    lead = engines[0]
+    n, _, temperature = sbs.check_args(samples_per_image, 20, temperature, len(lead.caption_vocab))
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError("seed %r is not a non-negative integer" % (seed,))
+    with _on_stream(lead):
+        for e in engines:
+            e.model.eval()
+        dp = icz_dist.is_distributed()
+        rank, world = icz_dist.rank(), icz_dist.world_size()
+        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Sampling Process", tqdm_visible)
+        ens = None
+        ids_out, rows_out, keys_out = [], [], []
+        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
+            feats = [e._features(e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)) for e in engines]
+            handles = [e._hot_handle() for e in engines]
+            if not ensemble:
+                h, f = handles[0], feats[0]
+            else:
+                from .ensemble import EnsembleHandle
+                if ens is None or any(a is not b for a, b in zip(ens.handles, handles)):
+                    ens = EnsembleHandle(handles, weights)
+                h, f = ens, feats
+            # a batch above the row capacity / n is decoded in chunks of images; a chunk draws the noise of its images within the whole
+            # batch (first_image), so the chunked batch is the whole one
+            B, per = len(image_ids), max(1, h.max_rows // n)
+            part = lambda lo: [_slice_feats(x, lo, lo + per) for x in f] if ensemble else _slice_feats(f, lo, lo + per)      # noqa: E731
+            outs = [sbs.sample_distinct(h, f if per >= B else part(lo), n, 20, temperature, ((seed << 20) + batch_i, lo))
+                    for lo in range(0, B, per)]
+            ids, lens, phi, G = (torch.cat([o[k] for o in outs]).cpu().numpy() for k in (0, 1, 3, 4))
+            pbits, gbits = phi.view(np.uint32), G.view(np.uint64)
+            for r in range(ids.shape[0]):
+                if lens[r] == 0:                                           # an unoccupied slot: fewer than n sequences exist
+                    continue
+                ids_out.append(int(image_ids[r // n]))
+                # the score and the perturbed value travel as their bit patterns (non-negative integers)
+                rows_out.append(np.concatenate([ids[r], [int(pbits[r]), int(gbits[r] & 0xFFFFFFFF), int(gbits[r] >> 32)]]))
+                keys_out.append((batch_i << 20) + r)                       # loader order: batch index, then image, then slot
+        if dp:
+            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, lead.device)
+    result = []
+    ix2word = lead.caption_vocab.ix2word
+    for image_id, row in zip(ids_out, rows_out):
+        words = []
+        for word_id in row[:-3]:
+            word = ix2word[int(word_id)]
+            if word == "<end>" or int(word_id) == 0:
+                break
+            elif word != "<sta>":
+                words.append(word)
+        score = float(np.array([int(row[-3])], dtype=np.uint32).view(np.float32)[0])
+        pert = float(np.array([int(row[-2]) | (int(row[-1]) << 32)], dtype=np.uint64).view(np.float64)[0])
+        result.append({"image_id": image_id, "caption": " ".join(words), "score": score, "perturbed": pert})
+    return result
+
+
+def sample_distinct_ensemble_captions_json_generation(engines, dataloader, samples_per_image=5, temperature=1.0, seed=0, tqdm_visible=True, *,
+                                                      weights=None):
+    """Engine.sample_distinct_captions_json_generation for an ensemble of 1..4 engines (BUTD / AoA / NIC) of one vocabulary (an
+    extension; include/icz.h: icz_ensemble_sample_distinct): `samples_per_image` distinct captions per image, a sample without
+    replacement from the members' averaged word probabilities (`weights`: None = uniform) at the temperature.  Entries, seeding,
+    sharding and gathering as the single-model method (the first engine's vocabulary); score = the ensemble's summed log-probability.
+    Arguments are checked before any device work (ValueError)."""
+    engines = _ensemble_engine_checks(engines, weights)
+    return _sample_distinct_captions_json_generation(engines, weights, True, dataloader, samples_per_image, temperature, seed, tqdm_visible)
 
 
 # ---- scoring given captions: what the Engine methods and the ensemble functions share ---------------------------------------------
