@@ -789,6 +789,76 @@ int icz_aoa_xe_backward_dlogits(icz_aoa_t* h, const float* dpacked, const icz_ao
 int icz_nic_xe_backward_dlogits(icz_nic_t* h, const float* dpacked, const icz_nic_params* grads, float* dfeatures_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * SCST objectives (beyond the reference; csrc/scst_objective.hip): what turns the sampled captions of a stored rollout into a gradient,
+ * in the place of RewardCriterion in icz_*_sample_backward.
+ *
+ * Rows are r = img * K + k; a single-sample rollout has K = 1.  mask[r, 0] = 1 and mask[r, t] = seq[r, t - 1] > 0, as in
+ * RewardCriterion.  M is sum(mask), or the global mask sum under the rules of icz_*_sample_backward: mask_sum_global > 0 is the global
+ * sum given on the host side, < 0 takes the device scalar of icz_*_set_mask_sum_global / _set_norm_global, 0 uses the local sum.
+ * p[r, t, :] is the softmax of the STORED training-mode logits of step t -- the distribution the token was drawn from, with dropout
+ * applied; its log-sum-exp is stored beside the drawn token.
+ *
+ * Objective term, one of
+ *   ICZ_SCST_REINFORCE (0): obj = -sum(logp * reward * mask) / M with reward [rows, T] float32 -- today's form; coef = d obj / d logp
+ *     comes from reinforce_loss_kernel, unchanged.
+ *   ICZ_SCST_RISK (1), K = 2..8, scores [rows] float64 (the CIDEr-D of every sample, laid out as icz_ciderd_reward_loo's scores_out),
+ *     minimum-risk training: the expected cost under the model's distribution renormalised over the K samples.  With c_r = -scores[r]:
+ *       s_r   = sum_t mask[r, t] * logp[r, t]        (the float32 logp values, summed in float64 in ascending t)
+ *       Q_r   = exp(a s_r) / sum_{j in image} exp(a s_j)   (float64, shifted by the image's largest a s_j, j ascending)
+ *       L_img = sum_k Q_k c_k
+ *       obj   = (1 / N) sum_img L_img                (N = n_img_global if > 0, else the call's image count)
+ *       coef[r, t] = mask[r, t] * a * Q_r * (c_r - L_img) / N     (stored as float32)
+ *     a = risk_alpha must be finite and > 0.
+ * Entropy term, for entropy_weight = b >= 0 (finite):
+ *       H[r, t] = -sum_v p_v log p_v,   ent = sum(mask * H) / M,   loss = obj - b * ent.
+ * The gradient written in place over the stored logits (pad columns [V, ldl) zero) is
+ *       dlogits[row, v] = coef[r, t] * (1[v == draw] - p_v) + (b * mask[r, t] / M) * p_v * (log p_v + H[r, t])
+ * with log p_v = logits[v] - lse[row].  A row with mask = 0, or draw < 0 (the evaluation-mode rows of a merged chain), becomes all
+ * zeros WITHOUT BEING READ: steps behind the rollout's early-out hold stale data.
+ *
+ * Kernels: scst_risk_kernel (one wave per image, float64, fixed orders) + scst_risk_sum_kernel fill coef, obj and the mask sum;
+ * scst_entropy_dlogits_kernel (b > 0; one 256-thread workgroup per stored row, two passes over the row with 16-byte loads, fp32 terms
+ * and float64 sums in one fixed order, nothing kept in LDS: no cap on V) stands in for reinforce_dlogits_kernel; scst_finish_kernel
+ * sums the per-row entropies in a fixed order.  No float atomics: two runs give the same bits.  Kind 0 with b = 0 runs the launches
+ * of icz_*_sample_backward (bit for bit its gradients, loss and mask sum).
+ * loss_out3 = {loss, obj, ent} (device floats); ent_out [rows, T] (optional) = mask * H.  With b = 0 no row is read for H: ent and
+ * ent_out are reported as 0.
+ *
+ * icz_scst_objective_check returns ICZ_ERR_INVALID in this order: 1. null struct; 2. kind; 3. K outside 1..8 (risk: 2..8), or rows / T
+ * not positive, or rows % K != 0; 4. risk_alpha not finite or <= 0 (both kinds); 5. entropy_weight not finite or < 0; 6. n_img_global
+ * not finite or < 0; 7. the pointer the kind needs (reward / scores) null.  icz_*_sample_backward_objective applies rules 1 - 7 (rule 3
+ * without the row count), then 8. null grads or loss_out3; 9. null handle; 10. no rollout stored; 11. rule 3 against the stored rows;
+ * 12. a risk term whose K is not the stored rollout's (icz_*_sample_n's K, else 1).  Every refusal happens before anything is queued:
+ * the stored rollout stays usable.
+ * BUTD and AoA replay captured graphs as icz_*_sample_backward does; the key also carries kind, K, the bit patterns of risk_alpha,
+ * entropy_weight and n_img_global, and the reward / scores / ent_out pointers.  BUTD with a gradient callback runs the loss head in
+ * its first phase.  train_refiner, per-image region counts, the early-out and the global mask sum work as behind icz_*_sample_backward.
+ * ---------------------------------------------------------------------------------------------------------- */
+enum { ICZ_SCST_REINFORCE = 0, ICZ_SCST_RISK = 1 };
+typedef struct {
+    int32_t kind, K;
+    float risk_alpha, entropy_weight, n_img_global;
+    const float* reward;           /* kind 0: [rows, T] (device) */
+    const double* scores;          /* kind 1: [rows] (device) */
+} icz_scst_objective;
+/* rules 1 - 7 above on their own (host only: no handle, no device) */
+int icz_scst_objective_check(const icz_scst_objective* obj, int32_t rows, int32_t T);
+int icz_butd_sample_backward_objective(icz_butd_t* h, const icz_scst_objective* obj, const icz_butd_params* grads, float* loss_out3,
+                                       float* ent_out, float* mask_sum_out, float mask_sum_global, void* stream);
+int icz_aoa_sample_backward_objective(icz_aoa_t* h, const icz_scst_objective* obj, const icz_aoa_params* grads, float* loss_out3, float* ent_out,
+                                      float* mask_sum_out, float mask_sum_global, void* stream);
+/* dfeatures_out [images, E] or NULL, as icz_nic_sample_backward */
+int icz_nic_sample_backward_objective(icz_nic_t* h, const icz_scst_objective* obj, const icz_nic_params* grads, float* dfeatures_out,
+                                      float* loss_out3, float* ent_out, float* mask_sum_out, float mask_sum_global, void* stream);
+/* The kernels alone (tests, tools), in the shape of icz_test_reinforce: logp, seq, coef [B, T] (B = rows of the rollout);
+ * mask_sum_global a device scalar or NULL; logits [T Bs', ldl] (Bs' = Bs or B), draw / lse [T Bs'], Bs > 0: Bs rows per step of which
+ * [row0, row0 + B) are the rollout's.  loss_out3 [3]; ent_out [B, T] and mask_sum_out optional.  With entropy_weight > 0: ldl % 4 == 0
+ * and 16-byte aligned logits.  Kind 0 with entropy_weight 0 is icz_test_reinforce. */
+int icz_test_scst_objective(const icz_scst_objective* obj, const float* logp, const int64_t* seq, int32_t B, int32_t T,
+                            const float* mask_sum_global, float* coef, float* loss_out3, float* ent_out, float* mask_sum_out, float* logits,
+                            int32_t V, int32_t ldl, const int32_t* draw, const float* lse, int32_t Bs, int32_t row0, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser step: clip_gradient (Utils.py:241-250, value clamp) + torch.optim.Adam(betas=(0.9,0.999),
  * eps=1e-8, weight_decay=0) (Utils.py:219-220) fused, one call per parameter tensor.
  * ---------------------------------------------------------------------------------------------------------- */

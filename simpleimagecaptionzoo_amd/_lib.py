@@ -153,6 +153,11 @@ class DistillOpts(C.Structure):    # icz_distill_opts
                 ("alpha", C.c_float), ("temperature", C.c_float), ("smoothing", C.c_float)]
 
 
+class ScstObjective(C.Structure):  # icz_scst_objective
+    _fields_ = [("kind", C.c_int32), ("K", C.c_int32), ("risk_alpha", C.c_float), ("entropy_weight", C.c_float), ("n_img_global", C.c_float),
+                ("reward", C.c_void_p), ("scores", C.c_void_p)]
+
+
 class DropPArgs(C.Structure):      # icz_test_dropp
     _fields_ = [("mode", C.c_int32), ("mask", C.c_void_p), ("seed", C.c_void_p), ("stream", C.c_uint32), ("step", C.c_uint32),
                 ("p", C.c_float), ("idx0", C.c_uint64)]
@@ -303,6 +308,11 @@ def lib():
         "icz_aoa_xe_backward_distill": (C.c_int, [vp, C.POINTER(DistillOpts), C.POINTER(AoaParams), vp, f32, vp]),
         "icz_nic_xe_backward_distill": (C.c_int, [vp, C.POINTER(DistillOpts), C.POINTER(NicParams), vp, vp, f32, vp]),
         "icz_distill_loss": (C.c_int, [vp, i32, C.POINTER(DistillOpts), vp, i32, i32, f32, vp, i32, vp, vp]),
+        "icz_scst_objective_check": (C.c_int, [C.POINTER(ScstObjective), i32, i32]),
+        "icz_butd_sample_backward_objective": (C.c_int, [vp, C.POINTER(ScstObjective), C.POINTER(ButdParams), vp, vp, vp, f32, vp]),
+        "icz_aoa_sample_backward_objective": (C.c_int, [vp, C.POINTER(ScstObjective), C.POINTER(AoaParams), vp, vp, vp, f32, vp]),
+        "icz_nic_sample_backward_objective": (C.c_int, [vp, C.POINTER(ScstObjective), C.POINTER(NicParams), vp, vp, vp, vp, f32, vp]),
+        "icz_test_scst_objective": (C.c_int, [C.POINTER(ScstObjective), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp]),
         "icz_aoa_xe_backward_dlogits": (C.c_int, [vp, vp, C.POINTER(AoaParams), vp]),
         "icz_nic_xe_backward_dlogits": (C.c_int, [vp, vp, C.POINTER(NicParams), vp, vp]),
         "icz_aoa_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),

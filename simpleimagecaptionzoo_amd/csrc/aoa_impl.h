@@ -253,7 +253,10 @@ struct Aoa : CaptionHead, DecodeMember {
     int sample_prelude(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st, int K = 1);
     int sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st, const float* proj = nullptr, bool refined_ready = false,
                     int n_img = 0);
-    int sample_backward_impl(const float* reward, const icz_aoa_params& G, float* loss_out, float* msum_out, hipStream_t st);
+    int sample_backward_impl(const RolloutHead& hd, const icz_aoa_params& G, hipStream_t st);
+    int sample_backward_head(const RolloutHead& hd, const icz_aoa_params* G, float msum_global, hipStream_t st);
+    int sample_backward_objective(const icz_scst_objective* obj, const icz_aoa_params* G, float* loss_out3, float* ent_out, float* msum_out,
+                                  float msum_global, hipStream_t st);
     int sample_backward(const float* reward, const icz_aoa_params* G, float* loss_out, float* msum_out, float msum_global, hipStream_t st);
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_aoa_rng* r, int train,
                    float* packed_out, hipStream_t st);

@@ -437,6 +437,20 @@ int Aoa::rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int64
 int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* loss_out, float* msum_out, float msum_global, hipStream_t st) {
     ICZ_TRY(require_mode(1, "aoa"));
     ICZ_REQUIRE(reward && G, "aoa sample_backward: null argument");
+    return sample_backward_head({reward, nullptr, loss_out, nullptr, msum_out}, G, msum_global, st);
+}
+
+// sample_backward with an SCST objective (scst_objective.hip) in the place of RewardCriterion; the captured graph carries the
+// objective in its key (ScstObjective::key) beside the output pointers
+int Aoa::sample_backward_objective(const icz_scst_objective* obj, const icz_aoa_params* G, float* loss_out3, float* ent_out, float* msum_out,
+                                   float msum_global, hipStream_t st) {
+    ICZ_TRY(require_mode(1, "aoa"));
+    ScstObjective o;
+    ICZ_TRY(check_objective("aoa sample_backward_objective", obj, cur_K, &o));
+    return sample_backward_head({nullptr, &o, loss_out3, ent_out, msum_out}, G, msum_global, st);
+}
+
+int Aoa::sample_backward_head(const RolloutHead& hd, const icz_aoa_params* G, float msum_global, hipStream_t st) {
     if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
     set_msum_global(msum_global, st);      // < 0: keep the device value handed over by icz_aoa_set_norm_global
     mode = 0;
@@ -445,19 +459,20 @@ int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* lo
     // streams' work can serialise on this runtime (EXPERIMENTS.md, round 4, section 8), and the AoA paths are eager
     ICZ_TRY(low.ensure());
     // with a DP callback the hook must fire on every call: eager launches (a replayed graph would not call it)
-    if (!use_graphs || lens || grad_cb || aoa_explicit_rng(rng)) return sample_backward_impl(reward, *G, loss_out, msum_out, st);
-    std::vector<uintptr_t> key = {2, (uintptr_t)reward, (uintptr_t)loss_out, (uintptr_t)msum_out, (uintptr_t)cur_B, (uintptr_t)cur_T, (uintptr_t)cur_R,
+    if (!use_graphs || lens || grad_cb || aoa_explicit_rng(rng)) return sample_backward_impl(hd, *G, st);
+    std::vector<uintptr_t> key = {2, (uintptr_t)hd.reward, (uintptr_t)hd.loss_out, (uintptr_t)hd.msum_out, (uintptr_t)cur_B, (uintptr_t)cur_T, (uintptr_t)cur_R,
                                   (uintptr_t)cur_seq, (uintptr_t)cur_logp, (uintptr_t)cur_K,      // sample_n of B K rows against sample of B K rows: other launches
                                   (uintptr_t)bank[0].refined, (uintptr_t)bank[0].Kd, (uintptr_t)bank[1].refined, (uintptr_t)bank[1].Kd, (uintptr_t)bank[1].Vd, (uintptr_t)cur_bank,      // paired-refine banks (rollouts) or the handle's own (sample)
                                   (uintptr_t)train_refiner, (uintptr_t)xs[0], (uintptr_t)ref_feats};      // the refiner's backward pass behind bptt
     const float* const* gp = reinterpret_cast<const float* const*>(G);
     for (size_t i = 0; i < sizeof(icz_aoa_params) / sizeof(float*); ++i) key.push_back((uintptr_t)gp[i]);
+    if (hd.obj) { hd.obj->key(key); key.push_back((uintptr_t)hd.ent_out); }
     const icz_aoa_params Gc = *G;
-    return gc.run(key, st, [&](hipStream_t s) { return sample_backward_impl(reward, Gc, loss_out, msum_out, s); });
+    return gc.run(key, st, [&](hipStream_t s) { return sample_backward_impl(hd, Gc, s); });
 }
 
-int Aoa::sample_backward_impl(const float* reward, const icz_aoa_params& G, float* loss_out, float* msum_out, hipStream_t st) {
-    ICZ_TRY(reinforce(reward, tlogit, dims.V, Vp, loss_out, msum_out, st));
+int Aoa::sample_backward_impl(const RolloutHead& hd, const icz_aoa_params& G, hipStream_t st) {
+    ICZ_TRY(rollout_head(hd, tlogit, dims.V, Vp, st));
     return bptt(G, st);
 }
 
@@ -833,6 +848,13 @@ int icz_aoa_sample_backward(icz_aoa_t* h, const float* reward, const icz_aoa_par
                             float mask_sum_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Aoa*>(h)->sample_backward(reward, grads, loss_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
+}
+int icz_aoa_sample_backward_objective(icz_aoa_t* h, const icz_scst_objective* obj, const icz_aoa_params* grads, float* loss_out3, float* ent_out,
+                                      float* mask_sum_out, float mask_sum_global, void* stream) {
+    ICZ_TRY(icz::scst_objective_args("icz_aoa_sample_backward_objective", obj, obj ? obj->K : 1, 1, nullptr));
+    ICZ_REQUIRE(grads && loss_out3, "icz_aoa_sample_backward_objective: null argument");
+    ICZ_REQUIRE(h, "icz_aoa_sample_backward_objective: null handle");
+    return reinterpret_cast<Aoa*>(h)->sample_backward_objective(obj, grads, loss_out3, ent_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
 }
 int icz_aoa_set_scheduled_sampling(icz_aoa_t* h, float ss_prob, const float* gate_uniforms, const float* draw_uniforms) {
     return set_scheduled_sampling("icz_aoa_set_scheduled_sampling", reinterpret_cast<Aoa*>(h), ss_prob, gate_uniforms, draw_uniforms);

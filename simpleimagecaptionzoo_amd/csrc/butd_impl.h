@@ -126,8 +126,8 @@ struct Butd : CaptionHead, DecodeMember {
     SideStream low;                      // lowest priority, for work overlapped with the BPTT chain; its second event pair: the attention
                                          // block's tail beside the LSTM weight gradients (bptt)
     icz_grad_ready_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // DP overlap hook (icz_butd_set_grad_callback)
-    int sample_backward_impl(const float* reward, const icz_butd_params& G, float* loss_out, float* mask_sum_out, hipStream_t st,
-                             int phases = 0xF, bool fire_cb = true);
+    int sample_backward_impl(const RolloutHead& hd, const icz_butd_params& G, hipStream_t st, int phases = 0xF, bool fire_cb = true);
+    int sample_backward_head(const RolloutHead& hd, const icz_butd_params* G, float mask_sum_global, hipStream_t st);
     int merge_small = 8;                 // option "merge_small" = n: SCST rollouts of <= n images (n <= 32) run as ONE chain of 2 B decoder rows
                                          // (sample_chain with row0 = B); 0 = never.  Default 8: measured round 5 (EXPERIMENTS.md), the
                                          // merged chain saves 0.2 ms of rollouts at every size but costs the backward pass 0.06 / 0.15 /
@@ -177,6 +177,8 @@ struct Butd : CaptionHead, DecodeMember {
                         float mask_sum_global, hipStream_t st);
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r,
                    int train, float* packed_out, hipStream_t st);
+    int sample_backward_objective(const icz_scst_objective* obj, const icz_butd_params* G, float* loss_out3, float* ent_out, float* mask_sum_out,
+                                  float mask_sum_global, hipStream_t st);
     int sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hipStream_t st);
     int xe_backward_dlogits(const float* dpacked, const icz_butd_params* G, hipStream_t st);
     int xe_backward(float smoothing, const icz_butd_params* G, float* loss_out, float n_tokens_global, hipStream_t st);

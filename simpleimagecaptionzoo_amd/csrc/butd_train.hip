@@ -328,22 +328,38 @@ int Butd::sample_backward(const float* reward, const icz_butd_params* G, float* 
                           float mask_sum_global, hipStream_t st) {
     ICZ_TRY(require_mode(1, "butd"));
     ICZ_REQUIRE(reward && G, "butd sample_backward: null argument");
+    return sample_backward_head({reward, nullptr, loss_out, nullptr, mask_sum_out}, G, mask_sum_global, st);
+}
+
+// sample_backward with an SCST objective (scst_objective.hip) in the place of RewardCriterion; the captured graphs carry the
+// objective in their key (ScstObjective::key) beside the output pointers
+int Butd::sample_backward_objective(const icz_scst_objective* obj, const icz_butd_params* G, float* loss_out3, float* ent_out,
+                                    float* mask_sum_out, float mask_sum_global, hipStream_t st) {
+    const char* who = "butd sample_backward_objective";
+    ICZ_TRY(require_mode(1, "butd"));
+    ScstObjective o;
+    ICZ_TRY(check_objective(who, obj, cur_K, &o));
+    return sample_backward_head({nullptr, &o, loss_out3, ent_out, mask_sum_out}, G, mask_sum_global, st);
+}
+
+int Butd::sample_backward_head(const RolloutHead& hd, const icz_butd_params* G, float mask_sum_global, hipStream_t st) {
     set_msum_global(mask_sum_global, st);      // < 0: keep the device value set by icz_butd_set_mask_sum_global
     mode = 0;   // the saved logits are consumed
     bptt_early_out = true;
     ICZ_TRY(bptt_prelude(st));      // outside the captured graph
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
-    if (explicit_rng || !graphs_on()) return sample_backward_impl(reward, *G, loss_out, mask_sum_out, st);
-    std::vector<uintptr_t> key = {3, (uintptr_t)reward, (uintptr_t)loss_out, (uintptr_t)mask_sum_out, (uintptr_t)cur_B, (uintptr_t)cur_T,
+    if (explicit_rng || !graphs_on()) return sample_backward_impl(hd, *G, st);
+    std::vector<uintptr_t> key = {3, (uintptr_t)hd.reward, (uintptr_t)hd.loss_out, (uintptr_t)hd.msum_out, (uintptr_t)cur_B, (uintptr_t)cur_T,
                                   (uintptr_t)cur_feats, (uintptr_t)cur_seq, (uintptr_t)cur_logp,
                                   (uintptr_t)cur_rows, (uintptr_t)cur_row0,       // merged / unmerged rollouts share the caller's buffers: slot strides differ
                                   (uintptr_t)cur_K};                              // sample_n of B K rows against sample of B K rows: other kernels
     const float* const* gp = reinterpret_cast<const float* const*>(G);
     for (size_t i = 0; i < sizeof(icz_butd_params) / sizeof(float*); ++i) key.push_back((uintptr_t)gp[i]);
+    if (hd.obj) { hd.obj->key(key); key.push_back((uintptr_t)hd.ent_out); }
     const icz_butd_params Gc = *G;
     if (!grad_cb) {
         key.push_back(opt_bits());
-        return gc.run(key, st, [&](hipStream_t s) { return sample_backward_impl(reward, Gc, loss_out, mask_sum_out, s); });
+        return gc.run(key, st, [&](hipStream_t s) { return sample_backward_impl(hd, Gc, s); });
     }
     // The DP hook must fire on every call (a replayed graph would not call it): the backward is cut at the three points where a
     // gradient group is complete, every piece is its own captured graph, and the hook is called between the replays -- the
@@ -352,15 +368,14 @@ int Butd::sample_backward(const float* reward, const icz_butd_params* G, float* 
         std::vector<uintptr_t> k2 = key;
         k2.push_back(0x100 + ph);
         k2.push_back(opt_bits());
-        ICZ_TRY(gc.run(k2, st, [&](hipStream_t s) { return sample_backward_impl(reward, Gc, loss_out, mask_sum_out, s, 1 << ph, false); }));
+        ICZ_TRY(gc.run(k2, st, [&](hipStream_t s) { return sample_backward_impl(hd, Gc, s, 1 << ph, false); }));
         if (ph < 3) grad_cb(grad_cb_user, ph);
     }
     return ICZ_OK;
 }
 
-int Butd::sample_backward_impl(const float* reward, const icz_butd_params& G, float* loss_out, float* mask_sum_out, hipStream_t st,
-                               int phases, bool fire_cb) {
-    if (phases & 1) ICZ_TRY(reinforce(reward, tb.logit, dims.V, pad_vocab(dims.V), loss_out, mask_sum_out, st, cur_rows, cur_row0));
+int Butd::sample_backward_impl(const RolloutHead& hd, const icz_butd_params& G, hipStream_t st, int phases, bool fire_cb) {
+    if (phases & 1) ICZ_TRY(rollout_head(hd, tb.logit, dims.V, pad_vocab(dims.V), st, cur_rows, cur_row0));
     return bptt(G, st, phases, fire_cb);
 }
 
@@ -844,6 +859,13 @@ int icz_butd_sample_backward(icz_butd_t* h, const float* reward, const icz_butd_
                              float* mask_sum_out, float mask_sum_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Butd*>(h)->sample_backward(reward, grads, loss_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
+}
+int icz_butd_sample_backward_objective(icz_butd_t* h, const icz_scst_objective* obj, const icz_butd_params* grads, float* loss_out3,
+                                       float* ent_out, float* mask_sum_out, float mask_sum_global, void* stream) {
+    ICZ_TRY(icz::scst_objective_args("icz_butd_sample_backward_objective", obj, obj ? obj->K : 1, 1, nullptr));
+    ICZ_REQUIRE(grads && loss_out3, "icz_butd_sample_backward_objective: null argument");
+    ICZ_REQUIRE(h, "icz_butd_sample_backward_objective: null handle");
+    return reinterpret_cast<Butd*>(h)->sample_backward_objective(obj, grads, loss_out3, ent_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
 }
 int icz_butd_sample_backward_dlogp(icz_butd_t* h, const float* dlogp, const icz_butd_params* grads, void* stream) {
     ICZ_REQUIRE(h, "null handle");

@@ -193,6 +193,17 @@ struct SideStream {
 };
 
 struct DistillArgs;                   // ens_sample.h: the teachers' packed logits and the options of a distillation step
+// An SCST objective (scst_objective.hip; include/icz.h: icz_scst_objective, checked by scst_objective_args) as the loss head takes it;
+// key(): what a captured backward pass bakes in of it -- kind, K, the bit patterns of the three reals, the reward / scores pointers.
+struct ScstObjective {
+    int kind, K; float risk_alpha, entropy_weight, n_img_global; const float* reward; const double* scores;
+    void key(std::vector<uintptr_t>& k) const;
+};
+// scratch of the objective's kernels: per-row entropies [T rows], per-image risk and mask count [images], the local mask sum
+struct ScstScratch { float* ent_rows; double* L_img; int* m_img; float* scal; };
+// The loss head of a rollout's backward pass as a decoder calls it: obj null = RewardCriterion on `reward` (loss_out [1]), else the
+// objective (loss_out [3] = {loss, obj, ent}, ent_out [rows, T] or null)
+struct RolloutHead { const float* reward; const ScstObjective* obj; float* loss_out; float* ent_out; float* msum_out; };
 // The caption loss head: host-side state of a stored training-mode forward pass and the loss buffers of all three decoders.
 struct CaptionHead {
     int mode = 0;                 // 0 none, 1 sample rollout stored, 2 XE forward stored
@@ -212,6 +223,7 @@ struct CaptionHead {
     uint8_t* gunf = nullptr; int* gnunf = nullptr;     // the same for the greedy baseline of an SCST step
     int* live_rows = nullptr;     // (steps the sampled rollout ran) x B: row limit of the backward pass's batched GEMMs
     int* pack_idx = nullptr; int pack_cap = 0;         // packed-sequence index: row_off[T] | rows_t[T]
+    double* obj_img = nullptr; int* obj_mimg = nullptr; float* obj_scal = nullptr;      // ScstScratch beside loss_rows (scst_objective)
 
     int alloc_scalars(DeviceBuffers& m);
     int alloc_loss_buffers(DeviceBuffers& m, size_t TB, size_t B, size_t T);
@@ -234,6 +246,13 @@ struct CaptionHead {
     // REINFORCE: loss, mask sum and dlogits (in place) of the stored rollout; rows / row0: rows per step slot and the first of the
     // sampled rollout's (a merged SCST chain stores 2 B rows per slot)
     int reinforce(const float* reward, float* logits, int V, int ldl, float* loss_out, float* msum_out, hipStream_t st, int rows = 0, int row0 = 0);
+    // An SCST objective in the place of reinforce (scst_objective.hip): kind 0 with entropy_weight 0 calls reinforce itself;
+    // loss_out3 = {loss, obj, ent}, ent_out [rows of the rollout, T] optional.  check_objective: the rules of icz_scst_objective
+    // against the stored rollout (stored_K = its samples per image), before anything is queued.
+    int check_objective(const char* who, const icz_scst_objective* obj, int stored_K, ScstObjective* out) const;
+    int scst_objective(const ScstObjective& o, float* logits, int V, int ldl, float* loss_out3, float* ent_out, float* msum_out, hipStream_t st,
+                       int rows = 0, int row0 = 0);
+    int rollout_head(const RolloutHead& hd, float* logits, int V, int ldl, hipStream_t st, int rows = 0, int row0 = 0);
     void set_msum_global(float msum_global, hipStream_t st) const;       // < 0: keep the device value handed over by icz_*_set_norm_global
     int upload_pack_index(hipStream_t st);
 };
@@ -245,6 +264,12 @@ int launch_xe_loss(float* logits, int V, int ldl, const int64_t* captions, int L
                    const float* n_dev, float* loss_rows, float* loss_out, hipStream_t st);
 int launch_reinforce(const float* logp, const int64_t* seq, const float* reward, int B, int T, const float* msum_dev, float* coef, float* loss_out,
                      float* msum_out, float* logits, int V, int ldl, const int32_t* draw, const float* lse, int rows, int row0, hipStream_t st);
+
+// The launch site of the SCST objectives, shared by CaptionHead::scst_objective and icz_test_scst_objective; arguments as launch_reinforce
+int scst_objective_args(const char* who, const icz_scst_objective* o, int rows, int T, ScstObjective* out);
+int launch_scst_objective(const ScstObjective& o, const float* logp, const int64_t* seq, int B, int T, const float* msum_dev,
+                          const ScstScratch& w, float* coef, float* out3, float* ent_out, float* msum_out, float* logits, int V, int ldl,
+                          const int32_t* draw, const float* lse, int rows, int row0, hipStream_t st);
 
 // Where one decoder step left its logits: ns == 1 finished rows [rows][ld]; ns > 1 the predict GEMM's split-K slabs [ns][rows][ld]
 // (slab z at p + z * slab_stride, no bias yet) + bias[v], summed in slab order as greedy_select_kernel / sample_select_kernel do.

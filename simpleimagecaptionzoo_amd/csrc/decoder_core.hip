@@ -60,12 +60,16 @@ int CaptionHead::alloc_loss_buffers(DeviceBuffers& m, size_t TB, size_t B, size_
     ICZ_TRY(m.alloc((void**)&live_rows, 16));
     ICZ_TRY(m.alloc((void**)&pack_idx, sizeof(int) * 2 * T));
     pack_cap = (int)(2 * T);
+    ICZ_TRY(m.alloc((void**)&obj_img, sizeof(double) * B));
+    ICZ_TRY(m.alloc((void**)&obj_mimg, sizeof(int) * B));
+    ICZ_TRY(m.alloc((void**)&obj_scal, 16));
     return ICZ_OK;
 }
 
 void CaptionHead::drop_loss_buffers() {
     coef = lse = loss_rows = kd_rows = nullptr; draw = nullptr; unf = gunf = nullptr; nunf = gnunf = live_rows = pack_idx = nullptr;
     pack_cap = 0;
+    obj_img = nullptr; obj_mimg = nullptr; obj_scal = nullptr;
     mode = 0;
 }
 

@@ -54,6 +54,9 @@ struct Nic : CaptionHead, DecodeMember {
     int sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
     int sample_n(const float* feats, int B, int K, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
     int sample_backward(const float* reward, const icz_nic_params* G, float* dfeats, float* loss_out, float* msum_out, float msum_global, hipStream_t st);
+    int sample_backward_head(const RolloutHead& hd, const icz_nic_params* G, float* dfeats, float msum_global, hipStream_t st);
+    int sample_backward_objective(const icz_scst_objective* obj, const icz_nic_params* G, float* dfeats, float* loss_out3, float* ent_out,
+                                  float* msum_out, float msum_global, hipStream_t st);
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r, int train,
                    float* packed_out, hipStream_t st);
     int xe_backward(float smoothing, const icz_nic_params* G, float* dfeats, float* loss_out, float n_tokens_global, hipStream_t st);
@@ -265,8 +268,21 @@ int Nic::sample_backward(const float* reward, const icz_nic_params* G, float* df
                          hipStream_t st) {
     ICZ_TRY(require_mode(1, "nic"));
     ICZ_REQUIRE(reward && G, "nic sample_backward: null argument");
+    return sample_backward_head({reward, nullptr, loss_out, nullptr, msum_out}, G, dfeats, msum_global, st);
+}
+
+// sample_backward with an SCST objective (scst_objective.hip) in the place of RewardCriterion (eager, as every NIC backward pass)
+int Nic::sample_backward_objective(const icz_scst_objective* obj, const icz_nic_params* G, float* dfeats, float* loss_out3, float* ent_out,
+                                   float* msum_out, float msum_global, hipStream_t st) {
+    ICZ_TRY(require_mode(1, "nic"));
+    ScstObjective o;
+    ICZ_TRY(check_objective("nic sample_backward_objective", obj, cur_K, &o));
+    return sample_backward_head({nullptr, &o, loss_out3, ent_out, msum_out}, G, dfeats, msum_global, st);
+}
+
+int Nic::sample_backward_head(const RolloutHead& hd, const icz_nic_params* G, float* dfeats, float msum_global, hipStream_t st) {
     set_msum_global(msum_global, st);      // < 0: keep the device value handed over by icz_nic_set_norm_global
-    ICZ_TRY(reinforce(reward, tlogit, dims.V, Vp, loss_out, msum_out, st));
+    ICZ_TRY(rollout_head(hd, tlogit, dims.V, Vp, st));
     mode = 0;
     bptt_early_out = true;
     if (cur_K == 1 || !dfeats) return bptt(*G, dfeats, st);
@@ -461,6 +477,14 @@ int icz_nic_sample_backward(icz_nic_t* h, const float* reward, const icz_nic_par
                             float* mask_sum_out, float mask_sum_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Nic*>(h)->sample_backward(reward, grads, dfeatures_out, loss_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
+}
+int icz_nic_sample_backward_objective(icz_nic_t* h, const icz_scst_objective* obj, const icz_nic_params* grads, float* dfeatures_out,
+                                      float* loss_out3, float* ent_out, float* mask_sum_out, float mask_sum_global, void* stream) {
+    ICZ_TRY(icz::scst_objective_args("icz_nic_sample_backward_objective", obj, obj ? obj->K : 1, 1, nullptr));
+    ICZ_REQUIRE(grads && loss_out3, "icz_nic_sample_backward_objective: null argument");
+    ICZ_REQUIRE(h, "icz_nic_sample_backward_objective: null handle");
+    return reinterpret_cast<Nic*>(h)->sample_backward_objective(obj, grads, dfeatures_out, loss_out3, ent_out, mask_sum_out, mask_sum_global,
+                                                                (hipStream_t)stream);
 }
 int icz_nic_set_scheduled_sampling(icz_nic_t* h, float ss_prob, const float* gate_uniforms, const float* draw_uniforms) {
     return set_scheduled_sampling("icz_nic_set_scheduled_sampling", reinterpret_cast<Nic*>(h), ss_prob, gate_uniforms, draw_uniforms);

@@ -20,6 +20,7 @@ from ._lib import BUTD_PARAM_KEYS, check, lib, ptr, stream_ptr
 from .beam import make_diversity, parse_length_penalty
 from .sampling import make_sample_opts
 from .multisample import sample_n
+from .scst_objective import sample_backward_objective
 from .captioner import BUTDDetection_Captioner
 from .ciderd import CiderDReward
 from . import dist as icz_dist
@@ -141,6 +142,7 @@ class Engine(object):
         import os
         self.dp_overlap = os.environ.get("ICZ_DP_OVERLAP", "1") not in ("0", "")
         self.phase_events = None    # a list: every SCST step appends its phase-boundary events (phase_times() turns them into ms)
+        self.scst_terms = None      # a list: every SCST step run with an objective appends its (obj, ent) pair of 1-element device tensors
         # The hot path runs on its own non-default stream: after hipGraph replays, eager launches on the legacy null
         # stream were measured 2-3x slower on ROCm 7.2 (implicit synchronisation with the graph's internal streams).
         self.stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
@@ -197,11 +199,38 @@ class Engine(object):
         step.  K = samples_per_image (2..8) captions are sampled per image (multisample.sample_n: the per-image work runs once per
         image), each is baselined by the mean CIDEr-D of the image's other K - 1 (reward_loo), and there is no greedy rollout; the
         mask-sum exchange, the gradient-reduce hooks, the 0.25 clamp and Adam are SCST_training_epoch's.  B K must fit the handle's
-        row capacity.  ValueError for a K outside 2..8, a bool or a non-integer, before any device work."""
+        row capacity.  ValueError for a K outside 2..8, a bool or a non-integer, before any device work.  (Other objectives over the
+        same K samples: SCST_objective_training_epoch.)"""
         from .multisample import check_samples
         k = check_samples(samples_per_image)
         with _on_stream(self):
             return self._scst_training_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs, k)
+
+    def SCST_objective_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=5,
+                                      objective="loo", risk_alpha=1.0, entropy_weight=0.0):
+        """SCST_multisample_training_epoch (same arguments in front, every decoder family) with the objective to choose (beyond the
+        reference; scst_objective.py): objective "loo" is that method's leave-one-out reward through RewardCriterion, "risk" is
+        minimum-risk training over the K samples of an image with sharpness risk_alpha (finite, > 0); entropy_weight > 0 (finite)
+        subtracts that multiple of the mean per-step entropy of the word distribution from the loss.  The defaults run
+        SCST_multisample_training_epoch's calls exactly.  The returned list stays the total loss per step; while `scst_terms` is a
+        list every step run with an objective appends its (obj, ent) device pair.  Data-parallel, "risk" divides by the all-reduced
+        image count.  ValueError for a bad samples_per_image, objective, risk_alpha or entropy_weight before any device work."""
+        from .multisample import check_samples
+        k = check_samples(samples_per_image)
+        if objective not in ("loo", "risk"):
+            raise ValueError("objective must be 'loo' or 'risk', got %r" % (objective,))
+        obj = _scst_objective_args(objective == "risk", k, risk_alpha, entropy_weight)
+        with _on_stream(self):
+            return self._scst_training_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs, k, obj)
+
+
+def _scst_objective_args(risk, k, risk_alpha, entropy_weight):
+    """The objective arguments of an SCST epoch (risk: minimum-risk training, else the step's reward) -> None (today's calls: the
+    reward through RewardCriterion, no entropy term) or the scst_objective.Objective every step attaches its reward / scores to;
+    ValueError for a bad argument."""
+    from .scst_objective import make_objective
+    obj = make_objective("risk" if risk else "reinforce", k, risk_alpha, entropy_weight)
+    return None if not risk and obj.entropy_weight == 0.0 else obj
 
 
 class BUTDDetection_Eng(Engine):
@@ -492,10 +521,12 @@ class BUTDDetection_Eng(Engine):
     # keep refusing it there and run the multi-sample step through SCST_multisample_training_epoch, which serves all three
     _multi_sample = True
 
-    def SCST_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=None):
+    def SCST_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=None, entropy_weight=0.0):
         """samples_per_image (beyond the reference): None = the reference's step (one sampled caption per image, greedy baseline);
         K = 2..8 = the multi-sample variant: K sampled captions per image, each baselined by the mean CIDEr-D of the other K - 1,
-        no greedy rollout (BUTD decoders only)."""
+        no greedy rollout (BUTD decoders only).  entropy_weight > 0 (beyond the reference, both forms): the loss minus that multiple
+        of the mean per-step entropy of the word distribution (scst_objective.py); 0 runs today's calls exactly.  ValueError for a
+        bad argument before any device work."""
         if samples_per_image is not None:
             k = samples_per_image
             if not self._multi_sample:
@@ -505,10 +536,11 @@ class BUTDDetection_Eng(Engine):
             if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= int(k) <= 8:
                 raise ValueError("samples_per_image must be None or an integer in 2..8, got %r" % (k,))
             samples_per_image = int(k)
+        obj = _scst_objective_args(False, samples_per_image or 1, 1.0, entropy_weight)
         with _on_stream(self):
-            return self._scst_training_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs, samples_per_image)
+            return self._scst_training_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs, samples_per_image, obj)
 
-    def _scst_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=None):
+    def _scst_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=None, objective=None):
         """Engine.py:251-272: greedy baseline (eval mode) + multinomial rollout (train mode) + CIDEr-D reward +
         REINFORCE + clamp 0.25 + Adam, all on the device; `criterion` (RewardCriterion) is implied."""
         self.model.train()
@@ -521,7 +553,7 @@ class BUTDDetection_Eng(Engine):
         monitor = _monitor(dataloader, "Training Process", tqdm_visible)
         losses = []
         try:
-            self._scst_steps(monitor, scorer, optimizer, rngs, tqdm_visible, losses, samples_per_image)
+            self._scst_steps(monitor, scorer, optimizer, rngs, tqdm_visible, losses, samples_per_image, objective)
         finally:
             restore()
         return losses
@@ -542,7 +574,8 @@ class BUTDDetection_Eng(Engine):
             return {}
         return {n: sum(m[i].elapsed_time(m[i + 1]) for m in steps) / len(steps) for i, n in enumerate(names)}
 
-    def _scst_steps(self, monitor, scorer, optimizer, rngs, tqdm_visible, losses, samples_per_image=None):
+    def _scst_steps(self, monitor, scorer, optimizer, rngs, tqdm_visible, losses, samples_per_image=None, objective=None):
+        risk = objective is not None and objective.kind == "risk"
         for batch_i, (img_ids, img_tensors, img_gts, supp_info_datas) in enumerate(monitor):
             visual_inputs = self.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
             feats = self._features(visual_inputs)
@@ -557,7 +590,7 @@ class BUTDDetection_Eng(Engine):
             else:       # K sampled captions per image (rows img * K + k), each baselined by the mean reward of the other K - 1
                 seq_gen, seq_logprobs = sample_n(h, feats, samples_per_image, 20, rng)
                 self._mark(marks)
-                rewards = scorer.reward_loo(seq_gen, samples_per_image, img_gts, img_ids)
+                rewards = scorer.reward_loo(seq_gen, samples_per_image, img_gts, img_ids, return_scores=risk)
             self._mark(marks)
             grads = self._grads()
             msum_glob = 0.0
@@ -570,8 +603,19 @@ class BUTDDetection_Eng(Engine):
                     msum_glob = -1.0
                 else:
                     msum_glob = icz_dist.all_reduce_scalar(ms)
+            if risk:      # the objective divides by the image count of the whole step
+                step_obj = objective.with_data(scores=rewards[1], n_img_global=icz_dist.all_reduce_scalar(float(len(img_ids)))
+                                               if icz_dist.is_distributed() else 0.0)
+            elif objective is not None:
+                step_obj = objective.with_data(reward=rewards)
             ov = self._reduce_grads_begin(h)
-            loss, _ = h.sample_backward(rewards, grads, msum_glob)
+            if objective is None:
+                loss, _ = h.sample_backward(rewards, grads, msum_glob)
+            else:
+                loss3, _ = sample_backward_objective(h, step_obj, grads, msum_glob)
+                loss = loss3[0:1]
+                if self.scst_terms is not None:
+                    self.scst_terms.append((loss3[1:2].clone(), loss3[2:3].clone()))
             self._mark(marks)
             self._reduce_grads_end(ov)
             self._mark(marks)

@@ -16,7 +16,8 @@ from .scheduled import ScheduledSamplingState
 # the icz_<family>_<name> entries the shared methods call; a family lists the ones only it has in `_own_entries`
 _ENTRIES = ("create", "destroy", "bind_params", "refresh_weights", "set_option", "set_grad_callback", "set_scheduled_sampling",
             "set_norm_global", "greedy", "sample", "scst_rollouts", "sample_backward", "xe_forward", "xe_backward", "beam_search",
-            "beam_search_opts", "beam_search_diverse", "beam_search_constrained", "sample_decode", "sample_distinct", "score_captions", "xe_backward_distill")
+            "beam_search_opts", "beam_search_diverse", "beam_search_constrained", "sample_decode", "sample_distinct", "score_captions", "xe_backward_distill",
+            "sample_backward_objective")
 
 
 class DecoderHandle:
