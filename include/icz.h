@@ -1426,6 +1426,80 @@ typedef struct {
     const int32_t* live; const int32_t* carry_live;
 } icz_test_lstm_bwd_args;
 int icz_test_lstm_bwd_point(const icz_test_lstm_bwd_args* a, const icz_test_drop* drop, void* stream);
+/* Test entries for the kernels of the BUTD soft attention (csrc/butd_kernels.h), each on given operands
+ * (tests/test_gpu_butd_att_kernels.py): the library's kernel through the launch helper the decoders use (csrc/butd_impl.h) -- the same
+ * template instance, grid rule and dynamic LDS size.  All data pointers are DEVICE pointers.  Every entry checks its arguments on the
+ * host and returns ICZ_ERR_INVALID without launching otherwise; the device index arrays (counts [n_img], each 1..R; img_of_row [rows],
+ * each 0..n_img-1) are read back and checked too, for which the entry waits for the stream.
+ *
+ * Common to all: n_img images of R regions (1..128; R stays the row stride of every tensor); the <true> instances of the kernels are
+ * taken where counts are given or R > 64, as the handle takes them; widths (A, D) are positive multiples of 4 and the tensors read or
+ * written 16 bytes at a time are 16-byte aligned; img_of_row null = row r attends over image r (rows <= n_img); live: optional device
+ * int32, 0 = a dead step.  Dropout: icz_test_drop above (the keep index of element (row, r, a) is ((row - row0) R + r) A + a; keep
+ * flags 4-byte aligned).
+ *
+ * mean_feats_kernel, or mean_feats_counts_kernel where counts are given: mean[b, :] = sum_{r < c_b} feats[b, r, :] / c_b in row order. */
+int icz_test_att_mean(const float* feats, int32_t n_img, int32_t R, int32_t D, const int32_t* counts, float* mean, void* stream);
+/* The score kernels, every field of AttScoreArgs:
+ *   dec_ctx[row, :] = slab 0 + slab 1 + ... + slab nsplit-1 + b_dec (fp32, in that order; slabs rows A floats apart, nsplit in 1..32),
+ *   also written to dec_ctx_out (optional) [rows, A];
+ *   scores[row, r] = sum_a w_aff[a] drop(relu(enc_ctx[img, r, a] + dec_ctx[row, a])) + b_aff[0] for r < c_img, 0 behind it. */
+typedef struct {
+    const float* enc_ctx; int32_t n_img;     /* [n_img, R, A] */
+    const int32_t* img_of_row;
+    const float* dec_slab; int32_t nsplit;
+    const float* b_dec; const float* w_aff; const float* b_aff;
+    float* dec_ctx_out; float* scores;
+    int32_t rows, R, A;
+    const int32_t* live; const int32_t* counts;
+} icz_test_att_scores_args;
+/* route 0 = att_scores_kernel (G 0 or 1), 1 = att_scores_group_kernel (neither dropout nor live), 2 = att_scores_group_train_kernel.
+ * The grouped routes take rows = G rows of each of rows / G <= n_img images, G in 1..8 with G A floats within 60 KB of LDS, an
+ * img_of_row that says row / G or none, and row0 = 0.  parts: gridDim.y, 0 = ATT_PARTS. */
+int icz_test_att_scores(int32_t route, const icz_test_att_scores_args* a, const icz_test_drop* drop, int32_t G, int32_t parts, void* stream);
+/* att_ctx_kernel (G = 0) or att_ctx_group_kernel (G in 1..8, rows = G rows per image, no img_of_row but row / G, no alpha_out2):
+ * alpha[row, :] = softmax over the image's regions of scores[row, :] (0 behind the count), written to alpha_out [rows, R] and (optional)
+ * alpha_out2 with row stride alpha2_stride >= R; ctx[row, :] = sum_r alpha[row, r] feats[img, r, :]. */
+int icz_test_att_ctx(const float* feats, int32_t n_img, const int32_t* img_of_row, const float* scores, float* alpha_out, float* alpha_out2,
+                     int32_t alpha2_stride, float* ctx, int32_t rows, int32_t R, int32_t D, int32_t G, const int32_t* live, const int32_t* counts,
+                     void* stream);
+/* saved_alphas_kernel: src [T, B, NH, R] -> out [B, T, R], the fp32 mean over the NH heads added in head order. */
+int icz_test_att_saved_alphas(const float* src, int32_t T, int32_t B, int32_t NH, int32_t R, float* out, void* stream);
+/* att_bwd_dalpha_kernel: dctx = the sum of ns slabs (1..32) of rows rows of ldc floats (ldc >= D, a multiple of 4; columns 0..D);
+ * dalpha_part[row][p][r] = dctx[row, 512 p .. 512 p + 512] . feats[img, r, the same columns] for r < c_img, [rows][ceil(D / 512)][R];
+ * behind the count nothing is written. */
+int icz_test_att_bwd_dalpha(const float* dctx, int32_t ns, int32_t ldc, int32_t rows, const float* feats, int32_t n_img, int32_t R, int32_t D,
+                            float* dalpha_part, const int32_t* live, const int32_t* img_of_row, const int32_t* counts, void* stream);
+/* att_bwd_ddec_kernel, every field of AttBwdDdecArgs: dalpha[row, r] = the nparts parts of dalpha [rows][nparts][R] added in order,
+ * ds = alpha o (dalpha - alpha . dalpha) -> ds_out [rows, R] (0 behind the count); ddec[row, a] = sum_r on ds_r w_aff[a] (x 2 under
+ * dropout) with on = (enc_ctx[img, r, a] + dec_ctx[row, a] > 0 in fp32) and kept.  A dead step writes zero ddec and ds rows.  row0 = 0. */
+typedef struct {
+    const float* enc_ctx; int32_t n_img;
+    const float* dec_ctx; const float* w_aff; const float* alpha; const float* dalpha;
+    float* ddec; float* ds_out;
+    int32_t rows, R, A, nparts;
+    const int32_t* live; const int32_t* img_of_row; const int32_t* counts;
+} icz_test_att_ddec_args;
+int icz_test_att_bwd_ddec(const icz_test_att_ddec_args* a, const icz_test_drop* drop, void* stream);
+/* att_bwd_denc_kernel (G = 0) or att_bwd_denc_group_kernel (G >= 1: B = G rows of each of B / G <= n_img images, no img_of_row), every
+ * field of AttBwdDencArgs: dec_all [T][Bs][A] and ds_all [T][Bs][R] (Bs 0 = B, else >= B rows per step of which the first B are taken:
+ * pass the pointers at the row offset); on_t = (enc_ctx[img, r, a] + dec_all[t, row, a] > 0 in fp32) and kept, the keep flag of step t
+ * from mask + t mask_step (mode 1; mask_step a multiple of 4, at least B R A) or Philox step t of `stream` (mode 2), index (row R + r) A + a;
+ *   denc[row, r, a] = sum_t on_t ds_t[row, r] w_aff[a] (x 2 under dropout), rows behind the count zeros; grouped: the G rows of an
+ *   image added in k order into denc[img];
+ *   dwaff_part[row, p, a] = sum over the regions r = p mod parts and t of on_t (enc_ctx + dec_all) ds_t (x 2), [B or B / G][parts][A].
+ * parts: gridDim.y, 0 = the library's rule (ATT_PARTS; grouped: as many parts of 16 regions as cover R, at least ATT_PARTS); a grouped
+ * launch whose parts do not cover R is refused.  *parts_out (optional, host): the parts launched.  T R floats fit 60 KB of LDS. */
+typedef struct {
+    const float* enc_ctx; int32_t n_img;
+    const float* dec_all; const float* ds_all; const float* w_aff;
+    float* denc; float* dwaff_part;
+    int32_t B, R, A, T;
+    int32_t mode; const uint8_t* mask; int64_t mask_step; const uint64_t* seed; uint32_t stream;
+    int32_t Bs;
+    const int32_t* img_of_row; const int32_t* counts;
+} icz_test_att_denc_args;
+int icz_test_att_bwd_denc(const icz_test_att_denc_args* a, int32_t G, int32_t parts, int32_t* parts_out, void* stream);
 /* Live timing of the dominant kernel (the forward GEMMs of a decoder step at 33..64 rows: gemm_resident_x3_kernel, or
  * gemm_nt_kernel<4, ...> with ICZ_GEMM_RESIDENT_X3=0; see icz_prof_select) with HIP events on its launch stream, for bench.py's
  * roofline line.  Between begin and end every launch is bracketed by an event

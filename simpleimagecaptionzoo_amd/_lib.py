@@ -189,6 +189,34 @@ class LstmBwdArgs(C.Structure):    # icz_test_lstm_bwd_args
                 ("live", C.c_void_p), ("carry_live", C.c_void_p)]
 
 
+ATT_SCORES_POINTERS = ("enc_ctx", "img_of_row", "dec_slab", "b_dec", "w_aff", "b_aff", "dec_ctx_out", "scores", "live", "counts")
+
+
+class AttScoresArgs(C.Structure):  # icz_test_att_scores_args
+    _fields_ = [("enc_ctx", C.c_void_p), ("n_img", C.c_int32), ("img_of_row", C.c_void_p), ("dec_slab", C.c_void_p), ("nsplit", C.c_int32),
+                ("b_dec", C.c_void_p), ("w_aff", C.c_void_p), ("b_aff", C.c_void_p), ("dec_ctx_out", C.c_void_p), ("scores", C.c_void_p),
+                ("rows", C.c_int32), ("R", C.c_int32), ("A", C.c_int32), ("live", C.c_void_p), ("counts", C.c_void_p)]
+
+
+ATT_DDEC_POINTERS = ("enc_ctx", "dec_ctx", "w_aff", "alpha", "dalpha", "ddec", "ds_out", "live", "img_of_row", "counts")
+
+
+class AttDdecArgs(C.Structure):    # icz_test_att_ddec_args
+    _fields_ = [("enc_ctx", C.c_void_p), ("n_img", C.c_int32), ("dec_ctx", C.c_void_p), ("w_aff", C.c_void_p), ("alpha", C.c_void_p),
+                ("dalpha", C.c_void_p), ("ddec", C.c_void_p), ("ds_out", C.c_void_p), ("rows", C.c_int32), ("R", C.c_int32), ("A", C.c_int32),
+                ("nparts", C.c_int32), ("live", C.c_void_p), ("img_of_row", C.c_void_p), ("counts", C.c_void_p)]
+
+
+ATT_DENC_POINTERS = ("enc_ctx", "dec_all", "ds_all", "w_aff", "denc", "dwaff_part", "mask", "seed", "img_of_row", "counts")
+
+
+class AttDencArgs(C.Structure):    # icz_test_att_denc_args
+    _fields_ = [("enc_ctx", C.c_void_p), ("n_img", C.c_int32), ("dec_all", C.c_void_p), ("ds_all", C.c_void_p), ("w_aff", C.c_void_p),
+                ("denc", C.c_void_p), ("dwaff_part", C.c_void_p), ("B", C.c_int32), ("R", C.c_int32), ("A", C.c_int32), ("T", C.c_int32),
+                ("mode", C.c_int32), ("mask", C.c_void_p), ("mask_step", C.c_int64), ("seed", C.c_void_p), ("stream", C.c_uint32),
+                ("Bs", C.c_int32), ("img_of_row", C.c_void_p), ("counts", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -393,6 +421,13 @@ def lib():
         "icz_test_embed_steps": (C.c_int, [vp, i32, i32, vp, i32, i32, C.POINTER(i32), vp, C.POINTER(DropArgs), vp]),
         "icz_test_lstm_point": (C.c_int, [i32, C.POINTER(LstmPointArgs), C.POINTER(DropArgs), C.POINTER(i32), vp]),
         "icz_test_lstm_bwd_point": (C.c_int, [C.POINTER(LstmBwdArgs), C.POINTER(DropArgs), vp]),
+        "icz_test_att_mean": (C.c_int, [vp, i32, i32, i32, vp, vp, vp]),
+        "icz_test_att_scores": (C.c_int, [i32, C.POINTER(AttScoresArgs), C.POINTER(DropArgs), i32, i32, vp]),
+        "icz_test_att_ctx": (C.c_int, [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "icz_test_att_saved_alphas": (C.c_int, [vp, i32, i32, i32, i32, vp, vp]),
+        "icz_test_att_bwd_dalpha": (C.c_int, [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "icz_test_att_bwd_ddec": (C.c_int, [C.POINTER(AttDdecArgs), C.POINTER(DropArgs), vp]),
+        "icz_test_att_bwd_denc": (C.c_int, [C.POINTER(AttDencArgs), i32, i32, C.POINTER(i32), vp]),
     }
     for name, (res, args) in sig.items():
         try:

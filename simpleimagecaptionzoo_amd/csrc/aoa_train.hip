@@ -868,8 +868,7 @@ int icz_aoa_saved_alphas(icz_aoa_t* h, float* alphas_out, void* stream) {
     ICZ_REQUIRE(h && alphas_out, "icz_aoa_saved_alphas: null argument");
     Aoa* a = reinterpret_cast<Aoa*>(h);
     ICZ_REQUIRE(a->mode != 0 && a->tP, "icz_aoa_saved_alphas: no forward pass stored");
-    const int n = a->cur_B * a->cur_T * a->cur_R;
-    hipLaunchKernelGGL(saved_alphas_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, a->tP, a->cur_T, a->cur_B, a->dims.NH, a->cur_R, alphas_out);
+    launch_saved_alphas(a->tP, a->cur_T, a->cur_B, a->dims.NH, a->cur_R, alphas_out, (hipStream_t)stream);
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }

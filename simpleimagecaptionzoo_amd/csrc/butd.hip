@@ -125,8 +125,7 @@ int Butd::prologue(const float* feats, int n_img, hipStream_t st) {
     ICZ_REQUIRE(fresh, "butd: call icz_butd_refresh_weights after binding/updating parameters");
     ICZ_REQUIRE(n_img > 0 && n_img <= dims.max_rows, "butd: %d images exceed capacity %d", n_img, dims.max_rows);
     ICZ_TRY(check_counts(n_img));
-    if (cnt) hipLaunchKernelGGL(mean_feats_counts_kernel, dim3(cdiv(D, 1024), n_img), dim3(256), 0, st, feats, mean, R, D, cnt);
-    else hipLaunchKernelGGL(mean_feats_kernel, dim3(cdiv(D, 1024), n_img), dim3(256), 0, st, feats, mean, R, D);
+    launch_mean_feats(feats, mean, n_img, R, D, cnt, st);
     {   // premean = mean . W_ih[:, H:H+D]^T   [n_img, 4H]
         GemmArgs g = gemm_args({{mean, P.td_w_ih + H, D, H + D + E, D}}, n_img, 4 * H, premean, 4 * H);
         ICZ_TRY(gemm_nt(g, nullptr, st));
@@ -176,23 +175,13 @@ int Butd::step(const StepIO& s, hipStream_t st) {
         const int G = s.rows_per_img;
         // compare the accumulation order: the per-row kernel sums a region row in the lane order of three regions at a time, the
         // grouped one region by region -- identical per (row, region): a wave's lanes cover the same columns in the same order
-        const bool grouped = G > 1 && G <= ATT_CTX_MAX_G && rows % G == 0 && sizeof(float) * A * G <= 60 * 1024;
+        const bool grouped = G > 1 && att_scores_group_fits(rows, G, A);
         // (the <true> instances: per-image counts or more than 64 regions, Butd::adaptive)
-        if (grouped && s.drop_att.mode == 0 && !s.live)          // beam search
-            hipLaunchKernelGGL(ad ? att_scores_group_kernel<true> : att_scores_group_kernel<false>, dim3(rows / G, ATT_PARTS), dim3(256),
-                               sizeof(float) * A * G, st, a, G);
-        else if (grouped)                                        // the multi-sample rollout (sample_n): dropout per row, early-out
-            hipLaunchKernelGGL(ad ? att_scores_group_train_kernel<true> : att_scores_group_train_kernel<false>, dim3(rows / G, ATT_PARTS), dim3(256),
-                               sizeof(float) * A * G, st, a, s.drop_att, G);
-        else
-            hipLaunchKernelGGL(ad ? att_scores_kernel<true> : att_scores_kernel<false>, dim3(rows, ATT_PARTS), dim3(256), sizeof(float) * A, st, a, s.drop_att);
-        if (G > 1 && G <= ATT_CTX_MAX_G && rows % G == 0 && !s.alpha_out2)
-            hipLaunchKernelGGL(ad ? att_ctx_group_kernel<true> : att_ctx_group_kernel<false>, dim3(rows / G, cdiv(D, 512)), dim3(256), 0, st, s.feats,
-                               (const float*)scores, s.alpha_out ? s.alpha_out : alpha, s.ctx_out ? s.ctx_out : ctx, R, D, G, s.live, cnt);
-        else
-            hipLaunchKernelGGL(ad ? att_ctx_kernel<true> : att_ctx_kernel<false>, dim3(rows, cdiv(D, 512)), dim3(256), 0, st, s.feats, s.img_of_row,
-                               (const float*)scores, s.alpha_out ? s.alpha_out : alpha, s.alpha_out2, s.alpha2_stride, s.ctx_out ? s.ctx_out : ctx, R, D,
-                               s.live, cnt);
+        // grouped without dropout and early-out: beam search; grouped with them: the multi-sample rollout (sample_n)
+        launch_att_scores(!grouped ? ATT_PER_ROW : (s.drop_att.mode == 0 && !s.live ? ATT_GROUP : ATT_GROUP_TRAIN), ad, a, s.drop_att, G, ATT_PARTS, st);
+        const bool ctx_grouped = G > 1 && G <= ATT_CTX_MAX_G && rows % G == 0 && !s.alpha_out2;
+        launch_att_ctx(ad, s.feats, s.img_of_row, scores, s.alpha_out ? s.alpha_out : alpha, s.alpha_out2, s.alpha2_stride, s.ctx_out ? s.ctx_out : ctx,
+                       rows, R, D, ctx_grouped ? G : 0, s.live, cnt, st);
         kprof_mark(KP_ATTENTION, false, st);
     }
     const float* ctxp = s.ctx_out ? s.ctx_out : ctx;

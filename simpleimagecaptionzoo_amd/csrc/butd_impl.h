@@ -3,6 +3,7 @@
 #include <vector>
 #include <stdint.h>
 
+#include "butd_kernels.h"
 #include "decoder_core.h"
 #include "rng.h"
 
@@ -199,5 +200,62 @@ struct Butd : CaptionHead, DecodeMember {
     int bptt_lm_wgrad(BpttCall& c);             // bit 2: LM-LSTM weight gradients
     int bptt_attention_tail(BpttCall& c);       // bit 3: attention block, bias sums, weight-norm backward
 };
+
+// ---------------------------------------------------------------------------------------------------------
+// The launches of the attention kernels (butd_kernels.h): template instance, grid and dynamic LDS size of each, in one place.  Butd::step,
+// the BPTT and the kernel-alone test entries (butd_att_test_entries.hip, tests/test_gpu_butd_att_kernels.py) all launch through these,
+// so what the tests run is what the decoders run.  `ad`: the <true> instances (Butd::adaptive()).  `parts`: Butd::ATT_PARTS in the decoders.
+inline void launch_mean_feats(const float* feats, float* mean, int n_img, int R, int D, const int32_t* counts, hipStream_t st) {
+    if (counts) hipLaunchKernelGGL(mean_feats_counts_kernel, dim3(cdiv(D, 1024), n_img), dim3(256), 0, st, feats, mean, R, D, counts);
+    else hipLaunchKernelGGL(mean_feats_kernel, dim3(cdiv(D, 1024), n_img), dim3(256), 0, st, feats, mean, R, D);
+}
+enum AttRoute { ATT_PER_ROW = 0, ATT_GROUP = 1, ATT_GROUP_TRAIN = 2 };
+constexpr size_t ATT_GROUP_LDS = 60 * 1024;      // the G dec_ctx rows of a grouped score kernel
+// what a grouped score launch needs of its shape (Butd::step asks G > 1 besides: one row per image is the per-row kernel's)
+inline bool att_scores_group_fits(int rows, int G, int A) {
+    return G >= 1 && G <= ATT_CTX_MAX_G && rows % G == 0 && sizeof(float) * A * G <= ATT_GROUP_LDS;
+}
+inline void launch_att_scores(AttRoute route, bool ad, const AttScoreArgs& a, const DropCfg& dc, int G, int parts, hipStream_t st) {
+    if (route == ATT_GROUP)                   // beam search
+        hipLaunchKernelGGL(ad ? att_scores_group_kernel<true> : att_scores_group_kernel<false>, dim3(a.rows / G, parts), dim3(256),
+                           sizeof(float) * a.A * G, st, a, G);
+    else if (route == ATT_GROUP_TRAIN)        // the multi-sample rollout (sample_n): dropout per row, early-out
+        hipLaunchKernelGGL(ad ? att_scores_group_train_kernel<true> : att_scores_group_train_kernel<false>, dim3(a.rows / G, parts), dim3(256),
+                           sizeof(float) * a.A * G, st, a, dc, G);
+    else
+        hipLaunchKernelGGL(ad ? att_scores_kernel<true> : att_scores_kernel<false>, dim3(a.rows, parts), dim3(256), sizeof(float) * a.A, st, a, dc);
+}
+// G > 0: the grouped kernel (rows = n_img G, img_of_row and alpha_out2 are not taken); G = 0: the per-row kernel
+inline void launch_att_ctx(bool ad, const float* feats, const int32_t* img_of_row, const float* scores, float* alpha_out, float* alpha_out2,
+                           int alpha2_stride, float* ctx, int rows, int R, int D, int G, const int* live, const int32_t* counts, hipStream_t st) {
+    if (G > 0)
+        hipLaunchKernelGGL(ad ? att_ctx_group_kernel<true> : att_ctx_group_kernel<false>, dim3(rows / G, cdiv(D, 512)), dim3(256), 0, st, feats, scores,
+                           alpha_out, ctx, R, D, G, live, counts);
+    else
+        hipLaunchKernelGGL(ad ? att_ctx_kernel<true> : att_ctx_kernel<false>, dim3(rows, cdiv(D, 512)), dim3(256), 0, st, feats, img_of_row, scores,
+                           alpha_out, alpha_out2, alpha2_stride, ctx, R, D, live, counts);
+}
+inline int att_dalpha_parts(int D) { return cdiv(D, DALPHA_COLS); }
+// dalpha_part: [rows][att_dalpha_parts(D)][R]
+inline void launch_att_bwd_dalpha(bool ad, const float* dctx, int ns, int ldc, int rows, const float* feats, int R, int D, float* dalpha_part,
+                                  const int* live, const int32_t* img_of_row, const int32_t* counts, hipStream_t st) {
+    hipLaunchKernelGGL(ad ? att_bwd_dalpha_kernel<true> : att_bwd_dalpha_kernel<false>, dim3(rows, att_dalpha_parts(D)), dim3(256), 0, st, dctx, ns, ldc,
+                       rows, feats, R, D, dalpha_part, live, img_of_row, counts);
+}
+inline void launch_att_bwd_ddec(bool ad, const AttBwdDdecArgs& a, const DropCfg& dc, int rows, hipStream_t st) {
+    hipLaunchKernelGGL(ad ? att_bwd_ddec_kernel<true> : att_bwd_ddec_kernel<false>, dim3(rows, cdiv(a.A, 256)), dim3(256), 0, st, a, dc);
+}
+constexpr int ATT_DENC_TT = 20;                  // time steps of dec_ctx a d enc_ctx thread keeps in registers
+// parts of the grouped d enc_ctx kernel: DENC_GROUP_REGS regions each (more than `parts` only above parts * DENC_GROUP_REGS regions)
+inline int att_denc_group_parts(int R, int parts) { return parts * DENC_GROUP_REGS >= R ? parts : cdiv(R, DENC_GROUP_REGS); }
+// G > 0: the grouped kernel over the n_img images of a.B = n_img G rows with `parts` = att_denc_group_parts(...); G = 0: the per-row kernel over a.B rows
+inline void launch_att_bwd_denc(bool ad, const AttBwdDencArgs& a, int n_img, int G, int parts, hipStream_t st) {
+    if (G > 0)
+        hipLaunchKernelGGL((ad ? att_bwd_denc_group_kernel<ATT_DENC_TT, true> : att_bwd_denc_group_kernel<ATT_DENC_TT, false>), dim3(n_img, parts),
+                           dim3(256), sizeof(float) * a.T * a.R, st, a, G);
+    else
+        hipLaunchKernelGGL((ad ? att_bwd_denc_kernel<ATT_DENC_TT, true> : att_bwd_denc_kernel<ATT_DENC_TT, false>), dim3(a.B, parts), dim3(256),
+                           sizeof(float) * a.T * a.R, st, a);
+}
 
 }  // namespace icz

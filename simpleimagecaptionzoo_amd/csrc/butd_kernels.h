@@ -1,6 +1,10 @@
 // Device kernels of the BUTD soft attention: the mean over regions, attention scores, softmax and context (per row and grouped
 // per image), their backward kernels and the saved attention maps.  HBM-bound byte movers: coalesced 16-byte accesses, wave-shuffle
 // reductions, no atomics (bitwise reproducible).  Reference line numbers: Models/BUTD_Model.py.
+// Every kernel here is launched through a helper of butd_impl.h (saved_alphas: below) and tested alone on given operands through the
+// icz_test_att_* entries (butd_att_test_entries.hip): tests/test_gpu_butd_att_kernels.py holds each to a float64 reference under an
+// a-priori rounding bound, and the promises made in the comments below -- no load outside the operands, nothing read or written behind
+// an image's count, <true> = <false> at R = c, grouped = per row -- to bits.
 #pragma once
 #include "icz_common.h"
 #include "rng.h"
@@ -435,6 +439,9 @@ __global__ void saved_alphas_kernel(const float* __restrict__ src, int T, int B,
     float s = 0.f;
     for (int h = 0; h < NH; ++h) s += p[(size_t)h * R];
     out[i] = s / (float)NH;
+}
+inline void launch_saved_alphas(const float* src, int T, int B, int NH, int R, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(saved_alphas_kernel, dim3(cdiv(B * T * R, 256)), dim3(256), 0, st, src, T, B, NH, R, out);
 }
 
 // ---------------------------------------------------------------------------------------------------------

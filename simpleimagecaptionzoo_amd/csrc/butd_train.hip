@@ -674,11 +674,10 @@ int Butd::bptt_loop(BpttCall& c) {
         // X1 = dG_lm . W_ih_lm   [bt, D+H]
         ICZ_TRY(dgrad(gemm_args({wseg(dglm, wt_lm_ih, P.lm_w_ih, D + H)}, bt, D + H, tb.X[0], D + H, live), tb.X[0], &ns1));
         {   // attention backward
-            const int dparts = cdiv(D, DALPHA_COLS);
-            hipLaunchKernelGGL(ad ? att_bwd_dalpha_kernel<true> : att_bwd_dalpha_kernel<false>, dim3(bt, dparts), dim3(256), 0, st, tb.X[0], ns1, D + H, bt,
-                               feats, R, D, tb.dalpha, live, imgk, cnt);
+            const int dparts = att_dalpha_parts(D);
+            launch_att_bwd_dalpha(ad, tb.X[0], ns1, D + H, bt, feats, R, D, tb.dalpha, live, imgk, cnt, st);
             AttBwdDdecArgs da = {enc_ctx, tb.dec + slot * A, w_aff, tb.alpha + slot * R, tb.dalpha, tb.dDec + slot * A, tb.dS + slot * R, R, A, dparts, live, imgk, cnt};
-            hipLaunchKernelGGL(ad ? att_bwd_ddec_kernel<true> : att_bwd_ddec_kernel<false>, dim3(bt, cdiv(A, 256)), dim3(256), 0, st, da, d_att);
+            launch_att_bwd_ddec(ad, da, d_att, bt, st);
             // X2 = dDec . w_dec   [bt, H] (the fused route forms it inside the TD-LSTM launch below: tb.X[1] is not written then, and
             // nothing else reads it)
             if (!fdh) {
@@ -777,7 +776,7 @@ int Butd::bptt_attention_tail(BpttCall& c) {
     const bool ad = adaptive();
     // parts of the grouped d enc_ctx kernel: DENC_GROUP_REGS regions each (more than ATT_PARTS only above 64 regions; n_img <= B / 2
     // images there, so tb.dwaff's B x ATT_PARTS blocks still hold them)
-    const int gparts = ATT_PARTS * DENC_GROUP_REGS >= R ? ATT_PARTS : cdiv(R, DENC_GROUP_REGS);
+    const int gparts = att_denc_group_parts(R, ATT_PARTS);
     const size_t sH = (size_t)Bs * H;
     const icz_butd_params& G = c.G;
     const float* const feats = cur_feats;
@@ -789,10 +788,9 @@ int Butd::bptt_attention_tail(BpttCall& c) {
                              cur_train ? (rng.att_mask ? 1 : 2) : 0, rng.att_mask, (size_t)B * R * A, d_seed, (uint32_t)RNG_ATT, Bs, imgk, cnt};
         if (K > 1 && group_att) {       // sample_n, grouped: the K rows of an image in one workgroup, summed into d enc_ctx[img]
             ea.denc = tb.dEncImg;
-            hipLaunchKernelGGL((ad ? att_bwd_denc_group_kernel<20, true> : att_bwd_denc_group_kernel<20, false>), dim3(n_img, gparts), dim3(256),
-                               sizeof(float) * T * R, st, ea, K);
+            launch_att_bwd_denc(ad, ea, n_img, K, gparts, st);
         } else {
-            hipLaunchKernelGGL((ad ? att_bwd_denc_kernel<20, true> : att_bwd_denc_kernel<20, false>), dim3(B, ATT_PARTS), dim3(256), sizeof(float) * T * R, st, ea);
+            launch_att_bwd_denc(ad, ea, B, 0, ATT_PARTS, st);
             if (K > 1) {                // sample_n, per row: d enc_ctx of the B K rows, then the K rows of an image added in k order
                 const size_t N = (size_t)R * A;
                 launch_rowgroup_sum(tb.dEnc, n_img, K, N, tb.dEncImg, st);
@@ -884,8 +882,7 @@ int icz_butd_saved_alphas(icz_butd_t* h, float* alphas_out, void* stream) {
     Butd* b = reinterpret_cast<Butd*>(h);
     ICZ_REQUIRE(b->mode != 0 && b->tb.alpha, "icz_butd_saved_alphas: no forward pass stored");
     ICZ_REQUIRE(b->cur_row0 == 0, "icz_butd_saved_alphas: not available behind a merged SCST rollout (set option merge_small = 0)");
-    const int n = b->cur_B * b->cur_T * b->cur_R;
-    hipLaunchKernelGGL(saved_alphas_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, b->tb.alpha, b->cur_T, b->cur_B, 1, b->cur_R, alphas_out);
+    launch_saved_alphas(b->tb.alpha, b->cur_T, b->cur_B, 1, b->cur_R, alphas_out, (hipStream_t)stream);
     ICZ_CHECK_HIP(hipGetLastError());
     return ICZ_OK;
 }
