@@ -22,6 +22,7 @@ from .sampling import make_sample_opts
 from .multisample import sample_n
 from .scst_objective import sample_backward_objective
 from .captioner import BUTDDetection_Captioner
+from .handle import CaptionerBase
 from .ciderd import CiderDReward
 from . import dist as icz_dist
 from .features import wait_event
@@ -438,20 +439,28 @@ class BUTDDetection_Eng(Engine):
     def _training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None):
         """Engine.py:169-188.  `criterion` is the reference's LabelSmoothingLoss (only its .smoothing is read: the
         loss and its gradient are fused into the backward kernels).  `rngs` (tests) supplies one icz_rng per batch."""
+        return self._xe_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs, "Training Process",
+                              lambda *batch: lambda h, grads, smoothing, n_glob: h.xe_backward(grads, smoothing, n_glob))
+
+    def _xe_epoch(self, dataloader, optimizer, criterion, tqdm_visible, rngs, desc, begin):
+        """The XE epoch of _training_epoch and _distill_training_epoch.  What varies is the backward call: begin(img_tensors,
+        supp_info_datas, captions, lengths) runs in front of the student's forward pass and returns backward(h, grads, smoothing,
+        n_glob) -> loss."""
         self.model.train()
         smoothing = float(getattr(criterion, "smoothing", 0.0))
-        monitor = _monitor(dataloader, "Training Process", tqdm_visible)
+        monitor = _monitor(dataloader, desc, tqdm_visible)
         losses = []
         for batch_i, (img_ids, img_tensors, captions, lengths, supp_info_datas) in enumerate(monitor):
             visual_inputs = self.modify_visual_inputs(img_tensors, supp_info_datas)
             lengths = [cap_len - 1 for cap_len in lengths]
+            backward = begin(img_tensors, supp_info_datas, captions, lengths)
             h = self.model._handle()
             rng = rngs[batch_i] if rngs is not None else self.model._next_rng()
             h.xe_forward(self._features(visual_inputs), captions, lengths, rng, train=True)
             grads = self._grads()
             n_glob = self._xe_token_norm(h, lengths)
             ov = self._reduce_grads_begin(h)
-            loss = h.xe_backward(grads, smoothing, n_glob)
+            loss = backward(h, grads, smoothing, n_glob)
             self._reduce_grads_end(ov)
             self._apply(optimizer, 0.1)
             losses.append(loss)
@@ -488,33 +497,22 @@ class BUTDDetection_Eng(Engine):
             return self._distill_training_epoch(dataloader, optimizer, criterion, teachers, tqdm_visible, rngs, alpha, temperature, weights)
 
     def _distill_training_epoch(self, dataloader, optimizer, criterion, teachers, tqdm_visible, rngs, alpha, temperature, weights):
-        """_training_epoch with the teachers' forward passes in front of the backward call and xe_backward_distill in its place"""
+        """_training_epoch with the teachers' forward passes in front of the student's and xe_backward_distill as the backward call"""
         from .distill import teacher_logits, xe_backward_distill
-        self.model.train()
         for e in teachers:
             e.model.eval()
-        smoothing = float(getattr(criterion, "smoothing", 0.0))
-        monitor = _monitor(dataloader, "Distillation Process", tqdm_visible)
-        losses, self.last_distill_terms = [], []
-        for batch_i, (img_ids, img_tensors, captions, lengths, supp_info_datas) in enumerate(monitor):
-            visual_inputs = self.modify_visual_inputs(img_tensors, supp_info_datas)
-            lengths = [cap_len - 1 for cap_len in lengths]
+        self.last_distill_terms = []
+
+        def begin(img_tensors, supp_info_datas, captions, lengths):
             t_feats = [e._features(e.modify_visual_inputs(img_tensors, supp_info_datas)) for e in teachers]
             t_logits = teacher_logits([e.model._handle() for e in teachers], t_feats, captions, lengths)
-            h = self.model._handle()
-            rng = rngs[batch_i] if rngs is not None else self.model._next_rng()
-            h.xe_forward(self._features(visual_inputs), captions, lengths, rng, train=True)
-            grads = self._grads()
-            n_glob = self._xe_token_norm(h, lengths)
-            ov = self._reduce_grads_begin(h)
-            loss, hard, kd = xe_backward_distill(h, grads, t_logits, weights, alpha, temperature, smoothing, n_glob)
-            self._reduce_grads_end(ov)
-            self._apply(optimizer, 0.1)
-            losses.append(loss)
-            self.last_distill_terms.append((hard, kd))
-            if tqdm_visible:
-                monitor.set_postfix(Loss=np.round(loss.item(), decimals=4))
-        return losses
+
+            def backward(h, grads, smoothing, n_glob):
+                loss, hard, kd = xe_backward_distill(h, grads, t_logits, weights, alpha, temperature, smoothing, n_glob)
+                self.last_distill_terms.append((hard, kd))
+                return loss
+            return backward
+        return self._xe_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs, "Distillation Process", begin)
 
     # ---- E2 -------------------------------------------------------------------------------------------------
     # decoders whose SCST_training_epoch takes samples_per_image (BUTD, where the argument was introduced); the AoA and NIC engines
@@ -634,65 +632,8 @@ class BUTDDetection_Eng(Engine):
         a length-penalised score (None, ('avg' | 'wu', alpha), 'avg_<alpha>', 'wu_<alpha>') and forbid repeated n-grams.
         beam_groups / diversity (beam search only; icz_beam_diversity): diverse beam search with eval_beam_size / beam_groups
         beams per group; the JSON holds each image's rank-0 hypothesis."""
-        opts = None
-        diverse = isinstance(beam_groups, bool) or isinstance(diversity, bool) or beam_groups != 1 or diversity != 0.0
-        if length_penalty is not None or block_ngram or diverse:
-            if eval_beam_size == -1:
-                raise ValueError("length_penalty / block_ngram / beam_groups / diversity need beam search (eval_beam_size != -1)")
-            parse_length_penalty(length_penalty)          # a bad penalty raises here, before any device work
-            if int(block_ngram) not in (0, 2, 3, 4):
-                raise ValueError("block_ngram %d not 0, 2, 3 or 4" % int(block_ngram))
-            make_diversity(beam_groups, diversity, eval_beam_size)      # groups not dividing the beam, bad diversity
-            opts = (length_penalty, int(block_ngram), int(beam_groups), float(diversity))
-        with _on_stream(self):
-            return self._eval_captions_json_generation(dataloader, eval_beam_size, tqdm_visible, opts)
-
-    def _eval_captions_json_generation(self, dataloader, eval_beam_size=-1, tqdm_visible=True, opts=None):
-        """Engine.py:274-300.  Beam search accepts any batch size here (the reference's loader uses 1).
-        Data-parallel (torch.distributed initialised): rank r decodes the batches i with i % world == r (and
-        loads only those where the loader allows, _rank_batches); the (image id, token ids) rows are all-gathered and every rank returns the
-        complete list in loader order -- what the corpus-level scorer after it (COCO_Eval_Utils.py:15-35) needs in one
-        place; rank 0 is the one that should write / score it."""
-        self.model.eval()
-        print("Generating captions json for evaluation. Beam Search: %s" % (eval_beam_size != -1))
-        dp = icz_dist.is_distributed()
-        rank, world = icz_dist.rank(), icz_dist.world_size()
-        # data-parallel: this rank's batches only.  An indexable loader (list, Dataset-like: __len__ + __getitem__) or one with a
-        # shard(rank, world) method is never asked for the other ranks' batches (no feature I/O for them); any other iterable is
-        # walked in full and the foreign batches dropped
-        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Generating Process", tqdm_visible)
-        ids_out, rows_out, keys_out = [], [], []
-        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
-            nb = len(image_ids)
-            visual_inputs = self.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
-            h = self._hot_handle()
-            if eval_beam_size != -1 and opts is not None:
-                seqs, lens, _ = h.beam_search_opts(self._features(visual_inputs), eval_beam_size, 50, 1, *opts)
-                seqs, lens = seqs[:, 0].cpu().numpy(), lens[:, 0].cpu().numpy()
-                rows = [seqs[i, :lens[i]] for i in range(len(lens))]
-            elif eval_beam_size != -1:
-                seqs, lens = h.beam_search(self._features(visual_inputs), eval_beam_size, 50)
-                seqs, lens = seqs.cpu().numpy(), lens.cpu().numpy()
-                rows = [seqs[i, :lens[i]] for i in range(len(lens))]
-            else:
-                rows = list(h.greedy(self._features(visual_inputs), 20).cpu().numpy())
-            ids_out += [int(i) for i in image_ids]
-            rows_out += rows
-            keys_out += [(batch_i << 20) + j for j in range(nb)]      # loader order: batch index, then row
-        if dp:
-            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, self.device)
-        result = []
-        ix2word = self.caption_vocab.ix2word
-        for image_id, sampled_ids in zip(ids_out, rows_out):
-            sampled_caption = []
-            for word_id in sampled_ids:
-                word = ix2word[int(word_id)]
-                if word == "<end>":
-                    break
-                elif word != "<sta>":
-                    sampled_caption.append(word)
-            result.append({"image_id": image_id, "caption": " ".join(sampled_caption)})
-        return result
+        opts = _check_beam_opts(eval_beam_size, length_penalty, block_ngram, beam_groups, diversity, False)
+        return _eval_captions([self], None, False, dataloader, eval_beam_size, tqdm_visible, opts)
 
     def constrained_captions_json_generation(self, dataloader, constraints, eval_beam_size=3, tqdm_visible=True, *, length_penalty=None,
                                              block_ngram=0):
@@ -715,44 +656,8 @@ class BUTDDetection_Eng(Engine):
         samples_per_image per image in loader order; score = the model's summed log-probability of the caption's tokens.  Batch i
         of the loader draws from Philox seed `seed * 2**20 + i`: one seed gives the same captions run to run.  Sharded over the
         ranks and gathered as eval_captions_json_generation does.  Bad arguments raise ValueError before any device work."""
-        make_sample_opts(temperature, top_k, top_p, samples_per_image)
-        if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
-            raise ValueError("seed %r is not a non-negative integer" % (seed,))
-        if top_k > len(self.caption_vocab):
-            raise ValueError("top_k %d above the vocabulary size %d" % (top_k, len(self.caption_vocab)))
-        with _on_stream(self):
-            return self._sample_captions_json_generation(dataloader, int(samples_per_image), temperature, top_k, top_p, seed, tqdm_visible)
-
-    def _sample_captions_json_generation(self, dataloader, n, temperature, top_k, top_p, seed, tqdm_visible):
-        self.model.eval()
-        dp = icz_dist.is_distributed()
-        rank, world = icz_dist.rank(), icz_dist.world_size()
-        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Sampling Process", tqdm_visible)
-        ids_out, rows_out, keys_out = [], [], []
-        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
-            visual_inputs = self.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
-            h = self._hot_handle()
-            ids, _, score = h.sample_decode(self._features(visual_inputs), n, 20, temperature, top_k, top_p, (seed << 20) + batch_i)
-            ids, bits = ids.cpu().numpy(), score.cpu().numpy().view(np.uint32)
-            for r in range(ids.shape[0]):
-                ids_out.append(int(image_ids[r // n]))
-                rows_out.append(np.concatenate([ids[r], [int(bits[r])]]))      # the score travels as its bit pattern (non-negative)
-                keys_out.append((batch_i << 20) + r)                           # loader order: batch index, then image, then sample
-        if dp:
-            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, self.device)
-        result = []
-        ix2word = self.caption_vocab.ix2word
-        for image_id, row in zip(ids_out, rows_out):
-            words = []
-            for word_id in row[:-1]:
-                word = ix2word[int(word_id)]
-                if word == "<end>" or int(word_id) == 0:
-                    break
-                elif word != "<sta>":
-                    words.append(word)
-            score = float(np.array([int(row[-1])], dtype=np.uint32).view(np.float32)[0])
-            result.append({"image_id": image_id, "caption": " ".join(words), "score": score})
-        return result
+        _check_sample_args(self, samples_per_image, temperature, top_k, top_p, seed)
+        return _sample_captions([self], None, False, dataloader, int(samples_per_image), temperature, top_k, top_p, seed, tqdm_visible)
 
     # ---- caption sets: consensus reranking and the set report (an extension; caption_sets.py, include/icz.h "Caption sets") -------
     def _pack_set(self, entries, samples_per_image):
@@ -767,8 +672,7 @@ class BUTDDetection_Eng(Engine):
                 for w in words:
                     if w not in word2ix:
                         raise ValueError("word %r is not in the vocabulary" % (w,))
-        if self._cider_df is None and self._scorer is None:
-            raise ValueError("caption sets are scored with CIDEr-D: the engine needs cider_df (the document-frequency table)")
+        _check_cider_df(self)
         return ids, caps, lambda: cs.pack_candidates(caps, word2ix, self.device)
 
     def rerank_captions_json(self, entries, samples_per_image):
@@ -796,8 +700,7 @@ class BUTDDetection_Eng(Engine):
         caption per image."""
         from .caption_sets import check_k
         check_k(samples_per_image, 2)
-        if self._cider_df is None and self._scorer is None:
-            raise ValueError("caption sets are scored with CIDEr-D: the engine needs cider_df (the document-frequency table)")
+        _check_cider_df(self)
         entries = self.sample_captions_json_generation(dataloader, samples_per_image, temperature, top_k, top_p, seed, tqdm_visible)
         return self.rerank_captions_json(entries, samples_per_image)
 
@@ -821,8 +724,7 @@ class BUTDDetection_Eng(Engine):
         consensus caption per image, voted by distinct candidates."""
         from .caption_sets import check_k
         check_k(samples_per_image, 2)
-        if self._cider_df is None and self._scorer is None:
-            raise ValueError("caption sets are scored with CIDEr-D: the engine needs cider_df (the document-frequency table)")
+        _check_cider_df(self)
         entries = self.sample_distinct_captions_json_generation(dataloader, samples_per_image, temperature, seed, tqdm_visible)
         return self.rerank_captions_json(entries, samples_per_image)
 
@@ -1030,14 +932,150 @@ def _monitor(dataloader, desc, visible):
     return tqdm.tqdm(dataloader, desc=desc)
 
 
-def eval_ensemble_captions_json_generation(engines, dataloader, eval_beam_size=-1, tqdm_visible=True, *, weights=None, length_penalty=None,
-                                           block_ngram=0, beam_groups=1, diversity=0.0):
-    """Engine.eval_captions_json_generation for an ensemble of 1..4 engines (BUTD / AoA / NIC) of one vocabulary (an extension;
-    include/icz.h: icz_ensemble_*): every engine turns the shared batch into its own features (its modify_visual_inputs and
-    _features), the members decode together on the averaged word probabilities (`weights`: None = uniform), greedy or with beam
-    search and its options.  Returns the JSON list of the single-model method (the first engine's vocabulary), sharded over the
-    ranks and all-gathered in loader order the same way.  Arguments are checked before any device work (ValueError)."""
-    from .ensemble import EnsembleHandle, check_members, check_weights
+# ---- what the caption-generation and scoring paths share: the batch walk, the gathered rows, the chunks, the checks ---------------
+def _prepare(engines, weights, ensemble, ens, img_tensors, supp_info_datas):
+    """One loader batch under the one engine or (ensemble) the ensemble of the engines: every engine turns it into its own features
+    and hands out its hot handle -> (the handle to call, its features -- a list of one per member for the ensemble --, the
+    EnsembleHandle to keep for the next batch: it is rebuilt only when a member's handle is another object)."""
+    feats = [e._features(e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)) for e in engines]
+    handles = [e._hot_handle() for e in engines]
+    if not ensemble:
+        return handles[0], feats[0], None
+    from .ensemble import EnsembleHandle
+    if ens is None or any(a is not b for a, b in zip(ens.handles, handles)):
+        ens = EnsembleHandle(handles, weights)
+    return ens, feats, ens
+
+
+def _batches(engines, weights, ensemble, dataloader, desc, tqdm_visible, shard=True):
+    """The batch walk of every generation and scoring path: the engines go into evaluation mode now, and the generator returned
+    hands out (batch index, image ids, handle, features) per batch of the evaluation loader (_prepare).  Data-parallel with `shard`
+    (torch.distributed initialised): this rank's batches only, i % world == rank.  An indexable loader (list,
+    Dataset-like: __len__ + __getitem__) or one with a shard(rank, world) method is never asked for the other ranks' batches (no
+    feature I/O for them); any other iterable is walked in full and the foreign batches dropped (_rank_batches)."""
+    for e in engines:
+        e.model.eval()
+    if not shard:
+        numbered = enumerate(_monitor(dataloader, desc, tqdm_visible))
+    elif icz_dist.is_distributed():
+        numbered = _monitor(_rank_batches(dataloader, icz_dist.rank(), icz_dist.world_size()), desc, tqdm_visible)
+    else:
+        numbered = _monitor(enumerate(dataloader), desc, tqdm_visible)
+
+    def walk():
+        ens = None
+        for batch_i, (image_ids, img_tensors, supp_info_datas) in numbered:
+            h, feats, ens = _prepare(engines, weights, ensemble, ens, img_tensors, supp_info_datas)
+            yield batch_i, image_ids, h, feats
+    return walk()
+
+
+class _Rows:
+    """The rows a rank decoded, each with its image id and its place in the loader: key = (batch index << 20) + row index within
+    the batch.  gathered(): (image id, row) of ALL ranks in loader order -- what the corpus-level scorer after it
+    (COCO_Eval_Utils.py:15-35) needs in one place; every rank gets the complete list, rank 0 is the one that should write / score it."""
+
+    def __init__(self):
+        self.ids, self.rows, self.keys = [], [], []
+
+    def add(self, batch_i, j, image_id, row):
+        self.ids.append(int(image_id))
+        self.rows.append(row)
+        self.keys.append((batch_i << 20) + j)
+
+    def gathered(self, device):
+        if icz_dist.is_distributed():
+            return zip(*icz_dist.gather_caption_rows(self.keys, self.ids, self.rows, device))
+        return zip(self.ids, self.rows)
+
+
+def _slice_feats(f, lo, hi):
+    from .regions import RegionBatch
+    if isinstance(f, RegionBatch):
+        return RegionBatch(f.feats[lo:hi], None if f.counts is None else list(f.counts)[lo:hi])
+    return f[lo:hi]
+
+
+def _chunks(feats, ensemble, n_img, per, refuse=None, limit=None, whole=False):
+    """A batch of n_img images in calls of at most `per` (and at most `limit`) images -> (lo, hi, the features of images lo..hi).
+    Where not even one image fits (per < 1): ValueError(refuse), or one image per call without a `refuse`.  whole: a batch that
+    fits one call is handed over unsliced."""
+    if per < 1:
+        if refuse is not None:
+            raise ValueError(refuse)
+        per = 1
+    if limit is not None:
+        per = min(per, limit)
+    for lo in range(0, n_img, per):
+        hi = min(n_img, lo + per)
+        if whole and per >= n_img:
+            yield lo, hi, feats
+        else:
+            yield lo, hi, [_slice_feats(f, lo, hi) for f in feats] if ensemble else _slice_feats(feats, lo, hi)
+
+
+_words = CaptionerBase._words      # a row of ids -> its words up to <end> (stop_at_pad: or up to the first <pad>), without <sta>
+
+
+def _pack_row(ids, score, perturbed=None):
+    """Token ids with a float32 score and, if given, a float64 perturbed value behind them as their bit patterns: one uint32, then
+    two uint32 halves, low then high -- non-negative integers, which is what gather_caption_rows carries."""
+    tail = [int(score.view(np.uint32))]
+    if perturbed is not None:
+        bits = int(perturbed.view(np.uint64))
+        tail += [bits & 0xFFFFFFFF, bits >> 32]
+    return np.concatenate([ids, tail])
+
+
+def _unpack_row(row, perturbed=False):
+    """_pack_row back -> (ids, score) or (ids, score, perturbed value), bit for bit"""
+    tail = 3 if perturbed else 1
+    score = float(np.array([int(row[-tail])], dtype=np.uint32).view(np.float32)[0])
+    if not perturbed:
+        return row[:-1], score
+    return row[:-3], score, float(np.array([int(row[-2]) | (int(row[-1]) << 32)], dtype=np.uint64).view(np.float64)[0])
+
+
+def _check_seed(seed):
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError("seed %r is not a non-negative integer" % (seed,))
+
+
+def _check_sample_args(lead, samples_per_image, temperature, top_k, top_p, seed):
+    make_sample_opts(temperature, top_k, top_p, samples_per_image)
+    _check_seed(seed)
+    if top_k > len(lead.caption_vocab):
+        raise ValueError("top_k %d above the vocabulary size %d" % (top_k, len(lead.caption_vocab)))
+
+
+def _check_cider_df(eng):
+    if eng._cider_df is None and eng._scorer is None:
+        raise ValueError("caption sets are scored with CIDEr-D: the engine needs cider_df (the document-frequency table)")
+
+
+def _check_beam_opts(eval_beam_size, length_penalty, block_ngram, beam_groups, diversity, ensemble):
+    """The beam options of eval_captions_json_generation (checked where one is set) and eval_ensemble_captions_json_generation
+    (always checked, the beam size with them) -> (length_penalty, block_ngram, beam_groups, diversity) for beam_search_opts, or None
+    for the single model without an option: the plain beam_search.  A bad option raises here, before any device work."""
+    diverse = isinstance(beam_groups, bool) or isinstance(diversity, bool) or beam_groups != 1 or diversity != 0.0
+    given = length_penalty is not None or bool(block_ngram) or diverse
+    if given and eval_beam_size == -1:
+        raise ValueError("length_penalty / block_ngram / beam_groups / diversity need beam search (eval_beam_size != -1)")
+    if not given and not ensemble:
+        return None
+    parse_length_penalty(length_penalty)
+    if int(block_ngram) not in (0, 2, 3, 4):
+        raise ValueError("block_ngram %d not 0, 2, 3 or 4" % int(block_ngram))
+    if eval_beam_size != -1:
+        if ensemble and (isinstance(eval_beam_size, bool) or not isinstance(eval_beam_size, int) or eval_beam_size < 1):
+            raise ValueError("eval_beam_size %r: -1 (greedy) or a beam size >= 1" % (eval_beam_size,))
+        make_diversity(beam_groups, diversity, eval_beam_size)      # groups not dividing the beam, bad diversity
+    return length_penalty, int(block_ngram), int(beam_groups), float(diversity)
+
+
+def _ensemble_engine_checks(engines, weights):
+    """the engine checks of eval_ensemble_captions_json_generation -> the engines as a list"""
+    from .ensemble import check_members, check_weights
     engines = list(engines)
     check_members(len(engines))
     if len({len(e.caption_vocab) for e in engines}) != 1:
@@ -1045,68 +1083,55 @@ def eval_ensemble_captions_json_generation(engines, dataloader, eval_beam_size=-
     if len({str(e.device) for e in engines}) != 1:
         raise ValueError("the engines sit on different devices %s" % [str(e.device) for e in engines])
     check_weights(weights, len(engines))
-    diverse = isinstance(beam_groups, bool) or isinstance(diversity, bool) or beam_groups != 1 or diversity != 0.0
-    if (length_penalty is not None or block_ngram or diverse) and eval_beam_size == -1:
-        raise ValueError("length_penalty / block_ngram / beam_groups / diversity need beam search (eval_beam_size != -1)")
-    parse_length_penalty(length_penalty)
-    if int(block_ngram) not in (0, 2, 3, 4):
-        raise ValueError("block_ngram %d not 0, 2, 3 or 4" % int(block_ngram))
-    if eval_beam_size != -1:
-        if isinstance(eval_beam_size, bool) or not isinstance(eval_beam_size, int) or eval_beam_size < 1:
-            raise ValueError("eval_beam_size %r: -1 (greedy) or a beam size >= 1" % (eval_beam_size,))
-        make_diversity(beam_groups, diversity, eval_beam_size)
-    opts = (1, length_penalty, int(block_ngram), int(beam_groups), float(diversity))
+    return engines
+
+
+# ---- greedy / beam evaluation ---------------------------------------------------------------------------------------------------
+def _eval_captions(engines, weights, ensemble, dataloader, eval_beam_size, tqdm_visible, opts):
+    """Engine.py:274-300 under the one engine or (ensemble) the ensemble of the engines.  Beam search accepts any batch size here
+    (the reference's loader uses 1); opts: _check_beam_opts.  Data-parallel: rank r decodes the batches i with i % world == r
+    (_batches), the (image id, token ids) rows are all-gathered and every rank returns the complete list in loader order (_Rows)."""
     lead = engines[0]
     with _on_stream(lead):
-        for e in engines:
-            e.model.eval()
-        print("Generating captions json for evaluation (ensemble of %d). Beam Search: %s" % (len(engines), eval_beam_size != -1))
-        dp = icz_dist.is_distributed()
-        rank, world = icz_dist.rank(), icz_dist.world_size()
-        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Generating Process", tqdm_visible)
-        ens = None
-        ids_out, rows_out, keys_out = [], [], []
-        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
-            nb = len(image_ids)
-            feats = []
-            for e in engines:
-                vi = e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
-                feats.append(e._features(vi))
-            handles = [e._hot_handle() for e in engines]
-            if ens is None or any(a is not b for a, b in zip(ens.handles, handles)):
-                ens = EnsembleHandle(handles, weights)
-            if eval_beam_size != -1:
-                seqs, lens, _ = ens.beam_search_opts(feats, eval_beam_size, 50, *opts)
+        batches = _batches(engines, weights, ensemble, dataloader, "Generating Process", tqdm_visible)
+        print("Generating captions json for evaluation%s. Beam Search: %s" % (" (ensemble of %d)" % len(engines) if ensemble else "",
+                                                                                eval_beam_size != -1))
+        out = _Rows()
+        for batch_i, image_ids, h, feats in batches:
+            if eval_beam_size != -1 and opts is not None:
+                seqs, lens, _ = h.beam_search_opts(feats, eval_beam_size, 50, 1, *opts)
                 seqs, lens = seqs[:, 0].cpu().numpy(), lens[:, 0].cpu().numpy()
                 rows = [seqs[i, :lens[i]] for i in range(len(lens))]
+            elif eval_beam_size != -1:
+                seqs, lens = h.beam_search(feats, eval_beam_size, 50)
+                seqs, lens = seqs.cpu().numpy(), lens.cpu().numpy()
+                rows = [seqs[i, :lens[i]] for i in range(len(lens))]
             else:
-                rows = list(ens.greedy(feats, 20).cpu().numpy())
-            ids_out += [int(i) for i in image_ids]
-            rows_out += rows
-            keys_out += [(batch_i << 20) + j for j in range(nb)]      # loader order: batch index, then row
-        if dp:
-            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, lead.device)
-    result = []
-    ix2word = lead.caption_vocab.ix2word
-    for image_id, sampled_ids in zip(ids_out, rows_out):
-        sampled_caption = []
-        for word_id in sampled_ids:
-            word = ix2word[int(word_id)]
-            if word == "<end>":
-                break
-            elif word != "<sta>":
-                sampled_caption.append(word)
-        result.append({"image_id": image_id, "caption": " ".join(sampled_caption)})
-    return result
+                rows = list(h.greedy(feats, 20).cpu().numpy())
+            for j, image_id in enumerate(image_ids):
+                out.add(batch_i, j, image_id, rows[j])
+        pairs = out.gathered(lead.device)
+    return [{"image_id": image_id, "caption": " ".join(_words(row, lead.caption_vocab))} for image_id, row in pairs]
 
 
+def eval_ensemble_captions_json_generation(engines, dataloader, eval_beam_size=-1, tqdm_visible=True, *, weights=None, length_penalty=None,
+                                           block_ngram=0, beam_groups=1, diversity=0.0):
+    """Engine.eval_captions_json_generation for an ensemble of 1..4 engines (BUTD / AoA / NIC) of one vocabulary (an extension;
+    include/icz.h: icz_ensemble_*): every engine turns the shared batch into its own features (its modify_visual_inputs and
+    _features), the members decode together on the averaged word probabilities (`weights`: None = uniform), greedy or with beam
+    search and its options.  Returns the JSON list of the single-model method (the first engine's vocabulary), sharded over the
+    ranks and all-gathered in loader order the same way.  Arguments are checked before any device work (ValueError)."""
+    engines = _ensemble_engine_checks(engines, weights)
+    opts = _check_beam_opts(eval_beam_size, length_penalty, block_ngram, beam_groups, diversity, True)
+    return _eval_captions(engines, weights, True, dataloader, eval_beam_size, tqdm_visible, opts)
+
+
+# ---- constrained beam search ----------------------------------------------------------------------------------------------------
 def _constrained_captions_json_generation(engines, weights, ensemble, dataloader, constraints, beam, tqdm_visible, length_penalty, block_ngram,
                                           max_chunk=None):
     """The constrained search of Engine.constrained_captions_json_generation under the one engine or (ensemble) the ensemble of the
     engines.  max_chunk (tests): at most that many images per call."""
     from . import constrained as cst
-    from .ensemble import EnsembleHandle
-    from .handle import CaptionerBase
     lead = engines[0]
     if not isinstance(constraints, dict):
         raise ValueError("constraints must map image ids to lists of constraints, got %s" % type(constraints).__name__)
@@ -1124,46 +1149,24 @@ def _constrained_captions_json_generation(engines, weights, ensemble, dataloader
         lost.setdefault(keys[img], set()).add(q)
     ids_of = dict(zip(keys, enc))
     with _on_stream(lead):
-        for e in engines:
-            e.model.eval()
-        dp = icz_dist.is_distributed()
-        rank, world = icz_dist.rank(), icz_dist.world_size()
-        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Generating Process", tqdm_visible)
-        ens = None
-        ids_out, rows_out, keys_out = [], [], []
-        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
+        out = _Rows()
+        for batch_i, image_ids, h, feats in _batches(engines, weights, ensemble, dataloader, "Generating Process", tqdm_visible):
             nb = len(image_ids)
-            feats = []
-            for e in engines:
-                vi = e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
-                feats.append(e._features(vi))
-            handles = [e._hot_handle() for e in engines]
-            if ensemble and (ens is None or any(a is not b for a, b in zip(ens.handles, handles))):
-                ens = EnsembleHandle(handles, weights)
-            h = ens if ensemble else handles[0]
             words = cst.make_constraints([ids_of.get(int(i), []) for i in image_ids], nb, h.V)
             # One C for the whole batch: a chunk with a constrained image searches the states the batch does.  A chunk without any
             # (as a batch without any) is the plain options search on eval_beam_size rows per image, which is what an unconstrained
             # image's state 0 runs inside a constrained call; its caption is the same as far as the decoder's GEMMs agree between
             # the two row counts (they do on every case tested), not by construction.
-            per = h.max_rows // cst.rows_per_image(words, beam)
-            if per < 1:
-                raise ValueError("one image takes %d rows, the handle's row capacity is %d" % (cst.rows_per_image(words, beam), h.max_rows))
-            per = per if max_chunk is None else min(per, max_chunk)
-            for lo in range(0, nb, per):
-                hi = min(nb, lo + per)
-                part = [_slice_feats(f, lo, hi) for f in feats]
-                seqs, lens, _, sat = cst.beam_search(h, part if ensemble else part[0], words[lo:hi], beam, 50, 1, length_penalty, int(block_ngram))
+            need = cst.rows_per_image(words, beam)
+            refuse = "one image takes %d rows, the handle's row capacity is %d" % (need, h.max_rows)
+            for lo, hi, part in _chunks(feats, ensemble, nb, h.max_rows // need, refuse, max_chunk):
+                seqs, lens, _, sat = cst.beam_search(h, part, words[lo:hi], beam, 50, 1, length_penalty, int(block_ngram))
                 seqs, lens, sat = seqs[:, 0].cpu().numpy(), lens[:, 0].cpu().numpy(), sat[:, 0].cpu().numpy()
-                # the state rides behind the tokens through the gather
-                rows_out += [np.concatenate([seqs[i, :lens[i]], [np.float32(sat[i])]]) for i in range(hi - lo)]
-            ids_out += [int(i) for i in image_ids]
-            keys_out += [(batch_i << 20) + j for j in range(nb)]      # loader order: batch index, then row
-        if dp:
-            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, lead.device)
+                for i in range(hi - lo):      # the state rides behind the tokens through the gather
+                    out.add(batch_i, lo + i, image_ids[lo + i], np.concatenate([seqs[i, :lens[i]], [np.float32(sat[i])]]))
+        pairs = out.gathered(lead.device)
     result = []
-    for image_id, row in zip(ids_out, rows_out):
-        caption = CaptionerBase._words(torch.as_tensor(np.asarray(row[:-1])), lead.caption_vocab)
+    for image_id, row in pairs:
         sat, q, flags = int(row[-1]), 0, []
         for c in range(len(given.get(image_id, []))):          # a dropped constraint took no bit
             if c in lost.get(image_id, ()):
@@ -1171,7 +1174,7 @@ def _constrained_captions_json_generation(engines, weights, ensemble, dataloader
             else:
                 flags.append(bool((sat >> q) & 1))
                 q += 1
-        result.append({"image_id": image_id, "caption": " ".join(caption), "satisfied": flags})
+        result.append({"image_id": image_id, "caption": " ".join(_words(row[:-1], lead.caption_vocab)), "satisfied": flags})
     return result
 
 
@@ -1185,17 +1188,23 @@ def constrained_ensemble_captions_json_generation(engines, dataloader, constrain
                                                  block_ngram)
 
 
-def _ensemble_engine_checks(engines, weights):
-    """the engine checks of eval_ensemble_captions_json_generation -> the engines as a list"""
-    from .ensemble import check_members, check_weights
-    engines = list(engines)
-    check_members(len(engines))
-    if len({len(e.caption_vocab) for e in engines}) != 1:
-        raise ValueError("the engines' vocabularies differ in size %s" % [len(e.caption_vocab) for e in engines])
-    if len({str(e.device) for e in engines}) != 1:
-        raise ValueError("the engines sit on different devices %s" % [str(e.device) for e in engines])
-    check_weights(weights, len(engines))
-    return engines
+# ---- sampled captions -----------------------------------------------------------------------------------------------------------
+def _sample_captions(engines, weights, ensemble, dataloader, n, temperature, top_k, top_p, seed, tqdm_visible):
+    """Engine.sample_captions_json_generation under the one engine or (ensemble) the ensemble of the engines"""
+    lead = engines[0]
+    with _on_stream(lead):
+        out = _Rows()
+        for batch_i, image_ids, h, feats in _batches(engines, weights, ensemble, dataloader, "Sampling Process", tqdm_visible):
+            ids, _, score = h.sample_decode(feats, n, 20, temperature, top_k, top_p, (seed << 20) + batch_i)
+            ids, score = ids.cpu().numpy(), score.cpu().numpy()
+            for r in range(ids.shape[0]):                              # loader order: batch index, then image, then sample
+                out.add(batch_i, r, image_ids[r // n], _pack_row(ids[r], score[r]))
+        pairs = out.gathered(lead.device)
+    result = []
+    for image_id, row in pairs:
+        ids, score = _unpack_row(row)
+        result.append({"image_id": image_id, "caption": " ".join(_words(ids, lead.caption_vocab, True)), "score": score})
+    return result
 
 
 def sample_ensemble_captions_json_generation(engines, dataloader, samples_per_image=1, temperature=1.0, top_k=0, top_p=1.0, seed=0,
@@ -1207,52 +1216,9 @@ def sample_ensemble_captions_json_generation(engines, dataloader, samples_per_im
     engine's vocabulary); score = the ensemble's summed log-probability of the caption's tokens.  Batch i draws from Philox seed
     `seed * 2**20 + i`; sharded over the ranks and gathered as the single-model method.  Arguments are checked before any device
     work (ValueError)."""
-    from .ensemble import EnsembleHandle
     engines = _ensemble_engine_checks(engines, weights)
-    make_sample_opts(temperature, top_k, top_p, samples_per_image)
-    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
-        raise ValueError("seed %r is not a non-negative integer" % (seed,))
-    lead = engines[0]
-    if top_k > len(lead.caption_vocab):
-        raise ValueError("top_k %d above the vocabulary size %d" % (top_k, len(lead.caption_vocab)))
-    n = int(samples_per_image)
-    with _on_stream(lead):
-        for e in engines:
-            e.model.eval()
-        dp = icz_dist.is_distributed()
-        rank, world = icz_dist.rank(), icz_dist.world_size()
-        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Sampling Process", tqdm_visible)
-        ens = None
-        ids_out, rows_out, keys_out = [], [], []
-        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
-            feats = []
-            for e in engines:
-                vi = e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
-                feats.append(e._features(vi))
-            handles = [e._hot_handle() for e in engines]
-            if ens is None or any(a is not b for a, b in zip(ens.handles, handles)):
-                ens = EnsembleHandle(handles, weights)
-            ids, _, score = ens.sample_decode(feats, n, 20, temperature, top_k, top_p, (seed << 20) + batch_i)
-            ids, bits = ids.cpu().numpy(), score.cpu().numpy().view(np.uint32)
-            for r in range(ids.shape[0]):
-                ids_out.append(int(image_ids[r // n]))
-                rows_out.append(np.concatenate([ids[r], [int(bits[r])]]))      # the score travels as its bit pattern (non-negative)
-                keys_out.append((batch_i << 20) + r)                           # loader order: batch index, then image, then sample
-        if dp:
-            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, lead.device)
-    result = []
-    ix2word = lead.caption_vocab.ix2word
-    for image_id, row in zip(ids_out, rows_out):
-        words = []
-        for word_id in row[:-1]:
-            word = ix2word[int(word_id)]
-            if word == "<end>" or int(word_id) == 0:
-                break
-            elif word != "<sta>":
-                words.append(word)
-        score = float(np.array([int(row[-1])], dtype=np.uint32).view(np.float32)[0])
-        result.append({"image_id": image_id, "caption": " ".join(words), "score": score})
-    return result
+    _check_sample_args(engines[0], samples_per_image, temperature, top_k, top_p, seed)
+    return _sample_captions(engines, weights, True, dataloader, int(samples_per_image), temperature, top_k, top_p, seed, tqdm_visible)
 
 
 def consensus_ensemble_captions_json_generation(engines, dataloader, samples_per_image=5, temperature=1.0, top_k=0, top_p=1.0, seed=0,
@@ -1262,74 +1228,37 @@ def consensus_ensemble_captions_json_generation(engines, dataloader, samples_per
     from .caption_sets import check_k
     engines = _ensemble_engine_checks(engines, weights)
     check_k(samples_per_image, 2)
-    make_sample_opts(temperature, top_k, top_p, samples_per_image)         # every option error in front of the engines' state
-    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
-        raise ValueError("seed %r is not a non-negative integer" % (seed,))
     lead = engines[0]
-    if top_k > len(lead.caption_vocab):
-        raise ValueError("top_k %d above the vocabulary size %d" % (top_k, len(lead.caption_vocab)))
-    if lead._cider_df is None and lead._scorer is None:
-        raise ValueError("caption sets are scored with CIDEr-D: the engine needs cider_df (the document-frequency table)")
+    _check_sample_args(lead, samples_per_image, temperature, top_k, top_p, seed)         # every option error in front of the engines' state
+    _check_cider_df(lead)
     entries = sample_ensemble_captions_json_generation(engines, dataloader, samples_per_image, temperature, top_k, top_p, seed, tqdm_visible,
                                                        weights=weights)
     return lead.rerank_captions_json(entries, samples_per_image)
 
 
+# ---- sampling without replacement -----------------------------------------------------------------------------------------------
 def _sample_distinct_captions_json_generation(engines, weights, ensemble, dataloader, samples_per_image, temperature, seed, tqdm_visible):
     """Engine.sample_distinct_captions_json_generation over one engine's own handle, or (ensemble) an EnsembleHandle over the engines'"""
     from . import stochastic_beam as sbs
     lead = engines[0]
     n, _, temperature = sbs.check_args(samples_per_image, 20, temperature, len(lead.caption_vocab))
-    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
-        raise ValueError("seed %r is not a non-negative integer" % (seed,))
+    _check_seed(seed)
     with _on_stream(lead):
-        for e in engines:
-            e.model.eval()
-        dp = icz_dist.is_distributed()
-        rank, world = icz_dist.rank(), icz_dist.world_size()
-        monitor = _monitor(_rank_batches(dataloader, rank, world) if dp else enumerate(dataloader), "Sampling Process", tqdm_visible)
-        ens = None
-        ids_out, rows_out, keys_out = [], [], []
-        for batch_i, (image_ids, img_tensors, supp_info_datas) in monitor:
-            feats = [e._features(e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)) for e in engines]
-            handles = [e._hot_handle() for e in engines]
-            if not ensemble:
-                h, f = handles[0], feats[0]
-            else:
-                from .ensemble import EnsembleHandle
-                if ens is None or any(a is not b for a, b in zip(ens.handles, handles)):
-                    ens = EnsembleHandle(handles, weights)
-                h, f = ens, feats
+        out = _Rows()
+        for batch_i, image_ids, h, feats in _batches(engines, weights, ensemble, dataloader, "Sampling Process", tqdm_visible):
             # a batch above the row capacity / n is decoded in chunks of images; a chunk draws the noise of its images within the whole
             # batch (first_image), so the chunked batch is the whole one
-            B, per = len(image_ids), max(1, h.max_rows // n)
-            part = lambda lo: [_slice_feats(x, lo, lo + per) for x in f] if ensemble else _slice_feats(f, lo, lo + per)      # noqa: E731
-            outs = [sbs.sample_distinct(h, f if per >= B else part(lo), n, 20, temperature, ((seed << 20) + batch_i, lo))
-                    for lo in range(0, B, per)]
+            outs = [sbs.sample_distinct(h, part, n, 20, temperature, ((seed << 20) + batch_i, lo))
+                    for lo, _, part in _chunks(feats, ensemble, len(image_ids), h.max_rows // n, whole=True)]
             ids, lens, phi, G = (torch.cat([o[k] for o in outs]).cpu().numpy() for k in (0, 1, 3, 4))
-            pbits, gbits = phi.view(np.uint32), G.view(np.uint64)
-            for r in range(ids.shape[0]):
-                if lens[r] == 0:                                           # an unoccupied slot: fewer than n sequences exist
-                    continue
-                ids_out.append(int(image_ids[r // n]))
-                # the score and the perturbed value travel as their bit patterns (non-negative integers)
-                rows_out.append(np.concatenate([ids[r], [int(pbits[r]), int(gbits[r] & 0xFFFFFFFF), int(gbits[r] >> 32)]]))
-                keys_out.append((batch_i << 20) + r)                       # loader order: batch index, then image, then slot
-        if dp:
-            ids_out, rows_out = icz_dist.gather_caption_rows(keys_out, ids_out, rows_out, lead.device)
+            for r in range(ids.shape[0]):                              # loader order: batch index, then image, then slot
+                if lens[r] != 0:                                       # 0: an unoccupied slot (fewer than n sequences exist); its index stays taken
+                    out.add(batch_i, r, image_ids[r // n], _pack_row(ids[r], phi[r], G[r]))
+        pairs = out.gathered(lead.device)
     result = []
-    ix2word = lead.caption_vocab.ix2word
-    for image_id, row in zip(ids_out, rows_out):
-        words = []
-        for word_id in row[:-3]:
-            word = ix2word[int(word_id)]
-            if word == "<end>" or int(word_id) == 0:
-                break
-            elif word != "<sta>":
-                words.append(word)
-        score = float(np.array([int(row[-3])], dtype=np.uint32).view(np.float32)[0])
-        pert = float(np.array([int(row[-2]) | (int(row[-1]) << 32)], dtype=np.uint64).view(np.float64)[0])
-        result.append({"image_id": image_id, "caption": " ".join(words), "score": score, "perturbed": pert})
+    for image_id, row in pairs:
+        ids, score, pert = _unpack_row(row, True)
+        result.append({"image_id": image_id, "caption": " ".join(_words(ids, lead.caption_vocab, True)), "score": score, "perturbed": pert})
     return result
 
 
@@ -1365,51 +1294,24 @@ def _check_score_entries(entries, captions_per_image):
     return entries, n
 
 
-def _slice_feats(f, lo, hi):
-    from .regions import RegionBatch
-    if isinstance(f, RegionBatch):
-        return RegionBatch(f.feats[lo:hi], None if f.counts is None else list(f.counts)[lo:hi])
-    return f[lo:hi]
-
-
-def _score_batch(engines, weights, ens, img_tensors, supp_info_datas, ids, n, ensemble=False):
-    """ids [images x n, T] (numpy) of one loader batch under the one engine, or (ensemble) under the ensemble of the engines ->
-    (logp [rows, T], score [rows]) as numpy arrays, the ensemble handle to keep for the next batch; scored in chunks of images
-    where the rows exceed the handle's capacity"""
-    from .ensemble import EnsembleHandle
+def _score_chunks(h, feats, ensemble, ids, n):
+    """ids [images x n, T] (numpy) of one loader batch under the handle and its features -> (logp [rows, T], score [rows]) as numpy
+    arrays; scored in chunks of images where the rows exceed the handle's capacity"""
     from .scoring import score_captions
-    feats = []
-    for e in engines:
-        vi = e.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
-        feats.append(e._features(vi))
-    handles = [e._hot_handle() for e in engines]
-    if not ensemble:
-        h = handles[0]
-    else:
-        if ens is None or any(a is not b for a, b in zip(ens.handles, handles)):
-            ens = EnsembleHandle(handles, weights)
-        h = ens
-    per = h.max_rows // n
-    if per < 1:
-        raise ValueError("%d captions per image exceed the handle's row capacity %d" % (n, h.max_rows))
-    n_img = ids.shape[0] // n
+    refuse = "%d captions per image exceed the handle's row capacity %d" % (n, h.max_rows)
     logps, scores = [], []
-    for lo in range(0, n_img, per):
-        hi = min(n_img, lo + per)
-        part = [_slice_feats(f, lo, hi) for f in feats]
-        lp, sc = score_captions(h, part if ensemble else part[0], ids[lo * n:hi * n], n)
+    for lo, hi, part in _chunks(feats, ensemble, ids.shape[0] // n, h.max_rows // n, refuse):
+        lp, sc = score_captions(h, part, ids[lo * n:hi * n], n)
         logps.append(lp.cpu().numpy())
         scores.append(sc.cpu().numpy())
-    return np.concatenate(logps), np.concatenate(scores), ens
+    return np.concatenate(logps), np.concatenate(scores)
 
 
 def _score_entries(engines, weights, dataloader, entries, n, tqdm_visible, ensemble=False):
     from .scoring import encode_captions, scored_lengths
     lead = engines[0]
-    for e in engines:
-        e.model.eval()
-    ens, out, at = None, [], 0
-    for image_ids, img_tensors, supp_info_datas in _monitor(dataloader, "Scoring Process", tqdm_visible):
+    out, at = [], 0
+    for _, image_ids, h, feats in _batches(engines, weights, ensemble, dataloader, "Scoring Process", tqdm_visible, shard=False):
         nb = len(image_ids)
         group = entries[at:at + nb * n]
         if len(group) != nb * n:
@@ -1418,7 +1320,7 @@ def _score_entries(engines, weights, dataloader, entries, n, tqdm_visible, ensem
             if str(group[j * n]["image_id"]) != str(int(image_id) if not isinstance(image_id, str) else image_id):
                 raise ValueError("entries %d..: image_id %r, but the loader's image is %r" % (at + j * n, group[j * n]["image_id"], image_id))
         ids = encode_captions([e["caption"] for e in group], lead.caption_vocab)
-        logp, score, ens = _score_batch(engines, weights, ens, img_tensors, supp_info_datas, ids, n, ensemble)
+        logp, score = _score_chunks(h, feats, ensemble, ids, n)
         lens = scored_lengths(ids)
         for r, e in enumerate(group):
             d = dict(e)
@@ -1458,7 +1360,8 @@ def _reference_perplexity(eng, dataloader, tqdm_visible):
             for j, c in enumerate(c for g in caps for c in g):
                 if c is None:
                     ids[j] = 0                   # no reference here: an empty caption, which scores nothing
-            logp, _, _ = _score_batch([eng], None, None, img_tensors, supp_info_datas, ids, n)
+            h, feats, _ = _prepare([eng], None, False, None, img_tensors, supp_info_datas)
+            logp, _ = _score_chunks(h, feats, False, ids, n)
             lens = scored_lengths(ids)
             total += float(sum(np.sum(logp[r, :lens[r]], dtype=np.float64) for r in range(ids.shape[0])))
             tokens += int(lens.sum())

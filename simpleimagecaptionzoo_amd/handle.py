@@ -364,12 +364,13 @@ class CaptionerBase(ScheduledSamplingState):
         return nbest_lists(seqs, lens, scores)
 
     @staticmethod
-    def _words(ids, caption_vocab):
-        """The words of one decoded row up to <end>, without <sta> (the tail of every eval_test_image)."""
-        caption = []
-        for word_id in ids.cpu().numpy():
-            word = caption_vocab.ix2word[int(word_id)]
-            if word == "<end>":
+    def _words(ids, caption_vocab, stop_at_pad=False):
+        """The words of one decoded row (a tensor or an array of ids) up to <end>, without <sta>: the tail of every eval_test_image
+        and of the engine's caption lists.  stop_at_pad: the row also ends at its first <pad> (0), as a sampled row does."""
+        caption, ix2word = [], caption_vocab.ix2word
+        for word_id in (ids.cpu().numpy() if torch.is_tensor(ids) else ids):
+            word = ix2word[int(word_id)]
+            if word == "<end>" or (stop_at_pad and int(word_id) == 0):
                 break
             elif word != "<sta>":
                 caption.append(word)
