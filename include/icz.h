@@ -859,6 +859,71 @@ int icz_test_scst_objective(const icz_scst_objective* obj, const float* logp, co
                             int32_t V, int32_t ldl, const int32_t* draw, const float* lse, int32_t Bs, int32_t row0, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * SCST on without-replacement samples (beyond the reference; csrc/swor_objective.hip): the policy-gradient estimators of Kool, van
+ * Hoof and Welling ("Buy 4 REINFORCE Samples, Get a Baseline for Free!", 2019; "Estimating Gradients for Discrete Random Variables
+ * by Sampling without Replacement", ICLR 2020) on the n distinct captions per image of icz_*_sample_distinct at temperature 1, in the
+ * place of LabelSmoothingLoss behind a TRAINING-MODE icz_*_xe_forward on those captions (dropout on, state kept for the backward pass).
+ *
+ * phi [images n] float32, G [images n] float64 and scores [images n] float64 (the CIDEr-D of every slot: icz_ciderd_reward_loo's
+ * scores_out) are in icz_*_sample_distinct's row order img * n + slot, the slots of an image sorted by G descending.  Slot n - 1 is
+ * only the threshold kappa = G[n - 1]; the m = n - 1 slots in front of it are the samples, n in 3..8.  In float64, sums in ascending
+ * slot order:
+ *     d_i = phi_i - kappa,   q_i = 1 - exp(-exp(d_i)) = -expm1(-exp(d_i)),
+ *     log q_i = d_i - exp(d_i) / 2 where d_i < -18 (the series behind its first term: the next one is below exp(-36) / 24 < 1e-17)
+ *     p_i = exp(phi_i),   w_i = p_i / q_i = exp(phi_i - log q_i),   W = sum_j w_j,   Bu = sum_j w_j f_j        (f = scores)
+ *     ICZ_SWOR_NORMALISED (0):  c_i = w_i / (W - w_i + p_i) * (f_i - Bu / W)
+ *     ICZ_SWOR_UNBIASED (1):    c_i = w_i * (f_i * (1 + w_i - p_i) - Bu)
+ *     loss = -(1 / N) sum_img sum_{i < m} c_i logp_i,   logp_i = sum_{t < len_i} log softmax(z_{i,t})[y_{i,t}]
+ *     d loss / d z[row, t, v] = -(c_row / N) * (1[v == y] - softmax(z)[v])
+ * c is a constant of the backward pass.  N = n_img_global if > 0 (data-parallel: the all-reduced image count), else the call's image
+ * count rows / (n - 1).  The weights use the sampler's evaluation-mode phi; logp and the gradient are the stored training-mode
+ * forward's.  The threshold slot has c = 0 and takes no part in the forward pass: the stored forward holds rows = images (n - 1) rows,
+ * sorted by decreasing length as icz_*_xe_forward wants them, and perm [rows] int32 (device) maps the sorted row b back to
+ * img * n + slot.
+ *
+ * Kernels: swor_weights_kernel (one wave per image, lane = slot, float64) writes coef [images n] = -c / N as float32 and
+ * stats_out [images, 3] float64 = {W, Bu / W, 1 / sum_j (w_j / W)^2 (the effective sample size)} (NULL: not wanted);
+ * swor_dlogits_kernel (grid (B, T), 256 threads, the addressing of xe_loss_dlogits_kernel; an online max / sum-exp of the row with
+ * 16-byte loads, the gradient written in place with zeros in the pad columns and in inactive rows; a row whose coefficient is exactly
+ * 0 is written as zeros WITHOUT BEING READ; nothing of the row is kept in LDS: no cap on V) leaves the target's log-prob of every
+ * (b, t) in loss_rows (0 for a row that was not read); swor_finish_kernel sums in one fixed order to
+ * loss_out [1 + images] = {loss, sum_i (-c_i / N) logp_i of every image}.  No float atomics: two runs give the same bits.  In the
+ * softmax rows every exponent is taken behind its row's maximum.
+ *
+ * Errors return ICZ_ERR_INVALID before anything is queued, in this order: 1. null opts; 2. n outside 3..8; 3. an unknown estimator;
+ * 4. n_img_global not finite or < 0; 5. rows < 1 or not a multiple of n - 1; 6. null phi, G, scores or perm; then for
+ * icz_*_xe_backward_swor 7. null grads or loss_out; 8. null handle; 9. no XE forward stored; 10. the stored forward ran in evaluation
+ * mode; 11. it ran with scheduled sampling (ss_prob > 0): it was fed other tokens than the sampled captions; 12. rows is not the
+ * stored forward's row count.  A refused call leaves the stored forward usable.
+ * icz_swor_check applies rules 1 - 6 and then, on the host copies it is given (each may be NULL), 7'. perm_host [rows]: every entry
+ * inside [0, images n), no threshold slot, none twice; 8'. lengths_host [rows]: >= 1 and sorted in decreasing order.  (On the device a
+ * perm entry outside [0, images n) is never used as an index: its row counts as one of coefficient 0.)
+ * ---------------------------------------------------------------------------------------------------------- */
+enum { ICZ_SWOR_NORMALISED = 0, ICZ_SWOR_UNBIASED = 1 };
+typedef struct {
+    int32_t n, estimator;
+    float n_img_global;
+    const float* phi;              /* [images n] (device) */
+    const double* G;               /* [images n] (device) */
+    const double* scores;          /* [images n] (device) */
+    const int32_t* perm;           /* [rows] (device) */
+    double* stats_out;             /* [images, 3] (device) or NULL */
+} icz_swor_opts;
+int icz_swor_check(const icz_swor_opts* opts, int32_t rows, const int32_t* perm_host, const int32_t* lengths_host);
+/* icz_*_xe_backward with this loss head (for AoA with the refiner's backward pass when train_refiner is on; for NIC with
+ * dfeatures_out [rows, E] or NULL); loss_out [1 + rows / (n - 1)] */
+int icz_butd_xe_backward_swor(icz_butd_t* h, const icz_swor_opts* opts, int32_t rows, const icz_butd_params* grads, float* loss_out,
+                              void* stream);
+int icz_aoa_xe_backward_swor(icz_aoa_t* h, const icz_swor_opts* opts, int32_t rows, const icz_aoa_params* grads, float* loss_out, void* stream);
+int icz_nic_xe_backward_swor(icz_nic_t* h, const icz_swor_opts* opts, int32_t rows, const icz_nic_params* grads, float* dfeatures_out,
+                             float* loss_out, void* stream);
+/* The kernels alone (tests, tools), in the shape of icz_test_xe_loss: logits [T B, ldl] (ldl % 4 == 0, 16-byte aligned; the gradient is
+ * written over it), captions [B, L] int64 with L > T (the target of (b, t) is captions[b, t + 1]; one outside [0, V) matches no column
+ * and is never used as an index), rows_t [T] a HOST array; coef_out [B / (n - 1) * n], loss_rows [T B], loss_out [1 + B / (n - 1)]. */
+int icz_test_swor_objective(const icz_swor_opts* opts, float* logits, int32_t V, int32_t ldl, const int64_t* captions, int32_t L, int32_t B,
+                            int32_t T, const int32_t* rows_t, float* coef_out, float* loss_rows, float* loss_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser step: clip_gradient (Utils.py:241-250, value clamp) + torch.optim.Adam(betas=(0.9,0.999),
  * eps=1e-8, weight_decay=0) (Utils.py:219-220) fused, one call per parameter tensor.
  * ---------------------------------------------------------------------------------------------------------- */

@@ -158,6 +158,11 @@ class ScstObjective(C.Structure):  # icz_scst_objective
                 ("reward", C.c_void_p), ("scores", C.c_void_p)]
 
 
+class SworOpts(C.Structure):       # icz_swor_opts
+    _fields_ = [("n", C.c_int32), ("estimator", C.c_int32), ("n_img_global", C.c_float), ("phi", C.c_void_p), ("G", C.c_void_p),
+                ("scores", C.c_void_p), ("perm", C.c_void_p), ("stats_out", C.c_void_p)]
+
+
 class DropPArgs(C.Structure):      # icz_test_dropp
     _fields_ = [("mode", C.c_int32), ("mask", C.c_void_p), ("seed", C.c_void_p), ("stream", C.c_uint32), ("step", C.c_uint32),
                 ("p", C.c_float), ("idx0", C.c_uint64)]
@@ -341,6 +346,11 @@ def lib():
         "icz_aoa_sample_backward_objective": (C.c_int, [vp, C.POINTER(ScstObjective), C.POINTER(AoaParams), vp, vp, vp, f32, vp]),
         "icz_nic_sample_backward_objective": (C.c_int, [vp, C.POINTER(ScstObjective), C.POINTER(NicParams), vp, vp, vp, vp, f32, vp]),
         "icz_test_scst_objective": (C.c_int, [C.POINTER(ScstObjective), vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp]),
+        "icz_swor_check": (C.c_int, [C.POINTER(SworOpts), i32, C.POINTER(i32), C.POINTER(i32)]),
+        "icz_butd_xe_backward_swor": (C.c_int, [vp, C.POINTER(SworOpts), i32, C.POINTER(ButdParams), vp, vp]),
+        "icz_aoa_xe_backward_swor": (C.c_int, [vp, C.POINTER(SworOpts), i32, C.POINTER(AoaParams), vp, vp]),
+        "icz_nic_xe_backward_swor": (C.c_int, [vp, C.POINTER(SworOpts), i32, C.POINTER(NicParams), vp, vp, vp]),
+        "icz_test_swor_objective": (C.c_int, [C.POINTER(SworOpts), vp, i32, i32, vp, i32, i32, i32, C.POINTER(i32), vp, vp, vp, vp]),
         "icz_aoa_xe_backward_dlogits": (C.c_int, [vp, vp, C.POINTER(AoaParams), vp]),
         "icz_nic_xe_backward_dlogits": (C.c_int, [vp, vp, C.POINTER(NicParams), vp, vp]),
         "icz_aoa_sample": (C.c_int, [vp, vp, i32, i32, C.POINTER(AoaRng), vp, vp, vp]),

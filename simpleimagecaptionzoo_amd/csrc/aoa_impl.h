@@ -262,6 +262,7 @@ struct Aoa : CaptionHead, DecodeMember {
                    float* packed_out, hipStream_t st);
     int xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
     int xe_backward_distill(const DistillArgs& a, const icz_aoa_params* G, float* loss_out3, float n_tokens_global, hipStream_t st);
+    int xe_backward_swor(const SworArgs& a, int rows, const icz_aoa_params* G, float* loss_out, hipStream_t st);
     int xe_backward_dlogits(const float* dpacked, const icz_aoa_params* G, hipStream_t st);
     int bptt(const icz_aoa_params& G, hipStream_t st);      // the driver over the parts below, then refiner_backward
     struct BpttCall;

@@ -540,6 +540,16 @@ int Aoa::xe_backward_distill(const DistillArgs& a, const icz_aoa_params* G, floa
     return bptt(*G, st);
 }
 
+// xe_backward with the without-replacement SCST head (swor_objective.hip) in the place of xe_loss
+int Aoa::xe_backward_swor(const SworArgs& a, int rows, const icz_aoa_params* G, float* loss_out, hipStream_t st) {
+    ICZ_TRY(check_swor("aoa", rows));
+    if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
+    ICZ_TRY(swor_loss(a, tlogit, dims.V, Vp, loss_out, st));
+    bptt_early_out = false;
+    ICZ_TRY(low.ensure());
+    return bptt(*G, st);
+}
+
 // xe_backward driven by an upstream gradient w.r.t. the packed logits (Butd::xe_backward_dlogits)
 int Aoa::xe_backward_dlogits(const float* dpacked, const icz_aoa_params* G, hipStream_t st) {
     ICZ_TRY(require_mode(2, "aoa"));
@@ -893,6 +903,13 @@ int icz_aoa_xe_backward_distill(icz_aoa_t* h, const icz_distill_opts* opts, cons
     ICZ_REQUIRE(grads && loss_out3, "icz_aoa_xe_backward_distill: null grads or loss");
     ICZ_REQUIRE(h, "icz_aoa_xe_backward_distill: null handle");
     return a->xe_backward_distill(d, grads, loss_out3, n_tokens_global, (hipStream_t)stream);
+}
+int icz_aoa_xe_backward_swor(icz_aoa_t* h, const icz_swor_opts* opts, int32_t rows, const icz_aoa_params* grads, float* loss_out, void* stream) {
+    SworArgs a;
+    ICZ_TRY(swor_args("icz_aoa_xe_backward_swor", opts, rows, &a));
+    ICZ_REQUIRE(grads && loss_out, "icz_aoa_xe_backward_swor: null grads or loss");
+    ICZ_REQUIRE(h, "icz_aoa_xe_backward_swor: null handle");
+    return reinterpret_cast<Aoa*>(h)->xe_backward_swor(a, rows, grads, loss_out, (hipStream_t)stream);
 }
 int icz_aoa_xe_backward_dlogits(icz_aoa_t* h, const float* dpacked, const icz_aoa_params* grads, void* stream) {
     ICZ_REQUIRE(h, "null handle");

@@ -184,6 +184,7 @@ struct Butd : CaptionHead, DecodeMember {
     int xe_backward_dlogits(const float* dpacked, const icz_butd_params* G, hipStream_t st);
     int xe_backward(float smoothing, const icz_butd_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
     int xe_backward_distill(const DistillArgs& a, const icz_butd_params* G, float* loss_out3, float n_tokens_global, hipStream_t st);
+    int xe_backward_swor(const SworArgs& a, int rows, const icz_butd_params* G, float* loss_out, hipStream_t st);
     int gemm_auto(GemmLayout layout, GemmArgs& g, float* slab, size_t slab_floats, int* ns_out, hipStream_t st);
     // the wgrad slab region of the stream a product is issued on: never shared between streams (TrainBuf::wslab)
     int wslab_of(hipStream_t st) const { return st == low.st ? 1 : 0; }

@@ -474,6 +474,15 @@ int Butd::xe_backward_distill(const DistillArgs& a, const icz_butd_params* G, fl
     return bptt(*G, st);
 }
 
+// xe_backward with the without-replacement SCST head (swor_objective.hip) in the place of xe_loss
+int Butd::xe_backward_swor(const SworArgs& a, int rows, const icz_butd_params* G, float* loss_out, hipStream_t st) {
+    ICZ_TRY(check_swor("butd", rows));
+    ICZ_TRY(swor_loss(a, tb.logit, dims.V, pad_vocab(dims.V), loss_out, st));
+    bptt_early_out = false;
+    ICZ_TRY(bptt_prelude(st));
+    return bptt(*G, st);
+}
+
 // ------------------------------------------------------------------------------------------------
 // helpers for the backward GEMMs
 // direct output (ns = 1, where g.out points) if there are already enough tiles, else slabs in `slab` (null: never split above 64 rows)
@@ -908,6 +917,14 @@ int icz_butd_xe_backward_distill(icz_butd_t* h, const icz_distill_opts* opts, co
     ICZ_REQUIRE(grads && loss_out3, "icz_butd_xe_backward_distill: null grads or loss");
     ICZ_REQUIRE(h, "icz_butd_xe_backward_distill: null handle");
     return b->xe_backward_distill(a, grads, loss_out3, n_tokens_global, (hipStream_t)stream);
+}
+int icz_butd_xe_backward_swor(icz_butd_t* h, const icz_swor_opts* opts, int32_t rows, const icz_butd_params* grads, float* loss_out,
+                              void* stream) {
+    SworArgs a;
+    ICZ_TRY(swor_args("icz_butd_xe_backward_swor", opts, rows, &a));
+    ICZ_REQUIRE(grads && loss_out, "icz_butd_xe_backward_swor: null grads or loss");
+    ICZ_REQUIRE(h, "icz_butd_xe_backward_swor: null handle");
+    return reinterpret_cast<Butd*>(h)->xe_backward_swor(a, rows, grads, loss_out, (hipStream_t)stream);
 }
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }

@@ -204,6 +204,10 @@ struct ScstScratch { float* ent_rows; double* L_img; int* m_img; float* scal; };
 // The loss head of a rollout's backward pass as a decoder calls it: obj null = RewardCriterion on `reward` (loss_out [1]), else the
 // objective (loss_out [3] = {loss, obj, ent}, ent_out [rows, T] or null)
 struct RolloutHead { const float* reward; const ScstObjective* obj; float* loss_out; float* ent_out; float* msum_out; };
+// SCST on without-replacement samples (swor_objective.hip; include/icz.h: icz_swor_opts, checked by swor_args) as the loss head takes it
+struct SworArgs { int n, estimator; float n_img_global; const float* phi; const double* G; const double* scores; const int32_t* perm; double* stats_out; };
+// scratch of its kernels: coef [images n] (-c / N per slot), cs [images n] (coef logp per slot, float64)
+struct SworScratch { float* coef; double* cs; };
 // The caption loss head: host-side state of a stored training-mode forward pass and the loss buffers of all three decoders.
 struct CaptionHead {
     int mode = 0;                 // 0 none, 1 sample rollout stored, 2 XE forward stored
@@ -224,6 +228,7 @@ struct CaptionHead {
     int* live_rows = nullptr;     // (steps the sampled rollout ran) x B: row limit of the backward pass's batched GEMMs
     int* pack_idx = nullptr; int pack_cap = 0;         // packed-sequence index: row_off[T] | rows_t[T]
     double* obj_img = nullptr; int* obj_mimg = nullptr; float* obj_scal = nullptr;      // ScstScratch beside loss_rows (scst_objective)
+    float* swor_coef = nullptr; double* swor_cs = nullptr;      // SworScratch [2 B]: n / (n - 1) <= 3 / 2 slots per stored row (swor_loss)
 
     int alloc_scalars(DeviceBuffers& m);
     int alloc_loss_buffers(DeviceBuffers& m, size_t TB, size_t B, size_t T);
@@ -242,6 +247,11 @@ struct CaptionHead {
     // Distillation (distill.hip): the mixed hard / soft-target loss and dlogits (in place) of the stored XE forward pass against the
     // teachers' packed logits; loss_out3 = {loss, sum hard / N, sum kd / N}.  alpha = 0 is xe_loss.
     int distill_loss(const DistillArgs& a, float n_tokens_global, float* logits, int V, int ldl, float* loss_out3, hipStream_t st);
+    // SCST on without-replacement samples (swor_objective.hip): loss and dlogits (in place) of the stored XE forward pass on the sampled
+    // captions; loss_out [1 + images] = {loss, sum c logp by image}.  check_swor: the rules against the stored forward pass (a
+    // training-mode one, teacher-forced, of `rows` rows), before anything is queued.
+    int check_swor(const char* who, int rows) const;
+    int swor_loss(const SworArgs& a, float* logits, int V, int ldl, float* loss_out, hipStream_t st);
     int require_teacher_forced(const char* who) const;      // the stored XE forward pass fed the captions' own tokens (no scheduled sampling)
     // REINFORCE: loss, mask sum and dlogits (in place) of the stored rollout; rows / row0: rows per step slot and the first of the
     // sampled rollout's (a merged SCST chain stores 2 B rows per slot)
@@ -270,6 +280,11 @@ int scst_objective_args(const char* who, const icz_scst_objective* o, int rows, 
 int launch_scst_objective(const ScstObjective& o, const float* logp, const int64_t* seq, int B, int T, const float* msum_dev,
                           const ScstScratch& w, float* coef, float* out3, float* ent_out, float* msum_out, float* logits, int V, int ldl,
                           const int32_t* draw, const float* lse, int rows, int row0, hipStream_t st);
+
+// The launch site of the without-replacement SCST head, shared by CaptionHead::swor_loss and icz_test_swor_objective
+int swor_args(const char* who, const icz_swor_opts* o, int rows, SworArgs* out);
+int launch_swor_objective(const SworArgs& a, float* logits, int V, int ldl, const int64_t* captions, int L, int B, int T, const int* rows_t,
+                          const SworScratch& w, float* loss_rows, float* loss_out, hipStream_t st);
 
 // Where one decoder step left its logits: ns == 1 finished rows [rows][ld]; ns > 1 the predict GEMM's split-K slabs [ns][rows][ld]
 // (slab z at p + z * slab_stride, no bias yet) + bias[v], summed in slab order as greedy_select_kernel / sample_select_kernel do.

@@ -63,6 +63,8 @@ int CaptionHead::alloc_loss_buffers(DeviceBuffers& m, size_t TB, size_t B, size_
     ICZ_TRY(m.alloc((void**)&obj_img, sizeof(double) * B));
     ICZ_TRY(m.alloc((void**)&obj_mimg, sizeof(int) * B));
     ICZ_TRY(m.alloc((void**)&obj_scal, 16));
+    ICZ_TRY(m.alloc((void**)&swor_coef, sizeof(float) * 2 * B));
+    ICZ_TRY(m.alloc((void**)&swor_cs, sizeof(double) * 2 * B));
     return ICZ_OK;
 }
 
@@ -70,6 +72,7 @@ void CaptionHead::drop_loss_buffers() {
     coef = lse = loss_rows = kd_rows = nullptr; draw = nullptr; unf = gunf = nullptr; nunf = gnunf = live_rows = pack_idx = nullptr;
     pack_cap = 0;
     obj_img = nullptr; obj_mimg = nullptr; obj_scal = nullptr;
+    swor_coef = nullptr; swor_cs = nullptr;
     mode = 0;
 }
 

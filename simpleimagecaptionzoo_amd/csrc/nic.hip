@@ -61,6 +61,7 @@ struct Nic : CaptionHead, DecodeMember {
                    float* packed_out, hipStream_t st);
     int xe_backward(float smoothing, const icz_nic_params* G, float* dfeats, float* loss_out, float n_tokens_global, hipStream_t st);
     int xe_backward_distill(const DistillArgs& a, const icz_nic_params* G, float* dfeats, float* loss_out3, float n_tokens_global, hipStream_t st);
+    int xe_backward_swor(const SworArgs& a, int rows, const icz_nic_params* G, float* dfeats, float* loss_out, hipStream_t st);
     int xe_backward_dlogits(const float* dpacked, const icz_nic_params* G, float* dfeats, hipStream_t st);
     int bptt(const icz_nic_params& G, float* dfeats, hipStream_t st);
     int nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* out, int* ns, int target, hipStream_t st,
@@ -341,6 +342,14 @@ int Nic::xe_backward_distill(const DistillArgs& a, const icz_nic_params* G, floa
     return bptt(*G, dfeats, st);
 }
 
+// xe_backward with the without-replacement SCST head (swor_objective.hip) in the place of xe_loss
+int Nic::xe_backward_swor(const SworArgs& a, int rows, const icz_nic_params* G, float* dfeats, float* loss_out, hipStream_t st) {
+    ICZ_TRY(check_swor("nic", rows));
+    ICZ_TRY(swor_loss(a, tlogit, dims.V, Vp, loss_out, st));
+    bptt_early_out = false;
+    return bptt(*G, dfeats, st);
+}
+
 // xe_backward driven by an upstream gradient w.r.t. the packed logits (Butd::xe_backward_dlogits)
 int Nic::xe_backward_dlogits(const float* dpacked, const icz_nic_params* G, float* dfeats, hipStream_t st) {
     ICZ_TRY(require_mode(2, "nic"));
@@ -516,6 +525,14 @@ int icz_nic_xe_backward_distill(icz_nic_t* h, const icz_distill_opts* opts, cons
     ICZ_REQUIRE(grads && loss_out3, "icz_nic_xe_backward_distill: null grads or loss");
     ICZ_REQUIRE(h, "icz_nic_xe_backward_distill: null handle");
     return n->xe_backward_distill(a, grads, dfeatures_out, loss_out3, n_tokens_global, (hipStream_t)stream);
+}
+int icz_nic_xe_backward_swor(icz_nic_t* h, const icz_swor_opts* opts, int32_t rows, const icz_nic_params* grads, float* dfeatures_out,
+                             float* loss_out, void* stream) {
+    SworArgs a;
+    ICZ_TRY(swor_args("icz_nic_xe_backward_swor", opts, rows, &a));
+    ICZ_REQUIRE(grads && loss_out, "icz_nic_xe_backward_swor: null grads or loss");
+    ICZ_REQUIRE(h, "icz_nic_xe_backward_swor: null handle");
+    return reinterpret_cast<Nic*>(h)->xe_backward_swor(a, rows, grads, dfeatures_out, loss_out, (hipStream_t)stream);
 }
 int icz_nic_xe_backward_dlogits(icz_nic_t* h, const float* dpacked, const icz_nic_params* grads, float* dfeatures_out, void* stream) {
     ICZ_REQUIRE(h, "null handle");

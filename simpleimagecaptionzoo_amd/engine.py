@@ -224,6 +224,45 @@ class Engine(object):
         with _on_stream(self):
             return self._scst_training_epoch(dataloader, optimizer, criterion, tqdm_visible, rngs, k, obj)
 
+    def SCST_distinct_training_epoch(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, samples_per_image=5,
+                                     estimator="normalised"):
+        """Beyond the reference, for every decoder family: SCST on samples drawn WITHOUT replacement (swor.py).  Per step,
+        n = samples_per_image (3..8) distinct captions per image come from stochastic beam search at temperature 1 in evaluation
+        mode (stochastic_beam.sample_distinct); the last slot of an image is only the threshold, its n - 1 others are the samples;
+        every slot is scored by CIDEr-D; the samples go through a training-mode teacher-forced forward (dropout on) and
+        xe_backward_swor weighs them: estimator "normalised" (default; biased, low variance) or "unbiased".  The gradient-reduce
+        hooks, the 0.25 clamp and Adam are SCST_training_epoch's; data-parallel, the all-reduced image count is the normaliser.
+        `rngs` (tests) supplies per batch a pair (sample_distinct's rng, the forward's icz_rng).  Returns the loss per step; the
+        per-step stats (images, 3) = {W, baseline, effective sample size} stay in self.last_swor_stats.  Every row of the forward
+        repeats its image's features and per-image prologue.  ValueError, before any device work, for a bad samples_per_image or
+        estimator, B n above the handle's row capacity, scheduled sampling live, or a batch with per-image region counts
+        (repeating a RegionBatch per row is out of this method's scope)."""
+        from .swor import check_args
+        n, _, _ = check_args(samples_per_image, estimator)
+        if self.model.scheduled_sampling and float(self.model.ss_prob) > 0.0:
+            raise ValueError("scheduled sampling is live (ss_prob %g): the forward pass would be fed other tokens than the sampled captions"
+                             % float(self.model.ss_prob))
+        with _on_stream(self):
+            return self._scst_distinct_training_epoch(dataloader, optimizer, tqdm_visible, rngs, n, estimator)
+
+
+def _check_distinct_batch(n_img, n, max_rows, supp_info_datas):
+    """The per-batch refusals of SCST_distinct_training_epoch, looked at before the step touches the device"""
+    if n_img * n > max_rows:
+        raise ValueError("%d images x %d slots exceed the handle's row capacity %d" % (n_img, n, max_rows))
+    if _has_region_counts(supp_info_datas):
+        raise ValueError("a batch with per-image region counts: SCST on distinct samples repeats one feature tensor per row")
+
+
+def _has_region_counts(supp_info_datas):
+    """whether a batch carries per-image region counts (a resident batch with `bu_counts`, or host features of unequal row counts)"""
+    if isinstance(supp_info_datas, dict):
+        return supp_info_datas.get("bu_counts") is not None
+    try:
+        return len({int(s["bu_feat"].shape[0]) for s in supp_info_datas}) > 1
+    except (TypeError, KeyError, IndexError, AttributeError):
+        return False
+
 
 def _scst_objective_args(risk, k, risk_alpha, entropy_weight):
     """The objective arguments of an SCST epoch (risk: minimum-risk training, else the step's reward) -> None (today's calls: the
@@ -624,6 +663,47 @@ class BUTDDetection_Eng(Engine):
             losses.append(loss.clone())      # with graphs the handle returns one persistent buffer, overwritten by the next step
             if tqdm_visible:
                 monitor.set_postfix(Loss=np.round(loss.item(), decimals=4))
+
+    def _scst_distinct_training_epoch(self, dataloader, optimizer, tqdm_visible, rngs, n, estimator):
+        """SCST_distinct_training_epoch's steps: sample_distinct, reward_loo's scores, make_batch, the training-mode forward,
+        xe_backward_swor, then _scst_steps' tail"""
+        from .stochastic_beam import sample_distinct
+        from .swor import make_batch, swor_forward, xe_backward_swor
+        self.model.train()
+        scorer = self.scorer()
+        dataloader, restore = _cook_ahead(dataloader, scorer, self.device, getattr(self, "cook_ahead", True),
+                                          self.__dict__.setdefault("_cook_cache", {}))
+        monitor = _monitor(dataloader, "Training Process", tqdm_visible)
+        sta = self.caption_vocab.word2ix["<sta>"]
+        losses, self.last_swor_stats = [], []
+        try:
+            for batch_i, (img_ids, img_tensors, img_gts, supp_info_datas) in enumerate(monitor):
+                _check_distinct_batch(len(img_ids), n, self.model.max_rows, supp_info_datas)      # before the step's device work
+                visual_inputs = self.modify_visual_inputs(img_tensors=img_tensors, supp_info_datas=supp_info_datas)
+                feats = self._features(visual_inputs)
+                h = self.model._handle()
+                if rngs is not None:
+                    s_rng, f_rng = rngs[batch_i]
+                else:
+                    f_rng = self.model._next_rng()
+                    s_rng = icz_dist.seed_for_rank(self.model._seed)
+                ids, lens, _fin, phi, G = sample_distinct(h, feats, n, 20, 1.0, s_rng)
+                _, scores = scorer.reward_loo(ids, n, img_gts, img_ids, return_scores=True)
+                batch = make_batch(ids, lens, sta, n)
+                swor_forward(h, feats, batch, f_rng)
+                grads = self._grads()
+                n_glob = icz_dist.all_reduce_scalar(float(len(img_ids))) if icz_dist.is_distributed() else 0.0
+                ov = self._reduce_grads_begin(h)
+                (loss, _by_image), stats = xe_backward_swor(h, grads, phi, G, scores, batch, estimator, n_glob)
+                self._reduce_grads_end(ov)
+                self._apply(optimizer, 0.25)
+                self.last_swor_stats.append(stats)
+                losses.append(loss.clone())
+                if tqdm_visible:
+                    monitor.set_postfix(Loss=np.round(loss.item(), decimals=4))
+        finally:
+            restore()
+        return losses
 
     # ---- E3 -------------------------------------------------------------------------------------------------
     def eval_captions_json_generation(self, dataloader, eval_beam_size=-1, tqdm_visible=True, *, length_penalty=None, block_ngram=0,

@@ -17,7 +17,7 @@ from .scheduled import ScheduledSamplingState
 _ENTRIES = ("create", "destroy", "bind_params", "refresh_weights", "set_option", "set_grad_callback", "set_scheduled_sampling",
             "set_norm_global", "greedy", "sample", "scst_rollouts", "sample_backward", "xe_forward", "xe_backward", "beam_search",
             "beam_search_opts", "beam_search_diverse", "beam_search_constrained", "sample_decode", "sample_distinct", "score_captions", "xe_backward_distill",
-            "sample_backward_objective")
+            "sample_backward_objective", "xe_backward_swor")
 
 
 class DecoderHandle:
