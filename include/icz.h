@@ -188,6 +188,25 @@ int icz_butd_xe_forward(icz_butd_t* h, const float* feats, const int64_t* captio
                         float* packed_logits_out, void* stream);
 int icz_butd_xe_backward(icz_butd_t* h, float smoothing, const icz_butd_params* grads, float* loss_out,
                          float n_tokens_global, void* stream);
+/* Beyond the reference (whose loader hands every annotation over as a row of its own, Datasets.py:47-51): teacher-forced XE on K = 2..8
+ * captions per image, the regime of seq_per_img = 5, in the layout of icz_butd_sample_n.  feats [B, R, D], one feature set per image;
+ * captions [B K, L] int64, row = img * K + k, each with its leading <sta> and zero padded, in ANY length order (nothing is sorted);
+ * lengths_host [B K] = len - 1 as for icz_butd_xe_forward, each in 1..L-1; T = max(lengths); B K <= max_rows.  The per-image work
+ * (enc_att(feats), the mean features, the hoisted part of the TD gates) runs once over the B images, the teacher-forced chain over the
+ * B K rows (grouped attention kernels where option "group_att" is on).  A row that has ended is fed <pad> and its later steps carry no
+ * loss.  Dropout keep-bits and Philox indices are those of row img * K + k in the B K space: explicit icz_rng arrays are laid out
+ * [T, B K, ...], and row r gets what row r of icz_butd_sample_n gets.  Region counts (icz_butd_set_regions) are per image, as there.
+ * logits_out: NULL, or [B K, T, V] with zeros at t >= the row's length.  The call is eager (no graph capture), as icz_butd_xe_forward.
+ * Refused, in this order, each before anything is queued and with the handle left as it was:
+ *   1 null feats, captions or lengths_host;  2 K outside 2..8;  3 B < 1, L < 2 or a length outside 1..L-1;  (a null handle);
+ *   4 B K above the row capacity, or more images than region counts were set for;  5 weights not refreshed;  6 train without an rng;
+ *   7 scheduled sampling switched on (icz_butd_set_scheduled_sampling).
+ * icz_butd_xe_backward then runs the same loss over the image-major rows (mask t < length of the row) and the backward pass with the
+ * image-side products folded onto the B images; n_tokens_global as above in all three forms.  icz_butd_saved_alphas returns [B K, T, R]
+ * (the steps behind a row's end hold the attention of its <pad> steps).  icz_butd_xe_backward_dlogits, icz_butd_xe_backward_distill and
+ * icz_butd_xe_backward_swor work on packed, length-sorted rows and refuse a stored grouped forward by name; it stays stored. */
+int icz_butd_xe_forward_n(icz_butd_t* h, const float* feats, const int64_t* captions, int32_t B, int32_t K, int32_t L,
+                          const int32_t* lengths_host, const icz_rng* rng, int32_t train, float* logits_out, void* stream);
 
 /* Scheduled sampling in DecoderRNN.forward (BUTD_Model.py:120-132; the decoder attribute `ss_prob`, which
  * Engine.py:140-144 means to raise per epoch but sets on the Captioner, where nothing reads it): from time step 2 on,
@@ -199,7 +218,7 @@ int icz_butd_xe_backward(icz_butd_t* h, float smoothing, const icz_butd_params* 
 int icz_butd_set_scheduled_sampling(icz_butd_t* h, float ss_prob, const float* gate_uniforms, const float* draw_uniforms);
 
 /* Attention maps of the forward pass the handle holds (the last icz_butd_xe_forward or icz_butd_sample of B rows and T
- * steps): alphas_out [B, T, R].  A teacher-forced evaluation-mode forward over a decoded sentence yields the alphas the
+ * steps, or icz_butd_xe_forward_n of B K rows): alphas_out [B, T, R].  A teacher-forced evaluation-mode forward over a decoded sentence yields the alphas the
  * reference's sample / beam_search_sample return beside the ids (BUTD_Model.py:178-189, :309-317), which
  * eval_test_image hands to show_additional_rlt (Engine.py:325,339). */
 int icz_butd_saved_alphas(icz_butd_t* h, float* alphas_out, void* stream);
@@ -1333,6 +1352,14 @@ int icz_test_ss_select(const float* logits_prev, int32_t rows, int32_t B, int32_
  * loss_out (optional) = their sum / N. */
 int icz_test_xe_loss(float* logits, int32_t V, int32_t ldl, const int64_t* captions, int32_t L, int32_t B, int32_t T, const int32_t* rows_t,
                      float smoothing, float n_tokens, const float* n_dev, float* loss_rows, float* loss_out, void* stream);
+/* The same loss over image-major rows (xe_group_loss_dlogits_kernel + sum_scale_kernel; what icz_butd_xe_backward runs behind
+ * icz_butd_xe_forward_n): lengths [rows] is a DEVICE array of per-row step counts, each 0..T (read back and checked), and (row, t) is
+ * active while t < lengths[row], in any order of the rows.  An inactive (row, t) is written as zeros without being read and leaves 0 in
+ * loss_rows; an active one gives the bits icz_test_xe_loss gives for it.  ldl % 4 == 0 and logits 16-byte aligned.  N = *n_dev if given
+ * and positive, else n_tokens if positive, else (n_tokens == 0) the sum of the lengths. */
+int icz_test_xe_group_loss(float* logits, int32_t V, int32_t ldl, const int64_t* captions, int32_t L, int32_t rows, int32_t T,
+                           const int32_t* lengths, float smoothing, float n_tokens, const float* n_dev, float* loss_rows, float* loss_out,
+                           void* stream);
 /* RewardCriterion and its gradient (reinforce_loss_kernel + reinforce_dlogits_kernel): logp, seq, reward, coef [B, T]; mask[b, 0] = 1,
  * mask[b, t] = seq[b, t - 1] > 0; denominator = *mask_sum_global if given and positive, else sum(mask); loss_out / mask_sum_out optional.
  * logits [T Bs', ldl] (Bs' = Bs or B), draw / lse [T Bs']: dlogits[row, v] = coef[b, t] (1[v == draw] - exp(logits - lse)) in place, zero

@@ -267,6 +267,7 @@ def lib():
         "icz_butd_sample_mask_sum": (C.c_int, [vp, vp, vp]),
         "icz_butd_xe_forward": (C.c_int, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Rng), i32, vp, vp]),
         "icz_butd_xe_backward": (C.c_int, [vp, f32, C.POINTER(ButdParams), vp, f32, vp]),
+        "icz_butd_xe_forward_n": (C.c_int, [vp, vp, vp, i32, i32, i32, C.POINTER(i32), C.POINTER(Rng), i32, vp, vp]),
         "icz_butd_set_scheduled_sampling": (C.c_int, [vp, f32, vp, vp]),
         "icz_nic_set_scheduled_sampling": (C.c_int, [vp, f32, vp, vp]),
         "icz_aoa_set_scheduled_sampling": (C.c_int, [vp, f32, vp, vp]),
@@ -418,6 +419,7 @@ def lib():
         "icz_test_sample_select": (C.c_int, [C.POINTER(SampleSelectArgs), i32, vp]),
         "icz_test_ss_select": (C.c_int, [vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
         "icz_test_xe_loss": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, C.POINTER(i32), f32, f32, vp, vp, vp, vp]),
+        "icz_test_xe_group_loss": (C.c_int, [vp, i32, i32, vp, i32, i32, i32, vp, f32, f32, vp, vp, vp, vp]),
         "icz_test_reinforce": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp]),
         "icz_test_aoa_layer_norm": (C.c_int, [i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
         "icz_aoa_self_attn_route_for": (C.c_int, [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_size_t)]),

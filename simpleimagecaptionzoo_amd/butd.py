@@ -34,7 +34,7 @@ class ButdHandle(RegionSets, GraphDecoderHandle):
     family, kind = "butd", 0
     _Params, _param_keys = ButdParams, BUTD_PARAM_KEYS
     _make_rng = staticmethod(make_rng)
-    _own_entries = ("create_regions", "set_regions", "step", "sample_n", "sample_mask_sum", "saved_alphas", "sample_backward_dlogp", "xe_backward_dlogits")
+    _own_entries = ("create_regions", "set_regions", "step", "sample_n", "xe_forward_n", "sample_mask_sum", "saved_alphas", "sample_backward_dlogp", "xe_backward_dlogits")
     _entry_names = {"set_norm_global": "set_mask_sum_global"}
     _sample_bufs = True
 

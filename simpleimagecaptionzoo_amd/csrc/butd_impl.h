@@ -50,6 +50,7 @@ struct TrainBuf {
     int32_t* img2 = nullptr;                                  // merged chain: image of each decoder row (row r of 2 B -> image r mod B)
     int32_t* imgk = nullptr;                                  // multi-sample rollout: image of each decoder row (row r of B K -> image r / K)
     float* dEncImg = nullptr;                                 // multi-sample backward: d enc_ctx folded onto the images [n_img, R, A]
+    int32_t* lenk = nullptr;                                  // grouped XE forward: steps of each decoder row (row r of B K, in any length order)
     float *dGtd = nullptr, *dGlm = nullptr, *dDec = nullptr, *dEmb = nullptr, *dH2d = nullptr, *dEnc = nullptr;
     float *dwaff = nullptr, *dalpha = nullptr, *dS = nullptr, *dGsum = nullptr;
     float *dc1[2] = {nullptr, nullptr}, *dc2[2] = {nullptr, nullptr};
@@ -143,6 +144,7 @@ struct Butd : CaptionHead, DecodeMember {
                                          // kernel as two launches (seven).  The same bits either way
     // multi-sample SCST rollout (sample_n, beyond the reference): K sampled rows per image, row = img * K + k, sharing the image's
     // hoisted tensors.  cur_K = rows per image of the stored rollout (1 = every other entry point), cur_nimg = its image count.
+    // xe_forward_n stores its teacher-forced forward pass in the same layout (mode 2 with cur_K > 1: xe_grouped()).
     int cur_K = 1, cur_nimg = 0;
     bool group_att = false;              // option "group_att": 1 = sample_n's attention (forward scores / context, backward d enc_ctx) runs on
                                          // the grouped kernels (each image's features / enc_ctx read once for its K rows); 0 (default) = the
@@ -178,6 +180,11 @@ struct Butd : CaptionHead, DecodeMember {
                         float mask_sum_global, hipStream_t st);
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r,
                    int train, float* packed_out, hipStream_t st);
+    // teacher-forced XE on K captions per image (beyond the reference): sample_n's layout -- the prologue once per image, the chain over
+    // the B K image-major rows, every row stored at every step (a row that has ended is fed <pad>; rows_t = B K throughout)
+    int xe_forward_n(const float* feats, const int64_t* captions, int B, int K, int L, const int32_t* lengths, const icz_rng* r,
+                     int train, float* logits_out, hipStream_t st);
+    bool xe_grouped() const { return mode == 2 && cur_K > 1; }      // the stored forward pass is xe_forward_n's
     int sample_backward_objective(const icz_scst_objective* obj, const icz_butd_params* G, float* loss_out3, float* ent_out, float* mask_sum_out,
                                   float mask_sum_global, hipStream_t st);
     int sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hipStream_t st);

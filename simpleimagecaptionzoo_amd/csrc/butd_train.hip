@@ -63,6 +63,7 @@ int Butd::ensure_train(int B, int T) {
     ICZ_TRY(alloc((void**)&tb.nany, sizeof(int) * T));
     ICZ_TRY(alloc((void**)&tb.img2, sizeof(int32_t) * B));
     ICZ_TRY(alloc((void**)&tb.imgk, sizeof(int32_t) * B));
+    ICZ_TRY(alloc((void**)&tb.lenk, sizeof(int32_t) * B));
     ICZ_TRY(alloc((void**)&tb.dGtd, sizeof(float) * TB * 4 * H));
     ICZ_TRY(alloc((void**)&tb.dGlm, sizeof(float) * TB * 4 * H));
     ICZ_TRY(alloc((void**)&tb.dDec, sizeof(float) * TB * A));
@@ -430,8 +431,75 @@ int Butd::xe_forward(const float* feats, const int64_t* captions, int B, int L, 
     return ICZ_OK;
 }
 
+// Teacher-forced XE on K captions per image (beyond the reference; the regime of seq_per_img = 5): sample_n's layout with the captions'
+// tokens in the place of the draws.  The prologue runs once over the B images; the chain runs over the B K rows, row = img * K + k in
+// any length order, on the stored-activation slots (slot stride B K rows), finding the image through tb.imgk.  Every row runs every
+// step: a row that has ended is fed <pad>, its later steps are masked by the loss (xe_group_loss: t < tb.lenk[row]) and so carry
+// zero gradient rows through bptt().  Dropout keep-bits are those of row img * K + k in the B K space, as sample_n's.
+// The refusals of include/icz.h in their order (1 - 3 stand in front of the handle, in the C entry's xe_forward_n_args), each before
+// anything is queued or any state of the handle is touched.
+static int xe_forward_n_args(const char* who, const float* feats, const int64_t* captions, int B, int K, int L, const int32_t* lengths) {
+    ICZ_REQUIRE(feats && captions && lengths, "%s: null feats, captions or lengths_host", who);
+    ICZ_REQUIRE(K >= 2 && K <= ATT_CTX_MAX_G, "%s: K=%d captions per image outside 2..%d", who, K, ATT_CTX_MAX_G);
+    ICZ_REQUIRE(B >= 1 && B <= (1 << 20) && L >= 2, "%s: B=%d images (at least 1) or L=%d columns (at least 2)", who, B, L);
+    for (int i = 0; i < B * K; ++i)
+        ICZ_REQUIRE(lengths[i] >= 1 && lengths[i] <= L - 1, "%s: lengths_host[%d]=%d outside 1..%d", who, i, lengths[i], L - 1);
+    return ICZ_OK;
+}
+
+int Butd::xe_forward_n(const float* feats, const int64_t* captions, int B, int K, int L, const int32_t* lengths, const icz_rng* r,
+                       int train, float* logits_out, hipStream_t st) {
+    const char* who = "butd xe_forward_n";
+    ICZ_TRY(xe_forward_n_args(who, feats, captions, B, K, L, lengths));
+    ICZ_REQUIRE((int64_t)B * K <= dims.max_rows, "%s: %d images x %d captions exceed the row capacity %d", who, B, K, dims.max_rows);
+    ICZ_TRY(check_counts(B));
+    ICZ_REQUIRE(fresh, "%s: call icz_butd_refresh_weights after binding/updating parameters", who);
+    ICZ_REQUIRE(!train || r, "%s: training mode needs an icz_rng", who);
+    ICZ_REQUIRE(ss_prob <= 0.f, "%s: scheduled sampling is switched on (ss_prob %g); the grouped forward feeds the captions' own tokens", who,
+                (double)ss_prob);
+    const int rows = B * K;
+    int T = 0;
+    for (int i = 0; i < rows; ++i) T = lengths[i] > T ? lengths[i] : T;
+    ICZ_TRY(ensure_train(rows, T));
+    if (r) rng = *r; else { rng = {}; }
+    begin_xe(lengths, rows, T, L, captions, train != 0, rng.seed, st);
+    rows_t.assign(T, rows);            // every row is stored at every step; n_tokens stays the sum of the lengths
+    cur_feats = feats;
+    cur_rows = rows; cur_row0 = 0; cur_K = K; cur_nimg = B;
+    const size_t H = dims.H;
+    const size_t Vp = pad_vocab(dims.V);
+    ICZ_TRY(prologue(feats, B, st));
+    hipLaunchKernelGGL(row_image_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, tb.imgk, rows, K);
+    upload_lengths(tb.lenk, lengths, rows, st);
+    {
+        ZeroList z = {{tb.h1, tb.c1, tb.h2, tb.c2}, 4};
+        const size_t n = (size_t)rows * H;
+        hipLaunchKernelGGL(zero_bufs_kernel, dim3(cdiv((int)(n / 4), 256)), dim3(256), 0, st, z, n);
+    }
+    launch_captions_to_tok_len(captions, rows, L, T, tb.lenk, tb.tok, st);
+    // as xe_forward: one embedding launch and one vocabulary projection over all (t, row), the slot addressing being the same
+    const bool batched_predict = T * rows >= 128;
+    const bool batched_embed = T <= EMB_MAX_T && dims.E % 4 == 0;
+    if (batched_embed) {
+        EmbRows er = {};
+        for (int t = 0; t < T; ++t) er.n[t] = rows;
+        hipLaunchKernelGGL(embed_steps_kernel, dim3(cdiv(dims.E, 1024), T * rows), dim3(256), 0, st, P.embed_weight, tb.tok, tb.emb, rows, dims.E, er,
+                           make_drop(d_seed, train != 0, rng.emb_mask, (size_t)rows * dims.E, RNG_EMB, 0));
+    }
+    for (int t = 0; t < T; ++t) ICZ_TRY(train_step(feats, rows, rows, t, train != 0, st, batched_embed, nullptr, batched_predict));
+    if (batched_predict) {
+        GemmArgs g = gemm_args({{tb.h2d, w_pred, (int)H, (int)H, (int)H}}, T * rows, dims.V, tb.logit, (int)Vp);
+        g.bias = P.predict_b;
+        ICZ_TRY(gemm_f32(GEMM_NT, g, st));
+    }
+    if (logits_out) launch_gather_rows(tb.logit, dims.V, (int)Vp, rows, T, tb.lenk, logits_out, st);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
 int Butd::xe_backward_dlogits(const float* dpacked, const icz_butd_params* G, hipStream_t st) {
     ICZ_TRY(require_mode(2, "butd"));
+    ICZ_REQUIRE(!xe_grouped(), "icz_butd_xe_backward_dlogits: the stored forward pass is a grouped one (icz_butd_xe_forward_n): its logits are not packed");
     ICZ_REQUIRE(dpacked && G, "butd xe_backward_dlogits: null argument");
     ICZ_TRY(scatter_packed(dpacked, dims.V, pad_vocab(dims.V), tb.logit, st));
     mode = 0;
@@ -458,7 +526,9 @@ int Butd::sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hi
 int Butd::xe_backward(float smoothing, const icz_butd_params* G, float* loss_out, float n_tokens_global, hipStream_t st) {
     ICZ_TRY(require_mode(2, "butd"));
     ICZ_REQUIRE(G, "butd xe_backward: null grads");
-    ICZ_TRY(xe_loss(smoothing, n_tokens_global, tb.logit, dims.V, pad_vocab(dims.V), loss_out, st));
+    // behind xe_forward_n: the loss over image-major rows; cur_K stays, so bptt() folds the image-side products onto the images
+    if (xe_grouped()) ICZ_TRY(xe_group_loss(tb.lenk, smoothing, n_tokens_global, tb.logit, dims.V, pad_vocab(dims.V), loss_out, st));
+    else ICZ_TRY(xe_loss(smoothing, n_tokens_global, tb.logit, dims.V, pad_vocab(dims.V), loss_out, st));
     bptt_early_out = false;
     ICZ_TRY(bptt_prelude(st));
     return bptt(*G, st);
@@ -467,6 +537,7 @@ int Butd::xe_backward(float smoothing, const icz_butd_params* G, float* loss_out
 // xe_backward with the distillation loss (distill.hip) in the place of xe_loss
 int Butd::xe_backward_distill(const DistillArgs& a, const icz_butd_params* G, float* loss_out3, float n_tokens_global, hipStream_t st) {
     ICZ_TRY(require_mode(2, "butd"));
+    ICZ_REQUIRE(!xe_grouped(), "icz_butd_xe_backward_distill: the stored forward pass is a grouped one (icz_butd_xe_forward_n): the teachers' logits are packed");
     ICZ_TRY(require_teacher_forced("butd xe_backward_distill"));
     ICZ_TRY(distill_loss(a, n_tokens_global, tb.logit, dims.V, pad_vocab(dims.V), loss_out3, st));
     bptt_early_out = false;
@@ -476,6 +547,7 @@ int Butd::xe_backward_distill(const DistillArgs& a, const icz_butd_params* G, fl
 
 // xe_backward with the without-replacement SCST head (swor_objective.hip) in the place of xe_loss
 int Butd::xe_backward_swor(const SworArgs& a, int rows, const icz_butd_params* G, float* loss_out, hipStream_t st) {
+    ICZ_REQUIRE(!xe_grouped(), "icz_butd_xe_backward_swor: the stored forward pass is a grouped one (icz_butd_xe_forward_n): its rows are not sorted by length");
     ICZ_TRY(check_swor("butd", rows));
     ICZ_TRY(swor_loss(a, tb.logit, dims.V, pad_vocab(dims.V), loss_out, st));
     bptt_early_out = false;
@@ -903,6 +975,12 @@ int icz_butd_xe_forward(icz_butd_t* h, const float* feats, const int64_t* captio
                         void* stream) {
     ICZ_REQUIRE(h, "null handle");
     return reinterpret_cast<Butd*>(h)->xe_forward(feats, captions, B, L, lengths_host, rng, train, packed_logits_out, (hipStream_t)stream);
+}
+int icz_butd_xe_forward_n(icz_butd_t* h, const float* feats, const int64_t* captions, int32_t B, int32_t K, int32_t L,
+                          const int32_t* lengths_host, const icz_rng* rng, int32_t train, float* logits_out, void* stream) {
+    ICZ_TRY(xe_forward_n_args("icz_butd_xe_forward_n", feats, captions, B, K, L, lengths_host));
+    ICZ_REQUIRE(h, "icz_butd_xe_forward_n: null handle");
+    return reinterpret_cast<Butd*>(h)->xe_forward_n(feats, captions, B, K, L, lengths_host, rng, train, logits_out, (hipStream_t)stream);
 }
 int icz_butd_xe_backward(icz_butd_t* h, float smoothing, const icz_butd_params* grads, float* loss_out,
                          float n_tokens_global, void* stream) {

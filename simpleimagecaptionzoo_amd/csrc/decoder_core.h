@@ -244,6 +244,8 @@ struct CaptionHead {
     int scatter_packed(const float* dpacked, int V, int ldl, float* logit, hipStream_t st);
     // LabelSmoothingLoss: loss and dlogits (in place) of the stored XE forward pass
     int xe_loss(float smoothing, float n_tokens_global, float* logits, int V, int ldl, float* loss_out, hipStream_t st);
+    // the same behind a grouped XE forward (cur_B image-major rows, every row stored at every step): the mask is t < len[row] (device)
+    int xe_group_loss(const int32_t* len, float smoothing, float n_tokens_global, float* logits, int V, int ldl, float* loss_out, hipStream_t st);
     // Distillation (distill.hip): the mixed hard / soft-target loss and dlogits (in place) of the stored XE forward pass against the
     // teachers' packed logits; loss_out3 = {loss, sum hard / N, sum kd / N}.  alpha = 0 is xe_loss.
     int distill_loss(const DistillArgs& a, float n_tokens_global, float* logits, int V, int ldl, float* loss_out3, hipStream_t st);
@@ -274,6 +276,15 @@ int launch_xe_loss(float* logits, int V, int ldl, const int64_t* captions, int L
                    const float* n_dev, float* loss_rows, float* loss_out, hipStream_t st);
 int launch_reinforce(const float* logp, const int64_t* seq, const float* reward, int B, int T, const float* msum_dev, float* coef, float* loss_out,
                      float* msum_out, float* logits, int V, int ldl, const int32_t* draw, const float* lse, int rows, int row0, hipStream_t st);
+// The XE loss head over image-major rows (xe_group_loss_dlogits_kernel + sum_scale_kernel), shared by CaptionHead::xe_group_loss and
+// icz_test_xe_group_loss: len [rows] (device) = steps of each row, the active (row, t) are those with t < len[row]; every (row, t) of
+// loss_rows [T rows] is written.  Beside it the other pieces of a grouped XE forward: the host step counts -> device (kernel arguments,
+// no copy), the token rows (<pad> behind a row's end) and the logits out [rows, T, V] (zeros behind a row's end).
+int launch_xe_group_loss(float* logits, int V, int ldl, const int64_t* captions, int L, int rows, int T, const int32_t* len, float smoothing,
+                         float n, const float* n_dev, float* loss_rows, float* loss_out, hipStream_t st);
+void upload_lengths(int32_t* dst, const int32_t* lengths_host, int n, hipStream_t st);
+void launch_captions_to_tok_len(const int64_t* captions, int rows, int L, int T, const int32_t* len, int64_t* tok, hipStream_t st);
+void launch_gather_rows(const float* logit, int V, int ldl, int rows, int T, const int32_t* len, float* out, hipStream_t st);
 
 // The launch site of the SCST objectives, shared by CaptionHead::scst_objective and icz_test_scst_objective; arguments as launch_reinforce
 int scst_objective_args(const char* who, const icz_scst_objective* o, int rows, int T, ScstObjective* out);

@@ -160,6 +160,66 @@ int CaptionHead::xe_loss(float smoothing, float n_tokens_global, float* logits, 
     return ICZ_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The grouped XE forward (K captions per image, rows image-major in any length order): per-row step counts on the device in the place
+// of rows_t.  The host array reaches the device as kernel arguments, 256 counts per launch: no copy from the caller's pageable memory,
+// so nothing to wait for and nothing that outlives the call.
+struct LenChunk { int32_t n[256]; };
+__global__ void set_lengths_kernel(int32_t* __restrict__ dst, int n, LenChunk c) {
+    if ((int)threadIdx.x < n) dst[threadIdx.x] = c.n[threadIdx.x];
+}
+void upload_lengths(int32_t* dst, const int32_t* lengths_host, int n, hipStream_t st) {
+    for (int i = 0; i < n; i += 256) {
+        LenChunk c = {};
+        const int m = n - i < 256 ? n - i : 256;
+        for (int j = 0; j < m; ++j) c.n[j] = lengths_host[i + j];
+        hipLaunchKernelGGL(set_lengths_kernel, dim3(1), dim3(256), 0, st, dst + i, m, c);
+    }
+}
+// tok[t, row] = captions[row, t] while the row runs, <pad> behind its end (whatever the caller's row holds there)
+__global__ void captions_to_tok_len_kernel(const int64_t* __restrict__ cap, int rows, int L, int T, const int32_t* __restrict__ len,
+                                           int64_t* __restrict__ tok) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // i = t * rows + row
+    if (i >= T * rows) return;
+    const int t = i / rows, r = i % rows;
+    tok[i] = t < len[r] ? cap[(size_t)r * L + t] : 0;
+}
+void launch_captions_to_tok_len(const int64_t* captions, int rows, int L, int T, const int32_t* len, int64_t* tok, hipStream_t st) {
+    hipLaunchKernelGGL(captions_to_tok_len_kernel, dim3(cdiv(T * rows, 256)), dim3(256), 0, st, captions, rows, L, T, len, tok);
+}
+// out [rows, T, V] = logit [T rows, ldl] at the active (row, t), zeros elsewhere
+__global__ void gather_rows_kernel(const float* __restrict__ logit, int V, int ldl, int rows, int T, const int32_t* __restrict__ len,
+                                   float* __restrict__ out) {
+    const int tr = blockIdx.y, t = tr / rows, r = tr % rows;
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= V) return;
+    out[((size_t)r * T + t) * V + v] = t < len[r] ? logit[(size_t)tr * ldl + v] : 0.f;
+}
+void launch_gather_rows(const float* logit, int V, int ldl, int rows, int T, const int32_t* len, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(cdiv(V, 256), T * rows), dim3(256), 0, st, logit, V, ldl, rows, T, len, out);
+}
+
+int launch_xe_group_loss(float* logits, int V, int ldl, const int64_t* captions, int L, int rows, int T, const int32_t* len, float smoothing,
+                         float n, const float* n_dev, float* loss_rows, float* loss_out, hipStream_t st) {
+    ICZ_REQUIRE(ldl % 4 == 0 && ((uintptr_t)logits & 15) == 0, "grouped xe loss: inactive rows are zeroed 16 bytes at a time: ldl=%d, logits %p", ldl,
+                (void*)logits);
+    ICZ_REQUIRE(T >= 1 && T <= 65535, "grouped xe loss: %d steps exceed the grid", T);
+    hipLaunchKernelGGL(xe_group_loss_dlogits_kernel, dim3(rows, T), dim3(256), 0, st, logits, V, ldl, captions, L, rows, len, smoothing, 1.0f / n,
+                       n_dev, loss_rows);
+    if (loss_out) hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, st, loss_rows, T * rows, 1.0f / n, n_dev, loss_out);
+    ICZ_CHECK_HIP(hipGetLastError());
+    return ICZ_OK;
+}
+
+int CaptionHead::xe_group_loss(const int32_t* len, float smoothing, float n_tokens_global, float* logits, int V, int ldl, float* loss_out,
+                               hipStream_t st) {
+    const float n = n_tokens_global > 0.f ? n_tokens_global : (float)n_tokens;
+    const float* n_dev = n_tokens_global < 0.f ? d_msum : nullptr;
+    ICZ_TRY(launch_xe_group_loss(logits, V, ldl, cur_captions, cur_L, cur_B, cur_T, len, smoothing, n, n_dev, loss_rows, loss_out, st));
+    mode = 0;
+    return ICZ_OK;
+}
+
 void CaptionHead::set_msum_global(float msum_global, hipStream_t st) const {
     if (msum_global >= 0.f)
         hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, (uint64_t*)nullptr, (uint64_t)0, d_msum, msum_global);
@@ -349,6 +409,32 @@ int icz_test_xe_loss(float* logits, int32_t V, int32_t ldl, const int64_t* capti
     ICZ_REQUIRE(smoothing >= 0.f && smoothing <= 1.f && n_tokens > 0.f, "%s: smoothing=%g outside [0, 1] or n_tokens=%g not positive", who,
                 (double)smoothing, (double)n_tokens);
     return launch_xe_loss(logits, V, ldl, captions, L, B, T, rows_t, smoothing, n_tokens, n_dev, loss_rows, loss_out, (hipStream_t)stream);
+}
+
+int icz_test_xe_group_loss(float* logits, int32_t V, int32_t ldl, const int64_t* captions, int32_t L, int32_t rows, int32_t T, const int32_t* lengths,
+                           float smoothing, float n_tokens, const float* n_dev, float* loss_rows, float* loss_out, void* stream) {
+    using namespace icz;
+    const char* who = "icz_test_xe_group_loss";
+    ICZ_REQUIRE(logits && captions && lengths && loss_rows, "%s: null argument", who);
+    ICZ_REQUIRE(V >= 2 && ldl >= V && ldl % 4 == 0 && tc_al16(logits), "%s: V=%d (at least 2), ldl=%d (at least V, a multiple of 4), logits 16-byte aligned",
+                who, V, ldl);
+    ICZ_REQUIRE(T >= 1 && T <= XE_MAX_T && L > T, "%s: T=%d outside 1..%d or not below L=%d", who, T, XE_MAX_T, L);
+    ICZ_REQUIRE(rows >= 1 && (long)rows * T <= (1 << 20), "%s: rows=%d", who, rows);
+    ICZ_REQUIRE(smoothing >= 0.f && smoothing <= 1.f && n_tokens >= 0.f, "%s: smoothing=%g outside [0, 1] or n_tokens=%g negative", who,
+                (double)smoothing, (double)n_tokens);
+    // the step counts are read back and checked; n_tokens == 0: N is their sum, as behind icz_butd_xe_forward_n
+    std::vector<int32_t> len(rows);
+    hipStream_t const st = (hipStream_t)stream;
+    ICZ_CHECK_HIP(hipMemcpyAsync(len.data(), lengths, sizeof(int32_t) * rows, hipMemcpyDeviceToHost, st));
+    ICZ_CHECK_HIP(hipStreamSynchronize(st));
+    long sum = 0;
+    for (int r = 0; r < rows; ++r) {
+        ICZ_REQUIRE(len[r] >= 0 && len[r] <= T, "%s: lengths[%d]=%d outside 0..T", who, r, len[r]);
+        sum += len[r];
+    }
+    ICZ_REQUIRE(n_tokens > 0.f || sum > 0, "%s: no active (row, t) and no n_tokens", who);
+    return launch_xe_group_loss(logits, V, ldl, captions, L, rows, T, lengths, smoothing, n_tokens > 0.f ? n_tokens : (float)sum, n_dev, loss_rows,
+                                loss_out, st);
 }
 
 int icz_test_reinforce(const float* logp, const int64_t* seq, const float* reward, int32_t B, int32_t T, const float* mask_sum_global, float* coef,

@@ -578,6 +578,35 @@ __global__ __launch_bounds__(256) void reinforce_dlogits_kernel(float* __restric
 // to at most B workgroups seventeen times per XE step.
 constexpr int XE_MAX_T = 128;
 struct XeRows { int n[XE_MAX_T]; };
+// One active row l [ldl] (target *tgp, read behind the sum-exp) by the workgroup's 256 threads: the loss of the row comes back (on every thread), the gradient goes
+// over the row, zeros into the pad columns [V, ldl).  Shared by the two kernels below, so that a row gives the same bits through either.
+__device__ __forceinline__ float xe_row_loss_dlogits(float* __restrict__ l, int V, int ldl, const int64_t* __restrict__ tgp, float smoothing, float inv_n,
+                                                     float* smf) {
+    const int tid = threadIdx.x;
+    float mx = -INFINITY;
+    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, l[v]);
+    mx = block_max_256(mx, smf);
+    float se = 0.f;
+    for (int v = tid; v < V; v += 256) se += expf(l[v] - mx);
+    se = block_sum_256(se, smf);
+    const float lse = mx + logf(se);
+    const int tg = (int)tgp[0];
+    const float conf = 1.f - smoothing, low = smoothing / (float)(V - 1);
+    const float lconf = conf > 0.f ? logf(conf) : 0.f, llow = low > 0.f ? logf(low) : 0.f;
+    float ls = 0.f;
+    for (int v = tid; v < ldl; v += 256) {
+        float g = 0.f;
+        if (v < V) {
+            const float lp = l[v] - lse;
+            const float tr = (v == tg) ? conf : low;
+            if (tr > 0.f) ls += tr * (((v == tg) ? lconf : llow) - lp);
+            g = (expf(lp) - tr) * inv_n;
+        }
+        l[v] = g;
+    }
+    return block_sum_256(ls, smf);
+}
+
 __global__ __launch_bounds__(256) void xe_loss_dlogits_kernel(float* __restrict__ logits, int V, int ldl,
                                                               const int64_t* __restrict__ captions, int L, int B, XeRows rows,
                                                               float smoothing, float inv_n_host, const float* __restrict__ n_dev,
@@ -592,29 +621,32 @@ __global__ __launch_bounds__(256) void xe_loss_dlogits_kernel(float* __restrict_
     // data-parallel: the all-reduced token count, a device scalar (0 = never handed over: the local count, as the SCST path does)
     const float inv_n = (n_dev && n_dev[0] > 0.f) ? 1.0f / n_dev[0] : inv_n_host;
     const int row = t * B + b;
-    float* l = logits + (size_t)row * ldl;
-    float mx = -INFINITY;
-    for (int v = tid; v < V; v += 256) mx = fmaxf(mx, l[v]);
-    mx = block_max_256(mx, smf);
-    float se = 0.f;
-    for (int v = tid; v < V; v += 256) se += expf(l[v] - mx);
-    se = block_sum_256(se, smf);
-    const float lse = mx + logf(se);
-    const int tg = (int)captions[(size_t)b * L + t + 1];
-    const float conf = 1.f - smoothing, low = smoothing / (float)(V - 1);
-    const float lconf = conf > 0.f ? logf(conf) : 0.f, llow = low > 0.f ? logf(low) : 0.f;
-    float ls = 0.f;
-    for (int v = tid; v < ldl; v += 256) {
-        float g = 0.f;
-        if (v < V) {
-            const float lp = l[v] - lse;
-            const float tr = (v == tg) ? conf : low;
-            if (tr > 0.f) ls += tr * (((v == tg) ? lconf : llow) - lp);
-            g = (expf(lp) - tr) * inv_n;
-        }
-        l[v] = g;
+    const float ls = xe_row_loss_dlogits(logits + (size_t)row * ldl, V, ldl, captions + (size_t)b * L + t + 1, smoothing, inv_n, smf);
+    if (tid == 0) loss_rows[row] = ls;
+}
+
+// The same loss over the image-major rows of a grouped XE forward (K captions per image, row = img * K + k, in no length order): the
+// active (row, t) are not a prefix of the rows of step t, so the mask is t < len[row], read from a device array of per-row step counts.
+// One workgroup (four waves) per (row, t) = row t * rows + row of the stored logits [T rows, ldl] (ldl % 4 == 0, 16-byte aligned rows).
+// An inactive (row, t) is written as zeros, 16 bytes per thread and store, WITHOUT BEING READ (the forward pass ran it on <pad>; NaN
+// there does not matter) and leaves 0 in loss_rows.  An active one goes through xe_row_loss_dlogits: the row is read three times (max,
+// sum-exp, gradient; 40 KB at V = 10 102, the second and third time from L2), nothing of it is kept in LDS, so there is no cap on V.
+__global__ __launch_bounds__(256) void xe_group_loss_dlogits_kernel(float* __restrict__ logits, int V, int ldl,
+                                                                    const int64_t* __restrict__ captions, int L, int rows,
+                                                                    const int32_t* __restrict__ len, float smoothing, float inv_n_host,
+                                                                    const float* __restrict__ n_dev, float* __restrict__ loss_rows) {
+    __shared__ float smf[4];
+    const int r = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+    const size_t row = (size_t)t * rows + r;
+    float* l = logits + row * ldl;
+    if (t >= len[r]) {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        for (int v = tid * 4; v < ldl; v += 1024) *reinterpret_cast<f32x4*>(l + v) = z;
+        if (tid == 0) loss_rows[row] = 0.f;
+        return;
     }
-    ls = block_sum_256(ls, smf);
+    const float inv_n = (n_dev && n_dev[0] > 0.f) ? 1.0f / n_dev[0] : inv_n_host;
+    const float ls = xe_row_loss_dlogits(l, V, ldl, captions + (size_t)r * L + t + 1, smoothing, inv_n, smf);
     if (tid == 0) loss_rows[row] = ls;
 }
 

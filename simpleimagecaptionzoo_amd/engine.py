@@ -507,6 +507,56 @@ class BUTDDetection_Eng(Engine):
                 monitor.set_postfix(Loss=np.round(loss.item(), decimals=4))
         return losses
 
+    # decoders with a grouped XE forward (icz_butd_xe_forward_n); the AoA and NIC engines refuse training_epoch_grouped
+    _grouped_xe = True
+
+    def training_epoch_grouped(self, dataloader, optimizer, criterion, tqdm_visible=True, rngs=None, captions_per_image=5):
+        """Beyond the reference: the XE epoch on K = captions_per_image (2..8) references per image, the regime of seq_per_img = 5.
+        `dataloader` is the SCST loader: batches (img_ids, img_tensors, img_gts, supp_info_datas).  Per step the features of the B
+        images are staged once, grouped.make_batch encodes the first K references of every image into image-major rows, and
+        grouped.xe_forward_n runs the per-image work once per image and the decoder chain over the B K rows; the token-count
+        exchange, the gradient-reduce hooks, xe_backward with criterion.smoothing, the 0.1 clamp and Adam are training_epoch's.
+        Per-image region counts are honoured.  BUTD decoders: BUTDDetection_Eng and BUTDSpatial_Eng (the same decoder over the 49
+        grid regions) run it; AoADetection_Eng and NIC_Eng raise NotImplementedError (their grouped forward is the follow-up).
+        ValueError, before any device work, for a bad captions_per_image, scheduled sampling live, an image with fewer than K
+        references, or a batch whose B K exceeds the handle's row capacity."""
+        from .grouped import check_captions_per_image
+        if not self._grouped_xe:
+            raise NotImplementedError("%s has no grouped XE forward yet: icz_butd_xe_forward_n serves the BUTD decoders; the AoA and NIC "
+                                      "forms (icz_aoa_xe_forward_n, icz_nic_xe_forward_n) are the follow-up" % type(self).__name__)
+        k = check_captions_per_image(captions_per_image)
+        if self.model.scheduled_sampling and float(self.model.ss_prob) > 0.0:
+            raise ValueError("scheduled sampling is live (ss_prob %g): the grouped forward feeds the captions' own tokens" % float(self.model.ss_prob))
+        with _on_stream(self):
+            return self._training_epoch_grouped(dataloader, optimizer, criterion, tqdm_visible, rngs, k)
+
+    def _training_epoch_grouped(self, dataloader, optimizer, criterion, tqdm_visible, rngs, k):
+        """training_epoch_grouped's steps: those of _xe_epoch with make_batch and xe_forward_n in the place of the loader's rows"""
+        from .grouped import make_batch, xe_forward_n
+        self.model.train()
+        smoothing = float(getattr(criterion, "smoothing", 0.0))
+        monitor = _monitor(dataloader, "Training Process", tqdm_visible)
+        losses = []
+        for batch_i, (img_ids, img_tensors, img_gts, supp_info_datas) in enumerate(monitor):
+            if len(img_ids) * k > self.model.max_rows:      # before the step's device work
+                raise ValueError("%d images x %d captions exceed the handle's row capacity %d" % (len(img_ids), k, self.model.max_rows))
+            captions, lengths = make_batch(self.caption_vocab, img_ids, img_gts, k)
+            visual_inputs = self.modify_visual_inputs(img_tensors, supp_info_datas)
+            lengths = [cap_len - 1 for cap_len in lengths]
+            h = self.model._handle()
+            rng = rngs[batch_i] if rngs is not None else self.model._next_rng()
+            xe_forward_n(h, self._features(visual_inputs), captions, lengths, k, rng, train=True)
+            grads = self._grads()
+            n_glob = self._xe_token_norm(h, lengths)
+            ov = self._reduce_grads_begin(h)
+            loss = h.xe_backward(grads, smoothing, n_glob)
+            self._reduce_grads_end(ov)
+            self._apply(optimizer, 0.1)
+            losses.append(loss)
+            if tqdm_visible:
+                monitor.set_postfix(Loss=np.round(loss.item(), decimals=4))
+        return losses
+
     def distill_training_epoch(self, dataloader, optimizer, criterion, teachers, tqdm_visible=True, rngs=None, *, alpha=0.5, temperature=1.0,
                                weights=None):
         """Beyond the reference: training_epoch with the word-level distillation loss of distill.py in the place of the XE loss.
@@ -887,6 +937,7 @@ class AoADetection_Eng(BUTDDetection_Eng):
     # the AoA library's callback stages (include/icz.h: icz_aoa_set_grad_callback): 41 MB + 92 MB of the 163 MB of decoder gradients are
     # on the wire before the backward call returns; the attention block and h_norm (30 MB) follow after it
     _multi_sample = False
+    _grouped_xe = False
     _GRAD_STAGES = (("decoder.predict.weight_v", "decoder.predict.weight_g", "decoder.predict.bias"),
                     ("decoder.embed.0.weight", "decoder.lstm.weight_ih", "decoder.lstm.weight_hh", "decoder.lstm.bias_ih", "decoder.lstm.bias_hh"))
 
@@ -923,6 +974,7 @@ class NIC_Eng(BUTDDetection_Eng):
     {'img_feats': (B, embed_dim) tensor}` -- or the Captioner was given an `encoder` module for `img_tensors`."""
 
     _multi_sample = False
+    _grouped_xe = False
 
     def model_construction(self, max_batch):
         from .nic import NICDecoder_Captioner

@@ -57,6 +57,13 @@ def entry_xe_loss(logits, V, ldl, captions, L, B, T, rows_t, smoothing, n_tokens
                                  ptr(n_dev), ptr(loss_rows), ptr(loss_out), stream_ptr()))
 
 
+def entry_xe_group_loss(logits, V, ldl, captions, L, rows, T, lengths, smoothing, n_tokens, n_dev, loss_rows, loss_out):
+    """Test entry icz_test_xe_group_loss: the same loss over image-major rows; lengths: a device int32 tensor of per-row step counts,
+    (row, t) active while t < lengths[row]; n_tokens 0: N is their sum."""
+    check(lib().icz_test_xe_group_loss(ptr(logits), int(V), int(ldl), ptr(captions), int(L), int(rows), int(T), ptr(lengths), float(smoothing),
+                                       float(n_tokens), ptr(n_dev), ptr(loss_rows), ptr(loss_out), stream_ptr()))
+
+
 def entry_reinforce(logp, seq, reward, B, T, mask_sum_global, coef, loss_out, mask_sum_out, logits, V, ldl, draw, lse, Bs=0, row0=0):
     """Test entry icz_test_reinforce: the REINFORCE loss, its mask sum and the gradient (in place) of a stored rollout."""
     check(lib().icz_test_reinforce(ptr(logp), ptr(seq), ptr(reward), int(B), int(T), ptr(mask_sum_global), ptr(coef), ptr(loss_out),
