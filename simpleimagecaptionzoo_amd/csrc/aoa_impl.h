@@ -169,7 +169,6 @@ struct Aoa : CaptionHead, DecodeMember {
           *tQp = nullptr, *tP = nullptr, *tPd = nullptr, *tdS = nullptr, *tdX = nullptr, *txatt = nullptr, *tz = nullptr, *tcd = nullptr, *tlogit = nullptr;
     float *dCd = nullptr, *dZ = nullptr, *dQp = nullptr, *dQn = nullptr, *dHln = nullptr, *dG = nullptr, *dEmb = nullptr, *dKd = nullptr,
           *dVd = nullptr, *dcb[2] = {nullptr, nullptr}, *X = nullptr, *X2 = nullptr, *dWp = nullptr, *prod = nullptr;
-    bool early_out = true, bptt_early_out = false;
     size_t xfloats = 0;
     // option "train_refiner" (aoa_refine_train.hip): a training-mode refiner pass keeps the input of every layer and of the final norm
     // (xs[l], xs[NL]: region rows x Hd each); the backward pass recomputes one layer at a time from them.  Training buffers, allocated
@@ -242,9 +241,8 @@ struct Aoa : CaptionHead, DecodeMember {
     }
     // training paths (aoa_train.hip)
     int ensure_train(int B, int T, int n_img = 0);
-    // multi-sample SCST rollout (sample_n, beyond the reference): cur_K sampled rows per image, row = img * K + k (1 = every other entry
-    // point; cur_B stays the decoder rows); imgk = the image of each row, allocated by the first sample_n
-    int cur_K = 1;
+    // multi-sample SCST rollout (sample_n, beyond the reference): cur_K (CaptionHead) sampled rows per image, row = img * K + k; cur_B
+    // stays the decoder rows; imgk = the image of each row, allocated by the first sample_n
     int32_t* imgk = nullptr;
     int sample_n(const float* feats, int B, int K, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
     int sample_n_impl(const float* feats, int B, int K, int T, int64_t* seq_out, float* logp_out, hipStream_t st);
@@ -253,18 +251,13 @@ struct Aoa : CaptionHead, DecodeMember {
     int sample_prelude(const float* feats, int B, int T, const icz_aoa_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st, int K = 1);
     int sample_impl(const float* feats, int B, int T, int64_t* seq_out, float* logp_out, hipStream_t st, const float* proj = nullptr, bool refined_ready = false,
                     int n_img = 0);
-    int sample_backward_impl(const RolloutHead& hd, const icz_aoa_params& G, hipStream_t st);
-    int sample_backward_head(const RolloutHead& hd, const icz_aoa_params* G, float msum_global, hipStream_t st);
-    int sample_backward_objective(const icz_scst_objective* obj, const icz_aoa_params* G, float* loss_out3, float* ent_out, float* msum_out,
-                                  float msum_global, hipStream_t st);
-    int sample_backward(const float* reward, const icz_aoa_params* G, float* loss_out, float* msum_out, float msum_global, hipStream_t st);
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_aoa_rng* r, int train,
                    float* packed_out, hipStream_t st);
-    int xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
-    int xe_backward_distill(const DistillArgs& a, const icz_aoa_params* G, float* loss_out3, float n_tokens_global, hipStream_t st);
-    int xe_backward_swor(const SworArgs& a, int rows, const icz_aoa_params* G, float* loss_out, hipStream_t st);
-    int xe_backward_dlogits(const float* dpacked, const icz_aoa_params* G, hipStream_t st);
-    int bptt(const icz_aoa_params& G, hipStream_t st);      // the driver over the parts below, then refiner_backward
+    // The backward pass of the stored forward pass behind the loss head `hd` (every icz_aoa_*_backward* entry): the head's rules, the
+    // refiner's, the head, bptt().  A ROLLOUT head and its bptt() replay as one captured graph (option "graphs").
+    int backward(const LossHead& hd, const icz_aoa_params* G, hipStream_t st);
+    // the driver over the parts below, then refiner_backward; eo: the early-out of a sampled rollout applies
+    int bptt(const icz_aoa_params& G, hipStream_t st, bool eo);
     struct BpttCall;
     int bptt_predict(BpttCall& c);              // d(dropped ctx) and the predict layer's gradients (side branch)
     int bptt_loop(BpttCall& c);                 // the reverse-time loop

@@ -297,12 +297,10 @@ int Aoa::sample_prelude(const float* feats, int B, int T, const icz_aoa_rng* r, 
     ICZ_REQUIRE(feats && seq_out && logp_out && r && B > 0 && B <= dims.max_rows && T > 0, "aoa sample: bad arguments");
     ICZ_REQUIRE(fresh, "aoa: call icz_aoa_refresh_weights after binding/updating parameters");
     ICZ_TRY(ensure_train(B, T, B / K));
-    cur_K = K;
     rng = *r;
-    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
-    mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_seq = seq_out; cur_logp = logp_out;
+    begin_rollout(B, T, seq_out, logp_out, rng.seed, st);
+    cur_K = K;
     xs_valid = false;                  // set by the training-mode refiner pass of this rollout (option "train_refiner")
-    rows_t.assign(T, B);
     return ICZ_OK;
 }
 
@@ -434,32 +432,26 @@ int Aoa::rollouts_impl(const float* feats, int B, int T, int64_t* ids_out, int64
     return baseline.join();
 }
 
-int Aoa::sample_backward(const float* reward, const icz_aoa_params* G, float* loss_out, float* msum_out, float msum_global, hipStream_t st) {
-    ICZ_TRY(require_mode(1, "aoa"));
-    ICZ_REQUIRE(reward && G, "aoa sample_backward: null argument");
-    return sample_backward_head({reward, nullptr, loss_out, nullptr, msum_out}, G, msum_global, st);
-}
-
-// sample_backward with an SCST objective (scst_objective.hip) in the place of RewardCriterion; the captured graph carries the
-// objective in its key (ScstObjective::key) beside the output pointers
-int Aoa::sample_backward_objective(const icz_scst_objective* obj, const icz_aoa_params* G, float* loss_out3, float* ent_out, float* msum_out,
-                                   float msum_global, hipStream_t st) {
-    ICZ_TRY(require_mode(1, "aoa"));
-    ScstObjective o;
-    ICZ_TRY(check_objective("aoa sample_backward_objective", obj, cur_K, &o));
-    return sample_backward_head({nullptr, &o, loss_out3, ent_out, msum_out}, G, msum_global, st);
-}
-
-int Aoa::sample_backward_head(const RolloutHead& hd, const icz_aoa_params* G, float msum_global, hipStream_t st) {
+int Aoa::backward(const LossHead& head, const icz_aoa_params* G, hipStream_t st) {
+    ICZ_TRY(check_loss_head(head, G));
     if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
-    set_msum_global(msum_global, st);      // < 0: keep the device value handed over by icz_aoa_set_norm_global
-    mode = 0;
-    bptt_early_out = true;
+    const bool eo = head.rollout_kind() && early_out;
+    // the REINFORCE / objective head goes into the captured graph with its bptt(); every other head is queued here
+    const bool in_graph = head.kind == LossHead::ROLLOUT;
+    ICZ_TRY(begin_backward(head, in_graph, tlogit, dims.V, Vp, st));
     // the side stream of bptt, created here, outside any capture.  A plain stream: eager launches on a PRIORITISED stream beside other
     // streams' work can serialise on this runtime (EXPERIMENTS.md, round 4, section 8), and the AoA paths are eager
     ICZ_TRY(low.ensure());
+    if (!in_graph) return bptt(*G, st, eo);
+    const RolloutHead& hd = head.rollout;
+    const icz_aoa_params Gc = *G;
+    auto run = [&](hipStream_t s) -> int {
+        ICZ_TRY(launch_loss_head(head, tlogit, dims.V, Vp, s));
+        return bptt(Gc, s, eo);
+    };
     // with a DP callback the hook must fire on every call: eager launches (a replayed graph would not call it)
-    if (!use_graphs || lens || grad_cb || aoa_explicit_rng(rng)) return sample_backward_impl(hd, *G, st);
+    if (!use_graphs || lens || grad_cb || aoa_explicit_rng(rng)) return run(st);
+    // the captured graph carries the objective in its key (ScstObjective::key) beside the output pointers
     std::vector<uintptr_t> key = {2, (uintptr_t)hd.reward, (uintptr_t)hd.loss_out, (uintptr_t)hd.msum_out, (uintptr_t)cur_B, (uintptr_t)cur_T, (uintptr_t)cur_R,
                                   (uintptr_t)cur_seq, (uintptr_t)cur_logp, (uintptr_t)cur_K,      // sample_n of B K rows against sample of B K rows: other launches
                                   (uintptr_t)bank[0].refined, (uintptr_t)bank[0].Kd, (uintptr_t)bank[1].refined, (uintptr_t)bank[1].Kd, (uintptr_t)bank[1].Vd, (uintptr_t)cur_bank,      // paired-refine banks (rollouts) or the handle's own (sample)
@@ -467,13 +459,7 @@ int Aoa::sample_backward_head(const RolloutHead& hd, const icz_aoa_params* G, fl
     const float* const* gp = reinterpret_cast<const float* const*>(G);
     for (size_t i = 0; i < sizeof(icz_aoa_params) / sizeof(float*); ++i) key.push_back((uintptr_t)gp[i]);
     if (hd.obj) { hd.obj->key(key); key.push_back((uintptr_t)hd.ent_out); }
-    const icz_aoa_params Gc = *G;
-    return gc.run(key, st, [&](hipStream_t s) { return sample_backward_impl(hd, Gc, s); });
-}
-
-int Aoa::sample_backward_impl(const RolloutHead& hd, const icz_aoa_params& G, hipStream_t st) {
-    ICZ_TRY(rollout_head(hd, tlogit, dims.V, Vp, st));
-    return bptt(G, st);
+    return gc.run(key, st, run);
 }
 
 int Aoa::xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_aoa_rng* r, int train,
@@ -519,49 +505,6 @@ int Aoa::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
     return ICZ_OK;
 }
 
-int Aoa::xe_backward(float smoothing, const icz_aoa_params* G, float* loss_out, float n_tokens_global, hipStream_t st) {
-    ICZ_TRY(require_mode(2, "aoa"));
-    ICZ_REQUIRE(G, "aoa xe_backward: null grads");
-    if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
-    ICZ_TRY(xe_loss(smoothing, n_tokens_global, tlogit, dims.V, Vp, loss_out, st));
-    bptt_early_out = false;
-    ICZ_TRY(low.ensure());          // as in sample_backward
-    return bptt(*G, st);
-}
-
-// xe_backward with the distillation loss (distill.hip) in the place of xe_loss
-int Aoa::xe_backward_distill(const DistillArgs& a, const icz_aoa_params* G, float* loss_out3, float n_tokens_global, hipStream_t st) {
-    ICZ_TRY(require_mode(2, "aoa"));
-    ICZ_TRY(require_teacher_forced("aoa xe_backward_distill"));
-    if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
-    ICZ_TRY(distill_loss(a, n_tokens_global, tlogit, dims.V, Vp, loss_out3, st));
-    bptt_early_out = false;
-    ICZ_TRY(low.ensure());
-    return bptt(*G, st);
-}
-
-// xe_backward with the without-replacement SCST head (swor_objective.hip) in the place of xe_loss
-int Aoa::xe_backward_swor(const SworArgs& a, int rows, const icz_aoa_params* G, float* loss_out, hipStream_t st) {
-    ICZ_TRY(check_swor("aoa", rows));
-    if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
-    ICZ_TRY(swor_loss(a, tlogit, dims.V, Vp, loss_out, st));
-    bptt_early_out = false;
-    ICZ_TRY(low.ensure());
-    return bptt(*G, st);
-}
-
-// xe_backward driven by an upstream gradient w.r.t. the packed logits (Butd::xe_backward_dlogits)
-int Aoa::xe_backward_dlogits(const float* dpacked, const icz_aoa_params* G, hipStream_t st) {
-    ICZ_TRY(require_mode(2, "aoa"));
-    ICZ_REQUIRE(dpacked && G, "aoa xe_backward_dlogits: null argument");
-    if (train_refiner) ICZ_TRY(refiner_backward_check(*G));
-    ICZ_TRY(scatter_packed(dpacked, dims.V, Vp, tlogit, st));
-    mode = 0;
-    bptt_early_out = false;
-    ICZ_TRY(low.ensure());
-    return bptt(*G, st);
-}
-
 int Aoa::nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* slab, size_t cap, int* ns_out, const SplitPolicy& p,
             hipStream_t st, const int* live, const int* rows_live) {
     GemmArgs g = gemm_args({{A, Bm, lda, ldb, K}}, M, N, slab, N, live);
@@ -586,13 +529,12 @@ struct Aoa::BpttCall {
     SideStream::Branch tail;         // the attention block's small products beside the batched weight gradients
 };
 
-int Aoa::bptt(const icz_aoa_params& G, hipStream_t st) {
+int Aoa::bptt(const icz_aoa_params& G, hipStream_t st, bool eo) {
     use_bank(1);
-    // Without a DP callback the two branches go to the side stream (a plain one, see sample_backward); with a callback they stay in line,
+    // Without a DP callback the two branches go to the side stream (a plain one, see backward()); with a callback they stay in line,
     // because the stages report their gradients complete in stream order.
     const bool side = !grad_cb;
     static const bool tail_side_on = [] { const char* e = getenv("ICZ_AOA_TAIL_SIDE"); return e ? atoi(e) != 0 : true; }();      // A/B switch (read once)
-    const bool eo = bptt_early_out && early_out;
     BpttCall c = {G, st, cur_B, cur_T, cur_T * cur_B, cur_K, cur_B / cur_K, eo, eo ? live_rows : nullptr,
                   {side ? &low : nullptr, 0}, {side && tail_side_on ? &low : nullptr, 1}};
     ICZ_TRY(bptt_predict(c));
@@ -857,14 +799,23 @@ int icz_aoa_scst_rollouts(icz_aoa_t* h, const float* feats, int32_t B, int32_t m
 int icz_aoa_sample_backward(icz_aoa_t* h, const float* reward, const icz_aoa_params* grads, float* loss_out, float* mask_sum_out,
                             float mask_sum_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Aoa*>(h)->sample_backward(reward, grads, loss_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::ROLLOUT, "aoa", "aoa sample_backward"};
+    hd.rollout = {reward, nullptr, loss_out, nullptr, mask_sum_out};
+    hd.norm_global = mask_sum_global;
+    return reinterpret_cast<Aoa*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
+// sample_backward with an SCST objective (scst_objective.hip) in the place of RewardCriterion
 int icz_aoa_sample_backward_objective(icz_aoa_t* h, const icz_scst_objective* obj, const icz_aoa_params* grads, float* loss_out3, float* ent_out,
                                       float* mask_sum_out, float mask_sum_global, void* stream) {
-    ICZ_TRY(icz::scst_objective_args("icz_aoa_sample_backward_objective", obj, obj ? obj->K : 1, 1, nullptr));
+    ScstObjective o;
+    ICZ_TRY(icz::scst_objective_args("icz_aoa_sample_backward_objective", obj, obj ? obj->K : 1, 1, &o));
     ICZ_REQUIRE(grads && loss_out3, "icz_aoa_sample_backward_objective: null argument");
     ICZ_REQUIRE(h, "icz_aoa_sample_backward_objective: null handle");
-    return reinterpret_cast<Aoa*>(h)->sample_backward_objective(obj, grads, loss_out3, ent_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::ROLLOUT, "aoa", "aoa sample_backward_objective"};
+    hd.rollout = {nullptr, &o, loss_out3, ent_out, mask_sum_out};
+    hd.objective = obj;
+    hd.norm_global = mask_sum_global;
+    return reinterpret_cast<Aoa*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
 int icz_aoa_set_scheduled_sampling(icz_aoa_t* h, float ss_prob, const float* gate_uniforms, const float* draw_uniforms) {
     return set_scheduled_sampling("icz_aoa_set_scheduled_sampling", reinterpret_cast<Aoa*>(h), ss_prob, gate_uniforms, draw_uniforms);
@@ -893,7 +844,9 @@ int icz_aoa_set_norm_global(icz_aoa_t* h, const float* norm_dev, void* stream) {
 }
 int icz_aoa_xe_backward(icz_aoa_t* h, float smoothing, const icz_aoa_params* grads, float* loss_out, float n_tokens_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Aoa*>(h)->xe_backward(smoothing, grads, loss_out, n_tokens_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE, "aoa", "aoa xe_backward"};
+    hd.smoothing = smoothing; hd.loss_out = loss_out; hd.norm_global = n_tokens_global;
+    return reinterpret_cast<Aoa*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
 int icz_aoa_xe_backward_distill(icz_aoa_t* h, const icz_distill_opts* opts, const icz_aoa_params* grads, float* loss_out3, float n_tokens_global,
                                 void* stream) {
@@ -902,18 +855,25 @@ int icz_aoa_xe_backward_distill(icz_aoa_t* h, const icz_distill_opts* opts, cons
     ICZ_TRY(distill_args("icz_aoa_xe_backward_distill", opts, a ? a->dims.V : -1, &d));
     ICZ_REQUIRE(grads && loss_out3, "icz_aoa_xe_backward_distill: null grads or loss");
     ICZ_REQUIRE(h, "icz_aoa_xe_backward_distill: null handle");
-    return a->xe_backward_distill(d, grads, loss_out3, n_tokens_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE_DISTILL, "aoa", "aoa xe_backward_distill"};
+    hd.distill = &d; hd.loss_out = loss_out3; hd.norm_global = n_tokens_global;
+    return a->backward(hd, grads, (hipStream_t)stream);
 }
 int icz_aoa_xe_backward_swor(icz_aoa_t* h, const icz_swor_opts* opts, int32_t rows, const icz_aoa_params* grads, float* loss_out, void* stream) {
     SworArgs a;
     ICZ_TRY(swor_args("icz_aoa_xe_backward_swor", opts, rows, &a));
     ICZ_REQUIRE(grads && loss_out, "icz_aoa_xe_backward_swor: null grads or loss");
     ICZ_REQUIRE(h, "icz_aoa_xe_backward_swor: null handle");
-    return reinterpret_cast<Aoa*>(h)->xe_backward_swor(a, rows, grads, loss_out, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE_SWOR, "aoa", "aoa xe_backward_swor"};
+    hd.swor = &a; hd.swor_rows = rows; hd.loss_out = loss_out;
+    return reinterpret_cast<Aoa*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
+// xe_backward driven by an upstream gradient w.r.t. the packed logits
 int icz_aoa_xe_backward_dlogits(icz_aoa_t* h, const float* dpacked, const icz_aoa_params* grads, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Aoa*>(h)->xe_backward_dlogits(dpacked, grads, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE_DLOGITS, "aoa", "aoa xe_backward_dlogits"};
+    hd.upstream = dpacked;
+    return reinterpret_cast<Aoa*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
 
 }  // extern "C"

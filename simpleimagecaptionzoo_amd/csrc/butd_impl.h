@@ -128,24 +128,20 @@ struct Butd : CaptionHead, DecodeMember {
     SideStream low;                      // lowest priority, for work overlapped with the BPTT chain; its second event pair: the attention
                                          // block's tail beside the LSTM weight gradients (bptt)
     icz_grad_ready_cb grad_cb = nullptr; void* grad_cb_user = nullptr;   // DP overlap hook (icz_butd_set_grad_callback)
-    int sample_backward_impl(const RolloutHead& hd, const icz_butd_params& G, hipStream_t st, int phases = 0xF, bool fire_cb = true);
-    int sample_backward_head(const RolloutHead& hd, const icz_butd_params* G, float mask_sum_global, hipStream_t st);
     int merge_small = 8;                 // option "merge_small" = n: SCST rollouts of <= n images (n <= 32) run as ONE chain of 2 B decoder rows
                                          // (sample_chain with row0 = B); 0 = never.  Default 8: measured round 5 (EXPERIMENTS.md), the
                                          // merged chain saves 0.2 ms of rollouts at every size but costs the backward pass 0.06 / 0.15 /
                                          // 0.37 ms at 8 / 16 / 32 images (its batched GEMMs then run over 2 B rows per step)
     int cur_rows = 0, cur_row0 = 0;      // rows per step slot of the stored forward pass and the offset of the rows the backward pass works on
                                          // (a merged chain stores 2 B rows per step, the sampled rollout's are rows B .. 2 B - 1)
-    bool early_out = true;               // option "early_out": 0 = run the steps behind the reference's break as rounds 1 - 4 did (A/B)
-    bool bptt_early_out = false;         // backward of a sampled rollout: steps behind the reference's break return at entry (bptt)
     bool small_nt = true;                // option "small_nt": BPTT steps of <= 32 rows take their dgrad products on the transposed weight copies (fp32 NT kernel)
     bool fused_dh1 = true;               // option "fused_dh1": BPTT steps of <= 64 rows at widths lstm_bwd_dh1_fused_takes accepts form X2 = d dec . w_dec
                                          // inside the TD-LSTM backward launch (six launches per step); 0 = the product and the pointwise
                                          // kernel as two launches (seven).  The same bits either way
     // multi-sample SCST rollout (sample_n, beyond the reference): K sampled rows per image, row = img * K + k, sharing the image's
-    // hoisted tensors.  cur_K = rows per image of the stored rollout (1 = every other entry point), cur_nimg = its image count.
+    // hoisted tensors.  cur_K (CaptionHead) = rows per image of the stored rollout, cur_nimg = its image count.
     // xe_forward_n stores its teacher-forced forward pass in the same layout (mode 2 with cur_K > 1: xe_grouped()).
-    int cur_K = 1, cur_nimg = 0;
+    int cur_nimg = 0;
     bool group_att = false;              // option "group_att": 1 = sample_n's attention (forward scores / context, backward d enc_ctx) runs on
                                          // the grouped kernels (each image's features / enc_ctx read once for its K rows); 0 (default) = the
                                          // per-row kernels through img_of_row.  Measured (tools/perf_scst_n.py): the
@@ -176,8 +172,6 @@ struct Butd : CaptionHead, DecodeMember {
     int sample_n(const float* feats, int B, int K, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
     int sample_n_impl(const float* feats, int B, int K, int T, int64_t* seq_out, float* logp_out, hipStream_t st);
     int sample_mask_sum(float* out, hipStream_t st);
-    int sample_backward(const float* reward, const icz_butd_params* G, float* loss_out, float* mask_sum_out,
-                        float mask_sum_global, hipStream_t st);
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r,
                    int train, float* packed_out, hipStream_t st);
     // teacher-forced XE on K captions per image (beyond the reference): sample_n's layout -- the prologue once per image, the chain over
@@ -185,22 +179,18 @@ struct Butd : CaptionHead, DecodeMember {
     int xe_forward_n(const float* feats, const int64_t* captions, int B, int K, int L, const int32_t* lengths, const icz_rng* r,
                      int train, float* logits_out, hipStream_t st);
     bool xe_grouped() const { return mode == 2 && cur_K > 1; }      // the stored forward pass is xe_forward_n's
-    int sample_backward_objective(const icz_scst_objective* obj, const icz_butd_params* G, float* loss_out3, float* ent_out, float* mask_sum_out,
-                                  float mask_sum_global, hipStream_t st);
-    int sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hipStream_t st);
-    int xe_backward_dlogits(const float* dpacked, const icz_butd_params* G, hipStream_t st);
-    int xe_backward(float smoothing, const icz_butd_params* G, float* loss_out, float n_tokens_global, hipStream_t st);
-    int xe_backward_distill(const DistillArgs& a, const icz_butd_params* G, float* loss_out3, float n_tokens_global, hipStream_t st);
-    int xe_backward_swor(const SworArgs& a, int rows, const icz_butd_params* G, float* loss_out, hipStream_t st);
+    // The backward pass of the stored forward pass behind the loss head `hd` (every icz_butd_*_backward* entry): the refusals of a
+    // grouped forward, the head's own rules, the head, bptt().  A ROLLOUT head and its bptt() replay as captured graphs (graphs_on()).
+    int backward(LossHead hd, const icz_butd_params* G, hipStream_t st);
     int gemm_auto(GemmLayout layout, GemmArgs& g, float* slab, size_t slab_floats, int* ns_out, hipStream_t st);
     // the wgrad slab region of the stream a product is issued on: never shared between streams (TrainBuf::wslab)
     int wslab_of(hipStream_t st) const { return st == low.st ? 1 : 0; }
     int wgrad(const float* dY, int ldy, int M, const float* X, int ldx, int N, int K, float* out, int ldo, hipStream_t st, const int* rows_live = nullptr);
     int bptt_prelude(hipStream_t st);
     // phases: one bit per phase function below.  A call joins every branch it forked before it returns.  Values other than 0xF arise
-    // only in the callback path of sample_backward (one captured graph per phase), where the only branch, phase 0's predict branch,
-    // is joined behind the loop of that same call.
-    int bptt(const icz_butd_params& G, hipStream_t st, int phases = 0xF, bool fire_cb = true);
+    // only in the callback path of backward() (one captured graph per phase), where the only branch, phase 0's predict branch,
+    // is joined behind the loop of that same call.  eo: the early-out of a sampled rollout applies (a rollout head and option "early_out").
+    int bptt(const icz_butd_params& G, hipStream_t st, bool eo, int phases = 0xF, bool fire_cb = true);
     struct BpttCall;
     int bptt_predict(BpttCall& c);              // bit 0: d h2drop, the predict layer's gradients (side branch) ...
     int bptt_loop(BpttCall& c);                 //        ... and the reverse-time loop

@@ -165,11 +165,8 @@ int Butd::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* se
     ICZ_REQUIRE(fresh, "butd: call icz_butd_refresh_weights after binding/updating parameters");
     ICZ_TRY(ensure_train(B, T));
     rng = *r;
-    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
-    mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_feats = feats;
-    cur_rows = B; cur_row0 = 0; cur_K = 1; cur_nimg = B;
-    rows_t.assign(T, B);
-    cur_seq = seq_out; cur_logp = logp_out;
+    begin_rollout(B, T, seq_out, logp_out, rng.seed, st);
+    cur_feats = feats; cur_rows = B; cur_row0 = 0; cur_K = 1; cur_nimg = B;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
     if (explicit_rng || !graphs_on()) return sample_impl(feats, B, T, seq_out, logp_out, st);
     const std::vector<uintptr_t> key = {2, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)T, (uintptr_t)seq_out, (uintptr_t)logp_out, opt_bits()};
@@ -196,11 +193,8 @@ int Butd::sample_n(const float* feats, int B, int K, int T, const icz_rng* r, in
     const int rows = B * K;
     ICZ_TRY(ensure_train(rows, T));
     rng = *r;
-    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
-    mode = 1; cur_B = rows; cur_T = T; cur_train = true; cur_feats = feats;
-    cur_rows = rows; cur_row0 = 0; cur_K = K; cur_nimg = B;
-    rows_t.assign(T, rows);
-    cur_seq = seq_out; cur_logp = logp_out;
+    begin_rollout(rows, T, seq_out, logp_out, rng.seed, st);
+    cur_feats = feats; cur_rows = rows; cur_row0 = 0; cur_K = K; cur_nimg = B;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
     if (explicit_rng || !graphs_on()) return sample_n_impl(feats, B, K, T, seq_out, logp_out, st);
     const std::vector<uintptr_t> key = {5, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)K, (uintptr_t)T, (uintptr_t)seq_out, (uintptr_t)logp_out, opt_bits()};
@@ -228,11 +222,8 @@ int Butd::rollouts(const float* feats, int B, int T, const icz_rng* r, int64_t* 
     ICZ_TRY(ensure_train(merged ? 2 * B : B, T));
     ICZ_TRY(side.ensure());
     rng = *r;
-    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
-    mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_feats = feats;
-    cur_rows = merged ? 2 * B : B; cur_row0 = merged ? B : 0; cur_K = 1; cur_nimg = B;
-    rows_t.assign(T, B);
-    cur_seq = seq_out; cur_logp = logp_out;
+    begin_rollout(B, T, seq_out, logp_out, rng.seed, st);
+    cur_feats = feats; cur_rows = merged ? 2 * B : B; cur_row0 = merged ? B : 0; cur_K = 1; cur_nimg = B;
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
     if (explicit_rng || !graphs_on()) return rollouts_impl(feats, B, T, ids_out, seq_out, logp_out, st);
     const std::vector<uintptr_t> key = {4, (uintptr_t)feats, (uintptr_t)B, (uintptr_t)T, (uintptr_t)ids_out, (uintptr_t)seq_out, (uintptr_t)logp_out, opt_bits()};
@@ -325,31 +316,31 @@ int Butd::sample_mask_sum(float* out, hipStream_t st) {
     return ICZ_OK;
 }
 
-int Butd::sample_backward(const float* reward, const icz_butd_params* G, float* loss_out, float* mask_sum_out,
-                          float mask_sum_global, hipStream_t st) {
-    ICZ_TRY(require_mode(1, "butd"));
-    ICZ_REQUIRE(reward && G, "butd sample_backward: null argument");
-    return sample_backward_head({reward, nullptr, loss_out, nullptr, mask_sum_out}, G, mask_sum_global, st);
-}
-
-// sample_backward with an SCST objective (scst_objective.hip) in the place of RewardCriterion; the captured graphs carry the
-// objective in their key (ScstObjective::key) beside the output pointers
-int Butd::sample_backward_objective(const icz_scst_objective* obj, const icz_butd_params* G, float* loss_out3, float* ent_out,
-                                    float* mask_sum_out, float mask_sum_global, hipStream_t st) {
-    const char* who = "butd sample_backward_objective";
-    ICZ_TRY(require_mode(1, "butd"));
-    ScstObjective o;
-    ICZ_TRY(check_objective(who, obj, cur_K, &o));
-    return sample_backward_head({nullptr, &o, loss_out3, ent_out, mask_sum_out}, G, mask_sum_global, st);
-}
-
-int Butd::sample_backward_head(const RolloutHead& hd, const icz_butd_params* G, float mask_sum_global, hipStream_t st) {
-    set_msum_global(mask_sum_global, st);      // < 0: keep the device value set by icz_butd_set_mask_sum_global
-    mode = 0;   // the saved logits are consumed
-    bptt_early_out = true;
+int Butd::backward(LossHead head, const icz_butd_params* G, hipStream_t st) {
+    // behind xe_forward_n only the XE loss itself runs, over image-major rows; cur_K stays, so bptt() folds the image-side products onto the images
+    if (xe_grouped()) {
+        ICZ_REQUIRE(head.kind != LossHead::XE_DLOGITS, "icz_butd_xe_backward_dlogits: the stored forward pass is a grouped one (icz_butd_xe_forward_n): its logits are not packed");
+        ICZ_REQUIRE(head.kind != LossHead::XE_DISTILL, "icz_butd_xe_backward_distill: the stored forward pass is a grouped one (icz_butd_xe_forward_n): the teachers' logits are packed");
+        ICZ_REQUIRE(head.kind != LossHead::XE_SWOR, "icz_butd_xe_backward_swor: the stored forward pass is a grouped one (icz_butd_xe_forward_n): its rows are not sorted by length");
+        head.group_len = tb.lenk;
+    }
+    ICZ_TRY(check_loss_head(head, G));
+    const int V = dims.V, Vp = pad_vocab(dims.V);
+    const bool eo = head.rollout_kind() && early_out;
+    // the REINFORCE / objective head goes into the captured graph with its bptt(); every other head is queued here
+    const bool in_graph = head.kind == LossHead::ROLLOUT;
+    ICZ_TRY(begin_backward(head, in_graph, tb.logit, V, Vp, st, cur_rows, cur_row0));
     ICZ_TRY(bptt_prelude(st));      // outside the captured graph
+    if (!in_graph) return bptt(*G, st, eo);
+    const RolloutHead& hd = head.rollout;
+    const icz_butd_params Gc = *G;
+    auto run = [&](hipStream_t s, int phases, bool fire_cb) -> int {
+        if (phases & 1) ICZ_TRY(launch_loss_head(head, tb.logit, V, Vp, s, cur_rows, cur_row0));
+        return bptt(Gc, s, eo, phases, fire_cb);
+    };
     const bool explicit_rng = rng.uniforms || rng.emb_mask || rng.att_mask || rng.out_mask;
-    if (explicit_rng || !graphs_on()) return sample_backward_impl(hd, *G, st);
+    if (explicit_rng || !graphs_on()) return run(st, 0xF, true);
+    // the captured graphs carry the objective in their key (ScstObjective::key) beside the output pointers
     std::vector<uintptr_t> key = {3, (uintptr_t)hd.reward, (uintptr_t)hd.loss_out, (uintptr_t)hd.msum_out, (uintptr_t)cur_B, (uintptr_t)cur_T,
                                   (uintptr_t)cur_feats, (uintptr_t)cur_seq, (uintptr_t)cur_logp,
                                   (uintptr_t)cur_rows, (uintptr_t)cur_row0,       // merged / unmerged rollouts share the caller's buffers: slot strides differ
@@ -357,10 +348,9 @@ int Butd::sample_backward_head(const RolloutHead& hd, const icz_butd_params* G, 
     const float* const* gp = reinterpret_cast<const float* const*>(G);
     for (size_t i = 0; i < sizeof(icz_butd_params) / sizeof(float*); ++i) key.push_back((uintptr_t)gp[i]);
     if (hd.obj) { hd.obj->key(key); key.push_back((uintptr_t)hd.ent_out); }
-    const icz_butd_params Gc = *G;
     if (!grad_cb) {
         key.push_back(opt_bits());
-        return gc.run(key, st, [&](hipStream_t s) { return sample_backward_impl(hd, Gc, s); });
+        return gc.run(key, st, [&](hipStream_t s) { return run(s, 0xF, true); });
     }
     // The DP hook must fire on every call (a replayed graph would not call it): the backward is cut at the three points where a
     // gradient group is complete, every piece is its own captured graph, and the hook is called between the replays -- the
@@ -369,15 +359,10 @@ int Butd::sample_backward_head(const RolloutHead& hd, const icz_butd_params* G, 
         std::vector<uintptr_t> k2 = key;
         k2.push_back(0x100 + ph);
         k2.push_back(opt_bits());
-        ICZ_TRY(gc.run(k2, st, [&](hipStream_t s) { return sample_backward_impl(hd, Gc, s, 1 << ph, false); }));
+        ICZ_TRY(gc.run(k2, st, [&](hipStream_t s) { return run(s, 1 << ph, false); }));
         if (ph < 3) grad_cb(grad_cb_user, ph);
     }
     return ICZ_OK;
-}
-
-int Butd::sample_backward_impl(const RolloutHead& hd, const icz_butd_params& G, hipStream_t st, int phases, bool fire_cb) {
-    if (phases & 1) ICZ_TRY(rollout_head(hd, tb.logit, dims.V, pad_vocab(dims.V), st, cur_rows, cur_row0));
-    return bptt(G, st, phases, fire_cb);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -497,64 +482,6 @@ int Butd::xe_forward_n(const float* feats, const int64_t* captions, int B, int K
     return ICZ_OK;
 }
 
-int Butd::xe_backward_dlogits(const float* dpacked, const icz_butd_params* G, hipStream_t st) {
-    ICZ_TRY(require_mode(2, "butd"));
-    ICZ_REQUIRE(!xe_grouped(), "icz_butd_xe_backward_dlogits: the stored forward pass is a grouped one (icz_butd_xe_forward_n): its logits are not packed");
-    ICZ_REQUIRE(dpacked && G, "butd xe_backward_dlogits: null argument");
-    ICZ_TRY(scatter_packed(dpacked, dims.V, pad_vocab(dims.V), tb.logit, st));
-    mode = 0;
-    bptt_early_out = false;
-    ICZ_TRY(bptt_prelude(st));
-    return bptt(*G, st);
-}
-
-int Butd::sample_backward_dlogp(const float* dlogp, const icz_butd_params* G, hipStream_t st) {
-    ICZ_TRY(require_mode(1, "butd"));
-    ICZ_REQUIRE(dlogp && G, "butd sample_backward_dlogp: null argument");
-    const int B = cur_B, T = cur_T;
-    const int Vp = pad_vocab(dims.V);
-    ICZ_CHECK_HIP(hipMemcpyAsync(coef, dlogp, sizeof(float) * B * T, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(reinforce_dlogits_kernel, dim3(cdiv(Vp, 256), T * cur_rows), dim3(256), 0, st, tb.logit, dims.V, Vp,
-                       draw, lse, coef, B, T, cur_rows, cur_row0);
-    ICZ_CHECK_HIP(hipGetLastError());
-    mode = 0;
-    bptt_early_out = true;
-    ICZ_TRY(bptt_prelude(st));
-    return bptt(*G, st);
-}
-
-int Butd::xe_backward(float smoothing, const icz_butd_params* G, float* loss_out, float n_tokens_global, hipStream_t st) {
-    ICZ_TRY(require_mode(2, "butd"));
-    ICZ_REQUIRE(G, "butd xe_backward: null grads");
-    // behind xe_forward_n: the loss over image-major rows; cur_K stays, so bptt() folds the image-side products onto the images
-    if (xe_grouped()) ICZ_TRY(xe_group_loss(tb.lenk, smoothing, n_tokens_global, tb.logit, dims.V, pad_vocab(dims.V), loss_out, st));
-    else ICZ_TRY(xe_loss(smoothing, n_tokens_global, tb.logit, dims.V, pad_vocab(dims.V), loss_out, st));
-    bptt_early_out = false;
-    ICZ_TRY(bptt_prelude(st));
-    return bptt(*G, st);
-}
-
-// xe_backward with the distillation loss (distill.hip) in the place of xe_loss
-int Butd::xe_backward_distill(const DistillArgs& a, const icz_butd_params* G, float* loss_out3, float n_tokens_global, hipStream_t st) {
-    ICZ_TRY(require_mode(2, "butd"));
-    ICZ_REQUIRE(!xe_grouped(), "icz_butd_xe_backward_distill: the stored forward pass is a grouped one (icz_butd_xe_forward_n): the teachers' logits are packed");
-    ICZ_TRY(require_teacher_forced("butd xe_backward_distill"));
-    ICZ_TRY(distill_loss(a, n_tokens_global, tb.logit, dims.V, pad_vocab(dims.V), loss_out3, st));
-    bptt_early_out = false;
-    ICZ_TRY(bptt_prelude(st));
-    return bptt(*G, st);
-}
-
-// xe_backward with the without-replacement SCST head (swor_objective.hip) in the place of xe_loss
-int Butd::xe_backward_swor(const SworArgs& a, int rows, const icz_butd_params* G, float* loss_out, hipStream_t st) {
-    ICZ_REQUIRE(!xe_grouped(), "icz_butd_xe_backward_swor: the stored forward pass is a grouped one (icz_butd_xe_forward_n): its rows are not sorted by length");
-    ICZ_TRY(check_swor("butd", rows));
-    ICZ_TRY(swor_loss(a, tb.logit, dims.V, pad_vocab(dims.V), loss_out, st));
-    bptt_early_out = false;
-    ICZ_TRY(bptt_prelude(st));
-    return bptt(*G, st);
-}
-
 // ------------------------------------------------------------------------------------------------
 // helpers for the backward GEMMs
 // direct output (ns = 1, where g.out points) if there are already enough tiles, else slabs in `slab` (null: never split above 64 rows)
@@ -571,7 +498,7 @@ int Butd::wgrad(const float* dY, int ldy, int M, const float* X, int ldx, int N,
 }
 
 // The transposed weight copies of the per-step dgrad products are rebuilt lazily, by the first backward call after an optimizer
-// step: every entry point calls this in front of bptt(), OUTSIDE its captured graph (a replayed graph must not rebuild them).
+// step: backward() calls this in front of bptt(), OUTSIDE its captured graph (a replayed graph must not rebuild them).
 int Butd::bptt_prelude(hipStream_t st) {
     if (wt_lm_ih && !wt_fresh) ICZ_TRY(refresh_transposes(st));
     // the side stream of bptt, created here, outside any capture.  Lowest priority: its big GEMMs only fill CUs the BPTT chain leaves idle
@@ -587,7 +514,9 @@ struct Butd::BpttCall {
     // B rows are worked on per step; the buffers hold Bs rows per step, of which those are rows [roff, roff + B) (Bs = B, roff = 0
     // except behind a merged chain, whose evaluation-mode rows in front carry zero gradient rows through the GEMMs over all steps)
     int B, T, Bs, roff, TB;
-    // backward of a sampled rollout: the GEMMs over all (t, b) rows stop behind the last step the rollout ran (GemmArgs::rows_live)
+    // backward of a sampled rollout (eo): the steps behind the reference's break never ran -- their kernels return at entry, and the
+    // GEMMs over all (t, b) rows stop behind the last step the rollout ran (rl: GemmArgs::rows_live)
+    bool eo;
     const int* rl;
     // behind sample_n: K rows per image (row = img * K + k) -- the kernels that read the image's features / enc_ctx per row find it
     // through tb.imgk, and the image-side products (d enc_ctx, the mean-feature weights) are folded onto the n_img images first
@@ -601,7 +530,7 @@ struct Butd::BpttCall {
 // gradients, bit 3 = attention block, biases.  After each of the first three the corresponding gradient group is complete
 // in stream order (icz_butd_set_grad_callback); fire_cb = false leaves the callbacks to the caller, which replays every phase
 // as its own captured graph and calls them in between.
-int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_cb) {
+int Butd::bptt(const icz_butd_params& G, hipStream_t st, bool eo, int phases, bool fire_cb) {
     const bool cb = grad_cb && fire_cb;
     // The attention block's tail (phase 3: d enc_ctx, two small weight gradients, bias sums, weight-norm backward: ~0.2 ms of kernels
     // that fill a fraction of the chip) depends on the loop only.  When the whole backward is one call without a DP callback it is
@@ -611,7 +540,7 @@ int Butd::bptt(const icz_butd_params& G, hipStream_t st, int phases, bool fire_c
     // separate graphs and stay in line.
     const bool tail_side = phases == 0xF && !grad_cb && concurrent;
     const int K = cur_K;
-    BpttCall c = {G, st, cur_B, cur_T, cur_rows, cur_row0, cur_T * cur_rows, (bptt_early_out && early_out) ? live_rows : nullptr,
+    BpttCall c = {G, st, cur_B, cur_T, cur_rows, cur_row0, cur_T * cur_rows, eo, eo ? live_rows : nullptr,
                   K, K > 1 ? cur_nimg : cur_B, K > 1 ? tb.imgk : nullptr, {concurrent ? &low : nullptr, 0}, {tail_side ? &low : nullptr, 1}};
     if (phases & 1) {
         ICZ_TRY(bptt_predict(c));
@@ -712,8 +641,8 @@ int Butd::bptt_loop(BpttCall& c) {
         // REINFORCE backward of a sampled rollout: the steps behind the reference's break never ran (sample_chain) -- their kernels
         // return at entry, the producers of d gates / d dec / ds rows write zeros (the GEMMs over all steps read them), and the
         // first live step takes no carry from the dead one behind it
-        const int* const live = (bptt_early_out && early_out && t > 0) ? nunf + (t - 1) : nullptr;
-        const int* const carry_live = (bptt_early_out && early_out && t + 1 < T) ? nunf + t : nullptr;
+        const int* const live = (c.eo && t > 0) ? nunf + (t - 1) : nullptr;
+        const int* const carry_live = (c.eo && t + 1 < T) ? nunf + t : nullptr;
         DropCfg d_out = make_drop(d_seed, cur_train, rng.out_mask, (size_t)B * H, RNG_OUT, t);
         DropCfg d_att = make_drop(d_seed, cur_train, rng.att_mask, (size_t)B * R * A, RNG_ATT, t);
         DropCfg d_off = {0, nullptr, nullptr, 0, 0};
@@ -937,22 +866,35 @@ int icz_butd_scst_rollouts(icz_butd_t* h, const float* feats, int32_t B, int32_t
 int icz_butd_sample_backward(icz_butd_t* h, const float* reward, const icz_butd_params* grads, float* loss_out,
                              float* mask_sum_out, float mask_sum_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Butd*>(h)->sample_backward(reward, grads, loss_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::ROLLOUT, "butd", "butd sample_backward"};
+    hd.rollout = {reward, nullptr, loss_out, nullptr, mask_sum_out};
+    hd.norm_global = mask_sum_global;
+    return reinterpret_cast<Butd*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
+// sample_backward with an SCST objective (scst_objective.hip) in the place of RewardCriterion
 int icz_butd_sample_backward_objective(icz_butd_t* h, const icz_scst_objective* obj, const icz_butd_params* grads, float* loss_out3,
                                        float* ent_out, float* mask_sum_out, float mask_sum_global, void* stream) {
-    ICZ_TRY(icz::scst_objective_args("icz_butd_sample_backward_objective", obj, obj ? obj->K : 1, 1, nullptr));
+    ScstObjective o;
+    ICZ_TRY(icz::scst_objective_args("icz_butd_sample_backward_objective", obj, obj ? obj->K : 1, 1, &o));
     ICZ_REQUIRE(grads && loss_out3, "icz_butd_sample_backward_objective: null argument");
     ICZ_REQUIRE(h, "icz_butd_sample_backward_objective: null handle");
-    return reinterpret_cast<Butd*>(h)->sample_backward_objective(obj, grads, loss_out3, ent_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::ROLLOUT, "butd", "butd sample_backward_objective"};
+    hd.rollout = {nullptr, &o, loss_out3, ent_out, mask_sum_out};
+    hd.objective = obj;
+    hd.norm_global = mask_sum_global;
+    return reinterpret_cast<Butd*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
 int icz_butd_sample_backward_dlogp(icz_butd_t* h, const float* dlogp, const icz_butd_params* grads, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Butd*>(h)->sample_backward_dlogp(dlogp, grads, (hipStream_t)stream);
+    LossHead hd = {LossHead::ROLLOUT_DLOGP, "butd", "butd sample_backward_dlogp"};
+    hd.upstream = dlogp;
+    return reinterpret_cast<Butd*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
 int icz_butd_xe_backward_dlogits(icz_butd_t* h, const float* dpacked, const icz_butd_params* grads, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Butd*>(h)->xe_backward_dlogits(dpacked, grads, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE_DLOGITS, "butd", "butd xe_backward_dlogits"};
+    hd.upstream = dpacked;
+    return reinterpret_cast<Butd*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
 int icz_butd_sample_mask_sum(icz_butd_t* h, float* mask_sum_out, void* stream) {
     ICZ_REQUIRE(h, "null handle");
@@ -985,7 +927,9 @@ int icz_butd_xe_forward_n(icz_butd_t* h, const float* feats, const int64_t* capt
 int icz_butd_xe_backward(icz_butd_t* h, float smoothing, const icz_butd_params* grads, float* loss_out,
                          float n_tokens_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Butd*>(h)->xe_backward(smoothing, grads, loss_out, n_tokens_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE, "butd", "butd xe_backward"};
+    hd.smoothing = smoothing; hd.loss_out = loss_out; hd.norm_global = n_tokens_global;
+    return reinterpret_cast<Butd*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
 int icz_butd_xe_backward_distill(icz_butd_t* h, const icz_distill_opts* opts, const icz_butd_params* grads, float* loss_out3,
                                  float n_tokens_global, void* stream) {
@@ -994,7 +938,9 @@ int icz_butd_xe_backward_distill(icz_butd_t* h, const icz_distill_opts* opts, co
     ICZ_TRY(distill_args("icz_butd_xe_backward_distill", opts, b ? b->dims.V : -1, &a));
     ICZ_REQUIRE(grads && loss_out3, "icz_butd_xe_backward_distill: null grads or loss");
     ICZ_REQUIRE(h, "icz_butd_xe_backward_distill: null handle");
-    return b->xe_backward_distill(a, grads, loss_out3, n_tokens_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE_DISTILL, "butd", "butd xe_backward_distill"};
+    hd.distill = &a; hd.loss_out = loss_out3; hd.norm_global = n_tokens_global;
+    return b->backward(hd, grads, (hipStream_t)stream);
 }
 int icz_butd_xe_backward_swor(icz_butd_t* h, const icz_swor_opts* opts, int32_t rows, const icz_butd_params* grads, float* loss_out,
                               void* stream) {
@@ -1002,7 +948,9 @@ int icz_butd_xe_backward_swor(icz_butd_t* h, const icz_swor_opts* opts, int32_t 
     ICZ_TRY(swor_args("icz_butd_xe_backward_swor", opts, rows, &a));
     ICZ_REQUIRE(grads && loss_out, "icz_butd_xe_backward_swor: null grads or loss");
     ICZ_REQUIRE(h, "icz_butd_xe_backward_swor: null handle");
-    return reinterpret_cast<Butd*>(h)->xe_backward_swor(a, rows, grads, loss_out, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE_SWOR, "butd", "butd xe_backward_swor"};
+    hd.swor = &a; hd.swor_rows = rows; hd.loss_out = loss_out;
+    return reinterpret_cast<Butd*>(h)->backward(hd, grads, (hipStream_t)stream);
 }
 
 static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }

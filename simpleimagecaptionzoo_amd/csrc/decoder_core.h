@@ -1,5 +1,5 @@
 // Host-side machinery shared by the BUTD, AoA and NIC decoder handles: device allocations, the hipGraph cache, side
-// streams, the caption loss head (teacher-forced XE input, packed logits, XE / REINFORCE losses), the decoder seams (DecodeMember)
+// streams, the caption loss head (the state of the stored forward pass, packed logits, the loss heads that start a backward pass: LossHead), the decoder seams (DecodeMember)
 // with the drivers that run on them (beam search: beam.hip, sampling: sample_decode.hip, scoring given captions: score_captions.hip) and the greedy select tail.
 // Each rule below ("free => clear graphs", "zero-fill then sync", "sync => destroy a graph") has this one owner.
 // Destroying a captured graph: a replay of it may still be in flight on the caller's stream, so whoever destroys one synchronises the
@@ -208,10 +208,35 @@ struct RolloutHead { const float* reward; const ScstObjective* obj; float* loss_
 struct SworArgs { int n, estimator; float n_img_global; const float* phi; const double* G; const double* scores; const int32_t* perm; double* stats_out; };
 // scratch of its kernels: coef [images n] (-c / N per slot), cs [images n] (coef logp per slot, float64)
 struct SworScratch { float* coef; double* cs; };
+// What starts a backward pass: the loss head that turns the stored logits into dlogits in place, as a kind with that kind's arguments.
+// A C entry fills one in and hands it to its family's backward(); CaptionHead checks it against the stored pass (check_loss_head),
+// queues it (launch_loss_head) and marks the pass consumed (begin_backward); the family runs its BPTT behind it.
+struct LossHead {
+    enum Kind { XE, XE_DISTILL, XE_SWOR, XE_DLOGITS, ROLLOUT, ROLLOUT_DLOGP };
+    Kind kind;
+    const char* fam;                  // "butd" / "aoa" / "nic" and ...
+    const char* who;                  // ... the entry ("butd xe_backward_distill"), as the error texts name them
+    float norm_global = 0.f;          // n_tokens_global (XE kinds) / mask_sum_global (ROLLOUT): > 0 the value, 0 the local one, < 0 the device
+                                      // scalar handed over by icz_*_set_*_global
+    float* loss_out = nullptr;        // XE [1], XE_DISTILL [3], XE_SWOR [1 + images]; ROLLOUT keeps its outputs in `rollout`
+    float smoothing = 0.f;            // XE
+    const DistillArgs* distill = nullptr;
+    const SworArgs* swor = nullptr;   // XE_SWOR, with the caller's row count
+    int swor_rows = 0;
+    const float* upstream = nullptr;  // XE_DLOGITS: dpacked [n_tokens, V]; ROLLOUT_DLOGP: dlogp [rows, T]
+    RolloutHead rollout = {};         // ROLLOUT
+    const icz_scst_objective* objective = nullptr;      // ROLLOUT with an objective: the caller's struct, checked against the stored rollout
+    const int32_t* group_len = nullptr;                 // XE behind a grouped forward (Butd::xe_forward_n): steps per row (device) -> xe_group_loss
+    bool rollout_kind() const { return kind >= ROLLOUT; }      // the stored pass is a sampled rollout: the early-out of its backward pass applies
+};
 // The caption loss head: host-side state of a stored training-mode forward pass and the loss buffers of all three decoders.
 struct CaptionHead {
     int mode = 0;                 // 0 none, 1 sample rollout stored, 2 XE forward stored
     int cur_B = 0, cur_T = 0, cur_L = 0, n_tokens = 0;
+    // rows per image of the stored pass, row = img * K + k (sample_n, beyond the reference; Butd::xe_forward_n); 1 = every other entry
+    // point.  Set by the family behind begin_rollout / begin_xe.
+    int cur_K = 1;
+    bool early_out = true;        // option "early_out": rollout / BPTT steps behind the reference's break return at entry (0: they run, A/B)
     bool cur_train = false;
     const int64_t* cur_seq = nullptr; const float* cur_logp = nullptr; const int64_t* cur_captions = nullptr;
     std::vector<int> rows_t;      // active rows per step of the XE batch (lengths sorted in decreasing order)
@@ -238,6 +263,17 @@ struct CaptionHead {
     static int xe_steps(const char* who, const int32_t* lengths, int B, int L, int* T_out);
     // the state of an XE forward pass (rows_t, n_tokens) and the Philox seed upload
     void begin_xe(const int32_t* lengths, int B, int T, int L, const int64_t* captions, bool train, uint64_t seed, hipStream_t st);
+    // its twin for a sampled rollout of `rows` rows (every row stored at every step) into the caller's seq_out / logp_out [rows, T]
+    void begin_rollout(int rows, int T, const int64_t* seq_out, const float* logp_out, uint64_t seed, hipStream_t st);
+    // The start of a backward pass.  check_loss_head: the rules of `hd` against the stored pass, on the host before anything is queued
+    // (grads: the entry's gradient table, for the null-argument rule of the entries that leave it to the handle).  launch_loss_head:
+    // its launches alone, dlogits over `logits` in place (rows / row0 as reinforce); a ROLLOUT head may sit inside a captured graph.
+    // begin_backward: the one place that marks the stored pass consumed, outside any capture -- the normaliser of a ROLLOUT head, then
+    // either the head's launches (consumed once they all went through: a head that fails leaves the pass stored) or, in_graph, a head
+    // the caller launches itself inside its captured graph (consumed at once, whatever the capture returns).
+    int check_loss_head(const LossHead& hd, const void* grads) const;
+    int launch_loss_head(const LossHead& hd, float* logits, int V, int ldl, hipStream_t st, int rows = 0, int row0 = 0);
+    int begin_backward(const LossHead& hd, bool in_graph, float* logits, int V, int ldl, hipStream_t st, int rows = 0, int row0 = 0);
     void captions_to_tok(int64_t* tok, hipStream_t st) const;
     // logits [T B, ldl] <-> packed rows [n_tokens, V] through the packed-sequence index
     int gather_packed(const float* logit, int V, int ldl, float* packed_out, hipStream_t st);
@@ -250,7 +286,7 @@ struct CaptionHead {
     // teachers' packed logits; loss_out3 = {loss, sum hard / N, sum kd / N}.  alpha = 0 is xe_loss.
     int distill_loss(const DistillArgs& a, float n_tokens_global, float* logits, int V, int ldl, float* loss_out3, hipStream_t st);
     // SCST on without-replacement samples (swor_objective.hip): loss and dlogits (in place) of the stored XE forward pass on the sampled
-    // captions; loss_out [1 + images] = {loss, sum c logp by image}.  check_swor: the rules against the stored forward pass (a
+    // captions; loss_out [1 + images] = {loss, sum c logp by image}.  check_swor: the rules against the stored XE forward pass (a
     // training-mode one, teacher-forced, of `rows` rows), before anything is queued.
     int check_swor(const char* who, int rows) const;
     int swor_loss(const SworArgs& a, float* logits, int V, int ldl, float* loss_out, hipStream_t st);
@@ -260,8 +296,8 @@ struct CaptionHead {
     int reinforce(const float* reward, float* logits, int V, int ldl, float* loss_out, float* msum_out, hipStream_t st, int rows = 0, int row0 = 0);
     // An SCST objective in the place of reinforce (scst_objective.hip): kind 0 with entropy_weight 0 calls reinforce itself;
     // loss_out3 = {loss, obj, ent}, ent_out [rows of the rollout, T] optional.  check_objective: the rules of icz_scst_objective
-    // against the stored rollout (stored_K = its samples per image), before anything is queued.
-    int check_objective(const char* who, const icz_scst_objective* obj, int stored_K, ScstObjective* out) const;
+    // against the stored rollout (cur_K = its samples per image), before anything is queued.
+    int check_objective(const char* who, const icz_scst_objective* obj) const;
     int scst_objective(const ScstObjective& o, float* logits, int V, int ldl, float* loss_out3, float* ent_out, float* msum_out, hipStream_t st,
                        int rows = 0, int row0 = 0);
     int rollout_head(const RolloutHead& hd, float* logits, int V, int ldl, hipStream_t st, int rows = 0, int row0 = 0);

@@ -106,6 +106,54 @@ void CaptionHead::begin_xe(const int32_t* lengths, int B, int T, int L, const in
     }
 }
 
+void CaptionHead::begin_rollout(int rows, int T, const int64_t* seq_out, const float* logp_out, uint64_t seed, hipStream_t st) {
+    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, seed, (float*)nullptr, 0.f);
+    mode = 1; cur_B = rows; cur_T = T; cur_train = true; cur_seq = seq_out; cur_logp = logp_out;
+    rows_t.assign(T, rows);
+}
+
+int CaptionHead::check_loss_head(const LossHead& hd, const void* grads) const {
+    ICZ_TRY(require_mode(hd.rollout_kind() ? 1 : 2, hd.fam));
+    switch (hd.kind) {
+    case LossHead::XE: ICZ_REQUIRE(grads, "%s: null grads", hd.who); break;
+    case LossHead::XE_DISTILL: ICZ_TRY(require_teacher_forced(hd.who)); break;
+    case LossHead::XE_SWOR: ICZ_TRY(check_swor(hd.fam, hd.swor_rows)); break;
+    case LossHead::XE_DLOGITS:
+    case LossHead::ROLLOUT_DLOGP: ICZ_REQUIRE(hd.upstream && grads, "%s: null argument", hd.who); break;
+    case LossHead::ROLLOUT:
+        if (hd.objective) ICZ_TRY(check_objective(hd.who, hd.objective));
+        else ICZ_REQUIRE(hd.rollout.reward && grads, "%s: null argument", hd.who);
+        break;
+    }
+    return ICZ_OK;
+}
+
+int CaptionHead::launch_loss_head(const LossHead& hd, float* logits, int V, int ldl, hipStream_t st, int rows, int row0) {
+    switch (hd.kind) {
+    case LossHead::XE:
+        if (hd.group_len) return xe_group_loss(hd.group_len, hd.smoothing, hd.norm_global, logits, V, ldl, hd.loss_out, st);
+        return xe_loss(hd.smoothing, hd.norm_global, logits, V, ldl, hd.loss_out, st);
+    case LossHead::XE_DISTILL: return distill_loss(*hd.distill, hd.norm_global, logits, V, ldl, hd.loss_out, st);
+    case LossHead::XE_SWOR: return swor_loss(*hd.swor, logits, V, ldl, hd.loss_out, st);
+    case LossHead::XE_DLOGITS: return scatter_packed(hd.upstream, V, ldl, logits, st);
+    case LossHead::ROLLOUT: return rollout_head(hd.rollout, logits, V, ldl, st, rows, row0);
+    case LossHead::ROLLOUT_DLOGP:       // the upstream d loss / d logprobs in the place of reinforce's coefficients
+        ICZ_CHECK_HIP(hipMemcpyAsync(coef, hd.upstream, sizeof(float) * cur_B * cur_T, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(reinforce_dlogits_kernel, dim3(cdiv(ldl, 256), cur_T * (rows ? rows : cur_B)), dim3(256), 0, st, logits, V, ldl, draw, lse,
+                           (const float*)coef, cur_B, cur_T, rows, row0);
+        ICZ_CHECK_HIP(hipGetLastError());
+        return ICZ_OK;
+    }
+    return ICZ_OK;
+}
+
+int CaptionHead::begin_backward(const LossHead& hd, bool in_graph, float* logits, int V, int ldl, hipStream_t st, int rows, int row0) {
+    if (hd.kind == LossHead::ROLLOUT) set_msum_global(hd.norm_global, st);      // (a captured graph reads the device scalar)
+    if (!in_graph) ICZ_TRY(launch_loss_head(hd, logits, V, ldl, st, rows, row0));
+    mode = 0;                     // the stored logits are consumed
+    return ICZ_OK;
+}
+
 void CaptionHead::captions_to_tok(int64_t* tok, hipStream_t st) const {
     hipLaunchKernelGGL(captions_to_tok_kernel, dim3(cdiv(cur_T * cur_B, 256)), dim3(256), 0, st, cur_captions, cur_B, cur_L, cur_T, tok);
 }
@@ -155,9 +203,7 @@ int launch_xe_loss(float* logits, int V, int ldl, const int64_t* captions, int L
 int CaptionHead::xe_loss(float smoothing, float n_tokens_global, float* logits, int V, int ldl, float* loss_out, hipStream_t st) {
     const float n = n_tokens_global > 0.f ? n_tokens_global : (float)n_tokens;
     const float* n_dev = n_tokens_global < 0.f ? d_msum : nullptr;      // < 0: the device scalar handed over by *_set_*_global
-    ICZ_TRY(launch_xe_loss(logits, V, ldl, cur_captions, cur_L, cur_B, cur_T, rows_t.data(), smoothing, n, n_dev, loss_rows, loss_out, st));
-    mode = 0;
-    return ICZ_OK;
+    return launch_xe_loss(logits, V, ldl, cur_captions, cur_L, cur_B, cur_T, rows_t.data(), smoothing, n, n_dev, loss_rows, loss_out, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -215,9 +261,7 @@ int CaptionHead::xe_group_loss(const int32_t* len, float smoothing, float n_toke
                                hipStream_t st) {
     const float n = n_tokens_global > 0.f ? n_tokens_global : (float)n_tokens;
     const float* n_dev = n_tokens_global < 0.f ? d_msum : nullptr;
-    ICZ_TRY(launch_xe_group_loss(logits, V, ldl, cur_captions, cur_L, cur_B, cur_T, len, smoothing, n, n_dev, loss_rows, loss_out, st));
-    mode = 0;
-    return ICZ_OK;
+    return launch_xe_group_loss(logits, V, ldl, cur_captions, cur_L, cur_B, cur_T, len, smoothing, n, n_dev, loss_rows, loss_out, st);
 }
 
 void CaptionHead::set_msum_global(float msum_global, hipStream_t st) const {

@@ -4,8 +4,8 @@
 //   loss = ((1 - alpha) sum_rows hard + alpha sum_rows kd) / N,   kd = tau^2 KL(q || softmax(s / tau)),   hard = xe_loss_dlogits_kernel's
 //   d s  = ((1 - alpha) (softmax(s) - true) + alpha tau (softmax(s / tau) - q)) / N
 // distill_loss_dlogits_kernel forms q in registers from the teachers' packed logits and writes d s over the student's stored logits;
-// CaptionHead::distill_loss puts it in the place of xe_loss, and the three decoders' xe_backward_distill run their backward pass
-// behind it (butd_train.hip, aoa_train.hip, nic.hip).
+// CaptionHead::distill_loss puts it in the place of xe_loss (LossHead::XE_DISTILL), and the three decoders' backward() run their
+// backward pass behind it (butd_train.hip, aoa_train.hip, nic.hip).
 #include <cmath>
 
 #include "ens_sample.h"
@@ -210,7 +210,6 @@ int CaptionHead::distill_loss(const DistillArgs& a, float n_tokens_global, float
     hipLaunchKernelGGL(distill_sum_kernel, dim3(1), dim3(256), 0, st, (const float*)loss_rows, (const float*)kd_rows, T * B, a.alpha, 1.0f / n,
                        n_dev, loss_out3);
     ICZ_CHECK_HIP(hipGetLastError());
-    mode = 0;
     return ICZ_OK;
 }
 

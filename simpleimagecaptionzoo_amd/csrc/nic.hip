@@ -33,9 +33,8 @@ struct Nic : CaptionHead, DecodeMember {
     float *dG = nullptr, *dHd = nullptr, *dEmb = nullptr, *dcb[2] = {nullptr, nullptr}, *X = nullptr, *dWp = nullptr;
     size_t xfloats = 0;
     float* feat_rows = nullptr;          // beam search: the image embedding replicated per beam row (prologue)
-    // multi-sample SCST rollout (sample_n, beyond the reference): cur_K sampled rows per image, row = img * K + k (1 = every other entry
-    // point); the rollout runs on the image embeddings expanded to the rows, the backward pass folds d features back onto the images
-    int cur_K = 1;
+    // multi-sample SCST rollout (sample_n, beyond the reference): cur_K (CaptionHead) sampled rows per image, row = img * K + k; the
+    // rollout runs on the image embeddings expanded to the rows, the backward pass folds d features back onto the images
     int32_t* imgk = nullptr;             // image of each decoder row
     float *feat_n = nullptr, *dfeat_n = nullptr;      // [max_rows, E]: the expanded embeddings (kept for the backward pass), their gradient per row
     icz_rng rng = {};
@@ -48,22 +47,16 @@ struct Nic : CaptionHead, DecodeMember {
     int token_step(int rows, const int64_t* tokens, bool emb_ready, const float* h_in, const float* c_in, float* h_out, float* c_out,
                    float* emb_out, float* gates_out, float* hdrop_out, float* logits_out, DropCfg drop_out, hipStream_t st, int* pred_nsplit = nullptr,
                    const int* live = nullptr);
-    bool early_out = true, bptt_early_out = false;      // rollout / BPTT steps behind sample_rl's break (NIC_Model.py:150) return at entry
     int greedy(const float* feats, int B, int T, int64_t* ids_out, hipStream_t st);
     int ensure_train(int B, int T);
     int sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
     int sample_n(const float* feats, int B, int K, int T, const icz_rng* r, int64_t* seq_out, float* logp_out, hipStream_t st);
-    int sample_backward(const float* reward, const icz_nic_params* G, float* dfeats, float* loss_out, float* msum_out, float msum_global, hipStream_t st);
-    int sample_backward_head(const RolloutHead& hd, const icz_nic_params* G, float* dfeats, float msum_global, hipStream_t st);
-    int sample_backward_objective(const icz_scst_objective* obj, const icz_nic_params* G, float* dfeats, float* loss_out3, float* ent_out,
-                                  float* msum_out, float msum_global, hipStream_t st);
     int xe_forward(const float* feats, const int64_t* captions, int B, int L, const int32_t* lengths, const icz_rng* r, int train,
                    float* packed_out, hipStream_t st);
-    int xe_backward(float smoothing, const icz_nic_params* G, float* dfeats, float* loss_out, float n_tokens_global, hipStream_t st);
-    int xe_backward_distill(const DistillArgs& a, const icz_nic_params* G, float* dfeats, float* loss_out3, float n_tokens_global, hipStream_t st);
-    int xe_backward_swor(const SworArgs& a, int rows, const icz_nic_params* G, float* dfeats, float* loss_out, hipStream_t st);
-    int xe_backward_dlogits(const float* dpacked, const icz_nic_params* G, float* dfeats, hipStream_t st);
-    int bptt(const icz_nic_params& G, float* dfeats, hipStream_t st);
+    // the backward pass of the stored forward pass behind the loss head `hd` (every icz_nic_*_backward* entry; eager, as every NIC path)
+    int backward(const LossHead& hd, const icz_nic_params* G, float* dfeats, hipStream_t st);
+    // eo: rollout / BPTT steps behind sample_rl's break (NIC_Model.py:150) return at entry (a rollout head and option "early_out")
+    int bptt(const icz_nic_params& G, float* dfeats, hipStream_t st, bool eo);
     int nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* out, int* ns, int target, hipStream_t st,
            const int* live = nullptr);
     // decoder seams (DecodeMember, decoder_core.h): the image step, one token step, the beam-state gather
@@ -212,10 +205,8 @@ int Nic::sample(const float* feats, int B, int T, const icz_rng* r, int64_t* seq
     ICZ_REQUIRE(fresh, "nic: call icz_nic_refresh_weights after binding/updating parameters");
     ICZ_TRY(ensure_train(B, T));
     rng = *r;
-    hipLaunchKernelGGL(set_scalars_kernel, dim3(1), dim3(1), 0, st, d_seed, rng.seed, (float*)nullptr, 0.f);
-    mode = 1; cur_B = B; cur_T = T; cur_train = true; cur_feats = feats; cur_seq = seq_out; cur_logp = logp_out;
-    cur_K = 1;
-    rows_t.assign(T, B);
+    begin_rollout(B, T, seq_out, logp_out, rng.seed, st);
+    cur_feats = feats; cur_K = 1;
     const size_t H = dims.H, E = dims.E, sH = (size_t)B * H;
     ICZ_CHECK_HIP(hipMemsetAsync(th, 0, sizeof(float) * sH, st));
     ICZ_CHECK_HIP(hipMemsetAsync(tc, 0, sizeof(float) * sH, st));
@@ -265,30 +256,13 @@ int Nic::sample_n(const float* feats, int B, int K, int T, const icz_rng* r, int
     return ICZ_OK;
 }
 
-int Nic::sample_backward(const float* reward, const icz_nic_params* G, float* dfeats, float* loss_out, float* msum_out, float msum_global,
-                         hipStream_t st) {
-    ICZ_TRY(require_mode(1, "nic"));
-    ICZ_REQUIRE(reward && G, "nic sample_backward: null argument");
-    return sample_backward_head({reward, nullptr, loss_out, nullptr, msum_out}, G, dfeats, msum_global, st);
-}
-
-// sample_backward with an SCST objective (scst_objective.hip) in the place of RewardCriterion (eager, as every NIC backward pass)
-int Nic::sample_backward_objective(const icz_scst_objective* obj, const icz_nic_params* G, float* dfeats, float* loss_out3, float* ent_out,
-                                   float* msum_out, float msum_global, hipStream_t st) {
-    ICZ_TRY(require_mode(1, "nic"));
-    ScstObjective o;
-    ICZ_TRY(check_objective("nic sample_backward_objective", obj, cur_K, &o));
-    return sample_backward_head({nullptr, &o, loss_out3, ent_out, msum_out}, G, dfeats, msum_global, st);
-}
-
-int Nic::sample_backward_head(const RolloutHead& hd, const icz_nic_params* G, float* dfeats, float msum_global, hipStream_t st) {
-    set_msum_global(msum_global, st);      // < 0: keep the device value handed over by icz_nic_set_norm_global
-    ICZ_TRY(rollout_head(hd, tlogit, dims.V, Vp, st));
-    mode = 0;
-    bptt_early_out = true;
-    if (cur_K == 1 || !dfeats) return bptt(*G, dfeats, st);
+int Nic::backward(const LossHead& hd, const icz_nic_params* G, float* dfeats, hipStream_t st) {
+    ICZ_TRY(check_loss_head(hd, G));
+    ICZ_TRY(begin_backward(hd, false, tlogit, dims.V, Vp, st));
+    const bool eo = hd.rollout_kind() && early_out;
+    if (!hd.rollout_kind() || cur_K == 1 || !dfeats) return bptt(*G, dfeats, st, eo);
     // behind sample_n: d features of the B K rows, then the K rows of an image added in k order -> [B, E]
-    ICZ_TRY(bptt(*G, dfeat_n, st));
+    ICZ_TRY(bptt(*G, dfeat_n, st, eo));
     const int n_img = cur_B / cur_K;
     launch_rowgroup_sum(dfeat_n, n_img, cur_K, (size_t)dims.E, dfeats, st);
     ICZ_CHECK_HIP(hipGetLastError());
@@ -325,41 +299,6 @@ int Nic::xe_forward(const float* feats, const int64_t* captions, int B, int L, c
     return ICZ_OK;
 }
 
-int Nic::xe_backward(float smoothing, const icz_nic_params* G, float* dfeats, float* loss_out, float n_tokens_global, hipStream_t st) {
-    ICZ_TRY(require_mode(2, "nic"));
-    ICZ_REQUIRE(G, "nic xe_backward: null grads");
-    ICZ_TRY(xe_loss(smoothing, n_tokens_global, tlogit, dims.V, Vp, loss_out, st));
-    bptt_early_out = false;
-    return bptt(*G, dfeats, st);
-}
-
-// xe_backward with the distillation loss (distill.hip) in the place of xe_loss
-int Nic::xe_backward_distill(const DistillArgs& a, const icz_nic_params* G, float* dfeats, float* loss_out3, float n_tokens_global, hipStream_t st) {
-    ICZ_TRY(require_mode(2, "nic"));
-    ICZ_TRY(require_teacher_forced("nic xe_backward_distill"));
-    ICZ_TRY(distill_loss(a, n_tokens_global, tlogit, dims.V, Vp, loss_out3, st));
-    bptt_early_out = false;
-    return bptt(*G, dfeats, st);
-}
-
-// xe_backward with the without-replacement SCST head (swor_objective.hip) in the place of xe_loss
-int Nic::xe_backward_swor(const SworArgs& a, int rows, const icz_nic_params* G, float* dfeats, float* loss_out, hipStream_t st) {
-    ICZ_TRY(check_swor("nic", rows));
-    ICZ_TRY(swor_loss(a, tlogit, dims.V, Vp, loss_out, st));
-    bptt_early_out = false;
-    return bptt(*G, dfeats, st);
-}
-
-// xe_backward driven by an upstream gradient w.r.t. the packed logits (Butd::xe_backward_dlogits)
-int Nic::xe_backward_dlogits(const float* dpacked, const icz_nic_params* G, float* dfeats, hipStream_t st) {
-    ICZ_TRY(require_mode(2, "nic"));
-    ICZ_REQUIRE(dpacked && G, "nic xe_backward_dlogits: null argument");
-    ICZ_TRY(scatter_packed(dpacked, dims.V, Vp, tlogit, st));
-    mode = 0;
-    bptt_early_out = false;
-    return bptt(*G, dfeats, st);
-}
-
 // A[M,K] . B[K,N]: with ns_out, slabs [ns][M][N] in `out` (= X, one slab: the dense product) for the consumer to sum; without, the
 // finished dense product in `out`, split-K slabs going through `ws`
 int Nic::nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int N, float* out, int* ns_out, int target, hipStream_t st,
@@ -369,7 +308,7 @@ int Nic::nn(const float* A, int lda, int M, int K, const float* Bm, int ldb, int
     return gemm_finished(GEMM_NN, g, split_backward(target), nullptr, ws, ws_floats, st, "nic");
 }
 
-int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st) {
+int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st, bool eo) {
     const int B = cur_B, T = cur_T, H = dims.H, E = dims.E, V = dims.V;
     const int TB = T * B;
     const size_t sH = (size_t)B * H;
@@ -394,7 +333,6 @@ int Nic::bptt(const icz_nic_params& G, float* dfeats, hipStream_t st) {
         a.dgates = dG + slot * 4 * H; a.dc_prev = dcb[cur ^ 1];
         a.rows = bt; a.H = H;
         // backward of a sampled rollout: a step behind the reference's break (NIC_Model.py:150) never ran -- zero d gates, no carry
-        const bool eo = bptt_early_out && early_out;
         const int* const live = (eo && t > 0) ? nunf + (t - 1) : nullptr;
         a.live = live; a.carry_live = (eo && t >= 0 && t + 1 < T) ? nunf + t : nullptr;
         DropCfg d = t >= 0 ? nic_drop(d_seed, cur_train, rng.out_mask, sH, t) : off;
@@ -485,15 +423,23 @@ int icz_nic_sample_n(icz_nic_t* h, const float* features, int32_t B, int32_t K, 
 int icz_nic_sample_backward(icz_nic_t* h, const float* reward, const icz_nic_params* grads, float* dfeatures_out, float* loss_out,
                             float* mask_sum_out, float mask_sum_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Nic*>(h)->sample_backward(reward, grads, dfeatures_out, loss_out, mask_sum_out, mask_sum_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::ROLLOUT, "nic", "nic sample_backward"};
+    hd.rollout = {reward, nullptr, loss_out, nullptr, mask_sum_out};
+    hd.norm_global = mask_sum_global;
+    return reinterpret_cast<Nic*>(h)->backward(hd, grads, dfeatures_out, (hipStream_t)stream);
 }
+// sample_backward with an SCST objective (scst_objective.hip) in the place of RewardCriterion
 int icz_nic_sample_backward_objective(icz_nic_t* h, const icz_scst_objective* obj, const icz_nic_params* grads, float* dfeatures_out,
                                       float* loss_out3, float* ent_out, float* mask_sum_out, float mask_sum_global, void* stream) {
-    ICZ_TRY(icz::scst_objective_args("icz_nic_sample_backward_objective", obj, obj ? obj->K : 1, 1, nullptr));
+    ScstObjective o;
+    ICZ_TRY(icz::scst_objective_args("icz_nic_sample_backward_objective", obj, obj ? obj->K : 1, 1, &o));
     ICZ_REQUIRE(grads && loss_out3, "icz_nic_sample_backward_objective: null argument");
     ICZ_REQUIRE(h, "icz_nic_sample_backward_objective: null handle");
-    return reinterpret_cast<Nic*>(h)->sample_backward_objective(obj, grads, dfeatures_out, loss_out3, ent_out, mask_sum_out, mask_sum_global,
-                                                                (hipStream_t)stream);
+    LossHead hd = {LossHead::ROLLOUT, "nic", "nic sample_backward_objective"};
+    hd.rollout = {nullptr, &o, loss_out3, ent_out, mask_sum_out};
+    hd.objective = obj;
+    hd.norm_global = mask_sum_global;
+    return reinterpret_cast<Nic*>(h)->backward(hd, grads, dfeatures_out, (hipStream_t)stream);
 }
 int icz_nic_set_scheduled_sampling(icz_nic_t* h, float ss_prob, const float* gate_uniforms, const float* draw_uniforms) {
     return set_scheduled_sampling("icz_nic_set_scheduled_sampling", reinterpret_cast<Nic*>(h), ss_prob, gate_uniforms, draw_uniforms);
@@ -515,7 +461,9 @@ int icz_nic_set_norm_global(icz_nic_t* h, const float* norm_dev, void* stream) {
 int icz_nic_xe_backward(icz_nic_t* h, float smoothing, const icz_nic_params* grads, float* dfeatures_out, float* loss_out,
                         float n_tokens_global, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Nic*>(h)->xe_backward(smoothing, grads, dfeatures_out, loss_out, n_tokens_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE, "nic", "nic xe_backward"};
+    hd.smoothing = smoothing; hd.loss_out = loss_out; hd.norm_global = n_tokens_global;
+    return reinterpret_cast<Nic*>(h)->backward(hd, grads, dfeatures_out, (hipStream_t)stream);
 }
 int icz_nic_xe_backward_distill(icz_nic_t* h, const icz_distill_opts* opts, const icz_nic_params* grads, float* dfeatures_out,
                                 float* loss_out3, float n_tokens_global, void* stream) {
@@ -524,7 +472,9 @@ int icz_nic_xe_backward_distill(icz_nic_t* h, const icz_distill_opts* opts, cons
     ICZ_TRY(distill_args("icz_nic_xe_backward_distill", opts, n ? n->dims.V : -1, &a));
     ICZ_REQUIRE(grads && loss_out3, "icz_nic_xe_backward_distill: null grads or loss");
     ICZ_REQUIRE(h, "icz_nic_xe_backward_distill: null handle");
-    return n->xe_backward_distill(a, grads, dfeatures_out, loss_out3, n_tokens_global, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE_DISTILL, "nic", "nic xe_backward_distill"};
+    hd.distill = &a; hd.loss_out = loss_out3; hd.norm_global = n_tokens_global;
+    return n->backward(hd, grads, dfeatures_out, (hipStream_t)stream);
 }
 int icz_nic_xe_backward_swor(icz_nic_t* h, const icz_swor_opts* opts, int32_t rows, const icz_nic_params* grads, float* dfeatures_out,
                              float* loss_out, void* stream) {
@@ -532,10 +482,15 @@ int icz_nic_xe_backward_swor(icz_nic_t* h, const icz_swor_opts* opts, int32_t ro
     ICZ_TRY(swor_args("icz_nic_xe_backward_swor", opts, rows, &a));
     ICZ_REQUIRE(grads && loss_out, "icz_nic_xe_backward_swor: null grads or loss");
     ICZ_REQUIRE(h, "icz_nic_xe_backward_swor: null handle");
-    return reinterpret_cast<Nic*>(h)->xe_backward_swor(a, rows, grads, dfeatures_out, loss_out, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE_SWOR, "nic", "nic xe_backward_swor"};
+    hd.swor = &a; hd.swor_rows = rows; hd.loss_out = loss_out;
+    return reinterpret_cast<Nic*>(h)->backward(hd, grads, dfeatures_out, (hipStream_t)stream);
 }
+// xe_backward driven by an upstream gradient w.r.t. the packed logits
 int icz_nic_xe_backward_dlogits(icz_nic_t* h, const float* dpacked, const icz_nic_params* grads, float* dfeatures_out, void* stream) {
     ICZ_REQUIRE(h, "null handle");
-    return reinterpret_cast<Nic*>(h)->xe_backward_dlogits(dpacked, grads, dfeatures_out, (hipStream_t)stream);
+    LossHead hd = {LossHead::XE_DLOGITS, "nic", "nic xe_backward_dlogits"};
+    hd.upstream = dpacked;
+    return reinterpret_cast<Nic*>(h)->backward(hd, grads, dfeatures_out, (hipStream_t)stream);
 }
 }  // extern "C"

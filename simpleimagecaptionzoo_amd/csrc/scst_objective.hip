@@ -7,8 +7,8 @@
 //            dlogits[row, v] = coef (1[v == draw] - p_v) + (b mask / M) p_v (log p_v + H)
 // scst_risk_kernel fills coef as reinforce_loss_kernel does for a reward; scst_entropy_dlogits_kernel stands in for
 // reinforce_dlogits_kernel when b > 0; scst_finish_kernel sums the per-row entropies in a fixed order.  No float atomics: two runs
-// give the same bits.  CaptionHead::scst_objective puts them in the place of reinforce, and the three decoders'
-// sample_backward_objective run their backward pass behind it (butd_train.hip, aoa_train.hip, nic.hip).
+// give the same bits.  CaptionHead::scst_objective puts them in the place of reinforce (LossHead::ROLLOUT with an objective), and the
+// three decoders' backward() run their backward pass behind it (butd_train.hip, aoa_train.hip, nic.hip).
 #include <cmath>
 
 #include "decoder_core.h"
@@ -244,10 +244,10 @@ int launch_scst_objective(const ScstObjective& o, const float* logp, const int64
     return ICZ_OK;
 }
 
-int CaptionHead::check_objective(const char* who, const icz_scst_objective* obj, int stored_K, ScstObjective* out) const {
-    ICZ_TRY(scst_objective_args(who, obj, cur_B, cur_T, out));
-    ICZ_REQUIRE(obj->kind != ICZ_SCST_RISK || obj->K == stored_K, "%s: the risk term over K=%d samples per image, the stored rollout has %d", who,
-                obj->K, stored_K);
+int CaptionHead::check_objective(const char* who, const icz_scst_objective* obj) const {
+    ICZ_TRY(scst_objective_args(who, obj, cur_B, cur_T, nullptr));
+    ICZ_REQUIRE(obj->kind != ICZ_SCST_RISK || obj->K == cur_K, "%s: the risk term over K=%d samples per image, the stored rollout has %d", who,
+                obj->K, cur_K);
     return ICZ_OK;
 }
 

@@ -194,9 +194,9 @@ int launch_swor_objective(const SworArgs& a, float* logits, int V, int ldl, cons
     return ICZ_OK;
 }
 
-// rules 9 - 12 of icz_*_xe_backward_swor against the stored forward pass; nothing is queued and the stored forward stays usable
+// rules 10 - 12 of icz_*_xe_backward_swor against the stored XE forward pass (rule 9, that there is one: check_loss_head); nothing is
+// queued and the stored forward stays usable
 int CaptionHead::check_swor(const char* who, int rows) const {
-    ICZ_TRY(require_mode(2, who));
     ICZ_REQUIRE(cur_train, "%s xe_backward_swor: the stored forward pass ran in evaluation mode: it keeps no state for a backward pass", who);
     ICZ_REQUIRE(cur_ss_prob <= 0.f, "%s xe_backward_swor: the stored forward pass ran with scheduled sampling (ss_prob %g): it was fed other "
                 "tokens than the sampled captions", who, (double)cur_ss_prob);
@@ -206,9 +206,7 @@ int CaptionHead::check_swor(const char* who, int rows) const {
 
 int CaptionHead::swor_loss(const SworArgs& a, float* logits, int V, int ldl, float* loss_out, hipStream_t st) {
     const SworScratch w = {swor_coef, swor_cs};
-    ICZ_TRY(launch_swor_objective(a, logits, V, ldl, cur_captions, cur_L, cur_B, cur_T, rows_t.data(), w, loss_rows, loss_out, st));
-    mode = 0;
-    return ICZ_OK;
+    return launch_swor_objective(a, logits, V, ldl, cur_captions, cur_L, cur_B, cur_T, rows_t.data(), w, loss_rows, loss_out, st);
 }
 
 }  // namespace icz

@@ -15,6 +15,7 @@ import torch
 
 from ._lib import DistillOpts, IczError, check, lib, ptr, stream_ptr
 from .ensemble import check_members, check_weights
+from .handle import grad_args
 
 MIN_TEMPERATURE, MAX_TEMPERATURE = 0.25, 8.0
 
@@ -86,16 +87,9 @@ def xe_backward_distill(handle, grads, teacher_logits, weights=None, alpha=0.5, 
     teachers = list(teacher_logits)
     o, keep = _opts(teachers, teachers[0].shape[0] if rows is None and teachers else rows, handle.V, weights, alpha, temperature, smoothing)
     out3 = torch.zeros(3, dtype=torch.float32, device=handle.device)
-    gs = handle._grad_struct(grads)
-    if handle.family == "nic":
-        dfe = torch.zeros_like(handle._live[0]) if want_dfeats else None
-        check(handle._e.xe_backward_distill(handle._h, C.byref(o), C.byref(gs), ptr(dfe), ptr(out3), float(n_tokens_global), stream_ptr()))
-    else:
-        if want_dfeats:
-            raise IczError("want_dfeats: only the NIC decoder returns a gradient for its features")
-        dfe = None
-        check(handle._e.xe_backward_distill(handle._h, C.byref(o), C.byref(gs), ptr(out3), float(n_tokens_global), stream_ptr()))
-    handle._distill_live = keep       # the kernel reads the teachers' tensors in stream order
+    ga, dfe = grad_args(handle, handle._grad_struct(grads), want_dfeats)
+    check(handle._e.xe_backward_distill(handle._h, C.byref(o), *ga, ptr(out3), float(n_tokens_global), stream_ptr()))
+    handle._distill_live = keep      # the kernel reads the teachers' tensors in stream order
     res = (out3[0:1], out3[1:2], out3[2:3])
     return res + (dfe,) if want_dfeats else res
 
@@ -104,15 +98,9 @@ def xe_backward_dlogits(handle, dpacked, grads, *, want_dfeats=False):
     """The backward pass of the handle's last xe_forward for an upstream gradient w.r.t. its packed logits (sum(lengths), V), for
     every family (include/icz.h: icz_*_xe_backward_dlogits); fills `grads`.  A NicHandle with want_dfeats returns d features (B, E)."""
     dpacked = dpacked.to(device=handle.device, dtype=torch.float32).contiguous()
-    gs = handle._grad_struct(grads)
-    if handle.family == "nic":
-        dfe = torch.zeros_like(handle._live[0]) if want_dfeats else None
-        check(handle._e.xe_backward_dlogits(handle._h, ptr(dpacked), C.byref(gs), ptr(dfe), stream_ptr()))
-        return dfe
-    if want_dfeats:
-        raise IczError("want_dfeats: only the NIC decoder returns a gradient for its features")
-    check(handle._e.xe_backward_dlogits(handle._h, ptr(dpacked), C.byref(gs), stream_ptr()))
-    return None
+    ga, dfe = grad_args(handle, handle._grad_struct(grads), want_dfeats)
+    check(handle._e.xe_backward_dlogits(handle._h, ptr(dpacked), *ga, stream_ptr()))
+    return dfe
 
 
 def distill_loss(student, teacher_logits, targets, weights=None, alpha=0.5, temperature=1.0, smoothing=0.1, n_tokens=None, ld_out=None):

@@ -20,6 +20,19 @@ _ENTRIES = ("create", "destroy", "bind_params", "refresh_weights", "set_option",
             "sample_backward_objective", "xe_backward_swor")
 
 
+def grad_args(handle, gs, want_dfeats):
+    """The gradient arguments of a backward entry of `handle`'s family: its gradient struct `gs` and, for a NicHandle, the d features
+    pointer right behind it (zeros like the stored pass's features with want_dfeats, else null) -> (the arguments, d features or
+    None).  IczError for want_dfeats on another family.  A function, as the entry points of distill.py, swor.py and scst_objective.py
+    that use it are: the handles keep their public surface."""
+    if handle.family != "nic":
+        if want_dfeats:
+            raise _lib.IczError("want_dfeats: only the NIC decoder returns a gradient for its features")
+        return (C.byref(gs),), None
+    dfe = torch.zeros_like(handle._live[0]) if want_dfeats else None
+    return (C.byref(gs), ptr(dfe)), dfe
+
+
 class DecoderHandle:
     """Wraps icz_<family>_* for a fixed architecture and row / step capacity.  A subclass declares `family`, `kind` (its member
     kind in icz_ensemble_create), `_Params` (the ctypes struct of parameter pointers) with `_param_keys` (the reference

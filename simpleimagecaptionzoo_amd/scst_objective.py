@@ -16,6 +16,7 @@ import numbers
 import torch
 
 from ._lib import IczError, ScstObjective, check, lib, ptr, stream_ptr
+from .handle import grad_args
 
 KINDS = {"reinforce": 0, "risk": 1}
 MAX_K = 8
@@ -93,18 +94,9 @@ def sample_backward_objective(handle, objective, grads, mask_sum_global=0.0, *, 
     out3 = handle._buf("obj_loss3", (3,), torch.float32)
     msum = handle._buf("obj_msum", (1,), torch.float32)
     ent = handle._buf("obj_ent", (rows, T), torch.float32) if want_entropy else None
-    gs = handle._grad_struct(grads)
-    if handle.family == "nic":
-        dfe = torch.zeros_like(handle._live[0]) if want_dfeats else None
-        check(handle._e.sample_backward_objective(handle._h, C.byref(o), C.byref(gs), ptr(dfe), ptr(out3), ptr(ent), ptr(msum),
-                                                  float(mask_sum_global), stream_ptr()))
-    else:
-        if want_dfeats:
-            raise IczError("want_dfeats: only the NIC decoder returns a gradient for its features")
-        dfe = None
-        check(handle._e.sample_backward_objective(handle._h, C.byref(o), C.byref(gs), ptr(out3), ptr(ent), ptr(msum), float(mask_sum_global),
-                                                  stream_ptr()))
-    handle._objective_live = keep      # the kernels read the reward / scores in stream order
+    ga, dfe = grad_args(handle, handle._grad_struct(grads), want_dfeats)
+    check(handle._e.sample_backward_objective(handle._h, C.byref(o), *ga, ptr(out3), ptr(ent), ptr(msum), float(mask_sum_global), stream_ptr()))
+    handle._objective_live = keep     # the kernels read the reward / scores in stream order
     res = (out3, msum)
     if want_entropy:
         res += (ent,)

@@ -20,6 +20,7 @@ import numbers
 import torch
 
 from ._lib import IczError, SworOpts, check, lib, ptr, stream_ptr
+from .handle import grad_args
 
 ESTIMATORS = {"normalised": 0, "unbiased": 1}
 MIN_N, MAX_N = 3, 8
@@ -115,16 +116,9 @@ def xe_backward_swor(handle, grads, phi, G, scores, batch, estimator="normalised
     nothing and leaves the stored forward usable."""
     o, rows, stats, keep = _opts(batch, phi, G, scores, estimator, n_img_global, handle.device)
     out = torch.zeros(1 + stats.shape[0], dtype=torch.float32, device=handle.device)
-    gs = handle._grad_struct(grads)
-    if handle.family == "nic":
-        dfe = torch.zeros_like(handle._live[0]) if want_dfeats else None
-        check(handle._e.xe_backward_swor(handle._h, C.byref(o), rows, C.byref(gs), ptr(dfe), ptr(out), stream_ptr()))
-    else:
-        if want_dfeats:
-            raise IczError("want_dfeats: only the NIC decoder returns a gradient for its features")
-        dfe = None
-        check(handle._e.xe_backward_swor(handle._h, C.byref(o), rows, C.byref(gs), ptr(out), stream_ptr()))
-    handle._swor_live = keep          # the kernels read phi, G, scores and perm in stream order
+    ga, dfe = grad_args(handle, handle._grad_struct(grads), want_dfeats)
+    check(handle._e.xe_backward_swor(handle._h, C.byref(o), rows, *ga, ptr(out), stream_ptr()))
+    handle._swor_live = keep         # the kernels read phi, G, scores and perm in stream order
     res = ((out[0:1], out[1:]), stats)
     return res + (dfe,) if want_dfeats else res
 
